@@ -22,6 +22,10 @@ process, before anything here touches a GPU).
 `--gpus 2 --layout split2`: BASELINE configs[2], the reference's default placement -- simulator + rollout policy on GPU 0,
 V-learner and P-learner on GPU 1, parameters and transitions shipped over xGMI by copy streams (one process, same metric).
 `--share-gpu` rehearses either layout on ONE card (and says so in `config`; `n_gpus` then stays 1).
+
+A plain run sets up, warms up, times ONE block of exactly --steps steps and prints the result line.  `--full` adds everything
+else the bench measures: further timed blocks (`repeats`), the roofline sections, the free-running rates and the CPU-oracle
+baseline.  `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -75,13 +79,18 @@ def parse():
     ap.add_argument("--override", action="append", default=[], metavar="KEY=VALUE",
                     help="extra cfg override in the entry point's syntax (A/B switches: algo.actor_ahead=False, algo.dpg_fused=False ...); "
                          "recorded in config.overrides")
-    ap.add_argument("--gather-event-probe", action="store_true", help="(with --no-roofline, under rocprofv3 --kernel-trace) time the K-batch gather "
-                    "with HIP events around single eager launches and print it: calibration of roofline_gather's method against the trace")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline block: --repeat blocks (default 5), the roofline / gather / free-running sections and "
+                         "the CPU-oracle baseline.  Off: set-up, warm-up, one timed block, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the learners' parameters and losses, the rollout's transitions and the "
+                         "observation statistics of the last step as DIR/<name>.npy (float32, <= 64 MB in all; rank 0)")
+    ap.add_argument("--gather-event-probe", action="store_true", help="(with --full --no-roofline, under rocprofv3 --kernel-trace) time the K-batch "
+                    "gather with HIP events around single eager launches and print it: calibration of roofline_gather's method against the trace")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle baseline")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the roofline / free-running sections after the timed blocks (rocprofv3 kernel-trace runs: the CSV's "
-                         "call counts then equal steps x launches per step; use with --burn-in-ms 0)")
-    ap.add_argument("--cpu-steps", type=int, default=96, help="schedule steps of the bounded CPU-oracle sample (~15 s)")
+                    help="--full without the roofline / free-running / CPU-baseline sections after the timed blocks")
+    ap.add_argument("--cpu-steps", type=int, default=96, help="schedule steps of the bounded CPU-oracle sample (~15 s; --full)")
     ap.add_argument("--v-only", action="store_true", help="time free-running V-learner steps only")
     ap.add_argument("--p-only", action="store_true", help="time free-running P-learner steps only (profiling)")
     ap.add_argument("--layout", default="dp", choices=["dp", "split2"],
@@ -91,8 +100,8 @@ def parse():
                     help="N>1 data parallel: weak = --num-envs / --replay / --batch are PER RANK (the job grows with N; `value` counts "
                          "batch-sized steps summed over ranks); strong = they are the JOB's sizes and every rank takes 1/N of each "
                          "(BASELINE configs[3] as written: --num-envs 16384 --gpus 8 = 2048 envs per rank)")
-    ap.add_argument("--repeat", type=int, default=5, help="timed blocks of --steps steps; `value` is the FIRST block, "
-                                                          "median/min/max over all blocks are reported beside it")
+    ap.add_argument("--repeat", type=int, default=None, help="timed blocks of --steps steps (default 1, with --full 5); `value` is "
+                                                             "the FIRST block, median/min/max over all blocks are reported beside it")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); 'gloo' + --share-gpu rehearses the DP path on one GPU")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
     return ap.parse_args()
@@ -737,6 +746,36 @@ def cpu_baseline(args, O, A, hidden):
                       f"batch {B}, hidden {list(hidden)}, replay {cap} rows, torch {torch.__version__} CPU, {dt:.1f} s"}
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, sched):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the live critic, target critic and policy
+    arenas, both learners' loss rings, the newest rollout's n-step transitions (the next hand-off) and the running observation
+    statistics -- as float32 DIR/<name>.npy.  Inputs are seeded, so two builds run with the same arguments can be compared file
+    for file.  Past DUMP_BYTES in all, every array larger than its share is cut to a fixed seeded sample of its rows (axis 0)."""
+    import numpy as np
+    v, p, rms = sched.v, sched.p, sched.actor.obs_rms
+    arrays = {"critic": v.critic.arena.data, "critic_target": v.critic_target.arena.data, "actor": p.actor.arena.data,
+              "v_loss_ring": v.loss_ring, "p_loss_ring": p.loss_ring}
+    if rms is not None:
+        arrays.update(obs_rms_mean=rms.mean, obs_rms_var=rms.var)
+    if sched.pending is not None:
+        arrays.update(zip(("transitions_obs", "transitions_action", "transitions_reward", "transitions_next_obs", "transitions_done"),
+                          sched.pending[1]))
+    arrays = {k: t.detach().float().cpu().numpy() for k, t in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                rows = max(1, a.shape[0] * share // a.nbytes)
+                keep = np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))
+                arrays[k] = np.ascontiguousarray(a[keep])
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` from a bare shell: start the N ranks as a torchrun CHILD process and leave with its exit
     code.  Runs before this process has made any HIP call (device_count() does not initialise the GPU on this image), so
@@ -853,7 +892,11 @@ def main():
     note("warm-up done")
     dt = timed_block()
     note(f"timed {args.steps} steps in {dt:.3f} s")
-    blocks = [dt] + [timed_block() for _ in range(max(args.repeat, 1) - 1)]
+    repeat = args.repeat if args.repeat is not None else (5 if args.full else 1)
+    blocks = [dt] + [timed_block() for _ in range(max(repeat, 1) - 1)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sched)
+        note(f"outputs written to {args.dump_outputs}")
 
     hidden = [int(x) for x in args.hidden.split(",")]
     O, A = env.obs_dim, env.act_dim
@@ -899,8 +942,8 @@ def main():
         "env_steps_per_s": (args.steps / dt) / int(cfg.algo.critic_sample_ratio) * args.shard.total_envs if mode == "schedule" else 0.0,
         "gflop_per_v_step": f_v / 1e9, "gflop_per_p_step": f_p / 1e9,
     }
-    if rank == 0 and args.no_roofline:
-        if args.gather_event_probe:
+    if rank == 0 and (not args.full or args.no_roofline):
+        if args.full and args.gather_event_probe:
             K = int(v._workspace(args.batch)["K"])
             t_l, t_n = gather_isolated_ms(v, K, in_step="events")
             print(f"[gather-event-probe] events around one eager launch inside a V step: {t_l:.2f} us; around a one-block no-op: {t_n:.2f} us", file=sys.stderr)

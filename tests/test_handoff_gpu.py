@@ -204,7 +204,7 @@ def _run_bench(*flags, timeout=600):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--num-envs", "256", "--batch", "1024", "--replay", "20000",
-                        "--steps", "16", "--warmup", "8", "--repeat", "2", "--no-cpu-baseline", *flags],
+                        "--steps", "16", "--warmup", "8", "--repeat", "2", "--full", "--no-cpu-baseline", *flags],
                        env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

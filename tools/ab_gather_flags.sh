@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 for F in 3 7 11 15; do
-  PQL_GATHER_FLAGS=$F python bench.py --no-cpu-baseline --repeat 1 > $OUT/bench_f$F.json 2> $OUT/bench_f$F.err || { tail -5 $OUT/bench_f$F.err; exit 1; }
+  PQL_GATHER_FLAGS=$F python bench.py --full --no-cpu-baseline --repeat 1 > $OUT/bench_f$F.json 2> $OUT/bench_f$F.err || { tail -5 $OUT/bench_f$F.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_f$F.json"))

@@ -19,7 +19,7 @@ for n in cfg5x8 cfg5x8@40M cfg5x8@100M cfg5x8@150M cfg5x8@200M p5x4 p5x4@200M; d
 done
 for rows in 5000000 50000000 140000000; do
   echo "[stress] bench.py replay $rows"
-  timeout -k 10 400 python3 bench.py --no-cpu-baseline --task Humanoid --batch 32768 --nstep 5 --replay $rows --steps 200 > $OUT/bench_cfg5_replay$rows.json 2> $OUT/bench_cfg5_replay$rows.err
+  timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --task Humanoid --batch 32768 --nstep 5 --replay $rows --steps 200 > $OUT/bench_cfg5_replay$rows.json 2> $OUT/bench_cfg5_replay$rows.err
   python3 - $OUT/bench_cfg5_replay$rows.json <<'P' | tee -a $LOG
 import json, sys
 d = json.load(open(sys.argv[1]))
