@@ -508,6 +508,57 @@ int pqlk_rms_normalize(const float* x, int64_t rows, int32_t cols, const float* 
 int pqlk_action_noise(const float* act, const float* draw, const float* std_rows, float std_scalar, int64_t rows, int32_t cols,
                       float lo, float hi, float* out, pqlk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * On-policy PPO baseline (reference pql/algo/ppo.py:79-183, pql/models/mlp.py:43-75).  All reductions in a fixed order.
+ *
+ * GAE / plain discounted returns over a (T, N) trajectory, one column per env, the reference's operation order:
+ *   use_gae: delta = r[t] + (gamma * nv) * nnt2 - v[t];  lastgaelam = delta + ((float)(gamma * lambda) * nnt) * lastgaelam;
+ *            adv[t] = lastgaelam, ret[t] = adv[t] + v[t];  nnt = 1 - (t == T-1 ? next_done : done[t+1]), nv likewise from
+ *            next_val / val[t+1];  nnt2 = logical_xor(nnt, timeout[t]) when timeout (T, N) != NULL, else nnt.
+ *   else:    ret[t] = r[t] + (gamma * nnt) * (t == T-1 ? next_val : ret[t+1]);  adv = ret - v  (time-outs ignored).
+ * rew / done / val / timeout / adv / ret are (T, N) contiguous, next_val / next_done (N); done and timeout hold 0 / 1. */
+int pqlk_gae(const float* rew, const float* done, const float* val, const float* next_val, const float* next_done,
+             const float* timeout, int32_t T, int64_t n, double gamma, double lambda, int32_t use_gae, float* adv, float* ret,
+             pqlk_stream_t stream);
+
+/* Diagonal-Gaussian head of DiagGaussianMLPPolicy: y (B, ld_y) = the MLP's mean block, logstd (A), eps (B, A) the standard-
+ * normal draw (NULL = the mean itself).  act[r * ld_act + j] = mean + exp(logstd_j) * eps; logp (B) = sum over j in index order
+ * of -((a - mu)^2) / (2 scale^2) - log(scale) - log(sqrt(2 pi)); ent (B) = sum_j 0.5 + 0.5 log(2 pi) + log(scale).  logp / ent
+ * may be NULL.  A <= 64. */
+int pqlk_ppo_gauss_head(const float* y, int64_t ld_y, const float* logstd, const float* eps, int64_t b, int32_t act_dim,
+                        float* act, int64_t ld_act, float* logp, float* ent, pqlk_stream_t stream);
+
+/* Minibatch gather from the flat (rows = T*N) trajectory: for r < mb and k = idx[r] (clamped into [0, rows)):
+ *   x[r] (ld ldx) = (obs[k] - mean) / sqrt(var + eps) (no clamp; raw when mean == var == NULL), pad columns [O, ldx) zero;
+ *   act_out[r] (A, contiguous) = act[k];  logp / adv / ret / val _out[r] = the trajectory's value at k;
+ *   adv_part (3 * pqlk_ppo_gather_parts(mb)) = per-block { rows, sum, sum of squared deviations from the block mean } of the
+ *   gathered advantages, read by pqlk_ppo_policy_loss for the minibatch's mean and unbiased std.  mb may be < the batch size. */
+int32_t pqlk_ppo_gather_parts(int64_t mb);
+int pqlk_ppo_gather(const int64_t* idx, int64_t mb, int64_t rows, const float* obs, int32_t obs_dim, const float* mean,
+                    const float* var, float eps, float* x, int64_t ldx, const float* act, int32_t act_dim, float* act_out,
+                    const float* logp, const float* adv, const float* ret, const float* val, float* logp_out, float* adv_out,
+                    float* ret_out, float* val_out, float* adv_part, pqlk_stream_t stream);
+
+/* Clipped-surrogate policy loss and its gradient.  With the minibatch's advantage mean m and unbiased std s (from adv_part),
+ *   logp = as pqlk_ppo_gauss_head at act (B, A contiguous), ratio = exp(logp - old_logp), na = (adv - m) / (s + 1e-8),
+ *   loss = mean(max(-na ratio, -na clamp(ratio, 1 - clip, 1 + clip))) - lambda_ent * mean(entropy)
+ * into loss_ring[*slot_dev % ring_len] (loss_ring may be NULL); dy (B, ld_y) columns [0, A) = d loss / d mean (pad columns
+ * untouched), dlogstd (A) = d loss / d logstd; logp_out (B, may be NULL).  autograd's tie rules: max splits the gradient 50/50 on
+ * equal arguments, clamp passes it on the closed interval.  scratch >= pqlk_ppo_scratch_floats(b, A) floats.  Two launches.
+ * b == 1 (a one-row last minibatch) is accepted: the unbiased std is NaN and so are the loss and gradient, as in the reference. */
+int64_t pqlk_ppo_scratch_floats(int64_t b, int32_t act_dim);
+int pqlk_ppo_policy_loss(const float* y, int64_t ld_y, const float* logstd, const float* act, const float* old_logp,
+                         const float* adv, const float* adv_part, int32_t n_parts, int64_t b, int32_t act_dim, float clip,
+                         float lambda_ent, float* dy, float* dlogstd, float* logp_out, float* scratch, int64_t scratch_floats,
+                         float* loss_ring, const int32_t* slot_dev, int32_t ring_len, pqlk_stream_t stream);
+
+/* Value loss: clip_on ? 0.5 mean(max((v - R)^2, (V + clamp(v - V, -clip, clip) - R)^2)) : 0.5 mean((v - R)^2), with v = column 0
+ * of the critic's output rows (stride ld_v), R = ret, V = old_v.  dy[r * ld_dy] = d loss / d v (same tie rules); the loss into
+ * loss_ring[*slot_dev % ring_len] when loss_ring != NULL.  scratch >= pqlk_ppo_scratch_floats(b, 1) floats. */
+int pqlk_ppo_value_loss(const float* v, int64_t ld_v, const float* ret, const float* old_v, int64_t b, int32_t clip_on, float clip,
+                        float* dy, int64_t ld_dy, float* scratch, int64_t scratch_floats, float* loss_ring,
+                        const int32_t* slot_dev, int32_t ring_len, pqlk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,13 @@ PROTOTYPES = {
     "pqlk_rms_merge": (C.c_int, [_P, _P, _P, _P, _F, _F, _F, _I32, _P, _P, _P]),
     "pqlk_rms_normalize": (C.c_int, [_P, _I64, _I32, _P, _P, _F, _P, _I64, _P]),
     "pqlk_action_noise": (C.c_int, [_P, _P, _P, _F, _I64, _I32, _F, _F, _P, _P]),
+    "pqlk_gae": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I64, C.c_double, C.c_double, _I32, _P, _P, _P]),
+    "pqlk_ppo_gauss_head": (C.c_int, [_P, _I64, _P, _P, _I64, _I32, _P, _I64, _P, _P, _P]),
+    "pqlk_ppo_gather_parts": (_I32, [_I64]),
+    "pqlk_ppo_gather": (C.c_int, [_P, _I64, _I64, _P, _I32, _P, _P, _F, _P, _I64, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pqlk_ppo_scratch_floats": (_I64, [_I64, _I32]),
+    "pqlk_ppo_policy_loss": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, _I64, _I32, _F, _F, _P, _P, _P, _P, _I64, _P, _P, _I32, _P]),
+    "pqlk_ppo_value_loss": (C.c_int, [_P, _I64, _P, _P, _I64, _I32, _F, _P, _I64, _P, _I64, _P, _P, _I32, _P]),
 }
 
 

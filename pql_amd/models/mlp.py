@@ -1,7 +1,8 @@
 """MLP actor / critic family on fused fp32-MFMA kernels.
 
 Drop-in for the hot classes of the reference's `pql/models/mlp.py`: `MLPNet` (:27-40),
-`TanhMLPPolicy` (:177-179), `DoubleQ` (:186-203), `DistributionalDoubleQ` (:244-267) -- same
+`TanhMLPPolicy` (:177-179), `DoubleQ` (:186-203), `DistributionalDoubleQ` (:244-267), `DiagGaussianMLPPolicy` (:43-75),
+`MLPCritic` (:270-278) -- same
 constructor arguments, same methods (`forward`, `get_q1_q2`, `get_q_min`, `get_q1`), same
 `state_dict()` key names (`net.{0,2,4,6}.{weight,bias}`, `net_q{1,2}.net.*`) so reference checkpoints
 load unchanged.  Selected by class name through `pql_amd.models.model_name_to_path`, exactly like the
@@ -157,6 +158,8 @@ class FusedMlpFn(torch.autograd.Function):
         splits = default_splits(B) if need_w else 1
         ws = torch.empty(lay.bwd_ws_floats(B, splits), dtype=torch.float32, device=dev)
         grads = torch.empty_like(arena) if need_w else None
+        if need_w and arena.numel() > lay.total:   # parameters kept after the MLP arena get their gradient elsewhere
+            grads[lay.total:].zero_()
         dx = torch.empty((B, lay.ld_in), dtype=torch.float32, device=dev) if need_x else None
         if not (need_w or need_x):
             return None, None, None, None
@@ -177,8 +180,12 @@ class FusedMLP(nn.Module):
         hidden = list(HIDDEN_DEFAULT if hidden_layers is None else hidden_layers)
         self.layout = ArenaLayout([_first(in_dim), *hidden, int(out_dim)], n_nets)
         self.out_act = out_act
-        self.arena = nn.Parameter(torch.zeros(self.layout.total, dtype=torch.float32))
+        self.arena = nn.Parameter(torch.zeros(self.layout.total + self._extra_floats(), dtype=torch.float32))
         self.reset_parameters()
+
+    def _extra_floats(self):
+        """Floats a subclass keeps after the MLP arena in the same flat buffer (DiagGaussianMLPPolicy: its logstd block)."""
+        return 0
 
     # ---- init = nn.Linear default (kaiming_uniform(a=sqrt(5)) -> U(+-1/sqrt(fan_in)) for W and b) -------
     @torch.no_grad()
@@ -342,6 +349,118 @@ class TanhDiagGaussianMLPPolicy(FusedMLP):
             eps = torch.empty((state.shape[0], self.act_dim), dtype=torch.float32, device=state.device).normal_()
         act, logp = self._head(state, eps.contiguous(), True)
         return act, None, logp
+
+
+class DiagGaussianMLPPolicy(FusedMLP):
+    """mlp.py:43-75: MLP -> mean, a state-independent `logstd` (A), Independent(Normal(mean, exp(logstd)), 1).
+
+    One flat parameter buffer: the MLP arena, then `logstd` padded to a 128-byte block, so one clip + AdamW launch covers every
+    actor parameter (the reference's clip_grad_norm_ and AdamW weight decay include `logstd`).  The module methods keep the
+    reference's signatures and are autograd-capable (fused MLP + torch.distributions over its output); the PPO learner drives
+    the same buffer through the HIP heads of pql_amd/csrc/ppo.hip (`sample`: the rollout's action / log-prob launch)."""
+
+    def __init__(self, state_dim, act_dim, hidden_layers=None, init_log_std=0.):
+        self.act_dim, self.init_log_std = int(act_dim), float(init_log_std)
+        super().__init__(state_dim, self.act_dim, hidden_layers, n_nets=1, out_act=L.ACT_NONE)
+        self.init_kwargs = dict(state_dim=_first(state_dim), act_dim=self.act_dim, hidden_layers=self.layout.dims[1:-1],
+                                init_log_std=self.init_log_std)
+
+    def _extra_floats(self):
+        return L.ld(self.act_dim)
+
+    @torch.no_grad()
+    def reset_parameters(self):
+        super().reset_parameters()
+        self.arena.data[self.layout.total: self.layout.total + self.act_dim].fill_(self.init_log_std)
+
+    @property
+    def logstd(self):
+        """(A,) view of the flat buffer (differentiable: its gradient lands in `arena.grad`)."""
+        return self.arena[self.layout.total: self.layout.total + self.act_dim]
+
+    def logstd_block(self, flat):
+        """The padded logstd block of a flat tensor laid out like `arena` (gradients, optimiser moments)."""
+        return flat[self.layout.total:]
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False, **kw):
+        out = super().state_dict(destination=destination, prefix=prefix)
+        with self.leased():
+            out[f"{prefix}logstd"] = self.logstd.detach().clone()
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        res = super().load_state_dict(state_dict, strict=False)
+        missing = list(res.missing_keys)
+        if "logstd" in state_dict:
+            src = torch.as_tensor(state_dict["logstd"])
+            if tuple(src.shape) != (self.act_dim,):
+                raise RuntimeError(f"size mismatch for logstd: {tuple(src.shape)} vs {(self.act_dim,)}")
+            self.arena.data[self.layout.total: self.layout.total + self.act_dim].copy_(src.to(self.arena.device, torch.float32))
+        else:
+            missing.append("logstd")
+        if strict and missing:
+            raise RuntimeError(f"Missing key(s) in state_dict: {missing}")
+        return nn.modules.module._IncompatibleKeys(missing, [])
+
+    def named_views(self):
+        yield from super().named_views()
+        yield "logstd", self.logstd.detach()
+
+    def num_params(self):
+        return self.layout.count_params() + self.act_dim
+
+    # ---- reference API (autograd-capable) -----------------------------------------------------------
+    def forward(self, x, sample=True):
+        return self.get_actions(x, sample=sample)[0]
+
+    def get_actions(self, x, sample=True):
+        from torch.distributions import Independent, Normal
+        mean = self._run(x)[0]
+        std = torch.exp(self.logstd.expand_as(mean))
+        action_dist = Independent(Normal(loc=mean, scale=std), 1)
+        actions = action_dist.rsample() if sample else mean
+        return actions, action_dist
+
+    def get_actions_logprob_entropy(self, state, sample=True):
+        actions, action_dist = self.get_actions(state, sample=sample)
+        return actions, action_dist, action_dist.log_prob(actions), action_dist.entropy()
+
+    def logprob_entropy(self, state, actions):
+        _, action_dist = self.get_actions(state)   # as the reference: an rsample is drawn and discarded
+        return actions, action_dist, action_dist.log_prob(actions), action_dist.entropy()
+
+    # ---- HIP path -----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(self, state, eps=None, want_entropy=False):
+        """-> (actions (B, A), log_prob (B,), entropy (B,) or None): fused MLP + one `pqlk_ppo_gauss_head` launch.
+        eps (B, A): the standard-normal draw (None: the mean, as get_actions(sample=False))."""
+        L.require_gpu(self.arena, "parameter arena")
+        x_pad = pad_cols(state.to(torch.float32), self.layout.ld_in)
+        B, dev, A = x_pad.shape[0], x_pad.device, self.act_dim
+        with self.leased():
+            y = output_view(self.layout, mlp_forward_raw(self.layout, self.arena.data, x_pad, L.ACT_NONE), B)[0]
+            act = torch.empty((B, A), dtype=torch.float32, device=dev)
+            logp = torch.empty(B, dtype=torch.float32, device=dev)
+            ent = torch.empty(B, dtype=torch.float32, device=dev) if want_entropy else None
+            e = eps.to(dev, torch.float32).contiguous() if eps is not None else None
+            with torch.cuda.device(dev):
+                L.check(L.lib.pqlk_ppo_gauss_head(L.ptr(y), y.stride(0), L.ptr(self.arena.data[self.layout.total:]), L.ptr(e), B, A,
+                                                  L.ptr(act), A, L.ptr(logp), L.ptr(ent), L.stream(dev)))
+        return act, logp, ent
+
+
+class MLPCritic(FusedMLP):
+    """mlp.py:270-278: one ELU MLP to a single value (state_dict prefix `critic.net.`)."""
+
+    key_prefixes = ("critic.net.",)
+
+    def __init__(self, state_dim, action_dim, hidden_layers=None):
+        super().__init__(state_dim, 1, hidden_layers, n_nets=1, out_act=L.ACT_NONE)
+        self.init_kwargs = dict(state_dim=_first(state_dim), action_dim=int(action_dim), hidden_layers=self.layout.dims[1:-1])
+
+    def forward(self, state):
+        return self._run(state)[0]
 
 
 class DoubleQ(FusedMLP):

@@ -127,9 +127,38 @@ def check_device(cfg):
         raise ValueError(f"Invalid GPU id(s) {bad}: only {cfg.available_gpus} device(s) visible")
 
 
+# PPO per-task presets of IsaacGymEnvs (isaac_param=True), reference common.py:245-275
+PPO_TASK_PRESETS = dict(
+    Ant=dict(num_envs=4096, batch_size=32768, horizon_len=16, update_times=4),
+    Humanoid=dict(num_envs=4096, batch_size=32768, horizon_len=32, update_times=5, value_norm=True),
+    Anymal=dict(num_envs=4096, batch_size=32768, horizon_len=16, update_times=5),
+    AllegroHand=dict(num_envs=16384, batch_size=32768, horizon_len=8, update_times=5, value_norm=True),
+    FrankaCubeStack=dict(num_envs=8192, batch_size=16384, horizon_len=32, update_times=5),
+)
+
+
+def preprocess_ppo_cfg(cfg):
+    """Per-task PPO hyper-parameters.  The reference's ShadowHand branch compares `cfg.task` (the node, not its name) with
+    'ShadowHand' and so never matches: ShadowHand keeps the defaults here too."""
+    task = cfg.task
+    name = task.name if task is not None else None
+    key = name if name in PPO_TASK_PRESETS else ("AllegroHand" if task == "ShadowHand" else None)
+    if key is None:
+        print(f"Cannot find config for PPO on task:{name}. Using default config.")
+        return
+    for k, v in PPO_TASK_PRESETS[key].items():
+        if k == "num_envs":
+            cfg.num_envs = v
+        else:
+            setattr(cfg.algo, k, v)
+
+
 def preprocess_cfg(cfg):
     cfg.available_gpus = torch.cuda.device_count()
-    if cfg.algo.name == "PQL":
+    if cfg.algo.name == "PPO":
+        if cfg.get("isaac_param"):
+            preprocess_ppo_cfg(cfg)
+    elif cfg.algo.name == "PQL":
         check_device(cfg)
     task_name = cfg.task.name if getattr(cfg, "task", None) is not None else None
     if task_name in TASK_REWARD_SCALE and cfg.algo.reward_scale == 1:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Single-process off-policy baseline loop (DDPG, SAC, CrossQ: `algo=ddpg_algo` / `sac_algo` / `crossq_algo`) -- same shape as the reference's scripts/train_baselines.py:39-72:
-warm-up rollout -> replay, then per iteration: rollout, insert, `agent.update_net(memory)`.
+"""Single-process baseline loop -- same shape as the reference's scripts/train_baselines.py:39-72.
+Off-policy (DDPG, SAC, CrossQ: `algo=ddpg_algo` / `sac_algo` / `crossq_algo`): warm-up rollout -> replay, then per iteration:
+rollout, insert, `agent.update_net(memory)`.  On-policy (PPO: `algo=ppo_algo`): per iteration rollout, `agent.update_net(trajectory)`.
     python scripts/train_baselines.py algo=ddpg_algo task.name=Toy num_envs=64 algo.batch_size=256 algo.memory_size=100000 max_step=20000
+    python scripts/train_baselines.py algo=ppo_algo task.name=Toy num_envs=64 max_step=20000
 """
 import os
 import sys
@@ -31,16 +33,21 @@ def main(cfg):
     logger = MetricLogger(cfg.logging.get("jsonl") if cfg.get("logging") else None)
     start, global_steps = time.time(), 0
     agent.reset_agent()
-    memory = ReplayBuffer(capacity=int(cfg.algo.memory_size), obs_dim=agent.obs_dim, action_dim=agent.action_dim, device=cfg.device)
-    trajectory, steps = agent.explore_env(env, cfg.algo.warm_up, random=True)
-    memory.add_to_buffer(trajectory)
-    global_steps += steps
+    is_off_policy = cfg.algo.name != "PPO"
+    if is_off_policy:
+        memory = ReplayBuffer(capacity=int(cfg.algo.memory_size), obs_dim=agent.obs_dim, action_dim=agent.action_dim, device=cfg.device)
+        trajectory, steps = agent.explore_env(env, cfg.algo.warm_up, random=True)
+        memory.add_to_buffer(trajectory)
+        global_steps += steps
     log_info = {}
     for iter_t in count():
         trajectory, steps = agent.explore_env(env, cfg.algo.horizon_len, random=False)
         global_steps += steps
-        memory.add_to_buffer(trajectory)
-        log_info = agent.update_net(memory)
+        if is_off_policy:
+            memory.add_to_buffer(trajectory)
+            log_info = agent.update_net(memory)
+        else:   # on-policy (PPO): no replay, no warm-up; the update consumes this rollout's trajectory
+            log_info = agent.update_net(trajectory)
         if iter_t % cfg.algo.log_freq == 0:
             log_info["global_steps"] = global_steps
             logger.log(log_info, global_steps)

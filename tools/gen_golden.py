@@ -641,6 +641,124 @@ def gen_ckpt(R, out):
             out[f"{role}_g_{k}"] = dd.summarize(p.grad.numpy())
 
 
+# --------------------------------------------------------------------------- PPO (on-policy baseline)
+def _ppo_agent(R, O, A, algo, actor_seed, critic_seed, logstd, num_envs=1):
+    """The reference's AgentPPO built with __new__ (its __post_init__ needs an env and Hydra): nets, AdamW, trackers, obs_rms."""
+    from pql.algo.ppo import AgentPPO
+    from pql.models.mlp import DiagGaussianMLPPolicy, MLPCritic
+    ag = AgentPPO.__new__(AgentPPO)
+    ag.cfg = NS(info_track_keys=None, device="cpu", num_envs=num_envs, algo=algo)
+    ag.obs_dim, ag.action_dim, ag.device = (O,), A, torch.device("cpu")
+    ag.actor = DiagGaussianMLPPolicy((O,), A)
+    st = {k: T(v) for k, v in dd.mlp_state(O, A, actor_seed).items()}
+    st["logstd"] = T(logstd)
+    ag.actor.load_state_dict(st)
+    ag.critic = MLPCritic((O,), A)
+    ag.critic.load_state_dict({k: T(v) for k, v in dd.mlp_state(O, 1, critic_seed, prefix="critic.net.").items()})
+    ag.actor_optimizer = torch.optim.AdamW(ag.actor.parameters(), algo.actor_lr)
+    ag.critic_optimizer = torch.optim.AdamW(ag.critic.parameters(), algo.critic_lr)
+    ag.return_tracker, ag.step_tracker, ag.success_tracker = R.Tracker(4), R.Tracker(4), R.Tracker(4)
+    ag.obs_rms = R.RunningMeanStd(shape=(O,), device="cpu")
+    ag.obs_rms.mean, ag.obs_rms.var = T(dd.uniform((O,), 901, -0.5, 0.5)), T(dd.uniform((O,), 902, 0.5, 2.0))
+    if algo.value_norm:
+        ag.value_rms = R.RunningMeanStd(shape=(1), device="cpu")
+    return ag
+
+
+def _ppo_algo(**kw):
+    base = dict(actor_lr=5e-4, critic_lr=5e-4, max_grad_norm=0.5, obs_norm=True, value_norm=False, gamma=0.99, lambda_gae_adv=0.95,
+                use_gae=True, value_clip=True, lambda_entropy=0.0, ratio_clip=0.2, batch_size=24, update_times=2)
+    base.update(kw)
+    return NS(**base)
+
+
+def gen_ppo(R, out):
+    from pql.models.mlp import DiagGaussianMLPPolicy
+    # known-answer vectors of DiagGaussianMLPPolicy (mlp.py:43-75): rsample, log-prob, entropy, parameter gradients of a scalar of both
+    for tag, O, A, B in (("kat_toy", 8, 2, 16), ("kat_allegro", 88, 16, 16)):
+        pol = DiagGaussianMLPPolicy((O,), A)
+        st = {k: T(v) for k, v in dd.mlp_state(O, A, 71).items()}
+        st["logstd"] = T(dd.uniform((A,), 72, -1.0, 0.5))
+        pol.load_state_dict(st)
+        x = T(dd.uniform((B, O), 73, -2, 2))
+        w = T(dd.uniform((B,), 74, -1, 1))
+        with _EpsCapture(7400) as cap:
+            a, _, logp, ent = pol.get_actions_logprob_entropy(x)
+        loss = (logp * w).mean() + 0.3 * ent.mean() - (a * a).mean()
+        grads = torch.autograd.grad(loss, list(pol.parameters()))
+        out[f"{tag}_meta"] = np.array([O, A, B]); out[f"{tag}_eps"] = cap.draws[0]
+        out[f"{tag}_act"] = a.detach().numpy(); out[f"{tag}_logp"] = logp.detach().numpy(); out[f"{tag}_ent"] = ent.detach().numpy()
+        out[f"{tag}_loss"] = np.array(float(loss.detach()))
+        for (k, _), g in zip(pol.named_parameters(), grads):
+            out[f"{tag}_g_{k}"] = dd.summarize(g.numpy())
+        out[f"{tag}_g_logstd_exact"] = dict(zip([k for k, _ in pol.named_parameters()], grads))["logstd"].numpy().copy()
+
+    # compute_adv traces (ppo.py:79-139) at T = 5, N = 37 with dones and time-outs, use_gae x value_norm
+    O, A, Tn, N = 8, 2, 5, 37
+    for gae in (True, False):
+        for vn in (False, True):
+            tag = f"adv_g{int(gae)}_v{int(vn)}"
+            ag = _ppo_agent(R, O, A, _ppo_algo(use_gae=gae, value_norm=vn), 81, 82, dd.uniform((A,), 83, -0.5, 0.0), num_envs=N)
+            obs = T(dd.uniform((Tn, N, O), 84, -3, 3))
+            rew = T(dd.uniform((Tn, N), 85, -2, 2)); dones = T(dd.bernoulli((Tn, N), 86, 0.2))
+            vals = T(dd.uniform((Tn, N), 87, -3, 3)); nobs = T(dd.uniform((N, O), 88, -3, 3))
+            ndone = T(dd.bernoulli((N,), 89, 0.2)); tmo = T(dd.bernoulli((Tn, N), 90, 0.15)).bool()
+            used = {}
+            if vn:   # the next value GAE reads is value_rms.unnormalize(critic(next obs)) after the update
+                real_un = ag.value_rms.unnormalize
+                ag.value_rms.unnormalize = lambda x: used.setdefault("nv", real_un(x))
+            with torch.no_grad():
+                nv = ag.critic(ag.obs_rms.normalize(nobs))
+                b = ag.compute_adv((obs, torch.zeros(Tn, N, A), torch.zeros(Tn, N), rew, dones, vals, nobs, ndone), gae=gae, timeout=tmo)
+            out[f"{tag}_next_value_raw"] = nv.numpy().reshape(-1).copy()
+            out[f"{tag}_gae_next_value"] = used.get("nv", nv).numpy().reshape(-1).copy()
+            for k, v in zip(("obs", "act", "logp", "adv", "ret", "val"), b):
+                if k in ("adv", "ret", "val"):
+                    out[f"{tag}_{k}"] = v.numpy().copy()
+            if vn:
+                out[f"{tag}_vrms"] = np.array([float(ag.value_rms.mean.reshape(-1)[0]), float(ag.value_rms.var.reshape(-1)[0]), ag.value_rms.count])
+
+    # update_net traces (ppo.py:141-190): 64 rows, batch 24 (short last minibatch of 16), 2 epochs
+    rows = 64
+    for tag, vc, lam in (("upd_c1_e0", True, 0.0), ("upd_c0_e1", False, 0.01)):
+        ag = _ppo_agent(R, O, A, _ppo_algo(value_clip=vc, lambda_entropy=lam), 91, 92, dd.uniform((A,), 93, -0.7, 0.2))
+        b_obs = T(dd.uniform((rows, O), 94, -3, 3)); b_act = T(dd.uniform((rows, A), 95, -2, 2))
+        with torch.no_grad():
+            _, dist = ag.actor.get_actions(ag.obs_rms.normalize(b_obs), sample=False)
+            b_logp = dist.log_prob(b_act) + T(dd.uniform((rows,), 96, -0.3, 0.3))
+        b_adv = T(dd.uniform((rows,), 97, -2, 3)); b_ret = T(dd.uniform((rows,), 98, -2, 2)); b_val = T(dd.uniform((rows,), 99, -2, 2))
+        losses, perms, n_mb = [], [], [0]
+        real_update, real_shuffle = ag.optimizer_update, np.random.shuffle
+
+        def rec_update(opt, objective, retain_graph=False, _tag=tag):
+            losses.append(float(objective.detach()))
+            r = real_update(opt, objective, retain_graph)
+            if opt is ag.critic_optimizer:   # after both steps of a minibatch
+                for k, p in list(ag.actor.named_parameters()) + list(ag.critic.named_parameters()):
+                    out[f"{_tag}_m{n_mb[0]}_{k}"] = dd.summarize(p.detach().numpy())
+                n_mb[0] += 1
+            return r
+
+        def rec_shuffle(a):
+            real_shuffle(a)
+            perms.append(np.array(a, dtype=np.int64))
+
+        ag.optimizer_update, np.random.shuffle = rec_update, rec_shuffle
+        np.random.seed(1234)
+        try:
+            with _EpsCapture(9400):   # logprob_entropy's discarded rsample
+                ag.update_net((b_obs, b_act, b_logp, b_adv, b_ret, b_val))
+        finally:
+            np.random.shuffle = real_shuffle
+        out[f"{tag}_data"] = np.concatenate([b_obs.numpy(), b_act.numpy(), b_logp.numpy()[:, None], b_adv.numpy()[:, None],
+                                             b_ret.numpy()[:, None], b_val.numpy()[:, None]], axis=1)
+        out[f"{tag}_losses"] = np.array(losses, np.float64).reshape(-1, 2)   # (minibatch, [actor, critic])
+        out[f"{tag}_perms"] = np.stack(perms)
+        out[f"{tag}_final_logstd"] = ag.actor.logstd.detach().numpy().copy()
+        out[f"{tag}_final_actor_last_w"] = ag.actor.state_dict()["net.6.weight"].numpy().copy()
+        out[f"{tag}_final_critic_last_w"] = ag.critic.state_dict()["critic.net.6.weight"].numpy().copy()
+
+
 def main():
     torch.set_num_threads(1)
     torch.manual_seed(0)
@@ -648,7 +766,8 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     only = set(sys.argv[1:])
     for name, fn in (("replay", gen_ring), ("nstep", gen_nstep), ("models", gen_models), ("math", gen_math),
-                     ("learners", gen_learners), ("sac", gen_sac), ("crossq", gen_crossq), ("ddpg", gen_ddpg), ("ckpt", gen_ckpt)):
+                     ("learners", gen_learners), ("sac", gen_sac), ("crossq", gen_crossq), ("ddpg", gen_ddpg), ("ckpt", gen_ckpt),
+                     ("ppo", gen_ppo)):
         if only and name not in only:
             continue
         out = {}
