@@ -48,6 +48,16 @@ class AgentCrossQ(PQLActor):
         self.aloss = torch.zeros(LOSS_RING, device=self.device)
         self._ws = None
 
+    def _state_tensors(self):
+        out = super()._state_tensors()   # (the policy itself is the base class's "actor")
+        out.update(critic=self.critic.arena.data, critic_stats=self.critic.stats,
+                   critic_batches=self.critic.num_batches_tracked, closs=self.closs, aloss=self.aloss)   # stats: BatchNorm running moments
+        if self.actor_target is not self.actor:
+            out["actor_target"] = self.actor_target.arena.data
+        for name, opt in (("aopt", self.aopt), ("copt", self.copt)):
+            out.update({f"{name}.m": opt.m, f"{name}.v": opt.v, f"{name}.step": opt.step})
+        return out
+
     def explore_env(self, env, timesteps, random=False):
         act_data, cri_data, steps = super().explore_env(env, timesteps, random)
         del act_data

@@ -44,6 +44,15 @@ class AgentDDPG(PQLActor):
         self.aloss = torch.zeros(LOSS_RING, device=self.device)
         self._ws = None
 
+    def _state_tensors(self):
+        out = super()._state_tensors()   # (the policy itself is the base class's "actor")
+        out.update(critic=self.critic.arena.data, critic_target=self.critic_target.arena.data, closs=self.closs, aloss=self.aloss)
+        if self.actor_target is not self.actor:
+            out["actor_target"] = self.actor_target.arena.data
+        for name, opt in (("aopt", self.aopt), ("copt", self.copt)):
+            out.update({f"{name}.m": opt.m, f"{name}.v": opt.v, f"{name}.step": opt.step})
+        return out
+
     def explore_env(self, env, timesteps, random=False):
         n0 = self.n_step_buffer.nstep_count
         act_data, cri_data, steps = super().explore_env(env, timesteps, random)

@@ -41,6 +41,13 @@ class DeviceTracker:
     def mean(self):
         return float(self.ring[: self.max_len].mean())
 
+    def training_state(self):
+        return {"ring": self.ring.detach().cpu(), "ptr": self.ptr.detach().cpu()}
+
+    def load_training_state(self, st):
+        self.ring.copy_(st["ring"])
+        self.ptr.copy_(st["ptr"])
+
 
 class PQLActor:
     def __init__(self, env, cfg, env_offset=0, total_envs=None):
@@ -72,6 +79,10 @@ class PQLActor:
         if self.sim_device.type == "cuda":
             self.gen = torch.Generator(device=self.sim_device)
             self.gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
+        artifact = getattr(cfg, "artifact", None)
+        if artifact is not None and self.obs_rms is not None:   # local warm start (pql_actor.py:37-38)
+            from pql_amd.algo.pql_v_learner import load_artifact
+            load_artifact(artifact, obs_rms=self.obs_rms)
         self._pk = None        # fragment-ordered copy of the rollout replica's weights (fused policy forward), see set_actor
         self._pk_stale = True  # re-derived at the start of every explore_env and after set_actor / assignment of `.actor`
         self._fwd_buf = None   # (zero-padded input tile, activation scratch) of the fused policy forward
@@ -89,6 +100,53 @@ class PQLActor:
         if noise.decay == "exp":
             return ExponentialSchedule(noise.std_max, noise.exp_decay_rate, noise.std_min)
         return None
+
+    # ---- training state ---------------------------------------------------------
+    def _state_tensors(self):
+        """{name: device tensor} restored in place.  Agents derived from this class add their arenas, optimiser moments and
+        loss rings."""
+        out = {"current_returns": self.current_returns, "current_lengths": self.current_lengths}
+        if self._actor is not None:
+            out["actor"] = self._actor.arena.data
+        return out
+
+    def training_state(self):
+        """Rollout side: running statistics, the policy replica, the current observation, per-env accumulators, the episode
+        windows, the noise schedule, the exploration generator and the n-step windows (the caller has synchronised)."""
+        rms, sch = self.obs_rms, self.noise_scheduler
+        return {"tensors": {k: t.detach().cpu() for k, t in self._state_tensors().items()},
+                "obs_rms": None if rms is None else (rms.mean.detach().cpu(), rms.var.detach().cpu(), float(rms.count)),
+                "obs": None if self.obs is None else self.obs.detach().cpu(),
+                "return_tracker": self.return_tracker.training_state(), "step_tracker": self.step_tracker.training_state(),
+                "noise": None if sch is None else (int(sch.count), float(sch.last_val)),
+                "gen": None if self.gen is None else self.gen.get_state().clone(),
+                "nstep": self.n_step_buffer.training_state()}
+
+    @torch.no_grad()
+    def load_training_state(self, st, nstep=True):
+        """nstep=False: the n-step windows start over (a checkpoint without replay rings)."""
+        mine = self._state_tensors()
+        missing = set(st["tensors"]) ^ set(mine)
+        if missing:
+            raise ValueError(f"{type(self).__name__}.load_training_state: tensors {sorted(missing)} are on one side only")
+        for k, t in mine.items():
+            t.copy_(st["tensors"][k])
+        if self.obs_rms is not None and st["obs_rms"] is not None:
+            mean, var, count = st["obs_rms"]
+            self.obs_rms.mean, self.obs_rms.var = mean.to(self.sim_device), var.to(self.sim_device)
+            self.obs_rms.count = float(count)
+        self.obs = None if st["obs"] is None else st["obs"].to(self.sim_device)
+        self.return_tracker.load_training_state(st["return_tracker"])
+        self.step_tracker.load_training_state(st["step_tracker"])
+        if self.noise_scheduler is not None and st["noise"] is not None:
+            self.noise_scheduler.count, self.noise_scheduler.last_val = int(st["noise"][0]), float(st["noise"][1])
+        if self.gen is not None and st["gen"] is not None:
+            self.gen.set_state(st["gen"].cpu())
+        if nstep:
+            self.n_step_buffer.load_training_state(st["nstep"])
+        else:
+            self.n_step_buffer.reset()
+        self._pk_stale = True
 
     # ---- small API kept from the reference ---------------------------------------------------
     def reset_agent(self):

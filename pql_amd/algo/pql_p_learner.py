@@ -19,15 +19,16 @@ from copy import deepcopy
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.pql_v_learner import (GATHER_FLAGS, LOSS_RING, LaggedLoss, _AdamState, _cfg_get, adopt_arena, allreduce_sum, apply_optimizer,
-                                        apply_optimizer_fused, f32_recip, graph_collective_enabled, pump, resident_norm)
-from pql_amd.models import model_name_to_path
+from pql_amd.algo.pql_v_learner import (GATHER_FLAGS, LOSS_RING, LaggedLoss, _AdamState, _cfg_get, _cpu, adam_state, adopt_arena, allreduce_sum,
+                                        apply_optimizer, apply_optimizer_fused, f32_recip, graph_collective_enabled, lagged_state, load_adam_state,
+                                        load_artifact, load_lagged_state, load_norm_state, make_actor, make_critic, norm_state, pump,
+                                        resident_norm)
 from pql_amd.models.mlp import PackedWeights, default_splits, mlp_forward_raw, output_view
 from pql_amd.replay.simple_replay import RecordRing, _obs_width, ring_plan
 from pql_amd.utils import handoff as H
 from pql_amd.utils.dp import drain_pending_collectives
 from pql_amd.utils import rng as R
-from pql_amd.utils.common import Tracker, load_class_from_path
+from pql_amd.utils.common import Tracker
 
 
 class PQLPLearner:
@@ -43,13 +44,9 @@ class PQLPLearner:
         # dp: the collective is issued even for a 1-rank group, so the RCCL path can be rehearsed on one GPU
         self.dp = process_group is not None
         algo = cfg.algo
-        act_class = load_class_from_path(algo.act_class, model_name_to_path[algo.act_class])
-        hidden = _cfg_get(algo, "hidden_layers")
-        hidden = list(hidden) if hidden is not None else None
-        with torch.cuda.device(self.device):
-            self.actor = act_class(self.obs_dim, self.action_dim, hidden_layers=hidden).to(self.device)
-        if cfg.artifact is not None:
-            raise NotImplementedError("W&B artifact download is out of scope (no network); load a local state_dict instead")
+        self.actor = make_actor(cfg, self.obs_dim, self.action_dim, self.device)
+        if cfg.artifact is not None:   # local warm start (pql_p_learner.py:27-28)
+            load_artifact(cfg.artifact, actor=self.actor)
         self.opt = _AdamState(self.actor.arena.data)
         self._fused = bool(_cfg_get(algo, "fused", True))
         self._fold_loss = bool(_cfg_get(algo, "fused_tail", True))   # see PQLVLearner
@@ -510,6 +507,47 @@ class PQLPLearner:
         else:
             self._slot_graphs[slot] = g
             self._graph_post, self._graph_key = g_post, key
+
+    def training_state(self):
+        """See PQLVLearner.training_state; the obs ring's rows are streamed separately (`ring.rows(cur_capacity)`)."""
+        with self._lock:
+            return {"actor": _cpu(self.actor.arena.data), "opt": adam_state(self.opt), "update_count": int(self.update_count),
+                    "loss_ring": _cpu(self.loss_ring), "lagged": lagged_state(self._lagged),
+                    "loss_tracker": [float(x) for x in self.loss_tracker.moving_average],
+                    "critic": None if self.critic is None else _cpu(self.critic.arena.data),   # lags the live critic by design
+                    "norm": norm_state(self), "sleep_time": float(self.sleep_time), "gen": self.gen.get_state().clone(),
+                    "memory": {"ring": self.ring.training_state(), "next_p": int(self.next_p), "if_full": bool(self.if_full),
+                               "cur_capacity": int(self.cur_capacity)},
+                    "published": self._pub.training_state()}
+
+    @torch.no_grad()
+    def load_training_state(self, st, memory=True):
+        """See PQLVLearner.load_training_state."""
+        with self._lock, torch.cuda.device(self.device):
+            self.actor.arena.data.copy_(st["actor"])
+            load_adam_state(self.opt, st["opt"])
+            self.update_count = int(st["update_count"])
+            self.loss_ring.copy_(st["loss_ring"])
+            load_lagged_state(self._lagged, st["lagged"])
+            self.loss_tracker = Tracker(LOSS_RING)
+            self.loss_tracker.update(list(st["loss_tracker"]))
+            if st["critic"] is not None:
+                if self.critic is None:
+                    self.critic = make_critic(self.cfg, self.obs_dim, self.action_dim, self.device)
+                    self.critic.requires_grad_(False)
+                    self.pk_critic = PackedWeights(self.critic.layout, self.device) if self._fused else None
+                self.critic.arena.data.copy_(st["critic"])
+            load_norm_state(self, st["norm"])
+            self.sleep_time = st["sleep_time"]
+            self.gen.set_state(st["gen"].cpu())
+            if memory:
+                m = st["memory"]
+                self.ring.load_training_state(m["ring"])
+                self.next_p, self.if_full, self.cur_capacity = int(m["next_p"]), bool(m["if_full"]), int(m["cur_capacity"])
+            self._pub.load_training_state(st["published"])
+            self.repack()
+            self._drop_ahead()
+            self._ahead_stamp = None
 
     def loss_mean(self):
         """Exact mean of the last 5 losses (Tracker(5).mean(), zero-filled before 5 steps); synchronises."""

@@ -213,6 +213,94 @@ def pump(learner, stop_event=None, max_in_flight=2):
         pending.popleft().synchronize()
 
 
+def make_critic(cfg, obs_dim, action_dim, device):
+    """The critic `cfg.algo` names, freshly initialised on `device` (consumes the CPU generator like any module constructor)."""
+    algo = cfg.algo
+    if algo.distl and "Distributional" not in algo.cri_class:
+        algo.cri_class = "Distributional" + algo.cri_class  # same rewrite as the reference (:30-31)
+    cri_class = load_class_from_path(algo.cri_class, model_name_to_path[algo.cri_class])
+    hidden = _cfg_get(algo, "hidden_layers")
+    hidden = list(hidden) if hidden is not None else None
+    with torch.cuda.device(device):
+        if algo.distl:
+            return cri_class(obs_dim, action_dim, v_min=algo.v_min, v_max=algo.v_max, num_atoms=algo.num_atoms, device=device,
+                             hidden_layers=hidden).to(device)
+        return cri_class(obs_dim, action_dim, hidden_layers=hidden).to(device)
+
+
+def make_actor(cfg, obs_dim, action_dim, device):
+    """The policy `cfg.algo` names, freshly initialised on `device`."""
+    act_class = load_class_from_path(cfg.algo.act_class, model_name_to_path[cfg.algo.act_class])
+    hidden = _cfg_get(cfg.algo, "hidden_layers")
+    hidden = list(hidden) if hidden is not None else None
+    with torch.cuda.device(device):
+        return act_class(obs_dim, action_dim, hidden_layers=hidden).to(device)
+
+
+ARTIFACT_ERROR = "W&B artifact download is out of scope (no network); load a local state_dict instead"
+
+
+def load_artifact(path, actor=None, critic=None, obs_rms=None):
+    """`cfg.artifact` as a local warm start: a file in the reference's checkpoint format (what `Evaluator` writes as
+    model.pth, pql_amd.utils.model_util) -> the given modules.  Anything that is not an existing file is a W&B artifact name."""
+    import os
+    from pql_amd.utils.model_util import load_model
+    if not os.path.isfile(str(path)):
+        raise NotImplementedError(ARTIFACT_ERROR)
+    if actor is not None:
+        load_model(actor, "actor", str(path))
+    if critic is not None:
+        load_model(critic, "critic", str(path))
+    if obs_rms is not None:
+        load_model(obs_rms, "obs_rms", str(path))
+
+
+def _cpu(t):
+    return t.detach().cpu()
+
+
+def adam_state(st):
+    return {"m": _cpu(st.m), "v": _cpu(st.v), "step": _cpu(st.step)}
+
+
+def load_adam_state(st, saved):
+    st.m.copy_(saved["m"])
+    st.v.copy_(saved["v"])
+    st.step.copy_(saved["step"])
+
+
+def lagged_state(lag):
+    """(count, value) a `LaggedLoss` reports once the copy it has in flight has landed (the caller has synchronised)."""
+    if lag.event is not None:
+        return {"count": int(lag.count_at_copy), "value": LaggedLoss.mean_of(lag.host.tolist(), lag.count_at_copy)}
+    return {"count": int(lag.count_at_copy), "value": float(lag.value)}
+
+
+def load_lagged_state(lag, saved):
+    lag.event, lag.count_at_copy, lag.value = None, int(saved["count"]), float(saved["value"])
+
+
+def norm_state(learner):
+    nt = learner.normalize_tuple
+    return None if nt is None else (_cpu(nt[0]), _cpu(nt[1]), float(nt[2]))
+
+
+def load_norm_state(learner, saved):
+    """Into the learner's resident buffers (`resident_norm`): captured graphs keep reading the same addresses."""
+    if saved is None:
+        learner.normalize_tuple = None
+        return
+    mean, var, eps = saved
+    cur = getattr(learner, "_norm_buf", None)
+    if cur is None or cur[0].shape != mean.reshape(-1).shape:
+        cur = (torch.empty(mean.numel(), dtype=torch.float32, device=learner.device),
+               torch.empty(var.numel(), dtype=torch.float32, device=learner.device))
+        learner._norm_buf = cur
+    cur[0].copy_(mean.reshape(-1))
+    cur[1].copy_(var.reshape(-1))
+    learner.normalize_tuple = (cur[0], cur[1], float(eps))
+
+
 class PQLVLearner:
     def __init__(self, obs_dim, action_dim, cfg, process_group=None):
         self.cfg = cfg
@@ -227,19 +315,9 @@ class PQLVLearner:
         self.dp = process_group is not None
 
         algo = cfg.algo
-        if algo.distl and "Distributional" not in algo.cri_class:
-            algo.cri_class = "Distributional" + algo.cri_class  # same rewrite as the reference (:30-31)
-        cri_class = load_class_from_path(algo.cri_class, model_name_to_path[algo.cri_class])
-        hidden = _cfg_get(algo, "hidden_layers")
-        hidden = list(hidden) if hidden is not None else None
-        with torch.cuda.device(self.device):
-            if algo.distl:
-                self.critic = cri_class(self.obs_dim, self.action_dim, v_min=algo.v_min, v_max=algo.v_max,
-                                        num_atoms=algo.num_atoms, device=self.device, hidden_layers=hidden).to(self.device)
-            else:
-                self.critic = cri_class(self.obs_dim, self.action_dim, hidden_layers=hidden).to(self.device)
-        if cfg.artifact is not None:
-            raise NotImplementedError("W&B artifact download is out of scope (no network); load a local state_dict instead")
+        self.critic = make_critic(cfg, self.obs_dim, self.action_dim, self.device)
+        if cfg.artifact is not None:   # local warm start (pql_v_learner.py:44-47): the target below is the copy of what was loaded
+            load_artifact(cfg.artifact, critic=self.critic)
         self.critic_target = deepcopy(self.critic)
         self.opt = _AdamState(self.critic.arena.data)
         fused = bool(_cfg_get(algo, "fused", True))
@@ -845,6 +923,47 @@ class PQLVLearner:
             torch.cuda.set_rng_state(rng, self.device)
 
     # ------------------------------------------------------------------------------------------
+    def training_state(self):
+        """Everything later steps depend on, as CPU tensors and plain values; the caller has synchronised the
+        device.  The replay rows themselves are streamed separately (`memory.rows()`): only the ring's header is here."""
+        with self._lock:
+            return {"critic": _cpu(self.critic.arena.data), "critic_target": _cpu(self.critic_target.arena.data),
+                    "opt": adam_state(self.opt), "update_count": int(self.update_count), "loss_ring": _cpu(self.loss_ring),
+                    "lagged": lagged_state(self._lagged), "loss_tracker": [float(x) for x in self.loss_tracker.moving_average],
+                    "actor": None if self.actor is None else _cpu(self.actor.arena.data),   # lags the live policy by design
+                    "norm": norm_state(self), "sleep_time": float(self.sleep_time), "gen": self.gen.get_state().clone(),
+                    "memory": self.memory.training_state(), "published": self._pub.training_state()}
+
+    @torch.no_grad()
+    def load_training_state(self, st, memory=True):
+        """In place: arenas, rings, packed copies, publisher buffers and captured hipGraphs keep their addresses.  memory=False
+        leaves the (empty) ring and its pointers alone -- a checkpoint written without rings.  The ring ROWS are read by the
+        caller right after this call; what was prepared ahead is dropped here, and the ring's version moves on."""
+        with self._lock, torch.cuda.device(self.device):
+            self.critic.arena.data.copy_(st["critic"])
+            self.critic_target.arena.data.copy_(st["critic_target"])
+            load_adam_state(self.opt, st["opt"])
+            self.update_count = int(st["update_count"])
+            self.loss_ring.copy_(st["loss_ring"])
+            load_lagged_state(self._lagged, st["lagged"])
+            self.loss_tracker = Tracker(LOSS_RING)
+            self.loss_tracker.update(list(st["loss_tracker"]))
+            if st["actor"] is not None:
+                if self.actor is None:
+                    self.actor = make_actor(self.cfg, self.obs_dim, self.action_dim, self.device)
+                    self.actor.requires_grad_(False)
+                    self.pk_actor = PackedWeights(self.actor.layout, self.device) if self._fused else None
+                self.actor.arena.data.copy_(st["actor"])
+            load_norm_state(self, st["norm"])
+            self.sleep_time = st["sleep_time"]
+            self.gen.set_state(st["gen"].cpu())
+            if memory:
+                self.memory.load_training_state(st["memory"])
+            self._pub.load_training_state(st["published"])
+            self.repack()
+            self._drop_ahead()
+            self._ahead_stamp = None
+
     def loss_mean(self):
         """Exact mean of the last 5 losses (Tracker(5).mean(), zero-filled before 5 steps); synchronises."""
         with torch.cuda.device(self.device), self._on_stream():

@@ -67,6 +67,16 @@ class AgentSAC(PQLActor):
         x = self.obs_rms.normalize(obs) if self.cfg.algo.obs_norm else obs
         return self.actor.get_actions(x, sample=sample)
 
+    def _state_tensors(self):
+        out = super()._state_tensors()   # (the policy itself is the base class's "actor")
+        out.update(critic=self.critic.arena.data, critic_target=self.critic_target.arena.data, closs=self.closs, aloss=self.aloss,
+                   log_alpha=self.log_alpha, alpha_loss=self.alpha_loss)
+        if self.actor_target is not self.actor:
+            out["actor_target"] = self.actor_target.arena.data
+        for name, opt in (("aopt", self.aopt), ("copt", self.copt), ("alpha_opt", self.alpha_opt)):
+            out.update({f"{name}.m": opt.m, f"{name}.v": opt.v, f"{name}.step": opt.step})
+        return out
+
     def explore_env(self, env, timesteps, random=False):
         act_data, cri_data, steps = super().explore_env(env, timesteps, random)
         del act_data

@@ -62,6 +62,19 @@ class SyntheticVecEnv:
         self._obs = self._normal(1, self.obs_dim)
         return self._obs
 
+    def state_dict(self):
+        """Everything the next transitions depend on besides the constructor arguments: the step counter (and the last
+        observation handed out)."""
+        return {"t": int(self.t), "obs": None if self._obs is None else self._obs.detach().clone(),
+                "seed": self.seed, "num_envs": self.num_envs, "env_offset": self.env_offset}
+
+    def load_state_dict(self, state):
+        for key in ("seed", "num_envs", "env_offset"):
+            if int(state[key]) != getattr(self, key):
+                raise ValueError(f"SyntheticVecEnv.load_state_dict: {key}={getattr(self, key)} but the state was saved with {int(state[key])}")
+        self.t = int(state["t"])
+        self._obs = None if state["obs"] is None else state["obs"].to(self.device, torch.float32).clone()
+
     @torch.no_grad()
     def step(self, action):
         self.t += 1

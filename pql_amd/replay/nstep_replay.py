@@ -32,6 +32,18 @@ class NStepReplay:
         self.win_ld = int(L.lib.pqlk_replay_rec_ld(self.O, self.A))
         self.window = torch.zeros((self.num_envs, self.nstep, self.win_ld), dtype=torch.float32, device=self.device)
 
+    def training_state(self):
+        return {"window": self.window.detach().cpu(), "nstep_count": int(self.nstep_count)}
+
+    def load_training_state(self, st):
+        self.window.copy_(st["window"])
+        self.nstep_count = int(st["nstep_count"])
+
+    def reset(self):
+        """Empty window, as constructed (a resume without replay rings starts its windows over together with the rings)."""
+        self.window.zero_()
+        self.nstep_count = 0
+
     def rows_out(self, T):
         """Rows the next add_to_buffer call with horizon T emits."""
         if self.nstep <= 1:

@@ -60,6 +60,21 @@ class RecordRing:
         self.off_rd = 2 * o4 + ((max(self.A, 0) + 3) & ~3)
         self.version = 0   # bumped by every insert: the learners' draws-ahead tiles are stamped with it (stale tiles are re-gathered)
 
+    def rows(self, n):
+        """Records [0, n) raw, pads included (a contiguous prefix of the record array): what a checkpoint streams."""
+        return self.records[: int(n)]
+
+    def training_state(self):
+        return {"capacity": self.capacity, "O": self.O, "A": self.A, "rec_ld": self.rec_ld, "version": int(self.version)}
+
+    def load_training_state(self, st):
+        """Header check + version.  The caller then writes `rows(cur_capacity)` straight into the record array, which no
+        `Tensor._version` sees: the version moves past the saved one so that tiles gathered ahead are re-gathered."""
+        for key in ("capacity", "O", "A", "rec_ld"):
+            if int(st[key]) != getattr(self, key):
+                raise ValueError(f"replay ring: {key}={getattr(self, key)} but the checkpoint holds {key}={int(st[key])}")
+        self.version = int(st["version"]) + 1
+
     def insert_segments(self, segs, obs, act=None, rew=None, nobs=None, done=None):
         self.version += 1
         with torch.cuda.device(self.device):
@@ -127,6 +142,17 @@ class ReplayBuffer:
     @property
     def buf_done(self):
         return self.ring.records[:, self.ring.off_rd + 1: self.ring.off_rd + 2] != 0
+
+    def training_state(self):
+        return {"ring": self.ring.training_state(), "next_p": int(self.next_p), "if_full": bool(self.if_full),
+                "cur_capacity": int(self.cur_capacity)}
+
+    def load_training_state(self, st):
+        self.ring.load_training_state(st["ring"])
+        self.next_p, self.if_full, self.cur_capacity = int(st["next_p"]), bool(st["if_full"]), int(st["cur_capacity"])
+
+    def rows(self):
+        return self.ring.rows(self.cur_capacity)
 
     # ---- a3 ---------------------------------------------------------------------------------
     @torch.no_grad()

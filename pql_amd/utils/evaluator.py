@@ -287,6 +287,17 @@ class Evaluator:
             return step > self.cfg.max_step
         return (time.time() - self.start_time) > self.cfg.max_time
 
+    def training_state(self):
+        """Best return so far and the wall time used, so that `max_time` is a budget over the whole run.  An evaluation in
+        flight is not saved: it is simply not reported."""
+        engine = getattr(self, "engine", None)
+        return {"ret_max": float(engine.ret_max) if engine is not None else float("-inf"), "elapsed": time.time() - self.start_time}
+
+    def load_training_state(self, st):
+        if getattr(self, "engine", None) is not None:
+            self.engine.ret_max = float(st["ret_max"])
+        self.start_time = time.time() - float(st["elapsed"])
+
     def close(self):
         """Ends the child process, if there is one (the reference relies on `daemon=True` alone)."""
         if self.process is not None:

@@ -150,6 +150,25 @@ class ArenaPublisher:
             return s
 
 
+    def last(self):
+        """The snapshot handed out last."""
+        return self.slots[(self.k - 1) % len(self.slots)]
+
+    def training_state(self):
+        """The snapshot last handed out: the driver's `critic` / `actor` variables refer to it, and it lags the live arena."""
+        return {"arena": self.last().arena.data.detach().cpu()}
+
+    def load_training_state(self, st):
+        """Into the slot `last()` names, ready on the current stream; returns that snapshot module."""
+        with LOCK:
+            s = self.last()
+            st_ = torch.cuda.current_stream(self.live.arena.device)
+            reclaim(s._pql_lease, st_)
+            s.arena.data.copy_(st["arena"])
+            s._pql_lease.ready = _event(st_)
+            return s
+
+
 _COPY_STREAMS = {}
 
 

@@ -77,3 +77,18 @@ class RatioController:
             self.actor_wait_time = old.actor_wait + slack if slack > 0 else max(0, old.actor_wait + slack)
         self._push(critic_updates, actor_updates)
         return self.sim_wait_time, self.critic_wait_time, self.actor_wait_time
+
+    def training_state(self):
+        """Window contents (times relative to now: the clock of the resuming process starts elsewhere) and the three waits."""
+        now = self.clock()
+        return {"sim_count": int(self.sim_count), "waits": (float(self.sim_wait_time), float(self.critic_wait_time), float(self.actor_wait_time)),
+                "window": [(float(s.time - now), int(s.sim), int(s.critic), int(s.actor), float(s.sim_wait), float(s.critic_wait),
+                            float(s.actor_wait)) for s in self.window]}
+
+    def load_training_state(self, st):
+        now = self.clock()
+        self.sim_count = int(st["sim_count"])
+        self.sim_wait_time, self.critic_wait_time, self.actor_wait_time = (float(x) for x in st["waits"])
+        self.window.clear()
+        for t, *rest in st["window"]:
+            self.window.append(_Sample(now + float(t), *rest))

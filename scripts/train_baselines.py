@@ -15,12 +15,40 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pql_amd.algo import alg_name_to_path  # noqa: E402
 from pql_amd.envs.synthetic import create_task_env  # noqa: E402
 from pql_amd.replay.simple_replay import ReplayBuffer  # noqa: E402
+from pql_amd.utils import checkpoint as CK  # noqa: E402
 from pql_amd.utils.cfg import load_cfg  # noqa: E402
 from pql_amd.utils.common import capture_keyboard_interrupt, load_class_from_path, preprocess_cfg, set_random_seed  # noqa: E402
 from pql_amd.utils.logger import MetricLogger  # noqa: E402
 
 
+def save_checkpoint(opt, cfg, env, agent, memory, global_steps, next_iter, elapsed):
+    """Agent + replay + env + process state at a loop boundary, behind one device synchronisation."""
+    import torch
+    torch.cuda.synchronize(agent.device)
+    state = {"structure": CK.structure(cfg, agent.obs_dim[0], agent.action_dim), "iter_t": int(next_iter), "env": env.state_dict(),
+             "agent": agent.training_state(), "memory": memory.training_state(), "elapsed": float(elapsed),
+             "process": CK.process_state([agent.device])}
+    return CK.save(opt["dir"], global_steps, state, {"ring": memory.rows()} if opt["replay"] else None, keep=opt["keep"])
+
+
+def load_checkpoint(opt, cfg, env, agent, memory):
+    import torch
+    ckpt, st = CK.load(opt["resume"])
+    has_ring = bool(st["rings"])
+    CK.check_structure(st["structure"], CK.structure(cfg, agent.obs_dim[0], agent.action_dim), has_ring)
+    env.load_state_dict(st["env"])
+    agent.load_training_state(st["agent"], nstep=has_ring)
+    if has_ring:
+        memory.load_training_state(st["memory"])
+        CK.load_ring(ckpt, st, "ring", memory.rows(), verify=opt["verify"])
+    torch.cuda.synchronize(agent.device)
+    CK.load_process_state(st["process"])   # last: building the agent drew from the generators
+    return ckpt, st
+
+
 def main(cfg):
+    CK.refuse(cfg, int(os.environ.get("WORLD_SIZE", "1")))
+    opt = CK.options(cfg)
     set_random_seed(cfg.seed)
     capture_keyboard_interrupt()
     if cfg.device == "cuda":
@@ -29,18 +57,38 @@ def main(cfg):
     preprocess_cfg(cfg)
     env = create_task_env(cfg)
     algo_name = cfg.algo.name if "Agent" in cfg.algo.name else "Agent" + cfg.algo.name
+    artifact = cfg.get("artifact")
+    if artifact is not None and opt["resume"] is not None:
+        print("[train_baselines] warning: resume and artifact are both set; resume wins, artifact is ignored", file=sys.stderr)
+        artifact = None
+    cfg.artifact = None   # (the agent's base class would read it at construction: here the weights are loaded once the agent is built)
     agent = load_class_from_path(algo_name, alg_name_to_path[algo_name])(env=env, cfg=cfg)
-    logger = MetricLogger(cfg.logging.get("jsonl") if cfg.get("logging") else None)
-    start, global_steps = time.time(), 0
+    if artifact is not None:   # local warm start, as the reference does after building the agent (train_baselines.py:33-37)
+        from pql_amd.algo.pql_v_learner import load_artifact
+        load_artifact(artifact, actor=agent.actor, critic=agent.critic, obs_rms=getattr(agent, "obs_rms", None))
+        if getattr(agent, "critic_target", None) is not None:
+            agent.critic_target.arena.data.copy_(agent.critic.arena.data)
+    logger = MetricLogger(cfg.logging.get("jsonl") if cfg.get("logging") else None)   # (appends: a resumed run continues the file)
+    start, global_steps, start_iter, resumed_from = time.time(), 0, 0, None
     agent.reset_agent()
     is_off_policy = cfg.algo.name != "PPO"
     if is_off_policy:
         memory = ReplayBuffer(capacity=int(cfg.algo.memory_size), obs_dim=agent.obs_dim, action_dim=agent.action_dim, device=cfg.device)
-        trajectory, steps = agent.explore_env(env, cfg.algo.warm_up, random=True)
-        memory.add_to_buffer(trajectory)
-        global_steps += steps
+        saved = None
+        if opt["resume"] is not None:
+            ckpt, saved = load_checkpoint(opt, cfg, env, agent, memory)
+            global_steps, start_iter, start = int(saved["global_steps"]), int(saved["iter_t"]), time.time() - float(saved["elapsed"])
+            resumed_from = dict(path=ckpt, global_steps=global_steps, actor_sha=CK.sha(agent.actor.arena.data), critic_sha=CK.sha(agent.critic.arena.data))
+        if saved is None or not saved["rings"]:
+            if saved is not None:
+                print("[train_baselines] resume: the checkpoint holds no replay ring -- repeating the warm-up rollout; from here on this "
+                      "run is not bit-exact with the uninterrupted one", file=sys.stderr)
+            trajectory, steps = agent.explore_env(env, cfg.algo.warm_up, random=True)
+            memory.add_to_buffer(trajectory)
+            global_steps += steps
     log_info = {}
-    for iter_t in count():
+    ckpt_dir, ckpt_freq = opt["dir"], opt["freq"]
+    for iter_t in count(start_iter):
         trajectory, steps = agent.explore_env(env, cfg.algo.horizon_len, random=False)
         global_steps += steps
         if is_off_policy:
@@ -51,9 +99,18 @@ def main(cfg):
         if iter_t % cfg.algo.log_freq == 0:
             log_info["global_steps"] = global_steps
             logger.log(log_info, global_steps)
-        if (cfg.max_step is not None and global_steps > cfg.max_step) or (cfg.max_step is None and time.time() - start > cfg.max_time):
+        stop = (cfg.max_step is not None and global_steps > cfg.max_step) or (cfg.max_step is None and time.time() - start > cfg.max_time)
+        if ckpt_dir is not None and (stop or (ckpt_freq is not None and (iter_t + 1) % ckpt_freq == 0)):
+            save_checkpoint(opt, cfg, env, agent, memory, global_steps, iter_t + 1, time.time() - start)
+        if stop:
             break
-    return {**log_info, "global_steps": global_steps, "iters": iter_t + 1}
+    result = {**log_info, "global_steps": global_steps, "iters": iter_t + 1}
+    if is_off_policy:   # fingerprints of what the run ends with, as scripts/train_pql.py returns them
+        import torch
+        torch.cuda.synchronize(agent.device)
+        result.update(actor_sha=CK.sha(agent.actor.arena.data), critic_sha=CK.sha(agent.critic.arena.data),
+                      replay_sha=CK.sha_stream(memory.rows()), resumed_from=resumed_from)
+    return result
 
 
 if __name__ == "__main__":

@@ -38,6 +38,7 @@ from pql_amd.algo.pql_actor import PQLActor  # noqa: E402
 from pql_amd.algo.pql_p_learner import PQLPLearner, asyn_p_learner  # noqa: E402
 from pql_amd.algo.pql_v_learner import PQLVLearner, asyn_v_learner  # noqa: E402
 from pql_amd.envs.synthetic import create_task_env  # noqa: E402
+from pql_amd.utils import checkpoint as CK  # noqa: E402
 from pql_amd.utils.cfg import load_cfg  # noqa: E402
 from pql_amd.utils.common import capture_keyboard_interrupt, preprocess_cfg, set_random_seed  # noqa: E402
 from pql_amd.utils.dp import broadcast_from_rank0, component_groups, init_data_parallel, shard  # noqa: E402
@@ -57,11 +58,64 @@ def agree_to_stop(stop, pg, device):
     return bool(flag.item())
 
 
+def _devices(*components):
+    return sorted({d for d in components if d.type == "cuda"}, key=lambda d: d.index or 0)
+
+
+def arena_fingerprints(v_learner, p_learner):
+    return dict(critic_sha=CK.sha(v_learner.critic.arena.data), critic_target_sha=CK.sha(v_learner.critic_target.arena.data),
+                actor_sha=CK.sha(p_learner.actor.arena.data))
+
+
+def save_checkpoint(opt, cfg, env, pql_actor, v_learner, p_learner, evaluator, ctl, global_steps, next_iter):
+    """Full training state at a loop boundary (every `learn_many` of the iteration issued, the next `explore_env` not yet):
+    behind one device synchronisation, with free-running learner threads parked at their locks for the duration."""
+    with v_learner._lock, p_learner._lock:
+        devices = _devices(pql_actor.sim_device, v_learner.device, p_learner.device)
+        for d in devices:
+            torch.cuda.synchronize(d)
+        state = {"structure": CK.structure(cfg, env.observation_space.shape[0], env.action_space.shape[0]), "iter_t": int(next_iter),
+                 "env": env.state_dict(), "rollout": pql_actor.training_state(), "v_learner": v_learner.training_state(),
+                 "p_learner": p_learner.training_state(), "evaluator": evaluator.training_state(),
+                 "ratio": None if ctl is None else ctl.training_state(), "process": CK.process_state(devices)}
+        rings = {"ring_v": v_learner.memory.rows(), "ring_p": p_learner.ring.rows(p_learner.cur_capacity)} if opt["replay"] else None
+        return CK.save(opt["dir"], global_steps, state, rings, keep=opt["keep"])
+
+
+def load_checkpoint(opt, cfg, env, pql_actor, v_learner, p_learner, evaluator):
+    """Restore what `save_checkpoint` wrote into freshly built components, in place.  The process generators come last: building
+    the components drew from them.  Returns (state, critic snapshot, actor snapshot, `resumed_from` entry of the result)."""
+    ckpt, st = CK.load(opt["resume"])
+    has_rings = bool(st["rings"])
+    CK.check_structure(st["structure"], CK.structure(cfg, env.observation_space.shape[0], env.action_space.shape[0]), has_rings)
+    env.load_state_dict(st["env"])
+    v_learner.load_training_state(st["v_learner"], memory=has_rings)
+    p_learner.load_training_state(st["p_learner"], memory=has_rings)
+    if has_rings:
+        staging = CK.Staging()
+        CK.load_ring(ckpt, st, "ring_v", v_learner.memory.rows(), staging, opt["verify"])
+        CK.load_ring(ckpt, st, "ring_p", p_learner.ring.rows(p_learner.cur_capacity), staging, opt["verify"])
+    critic, actor = v_learner._pub.last(), p_learner._pub.last()
+    pql_actor.set_actor(actor)
+    pql_actor.load_training_state(st["rollout"], nstep=has_rings)
+    evaluator.load_training_state(st["evaluator"])
+    for d in _devices(pql_actor.sim_device, v_learner.device, p_learner.device):
+        torch.cuda.synchronize(d)
+    CK.load_process_state(st["process"])
+    resumed_from = dict(path=ckpt, global_steps=int(st["global_steps"]), **arena_fingerprints(v_learner, p_learner))
+    return st, critic, actor, resumed_from
+
+
 def main(cfg):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     pg = None
+    CK.refuse(cfg, world)   # (in front of init_data_parallel: a refused job must not wait for its peers)
+    opt = CK.options(cfg)
+    if opt["resume"] is not None and cfg.get("artifact") is not None:
+        print("[train_pql] warning: resume and artifact are both set; resume wins, artifact is ignored", file=sys.stderr)
+        cfg.artifact = None
     if world > 1:
         # algo.dp_backend=nccl (RCCL, one GPU per rank); gloo + algo.dp_share_gpu=True rehearses this branch on ONE card
         pg, local = init_data_parallel(cfg.algo.get("dp_backend", "nccl"), bool(cfg.algo.get("dp_share_gpu", False)), local)
@@ -108,20 +162,35 @@ def main(cfg):
         want = "torch" if str(cfg.algo.get("rng", "auto")) == "torch" or bool(cfg.algo.get("graph_rng", False)) else (
             "philox (one launch per run of steps, torch's own numbers)" if R.verified(v_dev) is not None else "torch (the philox check failed on this device)")
         print(f"[train_pql] learner draws: {want}", file=sys.stderr)
-    critic, critic_update_times, critic_loss = v_learner.start()
-    actor, actor_update_times, actor_loss = p_learner.start()
-    pql_actor.set_actor(actor)
+    if opt["resume"] is None:
+        critic, critic_update_times, critic_loss = v_learner.start()
+        actor, actor_update_times, actor_loss = p_learner.start()
+        pql_actor.set_actor(actor)
 
-    logger = MetricLogger(cfg.logging.get("jsonl") if cfg.get("logging") else None) if rank == 0 else None
-    global_steps = 0
+    logger = MetricLogger(cfg.logging.get("jsonl") if cfg.get("logging") else None) if rank == 0 else None   # (appends: a resumed run continues the file)
+    global_steps, start_iter, saved, resumed_from = 0, 0, None, None
     # evaluation beside training (train_pql.py:55,171-185): rank 0 only; every rank keeps the stop criterion
     evaluator = Evaluator(cfg=cfg, wandb_run=None, enabled=rank == 0)
-    pql_actor.reset_agent()
-    p_data, v_data, steps = pql_actor.explore_env(env, cfg.algo.warm_up, random=True)
-    global_steps += steps * world
     rms = (lambda dev: pql_actor.obs_rms.get_states(dev)) if pql_actor.obs_rms is not None else (lambda dev: None)
-    critic, critic_loss, critic_update_times = v_learner.update(actor, v_data, rms(v_dev), 0)
-    actor, actor_loss, actor_update_times = p_learner.update(critic, p_data, rms(p_dev), 0)
+    if opt["resume"] is None:
+        pql_actor.reset_agent()
+    else:
+        # continue at the saved loop boundary: no start()-time hand-offs, no warm-up; `critic` / `actor` are the snapshots the
+        # stopped run held (they lag the live arenas by one hand-off)
+        saved, critic, actor, resumed_from = load_checkpoint(opt, cfg, env, pql_actor, v_learner, p_learner, evaluator)
+        global_steps, start_iter = int(saved["global_steps"]), int(saved["iter_t"])
+        critic_update_times, actor_update_times = v_learner.update_count, p_learner.update_count
+        critic_loss, actor_loss = v_learner._lagged.value, p_learner._lagged.value
+    if saved is None or not saved["rings"]:
+        if saved is not None:
+            print("[train_pql] resume: the checkpoint holds no replay rings -- repeating the warm-up rollout; from here on this run "
+                  "is not bit-exact with the uninterrupted one", file=sys.stderr)
+        p_data, v_data, steps = pql_actor.explore_env(env, cfg.algo.warm_up, random=True)
+        global_steps += steps * world
+        critic, critic_loss, critic_update_times = v_learner.update(actor, v_data, rms(v_dev), 0)
+        actor, actor_loss, actor_update_times = p_learner.update(critic, p_data, rms(p_dev), 0)
+        if saved is not None:
+            pql_actor.set_actor(actor)
 
     free_running = bool(cfg.algo.get("async_learners", False))
     if free_running and world > 1:
@@ -130,19 +199,25 @@ def main(cfg):
     stop_learners, threads, ctl = threading.Event(), [], None
     if free_running:
         # the reference's learners are separate processes with their own RNG streams
-        v_learner.use_private_rng(cfg.seed + 1)
-        p_learner.use_private_rng(cfg.seed + 2)
+        if saved is None:   # (a resumed run continues the restored streams)
+            v_learner.use_private_rng(cfg.seed + 1)
+            p_learner.use_private_rng(cfg.seed + 2)
         depth = int(cfg.algo.get("max_in_flight", 2))
         threads = [threading.Thread(target=asyn_v_learner, args=(v_learner, cfg, stop_learners, depth), daemon=True),
                    threading.Thread(target=asyn_p_learner, args=(p_learner, cfg, stop_learners, depth), daemon=True)]
         for t in threads:
             t.start()
         ctl = RatioController(cfg.algo.critic_sample_ratio, cfg.algo.critic_actor_ratio, critic_update_times, actor_update_times)
+        if saved is not None and saved["ratio"] is not None:
+            ctl.load_training_state(saved["ratio"])
 
     v_per_iter = int(cfg.algo.critic_sample_ratio)
     p_every = int(cfg.algo.critic_actor_ratio)
     critic_wait = actor_wait = 0
-    for iter_t in count():
+    if ctl is not None and saved is not None:
+        critic_wait, actor_wait = ctl.critic_wait_time, ctl.actor_wait_time
+    ckpt_dir, ckpt_freq = opt["dir"], opt["freq"]
+    for iter_t in count(start_iter):
         p_data, v_data, steps = pql_actor.explore_env(env, cfg.algo.horizon_len, random=False)
         global_steps += steps * world
         # hand-offs (train_pql.py:111-119): newest policy + transitions -> V-learner, newest critic + obs -> P-learner,
@@ -177,6 +252,8 @@ def main(cfg):
         stop = evaluator.check_if_should_stop(global_steps)
         if cfg.max_step is None:
             stop = agree_to_stop(stop, pg, sim_device)
+        if ckpt_dir is not None and (stop or (ckpt_freq is not None and (iter_t + 1) % ckpt_freq == 0)):
+            save_checkpoint(opt, cfg, env, pql_actor, v_learner, p_learner, evaluator, ctl, global_steps, iter_t + 1)
         if stop:
             break
     stop_learners.set()
@@ -187,15 +264,18 @@ def main(cfg):
             logger.log(evaluator.parent.recv(), global_steps)
         evaluator.close()
     torch.cuda.synchronize()
-    import hashlib
-    sha = lambda t: hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()[:16]   # noqa: E731  (replicas must stay bit-equal)
-    fingerprints = dict(critic_sha=sha(v_learner.critic.arena.data), critic_target_sha=sha(v_learner.critic_target.arena.data),
-                        actor_sha=sha(p_learner.actor.arena.data))
+    fingerprints = arena_fingerprints(v_learner, p_learner)   # (replicas must stay bit-equal)
+    # ... and of the resident data: both rings' first cur_capacity records, and the running statistics (mean || var)
+    staging = CK.Staging()
+    fingerprints.update(replay_sha=CK.sha_stream(v_learner.memory.rows(), staging),
+                        obs_ring_sha=CK.sha_stream(p_learner.ring.rows(p_learner.cur_capacity), staging),
+                        rms_sha=None if pql_actor.obs_rms is None else CK.sha(torch.cat([pql_actor.obs_rms.mean.reshape(-1),
+                                                                                         pql_actor.obs_rms.var.reshape(-1)])))
     if world > 1:
         torch.distributed.barrier(group=pg)
         torch.distributed.destroy_process_group()
     return dict(rank=rank, world=world, **fingerprints, global_steps=global_steps, critic_updates=v_learner.update_count, actor_updates=p_learner.update_count,
-                critic_loss=v_learner.loss_mean(), actor_loss=p_learner.loss_mean(), rollout_iterations=iter_t + 1, waits=(None if ctl is None else (ctl.sim_wait_time, ctl.critic_wait_time,
+                critic_loss=v_learner.loss_mean(), actor_loss=p_learner.loss_mean(), rollout_iterations=iter_t + 1, resumed_from=resumed_from, waits=(None if ctl is None else (ctl.sim_wait_time, ctl.critic_wait_time,
                                                                                  ctl.actor_wait_time)))
 
 
