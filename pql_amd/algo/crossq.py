@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
+from pql_amd.algo.learner import LOSS_RING, _AdamState, _cfg_get, apply_optimizer
 from pql_amd.algo.pql_actor import PQLActor
-from pql_amd.algo.pql_v_learner import LOSS_RING, _AdamState, _cfg_get, apply_optimizer
 from pql_amd.models import model_name_to_path
 from pql_amd.models.mlp import default_splits, mlp_forward_raw, output_view
 from pql_amd.utils.common import load_class_from_path

@@ -81,7 +81,7 @@ class PQLActor:
             self.gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
         artifact = getattr(cfg, "artifact", None)
         if artifact is not None and self.obs_rms is not None:   # local warm start (pql_actor.py:37-38)
-            from pql_amd.algo.pql_v_learner import load_artifact
+            from pql_amd.algo.learner import load_artifact
             load_artifact(artifact, obs_rms=self.obs_rms)
         self._pk = None        # fragment-ordered copy of the rollout replica's weights (fused policy forward), see set_actor
         self._pk_stale = True  # re-derived at the start of every explore_env and after set_actor / assignment of `.actor`

@@ -64,7 +64,7 @@ def main(cfg):
     cfg.artifact = None   # (the agent's base class would read it at construction: here the weights are loaded once the agent is built)
     agent = load_class_from_path(algo_name, alg_name_to_path[algo_name])(env=env, cfg=cfg)
     if artifact is not None:   # local warm start, as the reference does after building the agent (train_baselines.py:33-37)
-        from pql_amd.algo.pql_v_learner import load_artifact
+        from pql_amd.algo.learner import load_artifact
         load_artifact(artifact, actor=agent.actor, critic=agent.critic, obs_rms=getattr(agent, "obs_rms", None))
         if getattr(agent, "critic_target", None) is not None:
             agent.critic_target.arena.data.copy_(agent.critic.arena.data)

@@ -110,7 +110,7 @@ def main():
                                         None, 0, L.ptr(ws["bwd"]), ws["bwd"].numel(), st()))
 
     scratch_arena = [t.clone() for t in (v.critic.arena.data, v.opt.m, v.opt.v, v.critic_target.arena.data)]
-    from pql_amd.algo.pql_v_learner import apply_optimizer
+    from pql_amd.algo.learner import apply_optimizer
 
     def sec_opt():   # clip + AdamW + Polyak + re-pack on scratch copies (norm pass included: two launches)
         apply_optimizer(scratch_arena[0], ws["grads"], v.opt, scratch_arena[3], 5e-4, 0.5, 0.05, 1.0, dev, layout=cl,
