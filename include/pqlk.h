@@ -484,6 +484,21 @@ int pqlk_synth_env_step(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t se
                         pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PointMass vectorised environment step (the learnable task of pql_amd/envs/pointmass.py; not a reference component).
+ * Replaces the ~40 elementwise / masked-select torch launches of `PointMassVecEnv._step_torch`, to which every output is
+ * bit-equal (one fp32 rounding per operation, no contraction, the sums over act_dim taken in index order, no atomics):
+ *   a = clamp(action, -1, 1); v' = 0.8 v + 0.2 a; x' = x + 0.25 v'; k' = k + 1; oob = any |x'| > 1.5;
+ *   reward = -mean_j (x' - g)^2 - 0.01 mean_j a^2 - oob; truncated = k' >= episode_length && !oob; done = oob || truncated.
+ * State (x, v, g: (N, act_dim) floats; k, ep: (N) int32) is updated IN PLACE; a done env moves to episode ep + 1 and is reset
+ * from the counter-based uniform of the synthetic env keyed by (seed, env_offset + env, ep + 1), v = 0, k = 0.
+ * next_obs (N, obs_dim) = [x | v | g | 0 ...] AFTER the reset (16-byte stores when obs_dim % 4 == 0 and next_obs is 16-byte
+ * aligned); reward (N) floats; done / truncated (N) bytes.
+ * PQLK_E_NULL: any pointer NULL.  PQLK_E_SHAPE: n <= 0, act_dim <= 0, obs_dim < 3 * act_dim. */
+int pqlk_pointmass_step(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                        int32_t episode_length, const float* action, float* x, float* v, float* g, int32_t* k, int32_t* ep,
+                        float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-env-step bookkeeping of the rollout in one launch (pql_actor.py:104-114 slab writes, :129-135 update_tracker,
  * common.py:195-202 handle_timeout): column t of the (N, horizon, .) trajectory slabs <- (obs, action, reward, next_obs,
  * done * !truncated); cur_return += reward, cur_length += 1; the finished envs' values are appended IN ENV ORDER to the two

@@ -2,19 +2,7 @@
 // reference component): a counter-based generator, every output a pure function of (seed, global env id, step, column),
 // so data-parallel shards reproduce slices of the global env.  Same arithmetic as the torch-op definition in
 // pql_amd/envs/synthetic.py (which stays the CPU / test form); the torch version costs ~150 tiny launches per step.
-#include "pqlk_common.h"
-
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-  x = (x ^ (x >> 16)) * 0x7FEB352Du;
-  x = (x ^ (x >> 15)) * 0x846CA68Bu;
-  return x ^ (x >> 16);
-}
-
-__device__ __forceinline__ float uni(uint32_t env, uint32_t seed, uint32_t t, uint32_t stream, uint32_t col) {
-  const uint32_t key = hash32(env * 0x9E3779B1u + seed * 0x85EBCA77u + t * 0xC2B2AE3Du + stream * 0x27D4EB2Fu);
-  const uint32_t h = hash32(key * 0x165667B1u + col * 0x9E3779B1u + 0x5BD1E995u);
-  return ((float)h + 0.5f) * (1.0f / 4294967296.0f);
-}
+#include "envhash.h"
 
 __device__ __forceinline__ float gauss(uint32_t env, uint32_t seed, uint32_t t, uint32_t stream, uint32_t col) {
   const float u1 = uni(env, seed, t, 2 * stream, col), u2 = uni(env, seed, t, 2 * stream + 1, col);

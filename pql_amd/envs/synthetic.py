@@ -109,7 +109,8 @@ class SyntheticVecEnv:
 
 
 def create_task_env(cfg, num_envs=None, env_offset=0):
-    """Stand-in for pql.utils.isaacgym_util.create_task_env (:8-24)."""
+    """Stand-in for pql.utils.isaacgym_util.create_task_env (:8-24).  `task.kind` picks the env: absent / synthetic = the
+    counter-based generator above, pointmass = the learnable task of pql_amd/envs/pointmass.py."""
     task = cfg.task
     name = task.name if task is not None else "AllegroHand"
     O, A = TASK_SHAPES.get(name, (88, 16))
@@ -117,5 +118,12 @@ def create_task_env(cfg, num_envs=None, env_offset=0):
         O = int(task.obs_dim) if task.get("obs_dim") else O
         A = int(task.act_dim) if task.get("act_dim") else A
     ep = int(task.get("episode_length") or 300) if task is not None else 300
+    kind = (task.get("kind") if task is not None else None) or "synthetic"   # absent = the synthetic env, as before `kind` existed
+    if kind == "pointmass":
+        from pql_amd.envs.pointmass import PointMassVecEnv
+        return PointMassVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
+                               env_offset=env_offset)
+    if kind != "synthetic":
+        raise ValueError(f"task.kind={kind}: no such env; known kinds: synthetic, pointmass")
     return SyntheticVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
                            env_offset=env_offset)

@@ -46,7 +46,8 @@ def load_checkpoint(opt, cfg, env, agent, memory):
     return ckpt, st
 
 
-def main(cfg):
+def main(cfg, on_finish=None):
+    """`on_finish(agent)`: called once the loop has stopped, with the trained agent (tools/learn_pointmass.py evaluates it)."""
     CK.refuse(cfg, int(os.environ.get("WORLD_SIZE", "1")))
     opt = CK.options(cfg)
     set_random_seed(cfg.seed)
@@ -104,6 +105,8 @@ def main(cfg):
             save_checkpoint(opt, cfg, env, agent, memory, global_steps, iter_t + 1, time.time() - start)
         if stop:
             break
+    if on_finish is not None:
+        on_finish(agent)
     result = {**log_info, "global_steps": global_steps, "iters": iter_t + 1}
     if is_off_policy:   # fingerprints of what the run ends with, as scripts/train_pql.py returns them
         import torch

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Parallel Q-Learning entry point -- same command line as the reference's scripts/train_pql.py
 (`python scripts/train_pql.py task=AllegroHand algo.distl=True algo.num_gpus=1 ...`), same cfg keys, same
-metric names; the Isaac-Gym rollout is replaced by the synthetic vectorised env (task.name picks the shapes).
+metric names; the Isaac-Gym rollout is replaced by the synthetic vectorised env (task.name picks the shapes), or by the learnable
+PointMass task (`task=pointmass`, pql_amd/envs/pointmass.py).
 
 Orchestration (SURVEY 3.1 -> MI355X): instead of three Ray processes exchanging pickled nn.Modules through the
 object store, ONE process drives three launch queues (HIP streams; with `algo.num_gpus=2` the learners' queues sit
@@ -106,7 +107,9 @@ def load_checkpoint(opt, cfg, env, pql_actor, v_learner, p_learner, evaluator):
     return st, critic, actor, resumed_from
 
 
-def main(cfg):
+def main(cfg, on_finish=None):
+    """`on_finish(pql_actor, v_learner, p_learner)`: called once the loop has stopped and the device is idle (tools/learn_pointmass.py
+    evaluates the trained policy)."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -264,6 +267,9 @@ def main(cfg):
             logger.log(evaluator.parent.recv(), global_steps)
         evaluator.close()
     torch.cuda.synchronize()
+    if on_finish is not None:
+        on_finish(pql_actor, v_learner, p_learner)
+        torch.cuda.synchronize()
     fingerprints = arena_fingerprints(v_learner, p_learner)   # (replicas must stay bit-equal)
     # ... and of the resident data: both rings' first cur_capacity records, and the running statistics (mean || var)
     staging = CK.Staging()

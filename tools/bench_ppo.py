@@ -102,14 +102,16 @@ class EagerPPO:
             opt.step()
 
 
-def bench_shape(name, sh, iters, O, A):
+def bench_shape(name, sh, iters, overrides=()):
     from pql_amd.algo.ppo import AgentPPO
     from pql_amd.envs.synthetic import create_task_env
     from pql_amd.utils.cfg import load_cfg
     dev = torch.device("cuda:0")
-    cfg = load_cfg(["algo=ppo_algo", "task.name=AllegroHand", f"num_envs={sh['num_envs']}", f"algo.horizon_len={sh['horizon']}",
-                    f"algo.batch_size={sh['batch']}", f"algo.update_times={sh['epochs']}", "device=cuda:0"])
+    task = [] if any(o.lstrip("+").startswith(("task=", "task.name=")) for o in overrides) else ["task.name=AllegroHand"]
+    cfg = load_cfg(["algo=ppo_algo", *task, f"num_envs={sh['num_envs']}", f"algo.horizon_len={sh['horizon']}",
+                    f"algo.batch_size={sh['batch']}", f"algo.update_times={sh['epochs']}", "device=cuda:0", *overrides])
     env = create_task_env(cfg)
+    O, A = env.observation_space.shape[0], env.action_space.shape[0]
     agent = AgentPPO(env, cfg)
     agent.reset_agent()
     rows = sh["num_envs"] * sh["horizon"]
@@ -171,6 +173,8 @@ def main():
     ap.add_argument("--shape", choices=["all", *SHAPES], default="all")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the result lines to this JSON file")
+    ap.add_argument("overrides", nargs="*", help="config overrides, e.g. task=pointmass task.obs_dim=88 task.act_dim=16 "
+                    "(default: the synthetic env with AllegroHand's shapes)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_ppo needs a GPU"
     torch.manual_seed(0)
@@ -178,7 +182,7 @@ def main():
     res = []
     for name, sh in SHAPES.items():
         if a.shape in ("all", name):
-            r = bench_shape(name, sh, a.iters, 88, 16)
+            r = bench_shape(name, sh, a.iters, a.overrides)
             print(json.dumps(r), flush=True)
             res.append(r)
     if a.out:

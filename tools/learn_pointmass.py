@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Learning record on the PointMass task (pql_amd/envs/pointmass.py): do the kernels, assembled into a training run, improve a policy?
+
+Runs the two entry points themselves -- `scripts/train_baselines.py` (DDPG) and the fixed-ratio loop of `scripts/train_pql.py` -- on
+PointMass for a fixed number of rollout iterations, several seeds each, at two shapes:
+
+    small  (obs 8, act 2):   64 envs, batch 256, hidden [128, 128]
+    large  (obs 88, act 16): 1024 envs, batch 8192, the default hidden layers [512, 256, 128]
+
+everything else at the defaults (nstep 3, gamma 0.99, tau 0.05, lr 5e-4, mixed exploration noise).  Per run it records the return of
+the trained deterministic policy over one full episode on 256 fresh envs (R), the same for the zero action (R_zero) and for the PD
+controller a = clamp(4 (g - x) - 4 v, -1, 1) (R_pd), the gap fraction f = (R - R_zero) / (R_pd - R_zero) and the wall time.
+`--curve` adds DDPG at the small shape over a ladder of iteration counts (where does it plateau?).
+
+    python tools/learn_pointmass.py --out profiles/pointmass_learning.json
+    python tools/learn_pointmass.py --algos ddpg --shapes small --seeds 1 --iters 200      # a quick look
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from pql_amd.envs.pointmass import PointMassVecEnv, episode_return, pd_policy, zero_policy  # noqa: E402
+from pql_amd.utils.cfg import load_cfg  # noqa: E402
+
+EPISODE_LENGTH = 64
+EVAL_ENVS = 256
+WARM_UP = 32   # algo.warm_up default: random-policy env steps in front of the first iteration
+SHAPES = {
+    "small": dict(obs_dim=8, act_dim=2, num_envs=64, batch=256, hidden=[128, 128]),
+    "large": dict(obs_dim=88, act_dim=16, num_envs=1024, batch=8192, hidden=None),
+}
+ALGOS = {"ddpg": ("train_baselines.py", ["algo=ddpg_algo"]), "pql": ("train_pql.py", ["algo=pql_algo", "algo.num_gpus=1"])}
+_SCRIPTS = {}
+
+
+def script(name):
+    if name not in _SCRIPTS:
+        spec = importlib.util.spec_from_file_location(name[:-3], os.path.join(ROOT, "scripts", name))
+        _SCRIPTS[name] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(_SCRIPTS[name])
+    return _SCRIPTS[name]
+
+
+def overrides(algo, shape, seed, iters, run_dir):
+    sh = SHAPES[shape]
+    n = sh["num_envs"]
+    ov = [*ALGOS[algo][1], "task=pointmass", f"task.obs_dim={sh['obs_dim']}", f"task.act_dim={sh['act_dim']}",
+          f"task.episode_length={EPISODE_LENGTH}", f"num_envs={n}", f"algo.batch_size={sh['batch']}",
+          f"algo.memory_size={(WARM_UP + iters + 8) * n}", f"seed={seed}", f"max_step={(WARM_UP + iters) * n - 1}", f"+logging.dir={run_dir}"]
+    if sh["hidden"] is not None:
+        ov.append(f"algo.hidden_layers={sh['hidden']}")
+    return ov
+
+
+def yardsticks(shape, seed, device="cuda:0"):
+    """(eval env, R_zero, R_pd): 256 fresh envs (their seed is not the training env's) and the two hand-written controllers on them."""
+    sh = SHAPES[shape]
+    env = PointMassVecEnv(EVAL_ENVS, sh["obs_dim"], sh["act_dim"], device=device, seed=10_000 + seed, episode_length=EPISODE_LENGTH)
+    return env, episode_return(env, zero_policy(env)), episode_return(env, pd_policy(env))
+
+
+def run(algo, shape, seed, iters):
+    """One training run through the entry point's own `main`; the policy is evaluated by its `on_finish` hook."""
+    env, r_zero, r_pd = yardsticks(shape, seed)
+    got = {}
+
+    def evaluate(agent, *_learners):   # DDPG: the agent; PQL: (rollout actor, V-learner, P-learner)
+        agent.set_actor(agent.actor)   # the weights were stepped in place: refresh the rollout's packed copy
+        got["R"] = episode_return(env, lambda obs: agent.get_actions(obs, sample=False))
+
+    with tempfile.TemporaryDirectory() as run_dir:   # (the PQL loop's evaluator keeps its best model there)
+        cfg = load_cfg(overrides(algo, shape, seed, iters, run_dir))
+        torch.cuda.synchronize()
+        t0 = time.time()
+        res = script(ALGOS[algo][0]).main(cfg, on_finish=evaluate)
+        torch.cuda.synchronize()
+        wall = time.time() - t0
+    done_iters = res["iters"] if algo == "ddpg" else res["rollout_iterations"]
+    assert done_iters == iters, (done_iters, iters)
+    updates = iters * int(cfg.algo.update_times) if algo == "ddpg" else int(res["critic_updates"])
+    return dict(algo=algo, shape=shape, seed=seed, iters=iters, critic_updates=updates, R=got["R"], R_zero=r_zero, R_pd=r_pd,
+                f=(got["R"] - r_zero) / (r_pd - r_zero), wall_s=round(wall, 2))
+
+
+def env_step_time(num_envs=4096, obs_dim=88, act_dim=16, steps=2000, rounds=3):
+    """Microseconds per env step of the one-launch HIP step and of its torch definition on the GPU (host clock around `steps` steps
+    that end in a device synchronise; the two forms alternate, the best of `rounds` is kept; one warm-up round)."""
+    mk = lambda: PointMassVecEnv(num_envs, obs_dim, act_dim, device="cuda:0", seed=1, episode_length=EPISODE_LENGTH)   # noqa: E731
+    hip, ref = mk(), mk()
+    act = 2.0 * torch.rand((num_envs, act_dim), device="cuda:0") - 1.0
+    best = {"hip": float("inf"), "torch": float("inf")}
+    for r in range(rounds + 1):
+        for name, step in (("hip", hip.step), ("torch", ref._step_torch)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                step(act)
+            torch.cuda.synchronize()
+            if r > 0:
+                best[name] = min(best[name], (time.perf_counter() - t0) / steps * 1e6)
+    return dict(num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim, steps=steps, hip_us=round(best["hip"], 2), torch_us=round(best["torch"], 2))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--algos", default="ddpg,pql")
+    ap.add_argument("--shapes", default="small,large")
+    ap.add_argument("--seeds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=1000, help="rollout iterations per run (8 critic updates each)")
+    ap.add_argument("--curve", default=None, help="comma-separated iteration counts: DDPG at the small shape, every seed, at each of them")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "learn_pointmass needs a GPU"
+    out = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, episode_length=EPISODE_LENGTH, eval_envs=EVAL_ENVS,
+               shapes=SHAPES, env_step=env_step_time(), runs=[], curve=[])
+    print(json.dumps(out["env_step"]), flush=True)
+
+    def record(key, r):
+        out[key].append(r)
+        print(json.dumps(r), flush=True)
+        if a.out:   # rewritten after every run: a run that is cut short still leaves what was measured
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+
+    for algo in a.algos.split(","):
+        for shape in a.shapes.split(","):
+            for seed in range(a.seeds):
+                record("runs", run(algo, shape, seed, a.iters))
+    for iters in ([int(x) for x in a.curve.split(",")] if a.curve else []):
+        for seed in range(a.seeds):
+            record("curve", run("ddpg", "small", seed, iters))
+
+
+if __name__ == "__main__":
+    main()
