@@ -379,19 +379,21 @@ int pqlk_dpg_loss(const float* q, int64_t ld, int32_t k, const float* support /*
  *   p *= 1 - lr*wd ; m += (g-m)(1-b1) ; v = b2 v + (1-b2) g^2
  *   p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
  *   target = p*tau + target*(1-tau)                              (target may be NULL)
+ * lr, b1, b2, eps, wd, tau are doubles, as torch holds them: 1 - b2, 1 - lr*wd, 1 - tau and the bias corrections are
+ * formed in double and rounded once.
  * step_dev: device int32 counter t, incremented by the call (graph-replay safe).
  * scratch: >= 2048 floats.  gnorm_out (device, may be NULL) receives the pre-clip norm.
  * ---------------------------------------------------------------------------------------------- */
 int pqlk_clip_adamw_polyak(float* p, float* g, float* m, float* v, float* target, int64_t n, float grad_scale,
-                           float max_norm, float lr, float b1, float b2, float eps, float wd, float tau,
+                           float max_norm, double lr, double b1, double b2, double eps, double wd, double tau,
                            int32_t* step_dev, float* gnorm_out, float* scratch, pqlk_stream_t stream);
 
 /* Same update for the arena of the MLP `d`, which ALSO refreshes the fragment-ordered weight copies of the fused
  * forward path while each new value is in a register (packed_p for the parameters, packed_t -- may be NULL -- for the
  * Polyak target), replacing the separate pqlk_mlp_pack launches. */
 int pqlk_clip_adamw_polyak_pack(const PqlMlpDesc* d, float* p, float* g, float* m, float* v, float* target,
-                                float* packed_p, float* packed_t, float grad_scale, float max_norm, float lr, float b1,
-                                float b2, float eps, float wd, float tau, int32_t* step_dev, float* gnorm_out,
+                                float* packed_p, float* packed_t, float grad_scale, float max_norm, double lr, double b1,
+                                double b2, double eps, double wd, double tau, int32_t* step_dev, float* gnorm_out,
                                 float* scratch, pqlk_stream_t stream);
 
 /* The optimiser launch of a fused learner step (pql_v_learner.py:124-133 + :109-111, pql_p_learner.py:87-96): the same
@@ -403,8 +405,8 @@ int pqlk_clip_adamw_polyak_pack(const PqlMlpDesc* d, float* p, float* g, float* 
  *                  loss_scale (1/B, 1/(B K), -1/B), into loss_ring[(t - 1) % ring_len], t = the incremented step --
  *                  the slot and the bits the stand-alone fold writes.  NULL = no fold. */
 int pqlk_adamw_polyak_fused(const PqlMlpDesc* d, float* p, float* g, float* m, float* v, float* target,
-                            float* packed_p, float* packed_t, float grad_scale, float max_norm, float lr, float b1,
-                            float b2, float eps, float wd, float tau, int32_t* step_dev, float* gnorm_out,
+                            float* packed_p, float* packed_t, float grad_scale, float max_norm, double lr, double b1,
+                            double b2, double eps, double wd, double tau, int32_t* step_dev, float* gnorm_out,
                             float* scratch, int32_t prenorm, const float* loss_part, int32_t loss_parts,
                             float loss_scale, float* loss_ring, int32_t ring_len, pqlk_stream_t stream);
 /* Number of per-block partials a loss entry point leaves in `scratch` (k = atoms; 1 for scalar heads). */

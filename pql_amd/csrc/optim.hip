@@ -204,8 +204,8 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
   }
 }
 
-static int adamw_impl(float* p, float* g, float* m, float* v, float* target, int64_t n, float grad_scale, float max_norm, float lr,
-                      float b1, float b2, float eps, float wd, float tau, int32_t* step_dev, float* gnorm_out, float* scratch,
+static int adamw_impl(float* p, float* g, float* m, float* v, float* target, int64_t n, float grad_scale, float max_norm, double lr,
+                      double b1, double b2, double eps, double wd, double tau, int32_t* step_dev, float* gnorm_out, float* scratch,
                       const PackSpec& ps, pqlk_stream_t stream, int prenorm = 0, LossFold lf = LossFold{}) {
   PQLK_REQUIRE(p && g && m && v && step_dev && scratch, PQLK_E_NULL);
   PQLK_REQUIRE(n > 0, PQLK_E_SHAPE);
@@ -221,19 +221,20 @@ static int adamw_impl(float* p, float* g, float* m, float* v, float* target, int
     PQLK_LAUNCH_CHECK();
   }
   AdamC c;
-  // scalar constants are formed in double (python floats in torch) and rounded once to fp32
-  c.lr_wd_decay = (float)(1.0 - (double)lr * (double)wd);
-  c.w1 = (float)(1.0 - (double)b1);
-  c.b2 = b2;
-  c.one_m_b2 = (float)(1.0 - (double)b2);
-  c.eps = eps;
-  c.tau = tau;
-  c.one_m_tau = (float)(1.0 - (double)tau);
+  // scalar constants are formed in double (python floats in torch) and rounded once to fp32.  The hyper-parameters arrive as
+  // doubles for that reason: 1 - (float)0.999 is 1.3e-5 away from torch's 1 - 0.999, and v carried that error.
+  c.lr_wd_decay = (float)(1.0 - lr * wd);
+  c.w1 = (float)(1.0 - b1);
+  c.b2 = (float)b2;
+  c.one_m_b2 = (float)(1.0 - b2);
+  c.eps = (float)eps;
+  c.tau = (float)tau;
+  c.one_m_tau = (float)(1.0 - tau);
   c.max_norm = max_norm;
   c.grad_scale = grad_scale;
-  c.lr = (double)lr;
-  c.b1d = (double)b1;
-  c.b2d = (double)b2;
+  c.lr = lr;
+  c.b1d = b1;
+  c.b2d = b2;
   int blocks2 = (int)(((n + 3) / 4 + 255) / 256);   // one 16-B quad per thread
   if (blocks2 > 2048) blocks2 = 2048;
   hipLaunchKernelGGL(k_adamw, dim3(blocks2), dim3(256), 0, pqlk_s(stream), p, g, m, v, target, n, scratch, blocks, c, step_dev,
@@ -243,7 +244,7 @@ static int adamw_impl(float* p, float* g, float* m, float* v, float* target, int
 }
 
 extern "C" int pqlk_clip_adamw_polyak(float* p, float* g, float* m, float* v, float* target, int64_t n, float grad_scale,
-                                      float max_norm, float lr, float b1, float b2, float eps, float wd, float tau,
+                                      float max_norm, double lr, double b1, double b2, double eps, double wd, double tau,
                                       int32_t* step_dev, float* gnorm_out, float* scratch, pqlk_stream_t stream) {
   PackSpec ps = {};
   return adamw_impl(p, g, m, v, target, n, grad_scale, max_norm, lr, b1, b2, eps, wd, tau, step_dev, gnorm_out, scratch, ps, stream);
@@ -279,8 +280,8 @@ static int build_pack_spec(const PqlMlpDesc* d, float* packed_p, float* packed_t
 }
 
 extern "C" int pqlk_clip_adamw_polyak_pack(const PqlMlpDesc* d, float* p, float* g, float* m, float* v, float* target,
-                                           float* packed_p, float* packed_t, float grad_scale, float max_norm, float lr, float b1,
-                                           float b2, float eps, float wd, float tau, int32_t* step_dev, float* gnorm_out,
+                                           float* packed_p, float* packed_t, float grad_scale, float max_norm, double lr, double b1,
+                                           double b2, double eps, double wd, double tau, int32_t* step_dev, float* gnorm_out,
                                            float* scratch, pqlk_stream_t stream) {
   PackSpec ps;
   const int rc = build_pack_spec(d, packed_p, packed_t, ps);
@@ -295,8 +296,8 @@ extern "C" int pqlk_clip_adamw_polyak_pack(const PqlMlpDesc* d, float* p, float*
 //   loss_part    : optional per-block loss partials (pqlk_*_loss called with loss_out = NULL): block 0 folds loss_parts of
 //                  them, times loss_scale, into loss_ring[(t - 1) % ring_len] instead of a separate one-block launch.
 extern "C" int pqlk_adamw_polyak_fused(const PqlMlpDesc* d, float* p, float* g, float* m, float* v, float* target,
-                                       float* packed_p, float* packed_t, float grad_scale, float max_norm, float lr, float b1,
-                                       float b2, float eps, float wd, float tau, int32_t* step_dev, float* gnorm_out,
+                                       float* packed_p, float* packed_t, float grad_scale, float max_norm, double lr, double b1,
+                                       double b2, double eps, double wd, double tau, int32_t* step_dev, float* gnorm_out,
                                        float* scratch, int32_t prenorm, const float* loss_part, int32_t loss_parts,
                                        float loss_scale, float* loss_ring, int32_t ring_len, pqlk_stream_t stream) {
   PQLK_REQUIRE(d, PQLK_E_NULL);
@@ -335,6 +336,10 @@ extern "C" int pqlk_polyak(float* target, const float* cur, int64_t n, float tau
 // batch mean / unbiased variance per column, two stages so the whole chip streams the (N, cols) block:
 //   stage 1: grid (col tiles of 32, row chunks): per chunk mean and M2 = sum (x - chunk_mean)^2 (two passes over
 //            rows the block just touched, L2-resident);  stage 2: Chan merge of the chunk moments in fixed order.
+// Both stages work on d = x - x[0][col], the column's first row: a column that sits far from zero (1000 +- 0.01) otherwise
+// rounds every chunk mean to its own ulp (6e-5), the merge's `delta` between two chunk means is mostly that rounding, and the
+// variance came out 7e-4 off where torch's fp32 var is 8e-6 off.  Shifted, d is exact for such a column and the means are
+// small numbers; a constant column gives d == 0, mean == the constant and variance == 0 to the bit.
 #define MOM_CHUNKS 64
 __global__ __launch_bounds__(256) void k_moments_stage1(const float* __restrict__ x, int64_t ldx, int64_t n, int cols,
                                                         int64_t rows_per_chunk, float* __restrict__ part) {
@@ -344,9 +349,10 @@ __global__ __launch_bounds__(256) void k_moments_stage1(const float* __restrict_
   const int64_t r0 = blockIdx.y * rows_per_chunk;
   const int64_t r1 = r0 + rows_per_chunk < n ? r0 + rows_per_chunk : n;
   const float cnt = (float)(r1 > r0 ? r1 - r0 : 0);
+  const float x0 = col < cols ? x[col] : 0.f;   // the shift
   float s = 0.f;
   if (col < cols)
-    for (int64_t r = r0 + ry; r < r1; r += 8) s += x[r * ldx + col];
+    for (int64_t r = r0 + ry; r < r1; r += 8) s += x[r * ldx + col] - x0;
   sh[ry][cx] = s;
   __syncthreads();
   float mean = 0.f;
@@ -356,7 +362,7 @@ __global__ __launch_bounds__(256) void k_moments_stage1(const float* __restrict_
   float q = 0.f;
   if (col < cols)
     for (int64_t r = r0 + ry; r < r1; r += 8) {
-      const float d = x[r * ldx + col] - mean;
+      const float d = (x[r * ldx + col] - x0) - mean;
       q += d * d;
     }
   sh[ry][cx] = q;
@@ -374,7 +380,8 @@ __global__ __launch_bounds__(256) void k_moments_stage1(const float* __restrict_
 // lane = b), so the result does not depend on which lane one reads.  (Rounds 1-3 let one thread per column walk the 64 partials
 // serially, two IEEE divisions per partial in a dependent chain: 20 us for a 4096 x 88 batch, the slowest launch of the rollout.)
 __global__ __launch_bounds__(256) void k_moments_stage2(const float* __restrict__ part, int chunks, int cols, int64_t n,
-                                                        float* __restrict__ mean_out, float* __restrict__ var_out) {
+                                                        const float* __restrict__ x, float* __restrict__ mean_out,
+                                                        float* __restrict__ var_out) {
   const int lane = threadIdx.x & 63;
   const int col = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (col >= cols) return;   // wave-uniform
@@ -400,7 +407,7 @@ __global__ __launch_bounds__(256) void k_moments_stage2(const float* __restrict_
     cnt = tot;
   }
   if (lane == 0) {
-    mean_out[col] = mean;
+    mean_out[col] = x[col] + mean;   // undo the shift
     var_out[col] = m2 / (float)(n - 1);
   }
 }
@@ -416,7 +423,7 @@ extern "C" int pqlk_batch_moments(const float* x, int64_t ldx, int64_t n, int32_
                      rows_per_chunk, scratch);
   PQLK_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_moments_stage2, dim3((cols + 3) / 4), dim3(256), 0, pqlk_s(stream), scratch, chunks, (int)cols, n,
-                     mean_out, var_out);
+                     x, mean_out, var_out);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }
