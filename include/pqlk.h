@@ -61,17 +61,37 @@ int64_t pqlk_ld(int64_t cols);
  * rec_ld = pqlk_replay_rec_ld(O, A) floats (multiple of 32 => every record starts on a 128-B line, so
  * a random sample touches ceil(rec_bytes/128) HBM lines instead of ~10 for the SoA layout).
  * The obs-only ring of the P-learner is the same thing with A = -1 (record = obs, rec_ld = pqlk_ld(O)).
+ *
+ * Half-precision observation storage (obs_dtype = PQLK_OBS_F16; the reference's `reserve_space=True`,
+ * simple_replay.py:9,15,91,94 -- kept in HBM here, not parked on the host):
+ *     record = [ obs(O) f16 pad8 | next_obs(O) f16 pad8 | action(A) f32 pad4 | reward, done, 0, 0 | zero pad ]
+ * Fields still start on 16-B boundaries and records on 128-B lines; a 16-B chunk of an observation field holds
+ * 8 columns.  rec_ld stays in 4-byte words: 2 * (roundup(O, 8) / 2) + roundup(A, 4) + 4, rounded up to 32
+ * (obs-only: roundup(O, 8) / 2, rounded up to 32) -- 512 B against 896 B at O = 88, A = 16.
+ * Observations are rounded to nearest even ONCE, at insert (overflow -> +-inf, fp16 subnormals kept, NaN stays
+ * NaN), and widened exactly when gathered: an fp16 ring fed x behaves bit for bit like an fp32 ring fed
+ * (float)(half)x.  Actions, reward and done stay fp32.  fp16 and not bf16: it is the reference's dtype, and
+ * bf16's 8 significand bits are too coarse for raw, not yet normalised observations.
+ * Every entry point below dispatches on obs_dtype; an unknown value is PQLK_E_SHAPE.
  * ---------------------------------------------------------------------------------------------- */
+enum {
+  PQLK_OBS_F32 = 0, /* observations stored as fp32 (the default; a zeroed field means this) */
+  PQLK_OBS_F16 = 1  /* observations stored as IEEE binary16 */
+};
+
 typedef struct {
-  float* records;    /* (capacity, rec_ld) */
+  float* records;    /* (capacity, rec_ld) 4-byte words */
   int64_t capacity;  /* rows */
   int32_t obs_dim;   /* O */
   int32_t act_dim;   /* A, or -1 for an obs-only ring */
-  int32_t rec_ld;    /* floats per record */
-  int32_t reserved;
+  int32_t rec_ld;    /* 4-byte words per record */
+  int32_t obs_dtype; /* PQLK_OBS_F32 / PQLK_OBS_F16 (was `reserved`, always 0) */
 } PqlReplayDesc;
 
 int64_t pqlk_replay_rec_ld(int32_t obs_dim, int32_t act_dim);
+/* The same for either storage format; pqlk_replay_rec_ld(O, A) == pqlk_replay_rec_ld_ex(O, A, PQLK_OBS_F32).
+ * 0 for obs_dim <= 0 or an unknown obs_dtype. */
+int64_t pqlk_replay_rec_ld_ex(int32_t obs_dim, int32_t act_dim, int32_t obs_dtype);
 
 /* Ring insert of m rows at row `next_p` (host-side pointer law stays in Python, it is integer
  * bookkeeping: simple_replay.py:52-83).  Row r of the source goes to (dst_start + r) for r in

@@ -15,12 +15,13 @@ _HERE = Path(__file__).resolve().parent
 LIB_FILE = Path(os.environ.get("PQLK_LIB", _HERE / "csrc" / "libpqlk.so"))   # PQLK_LIB: A/B a tuning build
 
 MAX_LAYERS = 8
+OBS_F32, OBS_F16 = 0, 1   # PqlReplayDesc.obs_dtype (PQLK_OBS_*)
 ACT_NONE, ACT_TANH, ACT_TANH_NOISE = 0, 1, 2
 
 
 class PqlReplayDesc(C.Structure):
     _fields_ = [("records", C.c_void_p), ("capacity", C.c_int64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32),
-                ("rec_ld", C.c_int32), ("reserved", C.c_int32)]
+                ("rec_ld", C.c_int32), ("obs_dtype", C.c_int32)]
 
 
 class PqlMlpDesc(C.Structure):
@@ -35,6 +36,7 @@ PROTOTYPES = {
     "pqlk_strerror": (C.c_char_p, [C.c_int]),
     "pqlk_ld": (_I64, [_I64]),
     "pqlk_replay_rec_ld": (_I64, [_I32, _I32]),
+    "pqlk_replay_rec_ld_ex": (_I64, [_I32, _I32, _I32]),
     "pqlk_replay_insert": (C.c_int, [C.POINTER(PqlReplayDesc), _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     "pqlk_replay_gather": (C.c_int, [C.POINTER(PqlReplayDesc), _P, _I64, _P, _P, _P, _P, _P, _P]),
     "pqlk_replay_gather_fused": (C.c_int, [C.POINTER(PqlReplayDesc), _P, _I64, _P, _P, _F, C.c_int, _P, _I64, _P, _P, _I64, _P, _P, _P]),

@@ -18,6 +18,7 @@ from pql_amd import _lib as L
 from pql_amd.algo.learner import LOSS_RING, _AdamState, _cfg_get, apply_optimizer
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models import model_name_to_path
+from pql_amd.replay.simple_replay import cfg_obs_dtype
 from pql_amd.models.mlp import default_splits, mlp_forward_raw, output_view
 from pql_amd.utils.common import load_class_from_path
 
@@ -29,6 +30,7 @@ class AgentDDPG(PQLActor):
         super().__init__(env, cfg)
         self.device = self.sim_device
         algo = cfg.algo
+        self.replay_obs_dtype = cfg_obs_dtype(algo)   # algo.replay_obs_dtype: storage format of the replay ring built for this agent
         hidden = _cfg_get(algo, "hidden_layers")
         hidden = list(hidden) if hidden is not None else None
         act_class = load_class_from_path(algo.act_class, model_name_to_path[algo.act_class])

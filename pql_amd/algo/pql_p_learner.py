@@ -19,7 +19,7 @@ from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
                                   load_artifact, make_actor, make_critic, pump, resident_norm)
 from pql_amd.models.mlp import PackedWeights, default_splits, mlp_forward_raw, output_view
-from pql_amd.replay.simple_replay import RecordRing, _obs_width, ring_plan
+from pql_amd.replay.simple_replay import RecordRing, _obs_width, cfg_obs_dtype, ring_plan
 from pql_amd.utils import handoff as H
 from pql_amd.utils import rng as R
 
@@ -40,7 +40,7 @@ class PQLPLearner(Learner):
         self.pk_actor = PackedWeights(self.actor.layout, self.device) if self._fused else None
         # obs-only replay (reference :32-37: a bare (memory_size, obs) tensor + inline pointer logic)
         self.memory_size = int(algo.memory_size)
-        self.ring = RecordRing(self.memory_size, _obs_width(obs_dim), -1, self.device)
+        self.ring = RecordRing(self.memory_size, _obs_width(obs_dim), -1, self.device, obs_dtype=cfg_obs_dtype(algo))
         self.next_p = 0
         self.if_full = False
         self.cur_capacity = 0
@@ -52,7 +52,7 @@ class PQLPLearner(Learner):
     @property
     def memory(self):
         """(memory_size, obs_dim) view of the ring, the reference's attribute name (:34)."""
-        return self.ring.records[:, : self.ring.O]
+        return self.ring.obs_view()
 
     def _bound(self):
         return self.cur_capacity

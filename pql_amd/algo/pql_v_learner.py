@@ -23,7 +23,7 @@ from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
                                   graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
 from pql_amd.models.mlp import PackedWeights, default_splits, mlp_forward_raw, output_view
-from pql_amd.replay.simple_replay import ReplayBuffer
+from pql_amd.replay.simple_replay import ReplayBuffer, cfg_obs_dtype
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
 from pql_amd.utils import rng as R
@@ -46,7 +46,7 @@ class PQLVLearner(Learner):
         self.pk_target = PackedWeights(self.critic.layout, self.device) if self._fused else None
         self._td_in_head = bool(_cfg_get(algo, "td_in_head", True))   # TD target + MSE inside the head's backward launch
         self.memory = ReplayBuffer(capacity=int(algo.memory_size), obs_dim=self.obs_dim, action_dim=self.action_dim,
-                                   device=self.device)
+                                   device=self.device, obs_dtype=cfg_obs_dtype(algo))
         self.sleep_time = 0
         # data parallel, algo.dp_buckets: "layer" = the gradient travels in per-layer buckets, each all-reduced as soon as its dW
         # slabs are summed, under the MFMA launches of the layers below (pql_amd/utils/dp.py); "one" = a single collective after

@@ -51,6 +51,30 @@ __host__ __device__ static inline RecLayout rec_layout(int O, int A) {
   return L;
 }
 
+// Record layout with half-precision observations (PQLK_OBS_F16), offsets in 4-byte words:
+//   [ obs (O) f16 pad8 | next_obs (O) f16 pad8 | action (A) f32 pad4 | reward, done, 0, 0 | zero pad to 32 words ]
+// An observation field is oh = roundup(O, 8) / 2 words (a multiple of 4: its 16-B chunks hold 8 columns each).
+struct RecLayoutH {
+  int O, A;        // A < 0: obs-only record
+  int oh;          // words of one observation field
+  int off_nobs, off_act, off_rd;
+  int used;        // words in use (multiple of 4)
+  int ld;          // record stride in words (multiple of 32)
+};
+
+__host__ __device__ static inline RecLayoutH rec_layout_h(int O, int A) {
+  RecLayoutH L;
+  L.O = O; L.A = A;
+  L.oh = ((O + 7) & ~7) >> 1;
+  if (A < 0) {
+    L.off_nobs = L.off_act = L.off_rd = L.oh; L.used = L.oh;
+  } else {
+    L.off_nobs = L.oh; L.off_act = 2 * L.oh; L.off_rd = 2 * L.oh + ((A + 3) & ~3); L.used = L.off_rd + 4;
+  }
+  L.ld = (L.used + 31) & ~31;
+  return L;
+}
+
 // "have I raised this kernel's dynamic-LDS limit on the CURRENT device yet?"  hipFuncSetAttribute acts on the current
 // device only, and one process may drive several (sim on GPU 0, learners on GPU 1): the flag is per device.
 // ctypes drops the GIL, so two host threads (the V and the P learner of `algo.async_learners`) may make a kernel's first call

@@ -11,6 +11,23 @@ extern "C" int64_t pqlk_replay_rec_ld(int32_t obs_dim, int32_t act_dim) {
   return rec_layout(obs_dim, act_dim).ld;
 }
 
+extern "C" int64_t pqlk_replay_rec_ld_ex(int32_t obs_dim, int32_t act_dim, int32_t obs_dtype) {
+  if (obs_dim <= 0) return 0;
+  if (obs_dtype == PQLK_OBS_F32) return rec_layout(obs_dim, act_dim).ld;
+  if (obs_dtype == PQLK_OBS_F16) return rec_layout_h(obs_dim, act_dim).ld;
+  return 0;
+}
+
+// fp16 observation storage (PQLK_OBS_F16): kernels and launchers of their own at the end of this file
+static int replay_insert_f16(const PqlReplayDesc* ring, int64_t dst_start, int64_t m, const float* obs, int64_t ld_obs,
+                             const float* act, int64_t ld_act, const float* rew, int64_t ld_rew, const float* next_obs,
+                             int64_t ld_nobs, const float* done, int64_t ld_done, pqlk_stream_t stream);
+static int replay_gather_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, float* obs, float* act, float* rew,
+                             float* next_obs, float* done, pqlk_stream_t stream);
+static int replay_gather_fused_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, const float* mean, const float* var,
+                                   float eps, int flags, float* x_sa, int64_t ld_sa, float* xn_sa, float* xn_obs, int64_t ld_o,
+                                   float* rew, float* done, pqlk_stream_t stream);
+
 // ------------------------------------------------------------------------------------------------
 // insert: row r of the five source arrays -> record (dst_start + r).  One wave per record.
 __global__ __launch_bounds__(256) void k_replay_insert(float* __restrict__ records, RecLayout L, int64_t dst_start,
@@ -45,6 +62,9 @@ extern "C" int pqlk_replay_insert(const PqlReplayDesc* ring, int64_t dst_start, 
                                   pqlk_stream_t stream) {
   PQLK_REQUIRE(ring && ring->records && obs, PQLK_E_NULL);
   PQLK_REQUIRE(ring->obs_dim > 0 && ring->capacity > 0 && m >= 0, PQLK_E_SHAPE);
+  if (ring->obs_dtype == PQLK_OBS_F16)
+    return replay_insert_f16(ring, dst_start, m, obs, ld_obs, act, ld_act, rew, ld_rew, next_obs, ld_nobs, done, ld_done, stream);
+  PQLK_REQUIRE(ring->obs_dtype == PQLK_OBS_F32, PQLK_E_SHAPE);
   RecLayout L = rec_layout(ring->obs_dim, ring->act_dim);
   PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
   PQLK_REQUIRE(dst_start >= 0 && dst_start + m <= ring->capacity, PQLK_E_RANGE);
@@ -106,6 +126,8 @@ extern "C" int pqlk_replay_gather(const PqlReplayDesc* ring, const int64_t* idx,
                                   float* rew, float* next_obs, float* done, pqlk_stream_t stream) {
   PQLK_REQUIRE(ring && ring->records && idx && obs, PQLK_E_NULL);
   PQLK_REQUIRE(ring->obs_dim > 0 && ring->capacity > 0 && b >= 0, PQLK_E_SHAPE);
+  if (ring->obs_dtype == PQLK_OBS_F16) return replay_gather_f16(ring, idx, b, obs, act, rew, next_obs, done, stream);
+  PQLK_REQUIRE(ring->obs_dtype == PQLK_OBS_F32, PQLK_E_SHAPE);
   RecLayout L = rec_layout(ring->obs_dim, ring->act_dim);
   PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
   if (L.A >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
@@ -515,6 +537,9 @@ extern "C" int pqlk_replay_gather_fused(const PqlReplayDesc* ring, const int64_t
   int nt_loads = ((flags & PQLK_GATHER_NT_LOADS) ? 1 : 0) | ((flags & PQLK_GATHER_NT_STORES) ? 2 : 0);
   PQLK_REQUIRE(ring && ring->records && idx, PQLK_E_NULL);
   PQLK_REQUIRE(ring->obs_dim > 0 && ring->capacity > 0 && b >= 0, PQLK_E_SHAPE);
+  if (ring->obs_dtype == PQLK_OBS_F16)
+    return replay_gather_fused_f16(ring, idx, b, mean, var, eps, flags, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, stream);
+  PQLK_REQUIRE(ring->obs_dtype == PQLK_OBS_F32, PQLK_E_SHAPE);
   RecLayout L = rec_layout(ring->obs_dim, ring->act_dim);
   PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
   PQLK_REQUIRE((mean == nullptr) == (var == nullptr), PQLK_E_NULL);
@@ -607,6 +632,800 @@ extern "C" int pqlk_replay_gather_fused(const PqlReplayDesc* ring, const int64_t
   else
     launch_gather_fused<false>(nchunk, (unsigned)blocks, pqlk_s(stream), ring->records, L, ring->capacity, idx, b, mean, var, eps,
                                clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
+// ================================================================================================
+// Half-precision observation storage (PqlReplayDesc.obs_dtype == PQLK_OBS_F16; layout: RecLayoutH in pqlk_common.h).
+// The kernels below are the fp16 counterparts of the five above, under names of their own: the fp32 kernels carry no dtype flag
+// or template argument (round 4 lost 20 % on k_replay_gather_fast to exactly that), the entry points dispatch on the host.
+// Records are handled as raw 32-bit words: a word that packs two halves is only ever copied or taken apart with integer
+// shifts, never treated as a float.  fp32 -> fp16 is the hardware's round-to-nearest-even conversion (v_cvt_f16_f32: overflow
+// to +-inf, fp16 subnormals produced, NaN stays NaN), fp16 -> fp32 is exact, so a ring fed x holds q(x) = (float)(half)x.
+__device__ __forceinline__ uint32_t pack_h2(float a, float b) {
+  const _Float16 ha = (_Float16)a, hb = (_Float16)b;
+  return (uint32_t)__builtin_bit_cast(unsigned short, ha) | ((uint32_t)__builtin_bit_cast(unsigned short, hb) << 16);
+}
+__device__ __forceinline__ float h_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float h_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+// the 8 columns of one 16-B observation chunk
+__device__ __forceinline__ void widen8(const uint4& w, float e[8]) {
+  e[0] = h_lo(w.x); e[1] = h_hi(w.x); e[2] = h_lo(w.y); e[3] = h_hi(w.y);
+  e[4] = h_lo(w.z); e[5] = h_hi(w.z); e[6] = h_lo(w.w); e[7] = h_hi(w.w);
+}
+
+// insert: one wave per record, one 16-B store per lane and chunk over the WHOLE stride (pad halves and words written as zero)
+__global__ __launch_bounds__(256) void k_replay_insert_f16(uint32_t* __restrict__ records, RecLayoutH L, int64_t dst_start,
+                                                           int64_t m, const float* __restrict__ obs, int64_t ld_obs,
+                                                           const float* __restrict__ act, int64_t ld_act,
+                                                           const float* __restrict__ rew, int64_t ld_rew,
+                                                           const float* __restrict__ nobs, int64_t ld_nobs,
+                                                           const float* __restrict__ done, int64_t ld_done) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int nq = L.ld >> 2;
+  for (int64_t r = wave; r < m; r += nwaves) {
+    uint4* rec4 = reinterpret_cast<uint4*>(records + (dst_start + r) * L.ld);
+    for (int q = lane; q < nq; q += 64) {
+      const int c = q << 2;
+      uint4 w = make_uint4(0u, 0u, 0u, 0u);
+      if (c < L.off_act) {   // obs, or next_obs (transition ring only: off_nobs == off_act == oh in an obs-only ring)
+        const bool nx = c >= L.off_nobs;
+        const float* s = nx ? nobs + r * ld_nobs : obs + r * ld_obs;
+        const int col = (nx ? c - L.off_nobs : c) << 1;
+        float e[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = col + j < L.O ? s[col + j] : 0.f;
+        w = make_uint4(pack_h2(e[0], e[1]), pack_h2(e[2], e[3]), pack_h2(e[4], e[5]), pack_h2(e[6], e[7]));
+      } else if (c < L.off_rd) {
+        const int cc = c - L.off_act;
+        uint32_t e[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = cc + j < L.A ? __float_as_uint(act[r * ld_act + cc + j]) : 0u;
+        w = make_uint4(e[0], e[1], e[2], e[3]);
+      } else if (L.A >= 0 && c == L.off_rd) {
+        w.x = __float_as_uint(rew[r * ld_rew]);
+        w.y = (done[r * ld_done] != 0.f) ? __float_as_uint(1.f) : 0u;   // .bool() then .float()
+      }
+      rec4[q] = w;
+    }
+  }
+}
+
+// plain gather: five contiguous fp32 outputs, the observation fields widened exactly
+__global__ __launch_bounds__(256) void k_replay_gather_f16(const uint32_t* __restrict__ records, RecLayoutH L, int64_t capacity,
+                                                           const int64_t* __restrict__ idx, int64_t b,
+                                                           float* __restrict__ o_obs, float* __restrict__ o_act,
+                                                           float* __restrict__ o_rew, float* __restrict__ o_nobs,
+                                                           float* __restrict__ o_done) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int nchunk = L.used >> 2;
+  for (int64_t r = wave; r < b; r += nwaves) {
+    int64_t src = idx[r];
+    if (src < 0 || src >= capacity) src = 0;  // never fault on a bad index
+    const uint4* rec4 = reinterpret_cast<const uint4*>(records + src * L.ld);
+    for (int q = lane; q < nchunk; q += 64) {
+      const uint4 w = rec4[q];
+      const int c = q << 2;
+      if (c < L.off_act) {
+        const bool nx = c >= L.off_nobs;
+        float* o = (nx ? o_nobs : o_obs) + r * L.O;
+        const int col = (nx ? c - L.off_nobs : c) << 1;
+        float e[8];
+        widen8(w, e);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (col + j < L.O) o[col + j] = e[j];
+      } else if (c < L.off_rd) {
+        const int cc = c - L.off_act;
+        const uint32_t e[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (cc + j < L.A) o_act[r * L.A + cc + j] = __uint_as_float(e[j]);
+      } else {
+        o_rew[r] = __uint_as_float(w.x);
+        o_done[r] = __uint_as_float(w.y);
+      }
+    }
+  }
+}
+
+// Generic fused gather for fp16 rings (records of more than one 16-B chunk per lane, unaligned tiles): the structure of
+// k_replay_gather_fused; an observation chunk holds 8 columns and takes two 16-B stores per destination tile.  1 / sd is staged
+// once per block as a double (norm_div: one double-precision product rounded once).
+template <bool HAS_NORM, int R, int CH>
+__global__ __launch_bounds__(256) void k_replay_gather_fused_f16(const uint32_t* __restrict__ records, RecLayoutH L,
+                                                                 int64_t capacity, const int64_t* __restrict__ idx, int64_t b,
+                                                                 const float* __restrict__ mean, const float* __restrict__ var,
+                                                                 float eps, int clamp5, float* __restrict__ x_sa, int64_t ld_sa,
+                                                                 float* __restrict__ xn_sa, float* __restrict__ xn_obs,
+                                                                 int64_t ld_o, float* __restrict__ o_rew,
+                                                                 float* __restrict__ o_done, int write_pads) {
+  __shared__ float s_mean[HAS_NORM ? GATHER_MAX_OBS : 1];
+  __shared__ double s_rd[HAS_NORM ? GATHER_MAX_OBS : 1];
+  if (HAS_NORM) {
+    for (int c = threadIdx.x; c < L.O; c += 256) {
+      s_mean[c] = mean[c];
+      s_rd[c] = 1.0 / (double)sqrtf(var[c] + eps);
+    }
+    __syncthreads();
+  }
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int nchunk = L.used >> 2;
+  const int A = L.A < 0 ? 0 : L.A;
+  const int sa_cols = L.O + A;
+  const bool act_aligned = (L.O & 3) == 0;
+  for (int64_t r0 = wave * R; r0 < b; r0 += nwaves * R) {
+    uint4 v[R][CH];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t r = r0 + i;
+      int64_t src = r < b ? idx[r] : 0;
+      if (src < 0 || src >= capacity) src = 0;  // never fault on a bad index
+      const uint4* rec4 = reinterpret_cast<const uint4*>(records + src * L.ld);
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        const int q = lane + 64 * c;
+        v[i][c] = q < nchunk ? rec4[q] : make_uint4(0u, 0u, 0u, 0u);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t r = r0 + i;
+      if (r >= b) break;
+      float* xs = x_sa ? x_sa + r * ld_sa : nullptr;
+      float* xns = xn_sa ? xn_sa + r * ld_sa : nullptr;
+      float* xno = xn_obs ? xn_obs + r * ld_o : nullptr;
+#pragma unroll
+      for (int cch = 0; cch < CH; ++cch) {
+        const int q = lane + 64 * cch;
+        if (q >= nchunk) continue;
+        const uint4 w = v[i][cch];
+        const int c = q << 2;
+        if (c < L.off_act) {  // obs / next_obs: 8 columns
+          const bool nx = c >= L.off_nobs;
+          const int col = (nx ? c - L.off_nobs : c) << 1;
+          float e[8];
+          widen8(w, e);
+          if (HAS_NORM) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              if (col + j < L.O) {
+                e[j] = norm_div(e[j] - s_mean[col + j], s_rd[col + j]);
+                if (clamp5) e[j] = fminf(fmaxf(e[j], -5.f), 5.f);
+              }
+          }
+          if (!nx) {
+            if (xs) { store4(xs, col, L.O, e, true); store4(xs, col + 4, L.O, e + 4, true); }
+            if (L.A < 0 && xno) { store4(xno, col, L.O, e, true); store4(xno, col + 4, L.O, e + 4, true); }
+          } else {
+            if (xns) { store4(xns, col, L.O, e, true); store4(xns, col + 4, L.O, e + 4, true); }
+            if (xno) { store4(xno, col, L.O, e, true); store4(xno, col + 4, L.O, e + 4, true); }
+          }
+        } else if (c < L.off_rd) {  // action -> columns O.. of the critic input
+          const int cc = c - L.off_act;
+          const float e[4] = {__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w)};
+          if (xs) store4(xs + L.O, cc, L.A, e, act_aligned);
+        } else {
+          if (o_rew) o_rew[r] = __uint_as_float(w.x);
+          if (o_done) o_done[r] = __uint_as_float(w.y);
+        }
+      }
+      if (!write_pads) continue;
+      // zero the pad columns so the GEMM K-loop can run over the padded width unchecked
+      for (int c = sa_cols + lane; c < ld_sa; c += 64) {
+        if (xs) xs[c] = 0.f;
+        if (xns) xns[c] = 0.f;
+      }
+      if (xno)
+        for (int c = L.O + lane; c < ld_o; c += 64) xno[c] = 0.f;
+    }
+  }
+}
+
+// k_replay_gather_fast for fp16 transition rings of more than 512 B in use (cfg #4, cfg #5): the same plan-once structure (field decode, destinations and normalisation
+// constants per lane once per kernel, R records in flight, scalar index loads one trip ahead).  A lane's 16-B chunk is either
+// 8 observation columns (widened, normalised, TWO 16-B stores per destination tile) or 4 raw fp32 words (action / reward, done).
+template <bool HAS_NORM, int R>
+__global__ __launch_bounds__(256) void k_replay_gather_fast_f16(const uint32_t* __restrict__ records, RecLayoutH L, int64_t capacity,
+                                                                const int64_t* __restrict__ idx, int64_t b,
+                                                                const float* __restrict__ mean, const float* __restrict__ var,
+                                                                float eps, int clamp5, float* __restrict__ x_sa, int64_t ld_sa,
+                                                                float* __restrict__ xn_sa, float* __restrict__ xn_obs, int64_t ld_o,
+                                                                float* __restrict__ o_rew, float* __restrict__ o_done, int write_pads,
+                                                                int nt_loads, int halves) {
+  typedef float f4n __attribute__((ext_vector_type(4)));
+  typedef uint32_t u4n __attribute__((ext_vector_type(4)));
+  const int lane = threadIdx.x & 63;
+  const int half = halves == 2 ? (threadIdx.x >> 6) & 1 : 0;   // records of 1-2 KiB: two waves per row, one chunk per lane
+  const int cl = lane + 64 * half;   // this lane's chunk of the record
+  const int c = cl << 2;             // its first word
+  const int nchunk = L.used >> 2;
+  // per-lane plan
+  float* dstA = nullptr;
+  float* dstB = nullptr;
+  int64_t ldA = 0, ldB = 0;
+  int ncol = -1;     // column of the normalisation constants, -1 = raw words
+  int nvalid = 4;    // logical columns in this chunk: up to 8 in an observation chunk, up to 4 in an action chunk
+  bool is_h = false, alignA = true, is_rd = false;
+  if (cl < nchunk) {
+    if (c < L.oh) {
+      ncol = c << 1; is_h = true;
+      dstA = x_sa ? x_sa + ncol : nullptr; ldA = ld_sa; nvalid = min(8, L.O - ncol);
+    } else if (c < L.off_act) {
+      ncol = (c - L.off_nobs) << 1; is_h = true;
+      dstA = xn_sa ? xn_sa + ncol : nullptr; ldA = ld_sa;
+      dstB = xn_obs ? xn_obs + ncol : nullptr; ldB = ld_o;
+      nvalid = min(8, L.O - ncol);
+    } else if (c < L.off_rd) {
+      const int cc = c - L.off_act;
+      dstA = x_sa ? x_sa + L.O + cc : nullptr; ldA = ld_sa; nvalid = min(4, L.A - cc);
+      alignA = (L.O & 3) == 0;   // action columns start at O: 16-B aligned only then
+    } else {
+      is_rd = true;
+    }
+  }
+  // Stores of a chunk: columns [0, 4) as one 16-B store when the destination is aligned and they are all valid, columns [4, 8) as a
+  // second one when all 8 are valid; whatever is left (the tail of a field whose width is no multiple of 4, or an action field that
+  // starts on an unaligned column) is ONE group of up to 4 scalar stores at column sbase.
+  const bool vec0 = alignA && nvalid >= 4, vec1 = is_h && nvalid == 8;
+  const int sbase = vec0 ? 4 : 0;
+  const int scnt = !vec0 ? min(nvalid, 4) : (is_h && nvalid < 8 ? nvalid - 4 : 0);
+  const int clq = cl < nchunk ? cl : 0;   // idle lanes re-read chunk 0 of the record (same line, nothing stored): unconditional loads
+  float mm[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  double rd[8] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};   // 1 / sd (norm_div)
+  const bool do_norm = HAS_NORM && is_h;
+  if (do_norm) {   // scalar loads: O need not be a multiple of 8; invalid tail elements keep (0, 1)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (j < nvalid) { mm[j] = mean[ncol + j]; rd[j] = 1.0 / (double)sqrtf(var[ncol + j] + eps); }
+  }
+  const int sa_cols = L.O + L.A;
+  const int npad_sa = (int)(ld_sa - sa_cols), npad_o = xn_obs ? (int)(ld_o - L.O) : 0;
+  const bool pad_vec = (sa_cols & 3) == 0 && (L.O & 3) == 0;
+
+  const int hs = halves - 1;
+  const int64_t wave = ((int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) >> hs;
+  const int64_t nwaves = ((int64_t)gridDim.x * 4) >> hs;
+  int64_t nsrc[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) nsrc[i] = wave * R + i < b ? idx[wave * R + i] : 0;
+  for (int64_t r0 = wave * R; r0 < b; r0 += nwaves * R) {
+    u4n v[R];
+    int64_t srcs[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) srcs[i] = nsrc[i];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t rn = r0 + nwaves * R + i;
+      nsrc[i] = rn < b ? idx[rn] : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      int64_t src = srcs[i];
+      if (src < 0 || src >= capacity) src = 0;
+      if (nt_loads & 1) v[i] = __builtin_nontemporal_load(reinterpret_cast<const u4n*>(records + src * L.ld) + clq);
+      else v[i] = reinterpret_cast<const u4n*>(records + src * L.ld)[clq];
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t r = r0 + i;
+      if (r >= b) break;
+      const u4n w = v[i];
+      float e[8];   // the chunk widened as 8 halves (meaningless, and unused, for a chunk of raw fp32 words)
+      e[0] = h_lo(w[0]); e[1] = h_hi(w[0]); e[2] = h_lo(w[1]); e[3] = h_hi(w[1]);
+      e[4] = h_lo(w[2]); e[5] = h_hi(w[2]); e[6] = h_lo(w[3]); e[7] = h_hi(w[3]);
+      if (do_norm) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = norm_div(e[j] - mm[j], rd[j]);
+        if (clamp5) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) e[j] = fminf(fmaxf(e[j], -5.f), 5.f);
+        }
+      }
+      // columns [0, 4): the widened halves of an observation chunk, else the chunk's own four words (selected as integers: copies)
+      float lo[4], sc[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        lo[j] = __uint_as_float(is_h ? __float_as_uint(e[j]) : w[j]);
+        sc[j] = sbase ? e[4 + j] : lo[j];
+      }
+      if (dstA) {
+        float* d = dstA + r * ldA;
+        if (vec0) {
+          if (nt_loads & 2) __builtin_nontemporal_store(f4n{lo[0], lo[1], lo[2], lo[3]}, reinterpret_cast<f4n*>(d));
+          else *reinterpret_cast<float4*>(d) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+        }
+        if (vec1) {
+          if (nt_loads & 2) __builtin_nontemporal_store(f4n{e[4], e[5], e[6], e[7]}, reinterpret_cast<f4n*>(d + 4));
+          else *reinterpret_cast<float4*>(d + 4) = make_float4(e[4], e[5], e[6], e[7]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < scnt) d[sbase + j] = sc[j];
+      }
+      if (dstB) {   // only observation chunks have a second destination (always 16-B aligned)
+        float* d = dstB + r * ldB;
+        if (vec0) *reinterpret_cast<float4*>(d) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+        if (vec1) *reinterpret_cast<float4*>(d + 4) = make_float4(e[4], e[5], e[6], e[7]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < scnt) d[sbase + j] = sc[j];
+      }
+      if (is_rd) {
+        if (o_rew) o_rew[r] = lo[0];
+        if (o_done) o_done[r] = lo[1];
+      }
+      if (!write_pads || half) continue;
+      if (pad_vec) {   // pads start on a 16-B boundary: one 16-B zero store per lane
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lane < (npad_sa >> 2)) {
+          if (x_sa) *reinterpret_cast<float4*>(x_sa + r * ld_sa + sa_cols + 4 * lane) = z4;
+          if (xn_sa) *reinterpret_cast<float4*>(xn_sa + r * ld_sa + sa_cols + 4 * lane) = z4;
+        }
+        if (lane < (npad_o >> 2)) *reinterpret_cast<float4*>(xn_obs + r * ld_o + L.O + 4 * lane) = z4;
+      } else {
+        if (lane < npad_sa) {
+          if (x_sa) x_sa[r * ld_sa + sa_cols + lane] = 0.f;
+          if (xn_sa) xn_sa[r * ld_sa + sa_cols + lane] = 0.f;
+        }
+        if (lane < npad_o) xn_obs[r * ld_o + L.O + lane] = 0.f;
+      }
+    }
+  }
+}
+
+// k_replay_gather_obs for fp16 obs-only rings whose record exceeds the 512 B of the 8-B-chunk kernel below (O = 257..512): P = 2^lgp
+// lanes per record, 16-B chunks, every index and record load unconditional, a lane's 8 columns and constants fixed.
+template <bool HAS_NORM, int R>
+__global__ __launch_bounds__(256) void k_replay_gather_obs_f16(const uint32_t* __restrict__ records, RecLayoutH L, int64_t capacity,
+                                                               const int64_t* __restrict__ idx, int64_t b,
+                                                               const float* __restrict__ mean, const float* __restrict__ var,
+                                                               float eps, int clamp5, float* __restrict__ x_sa, int64_t ld_sa,
+                                                               float* __restrict__ x_obs, int64_t ld_o, int write_pads, int lgp) {
+  const int lane = threadIdx.x & 63;
+  const int P = 1 << lgp, G = 64 >> lgp;
+  const int grp = lane >> lgp, cl = lane & (P - 1);   // record of the instruction, chunk of the record
+  const int c = cl << 3;                               // first column of the chunk
+  const int nchunk = L.used >> 2;
+  const bool active = cl < nchunk;
+  const int nvalid = active ? min(8, L.O - c) : 0;   // < 8 only in the last chunk when O is not a multiple of 8
+  float mm[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  double rd[8] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};   // 1 / sd (norm_div)
+  if (HAS_NORM && active) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (j < nvalid) { mm[j] = mean[c + j]; rd[j] = 1.0 / (double)sqrtf(var[c + j] + eps); }
+  }
+  const int64_t rows_trip = (int64_t)R * G;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int clq = active ? cl : 0;   // idle lanes re-read chunk 0 of their record: loads stay unconditional
+  int64_t nsrc[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) nsrc[i] = idx[min(wave * rows_trip + i * G + grp, b - 1)];
+  for (int64_t r0 = wave * rows_trip; r0 < b; r0 += nwaves * rows_trip) {
+    uint4 v[R];
+    int64_t srcs[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) srcs[i] = nsrc[i];
+#pragma unroll
+    for (int i = 0; i < R; ++i) nsrc[i] = idx[min(r0 + nwaves * rows_trip + i * G + grp, b - 1)];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      int64_t src = srcs[i];
+      src = (src < 0 || src >= capacity) ? 0 : src;   // never fault on a bad index
+      v[i] = reinterpret_cast<const uint4*>(records + src * L.ld)[clq];
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t r = r0 + i * G + grp;
+      if (r >= b) continue;
+      float e[8];
+      widen8(v[i], e);
+      if (HAS_NORM) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = norm_div(e[j] - mm[j], rd[j]);
+        if (clamp5) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) e[j] = fminf(fmaxf(e[j], -5.f), 5.f);
+        }
+      }
+      if (nvalid == 8) {
+        const float4 lo = make_float4(e[0], e[1], e[2], e[3]), hi = make_float4(e[4], e[5], e[6], e[7]);
+        if (x_sa) { float* d = x_sa + r * ld_sa + c; *reinterpret_cast<float4*>(d) = lo; *reinterpret_cast<float4*>(d + 4) = hi; }
+        if (x_obs) { float* d = x_obs + r * ld_o + c; *reinterpret_cast<float4*>(d) = lo; *reinterpret_cast<float4*>(d + 4) = hi; }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (j < nvalid) {
+            if (x_sa) x_sa[r * ld_sa + c + j] = e[j];
+            if (x_obs) x_obs[r * ld_o + c + j] = e[j];
+          }
+      }
+      if (!write_pads) continue;   // (the learners keep the pads zero themselves: PQLK_GATHER_PADS_ZERO)
+      if (x_sa)
+        for (int64_t k = L.O + cl; k < ld_sa; k += P) x_sa[r * ld_sa + k] = 0.f;
+      if (x_obs)
+        for (int64_t k = L.O + cl; k < ld_o; k += P) x_obs[r * ld_o + k] = 0.f;
+    }
+  }
+}
+
+// Narrow variants for fp16 records of at most 512 B in use (cfg #2's 424 B; every obs-only ring up to O = 256): a lane takes an 8-B
+// chunk -- 4 observation columns, or 2 raw fp32 words of the action / reward fields -- instead of a 16-B one.  Measured with 16-B
+// chunks (tools/bench_gather.py, profiles/replay_fp16_gather.json): a 512-B record keeps only 27 of a wave's 64 lanes busy, each
+// with 8 columns to normalise and two half-populated 16-B stores per tile, and the cfg #2 K-batch gather took 31 us against the
+// fp32 kernel's 24.  With 8-B chunks the lane -> column map, the arithmetic per lane and the stores (ONE fully populated 16-B store
+// per destination tile) are exactly those of k_replay_gather_fast / k_replay_gather_obs; only the loads are half as wide.
+__device__ __forceinline__ void widen4(uint32_t w0, uint32_t w1, float e[4]) {
+  e[0] = h_lo(w0); e[1] = h_hi(w0); e[2] = h_lo(w1); e[3] = h_hi(w1);
+}
+
+template <bool HAS_NORM, int R>
+__global__ __launch_bounds__(256) void k_replay_gather_fast_h8(const uint32_t* __restrict__ records, RecLayoutH L, int64_t capacity,
+                                                               const int64_t* __restrict__ idx, int64_t b,
+                                                               const float* __restrict__ mean, const float* __restrict__ var,
+                                                               float eps, int clamp5, float* __restrict__ x_sa, int64_t ld_sa,
+                                                               float* __restrict__ xn_sa, float* __restrict__ xn_obs, int64_t ld_o,
+                                                               float* __restrict__ o_rew, float* __restrict__ o_done, int write_pads,
+                                                               int nt_loads) {
+  typedef float f4n __attribute__((ext_vector_type(4)));
+  typedef uint32_t u2n __attribute__((ext_vector_type(2)));
+  const int lane = threadIdx.x & 63;
+  const int c = lane << 1;             // first word of this lane's 8-B chunk
+  const int nchunk = L.used >> 1;      // <= 64 (host)
+  // per-lane plan
+  float* dstA = nullptr;
+  float* dstB = nullptr;
+  int64_t ldA = 0, ldB = 0;
+  int ncol = -1;     // column of the normalisation constants, -1 = raw words
+  int nvalid = 0;    // logical columns in this chunk: up to 4 of an observation field, up to 2 of the action field
+  bool is_h = false, is_rd = false, act_even = false;
+  if (lane < nchunk) {
+    if (c < L.oh) {
+      ncol = c << 1; is_h = true;
+      dstA = x_sa ? x_sa + ncol : nullptr; ldA = ld_sa; nvalid = max(0, min(4, L.O - ncol));
+    } else if (c < L.off_act) {
+      ncol = (c - L.off_nobs) << 1; is_h = true;
+      dstA = xn_sa ? xn_sa + ncol : nullptr; ldA = ld_sa;
+      dstB = xn_obs ? xn_obs + ncol : nullptr; ldB = ld_o;
+      nvalid = max(0, min(4, L.O - ncol));
+    } else if (c < L.off_rd) {
+      const int cc = c - L.off_act;
+      dstA = x_sa ? x_sa + L.O + cc : nullptr; ldA = ld_sa; nvalid = max(0, min(2, L.A - cc));
+      act_even = (L.O & 1) == 0;   // action columns start at O: 8-B aligned only then
+    } else if (c == L.off_rd) {
+      is_rd = true;
+    }
+  }
+  const bool vec4 = is_h && nvalid == 4, vec2 = act_even && nvalid == 2;
+  const int scnt = (vec4 || vec2) ? 0 : nvalid;   // scalar stores: a field's tail, or an action field on an odd column
+  float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  double rd[4] = {1.0, 1.0, 1.0, 1.0};   // 1 / sd (norm_div)
+  const bool do_norm = HAS_NORM && is_h;
+  if (do_norm) {
+    float mm[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < nvalid) { mm[j] = mean[ncol + j]; rd[j] = 1.0 / (double)sqrtf(var[ncol + j] + eps); }
+    m4 = make_float4(mm[0], mm[1], mm[2], mm[3]);
+  }
+  const int sa_cols = L.O + L.A;
+  const int npad_sa = (int)(ld_sa - sa_cols), npad_o = xn_obs ? (int)(ld_o - L.O) : 0;
+  const bool pad_vec = (sa_cols & 3) == 0 && (L.O & 3) == 0;
+  const int clq = lane < nchunk ? lane : 0;   // idle lanes re-read chunk 0 (same line, nothing stored): unconditional loads
+
+  const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  int64_t nsrc[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) nsrc[i] = wave * R + i < b ? idx[wave * R + i] : 0;
+  for (int64_t r0 = wave * R; r0 < b; r0 += nwaves * R) {
+    u2n v[R];
+    int64_t srcs[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) srcs[i] = nsrc[i];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t rn = r0 + nwaves * R + i;
+      nsrc[i] = rn < b ? idx[rn] : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      int64_t src = srcs[i];
+      if (src < 0 || src >= capacity) src = 0;
+      if (nt_loads & 1) v[i] = __builtin_nontemporal_load(reinterpret_cast<const u2n*>(records + src * L.ld) + clq);
+      else v[i] = reinterpret_cast<const u2n*>(records + src * L.ld)[clq];
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t r = r0 + i;
+      if (r >= b) break;
+      const u2n w = v[i];
+      float e[4];   // the chunk widened as 4 halves (unused for a chunk of raw fp32 words)
+      widen4(w[0], w[1], e);
+      if (do_norm) {
+        e[0] = norm_div(e[0] - m4.x, rd[0]); e[1] = norm_div(e[1] - m4.y, rd[1]);
+        e[2] = norm_div(e[2] - m4.z, rd[2]); e[3] = norm_div(e[3] - m4.w, rd[3]);
+        if (clamp5) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = fminf(fmaxf(e[j], -5.f), 5.f);
+        }
+      }
+      // columns [0, 2): the widened halves of an observation chunk, else the chunk's own two words (selected as integers: copies)
+      const float lo0 = __uint_as_float(is_h ? __float_as_uint(e[0]) : w[0]);
+      const float lo1 = __uint_as_float(is_h ? __float_as_uint(e[1]) : w[1]);
+      const float sc[4] = {lo0, lo1, e[2], e[3]};
+      if (dstA) {
+        float* d = dstA + r * ldA;
+        if (vec4) {
+          if (nt_loads & 2) __builtin_nontemporal_store(f4n{e[0], e[1], e[2], e[3]}, reinterpret_cast<f4n*>(d));
+          else *reinterpret_cast<float4*>(d) = make_float4(e[0], e[1], e[2], e[3]);
+        }
+        if (vec2) *reinterpret_cast<float2*>(d) = make_float2(lo0, lo1);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (j < scnt) d[j] = sc[j];
+      }
+      if (dstB) {   // only observation chunks have a second destination
+        float* d = dstB + r * ldB;
+        if (vec4) *reinterpret_cast<float4*>(d) = make_float4(e[0], e[1], e[2], e[3]);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (j < scnt) d[j] = sc[j];
+      }
+      if (is_rd) {
+        if (o_rew) o_rew[r] = lo0;
+        if (o_done) o_done[r] = lo1;
+      }
+      if (!write_pads) continue;
+      if (pad_vec) {   // pads start on a 16-B boundary: one 16-B zero store per lane
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lane < (npad_sa >> 2)) {
+          if (x_sa) *reinterpret_cast<float4*>(x_sa + r * ld_sa + sa_cols + 4 * lane) = z4;
+          if (xn_sa) *reinterpret_cast<float4*>(xn_sa + r * ld_sa + sa_cols + 4 * lane) = z4;
+        }
+        if (lane < (npad_o >> 2)) *reinterpret_cast<float4*>(xn_obs + r * ld_o + L.O + 4 * lane) = z4;
+      } else {
+        if (lane < npad_sa) {
+          if (x_sa) x_sa[r * ld_sa + sa_cols + lane] = 0.f;
+          if (xn_sa) xn_sa[r * ld_sa + sa_cols + lane] = 0.f;
+        }
+        if (lane < npad_o) xn_obs[r * ld_o + L.O + lane] = 0.f;
+      }
+    }
+  }
+}
+
+template <bool HAS_NORM, int R>
+__global__ __launch_bounds__(256) void k_replay_gather_obs_h8(const uint32_t* __restrict__ records, RecLayoutH L, int64_t capacity,
+                                                              const int64_t* __restrict__ idx, int64_t b,
+                                                              const float* __restrict__ mean, const float* __restrict__ var,
+                                                              float eps, int clamp5, float* __restrict__ x_sa, int64_t ld_sa,
+                                                              float* __restrict__ x_obs, int64_t ld_o, int write_pads, int lgp) {
+  const int lane = threadIdx.x & 63;
+  const int P = 1 << lgp, G = 64 >> lgp;
+  const int grp = lane >> lgp, cl = lane & (P - 1);   // record of the instruction, 8-B chunk of the record
+  const int c = cl << 2;                               // first column of the chunk
+  const int nchunk = L.used >> 1;
+  const bool active = cl < nchunk;
+  const int nvalid = active ? max(0, min(4, L.O - c)) : 0;   // < 4 only in a field's last chunks (O no multiple of 8)
+  float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  double rd[4] = {1.0, 1.0, 1.0, 1.0};   // 1 / sd (norm_div)
+  if (HAS_NORM && active) {
+    float mm[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < nvalid) { mm[j] = mean[c + j]; rd[j] = 1.0 / (double)sqrtf(var[c + j] + eps); }
+    m4 = make_float4(mm[0], mm[1], mm[2], mm[3]);
+  }
+  const int64_t rows_trip = (int64_t)R * G;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int clq = active ? cl : 0;   // idle lanes re-read chunk 0 of their record: loads stay unconditional
+  int64_t nsrc[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) nsrc[i] = idx[min(wave * rows_trip + i * G + grp, b - 1)];
+  for (int64_t r0 = wave * rows_trip; r0 < b; r0 += nwaves * rows_trip) {
+    uint2 v[R];
+    int64_t srcs[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) srcs[i] = nsrc[i];
+#pragma unroll
+    for (int i = 0; i < R; ++i) nsrc[i] = idx[min(r0 + nwaves * rows_trip + i * G + grp, b - 1)];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      int64_t src = srcs[i];
+      src = (src < 0 || src >= capacity) ? 0 : src;   // never fault on a bad index
+      v[i] = reinterpret_cast<const uint2*>(records + src * L.ld)[clq];
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t r = r0 + i * G + grp;
+      if (r >= b) continue;
+      float e[4];
+      widen4(v[i].x, v[i].y, e);
+      if (HAS_NORM) {
+        e[0] = norm_div(e[0] - m4.x, rd[0]); e[1] = norm_div(e[1] - m4.y, rd[1]);
+        e[2] = norm_div(e[2] - m4.z, rd[2]); e[3] = norm_div(e[3] - m4.w, rd[3]);
+        if (clamp5) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = fminf(fmaxf(e[j], -5.f), 5.f);
+        }
+      }
+      if (nvalid == 4) {
+        const float4 x = make_float4(e[0], e[1], e[2], e[3]);
+        if (x_sa) *reinterpret_cast<float4*>(x_sa + r * ld_sa + c) = x;
+        if (x_obs) *reinterpret_cast<float4*>(x_obs + r * ld_o + c) = x;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < nvalid) {
+            if (x_sa) x_sa[r * ld_sa + c + j] = e[j];
+            if (x_obs) x_obs[r * ld_o + c + j] = e[j];
+          }
+      }
+      if (!write_pads) continue;   // (the learners keep the pads zero themselves: PQLK_GATHER_PADS_ZERO)
+      if (x_sa)
+        for (int64_t k = L.O + cl; k < ld_sa; k += P) x_sa[r * ld_sa + k] = 0.f;
+      if (x_obs)
+        for (int64_t k = L.O + cl; k < ld_o; k += P) x_obs[r * ld_o + k] = 0.f;
+    }
+  }
+}
+
+// ---- host side of the fp16 rings: the entry points above hand over here once they have checked the descriptor ----
+static int replay_insert_f16(const PqlReplayDesc* ring, int64_t dst_start, int64_t m, const float* obs, int64_t ld_obs,
+                             const float* act, int64_t ld_act, const float* rew, int64_t ld_rew, const float* next_obs,
+                             int64_t ld_nobs, const float* done, int64_t ld_done, pqlk_stream_t stream) {
+  RecLayoutH L = rec_layout_h(ring->obs_dim, ring->act_dim);
+  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
+  PQLK_REQUIRE(dst_start >= 0 && dst_start + m <= ring->capacity, PQLK_E_RANGE);
+  if (L.A >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
+  PQLK_REQUIRE(ld_obs >= L.O, PQLK_E_SHAPE);
+  if (m == 0) return PQLK_OK;
+  int64_t blocks = (m + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_replay_insert_f16, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream),
+                     reinterpret_cast<uint32_t*>(ring->records), L, dst_start, m, obs, ld_obs, act, ld_act, rew, ld_rew, next_obs,
+                     ld_nobs, done, ld_done);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
+static int replay_gather_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, float* obs, float* act, float* rew,
+                             float* next_obs, float* done, pqlk_stream_t stream) {
+  RecLayoutH L = rec_layout_h(ring->obs_dim, ring->act_dim);
+  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
+  if (L.A >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
+  if (b == 0) return PQLK_OK;
+  int64_t blocks = (b + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(k_replay_gather_f16, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream),
+                     reinterpret_cast<const uint32_t*>(ring->records), L, ring->capacity, idx, b, obs, act, rew, next_obs, done);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
+// The launch shapes (rows in flight, waves per CU, the two-waves-per-row split, the 192-MB non-temporal threshold) are those of the
+// fp32 path applied to the fp16 record: nchunk and the bytes read come from RecLayoutH, so e.g. cfg #4 (O = 211: 1792 -> 1024 B)
+// moves from the two-waves-per-row shape to one 16-B chunk per lane.  Records with at most 512 B in use (cfg #2, every obs-only ring
+// up to O = 256) go to the 8-B-chunk kernels (`narrow`), the rest to the 16-B-chunk ones: the choice follows from the record alone.
+static int replay_gather_fused_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, const float* mean, const float* var,
+                                   float eps, int flags, float* x_sa, int64_t ld_sa, float* xn_sa, float* xn_obs, int64_t ld_o,
+                                   float* rew, float* done, pqlk_stream_t stream) {
+  const int clamp5 = flags & PQLK_GATHER_CLAMP5;
+  const int write_pads = (flags & PQLK_GATHER_PADS_ZERO) ? 0 : 1;
+  const int tune_R = (flags >> 8) & 15, tune_wpc = (flags >> 12) & 63;
+  int nt_loads = ((flags & PQLK_GATHER_NT_LOADS) ? 1 : 0) | ((flags & PQLK_GATHER_NT_STORES) ? 2 : 0);
+  RecLayoutH L = rec_layout_h(ring->obs_dim, ring->act_dim);
+  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
+  PQLK_REQUIRE((mean == nullptr) == (var == nullptr), PQLK_E_NULL);
+  if (mean) PQLK_REQUIRE(L.O <= GATHER_MAX_OBS, PQLK_E_UNSUPPORTED);
+  if (x_sa || xn_sa) PQLK_REQUIRE(ld_sa % 32 == 0 && ld_sa >= L.O + (L.A < 0 ? 0 : L.A), PQLK_E_ALIGN);
+  if (xn_obs) PQLK_REQUIRE(ld_o % 32 == 0 && ld_o >= L.O, PQLK_E_ALIGN);
+  if (L.A < 0) PQLK_REQUIRE(xn_sa == nullptr, PQLK_E_UNSUPPORTED);
+  if (b == 0) return PQLK_OK;
+  const int nchunk = L.used >> 2;
+  PQLK_REQUIRE(nchunk <= 1024, PQLK_E_UNSUPPORTED);
+  const uint32_t* records = reinterpret_cast<const uint32_t*>(ring->records);
+  const hipStream_t st = pqlk_s(stream);
+  const bool fast = L.A >= 0 && nchunk <= 128 && (!write_pads || ((ld_sa - L.O - L.A) <= 64 && (!xn_obs || (ld_o - L.O) <= 64))) &&
+                    pqlk_aligned16(x_sa) && pqlk_aligned16(xn_sa) && pqlk_aligned16(xn_obs);
+  const bool narrow = (L.used >> 1) <= 64;   // at most 512 B in use: one 8-B chunk per lane (k_replay_gather_fast_h8 / _obs_h8)
+  if (fast) {
+    int R = 2;
+    if (tune_R == 1 || tune_R == 2 || tune_R == 4 || tune_R == 8) R = tune_R;
+    const int halves = nchunk > 64 ? 2 : 1;
+    const int rows_blk = 4 / halves * R;
+    int64_t fb = (b + rows_blk - 1) / rows_blk;
+    const int wpc = tune_wpc ? tune_wpc : 12;
+    if (fb > 256 * (int64_t)wpc / 4) fb = 256 * (int64_t)wpc / 4;
+    if (!tune_R && !tune_wpc && b * (int64_t)L.ld * 4 > ((int64_t)192 << 20)) nt_loads |= 1;   // bytes actually read
+    const dim3 g((unsigned)fb), t(256);
+    if (narrow) {
+#define PQLK_GATHER_FAST_H8(NORM, RR) \
+      hipLaunchKernelGGL((k_replay_gather_fast_h8<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
+                         x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads, nt_loads)
+#define PQLK_GATHER_FAST_H8_R(NORM) \
+      do { if (R == 1) PQLK_GATHER_FAST_H8(NORM, 1); else if (R == 2) PQLK_GATHER_FAST_H8(NORM, 2); else if (R == 4) PQLK_GATHER_FAST_H8(NORM, 4); \
+           else PQLK_GATHER_FAST_H8(NORM, 8); } while (0)
+      if (mean) PQLK_GATHER_FAST_H8_R(true); else PQLK_GATHER_FAST_H8_R(false);
+#undef PQLK_GATHER_FAST_H8_R
+#undef PQLK_GATHER_FAST_H8
+      PQLK_LAUNCH_CHECK();
+      return PQLK_OK;
+    }
+#define PQLK_GATHER_FAST_H(NORM, RR) \
+    hipLaunchKernelGGL((k_replay_gather_fast_f16<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
+                       x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads, nt_loads, halves)
+#define PQLK_GATHER_FAST_H_R(NORM) \
+    do { if (R == 1) PQLK_GATHER_FAST_H(NORM, 1); else if (R == 2) PQLK_GATHER_FAST_H(NORM, 2); else if (R == 4) PQLK_GATHER_FAST_H(NORM, 4); \
+         else PQLK_GATHER_FAST_H(NORM, 8); } while (0)
+    if (mean) PQLK_GATHER_FAST_H_R(true); else PQLK_GATHER_FAST_H_R(false);
+#undef PQLK_GATHER_FAST_H_R
+#undef PQLK_GATHER_FAST_H
+    PQLK_LAUNCH_CHECK();
+    return PQLK_OK;
+  }
+  if (L.A < 0 && nchunk <= 64 && pqlk_aligned16(x_sa) && pqlk_aligned16(xn_obs) && (x_sa || xn_obs)) {
+    const int nlane = narrow ? (L.used >> 1) : nchunk;   // lanes a record takes: 8-B chunks when they fit a wave, else 16-B chunks
+    int lgp = 0;
+    while ((1 << lgp) < nlane) ++lgp;
+    const int G = 64 >> lgp;
+    const int64_t groups = (b + G - 1) / G;
+    int R = groups >= 4 * 4096 ? 4 : (groups >= 2 * 4096 ? 2 : 1);
+    if (tune_R == 1 || tune_R == 2 || tune_R == 4) R = tune_R;
+    const int wpc = tune_wpc ? tune_wpc : 16;
+    int64_t fb = (groups + 4 * R - 1) / (4 * R);
+    if (fb > 256 * (int64_t)wpc / 4) fb = 256 * (int64_t)wpc / 4;
+    const dim3 g((unsigned)fb), t(256);
+    if (narrow) {
+#define PQLK_GATHER_OBS_H8(NORM, RR) \
+      hipLaunchKernelGGL((k_replay_gather_obs_h8<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
+                         x_sa, ld_sa, xn_obs, ld_o, write_pads, lgp)
+#define PQLK_GATHER_OBS_H8_R(NORM) \
+      do { if (R == 1) PQLK_GATHER_OBS_H8(NORM, 1); else if (R == 2) PQLK_GATHER_OBS_H8(NORM, 2); else PQLK_GATHER_OBS_H8(NORM, 4); } while (0)
+      if (mean) PQLK_GATHER_OBS_H8_R(true); else PQLK_GATHER_OBS_H8_R(false);
+#undef PQLK_GATHER_OBS_H8_R
+#undef PQLK_GATHER_OBS_H8
+      PQLK_LAUNCH_CHECK();
+      return PQLK_OK;
+    }
+#define PQLK_GATHER_OBS_H(NORM, RR) \
+    hipLaunchKernelGGL((k_replay_gather_obs_f16<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
+                       x_sa, ld_sa, xn_obs, ld_o, write_pads, lgp)
+#define PQLK_GATHER_OBS_H_R(NORM) \
+    do { if (R == 1) PQLK_GATHER_OBS_H(NORM, 1); else if (R == 2) PQLK_GATHER_OBS_H(NORM, 2); else PQLK_GATHER_OBS_H(NORM, 4); } while (0)
+    if (mean) PQLK_GATHER_OBS_H_R(true); else PQLK_GATHER_OBS_H_R(false);
+#undef PQLK_GATHER_OBS_H_R
+#undef PQLK_GATHER_OBS_H
+    PQLK_LAUNCH_CHECK();
+    return PQLK_OK;
+  }
+  const int rows_per_wave = nchunk <= 64 ? 4 : (nchunk <= 128 ? 2 : 1);
+  int64_t blocks = (b + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
+  if (blocks > 2048) blocks = 2048;
+#define PQLK_GF_H(NORM, R, CH)                                                                                                  \
+  hipLaunchKernelGGL((k_replay_gather_fused_f16<NORM, R, CH>), dim3((unsigned)blocks), dim3(256), 0, st, records, L, ring->capacity, \
+                     idx, b, mean, var, eps, clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads)
+#define PQLK_GF_H_N(NORM)                                     \
+  do {                                                        \
+    if (nchunk <= 64) PQLK_GF_H(NORM, 4, 1);                  \
+    else if (nchunk <= 128) PQLK_GF_H(NORM, 2, 2);            \
+    else if (nchunk <= 256) PQLK_GF_H(NORM, 1, 4);            \
+    else PQLK_GF_H(NORM, 1, 16);                              \
+  } while (0)
+  if (mean) PQLK_GF_H_N(true); else PQLK_GF_H_N(false);
+#undef PQLK_GF_H_N
+#undef PQLK_GF_H
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }

@@ -8,6 +8,12 @@ MI355X design: the five SoA tensors of the reference become one array of fixed-s
 aligned records (layout in include/pqlk.h) so that a uniform random sample touches the minimum number
 of HBM lines; `buf_obs`, `buf_action`, `buf_next_obs`, `buf_reward` are strided views into it and
 `buf_done` a bool view computed on access.  Insert and gather are single HIP launches.
+
+`reserve_space=True` (the reference's switch, simple_replay.py:9,15,91,94) or `obs_dtype=torch.float16` stores the two
+observation fields as float16 -- 512 B per record instead of 896 B at obs 88 / act 16.  The reference parks those tensors on
+the host because its GPU is small; here they stay in HBM.  Observations are rounded to nearest even once, at insert, and
+widened exactly by every gather: the ring behaves bit for bit like an fp32 ring fed `x.to(float16).to(float32)`.  fp16 and
+not bf16: it is the reference's dtype, and 8 significand bits are too coarse for raw, not yet normalised observations.
 """
 from __future__ import annotations
 
@@ -24,6 +30,26 @@ def _obs_width(obs_dim) -> int:
     if len(obs_dim) != 1:
         raise NotImplementedError("only flat observations are supported (the reference flattens them too)")
     return int(obs_dim[0])
+
+
+_OBS_DTYPES = {"float32": torch.float32, "float16": torch.float16}
+
+
+def parse_obs_dtype(value, key="obs_dtype") -> torch.dtype:
+    """torch.float32 / torch.float16, or their names as the config writes them (`algo.replay_obs_dtype`)."""
+    if isinstance(value, torch.dtype):
+        dt = value if value in _OBS_DTYPES.values() else None
+    else:
+        dt = _OBS_DTYPES.get(str(value))
+    if dt is None:
+        raise ValueError(f"{key} must be float32 or float16, got {value!r}")
+    return dt
+
+
+def cfg_obs_dtype(algo) -> torch.dtype:
+    """`algo.replay_obs_dtype` of a config node (absent: float32)."""
+    value = algo.get("replay_obs_dtype") if hasattr(algo, "get") else getattr(algo, "replay_obs_dtype", None)
+    return parse_obs_dtype("float32" if value is None else value, key="algo.replay_obs_dtype")
 
 
 def ring_plan(next_p: int, if_full: bool, capacity: int, m: int):
@@ -47,29 +73,44 @@ def ring_plan(next_p: int, if_full: bool, capacity: int, m: int):
 class RecordRing:
     """Device record array + descriptor shared by ReplayBuffer (A >= 0) and the P-learner obs ring (A = -1)."""
 
-    def __init__(self, capacity: int, obs_dim: int, act_dim: int, device):
+    def __init__(self, capacity: int, obs_dim: int, act_dim: int, device, obs_dtype=torch.float32):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise L.PqlkError(f"replay ring must live on a GPU (got {device}); pql_amd has no CPU path")
         self.capacity, self.O, self.A = int(capacity), int(obs_dim), int(act_dim)
-        self.rec_ld = int(L.lib.pqlk_replay_rec_ld(self.O, self.A))
+        self.obs_dtype = parse_obs_dtype(obs_dtype)
+        self.half = self.obs_dtype == torch.float16
+        code = L.OBS_F16 if self.half else L.OBS_F32
+        self.rec_ld = int(L.lib.pqlk_replay_rec_ld_ex(self.O, self.A, code))
+        # raw 4-byte words whatever the observation format (an fp16 field packs two columns per word): checkpoints stream them as is
         self.records = torch.zeros((self.capacity, self.rec_ld), dtype=torch.float32, device=self.device)
-        self.desc = L.PqlReplayDesc(self.records.data_ptr(), self.capacity, self.O, self.A, self.rec_ld, 0)
-        o4 = (self.O + 3) & ~3
-        self.off_nobs, self.off_act = o4, 2 * o4
-        self.off_rd = 2 * o4 + ((max(self.A, 0) + 3) & ~3)
+        self.desc = L.PqlReplayDesc(self.records.data_ptr(), self.capacity, self.O, self.A, self.rec_ld, code)
+        ow = ((self.O + 7) & ~7) // 2 if self.half else (self.O + 3) & ~3   # words of one observation field
+        self.off_nobs, self.off_act = ow, 2 * ow   # (word offsets; meaningful for a transition ring)
+        self.off_rd = 2 * ow + ((max(self.A, 0) + 3) & ~3)
         self.version = 0   # bumped by every insert: the learners' draws-ahead tiles are stamped with it (stale tiles are re-gathered)
+
+    def obs_view(self, next_obs=False):
+        """(capacity, O) strided view of the obs (or next_obs) field in its storage dtype."""
+        off = self.off_nobs if next_obs else 0
+        if self.half:
+            return self.records.view(torch.float16)[:, 2 * off: 2 * off + self.O]
+        return self.records[:, off: off + self.O]
 
     def rows(self, n):
         """Records [0, n) raw, pads included (a contiguous prefix of the record array): what a checkpoint streams."""
         return self.records[: int(n)]
 
     def training_state(self):
-        return {"capacity": self.capacity, "O": self.O, "A": self.A, "rec_ld": self.rec_ld, "version": int(self.version)}
+        return {"capacity": self.capacity, "O": self.O, "A": self.A, "rec_ld": self.rec_ld, "version": int(self.version),
+                "obs_dtype": "float16" if self.half else "float32"}
 
     def load_training_state(self, st):
         """Header check + version.  The caller then writes `rows(cur_capacity)` straight into the record array, which no
         `Tensor._version` sees: the version moves past the saved one so that tiles gathered ahead are re-gathered."""
+        have, saved = ("float16" if self.half else "float32"), str(st.get("obs_dtype", "float32"))   # (no key: written before fp16 rings)
+        if have != saved:
+            raise ValueError(f"replay ring: obs_dtype={have} but the checkpoint holds obs_dtype={saved}")
         for key in ("capacity", "O", "A", "rec_ld"):
             if int(st[key]) != getattr(self, key):
                 raise ValueError(f"replay ring: {key}={getattr(self, key)} but the checkpoint holds {key}={int(st[key])}")
@@ -94,21 +135,26 @@ class RecordRing:
 
 def create_buffer(capacity, obs_dim, action_dim, device="cuda", reserve_space=False):
     """Reference-shaped allocator (simple_replay.py:4-18): returns (obs, action, next_obs, reward, done).
-    Kept for callers that want plain SoA tensors; ReplayBuffer itself uses the record layout."""
-    if reserve_space:
-        raise NotImplementedError("reserve_space (fp16 host-side obs) is not used by PQL and not supported")
+    Kept for callers that want plain SoA tensors; ReplayBuffer itself uses the record layout.
+    reserve_space=True gives float16 obs / next_obs, as in the reference -- but on `device`: the reference puts the two tensors
+    on the host to spare a small GPU's memory, a 288-GB card keeps them in HBM where the gather reads them."""
     cap = (capacity,) if isinstance(capacity, int) else tuple(capacity)
     O = _obs_width(obs_dim)
     f = dict(dtype=torch.float32, device=device)
-    return (torch.empty((*cap, O), **f), torch.empty((*cap, int(action_dim)), **f), torch.empty((*cap, O), **f),
+    fo = dict(dtype=torch.float16 if reserve_space else torch.float32, device=device)
+    return (torch.empty((*cap, O), **fo), torch.empty((*cap, int(action_dim)), **f), torch.empty((*cap, O), **fo),
             torch.empty((*cap, 1), **f), torch.empty((*cap, 1), dtype=torch.bool, device=device))
 
 
 class ReplayBuffer:
     def __init__(self, capacity: int, obs_dim, action_dim: int, device="cuda", left_agent: bool = False,
-                 reserve_space: bool = False):
-        if left_agent or reserve_space:
-            raise NotImplementedError("left_agent / reserve_space belong to the bimanual fork variants, out of scope")
+                 reserve_space: bool = False, obs_dtype=None):
+        if left_agent:
+            raise NotImplementedError("left_agent belongs to the bimanual fork variants, out of scope")
+        # reserve_space=True is the reference's name for float16 observation storage; obs_dtype= says the same thing directly
+        obs_dtype = parse_obs_dtype(obs_dtype if obs_dtype is not None else (torch.float16 if reserve_space else torch.float32))
+        if reserve_space and obs_dtype != torch.float16:
+            raise ValueError(f"reserve_space=True means float16 observations, but obs_dtype={obs_dtype} was given")
         self.obs_dim = (obs_dim,) if isinstance(obs_dim, int) else tuple(obs_dim)
         self.action_dim = int(action_dim)
         self.device = torch.device(device)
@@ -116,7 +162,7 @@ class ReplayBuffer:
         self.if_full = False
         self.cur_capacity = 0
         self.capacity = int(capacity)
-        self.ring = RecordRing(self.capacity, _obs_width(obs_dim), self.action_dim, self.device)
+        self.ring = RecordRing(self.capacity, _obs_width(obs_dim), self.action_dim, self.device, obs_dtype=obs_dtype)
 
     # ---- reference-named views -------------------------------------------------------------
     @property
@@ -125,11 +171,11 @@ class ReplayBuffer:
 
     @property
     def buf_obs(self):
-        return self.ring.records[:, : self.ring.O]
+        return self.ring.obs_view()
 
     @property
     def buf_next_obs(self):
-        return self.ring.records[:, self.ring.off_nobs: self.ring.off_nobs + self.ring.O]
+        return self.ring.obs_view(next_obs=True)
 
     @property
     def buf_action(self):

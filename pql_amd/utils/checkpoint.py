@@ -233,12 +233,13 @@ def structure(cfg, obs_dim, act_dim):
             "algo.hidden_layers": None if hidden is None else [int(h) for h in hidden],
             "algo.act_class": str(algo.get("act_class")), "algo.cri_class": cri, "algo.distl": distl,
             "algo.num_atoms": int(algo.get("num_atoms") or 0) if distl else 0, "algo.nstep": int(algo.get("nstep") or 1),
-            "algo.memory_size": int(algo.get("memory_size") or 0)}
+            "algo.memory_size": int(algo.get("memory_size") or 0),
+            "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32")}
 
 
 def check_structure(saved, current, has_rings=True):
     for key, want in saved.items():
-        if key == "algo.memory_size" and not has_rings:
+        if key in ("algo.memory_size", "algo.replay_obs_dtype") and not has_rings:
             continue
         have = current.get(key)
         if isinstance(want, (list, tuple)):

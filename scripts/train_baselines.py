@@ -74,7 +74,8 @@ def main(cfg, on_finish=None):
     agent.reset_agent()
     is_off_policy = cfg.algo.name != "PPO"
     if is_off_policy:
-        memory = ReplayBuffer(capacity=int(cfg.algo.memory_size), obs_dim=agent.obs_dim, action_dim=agent.action_dim, device=cfg.device)
+        memory = ReplayBuffer(capacity=int(cfg.algo.memory_size), obs_dim=agent.obs_dim, action_dim=agent.action_dim, device=cfg.device,
+                              obs_dtype=agent.replay_obs_dtype)
         saved = None
         if opt["resume"] is not None:
             ckpt, saved = load_checkpoint(opt, cfg, env, agent, memory)

@@ -5,10 +5,13 @@ hooks of the flag word.  Two timings per point (HIP events around hipGraph repla
   iso  -- ONE launch at a time behind a 384-MB eviction write, rotating output-tile sets (bench.isolated_launch_ms: what the
           schedule pays, and what rocprofv3's per-launch durations show)
 GPU only.
-    python tools/bench_gather.py [cfg2|cfg5|cfg4|cfg2x8|cfg5x8|cfg4x8|p2|p2x4] ... [--quick] [--auto]
+    python tools/bench_gather.py [cfg2|cfg5|cfg4|cfg2x8|cfg5x8|cfg4x8|p2|p2x4] ... [--quick] [--auto] [--obs-dtype float16]
+--obs-dtype float32|float16: storage format of the ring's observations (algo.replay_obs_dtype); the `auto` line of every shape is
+also printed as one JSON line.
 A name may carry a ring size, `cfg5x8@150M` (rows; the 1-KiB records of cfg #5 x 150 M = 154 GB): the same launch over a ring that
 takes most of the card.  --auto: only the learner's own flag word (no sweep)."""
 import ctypes as C
+import json
 import os
 import sys
 
@@ -30,7 +33,7 @@ CFG = {"cfg2": (88, 16, 8192, 1_000_000), "cfg5": (108, 21, 32768, 5_000_000), "
 SETS, N_ISO = 4, 16
 
 
-def run(name, quick=False, iters=30, auto=False):
+def run(name, quick=False, iters=30, auto=False, obs_dtype="float32"):
     name, _, rows = name.partition("@")
     iters = max(4, min(iters, (1 << 23) // CFG[name][2]))   # (bound the index tensor for the 8-batch launches)
     O, A, B, cap = CFG[name]
@@ -39,13 +42,13 @@ def run(name, quick=False, iters=30, auto=False):
     dev = torch.device("cuda:0")
     obs_only = A < 0
     if obs_only:
-        ring = RecordRing(cap, O, -1, dev)
+        ring = RecordRing(cap, O, -1, dev, obs_dtype=obs_dtype)
     else:
-        rb = ReplayBuffer(cap, (O,), A, dev)
+        rb = ReplayBuffer(cap, (O,), A, dev, obs_dtype=obs_dtype)
         rb.cur_capacity, rb.if_full = cap, True
         ring = rb.ring
     if cap * ring.rec_ld * 4 < (8 << 30):
-        ring.records.normal_()
+        (ring.records.view(torch.float16) if ring.half else ring.records).normal_()
     else:   # (values do not matter to the timing; a 100-GB normal_ is 25 G Philox draws)
         ring.records.fill_(0.25)
     ld_sa, ld_o = L.ld(O + max(A, 16)), L.ld(O)
@@ -101,12 +104,22 @@ def run(name, quick=False, iters=30, auto=False):
                     ui = iso(flags=flags)
                     print(f"  R={R} waves/CU={wpc} nopad={nopad} nt={nt}: b2b {us:6.2f} us ({alg / us / 1e6 / 8:.3f} of 8 TB/s)   "
                           f"iso {ui:6.2f} us ({alg / ui / 1e6 / 8:.3f})   moved {real / ui / 1e6:5.2f} TB/s iso", flush=True)
-    print(f"  auto (learner flags 3): b2b {b2b(flags=3):6.2f} us   iso {iso(flags=3):6.2f} us ({alg / iso(flags=3) / 1e6 / 8:.3f})", flush=True)
-    print(f"  auto, no normalisation: b2b {b2b(False, 3):6.2f} us   iso {iso(False, 3):6.2f} us", flush=True)
+    a_b2b, a_iso = b2b(flags=3), iso(flags=3)
+    print(f"  auto (learner flags 3): b2b {a_b2b:6.2f} us   iso {a_iso:6.2f} us ({alg / a_iso / 1e6 / 8:.3f})", flush=True)
+    n_b2b, n_iso = b2b(False, 3), iso(False, 3)
+    print(f"  auto, no normalisation: b2b {n_b2b:6.2f} us   iso {n_iso:6.2f} us", flush=True)
+    print(json.dumps({"shape": name, "obs": O, "act": A, "rows": B, "ring_rows": cap, "obs_dtype": obs_dtype, "record_bytes": ring.rec_ld * 4,
+                      "moved_mb": round(real / 1e6, 2), "auto_b2b_us": round(a_b2b, 2), "auto_iso_us": round(a_iso, 2),
+                      "auto_nonorm_b2b_us": round(n_b2b, 2), "auto_nonorm_iso_us": round(n_iso, 2)}), flush=True)
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv, dtype = sys.argv[1:], "float32"
+    if "--obs-dtype" in argv:
+        i = argv.index("--obs-dtype")
+        dtype = argv[i + 1]
+        del argv[i: i + 2]
+    args = [a for a in argv if not a.startswith("--")]
     for n in (args or ["cfg2", "cfg5"]):
-        run(n, quick="--quick" in sys.argv, auto="--auto" in sys.argv)
+        run(n, quick="--quick" in argv, auto="--auto" in argv, obs_dtype=dtype)
         torch.cuda.empty_cache()

@@ -14,6 +14,7 @@ controller a = clamp(4 (g - x) - 4 v, -1, 1) (R_pd), the gap fraction f = (R - R
 
     python tools/learn_pointmass.py --out profiles/pointmass_learning.json
     python tools/learn_pointmass.py --algos ddpg --shapes small --seeds 1 --iters 200      # a quick look
+    python tools/learn_pointmass.py --override algo.replay_obs_dtype=float16 --out profiles/pointmass_learning_fp16.json
 """
 import argparse
 import importlib.util
@@ -51,7 +52,7 @@ def script(name):
     return _SCRIPTS[name]
 
 
-def overrides(algo, shape, seed, iters, run_dir):
+def overrides(algo, shape, seed, iters, run_dir, extra=()):
     sh = SHAPES[shape]
     n = sh["num_envs"]
     ov = [*ALGOS[algo][1], "task=pointmass", f"task.obs_dim={sh['obs_dim']}", f"task.act_dim={sh['act_dim']}",
@@ -59,7 +60,7 @@ def overrides(algo, shape, seed, iters, run_dir):
           f"algo.memory_size={(WARM_UP + iters + 8) * n}", f"seed={seed}", f"max_step={(WARM_UP + iters) * n - 1}", f"+logging.dir={run_dir}"]
     if sh["hidden"] is not None:
         ov.append(f"algo.hidden_layers={sh['hidden']}")
-    return ov
+    return ov + list(extra)
 
 
 def yardsticks(shape, seed, device="cuda:0"):
@@ -69,8 +70,9 @@ def yardsticks(shape, seed, device="cuda:0"):
     return env, episode_return(env, zero_policy(env)), episode_return(env, pd_policy(env))
 
 
-def run(algo, shape, seed, iters):
-    """One training run through the entry point's own `main`; the policy is evaluated by its `on_finish` hook."""
+def run(algo, shape, seed, iters, extra=()):
+    """One training run through the entry point's own `main`; the policy is evaluated by its `on_finish` hook.
+    extra: further config overrides, e.g. ("algo.replay_obs_dtype=float16",)."""
     env, r_zero, r_pd = yardsticks(shape, seed)
     got = {}
 
@@ -79,7 +81,7 @@ def run(algo, shape, seed, iters):
         got["R"] = episode_return(env, lambda obs: agent.get_actions(obs, sample=False))
 
     with tempfile.TemporaryDirectory() as run_dir:   # (the PQL loop's evaluator keeps its best model there)
-        cfg = load_cfg(overrides(algo, shape, seed, iters, run_dir))
+        cfg = load_cfg(overrides(algo, shape, seed, iters, run_dir, extra))
         torch.cuda.synchronize()
         t0 = time.time()
         res = script(ALGOS[algo][0]).main(cfg, on_finish=evaluate)
@@ -88,7 +90,7 @@ def run(algo, shape, seed, iters):
     done_iters = res["iters"] if algo == "ddpg" else res["rollout_iterations"]
     assert done_iters == iters, (done_iters, iters)
     updates = iters * int(cfg.algo.update_times) if algo == "ddpg" else int(res["critic_updates"])
-    return dict(algo=algo, shape=shape, seed=seed, iters=iters, critic_updates=updates, R=got["R"], R_zero=r_zero, R_pd=r_pd,
+    return dict(algo=algo, shape=shape, seed=seed, iters=iters, **({"overrides": list(extra)} if extra else {}), critic_updates=updates, R=got["R"], R_zero=r_zero, R_pd=r_pd,
                 f=(got["R"] - r_zero) / (r_pd - r_zero), wall_s=round(wall, 2))
 
 
@@ -118,11 +120,12 @@ def main():
     ap.add_argument("--seeds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=1000, help="rollout iterations per run (8 critic updates each)")
     ap.add_argument("--curve", default=None, help="comma-separated iteration counts: DDPG at the small shape, every seed, at each of them")
+    ap.add_argument("--override", action="append", default=[], help="a further config override for every run (repeatable)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "learn_pointmass needs a GPU"
     out = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, episode_length=EPISODE_LENGTH, eval_envs=EVAL_ENVS,
-               shapes=SHAPES, env_step=env_step_time(), runs=[], curve=[])
+               shapes=SHAPES, overrides=list(a.override), env_step=env_step_time(), runs=[], curve=[])
     print(json.dumps(out["env_step"]), flush=True)
 
     def record(key, r):
@@ -135,10 +138,10 @@ def main():
     for algo in a.algos.split(","):
         for shape in a.shapes.split(","):
             for seed in range(a.seeds):
-                record("runs", run(algo, shape, seed, a.iters))
+                record("runs", run(algo, shape, seed, a.iters, tuple(a.override)))
     for iters in ([int(x) for x in a.curve.split(",")] if a.curve else []):
         for seed in range(a.seeds):
-            record("curve", run("ddpg", "small", seed, iters))
+            record("curve", run("ddpg", "small", seed, iters, tuple(a.override)))
 
 
 if __name__ == "__main__":
