@@ -218,6 +218,27 @@ int pqlk_mlp_forward(const PqlMlpDesc* d, const float* params, const float* pack
                      int32_t out_act, const float* draw, float noise_std, float noise_clip,
                      float* acts, float* out2, int64_t ld_out2, pqlk_stream_t stream);
 
+/* Forward-only stack on bf16 MFMA (pql_amd/csrc/fwd_bf16.hip): the V-learner's no-gradient target forwards with
+ * algo.target_dtype=bfloat16.  The law, for every net: x~ = bf16(x[:, :dims[0]]) and W~_l = bf16(W_l) for EVERY layer, both round
+ * to nearest even; z_l = sum_k a~_{l-1,k} W~_l[j,k] + b_l[j] accumulated in fp32 with fp32 biases; hidden a_l = bf16(elu(z_l)) with
+ * the fp32 ELU of the fused path; the output layer's z stays fp32, gets `out_act` in fp32 exactly as pqlk_mlp_forward and is written
+ * as fp32 with zero pad columns.  NaN / Inf propagate; a row's bits depend on neither b, its position, nor the launch.
+ * Eligible (pqlk_mlp_bf16_ok): n_layers >= 2, hidden widths multiples of 32 and <= 1024, output width <= 64, and an input
+ * width whose two 32-row bf16 images fit 160 KB of LDS (<= 1264).
+ *   packed[net][layer][tile n/32][k/16][lane = 32 h + r][j] = bf16(W[32 tile + r][16 (k/16) + 8 h + j]),
+ * every layer, K padded to 16 and N to 32 with zeros: pqlk_mlp_packed_bf16_elems() uint16 elements (0 when not eligible).  Call
+ * pqlk_mlp_pack_bf16() (one launch) whenever the arena changes.  pqlk_mlp_forward_bf16: `params` supplies the biases; x, ldx, b,
+ * out_act, draw, the noise arguments, out2 / ld_out2 as pqlk_mlp_forward; out is the (n_nets, b, pqlk_ld(out)) output block alone.
+ * Columns [dims[0], ldx) of x are ignored, and out2 may point into the rows of x that the same call reads (the policy writes its
+ * actions into the action columns of its own input tile).  PQLK_E_UNSUPPORTED when the descriptor is not eligible. */
+int pqlk_mlp_bf16_ok(const PqlMlpDesc* d);                 /* 1 / 0 */
+int64_t pqlk_mlp_packed_bf16_elems(const PqlMlpDesc* d);   /* uint16 elements; 0 when not ok */
+int pqlk_mlp_pack_bf16(const PqlMlpDesc* d, const float* params, uint16_t* packed, pqlk_stream_t stream);
+int pqlk_mlp_forward_bf16(const PqlMlpDesc* d, const float* params, const uint16_t* packed,
+                          const float* x, int64_t ldx, int64_t b,
+                          int32_t out_act, const float* draw, float noise_std, float noise_clip,
+                          float* out, float* out2, int64_t ld_out2, pqlk_stream_t stream);
+
 /* Backward.  dy: (n_nets, B, pqlk_ld(out)) gradient w.r.t. the last layer's PRE-activation output
  * (loss kernels below produce exactly that).  grads (arena layout) is overwritten with the full
  * parameter gradient when != NULL (deterministic split-batch partial sums through `ws`).

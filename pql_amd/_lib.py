@@ -53,6 +53,10 @@ PROTOTYPES = {
     "pqlk_mlp_packed_floats": (_I64, [C.POINTER(PqlMlpDesc)]),
     "pqlk_mlp_pack": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P]),
     "pqlk_mlp_forward": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I32, _P, _I64, _I64, _I32, _P, _F, _F, _P, _P, _I64, _P]),
+    "pqlk_mlp_bf16_ok": (C.c_int, [C.POINTER(PqlMlpDesc)]),
+    "pqlk_mlp_packed_bf16_elems": (_I64, [C.POINTER(PqlMlpDesc)]),
+    "pqlk_mlp_pack_bf16": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P]),
+    "pqlk_mlp_forward_bf16": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _I64, _I64, _I32, _P, _F, _F, _P, _P, _I64, _P]),
     "pqlk_mlp_backward": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _P, _I64,
                                     _P, _I64, _P]),
     "pqlk_mlp_backward_norm": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _P, _I64,

@@ -22,7 +22,7 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
                                   graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
-from pql_amd.models.mlp import PackedWeights, default_splits, mlp_forward_raw, output_view
+from pql_amd.models.mlp import HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_forward_bf16_raw, mlp_forward_raw, output_view
 from pql_amd.replay.simple_replay import ReplayBuffer, cfg_obs_dtype
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
@@ -63,6 +63,51 @@ class PQLVLearner(Learner):
                 self._buckets = DP.layer_buckets(self.critic.layout.n_layers)
                 self._reducer = DP.BucketAllReduce(self.pg)
         self._depth = max(1, int(_cfg_get(algo, "prefetch_steps", _cfg_get(algo, "critic_sample_ratio", 8))))
+        self.pk_target_bf16 = self.pk_actor_bf16 = None
+        self._bf16 = False
+        self.set_target_dtype(_cfg_get(algo, "target_dtype", "float32"))
+
+    def set_target_dtype(self, value):
+        """algo.target_dtype: float32 (default) = the two no-gradient forwards of a step -- target policy, target twin critic --
+        run on the fp32 kernels like everything else; bfloat16 = on the forward-only bf16-MFMA stack (pql_amd/csrc/fwd_bf16.hip:
+        inputs, weights and hidden activations rounded to bf16, fp32 accumulation, biases and output).  Nothing that
+        carries a gradient changes.  A shape the bf16 stack cannot take, or algo.fused=False, is an error: no silent fall-back."""
+        value = str(value)
+        if value not in ("float32", "bfloat16"):
+            raise ValueError(f"algo.target_dtype must be float32 or bfloat16, got {value!r}")
+        if value == "bfloat16":
+            if not self._fused:
+                raise ValueError("algo.target_dtype=bfloat16 needs the fused path (algo.fused=True)")
+            hidden = _cfg_get(self.cfg.algo, "hidden_layers")
+            O = self.obs_dim[0] if isinstance(self.obs_dim, (tuple, list)) else self.obs_dim
+            a_dims = [int(O), *(HIDDEN_DEFAULT if hidden is None else hidden), self.action_dim]
+            for name, desc, dims in (("critic", self.critic.layout.desc, self.critic.layout.dims), ("actor", L.mlp_desc(a_dims, 1), a_dims)):
+                if not L.lib.pqlk_mlp_bf16_ok(C.byref(desc)):
+                    raise ValueError(f"algo.target_dtype=bfloat16: the {name}'s layers {list(dims)} do not fit the bf16 forward (>= 2 "
+                                     f"layers, hidden widths multiples of 32 and <= 1024, output width <= 64)")
+            self.pk_target_bf16 = PackedWeightsBf16(self.critic.layout, self.device)
+        else:
+            self.pk_target_bf16 = None
+        self.pk_actor_bf16 = None
+        self._bf16 = value == "bfloat16"
+        self._ws, self._graph, self._graph_post, self._graph_key, self._slot_graphs, self._run_graph = None, None, None, None, {}, None
+        self._drop_ahead()
+        if self._bf16:
+            with torch.cuda.device(self.device):
+                self._repack_bf16()
+
+    def _repack_bf16(self):
+        """The bf16 weight copies of the two target networks, re-derived from their arenas."""
+        self.pk_target_bf16.refresh(self.critic_target.arena.data)
+        if self.actor is not None:
+            if self.pk_actor_bf16 is None or self.pk_actor_bf16.layout is not self.actor.layout:
+                self.pk_actor_bf16 = PackedWeightsBf16(self.actor.layout, self.device)
+            self.pk_actor_bf16.refresh(self.actor.arena.data)
+
+    def _actor_in_sa(self):
+        """Whether the target policy reads norm(next_obs) straight out of the target critic's input tile (its kernel masks
+        everything past column O while staging): the fused fp32 forward and the bf16 forward do."""
+        return self._bf16 or (self.pk_actor is not None and self.pk_actor.tensor is not None)
 
     def _bound(self):
         return self.memory.cur_capacity
@@ -148,7 +193,7 @@ class PQLVLearner(Learner):
     def _want_ahead(self):
         """Fused draws + batched gather: needs the fused actor forward (it reads norm(next_obs) out of the target critic's input
         tile, so a step's inputs are exactly two tiles), draws outside the graphs, and torch's numbers reproduced on this device."""
-        return self.pk_actor is not None and self.pk_actor.tensor is not None and super()._want_ahead()
+        return self._actor_in_sa() and super()._want_ahead()
 
     def repack(self):
         """Re-derive the fragment-ordered weight copies from the arenas (after loading a state_dict etc.)."""
@@ -157,13 +202,15 @@ class PQLVLearner(Learner):
             self.pk_target.refresh(self.critic_target.arena.data)
             if self.pk_actor is not None:
                 self.pk_actor.refresh(self.actor.arena.data)
+            if self._bf16:
+                self._repack_bf16()
 
     def _gather(self, ws, idx, rows, x_sa, xn_sa, rew, done):
         """Fused replay gather (+ normalise + concat) of `rows` samples into the given tiles."""
         mean, var, eps = self._norm_ptrs()
         # the fused actor forward masks everything past column O while staging its tile, so it can read norm(next_obs)
         # straight out of the target critic's input tile: one gather output (B x ld(O) floats) less to write
-        actor_in_sa = self.pk_actor is not None and self.pk_actor.tensor is not None
+        actor_in_sa = self._actor_in_sa()
         L.check(L.lib.pqlk_replay_gather_fused(C.byref(self.memory.ring.desc), L.ptr(idx), rows, L.ptr(mean), L.ptr(var), eps, GATHER_FLAGS,
                                                L.ptr(x_sa), ws["ld_sa"], L.ptr(xn_sa), None if actor_in_sa else L.ptr(ws["xn_obs"]),
                                                ws["ld_o"], L.ptr(rew), L.ptr(done), L.stream(self.device)))
@@ -181,8 +228,13 @@ class PQLVLearner(Learner):
         if ws["actor_ahead"]:   # a' = clamp(tanh(actor(s')) + clamp(0.8 N(0,1), +-0.2), +-1) of all K steps -> action columns of their tiles
             algo, O = self.cfg.algo, self.memory.ring.O
             xn = ws["xn_sa_all"].view(K * B, ws["ld_sa"])[: Kp * B]
-            mlp_forward_raw(self.actor.layout, self.actor.arena.data, xn, L.ACT_TANH_NOISE, self._ahead.normal.view(K * B, -1)[: Kp * B],
-                            algo.noise.tgt_pol_std, algo.noise.tgt_pol_noise_bound, ws["a_out_all"], xn[:, O:], packed=self.pk_actor, stash_all=2)
+            draws = self._ahead.normal.view(K * B, -1)[: Kp * B]
+            if self._bf16:
+                mlp_forward_bf16_raw(self.actor.layout, self.actor.arena.data, self.pk_actor_bf16, xn, L.ACT_TANH_NOISE, draws,
+                                     algo.noise.tgt_pol_std, algo.noise.tgt_pol_noise_bound, ws["a_out_all"], xn[:, O:])
+            else:
+                mlp_forward_raw(self.actor.layout, self.actor.arena.data, xn, L.ACT_TANH_NOISE, draws,
+                                algo.noise.tgt_pol_std, algo.noise.tgt_pol_noise_bound, ws["a_out_all"], xn[:, O:], packed=self.pk_actor, stash_all=2)
         self._ahead_stamp = self._data_stamp()
 
     def _step_kernels(self, ws, idx, draw, upto_backward=False, tiles=None, part=None):
@@ -194,7 +246,7 @@ class PQLVLearner(Learner):
         algo, dev, B = self.cfg.algo, self.device, ws["B"]
         O = self.memory.ring.O
         st = L.stream(dev)
-        actor_in_sa = self.pk_actor is not None and self.pk_actor.tensor is not None
+        actor_in_sa = self._actor_in_sa()
         tiles_ahead = tiles is not None
         if tiles is None:
             tiles = ws["slots"][0]
@@ -210,11 +262,20 @@ class PQLVLearner(Learner):
             # target policy smoothing (:63-71): a' written into the action columns of the target critic's input.
             # The two no-grad chains (actor, target critic) skip the activation stash; the critic keeps it for backward.
             xn_act = ws["xn_sa"][:, O:]
-            if not (tiles_ahead and ws["actor_ahead"]):   # (tiles gathered ahead already hold a': _prefetch)
+            if tiles_ahead and ws["actor_ahead"]:   # (tiles gathered ahead already hold a': _prefetch)
+                pass
+            elif self._bf16:   # (acts_a: only its first B x ld(A) floats, the output block, are written)
+                mlp_forward_bf16_raw(al, self.actor.arena.data, self.pk_actor_bf16, ws["xn_sa"], L.ACT_TANH_NOISE, draw, algo.noise.tgt_pol_std,
+                                     algo.noise.tgt_pol_noise_bound, ws["acts_a"], xn_act)
+            else:
                 mlp_forward_raw(al, self.actor.arena.data, ws["xn_sa"] if actor_in_sa else ws["xn_obs"], L.ACT_TANH_NOISE, draw, algo.noise.tgt_pol_std,
                                 algo.noise.tgt_pol_noise_bound, ws["acts_a"], xn_act, packed=self.pk_actor, stash_all=False)
-            mlp_forward_raw(cl, self.critic_target.arena.data, ws["xn_sa"], L.ACT_NONE, acts=ws["acts_t"], packed=self.pk_target,
-                            stash_all=False)
+            if self._bf16:   # the target Q lands where the loss / the TD head read it: the output block of the target's stash
+                mlp_forward_bf16_raw(cl, self.critic_target.arena.data, self.pk_target_bf16, ws["xn_sa"], L.ACT_NONE,
+                                     out=output_view(cl, ws["acts_t"], B))
+            else:
+                mlp_forward_raw(cl, self.critic_target.arena.data, ws["xn_sa"], L.ACT_NONE, acts=ws["acts_t"], packed=self.pk_target,
+                                stash_all=False)
             if ws["td_fwd"] > 0:
                 L.check(L.lib.pqlk_mlp_forward_td(C.byref(cl.desc), L.ptr(self.critic.arena.data), L.ptr(self.pk_critic.tensor), L.ptr(ws["x_sa"]),
                                                   ws["ld_sa"], B, L.ptr(ws["acts_c"]), L.ptr(ws["acts_t"]), L.ptr(ws["rew"]), L.ptr(ws["done"]),
@@ -279,6 +340,11 @@ class PQLVLearner(Learner):
         self._step_post(ws)
 
     def _step_post(self, ws):
+        self._optimizer(ws)
+        if self._bf16:   # the Polyak step moved the target: its bf16 copy follows in one launch, inside the captured step
+            self.pk_target_bf16.refresh(self.critic_target.arena.data)
+
+    def _optimizer(self, ws):
         algo, dev = self.cfg.algo, self.device
         if self._fold_loss:
             K = int(algo.num_atoms) if algo.distl else 1
@@ -338,6 +404,8 @@ class PQLVLearner(Learner):
 
     def set_actor(self, actor, home=None):
         self._adopt_partner(actor, home)
+        if self._bf16:
+            self._repack_bf16()
 
     @torch.no_grad()
     def update(self, actor, trajectory, normalize_tuple, sleep_time):

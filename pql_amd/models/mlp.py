@@ -123,6 +123,39 @@ def mlp_forward_raw(layout: ArenaLayout, arena, x_pad, out_act=L.ACT_NONE, draw=
     return acts
 
 
+class PackedWeightsBf16:
+    """Fragment-ordered bf16 copy of EVERY layer's weights, output layer included, for the forward-only bf16-MFMA stack
+    (pqlk_mlp_pack_bf16; `algo.target_dtype=bfloat16`).  `tensor` holds the bf16 bit patterns as int16.  A layout the bf16 stack
+    cannot take is a ValueError here: there is no fall-back.  refresh() must run after every change of the arena."""
+
+    def __init__(self, layout: ArenaLayout, device):
+        if not L.lib.pqlk_mlp_bf16_ok(C.byref(layout.desc)):
+            raise ValueError(f"the bf16 forward needs >= 2 layers, hidden widths that are multiples of 32 and <= 1024, and an "
+                             f"output width <= 64; got dims {layout.dims}")
+        self.layout = layout
+        self.tensor = torch.zeros(int(L.lib.pqlk_mlp_packed_bf16_elems(C.byref(layout.desc))), dtype=torch.int16, device=device)
+
+    def refresh(self, arena):
+        with torch.cuda.device(arena.device):
+            L.check(L.lib.pqlk_mlp_pack_bf16(C.byref(self.layout.desc), L.ptr(arena), L.ptr(self.tensor), L.stream(arena.device)))
+        return self
+
+
+def mlp_forward_bf16_raw(layout: ArenaLayout, arena, packed: PackedWeightsBf16, x_pad, out_act=L.ACT_NONE, draw=None, noise_std=0.0,
+                         noise_clip=0.0, out=None, out2=None):
+    """Launch the forward-only bf16 stack (the law: include/pqlk.h); returns the (n_nets, B, ld_out) fp32 output block.
+    `arena` supplies the fp32 biases, `packed` (refreshed from the same arena) the bf16 weights."""
+    B = x_pad.shape[0]
+    dev = x_pad.device
+    if out is None:
+        out = torch.empty((layout.n_nets, B, layout.ld_out), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib.pqlk_mlp_forward_bf16(C.byref(layout.desc), L.ptr(arena), L.ptr(packed.tensor), L.ptr(x_pad), x_pad.stride(0), B,
+                                            out_act, L.ptr(draw), float(noise_std), float(noise_clip), L.ptr(out), L.ptr(out2),
+                                            out2.stride(0) if out2 is not None else 0, L.stream(dev)))
+    return out
+
+
 def output_view(layout: ArenaLayout, acts, B):
     off, ld = layout.act_offset(B, 0, layout.n_layers - 1)
     return acts[off: off + layout.n_nets * B * ld].view(layout.n_nets, B, ld)

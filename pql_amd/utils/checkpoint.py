@@ -234,10 +234,13 @@ def structure(cfg, obs_dim, act_dim):
             "algo.act_class": str(algo.get("act_class")), "algo.cri_class": cri, "algo.distl": distl,
             "algo.num_atoms": int(algo.get("num_atoms") or 0) if distl else 0, "algo.nstep": int(algo.get("nstep") or 1),
             "algo.memory_size": int(algo.get("memory_size") or 0),
-            "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32")}
+            "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32"),
+            # (the V-learner's target forwards: bf16 targets change every later step, so a run resumes in the dtype it was saved in)
+            "algo.target_dtype": str(algo.get("target_dtype") or "float32")}
 
 
 def check_structure(saved, current, has_rings=True):
+    saved = {"algo.target_dtype": "float32", **saved}   # (a checkpoint from before the key existed was written with float32 targets)
     for key, want in saved.items():
         if key in ("algo.memory_size", "algo.replay_obs_dtype") and not has_rings:
             continue

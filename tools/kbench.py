@@ -4,7 +4,9 @@
     python tools/kbench.py [--variants "base;td=0;rng=torch"] [--rounds 5] [--sections actor,target,critic,bwd,opt,vstep,pstep] [bench.py flags ...]
 
 A variant is a comma-separated list of learner settings (`td=0|1`: TD loss inside the head backward or as its own launch;
-`rng=auto|torch`: draws ahead + batched gather or per-step ATen draws; `env:NAME=value`: an environment switch the library reads
+`rng=auto|torch`: draws ahead + batched gather or per-step ATen draws; `tdtype=float32|bfloat16`: `algo.target_dtype`, the target
+policy / target critic forwards (sections actor, target, actor8 = the K-batch policy forward, pack16 = the bf16 re-pack) on the fp32
+kernels or on the bf16-MFMA stack; `env:NAME=value`: an environment switch the library reads
 per call).  Every section is timed for every variant in every round (cdna_hip_programming.md rule 24: deltas come from
 interleaved rounds in ONE process); the table prints median and min per (section, variant).  Kernel-level experiments of a tuning
 round are built as a second variant behind a temporary switch and compared here; the switch goes once a variant is chosen
@@ -21,7 +23,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from pql_amd import _lib as L  # noqa: E402
-from pql_amd.models.mlp import mlp_forward_raw  # noqa: E402
+from pql_amd.models.mlp import mlp_forward_bf16_raw, mlp_forward_raw, output_view  # noqa: E402
 
 
 def graph_time(fn, dev, iters=20, reps=3):
@@ -74,6 +76,7 @@ def main():
     def apply(variant):
         v._td_in_head = True
         v._rng_mode = p._rng_mode = "auto"
+        tdtype = "float32"
         for k in [k for k in os.environ if k.startswith("PQLK_AB_")]:
             del os.environ[k]
         if variant != "base":
@@ -83,10 +86,13 @@ def main():
                     v._td_in_head = bool(int(val))
                 elif k == "rng":
                     v._rng_mode = p._rng_mode = val
+                elif k == "tdtype":
+                    tdtype = val
                 elif k.startswith("env:"):
                     os.environ["PQLK_AB_" + k[4:]] = val
                 else:
                     raise SystemExit(f"unknown variant key {k!r}")
+        v.set_target_dtype(tdtype)   # (drops the workspace and every captured graph)
         v._ws = None
         v._graph = None
         p._ws = None
@@ -95,11 +101,31 @@ def main():
         return v._workspace(B)
 
     def sec_actor():
-        mlp_forward_raw(al, v.actor.arena.data, ws["xn_sa"], L.ACT_TANH_NOISE, ws["draw"], 0.8, 0.2, ws["acts_a"], ws["xn_sa"][:, O:],
-                        packed=v.pk_actor, stash_all=False)
+        if v._bf16:
+            mlp_forward_bf16_raw(al, v.actor.arena.data, v.pk_actor_bf16, ws["xn_sa"], L.ACT_TANH_NOISE, ws["draw"], 0.8, 0.2, ws["acts_a"],
+                                 ws["xn_sa"][:, O:])
+        else:
+            mlp_forward_raw(al, v.actor.arena.data, ws["xn_sa"], L.ACT_TANH_NOISE, ws["draw"], 0.8, 0.2, ws["acts_a"], ws["xn_sa"][:, O:],
+                            packed=v.pk_actor, stash_all=False)
+
+    def sec_actor8():   # the target policy over the K x B rows gathered ahead: one launch per K steps (_prefetch)
+        K = ws["K"]
+        xn, draws = ws["xn_sa_all"].view(K * B, ws["ld_sa"]), v._ahead.normal.view(K * B, -1)
+        if v._bf16:
+            mlp_forward_bf16_raw(al, v.actor.arena.data, v.pk_actor_bf16, xn, L.ACT_TANH_NOISE, draws, 0.8, 0.2, ws["a_out_all"], xn[:, O:])
+        else:
+            mlp_forward_raw(al, v.actor.arena.data, xn, L.ACT_TANH_NOISE, draws, 0.8, 0.2, ws["a_out_all"], xn[:, O:], packed=v.pk_actor,
+                            stash_all=2)
 
     def sec_target():
-        mlp_forward_raw(cl, v.critic_target.arena.data, ws["xn_sa"], L.ACT_NONE, acts=ws["acts_t"], packed=v.pk_target, stash_all=False)
+        if v._bf16:
+            mlp_forward_bf16_raw(cl, v.critic_target.arena.data, v.pk_target_bf16, ws["xn_sa"], L.ACT_NONE, out=output_view(cl, ws["acts_t"], B))
+        else:
+            mlp_forward_raw(cl, v.critic_target.arena.data, ws["xn_sa"], L.ACT_NONE, acts=ws["acts_t"], packed=v.pk_target, stash_all=False)
+
+    def sec_pack16():   # bf16 re-pack of the target critic (the 10th launch of a bfloat16 step); nothing to time under float32
+        if v._bf16:
+            v.pk_target_bf16.refresh(v.critic_target.arena.data)
 
     def sec_critic():
         mlp_forward_raw(cl, v.critic.arena.data, ws["x_sa"], L.ACT_NONE, acts=ws["acts_c"], packed=v.pk_critic, stash_all=True)
@@ -133,7 +159,8 @@ def main():
             best = min(best, (time.perf_counter() - t0) / n * 1e6)
         return best
 
-    sections = {"actor": lambda: graph_time(sec_actor, dev), "target": lambda: graph_time(sec_target, dev),
+    sections = {"actor": lambda: graph_time(sec_actor, dev), "actor8": lambda: graph_time(sec_actor8, dev),
+                "pack16": lambda: graph_time(sec_pack16, dev) if v._bf16 else 0.0, "target": lambda: graph_time(sec_target, dev),
                 "critic": lambda: graph_time(sec_critic, dev), "bwd": lambda: graph_time(sec_bwd, dev),
                 "opt": lambda: graph_time(sec_opt, dev), "opt_nopack": lambda: graph_time(sec_opt_nopack, dev), "vstep": lambda: rate(v.learn, ns.steps),
                 "pstep": lambda: rate(p.learn, ns.steps)}

@@ -15,6 +15,7 @@ controller a = clamp(4 (g - x) - 4 v, -1, 1) (R_pd), the gap fraction f = (R - R
     python tools/learn_pointmass.py --out profiles/pointmass_learning.json
     python tools/learn_pointmass.py --algos ddpg --shapes small --seeds 1 --iters 200      # a quick look
     python tools/learn_pointmass.py --override algo.replay_obs_dtype=float16 --out profiles/pointmass_learning_fp16.json
+    python tools/learn_pointmass.py --algos pql --override algo.target_dtype=bfloat16 --versus-default --out profiles/pointmass_learning_bf16.json
 """
 import argparse
 import importlib.util
@@ -121,6 +122,8 @@ def main():
     ap.add_argument("--iters", type=int, default=1000, help="rollout iterations per run (8 critic updates each)")
     ap.add_argument("--curve", default=None, help="comma-separated iteration counts: DDPG at the small shape, every seed, at each of them")
     ap.add_argument("--override", action="append", default=[], help="a further config override for every run (repeatable)")
+    ap.add_argument("--versus-default", action="store_true", help="with --override: every run is preceded by the same run WITHOUT the "
+                    "overrides (no `overrides` key in its record), so the two variants alternate inside one call")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "learn_pointmass needs a GPU"
@@ -138,6 +141,8 @@ def main():
     for algo in a.algos.split(","):
         for shape in a.shapes.split(","):
             for seed in range(a.seeds):
+                if a.versus_default and a.override:
+                    record("runs", run(algo, shape, seed, a.iters))
                 record("runs", run(algo, shape, seed, a.iters, tuple(a.override)))
     for iters in ([int(x) for x in a.curve.split(",")] if a.curve else []):
         for seed in range(a.seeds):
