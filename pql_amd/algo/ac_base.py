@@ -1,0 +1,150 @@
+"""`ActorCriticBase`: what the synchronous replay baselines (DDPG, SAC, CrossQ) share -- the counterpart of the reference's
+`pql/algo/ac_base.py`.  The nets, their optimiser moments and loss rings, the checkpoint state, the rollout, the workspace, the
+replay sample and the launch blocks every one of them runs (TD-MSE loss, DPG loss, optimiser steps, Polyak).  An agent keeps its
+`update_once`: the algorithm, in the order of the reference's lines.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from copy import deepcopy
+
+import numpy as np
+import torch
+
+from pql_amd import _lib as L
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, make_actor, make_critic
+from pql_amd.algo.pql_actor import PQLActor
+from pql_amd.models.mlp import default_splits, mlp_backward_raw
+from pql_amd.replay.simple_replay import cfg_obs_dtype
+
+
+class ActorCriticBase(PQLActor):
+    TARGET_CRITIC = True   # False (CrossQ): the agent has no `critic_target` attribute at all
+
+    def __init__(self, env, cfg):
+        cfg.algo.v_learner_gpu = cfg.algo.get("v_learner_gpu", 0) or 0
+        cfg.algo.p_learner_gpu = cfg.algo.get("p_learner_gpu", 0) or 0
+        super().__init__(env, cfg)
+        self.device = self.sim_device
+        algo = cfg.algo
+        self.replay_obs_dtype = cfg_obs_dtype(algo)   # algo.replay_obs_dtype: storage format of the replay ring built for this agent
+        self.actor = make_actor(cfg, self.obs_dim, self.action_dim, self.device)   # actor first: both consume the CPU generator
+        self.critic = make_critic(cfg, self.obs_dim, self.action_dim, self.device)
+        if self.TARGET_CRITIC:
+            self.critic_target = deepcopy(self.critic)
+        # a Polyak-averaged copy of the actor, or (no_tgt_actor=True, every shipped config) the actor itself
+        self.actor_target = self.actor if algo.no_tgt_actor else deepcopy(self.actor)
+        self.aopt, self.copt = _AdamState(self.actor.arena.data), _AdamState(self.critic.arena.data)
+        self.closs = torch.zeros(LOSS_RING, device=self.device)
+        self.aloss = torch.zeros(LOSS_RING, device=self.device)
+        self._ws = None
+
+    # ---- training state ----------------------------------------------------------------------------
+    def _own_state(self):
+        """(extra named tensors, {name: _AdamState}) of this agent's checkpoint; a subclass extends either."""
+        return {}, {"aopt": self.aopt, "copt": self.copt}
+
+    def _state_tensors(self):
+        out = super()._state_tensors()   # (the policy itself is the base class's "actor")
+        out.update(critic=self.critic.arena.data, closs=self.closs, aloss=self.aloss)
+        if self.TARGET_CRITIC:
+            out["critic_target"] = self.critic_target.arena.data
+        if self.actor_target is not self.actor:
+            out["actor_target"] = self.actor_target.arena.data
+        extra, opts = self._own_state()
+        out.update(extra)
+        for name, opt in opts.items():
+            out.update({f"{name}.m": opt.m, f"{name}.v": opt.v, f"{name}.step": opt.step})
+        return out
+
+    def explore_env(self, env, timesteps, random=False):
+        _, cri_data, steps = super().explore_env(env, timesteps, random)
+        return cri_data, steps
+
+    # ---- learning ----------------------------------------------------------------------------------
+    def _own_tiles(self, ws, zeros, empty):
+        """The agent's tiles, put into `ws` before the common ones (a common name set here is kept: CrossQ's x_sa / xn_sa).
+        Here: what a critic that is one MLP arena needs."""
+        B, cl = ws["B"], self.critic.layout
+        ws["dy"] = zeros((2, B, cl.ld_out))
+        ws["acts_t"], ws["acts_c"] = empty(cl.acts_floats(B)), empty(cl.acts_floats(B))
+        ws["bwd_c"] = empty(cl.bwd_ws_floats(B, ws["splits"]))
+
+    def _workspace(self, B):
+        if self._ws is not None and self._ws["B"] == B:
+            return self._ws
+        f = dict(dtype=torch.float32, device=self.device)
+        O, A = self.obs_dim[0], self.action_dim
+        al = self.actor.layout
+        ws = dict(B=B, ld_sa=L.ld(O + A), ld_o=L.ld(O), ld_a=L.ld(A), splits=default_splits(B))
+        self._own_tiles(ws, lambda shape: torch.zeros(shape, **f), lambda n: torch.empty(n, **f))
+        # zeroed: nothing writes the pad columns afterwards, and the GEMMs read them
+        for k, shape in dict(x_sa=(B, ws["ld_sa"]), xn_sa=(B, ws["ld_sa"]), xn_obs=(B, ws["ld_o"]), x_obs=(B, ws["ld_o"]),
+                             x_pi=(B, ws["ld_sa"]), rew=(B,), done=(B,), gc=(self.critic.arena.numel(),), ga=(al.total,),
+                             scratch=(2048,)).items():
+            if k not in ws:
+                ws[k] = torch.zeros(shape, **f)
+        ws["acts_a"] = torch.empty(al.acts_floats(B), **f)
+        ws["bwd_a"] = torch.empty(al.bwd_ws_floats(B, ws["splits"]), **f)
+        self._ws = ws
+        return ws
+
+    def _sample(self, memory, ws, indices=None):
+        """Draw (or take) B replay indices and gather: [obs | action] -> x_sa, normalised next obs -> xn_sa / xn_obs, reward, done;
+        obs_rms.normalize WITHOUT clamp.  x_obs (= norm(obs), the actor-step input) and x_pi's observation columns are copies."""
+        B, O = ws["B"], self.obs_dim[0]
+        idx = memory.draw_indices(B) if indices is None else indices.to(self.device, torch.int64).contiguous()
+        mean = var = None
+        eps = 0.0
+        if self.cfg.algo.obs_norm:
+            mean, var, eps = self.obs_rms.get_states()
+            mean, var = mean.contiguous(), var.contiguous()
+        L.check(L.lib.pqlk_replay_gather_fused(C.byref(memory.ring.desc), L.ptr(idx), B, L.ptr(mean), L.ptr(var), float(eps), 0,
+                                               L.ptr(ws["x_sa"]), ws["ld_sa"], L.ptr(ws["xn_sa"]), L.ptr(ws["xn_obs"]), ws["ld_o"],
+                                               L.ptr(ws["rew"]), L.ptr(ws["done"]), L.stream(self.device)))
+        ws["x_obs"][:, :O].copy_(ws["x_sa"][:, :O])
+        ws["x_pi"][:, :O].copy_(ws["x_sa"][:, :O])
+        return idx
+
+    def _td_mse_loss(self, ws, q, qt, ld):
+        """Twin MSE against r + (1 - d) gamma^n min(qt): d loss / d q -> ws["dy"], the loss -> the critic's ring."""
+        algo = self.cfg.algo
+        L.check(L.lib.pqlk_td_mse_loss(L.ptr(q), L.ptr(qt), ld, L.ptr(ws["rew"]), L.ptr(ws["done"]), float(algo.gamma) ** int(algo.nstep),
+                                       ws["B"], L.ptr(ws["dy"]), L.ptr(self.closs), L.ptr(self.copt.step), LOSS_RING,
+                                       L.ptr(ws["scratch"]), L.stream(self.device)))
+
+    def _dpg_loss(self, ws, q, ld):
+        """-mean(min q): d loss / d q -> ws["dy"], the loss -> the actor's ring."""
+        L.check(L.lib.pqlk_dpg_loss(L.ptr(q), ld, 1, None, ws["B"], L.ptr(ws["dy"]), L.ptr(self.aloss), L.ptr(self.aopt.step), LOSS_RING,
+                                    L.ptr(ws["scratch"]), L.stream(self.device)))
+
+    def _critic_step(self, ws):
+        algo = self.cfg.algo
+        apply_optimizer(self.critic.arena.data, ws["gc"], self.copt, None, algo.critic_lr, algo.max_grad_norm, 0.0, 1.0, self.device)
+
+    def _actor_step(self, ws, dy_a):
+        """The policy MLP's backward from `dy_a` (the gradient at its pre-activation output), then clip + AdamW."""
+        algo = self.cfg.algo
+        mlp_backward_raw(self.actor.layout, self.actor.arena.data, ws["x_obs"], ws["acts_a"], dy_a, ws["bwd_a"], ws["ga"], ws["splits"])
+        apply_optimizer(self.actor.arena.data, ws["ga"], self.aopt, None, algo.actor_lr, algo.max_grad_norm, 0.0, 1.0, self.device)
+
+    def _update_targets(self):
+        """soft_update(target, net, tau) of whichever targets exist."""
+        pairs = [(self.critic_target, self.critic)] if self.TARGET_CRITIC else []
+        if self.actor_target is not self.actor:
+            pairs.append((self.actor_target, self.actor))
+        for tgt, net in pairs:
+            L.check(L.lib.pqlk_polyak(L.ptr(tgt.arena.data), L.ptr(net.arena.data), net.arena.numel(), float(self.cfg.algo.tau),
+                                      L.stream(self.device)))
+
+    def _extra_log(self):
+        return {}
+
+    def update_net(self, memory):
+        n = int(self.cfg.algo.update_times)
+        for _ in range(n):
+            self.update_once(memory)
+        c, a = self.closs.tolist(), self.aloss.tolist()
+        k = min(n, LOSS_RING)
+        return {"train/critic_loss": float(np.mean(c[:k])), "train/actor_loss": float(np.mean(a[:k])),
+                "train/return": self.return_tracker.mean(), "train/episode_length": self.step_tracker.mean(), **self._extra_log()}

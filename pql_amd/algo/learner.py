@@ -66,10 +66,8 @@ def apply_optimizer(arena, grads, st: _AdamState, target, lr, max_grad_norm, tau
                                                   L.ptr(st.scratch), L.stream(device)))
         return
     L.check(L.lib.pqlk_clip_adamw_polyak(L.ptr(arena), L.ptr(grads), L.ptr(st.m), L.ptr(st.v), L.ptr(target),
-                                         arena.numel(), float(grad_scale),
-                                         float(max_grad_norm) if max_grad_norm is not None else 0.0,
-                                         float(lr), 0.9, 0.999, 1e-8, 1e-2, float(tau), L.ptr(st.step), L.ptr(st.gnorm),
-                                         L.ptr(st.scratch), L.stream(device)))
+                                         arena.numel(), float(grad_scale), mn, float(lr), 0.9, 0.999, 1e-8, 1e-2, float(tau),
+                                         L.ptr(st.step), L.ptr(st.gnorm), L.ptr(st.scratch), L.stream(device)))
 
 
 def apply_optimizer_fused(layout, arena, grads, st: _AdamState, target, lr, max_grad_norm, tau, packed, packed_target,
@@ -216,13 +214,14 @@ def pump(learner, stop_event=None, max_in_flight=2):
 def make_critic(cfg, obs_dim, action_dim, device):
     """The critic `cfg.algo` names, freshly initialised on `device` (consumes the CPU generator like any module constructor)."""
     algo = cfg.algo
-    if algo.distl and "Distributional" not in algo.cri_class:
+    distl = _cfg_get(algo, "distl", False)   # (the baselines' configs need not carry the key)
+    if distl and "Distributional" not in algo.cri_class:
         algo.cri_class = "Distributional" + algo.cri_class  # same rewrite as the reference (:30-31)
     cri_class = load_class_from_path(algo.cri_class, model_name_to_path[algo.cri_class])
     hidden = _cfg_get(algo, "hidden_layers")
     hidden = list(hidden) if hidden is not None else None
     with torch.cuda.device(device):
-        if algo.distl:
+        if distl:
             return cri_class(obs_dim, action_dim, v_min=algo.v_min, v_max=algo.v_max, num_atoms=algo.num_atoms, device=device,
                              hidden_layers=hidden).to(device)
         return cri_class(obs_dim, action_dim, hidden_layers=hidden).to(device)

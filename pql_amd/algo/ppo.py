@@ -10,17 +10,13 @@ actor backward -> clip + AdamW (actor MLP and `logstd` in one flat buffer) -> cr
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import _AdamState, _cfg_get, apply_optimizer
+from pql_amd.algo.learner import _AdamState, _cfg_get, apply_optimizer, make_actor, make_critic
 from pql_amd.algo.pql_actor import DeviceTracker, PQLActor
-from pql_amd.models import model_name_to_path
-from pql_amd.models.mlp import default_splits, mlp_forward_raw, output_view
-from pql_amd.utils.common import load_class_from_path
+from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.utils.torch_util import RunningMeanStd
 
 TIMEOUT_KEYS = ("TimeLimit.truncated", "time_outs")
@@ -38,13 +34,8 @@ class AgentPPO:
         algo = cfg.algo
         if cfg.info_track_keys is not None:
             raise NotImplementedError("info_track_keys needs a simulator's info dict; out of scope")
-        hidden = _cfg_get(algo, "hidden_layers")
-        hidden = list(hidden) if hidden is not None else None
-        act_class = load_class_from_path(algo.act_class, model_name_to_path[algo.act_class])
-        cri_class = load_class_from_path(algo.cri_class, model_name_to_path[algo.cri_class])
-        with torch.cuda.device(dev):
-            self.actor = act_class(self.obs_dim, self.action_dim, hidden_layers=hidden).to(dev)
-            self.critic = cri_class(self.obs_dim, self.action_dim, hidden_layers=hidden).to(dev)
+        self.actor = make_actor(cfg, self.obs_dim, self.action_dim, dev)   # actor first: both consume the CPU generator
+        self.critic = make_critic(cfg, self.obs_dim, self.action_dim, dev)
         if not hasattr(self.actor, "logstd_block") or self.critic.layout.dims[-1] != 1:
             raise ValueError("PPO needs act_class: DiagGaussianMLPPolicy and cri_class: MLPCritic")
         self.aopt, self.copt = _AdamState(self.actor.arena.data), _AdamState(self.critic.arena.data)
@@ -260,8 +251,7 @@ class AgentPPO:
                                                mb, A, float(algo.ratio_clip), float(algo.lambda_entropy), L.ptr(dy_a),
                                                L.ptr(self.actor.logstd_block(ws["ga"])), None, L.ptr(ws["sc_a"]), ws["sc_a"].numel(),
                                                L.ptr(self.aloss), L.ptr(self.aopt.step), ring_len, st))
-            L.check(L.lib.pqlk_mlp_backward(C.byref(al.desc), L.ptr(self.actor.arena.data), L.ptr(x), ldx, mb, L.ptr(acts_a), L.ptr(dy_a),
-                                            L.ptr(ws["ga"]), splits, None, 0, 0, 0, None, 0, L.ptr(bwd_a), bwd_a.numel(), st))
+            mlp_backward_raw(al, self.actor.arena.data, x, acts_a, dy_a, bwd_a, ws["ga"], splits, rows=mb)
             apply_optimizer(self.actor.arena.data, ws["ga"], self.aopt, None, algo.actor_lr, algo.max_grad_norm, 0.0, 1.0, dev)
             # ---- critic: (clipped) value loss
             mlp_forward_raw(cl, self.critic.arena.data, x, L.ACT_NONE, acts=acts_c)
@@ -270,8 +260,7 @@ class AgentPPO:
             L.check(L.lib.pqlk_ppo_value_loss(L.ptr(v), cl.ld_out, L.ptr(ws["ret"]), L.ptr(ws["val"]), mb, 1 if algo.value_clip else 0,
                                               float(algo.ratio_clip), L.ptr(dy_c), cl.ld_out, L.ptr(ws["sc_c"]), ws["sc_c"].numel(),
                                               L.ptr(self.closs), L.ptr(self.copt.step), ring_len, st))
-            L.check(L.lib.pqlk_mlp_backward(C.byref(cl.desc), L.ptr(self.critic.arena.data), L.ptr(x), ldx, mb, L.ptr(acts_c), L.ptr(dy_c),
-                                            L.ptr(ws["gc"]), splits, None, 0, 0, 0, None, 0, L.ptr(bwd_c), bwd_c.numel(), st))
+            mlp_backward_raw(cl, self.critic.arena.data, x, acts_c, dy_c, bwd_c, ws["gc"], splits, rows=mb)
             apply_optimizer(self.critic.arena.data, ws["gc"], self.copt, None, algo.critic_lr, algo.max_grad_norm, 0.0, 1.0, dev)
 
     def minibatch_plan(self, rows):

@@ -18,7 +18,7 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
                                   load_artifact, make_actor, make_critic, pump, resident_norm)
-from pql_amd.models.mlp import PackedWeights, default_splits, mlp_forward_raw, output_view
+from pql_amd.models.mlp import PackedWeights, default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.simple_replay import RecordRing, _obs_width, cfg_obs_dtype, ring_plan
 from pql_amd.utils import handoff as H
 from pql_amd.utils import rng as R
@@ -187,9 +187,7 @@ class PQLPLearner(Learner):
                                                  0, None, 0, L.ptr(ws["bwd_a"]), ws["bwd_a"].numel(), L.ptr(self.opt.scratch),
                                                  L.ptr(self.opt.step), st))
         else:
-            L.check(L.lib.pqlk_mlp_backward(C.byref(al.desc), L.ptr(self.actor.arena.data), L.ptr(ws["x_obs"]), ws["ld_o"], B,
-                                            L.ptr(ws["acts_a"]), L.ptr(ws["dz_a"]), L.ptr(ws["grads"]), ws["splits"], None, 0, 0, 0,
-                                            None, 0, L.ptr(ws["bwd_a"]), ws["bwd_a"].numel(), st))
+            mlp_backward_raw(al, self.actor.arena.data, ws["x_obs"], ws["acts_a"], ws["dz_a"], ws["bwd_a"], ws["grads"], ws["splits"])
         if upto_backward:
             return
         self._allreduce_grads(ws)

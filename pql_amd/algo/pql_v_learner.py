@@ -22,7 +22,8 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
                                   graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
-from pql_amd.models.mlp import HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_forward_bf16_raw, mlp_forward_raw, output_view
+from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
+                                output_view)
 from pql_amd.replay.simple_replay import ReplayBuffer, cfg_obs_dtype
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
@@ -331,9 +332,7 @@ class PQLVLearner(Learner):
                                                  0, None, 0, L.ptr(ws["bwd"]), ws["bwd"].numel(), L.ptr(self.opt.scratch),
                                                  L.ptr(self.opt.step), st))
         else:
-            L.check(L.lib.pqlk_mlp_backward(C.byref(cl.desc), L.ptr(self.critic.arena.data), L.ptr(ws["x_sa"]), ws["ld_sa"], B,
-                                            L.ptr(ws["acts_c"]), L.ptr(ws["dy"]), L.ptr(ws["grads"]), ws["splits"], None, 0, 0, 0,
-                                            None, 0, L.ptr(ws["bwd"]), ws["bwd"].numel(), st))
+            mlp_backward_raw(cl, self.critic.arena.data, ws["x_sa"], ws["acts_c"], ws["dy"], ws["bwd"], ws["grads"], ws["splits"])
         if upto_backward:
             return
         self._allreduce_grads(ws)

@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from pql_amd import _lib as L
-from pql_amd.models.mlp import HIDDEN_DEFAULT, ArenaLayout, _first, default_splits, pad_cols
+from pql_amd.models.mlp import HIDDEN_DEFAULT, ArenaLayout, _first, default_splits, mlp_backward_raw, pad_cols
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1   # nn.BatchNorm1d defaults
 
@@ -222,10 +222,7 @@ class DoubleQBatchNorm(nn.Module):
                     else:
                         dx = ws["dx0"][n] if need_dx else None
                     g_lin = grads[self.off[(n, l, "lin")]:] if grads is not None else None
-                    L.check(L.lib.pqlk_mlp_backward(C.byref(lay.desc), L.ptr(arena[self.off[(n, l, "lin")]:]), L.ptr(x_in), x_in.stride(0), M,
-                                                    L.ptr(ws["z"][(n, l)]), L.ptr(dcur), L.ptr(g_lin), splits,
-                                                    L.ptr(dx), dx.stride(0) if dx is not None else 0, 0, 0, None, 0,
-                                                    L.ptr(ws["bwd"]), ws["bwd"].numel(), st))
+                    mlp_backward_raw(lay, arena[self.off[(n, l, "lin")]:], x_in, ws["z"][(n, l)], dcur, ws["bwd"], g_lin, splits, dx, rows=M)
                     dcur = dx
             if need_dx:
                 return ws["dx0"][0] + ws["dx0"][1]

@@ -123,6 +123,19 @@ def mlp_forward_raw(layout: ArenaLayout, arena, x_pad, out_act=L.ACT_NONE, draw=
     return acts
 
 
+def mlp_backward_raw(layout: ArenaLayout, arena, x_pad, acts, dy, ws, grads=None, splits=1, dx=None, dx_col0=0, dx_cols=0,
+                     dx_tanh_of=None, rows=None):
+    """Launch the backward of the forward that left `acts` for `x_pad`: the parameter gradient into `grads` (None: frozen) and/or
+    the input gradient, columns [dx_col0, dx_col0 + dx_cols), into `dx` (dx_tanh_of: chained through the tanh whose output that
+    is).  dx / dx_tanh_of may be (1, B, ld) views: the row stride is what counts.  rows: fewer rows than `x_pad` has."""
+    dev = x_pad.device
+    with torch.cuda.device(dev):
+        L.check(L.lib.pqlk_mlp_backward(C.byref(layout.desc), L.ptr(arena), L.ptr(x_pad), x_pad.stride(0), x_pad.shape[0] if rows is None else rows,
+                                        L.ptr(acts), L.ptr(dy), L.ptr(grads), splits, L.ptr(dx), dx.stride(-2) if dx is not None else 0,
+                                        dx_col0, dx_cols, L.ptr(dx_tanh_of), dx_tanh_of.stride(-2) if dx_tanh_of is not None else 0,
+                                        L.ptr(ws), ws.numel(), L.stream(dev)))
+
+
 class PackedWeightsBf16:
     """Fragment-ordered bf16 copy of EVERY layer's weights, output layer included, for the forward-only bf16-MFMA stack
     (pqlk_mlp_pack_bf16; `algo.target_dtype=bfloat16`).  `tensor` holds the bf16 bit patterns as int16.  A layout the bf16 stack
@@ -196,10 +209,7 @@ class FusedMlpFn(torch.autograd.Function):
         dx = torch.empty((B, lay.ld_in), dtype=torch.float32, device=dev) if need_x else None
         if not (need_w or need_x):
             return None, None, None, None
-        with torch.cuda.device(dev):
-            L.check(L.lib.pqlk_mlp_backward(C.byref(lay.desc), L.ptr(arena), L.ptr(x_pad), x_pad.stride(0), B, L.ptr(acts),
-                                            L.ptr(dy), L.ptr(grads), splits, L.ptr(dx), lay.ld_in if need_x else 0, 0, 0,
-                                            None, 0, L.ptr(ws), ws.numel(), L.stream(dev)))
+        mlp_backward_raw(lay, arena, x_pad, acts, dy, ws, grads, splits, dx)
         return (dx[:, : ctx.in_cols] if need_x else None), grads, None, None
 
 

@@ -817,6 +817,48 @@ def test_dx_slice_kernel_equals_full_input_gradient(dev, O, A, hidden, B):
     assert torch.all(sl[:, A:] == 3.0)   # only the slice columns are written
 
 
+@pytest.mark.parametrize("case", ["grads", "dx_tanh", "rows"])
+def test_mlp_backward_raw_marshals_what_the_raw_call_takes(dev, case):
+    """`mlp_backward_raw` against the ctypes call it stands for, bit for bit, on a twin [12, 32, 32, 4] net at B = 96 (a partial
+    row tile).  grads: the parameter gradient, splits=1.  dx_tanh: grads=None, the input gradient's columns [8, 12) through a
+    tanh, with dx and dx_tanh_of given as (1, B, ld) views (the row stride is what has to reach the kernel).  rows: both
+    gradients over the first 70 rows of the 96-row tile."""
+    from pql_amd import _lib as L
+    from pql_amd.models.mlp import ArenaLayout, mlp_backward_raw, mlp_forward_raw
+    B, lay = 96, ArenaLayout([12, 32, 32, 4], 2)
+    arena = torch.zeros(lay.total, device=dev)
+    for n in range(2):
+        for l in range(lay.n_layers):
+            bound = 1.0 / np.sqrt(lay.dims[l])
+            lay.weight(arena, n, l).copy_(T(dd.uniform((lay.dims[l + 1], lay.dims[l]), 100 * n + l, -bound, bound)))
+            lay.bias(arena, n, l).copy_(T(dd.uniform((lay.dims[l + 1],), 100 * n + l + 50, -bound, bound)))
+    x = torch.zeros((B, lay.ld_in), device=dev)
+    x[:, :12] = T(dd.uniform((B, 12), 7, -1, 1)).to(dev)
+    b = 70 if case == "rows" else B
+    acts = mlp_forward_raw(lay, arena, x[:b], L.ACT_NONE)
+    dy = torch.zeros((2, b, lay.ld_out), device=dev)
+    dy[:, :, :4] = T(dd.uniform((2, b, 4), 9, -1, 1)).to(dev)
+    ws = torch.empty(lay.bwd_ws_floats(b, 1), device=dev)
+    ld_a = L.ld(4)
+    a = torch.zeros(B * ld_a, device=dev).view(1, B, ld_a)
+    a[0, :, :4] = torch.tanh(T(dd.uniform((B, 4), 11, -2, 2))).to(dev)
+    got = {}
+    for who in ("raw", "wrapper"):   # (every output starts from the same fill: what a call leaves alone compares equal too)
+        grads = torch.full((lay.total,), 7.0, device=dev) if case != "dx_tanh" else None
+        dx = torch.full((1, B, ld_a), 7.0, device=dev) if case == "dx_tanh" else torch.full((B, lay.ld_in), 7.0, device=dev) if case == "rows" else None
+        col0, cols, tanh_of = (8, 4, a) if case == "dx_tanh" else (0, 0, None)
+        if who == "raw":
+            L.check(L.lib.pqlk_mlp_backward(C.byref(lay.desc), L.ptr(arena), L.ptr(x), lay.ld_in, b, L.ptr(acts), L.ptr(dy), L.ptr(grads), 1,
+                                            L.ptr(dx), 0 if dx is None else (ld_a if case == "dx_tanh" else lay.ld_in), col0, cols,
+                                            L.ptr(tanh_of), ld_a if tanh_of is not None else 0, L.ptr(ws), ws.numel(), L.stream(dev)))
+        else:
+            mlp_backward_raw(lay, arena, x, acts, dy, ws, grads=grads, splits=1, dx=dx, dx_col0=col0, dx_cols=cols, dx_tanh_of=tanh_of,
+                             rows=b if case == "rows" else None)
+        got[who] = (grads, dx)
+    for r, w in zip(got["raw"], got["wrapper"]):
+        assert (r is None) == (w is None) and (r is None or (torch.equal(r, w) and not torch.all(r == 7.0)))
+
+
 # --------------------------------------------------------------------------- shape sweep of the MLP path
 _SWEEP = [
     # dims (in, hidden..., out), nets, B, fused?

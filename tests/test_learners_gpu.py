@@ -686,6 +686,29 @@ def test_target_actor_is_polyak_averaged_in_sac_and_crossq(dev, algo):
     assert not torch.equal(agent.actor_target.arena.data, agent.actor.arena.data)
 
 
+_DDPG_STATE = {"actor", "current_returns", "current_lengths", "critic", "critic_target", "closs", "aloss", "aopt.m", "aopt.v", "aopt.step",
+               "copt.m", "copt.v", "copt.step"}
+
+
+@pytest.mark.parametrize("tgt_actor", [False, True])
+@pytest.mark.parametrize("algo", ["ddpg", "sac", "crossq"])
+def test_baseline_agents_checkpoint_tensor_names(dev, algo, tgt_actor):
+    """The names under which an agent's tensors go into a checkpoint (`_state_tensors`): a file written before must keep loading."""
+    from pql_amd.envs.synthetic import create_task_env
+    extra = [f"algo.no_tgt_actor={not tgt_actor}"]
+    if algo == "ddpg":
+        from pql_amd.algo.ddpg import AgentDDPG as Agent
+        cfg, want = _ddpg_cfg(extra), set(_DDPG_STATE)
+    elif algo == "sac":
+        from pql_amd.algo.sac import AgentSAC as Agent
+        cfg, want = _sac_cfg(extra), _DDPG_STATE | {"log_alpha", "alpha_loss", "alpha_opt.m", "alpha_opt.v", "alpha_opt.step"}
+    else:
+        from pql_amd.algo.crossq import AgentCrossQ as Agent
+        cfg, want = _crossq_cfg(extra), (_DDPG_STATE - {"critic_target"}) | {"critic_stats", "critic_batches"}
+    agent = Agent(create_task_env(cfg), cfg)
+    assert set(agent._state_tensors()) == want | ({"actor_target"} if tgt_actor else set())
+
+
 def test_train_baselines_entry_point_cfg1(dev):
     import importlib.util, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
