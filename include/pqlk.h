@@ -542,6 +542,26 @@ int pqlk_pointmass_step(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t se
                         float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SwingUp vectorised environment step (the nonlinear learnable task of pql_amd/envs/swingup.py; not a reference component):
+ * act_dim independent torque-limited pendulums per env, each held as (c, s) = (cos, sin) of its angle from upright and its
+ * angular velocity w.  Replaces the ~200 elementwise torch launches of `SwingUpVecEnv._step_torch`, to which every output
+ * is bit-equal (one fp32 rounding per operation, no contraction, the sum over act_dim taken in index order, no atomics, no
+ * transcendental function, division or square root):
+ *   rot(c, s, d): d2 = d d; cd = 1 - d2 (0.5 - d2 / 24); sd = d (1 - d2 (1/6 - d2 / 120)); cn = c cd - s sd; sn = s cd + c sd;
+ *                 m = 1.5 - 0.5 (cn cn + sn sn); return (cn m, sn m)          (the three fractions as fp32 literals)
+ *   a = clamp(action, -1, 1); w' = clamp(w + 0.05 (15 s + 6 a), -8, 8); (c', s') = rot(c, s, 0.05 w'); k' = k + 1;
+ *   reward = -0.05 mean_j ((1 - c') + 0.01 w'^2 + 0.01 a^2); truncated = k' >= episode_length; done = truncated.
+ * State (c, s, w: (N, act_dim) floats; k, ep: (N) int32) is updated IN PLACE; a done env moves to episode ep + 1 and is reset
+ * from the counter-based uniform u of the synthetic env keyed by (seed, env_offset + env, ep + 1): (c, s) = rot applied four
+ * times to (-1, 0) with d = 0.5 (2 u_13 - 1), w = 2 u_14 - 1, k = 0.
+ * next_obs (N, obs_dim) = [c | s | 0.125 w | 0 ...] AFTER the reset (16-byte stores when obs_dim % 4 == 0 and next_obs is
+ * 16-byte aligned); reward (N) floats; done / truncated (N) bytes.
+ * PQLK_E_NULL: any pointer NULL.  PQLK_E_SHAPE: n <= 0, act_dim <= 0, obs_dim < 3 * act_dim. */
+int pqlk_swingup_step(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                      int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k, int32_t* ep,
+                      float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-env-step bookkeeping of the rollout in one launch (pql_actor.py:104-114 slab writes, :129-135 update_tracker,
  * common.py:195-202 handle_timeout): column t of the (N, horizon, .) trajectory slabs <- (obs, action, reward, next_obs,
  * done * !truncated); cur_return += reward, cur_length += 1; the finished envs' values are appended IN ENV ORDER to the two

@@ -103,11 +103,11 @@ class PointMassVecEnv:
     def load_state_dict(self, state):
         for key in ("seed", "num_envs", "env_offset"):
             if int(state[key]) != getattr(self, key):
-                raise ValueError(f"PointMassVecEnv.load_state_dict: {key}={getattr(self, key)} but the state was saved with {int(state[key])}")
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {key}={getattr(self, key)} but the state was saved with {int(state[key])}")
         for name in self._STATE:
             mine = getattr(self, name)
             if tuple(state[name].shape) != tuple(mine.shape):
-                raise ValueError(f"PointMassVecEnv.load_state_dict: {name} has shape {tuple(mine.shape)} but the state holds {tuple(state[name].shape)}")
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {name} has shape {tuple(mine.shape)} but the state holds {tuple(state[name].shape)}")
             mine.copy_(state[name].to(self.device, mine.dtype))
 
     # ---- step --------------------------------------------------------------------------------------

@@ -110,7 +110,7 @@ class SyntheticVecEnv:
 
 def create_task_env(cfg, num_envs=None, env_offset=0):
     """Stand-in for pql.utils.isaacgym_util.create_task_env (:8-24).  `task.kind` picks the env: absent / synthetic = the
-    counter-based generator above, pointmass = the learnable task of pql_amd/envs/pointmass.py."""
+    counter-based generator above, pointmass / swingup = the learnable tasks of pql_amd/envs/pointmass.py and pql_amd/envs/swingup.py."""
     task = cfg.task
     name = task.name if task is not None else "AllegroHand"
     O, A = TASK_SHAPES.get(name, (88, 16))
@@ -123,7 +123,11 @@ def create_task_env(cfg, num_envs=None, env_offset=0):
         from pql_amd.envs.pointmass import PointMassVecEnv
         return PointMassVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
                                env_offset=env_offset)
+    if kind == "swingup":
+        from pql_amd.envs.swingup import SwingUpVecEnv
+        return SwingUpVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
+                             env_offset=env_offset)
     if kind != "synthetic":
-        raise ValueError(f"task.kind={kind}: no such env; known kinds: synthetic, pointmass")
+        raise ValueError(f"task.kind={kind}: no such env; known kinds: synthetic, pointmass, swingup")
     return SyntheticVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
                            env_offset=env_offset)

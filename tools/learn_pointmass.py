@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Learning record on the PointMass task (pql_amd/envs/pointmass.py): do the kernels, assembled into a training run, improve a policy?
+"""Learning record on the learnable tasks -- PointMass (pql_amd/envs/pointmass.py), or with `--task swingup` SwingUp
+(pql_amd/envs/swingup.py): do the kernels, assembled into a training run, improve a policy?
 
 Runs the two entry points themselves -- `scripts/train_baselines.py` (DDPG) and the fixed-ratio loop of `scripts/train_pql.py` -- on
 PointMass for a fixed number of rollout iterations, several seeds each, at two shapes:
@@ -10,12 +11,15 @@ PointMass for a fixed number of rollout iterations, several seeds each, at two s
 everything else at the defaults (nstep 3, gamma 0.99, tau 0.05, lr 5e-4, mixed exploration noise).  Per run it records the return of
 the trained deterministic policy over one full episode on 256 fresh envs (R), the same for the zero action (R_zero) and for the PD
 controller a = clamp(4 (g - x) - 4 v, -1, 1) (R_pd), the gap fraction f = (R - R_zero) / (R_pd - R_zero) and the wall time.
-`--curve` adds DDPG at the small shape over a ladder of iteration counts (where does it plateau?).
+`--curve` adds DDPG at the small shape over a ladder of iteration counts (where does it plateau?).  With `--task swingup` the shapes
+are the same, the episode length is 128 and the upper yardstick is the energy controller (`energy_policy`), recorded as R_ctrl.
 
     python tools/learn_pointmass.py --out profiles/pointmass_learning.json
     python tools/learn_pointmass.py --algos ddpg --shapes small --seeds 1 --iters 200      # a quick look
     python tools/learn_pointmass.py --override algo.replay_obs_dtype=float16 --out profiles/pointmass_learning_fp16.json
     python tools/learn_pointmass.py --algos pql --override algo.target_dtype=bfloat16 --versus-default --out profiles/pointmass_learning_bf16.json
+    python tools/learn_pointmass.py --task swingup --iters 2000 --curve 500,1000,2000,4000,8000 --out profiles/swingup_learning.json
+    python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.distl=True --out profiles/swingup_learning_distl.json
 """
 import argparse
 import importlib.util
@@ -31,10 +35,16 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
+from pql_amd.envs import swingup  # noqa: E402
 from pql_amd.envs.pointmass import PointMassVecEnv, episode_return, pd_policy, zero_policy  # noqa: E402
 from pql_amd.utils.cfg import load_cfg  # noqa: E402
 
 EPISODE_LENGTH = 64
+# task -> env class, episode length, (lower, upper) yardstick controllers and the record's key for the upper one
+TASKS = {
+    "pointmass": dict(env=PointMassVecEnv, episode_length=EPISODE_LENGTH, zero=zero_policy, ctrl=pd_policy, ctrl_key="R_pd"),
+    "swingup": dict(env=swingup.SwingUpVecEnv, episode_length=128, zero=swingup.zero_policy, ctrl=swingup.energy_policy, ctrl_key="R_ctrl"),
+}
 EVAL_ENVS = 256
 WARM_UP = 32   # algo.warm_up default: random-policy env steps in front of the first iteration
 SHAPES = {
@@ -53,28 +63,30 @@ def script(name):
     return _SCRIPTS[name]
 
 
-def overrides(algo, shape, seed, iters, run_dir, extra=()):
+def overrides(algo, shape, seed, iters, run_dir, extra=(), task="pointmass"):
     sh = SHAPES[shape]
     n = sh["num_envs"]
-    ov = [*ALGOS[algo][1], "task=pointmass", f"task.obs_dim={sh['obs_dim']}", f"task.act_dim={sh['act_dim']}",
-          f"task.episode_length={EPISODE_LENGTH}", f"num_envs={n}", f"algo.batch_size={sh['batch']}",
+    ov = [*ALGOS[algo][1], f"task={task}", f"task.obs_dim={sh['obs_dim']}", f"task.act_dim={sh['act_dim']}",
+          f"task.episode_length={TASKS[task]['episode_length']}", f"num_envs={n}", f"algo.batch_size={sh['batch']}",
           f"algo.memory_size={(WARM_UP + iters + 8) * n}", f"seed={seed}", f"max_step={(WARM_UP + iters) * n - 1}", f"+logging.dir={run_dir}"]
     if sh["hidden"] is not None:
         ov.append(f"algo.hidden_layers={sh['hidden']}")
     return ov + list(extra)
 
 
-def yardsticks(shape, seed, device="cuda:0"):
-    """(eval env, R_zero, R_pd): 256 fresh envs (their seed is not the training env's) and the two hand-written controllers on them."""
-    sh = SHAPES[shape]
-    env = PointMassVecEnv(EVAL_ENVS, sh["obs_dim"], sh["act_dim"], device=device, seed=10_000 + seed, episode_length=EPISODE_LENGTH)
-    return env, episode_return(env, zero_policy(env)), episode_return(env, pd_policy(env))
+def yardsticks(shape, seed, device="cuda:0", task="pointmass"):
+    """(eval env, R_zero, R_pd or R_ctrl): 256 fresh envs (their seed is not the training env's) and the task's two hand-written
+    controllers on them."""
+    sh, tk = SHAPES[shape], TASKS[task]
+    env = tk["env"](EVAL_ENVS, sh["obs_dim"], sh["act_dim"], device=device, seed=10_000 + seed, episode_length=tk["episode_length"])
+    return env, episode_return(env, tk["zero"](env)), episode_return(env, tk["ctrl"](env))
 
 
-def run(algo, shape, seed, iters, extra=()):
+def run(algo, shape, seed, iters, extra=(), task="pointmass"):
     """One training run through the entry point's own `main`; the policy is evaluated by its `on_finish` hook.
-    extra: further config overrides, e.g. ("algo.replay_obs_dtype=float16",)."""
-    env, r_zero, r_pd = yardsticks(shape, seed)
+    extra: further config overrides, e.g. ("algo.replay_obs_dtype=float16",).  task: a key of TASKS; the upper yardstick's return is
+    recorded as R_pd on PointMass and as R_ctrl on SwingUp (a PointMass record has no `task` key, as before the tool knew two tasks)."""
+    env, r_zero, r_pd = yardsticks(shape, seed, task=task)
     got = {}
 
     def evaluate(agent, *_learners):   # DDPG: the agent; PQL: (rollout actor, V-learner, P-learner)
@@ -82,7 +94,7 @@ def run(algo, shape, seed, iters, extra=()):
         got["R"] = episode_return(env, lambda obs: agent.get_actions(obs, sample=False))
 
     with tempfile.TemporaryDirectory() as run_dir:   # (the PQL loop's evaluator keeps its best model there)
-        cfg = load_cfg(overrides(algo, shape, seed, iters, run_dir, extra))
+        cfg = load_cfg(overrides(algo, shape, seed, iters, run_dir, extra, task))
         torch.cuda.synchronize()
         t0 = time.time()
         res = script(ALGOS[algo][0]).main(cfg, on_finish=evaluate)
@@ -91,14 +103,15 @@ def run(algo, shape, seed, iters, extra=()):
     done_iters = res["iters"] if algo == "ddpg" else res["rollout_iterations"]
     assert done_iters == iters, (done_iters, iters)
     updates = iters * int(cfg.algo.update_times) if algo == "ddpg" else int(res["critic_updates"])
-    return dict(algo=algo, shape=shape, seed=seed, iters=iters, **({"overrides": list(extra)} if extra else {}), critic_updates=updates, R=got["R"], R_zero=r_zero, R_pd=r_pd,
-                f=(got["R"] - r_zero) / (r_pd - r_zero), wall_s=round(wall, 2))
+    return dict(**({"task": task} if task != "pointmass" else {}), algo=algo, shape=shape, seed=seed, iters=iters,
+                **({"overrides": list(extra)} if extra else {}), critic_updates=updates, R=got["R"], R_zero=r_zero,
+                **{TASKS[task]["ctrl_key"]: r_pd}, f=(got["R"] - r_zero) / (r_pd - r_zero), wall_s=round(wall, 2))
 
 
-def env_step_time(num_envs=4096, obs_dim=88, act_dim=16, steps=2000, rounds=3):
-    """Microseconds per env step of the one-launch HIP step and of its torch definition on the GPU (host clock around `steps` steps
-    that end in a device synchronise; the two forms alternate, the best of `rounds` is kept; one warm-up round)."""
-    mk = lambda: PointMassVecEnv(num_envs, obs_dim, act_dim, device="cuda:0", seed=1, episode_length=EPISODE_LENGTH)   # noqa: E731
+def env_step_time(env_cls=PointMassVecEnv, num_envs=4096, obs_dim=88, act_dim=16, steps=2000, rounds=3, episode_length=EPISODE_LENGTH):
+    """Microseconds per env step of `env_cls`'s one-launch HIP step and of its torch definition on the GPU (host clock around `steps`
+    steps that end in a device synchronise; the two forms alternate, the best of `rounds` is kept; one warm-up round)."""
+    mk = lambda: env_cls(num_envs, obs_dim, act_dim, device="cuda:0", seed=1, episode_length=episode_length)   # noqa: E731
     hip, ref = mk(), mk()
     act = 2.0 * torch.rand((num_envs, act_dim), device="cuda:0") - 1.0
     best = {"hip": float("inf"), "torch": float("inf")}
@@ -116,6 +129,7 @@ def env_step_time(num_envs=4096, obs_dim=88, act_dim=16, steps=2000, rounds=3):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--task", default="pointmass", choices=sorted(TASKS))
     ap.add_argument("--algos", default="ddpg,pql")
     ap.add_argument("--shapes", default="small,large")
     ap.add_argument("--seeds", type=int, default=5)
@@ -127,8 +141,10 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "learn_pointmass needs a GPU"
-    out = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, episode_length=EPISODE_LENGTH, eval_envs=EVAL_ENVS,
-               shapes=SHAPES, overrides=list(a.override), env_step=env_step_time(), runs=[], curve=[])
+    tk = TASKS[a.task]
+    out = dict(**({"task": a.task} if a.task != "pointmass" else {}), device=torch.cuda.get_device_name(0), torch=torch.__version__,
+               episode_length=tk["episode_length"], eval_envs=EVAL_ENVS, shapes=SHAPES, overrides=list(a.override),
+               env_step=env_step_time(tk["env"], episode_length=tk["episode_length"]), runs=[], curve=[])
     print(json.dumps(out["env_step"]), flush=True)
 
     def record(key, r):
@@ -142,11 +158,11 @@ def main():
         for shape in a.shapes.split(","):
             for seed in range(a.seeds):
                 if a.versus_default and a.override:
-                    record("runs", run(algo, shape, seed, a.iters))
-                record("runs", run(algo, shape, seed, a.iters, tuple(a.override)))
+                    record("runs", run(algo, shape, seed, a.iters, task=a.task))
+                record("runs", run(algo, shape, seed, a.iters, tuple(a.override), task=a.task))
     for iters in ([int(x) for x in a.curve.split(",")] if a.curve else []):
         for seed in range(a.seeds):
-            record("curve", run("ddpg", "small", seed, iters, tuple(a.override)))
+            record("curve", run("ddpg", "small", seed, iters, tuple(a.override), task=a.task))
 
 
 if __name__ == "__main__":
