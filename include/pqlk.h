@@ -389,21 +389,34 @@ int pqlk_td_mse_loss(const float* q, const float* qt, int64_t ld, const float* r
 
 /* C51: softmax of target logits, categorical projection x2 (pql/utils/distl_util.py:4-20), elementwise
  * min (pql_v_learner.py:83-102), softmax of current logits, twin BCE (mean over B*K, log clamped at
- * -100 like torch) and its gradient w.r.t. the current logits.  logits: (2, B, ld), K <= 64 atoms;
+ * -100 like torch) and its gradient w.r.t. the current logits.  logits: (2, B, ld), 2 <= K <= PQLK_C51_MAX_ATOMS atoms
+ * (more: PQLK_E_UNSUPPORTED); dy's pad columns [K, ld) are written as zero;
  * support = DistributionalDoubleQ.z_atoms (mlp.py:253), passed in so its fp32 values are torch.linspace's.
- * If proj_out != NULL the (B, K) target pmf is also stored (tests). */
+ * If proj_out != NULL the (B, K) target pmf is also stored (tests); it changes no other output.
+ *
+ * Projection law, every K: per atom k, tz = clamp(r + ((1 - d) * gamma_n) * z_k, v_min, v_max), bpos = (tz - v_min) / dz with
+ * dz = (v_max - v_min) / (K - 1) formed in double and rounded once, lo = floor(bpos), up = ceil(bpos), then
+ * `if (up > 0 && lo == up) lo -= 1; if (lo < K - 1 && lo == up) up += 1;`, w_lo = p_k * (up - bpos), w_up = p_k * (bpos - lo),
+ * in fp32 without contraction.  Bin j receives every w_lo with lo == j in increasing atom order, then every w_up with up == j
+ * in increasing atom order, as one plain left-to-right fp32 sum: the order of the reference's two index_add_ passes.
+ * Precondition for K > 64: support increasing, 0 <= done <= 1, gamma_n >= 0 (then lo and up are non-decreasing in k, which the
+ * kernels for K > 64 rely on to find a bin's atoms; K <= 64 does not need it).  A non-finite reward can drop mass from a row at
+ * any K; it never makes a kernel read or write out of bounds. */
+#define PQLK_C51_MAX_ATOMS 256
 int pqlk_c51_bce_loss(const float* logits, const float* logits_t, int64_t ld, int32_t k,
                       const float* rew, const float* done, const float* support /*(K) z atoms*/, float gamma_n,
                       float v_min, float v_max, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
                       int32_t ring_len, float* proj_out, float* scratch, pqlk_stream_t stream);
 
-/* Stand-alone projection = projection() of distl_util.py:4-20 on a given pmf (B, K) contiguous. */
+/* Stand-alone projection = projection() of distl_util.py:4-20 on a given pmf (B, K) contiguous, 2 <= K <= PQLK_C51_MAX_ATOMS;
+ * law and precondition as above. */
 int pqlk_c51_project(const float* p, const float* rew, const float* done, const float* support, float gamma_n,
                      float v_min, float v_max, int32_t k, int64_t b, float* out, pqlk_stream_t stream);
 
 /* DPG actor loss (pql_p_learner.py:56-57): L = -mean(min(Q1,Q2)); dy = dL/dQ (ties split evenly, as
  * torch.min's backward).  k == 1: q (2,B,ld) scalar heads.  k > 1: logits of the distributional critic,
- * Q_i = sum softmax(logits_i) * z (mlp.py:256-260), dy = gradient w.r.t. the logits. */
+ * Q_i = sum softmax(logits_i) * z (mlp.py:256-260), dy = gradient w.r.t. the logits, pad columns [K, ld) written as zero;
+ * K <= PQLK_C51_MAX_ATOMS (more: PQLK_E_UNSUPPORTED). */
 int pqlk_dpg_loss_owner(const float* q, int64_t ld, int32_t k, const float* support, int64_t b, float* dy, float* loss_out,
                         const int32_t* slot_dev, int32_t ring_len, float* scratch,
                         uint8_t* owner /* (B), k == 1: bit 0 / bit 1 = the gradient of min(Q1, Q2) reaches net 0 / net 1 */,

@@ -17,6 +17,7 @@ LIB_FILE = Path(os.environ.get("PQLK_LIB", _HERE / "csrc" / "libpqlk.so"))   # P
 MAX_LAYERS = 8
 OBS_F32, OBS_F16 = 0, 1   # PqlReplayDesc.obs_dtype (PQLK_OBS_*)
 ACT_NONE, ACT_TANH, ACT_TANH_NOISE = 0, 1, 2
+C51_MAX_ATOMS = 256       # PQLK_C51_MAX_ATOMS: the C51 loss kernels hold one row's atoms in one wave, four per lane at most
 
 
 class PqlReplayDesc(C.Structure):

@@ -18,7 +18,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.models import model_name_to_path
-from pql_amd.models.mlp import PackedWeights
+from pql_amd.models.mlp import PackedWeights, check_num_atoms
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
 from pql_amd.utils import rng as R
@@ -220,6 +220,8 @@ def make_critic(cfg, obs_dim, action_dim, device):
     cri_class = load_class_from_path(algo.cri_class, model_name_to_path[algo.cri_class])
     hidden = _cfg_get(algo, "hidden_layers")
     hidden = list(hidden) if hidden is not None else None
+    if distl:
+        check_num_atoms(algo.num_atoms)   # before anything is allocated: a wrong value fails here, not after the warm-up rollout
     with torch.cuda.device(device):
         if distl:
             return cri_class(obs_dim, action_dim, v_min=algo.v_min, v_max=algo.v_max, num_atoms=algo.num_atoms, device=device,

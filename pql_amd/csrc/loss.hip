@@ -68,7 +68,7 @@ extern "C" int pqlk_td_mse_loss(const float* q, const float* qt, int64_t ld, con
 }
 
 // ------------------------------------------------------------------------------------------------
-// C51.  One wave per batch row, lane k <-> atom k (K <= 64).
+// C51.  One wave per batch row, lane k <-> atom k (K <= 64; more atoms: the k_*_wide kernels below).
 __device__ __forceinline__ float wave_softmax(float x, bool valid) {
   const float m = wave_max(valid ? x : -INFINITY);
   const float e = valid ? expf(x - m) : 0.f;
@@ -126,16 +126,259 @@ __global__ __launch_bounds__(256) void k_c51_project(const float* __restrict__ p
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// C51 with 65 ... PQLK_C51_MAX_ATOMS atoms.  Still one wave per batch row and four rows per block (same grids, same loss
+// partials); a lane holds atoms lane + 64 j, j < NJ = ceil(K / 64): coalesced row reads.  Softmax, E[z] and the softmax
+// backward's dot product reduce over the lane's own atoms first, then with wave_max / wave_sum.
+//
+// Projection: the per-atom arithmetic is project_row's, expression for expression.  The wave writes (lo, w_lo, up, w_up) of its K
+// atoms into its own 4 KiB LDS image.  lo and up are non-decreasing in the atom index (precondition in pqlk.h), so the atoms that
+// deposit into bin j are a contiguous range: the lane that owns the bin finds the first atom with lo >= j by binary search, walks
+// while lo == j, then does the same for up -- all lower-neighbour deposits in atom order, then all upper ones, a plain
+// left-to-right fp32 sum: the order of project_row and of the reference's two index_add_ passes.  O(K) LDS reads per bin at worst
+// (a terminal row: one bin collects every atom), O(log K) typically.  lo / up are only ever COMPARED, never used as an address:
+// a non-finite reward can drop mass, as in project_row, but cannot index outside the image.
+//
+// The image belongs to one wave and the row loop's trip count differs between the waves of a block (ragged last trip; B < 4 leaves
+// waves idle): no __syncthreads() inside that loop.  A wave's LDS accesses execute in order; wave_lds_fence() keeps the compiler
+// from reordering them.
+struct C51Image {
+  int lo[PQLK_C51_MAX_ATOMS];
+  float w_lo[PQLK_C51_MAX_ATOMS];
+  int up[PQLK_C51_MAX_ATOMS];
+  float w_up[PQLK_C51_MAX_ATOMS];
+};
+static_assert(sizeof(C51Image) == 4096 && PQLK_C51_MAX_ATOMS == 256, "first_ge's step and the launch table assume 256");
+
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// number of leading entries of the non-decreasing v[0, K) that are < bin (= index of the first one >= bin, or K)
+__device__ __forceinline__ int first_ge(const int* v, int K, int bin) {
+  int pos = 0;
+#pragma unroll
+  for (int s = PQLK_C51_MAX_ATOMS; s > 0; s >>= 1) {
+    const int e = pos + s;
+    const int x = v[min(e, PQLK_C51_MAX_ATOMS) - 1];   // (read inside the image whatever e is; used only when e <= K)
+    if (e <= K && x < bin) pos = e;
+  }
+  return pos;
+}
+
+template <int NJ>
+__device__ __forceinline__ void project_row_wide(const float (&p)[NJ], const float (&zk)[NJ], float r, float d, float gamma_n,
+                                                 float v_min, float v_max, float dz, int K, int lane, C51Image& img,
+                                                 float (&out)[NJ]) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int a = lane + 64 * j;
+    if (a < K) {
+      float tz = r + ((1.f - d) * gamma_n) * zk[j];
+      tz = fminf(fmaxf(tz, v_min), v_max);
+      const float bpos = (tz - v_min) / dz;
+      int lo = (int)floorf(bpos), up = (int)ceilf(bpos);
+      if (up > 0 && lo == up) lo -= 1;
+      if (lo < K - 1 && lo == up) up += 1;
+      img.lo[a] = lo;
+      img.w_lo[a] = p[j] * ((float)up - bpos);
+      img.up[a] = up;
+      img.w_up[a] = p[j] * (bpos - (float)lo);
+    }
+  }
+  wave_lds_fence();
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int bin = lane + 64 * j;
+    float o = 0.f;
+    if (bin < K) {
+      for (int a = first_ge(img.lo, K, bin); a < K && img.lo[a] == bin; ++a) o += img.w_lo[a];
+      for (int a = first_ge(img.up, K, bin); a < K && img.up[a] == bin; ++a) o += img.w_up[a];
+    }
+    out[j] = o;
+  }
+  wave_lds_fence();   // the next projection's writes stay behind these reads
+}
+
+// softmax over the K values a wave holds as x[j] <-> atom lane + 64 j (x[j] is ignored where the atom is >= K)
+template <int NJ>
+__device__ __forceinline__ void wave_softmax_wide(float (&x)[NJ], int K, int lane) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (lane + 64 * j < K) m = fmaxf(m, x[j]);
+  m = wave_max(m);
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    x[j] = lane + 64 * j < K ? expf(x[j] - m) : 0.f;
+    s += x[j];
+  }
+  s = wave_sum(s);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) x[j] = x[j] / s;
+}
+
+template <int NJ>
+__device__ __forceinline__ void load_row_wide(const float* __restrict__ row, int K, int lane, float (&x)[NJ]) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) x[j] = lane + 64 * j < K ? row[lane + 64 * j] : 0.f;
+}
+
+// one row of dy: columns [0, K) <- v, pad columns [K, ld) <- 0
+template <int NJ>
+__device__ __forceinline__ void store_dy_row_wide(float* __restrict__ row, int64_t ld, int K, int lane, const float (&v)[NJ]) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = lane + 64 * j;
+    if (c < ld) row[c] = c < K ? v[j] : 0.f;
+  }
+  for (int64_t c = 64 * NJ + lane; c < ld; c += 64) row[c] = 0.f;
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void k_c51_project_wide(const float* __restrict__ p, const float* __restrict__ rew,
+                                                          const float* __restrict__ done, const float* __restrict__ support,
+                                                          float gamma_n, float v_min, float v_max, float dz, int K, int64_t b,
+                                                          float* __restrict__ out) {
+  __shared__ C51Image image[4];
+  C51Image& img = image[threadIdx.x >> 6];
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  float zk[NJ], pv[NJ], o[NJ];
+  load_row_wide<NJ>(support, K, lane, zk);
+  for (int64_t i = wave; i < b; i += nw) {
+    load_row_wide<NJ>(p + i * K, K, lane, pv);
+    project_row_wide<NJ>(pv, zk, rew[i], done[i], gamma_n, v_min, v_max, dz, K, lane, img, o);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      if (lane + 64 * j < K) out[i * K + lane + 64 * j] = o[j];
+  }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void k_c51_bce_wide(const float* __restrict__ logits, const float* __restrict__ logits_t,
+                                                      int64_t ld, int K, const float* __restrict__ rew,
+                                                      const float* __restrict__ done, const float* __restrict__ support,
+                                                      float gamma_n, float v_min, float v_max, float dz, int64_t b,
+                                                      float* __restrict__ dy, float* __restrict__ proj_out,
+                                                      float* __restrict__ part) {
+  __shared__ C51Image image[4];
+  C51Image& img = image[threadIdx.x >> 6];
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const float inv_numel = 1.0f / ((float)b * (float)K);
+  float zk[NJ];
+  load_row_wide<NJ>(support, K, lane, zk);
+  float acc = 0.f;
+  for (int64_t i = wave; i < b; i += nw) {
+    const float r = rew[i], d = done[i];
+    float pt[NJ], t[NJ], pr[NJ];
+    load_row_wide<NJ>(logits_t + i * ld, K, lane, pt);
+    wave_softmax_wide<NJ>(pt, K, lane);
+    project_row_wide<NJ>(pt, zk, r, d, gamma_n, v_min, v_max, dz, K, lane, img, t);
+    load_row_wide<NJ>(logits_t + (b + i) * ld, K, lane, pt);
+    wave_softmax_wide<NJ>(pt, K, lane);
+    project_row_wide<NJ>(pt, zk, r, d, gamma_n, v_min, v_max, dz, K, lane, img, pr);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      t[j] = fminf(t[j], pr[j]);
+      if (proj_out && lane + 64 * j < K) proj_out[i * K + lane + 64 * j] = t[j];
+    }
+#pragma unroll
+    for (int net = 0; net < 2; ++net) {
+      const int64_t row = (int64_t)net * b + i;
+      float pc[NJ], gp[NJ];
+      load_row_wide<NJ>(logits + row * ld, K, lane, pc);
+      wave_softmax_wide<NJ>(pc, K, lane);
+      float dot = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        float le = 0.f;
+        gp[j] = 0.f;
+        if (lane + 64 * j < K) {
+          le = (t[j] - 1.f) * fmaxf(logf(1.f - pc[j]), -100.f) - t[j] * fmaxf(logf(pc[j]), -100.f);
+          gp[j] = (pc[j] - t[j]) / fmaxf((1.f - pc[j]) * pc[j], 1e-12f) * inv_numel;
+        }
+        acc += le;
+        dot += gp[j] * pc[j];
+      }
+      dot = wave_sum(dot);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) gp[j] = (gp[j] - dot) * pc[j];  // softmax backward (pc is 0 past K)
+      store_dy_row_wide<NJ>(dy + row * ld, ld, K, lane, gp);
+    }
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void k_dpg_dist_wide(const float* __restrict__ logits, int64_t ld, int K,
+                                                       const float* __restrict__ support, int64_t b, float* __restrict__ dy,
+                                                       float* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const float g = -1.0f / (float)b;
+  float zk[NJ];
+  load_row_wide<NJ>(support, K, lane, zk);
+  float acc = 0.f;
+  for (int64_t i = wave; i < b; i += nw) {
+    float p1[NJ], p2[NJ];
+    load_row_wide<NJ>(logits + i * ld, K, lane, p1);
+    load_row_wide<NJ>(logits + (b + i) * ld, K, lane, p2);
+    wave_softmax_wide<NJ>(p1, K, lane);
+    wave_softmax_wide<NJ>(p2, K, lane);
+    float q1 = 0.f, q2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      q1 += p1[j] * zk[j];
+      q2 += p2[j] * zk[j];
+    }
+    q1 = wave_sum(q1);
+    q2 = wave_sum(q2);
+    if (lane == 0) acc += fminf(q1, q2);
+    const float g1 = q1 < q2 ? g : (q1 == q2 ? 0.5f * g : 0.f);
+    const float g2 = q2 < q1 ? g : (q1 == q2 ? 0.5f * g : 0.f);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {   // dQ/dlogit_k = p_k (z_k - Q)
+      p1[j] = g1 * p1[j] * (zk[j] - q1);
+      p2[j] = g2 * p2[j] * (zk[j] - q2);
+    }
+    store_dy_row_wide<NJ>(dy + i * ld, ld, K, lane, p1);
+    store_dy_row_wide<NJ>(dy + (b + i) * ld, ld, K, lane, p2);
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// launch KERNEL<ceil(k / 64)> for 64 < k <= PQLK_C51_MAX_ATOMS
+#define C51_WIDE_LAUNCH(KERNEL, k, blocks, stream, ...)                                                               \
+  do {                                                                                                                \
+    const int nj__ = ((int)(k) + 63) / 64;                                                                            \
+    if (nj__ == 2) hipLaunchKernelGGL(KERNEL<2>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);            \
+    else if (nj__ == 3) hipLaunchKernelGGL(KERNEL<3>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);       \
+    else hipLaunchKernelGGL(KERNEL<4>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);                      \
+  } while (0)
+
 extern "C" int pqlk_c51_project(const float* p, const float* rew, const float* done, const float* support, float gamma_n,
                                 float v_min, float v_max, int32_t k, int64_t b, float* out, pqlk_stream_t stream) {
   PQLK_REQUIRE(p && rew && done && support && out, PQLK_E_NULL);
   PQLK_REQUIRE(b > 0 && k >= 2, PQLK_E_SHAPE);
-  PQLK_REQUIRE(k <= 64, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(k <= PQLK_C51_MAX_ATOMS, PQLK_E_UNSUPPORTED);
   const float dz = (float)(((double)v_max - (double)v_min) / (double)(k - 1));
   int blocks = (int)((b + 3) / 4);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_c51_project, dim3(blocks), dim3(256), 0, pqlk_s(stream), p, rew, done, support, gamma_n, v_min,
-                     v_max, dz, (int)k, b, out);
+  if (k <= 64)
+    hipLaunchKernelGGL(k_c51_project, dim3(blocks), dim3(256), 0, pqlk_s(stream), p, rew, done, support, gamma_n, v_min,
+                       v_max, dz, (int)k, b, out);
+  else
+    C51_WIDE_LAUNCH(k_c51_project_wide, k, blocks, stream, p, rew, done, support, gamma_n, v_min, v_max, dz, (int)k, b, out);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }
@@ -190,13 +433,17 @@ extern "C" int pqlk_c51_bce_loss(const float* logits, const float* logits_t, int
   PQLK_REQUIRE(logits && logits_t && rew && done && support && dy && scratch, PQLK_E_NULL);
   PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
   PQLK_REQUIRE(b > 0 && k >= 2, PQLK_E_SHAPE);
-  PQLK_REQUIRE(k <= 64, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(k <= PQLK_C51_MAX_ATOMS, PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(ld % 32 == 0 && ld >= k, PQLK_E_ALIGN);
   const float dz = (float)(((double)v_max - (double)v_min) / (double)(k - 1));
   int blocks = (int)((b + 3) / 4);
   if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
-  hipLaunchKernelGGL(k_c51_bce, dim3(blocks), dim3(256), 0, pqlk_s(stream), logits, logits_t, ld, (int)k, rew, done,
-                     support, gamma_n, v_min, v_max, dz, b, dy, proj_out, scratch);
+  if (k <= 64)
+    hipLaunchKernelGGL(k_c51_bce, dim3(blocks), dim3(256), 0, pqlk_s(stream), logits, logits_t, ld, (int)k, rew, done,
+                       support, gamma_n, v_min, v_max, dz, b, dy, proj_out, scratch);
+  else
+    C51_WIDE_LAUNCH(k_c51_bce_wide, k, blocks, stream, logits, logits_t, ld, (int)k, rew, done, support, gamma_n, v_min, v_max,
+                    dz, b, dy, proj_out, scratch);
   PQLK_LAUNCH_CHECK();
   if (!loss_out) return PQLK_OK;   // partials stay in scratch[0, pqlk_loss_parts(b, k))
   hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks,
@@ -264,7 +511,7 @@ static int dpg_loss_impl(const float* q, int64_t ld, int32_t k, const float* sup
   PQLK_REQUIRE(q && dy && scratch, PQLK_E_NULL);
   PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
   PQLK_REQUIRE(b > 0 && k >= 1, PQLK_E_SHAPE);
-  PQLK_REQUIRE(k <= 64, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(k <= PQLK_C51_MAX_ATOMS, PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(ld % 32 == 0 && ld >= k, PQLK_E_ALIGN);
   int blocks;
   if (k == 1) {
@@ -275,7 +522,10 @@ static int dpg_loss_impl(const float* q, int64_t ld, int32_t k, const float* sup
     PQLK_REQUIRE(support, PQLK_E_NULL);
     blocks = (int)((b + 3) / 4);
     if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_dpg_dist, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, ld, (int)k, support, b, dy, scratch);
+    if (k <= 64)
+      hipLaunchKernelGGL(k_dpg_dist, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, ld, (int)k, support, b, dy, scratch);
+    else
+      C51_WIDE_LAUNCH(k_dpg_dist_wide, k, blocks, stream, q, ld, (int)k, support, b, dy, scratch);
   }
   PQLK_LAUNCH_CHECK();
   if (!loss_out) return PQLK_OK;   // partials stay in scratch[0, pqlk_loss_parts(b, k))

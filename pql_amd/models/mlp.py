@@ -532,10 +532,18 @@ class DoubleQ(FusedMLP):
         return self._heads(state, action)[0]
 
 
+def check_num_atoms(num_atoms):
+    """The C51 loss kernels take 2 ... 256 atoms (PQLK_C51_MAX_ATOMS): anything else is an error where the critic is built, not a
+    PQLK_E_UNSUPPORTED at the first learner step."""
+    if int(num_atoms) != num_atoms or not 2 <= int(num_atoms) <= L.C51_MAX_ATOMS:
+        raise ValueError(f"num_atoms must be an integer from 2 to {L.C51_MAX_ATOMS} (the limit of the C51 loss kernels), got {num_atoms!r}")
+
+
 class DistributionalDoubleQ(DoubleQ):
     """mlp.py:244-267: twin categorical critics, softmax over `num_atoms` on a fixed support."""
 
     def __init__(self, state_dim, act_dim, v_min=-10, v_max=10, num_atoms=51, device="cuda", hidden_layers=None):
+        check_num_atoms(num_atoms)
         super().__init__(state_dim, act_dim, hidden_layers, out_dim=num_atoms)
         self.device = device
         self.v_min, self.v_max, self.num_atoms = v_min, v_max, int(num_atoms)
