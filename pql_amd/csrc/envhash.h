@@ -1,6 +1,8 @@
-// Counter-based uniform shared by the env-step kernels (synth.hip, pointmass.hip): a pure function of
-// (global env id, seed, counter, stream, column), so data-parallel shards reproduce slices of the global env.
-// Same constants as `_hash32` / `_uniform` of pql_amd/envs/synthetic.py.
+// Counter-based uniform shared by the env-step kernels (synth.hip, and through taskstep.h the hash-reset tasks
+// pointmass.hip and swingup.hip): a pure function of (global env id, seed, counter, stream, column), so data-parallel
+// shards reproduce slices of the global env.  Same constants as `_hash32` / `_uniform` of pql_amd/envs/base.py.
+// A new hash-reset task is a task struct for `k_task_step` (taskstep.h says what it has to supply), its own stream
+// numbers for uni_key, and an `extern "C"` entry point that calls `launch_task_step`.
 #pragma once
 #include "pqlk_common.h"
 

@@ -13,35 +13,21 @@ from __future__ import annotations
 
 import math
 import os
-from types import SimpleNamespace
 
 import torch
 
+from pql_amd.envs.base import VecEnvBase, _hash32  # noqa: F401  (`_hash32` is imported from here too)
+from pql_amd.envs.pointmass import PointMassVecEnv
+from pql_amd.envs.swingup import SwingUpVecEnv
+
 TASK_SHAPES = dict(AllegroHand=(88, 16), ShadowHand=(211, 20), Humanoid=(108, 21), Ant=(60, 8), Anymal=(48, 12), Toy=(8, 2))
 
-_M = 0xFFFFFFFF
 
-
-def _hash32(x):
-    """xorshift-multiply avalanche on int64 tensors holding 32-bit values."""
-    x = x & _M
-    x = ((x ^ (x >> 16)) * 0x7FEB352D) & _M
-    x = ((x ^ (x >> 15)) * 0x846CA68B) & _M
-    return x ^ (x >> 16)
-
-
-class SyntheticVecEnv:
+class SyntheticVecEnv(VecEnvBase):
     def __init__(self, num_envs, obs_dim, act_dim, device="cuda", seed=42, episode_length=300, env_offset=0):
-        self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
-        self.device = torch.device(device)
-        self.seed = int(seed)
-        self.max_episode_length = int(episode_length)
-        self.observation_space = SimpleNamespace(shape=(self.obs_dim,))
-        self.action_space = SimpleNamespace(shape=(self.act_dim,))
+        super().__init__(num_envs, obs_dim, act_dim, device, seed, episode_length, env_offset)
         self.t = 0
-        self.env_ids = (torch.arange(self.num_envs, device=self.device, dtype=torch.int64) + int(env_offset))
         self._p_done = 1.0 / float(episode_length)
-        self.env_offset = int(env_offset)
         self._no_trunc = None
         self._obs = None
 
@@ -65,13 +51,10 @@ class SyntheticVecEnv:
     def state_dict(self):
         """Everything the next transitions depend on besides the constructor arguments: the step counter (and the last
         observation handed out)."""
-        return {"t": int(self.t), "obs": None if self._obs is None else self._obs.detach().clone(),
-                "seed": self.seed, "num_envs": self.num_envs, "env_offset": self.env_offset}
+        return {"t": int(self.t), "obs": None if self._obs is None else self._obs.detach().clone(), **self._header()}
 
     def load_state_dict(self, state):
-        for key in ("seed", "num_envs", "env_offset"):
-            if int(state[key]) != getattr(self, key):
-                raise ValueError(f"SyntheticVecEnv.load_state_dict: {key}={getattr(self, key)} but the state was saved with {int(state[key])}")
+        self._check_header(state)
         self.t = int(state["t"])
         self._obs = None if state["obs"] is None else state["obs"].to(self.device, torch.float32).clone()
 
@@ -108,9 +91,13 @@ class SyntheticVecEnv:
         return next_obs, reward, done, {"TimeLimit.truncated": self._no_trunc}
 
 
+# task.kind -> env class: the one place a task is registered (tools/learn_pointmass.py reads it too)
+TASK_ENVS = {"synthetic": SyntheticVecEnv, "pointmass": PointMassVecEnv, "swingup": SwingUpVecEnv}
+
+
 def create_task_env(cfg, num_envs=None, env_offset=0):
-    """Stand-in for pql.utils.isaacgym_util.create_task_env (:8-24).  `task.kind` picks the env: absent / synthetic = the
-    counter-based generator above, pointmass / swingup = the learnable tasks of pql_amd/envs/pointmass.py and pql_amd/envs/swingup.py."""
+    """Stand-in for pql.utils.isaacgym_util.create_task_env (:8-24).  `task.kind` picks the env from TASK_ENVS: absent / synthetic =
+    the counter-based generator above, pointmass / swingup = the learnable tasks of pql_amd/envs/pointmass.py and pql_amd/envs/swingup.py."""
     task = cfg.task
     name = task.name if task is not None else "AllegroHand"
     O, A = TASK_SHAPES.get(name, (88, 16))
@@ -119,15 +106,6 @@ def create_task_env(cfg, num_envs=None, env_offset=0):
         A = int(task.act_dim) if task.get("act_dim") else A
     ep = int(task.get("episode_length") or 300) if task is not None else 300
     kind = (task.get("kind") if task is not None else None) or "synthetic"   # absent = the synthetic env, as before `kind` existed
-    if kind == "pointmass":
-        from pql_amd.envs.pointmass import PointMassVecEnv
-        return PointMassVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
-                               env_offset=env_offset)
-    if kind == "swingup":
-        from pql_amd.envs.swingup import SwingUpVecEnv
-        return SwingUpVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
-                             env_offset=env_offset)
-    if kind != "synthetic":
-        raise ValueError(f"task.kind={kind}: no such env; known kinds: synthetic, pointmass, swingup")
-    return SyntheticVecEnv(num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep,
-                           env_offset=env_offset)
+    if kind not in TASK_ENVS:
+        raise ValueError(f"task.kind={kind}: no such env; known kinds: {', '.join(TASK_ENVS)}")
+    return TASK_ENVS[kind](num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep, env_offset=env_offset)

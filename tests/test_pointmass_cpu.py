@@ -8,6 +8,7 @@ import torch
 from pql_amd.envs.pointmass import PointMassVecEnv, episode_return, pd_policy, zero_policy
 from pql_amd.envs.synthetic import SyntheticVecEnv, create_task_env
 from pql_amd.utils.cfg import load_cfg
+from task_cases import u_np
 
 F = np.float32
 
@@ -25,26 +26,13 @@ def _set(env, x=None, v=None, g=None):
 def _reset_obs(env, ep):
     """Start-of-episode observation recomputed from the hash with plain python integers: x = 2 u(e, ep, 11, j) - 1,
     g = 2 u(e, ep, 12, j) - 1, v = 0."""
-    M = 0xFFFFFFFF
-
-    def h32(x):
-        x &= M
-        x = ((x ^ (x >> 16)) * 0x7FEB352D) & M
-        x = ((x ^ (x >> 15)) * 0x846CA68B) & M
-        return x ^ (x >> 16)
-
-    def u(e, stream, j):
-        key = h32(e * 0x9E3779B1 + env.seed * 0x85EBCA77 + ep * 0xC2B2AE3D + stream * 0x27D4EB2F)
-        h = h32(key * 0x165667B1 + j * 0x9E3779B1 + 0x5BD1E995)
-        return (F(h) + F(0.5)) * F(1.0 / 4294967296.0)
-
     A = env.act_dim
     obs = np.zeros((env.num_envs, env.obs_dim), dtype=np.float32)
     for i in range(env.num_envs):
         e = env.env_offset + i
         for j in range(A):
-            obs[i, j] = F(2.0) * u(e, 11, j) - F(1.0)
-            obs[i, 2 * A + j] = F(2.0) * u(e, 12, j) - F(1.0)
+            obs[i, j] = F(2.0) * u_np(env.seed, e, ep, 11, j) - F(1.0)
+            obs[i, 2 * A + j] = F(2.0) * u_np(env.seed, e, ep, 12, j) - F(1.0)
     return torch.from_numpy(obs)
 
 

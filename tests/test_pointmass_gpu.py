@@ -1,14 +1,13 @@
 """PointMass on the GPU: the one-launch HIP step against its torch definition (bit-equal), the rollout's n-step rows with REAL
 time-limit truncations and terminals against the oracle's assembler, bit-exact resume of a DDPG run on the task, and the one thing no
 other test in this tree observes: a training run that improves a policy.  Run with `pytest -m gpu`."""
-import importlib.util
 import os
 import sys
-from collections import deque
 
-import numpy as np
 import pytest
 import torch
+
+import task_cases as tc
 
 pytestmark = pytest.mark.gpu
 
@@ -32,23 +31,7 @@ def _keep_sigint():
     signal.signal(signal.SIGINT, old)
 
 
-def _load(path, name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, path))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 # --------------------------------------------------------------------------- the kernel
-def pointmass_actions(n, A, steps, seed=0):
-    """Per step (n, A): 3 U(-1, 1), so the clamp is live; every fourth env pushes with a = +1 throughout, so some leave the box."""
-    g = torch.Generator().manual_seed(seed)
-    acts = [3.0 * (2.0 * torch.rand((n, A), generator=g) - 1.0) for _ in range(steps)]
-    for a in acts:
-        a[::4] = 1.0
-    return acts
-
-
 @pytest.mark.parametrize("n,O,A,off", [(33, 8, 2, 7), (257, 88, 16, 0), (1024, 211, 20, 1024), (64, 6, 2, 0)])
 def test_pointmass_kernel_equals_torch_definition(dev, n, O, A, off):
     """`pqlk_pointmass_step` vs `_step_torch` on the same device: observations, rewards, dones, truncations and every state tensor
@@ -59,7 +42,7 @@ def test_pointmass_kernel_equals_torch_definition(dev, n, O, A, off):
     b = PointMassVecEnv(n, O, A, device=dev, seed=1234, episode_length=5, env_offset=off)
     assert torch.equal(a.reset(), b.reset())
     seen = dict(oob=0, truncated=0, running=0)
-    for act in pointmass_actions(n, A, 12):
+    for act in tc.task_actions(n, A, 12):
         act = act.to(dev)
         oa, ra, da, ia = a.step(act)                 # the HIP launch
         ob, rb, db, ib = b._step_torch(act)          # the definition
@@ -77,120 +60,26 @@ def test_pointmass_kernel_equals_torch_definition(dev, n, O, A, off):
 
 
 # --------------------------------------------------------------------------- rollout integration
-class _RecordingEnv:
-    def __init__(self, env):
-        self.env, self.log, self.first_obs = env, [], None
-        self.observation_space, self.action_space = env.observation_space, env.action_space
-        self.max_episode_length, self.num_envs = env.max_episode_length, env.num_envs
-
-    def reset(self):
-        self.first_obs = self.env.reset()
-        return self.first_obs
-
-    def step(self, action):
-        out = self.env.step(action)
-        self.log.append(tuple(x.clone().cpu() for x in (action, out[0], out[1], out[2], out[3]["TimeLimit.truncated"])))
-        return out
-
-
 @pytest.mark.parametrize("timeout", [True, False])
 def test_rollout_nstep_rows_with_real_truncations(dev, timeout):
     """`PQLActor.explore_env` on PointMass (nstep 3, two calls of T = 8, episode_length 5, 32 envs): the emitted n-step rows equal
     `oracle.pql_ref_cpu.NStepRef` fed the very same transitions, bit for bit.  With handle_timeout a window that holds only a time
     limit carries done = 0 and bootstraps from the window's last next_obs (past the reset, as the reference does); without it the
     row is terminal and stops at the truncated step.  Episode windows equal a host recomputation."""
-    import detdata as dd
-    from oracle import pql_ref_cpu as ref
-    from pql_amd.algo.pql_actor import PQLActor
     from pql_amd.envs.pointmass import PointMassVecEnv
-    from pql_amd.envs.synthetic import create_task_env
-    from pql_amd.models.mlp import TanhMLPPolicy
-    from pql_amd.utils.cfg import load_cfg
-    N, O, A, n, T, WIN = 32, 8, 2, 3, 8, 20
-    cfg = load_cfg(["task=pointmass", "task.episode_length=5", f"num_envs={N}", f"algo.tracker_len={WIN}", "algo.v_learner_gpu=0",
-                    "algo.p_learner_gpu=0", "algo.num_gpus=1", "sim_device=cuda:0", "device=cuda:0", f"algo.nstep={n}",
-                    f"algo.handle_timeout={timeout}"])
-    inner = create_task_env(cfg)
-    assert isinstance(inner, PointMassVecEnv)
-    env = _RecordingEnv(inner)
-    actor = PQLActor(env, cfg)
-    pol = TanhMLPPolicy((O,), A).to(dev)
-    pol.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in dd.mlp_state(O, A, 17).items()})
-    actor.set_actor(pol)
-    actor.reset_agent()
-    inner.x[::4, 0], inner.v[::4, 0] = 1.4, 0.9       # leave the box in the first step whatever the action (x' >= 1.4 + 0.25 * 0.52)
-    inner.x[1::8, 0], inner.v[1::8, 0] = 1.25, 0.9    # ... and some a step or two later, or not at all: terminals inside the windows
-    actor.obs = inner._observe()
 
-    ns = ref.NStepRef(O, A, N, n)
-    ret_win, len_win = deque([0.0] * WIN, maxlen=WIN), deque([0.0] * WIN, maxlen=WIN)
-    cur_ret, cur_len = torch.zeros(N), torch.zeros(N)
-    g = torch.Generator().manual_seed(5)
-    obs, cursor = actor.obs.cpu(), 0
-    trunc_only = terminal = 0
-    for _call in range(2):
-        draws = [torch.randn((N, A), generator=g) for _ in range(T)]
-        p_data, v_data, steps = actor.explore_env(env, T, random=False, draws=[d.to(dev) for d in draws])
-        torch.cuda.synchronize()
-        sl = [torch.zeros((N, T, O)), torch.zeros((N, T, A)), torch.zeros((N, T, 1)), torch.zeros((N, T, O)), torch.zeros((N, T, 1))]
-        raw_done, raw_trunc = torch.zeros((N, T), dtype=torch.bool), torch.zeros((N, T), dtype=torch.bool)
-        for t in range(T):
-            act, nobs, rew, done, trunc = env.log[cursor]; cursor += 1
-            cur_ret += rew; cur_len += 1                                 # trackers see the env's own done (pql_actor.py:129-135)
-            ret_win.extend(cur_ret[done].tolist()); len_win.extend(cur_len[done].tolist())
-            cur_ret[done] = 0; cur_len[done] = 0
-            d = (done & ~trunc) if timeout else done                     # handle_timeout (common.py:195-202)
-            sl[0][:, t] = obs; sl[1][:, t] = act; sl[2][:, t, 0] = rew; sl[3][:, t] = nobs; sl[4][:, t, 0] = d.float()
-            raw_done[:, t], raw_trunc[:, t] = done, trunc
-            obs = nobs
-        first_call = ns.count == 0
-        want = ns.add(*sl)
-        assert steps == T * N
-        for name, got, exp in zip(("obs", "action", "reward", "next_obs", "done"), v_data, want):
-            assert got.shape == exp.shape and torch.equal(got.cpu(), exp), name
-        assert torch.equal(p_data.cpu(), want[0])
-        # what the rows mean, read off the raw transitions (first call: block b of N rows is the window of steps b .. b + n - 1)
-        if first_call:
-            got_nobs, got_done = v_data[3].cpu().view(T - n + 1, N, O), v_data[4].cpu().view(T - n + 1, N)
-            for b in range(T - n + 1):
-                w_done, w_trunc = raw_done[:, b:b + n], raw_trunc[:, b:b + n]
-                only_trunc = w_trunc.any(1) & ~(w_done & ~w_trunc).any(1)
-                first = w_done.float().argmax(1)
-                for e in torch.where(only_trunc)[0].tolist():
-                    trunc_only += 1
-                    if timeout:
-                        assert got_done[b, e] == 0 and torch.equal(got_nobs[b, e], sl[3][e, b + n - 1])
-                    else:
-                        assert got_done[b, e] == 1 and torch.equal(got_nobs[b, e], sl[3][e, b + int(first[e])])
-                for e in torch.where((w_done & ~w_trunc).any(1))[0].tolist():
-                    terminal += 1
-                    assert got_done[b, e] == 1
-        assert actor.return_tracker.mean() == pytest.approx(float(np.mean(ret_win)), rel=1e-5, abs=1e-7)
-        assert actor.step_tracker.mean() == pytest.approx(float(np.mean(len_win)), rel=1e-6)
-        assert torch.equal(actor.obs.cpu(), obs)
-    assert trunc_only > 0 and terminal > 0, (trunc_only, terminal)
-    assert sum(x != 0 for x in len_win) == WIN                          # 32 envs hit the time limit in ONE step: more than the window holds
+    def leave_the_box(inner):
+        inner.x[::4, 0], inner.v[::4, 0] = 1.4, 0.9       # leave the box in the first step whatever the action (x' >= 1.4 + 0.25 * 0.52)
+        inner.x[1::8, 0], inner.v[1::8, 0] = 1.25, 0.9    # ... and some a step or two later, or not at all: terminals inside the windows
+
+    tc.check_rollout_nstep_rows(dev, "pointmass", PointMassVecEnv, timeout, terminals=True, prepare=leave_the_box)
 
 
 # --------------------------------------------------------------------------- resume
 def test_ddpg_resume_on_pointmass_is_bit_exact(tmp_path):
     """scripts/train_baselines.py on PointMass: 6 iterations + checkpoint, then resumed (same process) to 12 == 12 uninterrupted:
     the env's episode state (x, v, g, k, ep) travels in the checkpoint."""
-    tb = _load("scripts/train_baselines.py", "train_baselines_pm")
-    from pql_amd.utils.cfg import load_cfg
-    N = 32
-    base = ["algo=ddpg_algo", "task=pointmass", "task.episode_length=5", f"num_envs={N}", "algo.batch_size=64", "algo.memory_size=4000",
-            "algo.hidden_layers=[64, 64]"]
-    upto = lambda iters: f"max_step={(32 + iters) * N - 1}"   # noqa: E731  (warm_up = 32 steps, then N env steps per iteration)
-    a = tb.main(load_cfg(base + [upto(12)]))
-    ck = tmp_path / "ck"
-    b1 = tb.main(load_cfg(base + [upto(6), f"checkpoint.dir={ck}"]))
-    assert (a["iters"], b1["iters"]) == (12, 6) and b1["actor_sha"] != a["actor_sha"]
-    b2 = tb.main(load_cfg(base + [upto(12), f"resume={ck}"]))
-    assert b2["resumed_from"]["global_steps"] == b1["global_steps"] and b2["resumed_from"]["actor_sha"] == b1["actor_sha"]
-    for key in ("actor_sha", "critic_sha", "replay_sha", "global_steps", "iters", "train/critic_loss", "train/actor_loss", "train/return",
-                "train/episode_length"):
-        assert a[key] == b2[key], key
+    tc.check_ddpg_resume(tmp_path, "pointmass", "train_baselines_pm")
 
 
 # --------------------------------------------------------------------------- it learns
@@ -205,7 +94,7 @@ F_MIN = 0.5 * 0.9469
 def test_ddpg_learns_pointmass():
     """DDPG at (8, 2), 64 envs, batch 256, hidden [128, 128], episode_length 64, seed 0: the trained deterministic policy closes at
     least F_MIN of the gap between the zero action and the PD controller, both measured here on 256 evaluation envs."""
-    lp = _load("tools/learn_pointmass.py", "learn_pointmass")
+    lp = tc.load_script("tools/learn_pointmass.py", "learn_pointmass")
     r = lp.run("ddpg", "small", 0, LEARN_ITERS)
     print(f"pointmass ddpg seed 0, {LEARN_ITERS} iterations: R={r['R']:.3f} R_zero={r['R_zero']:.3f} R_pd={r['R_pd']:.3f} f={r['f']:.4f} "
           f"wall={r['wall_s']}s")

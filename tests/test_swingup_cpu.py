@@ -14,6 +14,7 @@ from pql_amd.envs.pointmass import episode_return as pointmass_episode_return
 from pql_amd.envs.swingup import SwingUpVecEnv, energy_policy, episode_return, zero_policy
 from pql_amd.envs.synthetic import TASK_SHAPES, SyntheticVecEnv, create_task_env
 from pql_amd.utils.cfg import load_cfg
+from task_cases import u_np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -33,21 +34,6 @@ def rot_np(c, s, d):
     sn = s * cd + c * sd
     m = F(1.5) - F(0.5) * (cn * cn + sn * sn)
     return cn * m, sn * m
-
-
-def u_np(seed, e, ep, stream, j):
-    """The counter-based uniform with plain python integers."""
-    M = 0xFFFFFFFF
-
-    def h32(x):
-        x &= M
-        x = ((x ^ (x >> 16)) * 0x7FEB352D) & M
-        x = ((x ^ (x >> 15)) * 0x846CA68B) & M
-        return x ^ (x >> 16)
-
-    key = h32(e * 0x9E3779B1 + seed * 0x85EBCA77 + ep * 0xC2B2AE3D + stream * 0x27D4EB2F)
-    h = h32(key * 0x165667B1 + j * 0x9E3779B1 + 0x5BD1E995)
-    return (F(h) + F(0.5)) * F(1.0 / 4294967296.0)
 
 
 def _reset_obs(env, ep):

@@ -36,14 +36,16 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from pql_amd.envs import swingup  # noqa: E402
-from pql_amd.envs.pointmass import PointMassVecEnv, episode_return, pd_policy, zero_policy  # noqa: E402
+from pql_amd.envs.pointmass import episode_return, pd_policy, zero_policy  # noqa: E402
+from pql_amd.envs.synthetic import TASK_ENVS  # noqa: E402
 from pql_amd.utils.cfg import load_cfg  # noqa: E402
 
 EPISODE_LENGTH = 64
-# task -> env class, episode length, (lower, upper) yardstick controllers and the record's key for the upper one
+# task -> env class (the one `create_task_env` builds for that `task.kind`), episode length, (lower, upper) yardstick controllers and the
+# record's key for the upper one
 TASKS = {
-    "pointmass": dict(env=PointMassVecEnv, episode_length=EPISODE_LENGTH, zero=zero_policy, ctrl=pd_policy, ctrl_key="R_pd"),
-    "swingup": dict(env=swingup.SwingUpVecEnv, episode_length=128, zero=swingup.zero_policy, ctrl=swingup.energy_policy, ctrl_key="R_ctrl"),
+    "pointmass": dict(env=TASK_ENVS["pointmass"], episode_length=EPISODE_LENGTH, zero=zero_policy, ctrl=pd_policy, ctrl_key="R_pd"),
+    "swingup": dict(env=TASK_ENVS["swingup"], episode_length=128, zero=swingup.zero_policy, ctrl=swingup.energy_policy, ctrl_key="R_ctrl"),
 }
 EVAL_ENVS = 256
 WARM_UP = 32   # algo.warm_up default: random-policy env steps in front of the first iteration
@@ -108,7 +110,7 @@ def run(algo, shape, seed, iters, extra=(), task="pointmass"):
                 **{TASKS[task]["ctrl_key"]: r_pd}, f=(got["R"] - r_zero) / (r_pd - r_zero), wall_s=round(wall, 2))
 
 
-def env_step_time(env_cls=PointMassVecEnv, num_envs=4096, obs_dim=88, act_dim=16, steps=2000, rounds=3, episode_length=EPISODE_LENGTH):
+def env_step_time(env_cls=TASK_ENVS["pointmass"], num_envs=4096, obs_dim=88, act_dim=16, steps=2000, rounds=3, episode_length=EPISODE_LENGTH):
     """Microseconds per env step of `env_cls`'s one-launch HIP step and of its torch definition on the GPU (host clock around `steps`
     steps that end in a device synchronise; the two forms alternate, the best of `rounds` is kept; one warm-up round)."""
     mk = lambda: env_cls(num_envs, obs_dim, act_dim, device="cuda:0", seed=1, episode_length=episode_length)   # noqa: E731
