@@ -574,6 +574,19 @@ int pqlk_swingup_step(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed
                       int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k, int32_t* ep,
                       float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, pqlk_stream_t stream);
 
+/* The two steps above with the task's info channels (pql_amd/envs/base.py `info_keys`): the same launch, the same argument list
+ * plus `info` in front of the stream, every other output bit-identical.  info is channel-major (n_info, N) floats with row stride
+ * N; row c holds channel c of the step just taken, for a finished env the value BEFORE its reset:
+ *   pointmass: 0 = dist2 = mean_j (x' - g)^2, the very value of the reward; 1 = oob = 1.0 where the step left the box, else 0.0;
+ *   swingup:   0 = upright = mean_j c'; 1 = effort = mean_j a^2 of the clamped action; both sums in index order from the j = 0 term.
+ * PQLK_E_NULL: info NULL, besides the errors of the plain entries. */
+int pqlk_pointmass_step_info(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                             int32_t episode_length, const float* action, float* x, float* v, float* g, int32_t* k, int32_t* ep,
+                             float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, float* info, pqlk_stream_t stream);
+int pqlk_swingup_step_info(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                           int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k, int32_t* ep,
+                           float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, float* info, pqlk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Per-env-step bookkeeping of the rollout in one launch (pql_actor.py:104-114 slab writes, :129-135 update_tracker,
  * common.py:195-202 handle_timeout): column t of the (N, horizon, .) trajectory slabs <- (obs, action, reward, next_obs,
@@ -585,6 +598,34 @@ int pqlk_rollout_step(int64_t n, int32_t obs_dim, int32_t act_dim, int32_t horiz
                       const uint8_t* truncated, float* slab_obs, float* slab_act, float* slab_rew, float* slab_nobs,
                       float* slab_done, float* cur_return, float* cur_length, float* win_return, float* win_length,
                       int64_t* win_return_ptr, int64_t* win_length_ptr, int32_t win_len, pqlk_stream_t stream);
+
+/* The info trackers of one env step in one launch (`info_track_keys` / `info_track_step`: pql/algo/pql_actor.py:28-33,138-151,
+ * pql/algo/ac_base.py:54-59,88-101, pql/utils/evaluator.py:56-61,89-111, where every key costs a `torch.where(done)[0]`, a `.cpu()`
+ * and a `deque.extend` per env step).  One 1024-thread block per key; per key, with value(e) = values[e] (PQLK_INFO_F32) or
+ * values[e] != 0 as 0.0 / 1.0 (PQLK_INFO_U8: bool / uint8 bytes):
+ *   PQLK_INFO_LAST         value(e) of the envs with done[e] != 0 is appended IN ENV ORDER to the key's window;
+ *   PQLK_INFO_ALL_EPISODE  acc[e] += value(e) for every env, then acc[e] of the done envs is appended and set to zero;
+ *   PQLK_INFO_ALL_STEP     value(e) of every env is appended;
+ * appended = written behind the window's device write pointer ring_ptr[0] (in [0, win_len)), which advances by the number of
+ * appended values modulo win_len; when one step appends more than win_len values only the last win_len stay, like deque.extend
+ * (and like the windows of pqlk_rollout_step, whose ordered block-wide append this is).  ring holds win_len floats, acc (N)
+ * floats (read only by ALL_EPISODE, may be NULL otherwise), done (N) bytes.  Keys must not share rings, pointers or accumulators.
+ * Deterministic: no atomics, no host sync; bit-equal to the torch form in pql_amd/utils/info_track.py.
+ * PQLK_E_NULL: done, keys, or a key's values / ring / ring_ptr NULL, acc NULL under ALL_EPISODE.  PQLK_E_SHAPE: n <= 0,
+ * win_len <= 0, n_keys outside [1, PQLK_INFO_MAX_KEYS].  PQLK_E_UNSUPPORTED: an unknown dtype or mode. */
+#define PQLK_INFO_MAX_KEYS 8
+enum { PQLK_INFO_F32 = 0, PQLK_INFO_U8 = 1 };
+enum { PQLK_INFO_LAST = 0, PQLK_INFO_ALL_EPISODE = 1, PQLK_INFO_ALL_STEP = 2 };
+typedef struct PqlInfoKey {
+  const void* values; /* (N) this step's values of the key */
+  float* acc;         /* (N) per-env running sum (ALL_EPISODE) */
+  float* ring;        /* window of win_len floats */
+  int64_t* ring_ptr;  /* the window's write pointer */
+  int32_t dtype;      /* PQLK_INFO_F32 / PQLK_INFO_U8 */
+  int32_t mode;       /* PQLK_INFO_LAST / _ALL_EPISODE / _ALL_STEP */
+} PqlInfoKey;
+int pqlk_rollout_info(int64_t n, const uint8_t* done, int32_t win_len, int32_t n_keys, const PqlInfoKey* keys,
+                      pqlk_stream_t stream);
 
 /* The remaining per-env-step elementwise work of the rollout, one launch each (the reference issues 12 + 4 + 4 ATen launches):
  * RunningMeanStd.update_from_moments (pql/utils/torch_util.py:91-103): Chan merge of one batch's moments into the running

@@ -16,6 +16,9 @@ LIB_FILE = Path(os.environ.get("PQLK_LIB", _HERE / "csrc" / "libpqlk.so"))   # P
 
 MAX_LAYERS = 8
 OBS_F32, OBS_F16 = 0, 1   # PqlReplayDesc.obs_dtype (PQLK_OBS_*)
+INFO_MAX_KEYS = 8         # PQLK_INFO_MAX_KEYS: keys of one pqlk_rollout_info launch
+INFO_F32, INFO_U8 = 0, 1  # PqlInfoKey.dtype (PQLK_INFO_*)
+INFO_LAST, INFO_ALL_EPISODE, INFO_ALL_STEP = 0, 1, 2   # PqlInfoKey.mode
 ACT_NONE, ACT_TANH, ACT_TANH_NOISE = 0, 1, 2
 C51_MAX_ATOMS = 256       # PQLK_C51_MAX_ATOMS: the C51 loss kernels hold one row's atoms in one wave, four per lane at most
 
@@ -27,6 +30,11 @@ class PqlReplayDesc(C.Structure):
 
 class PqlMlpDesc(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("n_nets", C.c_int32), ("dims", C.c_int32 * (MAX_LAYERS + 1))]
+
+
+class PqlInfoKey(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("acc", C.c_void_p), ("ring", C.c_void_p), ("ring_ptr", C.c_void_p), ("dtype", C.c_int32),
+                ("mode", C.c_int32)]
 
 
 _P, _I64, _I32, _F, _D = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_double
@@ -99,7 +107,10 @@ PROTOTYPES = {
     "pqlk_synth_env_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, C.c_uint32, _F, _P, _P, _P, _P, _P]),
     "pqlk_pointmass_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pqlk_swingup_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pqlk_pointmass_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pqlk_swingup_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pqlk_rollout_step": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "pqlk_rollout_info": (C.c_int, [_I64, _P, _I32, _I32, C.POINTER(PqlInfoKey), _P]),
     "pqlk_batch_moments": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _P, _P]),
     "pqlk_rms_merge": (C.c_int, [_P, _P, _P, _P, _F, _F, _F, _I32, _P, _P, _P]),
     "pqlk_rms_normalize": (C.c_int, [_P, _I64, _I32, _P, _P, _F, _P, _I64, _P]),

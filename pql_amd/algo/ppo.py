@@ -17,6 +17,7 @@ from pql_amd import _lib as L
 from pql_amd.algo.learner import _AdamState, _cfg_get, apply_optimizer, make_actor, make_critic
 from pql_amd.algo.pql_actor import DeviceTracker, PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
+from pql_amd.utils.info_track import InfoTrackers
 from pql_amd.utils.torch_util import RunningMeanStd
 
 TIMEOUT_KEYS = ("TimeLimit.truncated", "time_outs")
@@ -32,8 +33,6 @@ class AgentPPO:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.device = self.sim_device = dev
         algo = cfg.algo
-        if cfg.info_track_keys is not None:
-            raise NotImplementedError("info_track_keys needs a simulator's info dict; out of scope")
         self.actor = make_actor(cfg, self.obs_dim, self.action_dim, dev)   # actor first: both consume the CPU generator
         self.critic = make_critic(cfg, self.obs_dim, self.action_dim, dev)
         if not hasattr(self.actor, "logstd_block") or self.critic.layout.dims[-1] != 1:
@@ -43,6 +42,7 @@ class AgentPPO:
         self.return_tracker = DeviceTracker(algo.tracker_len, dev)
         self.step_tracker = DeviceTracker(algo.tracker_len, dev)
         self.success_tracker = DeviceTracker(algo.tracker_len, dev)
+        self.info_trackers = InfoTrackers.from_cfg(cfg, env, n, algo.tracker_len, dev)   # ac_base.py:54-59 (empty without info_track_keys)
         self.current_returns = torch.zeros(n, dtype=torch.float32, device=dev)
         self.current_lengths = torch.zeros(n, dtype=torch.float32, device=dev)
         self.obs_rms = RunningMeanStd(shape=self.obs_dim, device=dev) if algo.obs_norm else None
@@ -66,8 +66,7 @@ class AgentPPO:
         if isinstance(info, dict) and "success" in info:
             self.success_tracker.update(info["success"].to(torch.float32), done.bool())
 
-    def add_info_tracker_log(self, log_info):
-        return log_info
+    add_info_tracker_log = PQLActor.add_info_tracker_log   # ac_base.py:116-119
 
     def _layout(self):
         return self.actor.layout, self.critic.layout

@@ -6,6 +6,8 @@ Drop-in for `pql/algo/pql_actor.py` (`PQLActor(env, cfg)`: `reset_agent`, `explo
 Differences that matter on MI355X: no per-step host sync (episode trackers are device rings read at log time; the
 reference's `torch.where(done)[0]` + `.tolist()` (:129-135) stalls the stream every env step), batch moments and the
 n-step window run as single HIP launches, and data parallel ranks index the GLOBAL env axis for the mixed noise.
+`info_track_keys` (pql_actor.py:28-33,138-151) are device windows too: `pql_amd.utils.info_track.InfoTrackers`, one launch per env
+step for all keys; with the default `info_track_keys: null` nothing of it is allocated or launched.
 """
 from __future__ import annotations
 
@@ -14,6 +16,7 @@ import torch
 from pql_amd.replay.nstep_replay import NStepReplay
 from pql_amd.utils import handoff as H
 from pql_amd.utils.common import handle_timeout
+from pql_amd.utils.info_track import InfoTrackers
 from pql_amd.utils.noise import add_mixed_normal_noise, add_normal_noise
 from pql_amd.utils.schedule_util import ExponentialSchedule, LinearSchedule
 from pql_amd.utils.torch_util import RunningMeanStd
@@ -62,9 +65,8 @@ class PQLActor:
         self.env_offset, self.total_envs = int(env_offset), total_envs   # position on the GLOBAL env axis (data parallel)
         self._actor = None  # rollout replica of the policy, assigned by the driver (`actor` is a property: see below)
         self.obs = None
-        if cfg.info_track_keys is not None:
-            raise NotImplementedError("info_track_keys needs a simulator's info dict; out of scope")
         algo, n, dev = cfg.algo, cfg.num_envs, self.sim_device
+        self.info_trackers = InfoTrackers.from_cfg(cfg, env, n, algo.tracker_len, dev)   # (empty without info_track_keys)
         self.return_tracker = DeviceTracker(algo.tracker_len, dev)
         self.step_tracker = DeviceTracker(algo.tracker_len, dev)
         self.current_returns = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -112,9 +114,11 @@ class PQLActor:
 
     def training_state(self):
         """Rollout side: running statistics, the policy replica, the current observation, per-env accumulators, the episode
-        windows, the noise schedule, the exploration generator and the n-step windows (the caller has synchronised)."""
+        windows, the noise schedule, the exploration generator and the n-step windows (the caller has synchronised); with
+        info_track_keys also their windows, pointers and accumulators."""
         rms, sch = self.obs_rms, self.noise_scheduler
-        return {"tensors": {k: t.detach().cpu() for k, t in self._state_tensors().items()},
+        info = {"info_trackers": self.info_trackers.training_state()} if len(self.info_trackers) else {}
+        return {**info, "tensors": {k: t.detach().cpu() for k, t in self._state_tensors().items()},
                 "obs_rms": None if rms is None else (rms.mean.detach().cpu(), rms.var.detach().cpu(), float(rms.count)),
                 "obs": None if self.obs is None else self.obs.detach().cpu(),
                 "return_tracker": self.return_tracker.training_state(), "step_tracker": self.step_tracker.training_state(),
@@ -138,6 +142,8 @@ class PQLActor:
         self.obs = None if st["obs"] is None else st["obs"].to(self.sim_device)
         self.return_tracker.load_training_state(st["return_tracker"])
         self.step_tracker.load_training_state(st["step_tracker"])
+        if len(self.info_trackers):   # (a checkpoint without the entry: the info windows start from zero)
+            self.info_trackers.load_training_state(st.get("info_trackers"))
         if self.noise_scheduler is not None and st["noise"] is not None:
             self.noise_scheduler.count, self.noise_scheduler.last_val = int(st["noise"][0]), float(st["noise"][1])
         if self.gen is not None and st["gen"] is not None:
@@ -345,6 +351,7 @@ class PQLActor:
                                             L.ptr(self.current_returns), L.ptr(self.current_lengths), L.ptr(self.return_tracker.ring),
                                             L.ptr(self.step_tracker.ring), L.ptr(self.return_tracker.ptr), L.ptr(self.step_tracker.ptr),
                                             self.return_tracker.max_len, L.stream(self.sim_device)))
+        self.info_trackers.update(done, info)   # (`update_tracker` is not called on this path: one update per env step either way)
         return True
 
     def update_tracker(self, reward, done, info):
@@ -357,7 +364,9 @@ class PQLActor:
         self.step_tracker.update(self.current_lengths, finished)
         self.current_returns.masked_fill_(finished, 0)
         self.current_lengths.masked_fill_(finished, 0)
+        self.info_trackers.update(finished, info)   # pql_actor.py:138-146
         return done
 
     def add_info_tracker_log(self, log_info):
-        return log_info
+        """pql_actor.py:148-151: the info windows' means under the bare key names (host reads, like the return window's)."""
+        return self.info_trackers.add_to_log(log_info) if len(self.info_trackers) else log_info

@@ -4,7 +4,8 @@
 // `k_task_step` of taskstep.h; this file is the task:
 //
 //   advance: clamp the action, integrate (v, x) in place, reduce the squared distance and the action cost over the A columns
-//            IN INDEX ORDER, form the reward; terminal = some |x'_j| > 1.5;
+//            IN INDEX ORDER, form the reward; terminal = some |x'_j| > 1.5; info channels (dist2, oob) = the reward's own mean
+//            squared distance and 1.0 / 0.0 for the terminal;
 //   reset:   x, g from the counter-based uniform of envhash.h, v = 0;
 //   obs:     [x | v | g | 0 ...].
 //
@@ -19,8 +20,9 @@
 
 struct PointMassTask {
   float *x, *v, *g;
+  static constexpr int N_INFO = 2;   // dist2, oob (PointMassVecEnv.info_keys)
 
-  __device__ __forceinline__ float advance(int64_t e, int A, const float* ae, float inv_a, bool& terminal) const {
+  __device__ __forceinline__ float advance(int64_t e, int A, const float* ae, float inv_a, bool& terminal, float* inf) const {
     float *xe = x + e * A, *ve = v + e * A, *ge = g + e * A;
     float d2 = 0.f, a2 = 0.f;
     bool oob = false;
@@ -39,6 +41,8 @@ struct PointMassTask {
     d2 = d2 * inv_a;
     a2 = a2 * inv_a;
     terminal = oob;
+    inf[0] = d2;
+    inf[1] = oob ? 1.f : 0.f;
     return (-d2 - 0.01f * a2) - (oob ? 1.f : 0.f);
   }
 
@@ -64,6 +68,14 @@ extern "C" int pqlk_pointmass_step(int64_t n, int32_t obs_dim, int32_t act_dim, 
                                    int32_t episode_length, const float* action, float* x, float* v, float* g, int32_t* k,
                                    int32_t* ep, float* next_obs, float* reward, uint8_t* done, uint8_t* truncated,
                                    pqlk_stream_t stream) {
-  return launch_task_step<PointMassTask>(n, obs_dim, act_dim, seed, env_offset, episode_length, action, x, v, g, k, ep, next_obs,
-                                         reward, done, truncated, stream);
+  return launch_task_step<PointMassTask, false>(n, obs_dim, act_dim, seed, env_offset, episode_length, action, x, v, g, k, ep, next_obs,
+                                                reward, done, truncated, nullptr, stream);
+}
+
+extern "C" int pqlk_pointmass_step_info(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                                        int32_t episode_length, const float* action, float* x, float* v, float* g, int32_t* k,
+                                        int32_t* ep, float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, float* info,
+                                        pqlk_stream_t stream) {
+  return launch_task_step<PointMassTask, true>(n, obs_dim, act_dim, seed, env_offset, episode_length, action, x, v, g, k, ep, next_obs,
+                                               reward, done, truncated, info, stream);
 }

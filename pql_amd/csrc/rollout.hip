@@ -9,7 +9,8 @@
 //   block 0     : cur_return += reward, cur_length += 1; the values of the finished envs are appended to the two windows
 //                 in env order, exactly as `deque.extend` would (only the LAST `win_len` of them when more finish in one
 //                 step), the finished envs' accumulators reset, the window pointer advanced.  An ordered compaction over N
-//                 flags = a block-wide exclusive scan in chunks of 1024; deterministic, no atomics, no host sync.
+//                 flags = a block-wide exclusive scan in chunks of 1024 (`append_in_order`, which the info trackers' kernel below
+//                 shares); deterministic, no atomics, no host sync.
 #include "pqlk_common.h"
 
 struct RolloutP {
@@ -36,6 +37,54 @@ __device__ __forceinline__ void copy_rows(const float* __restrict__ src, float* 
   }
 }
 
+// Ordered append of one 1024-thread block: the envs with flag(e) set are ranked in env order (a block-wide ballot + exclusive scan
+// over chunks of 1024 envs; deterministic, no atomics), and `body(e, in, fin, before, keep)` runs once per thread and chunk with
+// before = the number of flagged envs in front of e and keep = e's value stays in a window of `win` slots behind pointer p, at
+// slot (p + before) % win: only the LAST `win` of the flagged envs, as `deque.extend` leaves them.  `in` is false for the threads
+// past n in the last chunk (they meet the barriers).  Returns the number of flagged envs, to advance the pointer by.  Every thread
+// of the block must call it; the shared scratch is the routine's own, so it is called once per kernel.
+template <class Flag, class Body>
+__device__ __forceinline__ int append_in_order(int64_t n, int win, Flag flag, Body body) {
+  __shared__ int wave_tot[16];
+  __shared__ int s_total, s_base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // pass 1: how many envs are flagged (the appended run keeps only its last `win` entries)
+  int cnt = 0;
+  for (int64_t e = threadIdx.x; e < n; e += 1024) cnt += flag(e) ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if (lane == 0) wave_tot[wave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < 16; ++w) s += wave_tot[w];
+    s_total = s; s_base = 0;
+  }
+  __syncthreads();
+  const int total = s_total;
+  // pass 2: chunks of 1024 envs in order; rank = flagged envs before this one
+  for (int64_t e0 = 0; e0 < n; e0 += 1024) {
+    const int64_t e = e0 + threadIdx.x;
+    const bool in = e < n;
+    const bool fin = in && flag(e);
+    const unsigned long long ball = __ballot(fin);
+    const int before_in_wave = __popcll(ball & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(ball);
+    __syncthreads();
+    int before = s_base + before_in_wave;
+    for (int w = 0; w < wave; ++w) before += wave_tot[w];
+    body(e, in, fin, before, fin && before >= total - win);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int s = 0;
+      for (int w = 0; w < 16; ++w) s += wave_tot[w];
+      s_base += s;
+    }
+    __syncthreads();
+  }
+  return total;
+}
+
 __global__ __launch_bounds__(1024) void k_rollout_step(RolloutP p) {
   if (blockIdx.x > 0) {
     const int64_t nthreads = (int64_t)(gridDim.x - 1) * 1024, tid = (int64_t)(blockIdx.x - 1) * 1024 + threadIdx.x;
@@ -50,50 +99,19 @@ __global__ __launch_bounds__(1024) void k_rollout_step(RolloutP p) {
     return;
   }
   // ---- block 0: accumulators + ordered append of the finished episodes
-  __shared__ int wave_tot[16];
-  __shared__ int s_total, s_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // pass 1: how many episodes finished (the appended run keeps only its last `win` entries)
-  int cnt = 0;
-  for (int64_t e = threadIdx.x; e < p.n; e += 1024) cnt += p.done[e] != 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane == 0) wave_tot[wave] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < 16; ++w) s += wave_tot[w];
-    s_total = s; s_base = 0;
-  }
-  __syncthreads();
-  const int total = s_total;
   const int64_t ptr_r = p.ptr_ret[0], ptr_l = p.ptr_len[0];
-  // pass 2: chunks of 1024 envs in order; rank = finished envs before this one
-  for (int64_t e0 = 0; e0 < p.n; e0 += 1024) {
-    const int64_t e = e0 + threadIdx.x;
-    const bool in = e < p.n;
-    const bool fin = in && p.done[e] != 0;
-    float r = 0.f, l = 0.f;
-    if (in) { r = p.cur_ret[e] + p.rew[e]; l = p.cur_len[e] + 1.f; }
-    const unsigned long long ball = __ballot(fin);
-    const int before_in_wave = __popcll(ball & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(ball);
-    __syncthreads();
-    int before = s_base + before_in_wave;
-    for (int w = 0; w < wave; ++w) before += wave_tot[w];
-    if (fin && before >= total - p.win) {
-      p.win_ret[(ptr_r + before) % p.win] = r;
-      p.win_len[(ptr_l + before) % p.win] = l;
-    }
-    if (in) { p.cur_ret[e] = fin ? 0.f : r; p.cur_len[e] = fin ? 0.f : l; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int s = 0;
-      for (int w = 0; w < 16; ++w) s += wave_tot[w];
-      s_base += s;
-    }
-    __syncthreads();
-  }
+  const int total = append_in_order(
+      p.n, p.win, [&](int64_t e) { return p.done[e] != 0; },
+      [&](int64_t e, bool in, bool fin, int before, bool keep) {
+        if (!in) return;
+        const float r = p.cur_ret[e] + p.rew[e], l = p.cur_len[e] + 1.f;
+        if (keep) {
+          p.win_ret[(ptr_r + before) % p.win] = r;
+          p.win_len[(ptr_l + before) % p.win] = l;
+        }
+        p.cur_ret[e] = fin ? 0.f : r;
+        p.cur_len[e] = fin ? 0.f : l;
+      });
   if (threadIdx.x == 0) { p.ptr_ret[0] = (ptr_r + total) % p.win; p.ptr_len[0] = (ptr_l + total) % p.win; }
 }
 
@@ -117,6 +135,62 @@ extern "C" int pqlk_rollout_step(int64_t n, int32_t obs_dim, int32_t act_dim, in
   if (copy_blocks < 1) copy_blocks = 1;
   if (copy_blocks > 512) copy_blocks = 512;
   hipLaunchKernelGGL(k_rollout_step, dim3((unsigned)(1 + copy_blocks)), dim3(1024), 0, pqlk_s(stream), p);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// The info trackers of one env step in ONE launch (pql_amd/utils/info_track.py holds the torch form, which is the definition).
+// Reference: pql/algo/pql_actor.py:138-147, pql/algo/ac_base.py:88-101, pql/utils/evaluator.py:89-102 -- per key and env step a
+// `torch.where(done)[0]`, a `.cpu()` and a `deque.extend`.  Here one 1024-thread block per key:
+//   last         the values of the finished envs are appended to the key's window in env order;
+//   all-episode  acc += value; the finished envs' sums are appended and reset to zero;
+//   all-step     every env's value is appended;
+// with `append_in_order` above, i.e. only the last win_len of one step's values stay, and the window pointer advances by their
+// number.  Values are floats, or bytes read as 0.0 / 1.0 (bool / uint8).  No atomics, no host sync, bit-equal to the torch form.
+struct InfoP {
+  int64_t n; const uint8_t* done; int win;
+  PqlInfoKey key[PQLK_INFO_MAX_KEYS];
+};
+
+__global__ __launch_bounds__(1024) void k_rollout_info(InfoP p) {
+  const PqlInfoKey k = p.key[blockIdx.x];
+  const float* vf = static_cast<const float*>(k.values);
+  const uint8_t* vb = static_cast<const uint8_t*>(k.values);
+  const bool bytes = k.dtype == PQLK_INFO_U8;
+  const int mode = k.mode;
+  float* acc = k.acc;
+  float* ring = k.ring;
+  const int64_t ptr = k.ring_ptr[0];
+  const int total = append_in_order(
+      p.n, p.win, [&](int64_t e) { return mode == PQLK_INFO_ALL_STEP || p.done[e] != 0; },
+      [&](int64_t e, bool in, bool fin, int before, bool keep) {
+        if (!in) return;
+        float v = bytes ? (vb[e] != 0 ? 1.f : 0.f) : vf[e];
+        if (mode == PQLK_INFO_ALL_EPISODE) {
+          v = acc[e] + v;
+          acc[e] = fin ? 0.f : v;
+        }
+        if (keep) ring[(ptr + before) % p.win] = v;
+      });
+  if (threadIdx.x == 0) k.ring_ptr[0] = (ptr + total) % p.win;
+}
+
+extern "C" int pqlk_rollout_info(int64_t n, const uint8_t* done, int32_t win_len, int32_t n_keys, const PqlInfoKey* keys,
+                                 pqlk_stream_t stream) {
+  PQLK_REQUIRE(done && keys, PQLK_E_NULL);
+  PQLK_REQUIRE(n > 0 && win_len > 0 && n_keys > 0 && n_keys <= PQLK_INFO_MAX_KEYS, PQLK_E_SHAPE);
+  InfoP p;
+  p.n = n; p.done = done; p.win = win_len;
+  for (int i = 0; i < PQLK_INFO_MAX_KEYS; ++i) p.key[i] = keys[i < n_keys ? i : 0];
+  for (int i = 0; i < n_keys; ++i) {
+    const PqlInfoKey& k = keys[i];
+    PQLK_REQUIRE(k.dtype == PQLK_INFO_F32 || k.dtype == PQLK_INFO_U8, PQLK_E_UNSUPPORTED);
+    PQLK_REQUIRE(k.mode == PQLK_INFO_LAST || k.mode == PQLK_INFO_ALL_EPISODE || k.mode == PQLK_INFO_ALL_STEP, PQLK_E_UNSUPPORTED);
+    PQLK_REQUIRE(k.values && k.ring && k.ring_ptr && (k.acc || k.mode != PQLK_INFO_ALL_EPISODE), PQLK_E_NULL);
+  }
+  hipLaunchKernelGGL(k_rollout_info, dim3((unsigned)n_keys), dim3(1024), 0, pqlk_s(stream), p);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }

@@ -5,7 +5,8 @@
 // `k_task_step` of taskstep.h; this file is the task:
 //
 //   advance: clamp the action, integrate (w, then the rotation of (c, s) by 0.05 w') in place, reduce the cost over the A joints
-//            IN INDEX ORDER, form the reward; no terminal (the speed is clamped instead), so every done is a time limit;
+//            IN INDEX ORDER, form the reward; no terminal (the speed is clamped instead), so every done is a time limit; info
+//            channels (upright, effort) = the means over the joints of c' and of a^2, both summed in index order;
 //   reset:   (c, s) = four rotations of hanging by a draw from the counter-based uniform of envhash.h, w another draw;
 //   obs:     [c | s | 0.125 w | 0 ...].
 //
@@ -34,10 +35,11 @@ __device__ __forceinline__ void su_rot(float& c, float& s, float d) {
 
 struct SwingUpTask {
   float *c, *s, *w;
+  static constexpr int N_INFO = 2;   // upright, effort (SwingUpVecEnv.info_keys)
 
-  __device__ __forceinline__ float advance(int64_t e, int A, const float* ae, float inv_a, bool& terminal) const {
+  __device__ __forceinline__ float advance(int64_t e, int A, const float* ae, float inv_a, bool& terminal, float* inf) const {
     float *ce = c + e * A, *se = s + e * A, *we = w + e * A;
-    float cost = 0.f;
+    float cost = 0.f, up = 0.f, eff = 0.f;
     for (int j = 0; j < A; ++j) {
       float a = ae[j];
       a = a < -1.f ? -1.f : (a > 1.f ? 1.f : a);
@@ -47,11 +49,15 @@ struct SwingUpTask {
       su_rot(cj, sj, 0.05f * wn);
       const float cost_j = ((1.0f - cj) + 0.01f * (wn * wn)) + 0.01f * (a * a);
       cost = j == 0 ? cost_j : cost + cost_j;
+      up = j == 0 ? cj : up + cj;
+      eff = j == 0 ? a * a : eff + a * a;
       we[j] = wn;
       ce[j] = cj;
       se[j] = sj;
     }
     terminal = false;
+    inf[0] = up * inv_a;
+    inf[1] = eff * inv_a;
     return -(0.05f * (cost * inv_a));
   }
 
@@ -83,6 +89,14 @@ extern "C" int pqlk_swingup_step(int64_t n, int32_t obs_dim, int32_t act_dim, ui
                                  int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k,
                                  int32_t* ep, float* next_obs, float* reward, uint8_t* done, uint8_t* truncated,
                                  pqlk_stream_t stream) {
-  return launch_task_step<SwingUpTask>(n, obs_dim, act_dim, seed, env_offset, episode_length, action, c, s, w, k, ep, next_obs, reward,
-                                       done, truncated, stream);
+  return launch_task_step<SwingUpTask, false>(n, obs_dim, act_dim, seed, env_offset, episode_length, action, c, s, w, k, ep, next_obs,
+                                              reward, done, truncated, nullptr, stream);
+}
+
+extern "C" int pqlk_swingup_step_info(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                                      int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k,
+                                      int32_t* ep, float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, float* info,
+                                      pqlk_stream_t stream) {
+  return launch_task_step<SwingUpTask, true>(n, obs_dim, act_dim, seed, env_offset, episode_length, action, c, s, w, k, ep, next_obs,
+                                             reward, done, truncated, info, stream);
 }

@@ -13,7 +13,14 @@ A new task states
     `_EPISODE_LENGTH` (the default);
   * `_reset_values(ep)`: the three state tensors at the start of episode `ep` (N,);
   * `_advance(a)`: the clamped action (N, A) -> (the three new state tensors, reward (N,), terminal mask (N,) or None);
-  * `_obs_blocks()` where an observation block is not the state tensor itself.
+  * `_obs_blocks()` where an observation block is not the state tensor itself;
+  * `info_keys`: the names of its per-env float32 info channels, in the order of the task struct's `inf[]`; with
+    `info_channels=True`, `_advance` also leaves their values in `self._info_step` (a tuple of (N,) tensors).
+
+Info channels (`info_channels=True`; `create_task_env` asks for them exactly when `cfg.info_track_keys` is set): the values belong to
+the step just taken -- for an env that finishes, they are taken before its reset -- and `step` adds `{key: (N,) row}` to the info
+dict, beside `"TimeLimit.truncated"`.  The HIP step writes them from the same launch (the `_info` entry: a channel-major
+(n_info, N) block).  They are derived from the state, so `state_dict` does not hold them.
 `_step_torch` is the definition and the CPU / `PQL_SYNTH_TORCH` form; every written operation is one fp32 rounding, which is what
 lets the HIP step be bit-equal to it.
 """
@@ -63,13 +70,16 @@ class HashResetVecEnv(VecEnvBase):
     _ENTRY = None
     _LAYOUT = ""
     _EPISODE_LENGTH = 64
+    info_keys = ()
 
-    def __init__(self, num_envs, obs_dim, act_dim, device="cuda", seed=42, episode_length=None, env_offset=0):
+    def __init__(self, num_envs, obs_dim, act_dim, device="cuda", seed=42, episode_length=None, env_offset=0, info_channels=False):
         if int(act_dim) <= 0 or int(obs_dim) < 3 * int(act_dim):   # (before anything touches the device)
             raise ValueError(f"{type(self).__name__}: obs = {self._LAYOUT} needs obs_dim >= 3 * act_dim, got obs_dim={int(obs_dim)}, "
                              f"act_dim={int(act_dim)}")
         super().__init__(num_envs, obs_dim, act_dim, device, seed, self._EPISODE_LENGTH if episode_length is None else episode_length,
                          env_offset)
+        self.info_channels = bool(info_channels) and len(self.info_keys) > 0
+        self._info_step = None
         self.inv_a = float(np.float32(1.0) / np.float32(self.act_dim))   # the fp32 constant 1.0f / A, in both forms
         n, A, dev = self.num_envs, self.act_dim, self.device
         for name in self._STATE:
@@ -154,7 +164,10 @@ class HashResetVecEnv(VecEnvBase):
             setattr(self, name, torch.where(d, start, now))
         self.k = torch.where(done, torch.zeros_like(k), k)
         self.ep = ep
-        return self._observe(), reward, done, {"TimeLimit.truncated": truncated}
+        info = {"TimeLimit.truncated": truncated}
+        if self.info_channels:
+            info.update(zip(self.info_keys, self._info_step))
+        return self._observe(), reward, done, info
 
     def _step_hip(self, action):
         """Same transition as `_step_torch`, one launch (`_ENTRY`, include/pqlk.h): state updated in place."""
@@ -167,9 +180,14 @@ class HashResetVecEnv(VecEnvBase):
         act = action.to(dev, torch.float32).contiguous()
         if tuple(act.shape) != (n, self.act_dim):
             raise ValueError(f"{type(self).__name__}.step: action has shape {tuple(act.shape)}, expected {(n, self.act_dim)}")
+        entry, extra, info = self._ENTRY, (), {"TimeLimit.truncated": truncated}
+        if self.info_channels:   # the same launch, plus one coalesced row per channel
+            block = torch.empty((len(self.info_keys), n), dtype=torch.float32, device=dev)
+            entry, extra = self._ENTRY + "_info", (L.ptr(block),)
+            info.update(zip(self.info_keys, block.unbind(0)))
         with torch.cuda.device(dev):
-            L.check(getattr(L.lib, self._ENTRY)(n, self.obs_dim, self.act_dim, self.seed & 0xFFFFFFFF, self.env_offset & 0xFFFFFFFF,
-                                                self.max_episode_length, L.ptr(act), *(L.ptr(getattr(self, name)) for name in self._STATE),
-                                                L.ptr(self.k), L.ptr(self.ep), L.ptr(next_obs), L.ptr(reward), L.ptr(done),
-                                                L.ptr(truncated), L.stream(dev)))
-        return next_obs, reward, done, {"TimeLimit.truncated": truncated}
+            L.check(getattr(L.lib, entry)(n, self.obs_dim, self.act_dim, self.seed & 0xFFFFFFFF, self.env_offset & 0xFFFFFFFF,
+                                          self.max_episode_length, L.ptr(act), *(L.ptr(getattr(self, name)) for name in self._STATE),
+                                          L.ptr(self.k), L.ptr(self.ep), L.ptr(next_obs), L.ptr(reward), L.ptr(done),
+                                          L.ptr(truncated), *extra, L.stream(dev)))
+        return next_obs, reward, done, info

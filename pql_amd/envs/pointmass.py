@@ -11,6 +11,7 @@ A damped point mass in A dimensions is pushed towards a goal:
     reward    = -d2 - 0.01 (1/A) sum_j a_j^2 - (1 if oob else 0)
     truncated = k' >= episode_length and not oob
     done      = oob or truncated
+    info channels (`info_channels=True`): dist2 = d2, oob = 1.0 if oob else 0.0
 
 Every written operation is one fp32 rounding (no fused multiply-add), and nothing is transcendental, so the HIP step
 (`pqlk_pointmass_step`, pql_amd/csrc/pointmass.hip) is bit-equal to `_step_torch`, which is the definition and the CPU /
@@ -39,6 +40,7 @@ class PointMassVecEnv(HashResetVecEnv):
     _ENTRY = "pqlk_pointmass_step"
     _LAYOUT = "[x | v | g | 0 ...]"
     _EPISODE_LENGTH = 64
+    info_keys = ("dist2", "oob")   # of the step just taken: the reward's own d2, and 1.0 where the step left the box
 
     def _reset_values(self, ep):
         """(x, v, g) at the start of episode `ep` (N,) of every env."""
@@ -52,6 +54,8 @@ class PointMassVecEnv(HashResetVecEnv):
         d2 = self._sum_in_order(diff * diff) * self.inv_a
         a2 = self._sum_in_order(a * a) * self.inv_a
         oob = (x.abs() > OOB).any(dim=1)
+        if self.info_channels:
+            self._info_step = (d2, oob.to(torch.float32))
         return (x, v, self.g), -d2 - 0.01 * a2 - oob.to(torch.float32), oob
 
 

@@ -18,6 +18,7 @@ upright and its angular velocity w; gravity (15 sin) beats the torque (6 a), so 
     cost_j = ((1 - c') + 0.01 (w' w')) + 0.01 (a a)
     reward    = -(0.05 ((sum_j cost_j) (1/A)))     summed in index order j = 0 .. A-1
     k'  = k + 1 ;  truncated = k' >= episode_length ;  done = truncated
+    info channels (`info_channels=True`): upright = (sum_j c'_j) (1/A), effort = (sum_j a_j a_j) (1/A), summed in index order
 
 There is no terminal: the speed is clamped instead (an episode that can be ended early is ended on purpose by a learner that finds
 hanging more expensive than the end).  A pendulum at rest hanging costs 0.05 * 2 = 0.1 per step, so with gamma = 0.99 the
@@ -63,6 +64,7 @@ class SwingUpVecEnv(HashResetVecEnv):
     _ENTRY = "pqlk_swingup_step"
     _LAYOUT = "[c | s | w / 8 | 0 ...]"
     _EPISODE_LENGTH = 128
+    info_keys = ("upright", "effort")   # of the step just taken: the means over the joints of c' and of a^2
 
     def _reset_values(self, ep):
         """(c, s, w) at the start of episode `ep` (N,) of every env."""
@@ -79,6 +81,8 @@ class SwingUpVecEnv(HashResetVecEnv):
         w = (self.w + 0.05 * (15.0 * self.s + 6.0 * a)).clamp(-W_MAX, W_MAX)
         c, s = _rot(self.c, self.s, 0.05 * w)
         cost = ((1.0 - c) + 0.01 * (w * w)) + 0.01 * (a * a)
+        if self.info_channels:
+            self._info_step = (self._sum_in_order(c) * self.inv_a, self._sum_in_order(a * a) * self.inv_a)
         return (c, s, w), -(0.05 * (self._sum_in_order(cost) * self.inv_a)), None   # no terminal: every done is a time limit
 
 

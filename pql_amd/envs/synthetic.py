@@ -97,7 +97,8 @@ TASK_ENVS = {"synthetic": SyntheticVecEnv, "pointmass": PointMassVecEnv, "swingu
 
 def create_task_env(cfg, num_envs=None, env_offset=0):
     """Stand-in for pql.utils.isaacgym_util.create_task_env (:8-24).  `task.kind` picks the env from TASK_ENVS: absent / synthetic =
-    the counter-based generator above, pointmass / swingup = the learnable tasks of pql_amd/envs/pointmass.py and pql_amd/envs/swingup.py."""
+    the counter-based generator above, pointmass / swingup = the learnable tasks of pql_amd/envs/pointmass.py and pql_amd/envs/swingup.py.  A task with info channels emits them exactly
+    when `cfg.info_track_keys` is set."""
     task = cfg.task
     name = task.name if task is not None else "AllegroHand"
     O, A = TASK_SHAPES.get(name, (88, 16))
@@ -108,4 +109,8 @@ def create_task_env(cfg, num_envs=None, env_offset=0):
     kind = (task.get("kind") if task is not None else None) or "synthetic"   # absent = the synthetic env, as before `kind` existed
     if kind not in TASK_ENVS:
         raise ValueError(f"task.kind={kind}: no such env; known kinds: {', '.join(TASK_ENVS)}")
-    return TASK_ENVS[kind](num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep, env_offset=env_offset)
+    extra = {}
+    if getattr(cfg, "info_track_keys", None) is not None and hasattr(TASK_ENVS[kind], "info_keys"):   # the task's info channels, only when tracked
+        extra["info_channels"] = True
+    return TASK_ENVS[kind](num_envs or cfg.num_envs, O, A, device=cfg.sim_device, seed=cfg.seed, episode_length=ep, env_offset=env_offset,
+                           **extra)

@@ -82,8 +82,9 @@ def _run_dir(cfg, wandb_run):
 class _Job:
     """One evaluation in flight: device state + how far its episode has been enqueued."""
 
-    def __init__(self, actor, critic, normalizer, step, num_envs, device):
+    def __init__(self, actor, critic, normalizer, step, num_envs, device, info_trackers=None):
         from pql_amd.algo.pql_actor import DeviceTracker
+        self.info_trackers = info_trackers   # fresh per evaluation, window eval_num_envs (None without info_track_keys)
         self.actor, self.critic, self.normalizer, self.step = actor, critic, normalizer, step
         self.return_tracker = DeviceTracker(num_envs, device)
         self.step_tracker = DeviceTracker(num_envs, device)
@@ -92,7 +93,7 @@ class _Job:
         self.obs = None
         self.i_step = 0
         self.done_event = None
-        self.host = None   # pinned copies of the two tracker windows
+        self.host = None   # pinned copies of the two tracker windows (+ one row per info_track_keys entry)
 
 
 class RolloutEngine:
@@ -111,8 +112,16 @@ class RolloutEngine:
         self.run_dir = _run_dir(cfg, wandb_run)
         self.wandb_run = wandb_run
         self.ret_max = float("-inf")
-        if cfg.info_track_keys is not None:
-            raise NotImplementedError("info_track_keys needs a simulator's info dict; out of scope")
+        self._info_trackers()   # (a bad info_track_keys / info_track_step fails here, not at the first evaluation)
+
+    def _info_trackers(self):
+        """Fresh info windows for one evaluation (evaluator.py:56-61, capacity eval_num_envs), or None.  The reference builds them
+        once and so carries windows and partial `all-episode` sums from one evaluation into the next, although it resets the env
+        between them; here every evaluation starts from zero, like its return window."""
+        from pql_amd.utils.info_track import InfoTrackers
+        if getattr(self.cfg, "info_track_keys", None) is None and getattr(self.cfg, "info_track_step", None) is None:
+            return None
+        return InfoTrackers.from_cfg(self.cfg, self.env, self.num_envs, self.num_envs, self.device)
 
     def _ctx(self):
         return torch.cuda.stream(self.stream) if self.stream is not None else _NullCtx()
@@ -127,7 +136,7 @@ class RolloutEngine:
         if self.stream is not None:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
         with self._ctx():
-            return _Job(actor, critic, normalizer, step, self.num_envs, self.device)
+            return _Job(actor, critic, normalizer, step, self.num_envs, self.device, self._info_trackers())
 
     @torch.no_grad()
     def advance(self, job, n_steps):
@@ -141,7 +150,7 @@ class RolloutEngine:
             for _ in range(min(n_steps, self.max_step - job.i_step)):
                 x = job.normalizer.normalize(job.obs) if (self.cfg.algo.obs_norm and job.normalizer is not None) else job.obs
                 action = job.actor(x)
-                next_obs, reward, done, _info = self.env.step(action)
+                next_obs, reward, done, info = self.env.step(action)
                 job.returns += reward
                 job.lengths += 1
                 finished = done.bool()
@@ -149,10 +158,14 @@ class RolloutEngine:
                 job.step_tracker.update(job.lengths, finished)
                 job.returns.masked_fill_(finished, 0)
                 job.lengths.masked_fill_(finished, 0)
+                if job.info_trackers is not None:
+                    job.info_trackers.update(finished, info)   # evaluator.py:89-102
                 job.obs = next_obs
                 job.i_step += 1
             if job.i_step >= self.max_step:
                 windows = torch.stack((job.return_tracker.ring[: self.num_envs], job.step_tracker.ring[: self.num_envs]))
+                if job.info_trackers is not None:   # their windows ride in the same read-back
+                    windows = torch.cat((windows, job.info_trackers.windows()))
                 if self.stream is not None:
                     job.host = torch.empty(windows.shape, dtype=windows.dtype, pin_memory=True)
                     job.host.copy_(windows, non_blocking=True)
@@ -173,6 +186,8 @@ class RolloutEngine:
         w = job.host.numpy().astype(np.float64)
         ret_mean, step_mean = float(np.mean(w[0])), float(np.mean(w[1]))
         result = {"eval/return": ret_mean, "eval/episode_length": step_mean}
+        if job.info_trackers is not None:   # evaluator.py:109-111
+            result.update({f"eval/{key}": float(np.mean(w[2 + i])) for i, key in enumerate(job.info_trackers.keys)})
         if ret_mean > self.ret_max:
             self.ret_max = ret_mean
             has_sd = lambda m: m is not None and hasattr(m, "state_dict")   # noqa: E731

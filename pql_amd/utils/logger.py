@@ -16,8 +16,11 @@ class MetricLogger:
             self.fh.flush()
 
     def table(self, step, info):
+        extra = [k for k in info if "/" not in k]   # the bare names of `add_info_tracker_log` (info_track_keys): one more column each
         if not self.header_done:
-            print(f"{'Steps':>12s}{'Time':>12s}{'critic_loss':>12s}{'actor_loss':>12s}{'v-updates':>12s}{'p-updates':>12s}")
+            print(f"{'Steps':>12s}{'Time':>12s}{'critic_loss':>12s}{'actor_loss':>12s}{'v-updates':>12s}{'p-updates':>12s}"
+                  + "".join(f"{k[-11:]:>12s}" for k in extra))
             self.header_done = True
         print(f"{step:12.2e}{time.time() - self.t0:>12.1f}{info['train/critic_loss']:12.4f}{info['train/actor_loss']:12.4f}"
-              f"{info['train/critic_update_times']:12.0f}{info['train/actor_update_times']:12.0f}", flush=True)
+              f"{info['train/critic_update_times']:12.0f}{info['train/actor_update_times']:12.0f}"
+              + "".join(f"{float(info[k]):12.4f}" for k in extra), flush=True)

@@ -100,6 +100,7 @@ def main(cfg, on_finish=None):
             log_info = agent.update_net(trajectory)
         if iter_t % cfg.algo.log_freq == 0:
             log_info["global_steps"] = global_steps
+            agent.add_info_tracker_log(log_info)   # info_track_keys: the windows' means under the bare key names
             logger.log(log_info, global_steps)
         stop = (cfg.max_step is not None and global_steps > cfg.max_step) or (cfg.max_step is None and time.time() - start > cfg.max_time)
         if ckpt_dir is not None and (stop or (ckpt_freq is not None and (iter_t + 1) % ckpt_freq == 0)):

@@ -247,6 +247,7 @@ def main(cfg, on_finish=None):
                 "train/return": pql_actor.return_tracker.mean(), "train/episode_length": pql_actor.step_tracker.mean(),
                 "train/critic_update_times": critic_update_times, "train/actor_update_times": actor_update_times,
                 "train/global_steps": global_steps}
+            pql_actor.add_info_tracker_log(log_info)   # info_track_keys: the windows' means under the bare key names
             logger.log(log_info, global_steps)
             if iter_t % cfg.algo.eval_freq == 0:
                 logger.table(global_steps, log_info)
