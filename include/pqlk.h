@@ -326,8 +326,10 @@ int64_t pqlk_philox_increment(int64_t numel);
 /* DPG backward through the frozen twin critic (pql_p_learner.py:55-58): the input gradient of pqlk_mlp_backward's
  * (grads = NULL, dx + dx_tanh_of) form.  With scalar Q heads the gradient of min(Q1, Q2) reaches one net per sample, so the
  * samples are first partitioned by owning net and the dX chain runs over compact rows -- half the MFMA work, each sample's
- * values bit for bit those of the dense chain; other critics take the dense chain.  dx (B, ld_dx) is fully overwritten
- * (columns >= dx_cols with zero).  ws >= pqlk_dpg_backward_ws_floats(d, b) floats. */
+ * values bit for bit those of the dense chain; other critics take the dense chain.  The compact chain overwrites dx (B, ld_dx)
+ * fully (columns >= dx_cols with zero); the dense chain writes columns [0, dx_cols) alone and leaves the others untouched, as
+ * pqlk_mlp_backward does, so a caller that wants them zero keeps them zero itself (the P-learner allocates dx zeroed).
+ * ws >= pqlk_dpg_backward_ws_floats(d, b) floats. */
 int64_t pqlk_dpg_backward_ws_floats(const PqlMlpDesc* d, int64_t b);
 int pqlk_dpg_critic_backward(const PqlMlpDesc* d, const float* params, const float* x, int64_t ldx, int64_t b,
                              const float* acts, const float* dy, float* dx, int64_t ld_dx, int32_t dx_col0, int32_t dx_cols,

@@ -1,0 +1,760 @@
+"""Cases, inputs, references and checks for tests/test_backward_paths_gpu.py (plain numpy, no GPU, no library).
+
+pqlk_mlp_backward picks, per call, between three implementations of the output layer's backward (skinny.h), per hidden layer a dW
+and a dX k_gemm in two tile sizes, two main loops and three block orders (gemm.hip), and for the input gradient a GEMM or
+k_dx_slice (narrow.h); pqlk_dpg_critic_backward adds the compact-row chain (minnet.h).  `backward_plan` restates that dispatch so
+that every case can name the launches it reaches; tests/test_backward_cases_cpu.py holds the table against it and holds the mirror
+against the three host-side quantities of the library that depend on the dispatch.
+
+The backward never runs the forward: the activation stash is an INPUT.  Hidden activations come from {2, 1, 0.5, 0, -0.5, -0.75,
+-1} (ELU' = 1, 1, 1, 1, 0.5, 0.25, 0), weights from {-1, 0, 1}, x and dy are integers in [-2, 2], the tanh outputs come from
+{0, +-0.5, +-1} (1 - a^2 = 1, 0.75, 0): every product is a dyadic rational.  The library is built with -ffp-contract=off.  For an
+output element sum_i t_i whose terms are all multiples of 2^-g, if sum_i |t_i| 2^g <= 2^24 then every partial sum in any order or
+grouping is exactly representable in fp32: an MFMA chain, a split-slab sum, a wave fold and a float64 numpy matmul give the same
+value.  `exactness_bits` measures that condition per case (the CPU test asserts it), and the checks are `==`: no tolerance
+anywhere.  (Values are compared, so +0 == -0: the sign of a zero sum is a property of the summation order, not of the sum.)
+
+Source lines cited below are those of pql_amd/csrc at the commit that added this file."""
+import functools
+from collections import namedtuple
+
+import numpy as np
+
+import detdata as dd
+import reduction_cases as rc
+
+F32, F64 = np.float32, np.float64
+POISON, SLACK, IN_ONE = rc.POISON, rc.SLACK, rc.IN_ONE
+
+# ---------------------------------------------------------------- the library's constants
+SKINNY_MAX_N, SKINNY_MAX_K = 16, 1024     # skinny.h:9-10
+SKB_ROWS = 64                             # skinny.h:285
+KT, KT_MAX = 16, 32                       # gemm.hip:63-65 (PQLK_KT, KT_MAX)
+MN_TILE = 128                             # minnet.h:16
+LDS_BYTES = 160 * 1024                    # narrow.h:463
+E_WORKSPACE = 6                           # include/pqlk.h:46
+
+
+def ld(cols):
+    """pqlk_ld (replay.hip:7): round up to 32 floats."""
+    return (max(int(cols), 1) + 31) // 32 * 32
+
+
+def round_up(a, m):
+    return (a + m - 1) // m * m
+
+
+def cdiv(a, m):
+    return (a + m - 1) // m
+
+
+# ---------------------------------------------------------------- mirror: the output layer (skinny.h)
+def skinny_bwd_ok(n_out, k_padded):
+    """skinny.h:476."""
+    return n_out <= SKINNY_MAX_N and k_padded <= SKINNY_MAX_K
+
+
+def skinny_bwd_ch(k_padded):
+    """skinny.h:423: template CH of k_skinny_bwd."""
+    c = cdiv(k_padded, 256)
+    return c if c <= 2 else 4
+
+
+def skinny_bwd_nb(n_out):
+    """skinny.h:424: template NB of k_skinny_bwd."""
+    return 1 if n_out == 1 else 4 if n_out <= 4 else 8 if n_out <= 8 else 16
+
+
+def skinny_bwd_fused_ok(n_out, k_padded):
+    """skinny.h:425-427."""
+    return n_out <= SKINNY_MAX_N and k_padded <= SKINNY_MAX_K and skinny_bwd_nb(n_out) * skinny_bwd_ch(k_padded) <= 16
+
+
+def skinny_bwd_rows(m, groups):
+    """skinny.h:429-433: rows per block of k_skinny_bwd."""
+    r = SKB_ROWS
+    while r > 16 and cdiv(m, r) * groups < 512:
+        r >>= 1
+    return r
+
+
+def skinny_bwd_blocks(m, groups):
+    """skinny.h:434."""
+    return cdiv(m, skinny_bwd_rows(m, groups))
+
+
+def skinny_bwd_kernel(n_out, k_padded):
+    """skinny.h:451-471 (launch_skinny_bwd without the TD head): (NB, CH) of k_skinny_bwd<NB, CH>."""
+    ch = skinny_bwd_ch(k_padded)
+    if n_out == 1:
+        return (1, ch)                                             # :458-462
+    if n_out <= 4:
+        return (4, ch)                                             # :463-467
+    if n_out <= 8 and ch <= 2:
+        return (8, ch)                                             # :468-469
+    return (16, 1)                                                 # :470
+
+
+def skinny_dw_cls(k_padded, splits, groups):
+    """skinny.h:508-511 (launch_skinny_dw): CLS of k_skinny_dw<CLS>."""
+    return 16 if cdiv(k_padded, 64) * splits * groups >= 256 else 4
+
+
+def skinny_dx_blocks(m):
+    """skinny.h:493-495 (launch_skinny_dx): the grid is capped at 2048 blocks of four rows."""
+    return min(cdiv(m, 4), 2048)
+
+
+def head_is_fused(dims):
+    """gemm.hip:1230-1233."""
+    L = len(dims) - 1
+    return L >= 2 and skinny_bwd_ok(dims[L], ld(dims[L - 1])) and skinny_bwd_fused_ok(dims[L], ld(dims[L - 1]))
+
+
+# ---------------------------------------------------------------- mirror: k_gemm (gemm.hip)
+def launch_tile(mode, epi, M, ncols, gz):
+    """gemm.hip:826-836: 128 for k_gemm<MODE, 128, 128>, else 64."""
+    big = cdiv(M, 128) * cdiv(ncols, 128) * gz                     # :828
+    return 128 if big >= 256 and ncols >= 128 and epi != "DTANH_SLICE" else 64   # :832
+
+
+def gemm_plan(mode, epi, tile, M, N, K, lda, ldb, ncols_store, gz, splits=1, rows_per_split=0, col0=0, ncol=0):
+    """gemm.hip:751-782 with PQLK_GEMM_DMA and PQLK_GEMM_XCD unset and every operand 16-byte aligned (the arena, the stash, the
+    workspace and the tests' buffers all are; group strides are multiples of 32 floats): (grid, loop, xcd, n_base)."""
+    ncols, n_base = (N if mode == "dW" else ncols_store), 0        # :753-754
+    if epi == "DTANH_SLICE":
+        n_base = col0 & ~3                                         # :756
+        ncols = col0 + ncol - n_base                               # :757
+    grid = (cdiv(ncols, tile), cdiv(M, tile), gz)                  # :759
+    tiles, group = grid[0] * grid[1] * grid[2], (grid[0] * grid[1] if mode == "dW" else grid[0])   # :761
+    xcd = "groups" if tiles % (8 * group) == 0 else "runs" if tiles >= 64 else 0                   # :764-765
+    dma = False
+    if epi in ("NONE", "DELU"):                                    # :768
+        dma = M % tile == 0 and lda % 4 == 0 and ldb % 4 == 0      # :769-770
+        if mode == "dX":                                           # :771
+            dma = dma and ncols % tile == 0 and N % tile == 0 and K % (4 * KT) == 0 and K <= lda and ncols <= ldb
+        else:                                                      # :777-778
+            dma = (dma and round_up(N, tile) <= ldb and rows_per_split % (4 * KT) == 0 and K % rows_per_split == 0
+                   and K // rows_per_split == splits and M <= lda and N <= ldb)
+    return grid, ("dma" if dma else "staged"), xcd, n_base
+
+
+def gemm_launch(mode, epi, M, N, K, lda, ldb, ncols_store, gz, **kw):
+    """One k_gemm launch tuple: (mode, epi, tile, loop, xcd, has_edge_tile).  An edge tile is one the epilogue does not take as a
+    `whole` tile (gemm.hip:556, :662): a ragged last row tile or column tile; the slice epilogue is per element throughout."""
+    ncols = N if mode == "dW" else ncols_store
+    tile = launch_tile(mode, epi, M, ncols, gz)
+    _, loop, xcd, _ = gemm_plan(mode, epi, tile, M, N, K, lda, ldb, ncols_store, gz, **kw)
+    edge = M % tile != 0 or N % tile != 0 or epi == "DTANH_SLICE"
+    return (mode, epi, tile, loop, xcd, edge)
+
+
+# ---------------------------------------------------------------- mirror: the input-gradient slice (narrow.h)
+def dx_slice_lds(groups, K):
+    """narrow.h:456-459."""
+    return max(4 * 32 * (groups * K // 4 + 4) * 4, 16384)
+
+
+def dx_slice_ok(groups, K, ncol, lda):
+    """narrow.h:461-464 for an EPI_DTANH_SLICE, zsum product."""
+    return ncol <= 32 and K % 32 == 0 and 4 % groups == 0 and lda % 4 == 0 and dx_slice_lds(groups, K) <= LDS_BYTES
+
+
+def dx_slice_depth(groups, K):
+    """narrow.h:484, :500-502 (launch_dx_slice without the actor head): D of k_dx_slice<D>."""
+    K8 = groups * K // 32
+    return 16 if K8 % 16 == 0 else 4 if K8 % 4 == 0 else 1
+
+
+# ---------------------------------------------------------------- mirror: pqlk_mlp_backward (gemm.hip:1252-1414)
+def rows_per_split(B, splits):
+    """gemm.hip:1336, :1359."""
+    return round_up(cdiv(B, splits), KT_MAX)
+
+
+def empty_splits(B, splits):
+    """Splits whose first row lies past the batch: their slabs must come out as zeros."""
+    return sum(1 for s in range(splits) if s * rows_per_split(B, splits) >= B)
+
+
+def backward_plan(dims, nets, B, splits, want_grads, dx_form, ldx=None):
+    """One tuple per launch of pqlk_mlp_backward, in launch order.  dx_form: None | "full" | ("slice", col0, cols).
+    ("skinny_bwd", NB, CH, rows) | ("skinny_dw", CLS) | ("skinny_dx",) | gemm_launch tuples | ("dx_slice", D, groups) |
+    ("reduce", head partials folded?)."""
+    L = len(dims) - 1
+    ldx = ld(dims[0]) if ldx is None else ldx
+    plan, head_parts = [], False
+    for l in range(L - 1, -1, -1):                                 # :1295
+        ld_out, ld_in = ld(dims[l + 1]), ld(dims[l])               # :1301-1302
+        in_ld = ldx if l == 0 else ld_in                           # :1305-1311
+        skinny = l == L - 1 and skinny_bwd_ok(dims[l + 1], ld_in) and in_ld >= ld_in   # :1312
+        if skinny:
+            if want_grads and head_is_fused(dims):                 # :1318
+                plan.append(("skinny_bwd",) + skinny_bwd_kernel(dims[l + 1], ld_in) + (skinny_bwd_rows(B, nets),))
+                head_parts = True
+                continue                                           # :1332
+            if want_grads:                                         # :1334
+                plan.append(("skinny_dw", skinny_dw_cls(ld_in, splits, nets)))
+            if l > 0:                                              # :1340
+                plan.append(("skinny_dx",))
+                continue
+            if dx_form is None:                                    # :1348
+                continue
+        if want_grads and not skinny:                              # :1350
+            plan.append(gemm_launch("dW", "NONE", dims[l + 1], ld_in, B, ld_out, in_ld, ld_out, nets * splits, splits=splits,
+                                    rows_per_split=rows_per_split(B, splits)))
+        if l > 0:                                                  # :1366
+            plan.append(gemm_launch("dX", "DELU", B, dims[l], dims[l + 1], ld_out, ld_in, ld_in, nets))
+        elif dx_form is not None:                                  # :1378
+            if dx_form == "full":
+                plan.append(gemm_launch("dX", "NONE", B, dims[0], dims[1], ld_out, ld_in, ld_in, 1))
+            else:
+                _, col0, cols = dx_form
+                if dx_slice_ok(nets, dims[1], cols, ld_out):       # :1391
+                    plan.append(("dx_slice", dx_slice_depth(nets, dims[1]), nets))
+                else:
+                    plan.append(gemm_launch("dX", "DTANH_SLICE", B, dims[0], dims[1], ld_out, ld_in, ld_in, 1, col0=col0, ncol=cols))
+    if want_grads:                                                 # :1396
+        plan.append(("reduce", head_parts))
+    return plan
+
+
+# ---------------------------------------------------------------- mirror: the host-side sizes
+def net_stride(dims):
+    """gemm.hip:868-873."""
+    return sum(dims[l + 1] * ld(dims[l]) + ld(dims[l + 1]) for l in range(len(dims) - 1))
+
+
+def layer_offsets(dims, layer):
+    """gemm.hip:876-885: (w_off, b_off) inside one net's block."""
+    n = sum(dims[l + 1] * ld(dims[l]) + ld(dims[l + 1]) for l in range(layer))
+    return n, n + dims[layer + 1] * ld(dims[layer])
+
+
+def acts_floats(dims, nets, B):
+    """gemm.hip:887-892."""
+    return sum(nets * B * ld(dims[l + 1]) for l in range(len(dims) - 1))
+
+
+def act_offset(dims, nets, B, net, layer):
+    """gemm.hip:894-904: (offset, row stride) of one net's block of one layer's activations in the stash."""
+    return sum(nets * B * ld(dims[l + 1]) for l in range(layer)) + net * B * ld(dims[layer + 1]), ld(dims[layer + 1])
+
+
+def max_hidden_ld(dims):
+    """gemm.hip:906-910."""
+    return max(ld(d) for d in dims[1:])
+
+
+def head_part_floats(dims, nets, B):
+    """gemm.hip:912-919."""
+    hf = dims[-1] * ld(dims[-2]) + ld(dims[-1])
+    return max(skinny_bwd_blocks(B, nets), 2 * round_up(B, 128) // 32) * nets * hf
+
+
+def bwd_ws_floats(dims, nets, B, splits):
+    """gemm.hip:921-924 (pqlk_mlp_bwd_ws_floats)."""
+    return 2 * nets * B * max_hidden_ld(dims) + splits * net_stride(dims) * nets + head_part_floats(dims, nets, B)
+
+
+def bwd_ws_required(dims, nets, B, splits, want_grads):
+    """gemm.hip:1275-1277: what the call itself insists on (without grads neither slabs nor head partials)."""
+    return bwd_ws_floats(dims, nets, B, splits) if want_grads else 2 * nets * B * max_hidden_ld(dims)
+
+
+def norm_parts(dims, nets):
+    """gemm.hip:1226-1246 (pqlk_mlp_norm_parts): the head's fold blocks exist when head_is_fused."""
+    main = min(max(cdiv(net_stride(dims) * nets // 4, 256), 1), 1024)
+    hq = (dims[-1] * ld(dims[-2]) + ld(dims[-1])) // 4 * nets
+    return main + (cdiv(hq, 4) if head_is_fused(dims) else 0)
+
+
+def minnet_ok(dims, nets, dx_cols):
+    """gemm.hip:1421-1430 with dx and dx_tanh_of given."""
+    L = len(dims) - 1
+    if nets != 2 or L < 3 or dims[L] != 1 or dx_cols > 32 or not skinny_bwd_ok(1, ld(dims[L - 1])):
+        return False
+    return all(dims[l] % 32 == 0 for l in range(1, L)) and all(dims[l] % 128 == 0 for l in range(1, L - 1))
+
+
+def dpg_ws_floats(dims, nets, B):
+    """gemm.hip:1431, :1448-1453 (pqlk_dpg_backward_ws_floats)."""
+    cap = 2 * round_up(B, MN_TILE)
+    return max(bwd_ws_floats(dims, nets, B, 1), 2 * cap * max_hidden_ld(dims) + 2 * cap + 64)
+
+
+def smallest(pred, lo=1, hi=1 << 20):
+    for v in range(lo, hi):
+        if pred(v):
+            return v
+    raise AssertionError("no value below the cap satisfies the predicate")
+
+
+def default_splits(B, cap=16):
+    """pql_amd/models/mlp.py default_splits."""
+    return max(1, min(cap, B // 512))
+
+
+# ---------------------------------------------------------------- the table
+Case = namedtuple("Case", "name dims nets B splits form col0 cols ldx must")
+FORMS = ("gdx", "g", "dx", "slice")       # grads + full dx | grads only | dx only (grads = NULL) | slice only (grads = NULL)
+
+
+def _plan_of(dims, nets, B, splits, form, col0=0, cols=0, ldx=None):
+    dx_form = {"gdx": "full", "g": None, "dx": "full", "slice": ("slice", col0, cols)}[form]
+    return backward_plan(dims, nets, B, splits, form in ("gdx", "g"), dx_form, ldx)
+
+
+def plan(case):
+    return _plan_of(case.dims, case.nets, case.B, case.splits, case.form, case.col0, case.cols, case.ldx)
+
+
+# thresholds found on the mirror (the CPU tests prove they are minimal)
+B_ROWS32 = smallest(lambda B: skinny_bwd_rows(B, 2) == 32)                      # k_skinny_bwd at 32 rows per block, two nets
+B_ROWS64 = smallest(lambda B: skinny_bwd_rows(B, 2) == 64)
+B_DX_CAP = smallest(lambda B: cdiv(B, 4) > 2048)                                # k_skinny_dx walks its capped grid twice
+WIDE = [8, 512, 512, 1]                                                         # the 128 x 128 tiles, two nets
+B_DX128 = smallest(lambda B: launch_tile("dX", "DELU", B, 512, 2) == 128)
+S_DW128 = smallest(lambda s: launch_tile("dW", "NONE", 512, 512, 2 * s) == 128, hi=65)
+S_CLS16 = smallest(lambda s: skinny_dw_cls(1024, s, 2) == 16, hi=65)            # [8, 1024, 6], two nets
+
+_SB = "skinny_bwd"
+_TABLE = [
+    # dims, nets, B, splits, form, {col0, cols, ldx}, launches the row is there for
+    # ---- k_skinny_bwd<NB, CH>: all nine instantiations, one and two nets, B % 16 != 0, 16-row blocks
+    ([8, 32, 1], 1, 37, 1, "gdx", {}, [(_SB, 1, 1, 16)]),
+    ([8, 32, 1], 2, 37, 1, "g", {}, [(_SB, 1, 1, 16)]),
+    ([8, 32, 1], 1, 1, 1, "gdx", {}, [(_SB, 1, 1, 16)]),                        # a lone row
+    ([8, 32, 1], 2, 1, 1, "gdx", {}, [(_SB, 1, 1, 16)]),
+    ([8, 288, 1], 1, 37, 1, "g", {}, [(_SB, 1, 2, 16)]),
+    ([8, 288, 1], 2, 37, 1, "gdx", {}, [(_SB, 1, 2, 16)]),
+    ([8, 544, 1], 1, 37, 1, "gdx", {}, [(_SB, 1, 4, 16)]),                      # 544 = three chunks of 256: CH = 4 with one idle
+    ([8, 544, 1], 2, 37, 1, "g", {}, [(_SB, 1, 4, 16)]),
+    ([8, 1024, 1], 1, 37, 1, "g", {}, [(_SB, 1, 4, 16)]),
+    ([8, 1024, 1], 2, 37, 1, "gdx", {}, [(_SB, 1, 4, 16)]),
+    ([8, 64, 3], 1, 37, 1, "gdx", {}, [(_SB, 4, 1, 16)]),
+    ([8, 64, 3], 2, 37, 1, "g", {}, [(_SB, 4, 1, 16)]),
+    ([8, 512, 4], 1, 37, 1, "g", {}, [(_SB, 4, 2, 16)]),
+    ([8, 512, 4], 2, 37, 1, "gdx", {}, [(_SB, 4, 2, 16)]),
+    ([8, 800, 2], 1, 37, 1, "gdx", {}, [(_SB, 4, 4, 16)]),
+    ([8, 800, 2], 2, 37, 1, "g", {}, [(_SB, 4, 4, 16)]),
+    ([8, 96, 5], 1, 37, 1, "g", {}, [(_SB, 8, 1, 16)]),                         # CH == 1 && NB >= 8: eight rows in flight, four per block
+    ([8, 96, 5], 2, 37, 1, "gdx", {}, [(_SB, 8, 1, 16)]),
+    ([8, 320, 8], 1, 37, 1, "gdx", {}, [(_SB, 8, 2, 16)]),
+    ([8, 320, 8], 2, 37, 1, "g", {}, [(_SB, 8, 2, 16)]),
+    ([8, 256, 16], 1, 37, 1, "g", {}, [(_SB, 16, 1, 16)]),
+    ([8, 256, 16], 2, 37, 1, "gdx", {}, [(_SB, 16, 1, 16)]),
+    ([8, 36, 12], 1, 37, 1, "gdx", {}, [(_SB, 16, 1, 16)]),                     # a last hidden width that is no multiple of 32
+    ([8, 36, 12], 2, 37, 1, "g", {}, [(_SB, 16, 1, 16)]),
+    # ---- 32- and 64-row blocks, one row past a block boundary
+    ([8, 32, 1], 2, B_ROWS32, default_splits(B_ROWS32), "gdx", {}, [(_SB, 1, 1, 32)]),
+    ([8, 32, 1], 2, B_ROWS64, default_splits(B_ROWS64), "gdx", {}, [(_SB, 1, 1, 64)]),
+    # ---- the non-fused skinny head: k_skinny_dw<4> / <16> + k_skinny_dx
+    ([8, 288, 9], 1, 37, 1, "gdx", {}, [("skinny_dw", 4), ("skinny_dx",)]),     # N % 4 != 0: scalar dY staging
+    ([8, 288, 9], 2, 130, 64, "g", {}, [("skinny_dw", 16)]),                    # 64 splits of 32 rows, 59 of them empty
+    ([8, 288, 12], 1, 37, 1, "g", {}, [("skinny_dw", 4), ("skinny_dx",)]),      # N % 4 == 0: 16-byte dY staging
+    ([8, 288, 12], 2, 96, 8, "gdx", {}, [("skinny_dw", 4)]),                    # B = 96 in 8 splits: splits 3..7 are empty
+    ([8, 544, 5], 1, 37, 1, "gdx", {}, [("skinny_dw", 4), ("skinny_dx",)]),
+    ([8, 544, 5], 2, 1100, default_splits(1100), "g", {}, [("skinny_dw", 4)]),
+    ([40, 3], 1, 37, 1, "gdx", {}, [("skinny_dw", 4), ("dX", "NONE", 64, "staged", 0, True)]),   # one layer: CrossQ's Linear
+    ([40, 3], 2, 37, 1, "g", {}, [("skinny_dw", 4)]),
+    ([8, 1024, 6], 2, 300, S_CLS16, "g", {}, [("skinny_dw", 16)]),
+    ([8, 1024, 6], 2, 96, S_CLS16, "gdx", {}, [("skinny_dw", 16)]),             # ... with empty splits
+    ([8, 1024, 6], 2, 300, S_CLS16 - 1, "g", {}, [("skinny_dw", 4)]),
+    ([8, 64, 3], 2, B_DX_CAP, 1, "dx", {}, [("skinny_dx",), ("dX", "NONE", 64, "staged", "runs", True)]),   # grads = NULL: dX alone
+    ([8, 288, 12], 1, 37, 1, "dx", {}, [("skinny_dx",)]),
+    # ---- the GEMM head: more than 16 outputs, or a last hidden layer wider than 1024
+    ([8, 64, 17], 1, 37, 1, "gdx", {}, [("dW", "NONE", 64, "staged", 0, True), ("dX", "DELU", 64, "staged", 0, True)]),
+    ([8, 64, 51], 2, 70, 1, "g", {}, [("dW", "NONE", 64, "staged", 0, True)]),
+    ([8, 1056, 4], 1, 37, 1, "gdx", {}, [("dX", "DELU", 64, "staged", 0, True)]),
+    ([8, 1056, 4], 2, 37, 1, "dx", {}, [("dX", "DELU", 64, "staged", 0, True)]),
+    # ---- k_gemm dW and dX(DELU) on 64 x 64 tiles: both loops, whole and ragged grids, short reductions
+    ([8, 64, 64, 17], 1, 128, 1, "gdx", {}, [("dW", "NONE", 64, "dma", 0, False), ("dX", "DELU", 64, "dma", 0, False)]),   # dX: K = 64, one DMA group
+    ([8, 64, 64, 17], 2, 64, 1, "g", {}, [("dW", "NONE", 64, "dma", 0, False)]),          # dW: 64 rows, one four-stage DMA group
+    ([8, 64, 64, 17], 1, 96, 1, "g", {}, [("dW", "NONE", 64, "staged", 0, False)]),       # dW: 96 rows, register-staged interior loop
+    ([8, 64, 96, 17], 1, 128, 1, "gdx", {}, [("dX", "DELU", 64, "staged", 0, False)]),    # dX: K = 96
+    ([8, 64, 64, 17], 2, 96, 8, "gdx", {}, [("dW", "NONE", 64, "staged", "groups", False)]),   # empty splits on the GEMM dW
+    ([8, 64, 64, 17], 2, 130, 64, "g", {}, [("dW", "NONE", 64, "staged", "groups", False)]),
+    ([8, 64, 64, 17], 1, 1100, default_splits(1100), "g", {}, [("dW", "NONE", 64, "staged", 0, False)]),
+    ([8, 64, 64, 17], 1, 512, 1, "g", {}, [("dX", "DELU", 64, "dma", "groups", False)]),
+    ([8, 64, 64, 17], 1, 4100, 1, "g", {}, [("dX", "DELU", 64, "staged", "runs", True)]),
+    ([8, 64, 64, 3], 1, 96, 8, "gdx", {}, [(_SB, 4, 1, 16), ("dW", "NONE", 64, "staged", "groups", False)]),   # fused head ignores splits, the layers below do not
+    ([48, 100, 36, 12], 1, 130, 1, "gdx", {}, [("dW", "NONE", 64, "staged", 0, True), ("dX", "DELU", 64, "staged", 0, True)]),   # widths that are no multiples of 32
+    ([88, 64, 3], 1, 128, 1, "gdx", {"ldx": 128}, [("dW", "NONE", 64, "dma", 0, True)]),  # the input tile is wider than pqlk_ld(88) = 96: the DMA loop loads 128 columns
+    ([88, 64, 3], 2, 128, 2, "g", {"ldx": 128}, [("dW", "NONE", 64, "dma", 0, True)]),
+    # ---- 128 x 128 tiles: the smallest batch (dX) and split count (dW) that select them, then whole tiles under the DMA loop
+    (WIDE, 2, B_DX128, S_DW128, "g", {}, [("dW", "NONE", 128, "staged", "groups", False), ("dX", "DELU", 128, "staged", "groups", True)]),
+    (WIDE, 2, 4096, S_DW128, "gdx", {}, [("dW", "NONE", 128, "dma", "groups", False), ("dX", "DELU", 128, "dma", "groups", False)]),
+    (WIDE, 2, 96, S_DW128, "g", {}, [("dW", "NONE", 128, "staged", "groups", False)]),    # 128-row tiles over empty splits
+    (WIDE, 2, 256, 2, "g", {}, [("dW", "NONE", 64, "dma", "runs", False)]),
+    # ---- input gradient: k_dx_slice<D> at every depth, one and two nets
+    ([40, 512, 1], 1, 37, 1, "slice", {"col0": 5, "cols": 32}, [("dx_slice", 16, 1)]),
+    ([40, 256, 1], 2, 130, 1, "slice", {"col0": 8, "cols": 5}, [("dx_slice", 16, 2)]),    # col0 % 4 == 0: 16-byte weight staging
+    ([40, 128, 1], 1, 130, 1, "slice", {"col0": 3, "cols": 1}, [("dx_slice", 4, 1)]),
+    ([40, 64, 1], 2, 37, 1, "slice", {"col0": 7, "cols": 32}, [("dx_slice", 4, 2)]),
+    ([40, 32, 1], 1, 37, 1, "slice", {"col0": 5, "cols": 5}, [("dx_slice", 1, 1)]),
+    ([40, 32, 1], 2, 130, 1, "slice", {"col0": 8, "cols": 32}, [("dx_slice", 1, 2)]),
+    ([40, 96, 1], 1, 1, 1, "slice", {"col0": 6, "cols": 1}, [("dx_slice", 1, 1)]),
+    # ---- ... and the slice GEMM through each of its three doors
+    ([48, 64, 1], 1, 70, 1, "slice", {"col0": 5, "cols": 40}, [("dX", "DTANH_SLICE", 64, "staged", 0, True)]),    # more than 32 columns
+    ([24, 48, 3], 1, 70, 1, "slice", {"col0": 8, "cols": 5}, [("dX", "DTANH_SLICE", 64, "staged", 0, True)]),     # K % 32 != 0
+    ([24, 1024, 1], 2, 130, 1, "slice", {"col0": 19, "cols": 5}, [("dX", "DTANH_SLICE", 64, "staged", 0, True)]),  # two nets x 1024 > 1264
+    ([24, 1024, 1], 1, 37, 1, "slice", {"col0": 19, "cols": 5}, [("dx_slice", 16, 1)]),   # ... one net of the same width still fits
+]
+
+
+def _name(dims, nets, B, splits, form, kw):
+    s = "x".join(str(d) for d in dims) + f"-n{nets}-B{B}-s{splits}-{form}"
+    if form == "slice":
+        s += f"-c{kw['col0']}+{kw['cols']}"
+    return s + (f"-ldx{kw['ldx']}" if "ldx" in kw else "")
+
+
+CASES = [Case(_name(dims, nets, B, splits, form, kw), list(dims), nets, B, splits, form, kw.get("col0", 0), kw.get("cols", 0),
+              kw.get("ldx", ld(dims[0])), tuple(must)) for dims, nets, B, splits, form, kw, must in _TABLE]
+CASE_BY_NAME = {c.name: c for c in CASES}
+assert len(CASE_BY_NAME) == len(CASES)
+
+# every launch tuple the table reaches: the CPU test holds the union of the rows' plans against this list.  (rows_per_block of
+# k_skinny_bwd is a runtime argument of every instantiation: 32 and 64 are reached on <1, 1> only.)
+LAUNCHES = [
+    (_SB, 1, 1, 16), (_SB, 1, 2, 16), (_SB, 1, 4, 16), (_SB, 4, 1, 16), (_SB, 4, 2, 16), (_SB, 4, 4, 16), (_SB, 8, 1, 16), (_SB, 8, 2, 16),
+    (_SB, 16, 1, 16), (_SB, 1, 1, 32), (_SB, 1, 1, 64),
+    ("skinny_dw", 4), ("skinny_dw", 16), ("skinny_dx",),
+    ("dW", "NONE", 64, "staged", 0, False), ("dW", "NONE", 64, "staged", 0, True), ("dW", "NONE", 64, "staged", "groups", False),
+    ("dW", "NONE", 64, "staged", "groups", True), ("dW", "NONE", 64, "staged", "runs", True),
+    ("dW", "NONE", 64, "dma", 0, False), ("dW", "NONE", 64, "dma", 0, True), ("dW", "NONE", 64, "dma", "runs", False),
+    ("dW", "NONE", 128, "staged", "groups", False), ("dW", "NONE", 128, "dma", "groups", False),
+    ("dX", "DELU", 64, "staged", 0, False), ("dX", "DELU", 64, "staged", 0, True), ("dX", "DELU", 64, "staged", "runs", True),
+    ("dX", "DELU", 64, "staged", "groups", False),
+    ("dX", "DELU", 64, "dma", 0, False), ("dX", "DELU", 64, "dma", "groups", False),
+    ("dX", "DELU", 128, "staged", "groups", True), ("dX", "DELU", 128, "dma", "groups", False),
+    ("dX", "NONE", 64, "staged", 0, True), ("dX", "NONE", 64, "staged", "runs", True), ("dX", "NONE", 64, "staged", "groups", True),
+    ("dX", "DTANH_SLICE", 64, "staged", 0, True),
+    ("dx_slice", 16, 1), ("dx_slice", 16, 2), ("dx_slice", 4, 1), ("dx_slice", 4, 2), ("dx_slice", 1, 1), ("dx_slice", 1, 2),
+    ("reduce", False), ("reduce", True),
+]
+
+# rows on which pqlk_mlp_backward_layers is held against the single call: empty splits on either dW kernel, a non-fused skinny head
+LAYERS_CASES = ["8x64x64x17-n2-B96-s8-gdx", "8x64x64x3-n1-B96-s8-gdx", "8x288x12-n2-B96-s8-gdx", "8x288x9-n2-B130-s64-g",
+                "8x512x512x1-n2-B96-s8-g"]
+
+# ---- pqlk_dpg_critic_backward
+DpgCase = namedtuple("DpgCase", "name dims nets B col0 cols compact")
+OWNERS = ("mixed", "ties", "net0", "net1")
+DPG_CASES = [DpgCase(f"{'x'.join(map(str, dims))}-B{B}-c{col0}+{cols}", dims, 2, B, col0, cols, compact)
+             for dims, compact in (([24, 128, 128, 1], True), ([24, 128, 128, 32, 1], True), ([24, 128, 128, 51], False))
+             for col0, cols in ((8, 16), (19, 5)) for B in (1, 130, 257)]
+DPG_BY_NAME = {c.name: c for c in DPG_CASES}
+
+
+def as_case(c):
+    """A DpgCase as the slice-only Case the shared inputs and references take."""
+    return Case(c.name, list(c.dims), c.nets, c.B, 1, "slice", c.col0, c.cols, ld(c.dims[0]), ())
+
+
+# ---------------------------------------------------------------- inputs
+HVALS = np.array([2, 1, 0.5, 0, -0.5, -0.75, -1], dtype=F32)      # ELU' = 1, 1, 1, 1, 0.5, 0.25, 0
+TVALS = np.array([0, 0.5, -0.5, 1, -1], dtype=F32)                # 1 - a^2 = 1, 0.75, 0.75, 0, 0
+# seeds moved on where a stash patch of a handful of elements missed one of the three ELU' branches (design test, CPU)
+STASH_SALT = {"8x512x512x1-n2-B3969-s8-g": 1, "24x128x128x32x1-B257-c8+16": 1, "24x128x128x32x1-B257-c19+5": 1}
+
+
+def _seed(case, what, net=0, layer=0):
+    return 7919 * sum((i + 1) * d for i, d in enumerate(case.dims)) + 131 * case.B + 17 * net + 3 * layer + 1000003 * what
+
+
+def weights(case):
+    """[net][layer] -> W (out, in) over {-1, 0, 1}."""
+    dims = case.dims
+    return [[(dd.integers((dims[l + 1], dims[l]), _seed(case, 1, n, l), 3) - 1).astype(F32) for l in range(len(dims) - 1)]
+            for n in range(case.nets)]
+
+
+def arena(case):
+    """The parameter arena (include/pqlk.h layout): W (out, ld(in)) with zero pad columns, then ld(out) biases.  The backward
+    reads no bias; they hold 1.0 so that one read by mistake moves a sum by a whole unit."""
+    dims, ns = case.dims, net_stride(case.dims)
+    out = np.zeros(ns * case.nets, dtype=F32)
+    for n, net in enumerate(weights(case)):
+        for l, w in enumerate(net):
+            wo, bo = layer_offsets(dims, l)
+            out[n * ns + wo: n * ns + bo].reshape(dims[l + 1], ld(dims[l]))[:, : dims[l]] = w
+            out[n * ns + bo: n * ns + bo + dims[l + 1]] = 1.0
+    return out
+
+
+def hidden(case):
+    """[net][layer] -> (B, dims[layer + 1]) stashed activations of the hidden layers, over HVALS."""
+    salt = STASH_SALT.get(case.name, 0)
+    return [[HVALS[dd.integers((case.B, case.dims[l + 1]), _seed(case, 2, n, l) + 977 * salt, len(HVALS))]
+             for l in range(len(case.dims) - 2)] for n in range(case.nets)]
+
+
+def stash(case, q=None):
+    """The flat activation stash: hidden blocks with zero pad columns; the output layer's block, which pqlk_mlp_backward must
+    not read, is NaN -- or holds q (nets, B) in column 0 for pqlk_dpg_critic_backward, which derives the owners from it."""
+    dims, B = case.dims, case.B
+    out = np.zeros(acts_floats(dims, case.nets, B), dtype=F32)
+    for n, net in enumerate(hidden(case)):
+        for l, h in enumerate(net):
+            off, ldh = act_offset(dims, case.nets, B, n, l)
+            out[off: off + B * ldh].reshape(B, ldh)[:, : dims[l + 1]] = h
+    off, ldo = act_offset(dims, case.nets, B, 0, len(dims) - 2)
+    out[off:] = np.nan
+    if q is not None:
+        blk = out[off:].reshape(case.nets, B, ldo)
+        blk[:] = 0
+        blk[:, :, 0] = q
+    return out
+
+
+def x_input(case):
+    """(B, ldx): integers in [-2, 2], zero pad columns up to pqlk_ld(dims[0]), IN_ONE in the columns of a wider tile beyond."""
+    out = np.zeros((case.B, case.ldx), dtype=F32)
+    out[:, : case.dims[0]] = rc.ints((case.B, case.dims[0]), _seed(case, 3), -2, 2)
+    out[:, ld(case.dims[0]):] = IN_ONE
+    return out
+
+
+def dy_input(case):
+    """(nets, B, ld(out)): integers in [-2, 2], zero pad columns."""
+    N = case.dims[-1]
+    out = np.zeros((case.nets, case.B, ld(N)), dtype=F32)
+    out[:, :, :N] = rc.ints((case.nets, case.B, N), _seed(case, 4), -2, 2)
+    return out
+
+
+def tanh_input(case):
+    """(B, cols) over TVALS."""
+    return TVALS[dd.integers((case.B, max(case.cols, 1)), _seed(case, 5), len(TVALS))]
+
+
+def owner_input(case, pattern):
+    """(B,) owner bytes (bit 0: net 0, bit 1: net 1) and a (2, B) integer Q block that says the same (minnet.h:22-27)."""
+    B = case.B
+    if pattern == "mixed":
+        own = (dd.integers((B,), _seed(case, 6), 3) + 1).astype(np.uint8)       # 1, 2 or 3 (a tie)
+    else:
+        own = np.full(B, {"ties": 3, "net0": 1, "net1": 2}[pattern], dtype=np.uint8)
+    q = np.zeros((2, B), dtype=F32)
+    q[0] = rc.ints((B,), _seed(case, 7), -3, 3)
+    q[1] = q[0] + np.where(own == 1, 1, np.where(own == 2, -1, 0)).astype(F32)
+    return own, q
+
+
+def dpg_dy_input(case, own):
+    """(2, B, 32): integer dL/dQ in column 0, zero where the net does not own the row."""
+    dy = dy_input(case)
+    dy[0, :, 0] = np.where(own & 1, np.where(dy[0, :, 0] == 0, 1, dy[0, :, 0]), 0)
+    dy[1, :, 0] = np.where(own & 2, np.where(dy[1, :, 0] == 0, -1, dy[1, :, 0]), 0)
+    return dy
+
+
+# ---------------------------------------------------------------- the float64 reference
+def elu_prime(h):
+    """ELU'(z) from the stashed h = ELU(z): 1 for h > 0, else h + 1."""
+    return np.where(h > 0, 1.0, h.astype(F64) + 1.0)
+
+
+def _chain(case, dy=None, measure=False):
+    """Walks the backward in float64: ({(net, layer): dW}, {(net, layer): db}, dx summed over the nets) and, with measure, one
+    (name, sum_i |t_i| per output element, granularity g of the terms) per product of the chain."""
+    dims, B, L = case.dims, case.B, len(case.dims) - 1
+    W, H = weights(case), hidden(case)
+    x = x_input(case)[:, : dims[0]].astype(F64)
+    dy = dy_input(case) if dy is None else dy
+    prods, dW, db, dx = [], {}, {}, np.zeros((B, dims[0]))
+    dx_mass, dx_g = np.zeros((B, dims[0])), 0
+    for n in range(case.nets):
+        dz = dy[n][:, : dims[-1]].astype(F64)
+        for l in range(L - 1, -1, -1):
+            inp = x if l == 0 else H[n][l - 1].astype(F64)
+            w = W[n][l].astype(F64)
+            dW[n, l], db[n, l] = dz.T @ inp, dz.sum(0)
+            v = dz @ w
+            if measure:
+                gz = _gran(dz)
+                prods.append((f"dW{l} net {n}", np.abs(dz).T @ np.abs(inp), gz + _gran(inp)))
+                prods.append((f"db{l} net {n}", np.abs(dz).sum(0), gz))
+                if l > 0:
+                    prods.append((f"dX{l} net {n}", np.abs(dz) @ np.abs(w), gz + _gran(w)))
+                else:
+                    dx_mass += np.abs(dz) @ np.abs(w)
+                    dx_g = max(dx_g, gz + _gran(w))
+            if l > 0:
+                dz = v * elu_prime(H[n][l - 1])
+                if measure:
+                    prods.append((f"dX{l} * ELU' net {n}", np.abs(dz), _gran(dz)))
+            else:
+                dx += v
+    if measure:
+        prods.append(("dx", dx_mass, dx_g))
+    return prods, dW, db, dx
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, owner):
+    case = CASE_BY_NAME[name] if name in CASE_BY_NAME else as_case(DPG_BY_NAME[name])
+    dy = None if owner is None else dpg_dy_input(case, owner_input(case, owner)[0])
+    _, dW, db, dx = _chain(case, dy)
+    dims, ns = case.dims, net_stride(case.dims)
+    grads = np.zeros(ns * case.nets, dtype=F64)
+    for (n, l), g in dW.items():
+        wo, bo = layer_offsets(dims, l)
+        grads[n * ns + wo: n * ns + bo].reshape(dims[l + 1], ld(dims[l]))[:, : dims[l]] = g
+        grads[n * ns + bo: n * ns + bo + dims[l + 1]] = db[n, l]
+    out = {"grads": grads, "dx": dx}
+    if case.form == "slice":
+        a = tanh_input(case).astype(F64)
+        out["slice"] = dx[:, case.col0: case.col0 + case.cols] * (1.0 - a * a)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+def reference(case, owner=None):
+    """float64: "grads" (arena layout, zero pads), "dx" (B, dims[0]) summed over the nets, "slice" (B, cols) for a slice case.
+    Computed once per case and shared; read-only.  owner: a pattern of OWNERS for the DPG cases (dy from dpg_dy_input)."""
+    return _reference(case.name, owner)
+
+
+def _gran(*arrays):
+    """Smallest g with every element of every array a multiple of 2^-g."""
+    for g in range(0, 48):
+        if all(np.array_equal(np.round(a * 2.0 ** g), a * 2.0 ** g) for a in arrays):
+            return g
+    raise AssertionError("not dyadic")
+
+
+def exactness_bits(case, owner=None):
+    """Worst log2(sum_i |t_i| 2^g) over every output element of every product of the chain, g the granularity of the product's
+    terms (the sum of its operands' granularities); the elementwise ELU' and tanh' factors count as one-term products.  At most
+    24 means every partial sum of every order is exact in fp32."""
+    dy = None if owner is None else dpg_dy_input(case, owner_input(case, owner)[0])
+    prods, _, _, dx = _chain(case, dy, measure=True)
+    worst = 0.0
+    for _, mass, g in prods:
+        if mass.size and mass.max() > 0:
+            worst = max(worst, float(np.log2(mass.max() * 2.0 ** g)))
+    if case.form == "slice":
+        a = tanh_input(case).astype(F64)
+        s = dx[:, case.col0: case.col0 + case.cols]
+        out = np.abs(s * (1.0 - a * a))
+        if out.max() > 0:
+            worst = max(worst, float(np.log2(out.max() * 2.0 ** (_gran(s) + 2))))
+    return worst
+
+
+# ---------------------------------------------------------------- checks (numpy in, AssertionError out)
+def _first_bad(got, want):
+    bad = np.argwhere(~(got.astype(F64) == want))
+    return bad
+
+
+def check_grads(grads, case, ref=None, what=""):
+    """grads: the whole gradient arena as the kernel left it.  Every element equals the float64 reference, pads are zero."""
+    want = (ref or reference(case))["grads"]
+    assert grads.shape == want.shape, what
+    bad = _first_bad(grads, want)
+    assert bad.size == 0, (f"{what}: {len(bad)} arena elements differ from the reference, first at {int(bad[0][0])}: "
+                           f"{grads[bad[0][0]]} != {want[bad[0][0]]}")
+
+
+def check_dx_full(dx, before, case, ref=None, what=""):
+    """dx, before: (B, ld_dx) after and before the call.  Columns below dims[0] equal the reference, the pad up to pqlk_ld(dims[0])
+    is zero, columns beyond are untouched."""
+    want = (ref or reference(case))["dx"]
+    K, ldk = case.dims[0], ld(case.dims[0])
+    bad = _first_bad(dx[:, :K], want)
+    assert bad.size == 0, f"{what}: {len(bad)} elements of dx differ, first at (row, col) {tuple(bad[0])}: {dx[tuple(bad[0])]} != {want[tuple(bad[0])]}"
+    assert np.all(dx[:, K:ldk] == 0), f"{what}: pad columns of dx not zero"
+    assert np.array_equal(dx[:, ldk:].view(np.uint32), before[:, ldk:].view(np.uint32)), f"{what}: columns past pqlk_ld(dims[0]) written"
+
+
+def check_dx_slice(dx, before, case, ref=None, what="", rest="untouched"):
+    """dx, before: (B, ld_dx).  The `cols` slice columns equal the reference; every other element still holds what it held
+    (rest = "untouched") or is zero (rest = "zero": the compact path of pqlk_dpg_critic_backward)."""
+    want = (ref or reference(case))["slice"]
+    bad = _first_bad(dx[:, : case.cols], want)
+    assert bad.size == 0, f"{what}: {len(bad)} slice elements differ, first at (row, col) {tuple(bad[0])}: {dx[tuple(bad[0])]} != {want[tuple(bad[0])]}"
+    if rest == "zero":
+        assert np.all(dx[:, case.cols:] == 0), f"{what}: columns past the slice not zero"
+    else:
+        assert np.array_equal(dx[:, case.cols:].view(np.uint32), before[:, case.cols:].view(np.uint32)), f"{what}: columns past the slice written"
+
+
+def bits_equal(a, b):
+    return a.shape == b.shape and bool(np.all(a.view(np.uint32) == b.view(np.uint32)))
+
+
+def dx_geometry(case):
+    """(ld_dx, ld_tanh) the GPU test uses: 32 spare columns behind the written ones; a tanh matrix with an odd row stride."""
+    if case.form == "slice":
+        return ld(case.cols) + 32, case.cols + 1
+    return ld(case.dims[0]) + 32, 0
+
+
+# ---------------------------------------------------------------- a plain numpy backward, for the checks' own tests
+FAULTS = ("last_row", "stage", "no_elu", "stale_slab", "slice_shift", "pad", "nets_not_summed")
+
+
+def model_backward(case, fault=None):
+    """What a backward leaves in (grads arena, dx matrix with POISON where nothing is written), computed by plain numpy the way
+    the kernels split the work (split slabs summed, nets summed), with one fault planted:
+      last_row         the last batch row is dropped from every product
+      stage            one 16-deep reduction stage is dropped: rows [0, 16) of every dW, the first 16 of layer 0's dX reduction
+      no_elu           ELU' is taken as 1 for h <= 0
+      stale_slab       the slab of every empty split holds POISON instead of zeros when the slabs are summed
+      slice_shift      the slice starts at col0 & ~3
+      pad              one pad column of the first layer's dW is not zero
+      nets_not_summed  the input gradient is the last net's alone"""
+    dims, B, L, nets = case.dims, case.B, len(case.dims) - 1, case.nets
+    W, H = weights(case), hidden(case)
+    x = x_input(case)[:, : dims[0]].astype(F64)
+    dy = dy_input(case)
+    rows = B - 1 if fault == "last_row" else B
+    ns = net_stride(dims)
+    grads = np.zeros(ns * nets, dtype=F64)
+    dx = np.zeros((B, dims[0]))
+    rps = rows_per_split(B, case.splits)
+    for n in range(nets):
+        dz = dy[n][:rows, : dims[-1]].astype(F64)
+        for l in range(L - 1, -1, -1):
+            inp = (x if l == 0 else H[n][l - 1].astype(F64))[:rows]
+            lo = 16 if fault == "stage" else 0
+            wo, bo = layer_offsets(dims, l)
+            gw = grads[n * ns + wo: n * ns + bo].reshape(dims[l + 1], ld(dims[l]))
+            gb = grads[n * ns + bo: n * ns + bo + ld(dims[l + 1])]
+            for s in range(case.splits):           # split slabs, summed in split order
+                a, b = max(s * rps, lo), min(rows, (s + 1) * rps)
+                if s * rps >= B and fault == "stale_slab":
+                    gw += POISON; gb += POISON
+                elif a < b:
+                    gw[:, : dims[l]] += dz[a:b].T @ inp[a:b]
+                    gb[: dims[l + 1]] += dz[a:b].sum(0)
+            w = W[n][l].astype(F64)
+            if l > 0:
+                f = elu_prime(H[n][l - 1][:rows])
+                dz = (dz @ w) * (1.0 if fault == "no_elu" else f)
+            else:
+                k0 = 16 if fault == "stage" else 0
+                v = dz[:, k0:] @ w[k0:]
+                if fault == "nets_not_summed":
+                    dx[:rows] = v
+                else:
+                    dx[:rows] += v
+    if fault == "pad":
+        wo, _ = layer_offsets(dims, 0)
+        grads[wo + ld(dims[0]) - 1] = 2.0 ** -20
+        assert ld(dims[0]) > dims[0]
+    ld_dx, _ = dx_geometry(case)
+    out = np.full((B, ld_dx), POISON, dtype=F32)
+    if case.form == "slice":
+        a = tanh_input(case).astype(F64)
+        c0 = case.col0 & ~3 if fault == "slice_shift" else case.col0
+        out[:rows, : case.cols] = (dx[:, c0: c0 + case.cols] * (1.0 - a * a))[:rows]
+    else:
+        out[:rows, : dims[0]] = dx[:rows]
+        out[:rows, dims[0]: ld(dims[0])] = 0
+    return grads.astype(F32), out

@@ -862,7 +862,7 @@ def test_mlp_backward_raw_marshals_what_the_raw_call_takes(dev, case):
 # --------------------------------------------------------------------------- shape sweep of the MLP path
 _SWEEP = [
     # dims (in, hidden..., out), nets, B, fused?
-    ([104, 512, 512, 256, 1], 2, 1024, True),     # BASELINE critic: fused body + fused head, 128x128 tiles, interior prefetch
+    ([104, 512, 512, 256, 1], 2, 1024, True),     # BASELINE critic: fused body + fused head, 64x64 tiles on the LDS-DMA loop (128x128: test_backward_paths_gpu.py)
     ([88, 512, 256, 128, 16], 1, 1000, True),     # actor, ragged batch
     ([229, 512, 256, 128, 51], 2, 96, True),      # C51 head (two narrow tiles), tiny batch
     ([60, 96, 64, 8], 1, 257, True),              # narrow layers: idle waves, short reductions
