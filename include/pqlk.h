@@ -533,6 +533,55 @@ int pqlk_bn_elu_backward(const float* dy, const float* y, const float* z, int64_
                          float* dgamma, float* dbeta, float* scratch, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * LayerNorm + ELU blocks of the LayerNorm twin critic (pql_amd/models/layernorm.py; the reference only hints at it, a
+ * commented-out critic at pql/models/mlp.py:288-310).  Row-local: any m >= 1, no batch statistics, no train / eval difference.
+ * The Linear layers run as one-layer PqlMlpDesc calls like the BatchNorm critic's.
+ *
+ * The law.  Everything is fp32 and every written operation is ONE rounding (no contraction, correctly rounded division and
+ * sqrtf, no rsqrt, no fast-math builtin, not E[z^2] - mean^2).  Per row of n = cols values:
+ *   mean   = (sum_j z_j) / (float)n
+ *   var    = (sum_j (z_j - mean)^2) / (float)n            (biased; second pass over the row)
+ *   rstd   = 1.0f / sqrtf(var + eps)
+ *   xhat_j = (z_j - mean) * rstd
+ *   y_j    = elu(xhat_j * gamma_j + beta_j),   elu(x) = x > 0 ? x : expm1f(x)
+ * and the forward also writes mean[r], rstd[r] (m floats each).  Backward, per row, with y / z / mean / rstd of the forward:
+ *   g_j  = dy_j * (y_j > 0 ? 1 : y_j + 1)
+ *   h_j  = g_j * gamma_j
+ *   c1   = (sum_j h_j) / n,   c2 = (sum_j h_j * xhat_j) / n
+ *   dz_j = rstd * (h_j - c1 - xhat_j * c2)                (left to right)
+ * and, down the columns, dbeta_j = sum_r g_rj, dgamma_j = sum_r g_rj * xhat_rj.
+ * Summation orders (fixed: the same input gives the same bits, no float atomics).  A row sum: each lane adds its values in
+ * register order, then a 64-lane xor butterfly.  A column sum: each wave adds its rows in row order, a block adds its 4 waves in
+ * wave order, and pqlk_ln_elu_backward's second launch adds the blocks' partial rows ("chunks") in 16 groups of consecutive chunks,
+ * each in chunk order, then the groups in group order.
+ *
+ * Dispatch.  One wavefront per row, 4 rows per 256-thread block.  cols <= 128 / 256 / 512 / 1024: the row is held in 2 / 4 / 8 /
+ * 16 registers per lane (seams at 128|129, 256|257, 512|513); cols > 1024: a strided path that re-reads the row (seam 1024|1025),
+ * whose column sums run down the columns over min(m, PQLK_LN_CHUNKS) row chunks.  16-byte accesses when z, y, gamma, beta (backward:
+ * dy, y, z, gamma, dz) are 16-B aligned and ld % 4 == 0, scalar ones otherwise.
+ * Grid caps.  PQLK_LN_ROW_BLOCKS: blocks of a launch that forms no column sum (the forward; the backward without parameter
+ * gradients); past 4 * PQLK_LN_ROW_BLOCKS rows a wave takes several rows.  PQLK_LN_CHUNKS: blocks of the backward that forms column
+ * sums = partial rows in scratch; past 4 * PQLK_LN_CHUNKS rows a wave takes several rows.
+ *
+ * Contract: m >= 1, cols >= 1, ld >= cols, any float-aligned pointers; columns [cols, ld) of y and dz are left untouched and
+ * nothing past column cols (of z, dy, y) or element cols (of gamma, beta) is read.  PQLK_E_NULL: a required pointer is NULL.
+ * PQLK_E_SHAPE: m <= 0, cols <= 0, ld < cols. */
+#define PQLK_LN_ROW_BLOCKS 4096
+#define PQLK_LN_CHUNKS 512
+
+/* floats of pqlk_ln_elu_backward's scratch: 2 * PQLK_LN_CHUNKS * cols (0 for cols <= 0) */
+int64_t pqlk_ln_scratch_floats(int32_t cols);
+
+int pqlk_ln_elu_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps,
+                        float* y, float* mean, float* rstd, pqlk_stream_t stream);
+
+/* dz may alias dy.  dgamma == dbeta == NULL: no parameter gradient is formed, one launch, scratch may be NULL (and is not touched);
+ * otherwise scratch >= pqlk_ln_scratch_floats(cols) floats and either output may still be NULL. */
+int pqlk_ln_elu_backward(const float* dy, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols, const float* mean,
+                         const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
+                         pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic vectorised environment step (the Isaac-Gym stand-in of BASELINE.json; not a reference component).
  * Counter-based: outputs depend only on (seed, env_offset + env, t, column), so shards of the env axis reproduce
  * slices of the global env.  next_obs ~ N(0,1) (N, obs_dim); reward = N(0,1) - 0.1 mean(action^2) (N);

@@ -12,9 +12,9 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, make_actor, make_critic
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, make_actor, make_critic
 from pql_amd.algo.pql_actor import PQLActor
-from pql_amd.models.mlp import default_splits, mlp_backward_raw
+from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.simple_replay import cfg_obs_dtype
 
 
@@ -22,6 +22,7 @@ class ActorCriticBase(PQLActor):
     TARGET_CRITIC = True   # False (CrossQ): the agent has no `critic_target` attribute at all
 
     def __init__(self, env, cfg):
+        check_critic_class(cfg)   # before anything is allocated
         cfg.algo.v_learner_gpu = cfg.algo.get("v_learner_gpu", 0) or 0
         cfg.algo.p_learner_gpu = cfg.algo.get("p_learner_gpu", 0) or 0
         super().__init__(env, cfg)
@@ -64,8 +65,13 @@ class ActorCriticBase(PQLActor):
     # ---- learning ----------------------------------------------------------------------------------
     def _own_tiles(self, ws, zeros, empty):
         """The agent's tiles, put into `ws` before the common ones (a common name set here is kept: CrossQ's x_sa / xn_sa).
-        Here: what a critic that is one MLP arena needs."""
-        B, cl = ws["B"], self.critic.layout
+        Here: what a critic that is one MLP arena needs (a critic with `forward_raw` / `backward_raw` keeps its activations and its
+        backward workspace itself)."""
+        B = ws["B"]
+        if not self._one_layout:
+            ws["dy"] = zeros((2, B, 32))
+            return
+        cl = self.critic.layout
         ws["dy"] = zeros((2, B, cl.ld_out))
         ws["acts_t"], ws["acts_c"] = empty(cl.acts_floats(B)), empty(cl.acts_floats(B))
         ws["bwd_c"] = empty(cl.bwd_ws_floats(B, ws["splits"]))
@@ -105,6 +111,48 @@ class ActorCriticBase(PQLActor):
         ws["x_obs"][:, :O].copy_(ws["x_sa"][:, :O])
         ws["x_pi"][:, :O].copy_(ws["x_sa"][:, :O])
         return idx
+
+    # ---- the critic's launches: THE place where its kind is told apart.  A critic that is one MLP arena (`layout`: DoubleQ) runs
+    # the fused-MLP calls; a per-layer critic (`forward_raw` / `backward_raw`: DoubleQLayerNorm) runs its own.
+    @property
+    def _one_layout(self):
+        return hasattr(self.critic, "layout")
+
+    def _critic_forward(self, ws, net, x, slot):
+        """Q of `net` (the critic or its target) on x (B, ld_sa) -> ((2, B, ld) output, ld).  slot: "c" (the stash `_critic_grads` /
+        `_critic_dx` read) or "t" (the target's)."""
+        if self._one_layout:
+            cl = net.layout
+            mlp_forward_raw(cl, net.arena.data, x, L.ACT_NONE, acts=ws["acts_" + slot])
+            return output_view(cl, ws["acts_" + slot], ws["B"]), cl.ld_out
+        return net.forward_raw(x), 32
+
+    def _critic_grads(self, ws, x):
+        """Backward of the critic's last forward on x from ws["dy"]: the parameter gradient -> ws["gc"]."""
+        if self._one_layout:
+            mlp_backward_raw(self.critic.layout, self.critic.arena.data, x, ws["acts_c"], ws["dy"], ws["bwd_c"], ws["gc"], ws["splits"])
+        else:
+            self.critic.backward_raw(x, ws["dy"], grads=ws["gc"])
+
+    def _critic_dx(self, ws, x, dx, tanh_of=None):
+        """Backward of the critic's last forward on x from ws["dy"] to its input, parameters frozen.  tanh_of None: all of
+        d loss / d x -> dx (B, ld_sa).  tanh_of (1, B, ld): the actor's tanh output -- the action columns, taken through that tanh
+        -> dx (1, B, ld_a), the gradient at the actor's pre-activation output."""
+        O, A = self.obs_dim[0], self.action_dim
+        if self._one_layout:
+            cl = self.critic.layout
+            if tanh_of is None:
+                mlp_backward_raw(cl, self.critic.arena.data, x, ws["acts_c"], ws["dy"], ws["bwd_c"], dx=dx)
+            else:
+                mlp_backward_raw(cl, self.critic.arena.data, x, ws["acts_c"], ws["dy"], ws["bwd_c"], dx=dx, dx_col0=O, dx_cols=A,
+                                 dx_tanh_of=tanh_of)
+            return
+        g = self.critic.backward_raw(x, ws["dy"], grads=None, need_dx=True)
+        if tanh_of is None:
+            dx.copy_(g)
+        else:
+            a = tanh_of[0]
+            dx[0, :, :A] = g[:, O:O + A] * (1.0 - a[:, :A] * a[:, :A])
 
     def _td_mse_loss(self, ws, q, qt, ld):
         """Twin MSE against r + (1 - d) gamma^n min(qt): d loss / d q -> ws["dy"], the loss -> the critic's ring."""

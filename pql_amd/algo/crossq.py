@@ -23,9 +23,9 @@ class AgentCrossQ(ActorCriticBase):
 
     def __init__(self, env, cfg):
         # (crossQ.py:21,71,132-133: the target-policy actions come from a Polyak-averaged copy unless no_tgt_actor=True, the default)
+        if str(cfg.algo.cri_class) != "DoubleQBatchNorm":   # before anything is allocated
+            raise ValueError(f"CrossQ needs the BatchNorm critic: algo.cri_class=DoubleQBatchNorm, not {cfg.algo.cri_class}")
         super().__init__(env, cfg)
-        if not hasattr(self.critic, "backward_raw"):
-            raise ValueError("CrossQ needs the BatchNorm critic (cri_class: DoubleQBatchNorm)")
 
     def _own_state(self):
         extra, opts = super()._own_state()   # stats: BatchNorm running moments

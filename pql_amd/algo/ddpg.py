@@ -12,7 +12,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.ac_base import ActorCriticBase
-from pql_amd.models.mlp import mlp_backward_raw, mlp_forward_raw, output_view
+from pql_amd.models.mlp import mlp_forward_raw, output_view
 
 
 class AgentDDPG(ActorCriticBase):
@@ -27,25 +27,23 @@ class AgentDDPG(ActorCriticBase):
         B = int(algo.batch_size)
         ws = self._workspace(B)
         O, A = self.obs_dim[0], self.action_dim
-        al, cl = self.actor.layout, self.critic.layout
+        al = self.actor.layout
         with torch.cuda.device(dev):
             self._sample(memory, ws, indices)
             draw = ws["draw"].normal_() if noise is None else noise.to(dev, torch.float32).contiguous()
             # ---- critic step (ddpg.py:147-157)
             mlp_forward_raw(al, self.actor_target.arena.data, ws["xn_obs"], L.ACT_TANH_NOISE, draw, algo.noise.tgt_pol_std,
                             algo.noise.tgt_pol_noise_bound, ws["acts_a"], ws["xn_sa"][:, O:])
-            mlp_forward_raw(cl, self.critic_target.arena.data, ws["xn_sa"], L.ACT_NONE, acts=ws["acts_t"])
-            mlp_forward_raw(cl, self.critic.arena.data, ws["x_sa"], L.ACT_NONE, acts=ws["acts_c"])
-            self._td_mse_loss(ws, output_view(cl, ws["acts_c"], B), output_view(cl, ws["acts_t"], B), cl.ld_out)
-            mlp_backward_raw(cl, self.critic.arena.data, ws["x_sa"], ws["acts_c"], ws["dy"], ws["bwd_c"], ws["gc"], ws["splits"])
+            qt, _ = self._critic_forward(ws, self.critic_target, ws["xn_sa"], "t")
+            q, ld = self._critic_forward(ws, self.critic, ws["x_sa"], "c")
+            self._td_mse_loss(ws, q, qt, ld)
+            self._critic_grads(ws, ws["x_sa"])
             self._critic_step(ws)
             # ---- actor step through the UPDATED critic (ddpg.py:159-166)
             mlp_forward_raw(al, self.actor.arena.data, ws["x_obs"], L.ACT_TANH, acts=ws["acts_a"], out2=ws["x_pi"][:, O:])
-            mlp_forward_raw(cl, self.critic.arena.data, ws["x_pi"], L.ACT_NONE, acts=ws["acts_c"])
-            self._dpg_loss(ws, output_view(cl, ws["acts_c"], B), cl.ld_out)
+            self._dpg_loss(ws, *self._critic_forward(ws, self.critic, ws["x_pi"], "c"))
             # the critic's input gradient, action columns only, through the actor's tanh: the gradient at its pre-activation output
-            mlp_backward_raw(cl, self.critic.arena.data, ws["x_pi"], ws["acts_c"], ws["dy"], ws["bwd_c"], dx=ws["dz_a"], dx_col0=O,
-                             dx_cols=A, dx_tanh_of=output_view(al, ws["acts_a"], B))
+            self._critic_dx(ws, ws["x_pi"], ws["dz_a"], tanh_of=output_view(al, ws["acts_a"], B))
             self._actor_step(ws, ws["dz_a"])
             # ---- soft_update(critic_target, critic, tau) and, with a target actor, of it (ddpg.py:134-135)
             self._update_targets()

@@ -211,9 +211,23 @@ def pump(learner, stop_event=None, max_in_flight=2):
         pending.popleft().synchronize()
 
 
+def check_critic_class(cfg, fused_learner=None):
+    """Refusals that follow from `algo.cri_class` alone, raised before anything is allocated.  fused_learner: the name of a component
+    whose launch sequences are built on the fused MLP kernels (scripts/train_pql.py, PQLVLearner, PQLPLearner)."""
+    algo = cfg.algo
+    cri = str(_cfg_get(algo, "cri_class"))
+    if cri.endswith("DoubleQLayerNorm"):
+        if _cfg_get(algo, "distl", False):
+            raise ValueError("algo.distl=True is not supported with algo.cri_class=DoubleQLayerNorm: the LayerNorm critic has no C51 head")
+        if fused_learner is not None:
+            raise ValueError(f"algo.cri_class=DoubleQLayerNorm cannot run in {fused_learner}, whose launch sequences are built on the fused "
+                             f"MLP kernels: the class is for algo=ddpg_algo / algo=sac_algo (scripts/train_baselines.py)")
+
+
 def make_critic(cfg, obs_dim, action_dim, device):
     """The critic `cfg.algo` names, freshly initialised on `device` (consumes the CPU generator like any module constructor)."""
     algo = cfg.algo
+    check_critic_class(cfg)
     distl = _cfg_get(algo, "distl", False)   # (the baselines' configs need not carry the key)
     if distl and "Distributional" not in algo.cri_class:
         algo.cri_class = "Distributional" + algo.cri_class  # same rewrite as the reference (:30-31)

@@ -17,7 +17,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
-                                  load_artifact, make_actor, make_critic, pump, resident_norm)
+                                  check_critic_class, load_artifact, make_actor, make_critic, pump, resident_norm)
 from pql_amd.models.mlp import PackedWeights, default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.simple_replay import RecordRing, _obs_width, cfg_obs_dtype, ring_plan
 from pql_amd.utils import handoff as H
@@ -29,6 +29,7 @@ class PQLPLearner(Learner):
     RESTORE_AFTER_CAPTURE = False
 
     def __init__(self, obs_dim, action_dim, cfg, process_group=None):
+        check_critic_class(cfg, "PQLPLearner")
         if not torch.cuda.is_available():
             raise L.PqlkError("PQLPLearner needs an MI355X (no CPU path)")
         device = torch.device(f"cuda:{int(cfg.algo.p_learner_gpu)}")

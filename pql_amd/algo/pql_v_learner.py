@@ -21,7 +21,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
-                                  graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
+                                  check_critic_class, graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
                                 output_view)
 from pql_amd.replay.simple_replay import ReplayBuffer, cfg_obs_dtype
@@ -34,6 +34,7 @@ class PQLVLearner(Learner):
     PARTNER = "actor"   # the target policy: a resident replica of the P-learner's actor
 
     def __init__(self, obs_dim, action_dim, cfg, process_group=None):
+        check_critic_class(cfg, "PQLVLearner")
         if not torch.cuda.is_available():
             raise L.PqlkError("PQLVLearner needs an MI355X (no CPU path)")
         device = torch.device(f"cuda:{int(cfg.algo.v_learner_gpu)}")

@@ -19,7 +19,7 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.algo.ac_base import ActorCriticBase
 from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer
-from pql_amd.models.mlp import mlp_backward_raw, mlp_forward_raw, output_view
+from pql_amd.models.mlp import mlp_forward_raw, output_view
 
 
 class AgentSAC(ActorCriticBase):
@@ -68,7 +68,7 @@ class AgentSAC(ActorCriticBase):
         B = int(algo.batch_size)
         ws = self._workspace(B)
         O, A = self.obs_dim[0], self.action_dim
-        al, cl = self.actor.layout, self.critic.layout
+        al = self.actor.layout
         with torch.cuda.device(dev):
             st = L.stream(dev)
             self._sample(memory, ws, indices)
@@ -79,25 +79,23 @@ class AgentSAC(ActorCriticBase):
             y_a = output_view(al, ws["acts_a"], B)[0]
             L.check(L.lib.pqlk_sg_head_forward(L.ptr(y_a), al.ld_out, L.ptr(e_next), B, A, L.ptr(ws["xn_sa"][:, O:]), ws["ld_sa"],
                                                L.ptr(ws["logp_next"]), st))
-            mlp_forward_raw(cl, self.critic_target.arena.data, ws["xn_sa"], L.ACT_NONE, acts=ws["acts_t"])
-            mlp_forward_raw(cl, self.critic.arena.data, ws["x_sa"], L.ACT_NONE, acts=ws["acts_c"])
-            q, qt = output_view(cl, ws["acts_c"], B), output_view(cl, ws["acts_t"], B)
-            L.check(L.lib.pqlk_sac_entropy_shift(L.ptr(qt), cl.ld_out, B * cl.ld_out, 2, L.ptr(ws["logp_next"]), L.ptr(self.log_alpha), B, st))
-            self._td_mse_loss(ws, q, qt, cl.ld_out)
-            mlp_backward_raw(cl, self.critic.arena.data, ws["x_sa"], ws["acts_c"], ws["dy"], ws["bwd_c"], ws["gc"], ws["splits"])
+            qt, _ = self._critic_forward(ws, self.critic_target, ws["xn_sa"], "t")
+            q, ld = self._critic_forward(ws, self.critic, ws["x_sa"], "c")
+            L.check(L.lib.pqlk_sac_entropy_shift(L.ptr(qt), ld, B * ld, 2, L.ptr(ws["logp_next"]), L.ptr(self.log_alpha), B, st))
+            self._td_mse_loss(ws, q, qt, ld)
+            self._critic_grads(ws, ws["x_sa"])
             self._critic_step(ws)
             # ---- actor step through the UPDATED critic (sac.py:148-153): L = mean(alpha log pi(a|s) - min Q(s, a)), a ~ pi(.|s)
             mlp_forward_raw(al, self.actor.arena.data, ws["x_obs"], L.ACT_NONE, acts=ws["acts_a"])
             L.check(L.lib.pqlk_sg_head_forward(L.ptr(y_a), al.ld_out, L.ptr(e_cur), B, A, L.ptr(ws["x_pi"][:, O:]), ws["ld_sa"],
                                                L.ptr(ws["logp"]), st))
-            mlp_forward_raw(cl, self.critic.arena.data, ws["x_pi"], L.ACT_NONE, acts=ws["acts_c"])
-            self._dpg_loss(ws, output_view(cl, ws["acts_c"], B), cl.ld_out)
+            self._dpg_loss(ws, *self._critic_forward(ws, self.critic, ws["x_pi"], "c"))
             # temperature terms with the alpha the actor loss uses (before its own update): actor loss += alpha mean(log pi),
             # g_alpha = alpha * mean(-log pi - target_entropy)
             L.check(L.lib.pqlk_sac_alpha_terms(L.ptr(ws["logp"]), B, L.ptr(self.log_alpha), self.target_entropy, L.ptr(ws["g_alpha"]),
                                                L.ptr(self.alpha_loss), L.ptr(self.aloss), L.ptr(self.aopt.step), LOSS_RING, st))
             # dL/da = -(1/B) d minQ / da : the critic's input gradient, action columns [O, O+A) of dx_pi
-            mlp_backward_raw(cl, self.critic.arena.data, ws["x_pi"], ws["acts_c"], ws["dy"], ws["bwd_c"], dx=ws["dx_pi"])
+            self._critic_dx(ws, ws["x_pi"], ws["dx_pi"])
             L.check(L.lib.pqlk_sg_head_backward(L.ptr(y_a), al.ld_out, L.ptr(e_cur), L.ptr(ws["x_pi"][:, O:]), ws["ld_sa"],
                                                 L.ptr(ws["dx_pi"][:, O:]), ws["ld_sa"], L.ptr(self.log_alpha), 1.0 / B, B, A,
                                                 L.ptr(ws["dy_a"]), st))

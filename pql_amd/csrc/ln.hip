@@ -1,0 +1,335 @@
+// LayerNorm + ELU for the LayerNorm twin critic (DoubleQLayerNorm: `Linear -> LayerNorm -> ELU` blocks on DDPG / SAC).  The Linear
+// parts run on the fp32-MFMA GEMMs (a one-layer PqlMlpDesc); what is here is the row-wise normalise + activate pass, its backward
+// and the column sums the backward needs for dgamma / dbeta.  The law is written op by op in include/pqlk.h; every written
+// operation is one fp32 rounding (the library is built with -ffp-contract=off, division and sqrtf are correctly rounded).
+//
+// Shape: one wavefront per row, four rows per 256-thread block, the row held in registers (VPL values per lane: 2 / 4 / 8 / 16 for
+// cols <= 128 / 256 / 512 / 1024, ragged widths masked); wider rows take a strided path that re-reads the row.  16-byte (8-byte at
+// VPL = 2) accesses when every pointer is 16-B aligned and ld % 4 == 0, scalar ones otherwise.  Row sums: per-lane partials in
+// register order, then the xor butterfly of wave_sum (every lane ends with the same bits).  No float atomics anywhere.
+#include "pqlk_common.h"
+
+__device__ __forceinline__ float ln_elu(float x) { return x > 0.f ? x : expm1f(x); }   // nn.ELU(alpha=1)
+
+#define LN_WAVES 4             // rows in flight per block
+#define LN_MAX_REG_COLS 1024   // widest row held in registers
+
+// register slot i of lane `lane` <-> column: VEC: chunks of V consecutive columns, chunk k of a lane at (k * 64 + lane) * V;
+// scalar: column i * 64 + lane
+template <int VPL, bool VEC>
+struct LnMap {
+  static constexpr int V = VEC ? (VPL == 2 ? 2 : 4) : 1;
+  static constexpr int NCH = VPL / V;
+  __device__ static __forceinline__ int col(int i, int lane) { return ((i / V) * 64 + lane) * V + (i % V); }
+};
+
+// p[0, cols) -> v, slots past cols = 0 (nothing past cols is read)
+template <int VPL, bool VEC>
+__device__ __forceinline__ void ln_load(const float* __restrict__ p, int cols, int lane, float (&v)[VPL]) {
+  using M = LnMap<VPL, VEC>;
+#pragma unroll
+  for (int k = 0; k < M::NCH; ++k) {
+    const int c0 = (k * 64 + lane) * M::V;
+    if (M::V == 4 && c0 + 4 <= cols) {
+      const float4 t = *reinterpret_cast<const float4*>(p + c0);
+      v[k * M::V + 0] = t.x; v[k * M::V + 1 % M::V] = t.y; v[k * M::V + 2 % M::V] = t.z; v[k * M::V + 3 % M::V] = t.w;
+    } else if (M::V == 2 && c0 + 2 <= cols) {
+      const float2 t = *reinterpret_cast<const float2*>(p + c0);
+      v[k * M::V + 0] = t.x; v[k * M::V + 1 % M::V] = t.y;
+    } else {
+#pragma unroll
+      for (int e = 0; e < M::V; ++e) v[k * M::V + e] = c0 + e < cols ? p[c0 + e] : 0.f;
+    }
+  }
+}
+
+// v -> p[0, cols); nothing past cols is written
+template <int VPL, bool VEC>
+__device__ __forceinline__ void ln_store(float* __restrict__ p, int cols, int lane, const float (&v)[VPL]) {
+  using M = LnMap<VPL, VEC>;
+#pragma unroll
+  for (int k = 0; k < M::NCH; ++k) {
+    const int c0 = (k * 64 + lane) * M::V;
+    if (M::V == 4 && c0 + 4 <= cols) {
+      *reinterpret_cast<float4*>(p + c0) = make_float4(v[k * M::V + 0], v[k * M::V + 1 % M::V], v[k * M::V + 2 % M::V], v[k * M::V + 3 % M::V]);
+    } else if (M::V == 2 && c0 + 2 <= cols) {
+      *reinterpret_cast<float2*>(p + c0) = make_float2(v[k * M::V + 0], v[k * M::V + 1 % M::V]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < M::V; ++e)
+        if (c0 + e < cols) p[c0 + e] = v[k * M::V + e];
+    }
+  }
+}
+
+template <int VPL, bool VEC>
+__global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z, int64_t ld, int64_t m, int cols,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                    float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
+  using M = LnMap<VPL, VEC>;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float ga[VPL], be[VPL];
+  ln_load<VPL, VEC>(gamma, cols, lane, ga);
+  ln_load<VPL, VEC>(beta, cols, lane, be);
+  const float n = (float)cols;
+  for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
+    float v[VPL];
+    ln_load<VPL, VEC>(z + r * ld, cols, lane, v);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) s += v[i];
+    const float mu = wave_sum(s) / n;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const float d = M::col(i, lane) < cols ? v[i] - mu : 0.f;
+      v[i] = d;
+      q += d * d;
+    }
+    const float var = wave_sum(q) / n;
+    const float rs = 1.0f / sqrtf(var + eps);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) v[i] = ln_elu(v[i] * rs * ga[i] + be[i]);
+    ln_store<VPL, VEC>(y + r * ld, cols, lane, v);
+    if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
+  }
+}
+
+// rows wider than LN_MAX_REG_COLS: the same law with the row re-read from memory (sum, squared deviations, output)
+__global__ __launch_bounds__(256) void k_ln_elu_fwd_wide(const float* __restrict__ z, int64_t ld, int64_t m, int cols,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                         float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float n = (float)cols;
+  for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
+    const float* zr = z + r * ld;
+    float* yr = y + r * ld;
+    float s = 0.f;
+    for (int c = lane; c < cols; c += 64) s += zr[c];
+    const float mu = wave_sum(s) / n;
+    float q = 0.f;
+    for (int c = lane; c < cols; c += 64) { const float d = zr[c] - mu; q += d * d; }
+    const float var = wave_sum(q) / n;
+    const float rs = 1.0f / sqrtf(var + eps);
+    for (int c = lane; c < cols; c += 64) yr[c] = ln_elu((zr[c] - mu) * rs * gamma[c] + beta[c]);
+    if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
+  }
+}
+
+// Backward, one wave per row.  PARAMS: each wave also accumulates its rows' g and g * xhat per column in registers; the block
+// folds its waves through LDS in wave order and writes one partial row: part[(blockIdx.x * 2 + {0: dbeta, 1: dgamma}) * cols + c].
+template <int VPL, bool VEC, bool PARAMS>
+__global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float* __restrict__ y, const float* __restrict__ z,
+                                                    int64_t ld, int64_t m, int cols, const float* __restrict__ mean,
+                                                    const float* __restrict__ rstd, const float* __restrict__ gamma, float* dz,
+                                                    float* __restrict__ part) {
+  using M = LnMap<VPL, VEC>;
+  __shared__ float sh[PARAMS ? 2 * LN_WAVES * VPL * 64 : 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float ga[VPL], accb[VPL], accg[VPL];
+  ln_load<VPL, VEC>(gamma, cols, lane, ga);
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) accb[i] = accg[i] = 0.f;
+  const float n = (float)cols;
+  for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
+    const float mu = mean[r], rs = rstd[r];
+    float h[VPL], xh[VPL], yv[VPL];
+    ln_load<VPL, VEC>(dy + r * ld, cols, lane, h);
+    ln_load<VPL, VEC>(y + r * ld, cols, lane, yv);
+    ln_load<VPL, VEC>(z + r * ld, cols, lane, xh);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const bool in = M::col(i, lane) < cols;
+      const float g = in ? h[i] * (yv[i] > 0.f ? 1.f : yv[i] + 1.f) : 0.f;
+      const float x = in ? (xh[i] - mu) * rs : 0.f;
+      const float hh = g * ga[i];
+      if (PARAMS) { accb[i] += g; accg[i] += g * x; }
+      s1 += hh;
+      s2 += hh * x;
+      h[i] = hh; xh[i] = x;
+    }
+    const float c1 = wave_sum(s1) / n, c2 = wave_sum(s2) / n;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) h[i] = rs * (h[i] - c1 - xh[i] * c2);
+    ln_store<VPL, VEC>(dz + r * ld, cols, lane, h);
+  }
+  if (PARAMS) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      sh[(0 * LN_WAVES + wave) * (VPL * 64) + i * 64 + lane] = accb[i];
+      sh[(1 * LN_WAVES + wave) * (VPL * 64) + i * 64 + lane] = accg[i];
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 2 * VPL * 64; idx += 256) {
+      const int which = idx / (VPL * 64), slot = idx % (VPL * 64);
+      const int c = M::col(slot / 64, slot % 64);
+      if (c < cols) {
+        const float* s = sh + which * LN_WAVES * (VPL * 64) + slot;
+        float t = s[0];
+#pragma unroll
+        for (int w = 1; w < LN_WAVES; ++w) t += s[w * (VPL * 64)];
+        part[((int64_t)blockIdx.x * 2 + which) * cols + c] = t;
+      }
+    }
+  }
+}
+
+// wide rows: dz with the row re-read (dy fully read before dz, which may alias it, is written: the sums need all of it first,
+// and every element is then read and written by the same lane)
+__global__ __launch_bounds__(256) void k_ln_elu_bwd_wide(const float* dy, const float* __restrict__ y, const float* __restrict__ z,
+                                                         int64_t ld, int64_t m, int cols, const float* __restrict__ mean,
+                                                         const float* __restrict__ rstd, const float* __restrict__ gamma, float* dz) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float n = (float)cols;
+  for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
+    const float mu = mean[r], rs = rstd[r];
+    const float *dr = dy + r * ld, *yr = y + r * ld, *zr = z + r * ld;
+    float* o = dz + r * ld;
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = lane; c < cols; c += 64) {
+      const float yy = yr[c];
+      const float hh = dr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      s1 += hh;
+      s2 += hh * ((zr[c] - mu) * rs);
+    }
+    const float c1 = wave_sum(s1) / n, c2 = wave_sum(s2) / n;
+    for (int c = lane; c < cols; c += 64) {
+      const float yy = yr[c];
+      const float hh = dr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      o[c] = rs * (hh - c1 - ((zr[c] - mu) * rs) * c2);
+    }
+  }
+}
+
+// wide rows: the column sums of g and g * xhat over a chunk of rows, down the columns like k_bn_bwd_sums -> the same partial layout
+__global__ __launch_bounds__(256) void k_ln_bwd_sums_wide(const float* __restrict__ dy, const float* __restrict__ y,
+                                                          const float* __restrict__ z, int64_t ld, int64_t m, int cols,
+                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                          float* __restrict__ part) {
+  __shared__ float sh[2][4][64];
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  float s1 = 0.f, s2 = 0.f;
+  if (c < cols) {
+    const int64_t rows_per = (m + gridDim.y - 1) / gridDim.y;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per, r1 = min(m, r0 + rows_per);
+    for (int64_t r = r0 + rl; r < r1; r += 4) {
+      const float yy = y[r * ld + c];
+      const float g = dy[r * ld + c] * (yy > 0.f ? 1.f : yy + 1.f);
+      s1 += g;
+      s2 += g * ((z[r * ld + c] - mean[r]) * rstd[r]);
+    }
+  }
+  sh[0][rl][cl] = s1; sh[1][rl][cl] = s2;
+  __syncthreads();
+  if (rl == 0 && c < cols) {
+    part[((int64_t)blockIdx.y * 2 + 0) * cols + c] = (sh[0][0][cl] + sh[0][1][cl]) + (sh[0][2][cl] + sh[0][3][cl]);
+    part[((int64_t)blockIdx.y * 2 + 1) * cols + c] = (sh[1][0][cl] + sh[1][1][cl]) + (sh[1][2][cl] + sh[1][3][cl]);
+  }
+}
+
+// fold the chunk partials in index order: 16 columns x 16 groups of consecutive chunks per block, the groups then in group order.
+// blockIdx.y: 0 -> dbeta, 1 -> dgamma
+#define LN_FOLD_GROUPS 16
+__global__ __launch_bounds__(256) void k_ln_fold(const float* __restrict__ part, int chunks, int cols, float* __restrict__ dgamma,
+                                                 float* __restrict__ dbeta) {
+  __shared__ float sh[LN_FOLD_GROUPS][16];
+  const int cl = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl, which = blockIdx.y;
+  float* out = which ? dgamma : dbeta;
+  if (!out) return;   // (uniform over the block)
+  const int per = (chunks + LN_FOLD_GROUPS - 1) / LN_FOLD_GROUPS;
+  const int k0 = g * per, k1 = min(chunks, k0 + per);
+  float s = 0.f;
+  if (c < cols)
+    for (int k = k0; k < k1; ++k) s += part[((int64_t)k * 2 + which) * cols + c];
+  sh[g][cl] = s;
+  __syncthreads();
+  if (g == 0 && c < cols) {
+    float t = sh[0][cl];
+#pragma unroll
+    for (int j = 1; j < LN_FOLD_GROUPS; ++j) t += sh[j][cl];
+    out[c] = t;
+  }
+}
+
+static inline unsigned ln_blocks(int64_t m, int64_t cap) {
+  const int64_t nb = (m + LN_WAVES - 1) / LN_WAVES;
+  return (unsigned)(nb < cap ? nb : cap);
+}
+
+template <int VPL>
+static void ln_launch_fwd(bool vec, unsigned grid, hipStream_t s, const float* z, int64_t ld, int64_t m, int cols, const float* gamma,
+                          const float* beta, float eps, float* y, float* mean, float* rstd) {
+  if (vec)
+    hipLaunchKernelGGL((k_ln_elu_fwd<VPL, true>), dim3(grid), dim3(256), 0, s, z, ld, m, cols, gamma, beta, eps, y, mean, rstd);
+  else
+    hipLaunchKernelGGL((k_ln_elu_fwd<VPL, false>), dim3(grid), dim3(256), 0, s, z, ld, m, cols, gamma, beta, eps, y, mean, rstd);
+}
+
+template <int VPL>
+static void ln_launch_bwd(bool vec, bool params, unsigned grid, hipStream_t s, const float* dy, const float* y, const float* z, int64_t ld,
+                          int64_t m, int cols, const float* mean, const float* rstd, const float* gamma, float* dz, float* part) {
+  if (vec && params)
+    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, true, true>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+  else if (vec)
+    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, true, false>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+  else if (params)
+    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, false, true>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+  else
+    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, false, false>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+}
+
+extern "C" int64_t pqlk_ln_scratch_floats(int32_t cols) { return cols > 0 ? (int64_t)2 * PQLK_LN_CHUNKS * cols : 0; }
+
+extern "C" int pqlk_ln_elu_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps,
+                                   float* y, float* mean, float* rstd, pqlk_stream_t stream) {
+  PQLK_REQUIRE(z && gamma && beta && y && mean && rstd, PQLK_E_NULL);
+  PQLK_REQUIRE(m > 0 && cols > 0 && ld >= cols, PQLK_E_SHAPE);
+  const unsigned grid = ln_blocks(m, PQLK_LN_ROW_BLOCKS);
+  const bool vec = pqlk_aligned16(z) && pqlk_aligned16(y) && pqlk_aligned16(gamma) && pqlk_aligned16(beta) && ld % 4 == 0;
+  hipStream_t s = pqlk_s(stream);
+  if (cols <= 128) ln_launch_fwd<2>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
+  else if (cols <= 256) ln_launch_fwd<4>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
+  else if (cols <= 512) ln_launch_fwd<8>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
+  else if (cols <= LN_MAX_REG_COLS) ln_launch_fwd<16>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
+  else hipLaunchKernelGGL(k_ln_elu_fwd_wide, dim3(grid), dim3(256), 0, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
+extern "C" int pqlk_ln_elu_backward(const float* dy, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols, const float* mean,
+                                    const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
+                                    pqlk_stream_t stream) {
+  const bool params = dgamma || dbeta;
+  PQLK_REQUIRE(dy && y && z && mean && rstd && gamma && dz && (scratch || !params), PQLK_E_NULL);
+  PQLK_REQUIRE(m > 0 && cols > 0 && ld >= cols, PQLK_E_SHAPE);
+  hipStream_t s = pqlk_s(stream);
+  const int c = (int)cols;
+  int chunks;
+  if (cols <= LN_MAX_REG_COLS) {
+    const unsigned grid = ln_blocks(m, params ? PQLK_LN_CHUNKS : PQLK_LN_ROW_BLOCKS);
+    const bool vec = pqlk_aligned16(dy) && pqlk_aligned16(y) && pqlk_aligned16(z) && pqlk_aligned16(gamma) && pqlk_aligned16(dz) && ld % 4 == 0;
+    if (cols <= 128) ln_launch_bwd<2>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
+    else if (cols <= 256) ln_launch_bwd<4>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
+    else if (cols <= 512) ln_launch_bwd<8>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
+    else ln_launch_bwd<16>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
+    PQLK_LAUNCH_CHECK();
+    chunks = (int)grid;
+  } else {
+    chunks = (int)(m < PQLK_LN_CHUNKS ? m : PQLK_LN_CHUNKS);
+    if (params) {   // before dz, which may alias dy, is written
+      hipLaunchKernelGGL(k_ln_bwd_sums_wide, dim3((unsigned)((cols + 63) / 64), (unsigned)chunks), dim3(256), 0, s, dy, y, z, ld, m, c, mean,
+                         rstd, scratch);
+      PQLK_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_ln_elu_bwd_wide, dim3(ln_blocks(m, PQLK_LN_ROW_BLOCKS)), dim3(256), 0, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz);
+    PQLK_LAUNCH_CHECK();
+  }
+  if (params) {
+    hipLaunchKernelGGL(k_ln_fold, dim3((unsigned)((cols + 15) / 16), 2), dim3(256), 0, s, scratch, chunks, c, dgamma, dbeta);
+    PQLK_LAUNCH_CHECK();
+  }
+  return PQLK_OK;
+}

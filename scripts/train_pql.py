@@ -35,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import pql_amd  # noqa: E402,F401
+from pql_amd.algo.learner import check_critic_class  # noqa: E402
 from pql_amd.algo.pql_actor import PQLActor  # noqa: E402
 from pql_amd.algo.pql_p_learner import PQLPLearner, asyn_p_learner  # noqa: E402
 from pql_amd.algo.pql_v_learner import PQLVLearner, asyn_v_learner  # noqa: E402
@@ -110,6 +111,7 @@ def load_checkpoint(opt, cfg, env, pql_actor, v_learner, p_learner, evaluator):
 def main(cfg, on_finish=None):
     """`on_finish(pql_actor, v_learner, p_learner)`: called once the loop has stopped and the device is idle (tools/learn_pointmass.py
     evaluates the trained policy)."""
+    check_critic_class(cfg, "scripts/train_pql.py")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

@@ -616,6 +616,133 @@ def gen_ddpg(R, out, steps=3):
     out["ddpg_norm_mean"] = norm[0]; out["ddpg_norm_var"] = norm[1]
 
 
+# --------------------------------------------------------------------------- LayerNorm twin critic on DDPG / SAC
+def _ln_critic(O, A, hidden=(512, 256, 128)):
+    """The torch definition of DoubleQLayerNorm: twin `nn.Sequential(Linear, LayerNorm, ELU, ..., Linear)` on cat(state, action), with
+    the surface the reference's agents call (get_q1_q2 / get_q_min / get_q1) and the reference's key layout (net_q{1,2}.net.*)."""
+    from torch import nn
+
+    class _Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            dims, layers = [O + A, *hidden], []
+            for i, o in zip(dims[:-1], dims[1:]):
+                layers += [nn.Linear(i, o), nn.LayerNorm(o, eps=1e-5), nn.ELU()]
+            self.net = nn.Sequential(*layers, nn.Linear(dims[-1], 1))
+
+        def forward(self, x):
+            return self.net(x)
+
+    class _DoubleQLayerNorm(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.net_q1, self.net_q2 = _Net(), _Net()
+
+        def get_q1_q2(self, state, action):
+            x = torch.cat((state, action), dim=1)
+            return self.net_q1(x), self.net_q2(x)
+
+        def get_q_min(self, state, action):
+            return torch.min(*self.get_q1_q2(state, action))
+
+        def get_q1(self, state, action):
+            return self.net_q1(torch.cat((state, action), dim=1))
+
+    return _DoubleQLayerNorm()
+
+
+def gen_layernorm(R, out, steps=3):
+    """DoubleQLayerNorm (`_ln_critic`) plugged into the reference's own AgentDDPG and AgentSAC, exactly as gen_ddpg / the SAC trace plug
+    in DoubleQ: a known-answer forward / backward, a DDPG trace and a SAC trace, (O, A, B) = (8, 2, 64).  Its own seeds."""
+    from torch import nn
+    O, A, B = 8, 2, 64
+    norm = (dd.uniform((O,), 801, -0.5, 0.5), dd.uniform((O,), 802, 0.5, 2.0))
+    data = [T(d) for d in _fill_data(O, A, 300, 810)]
+    cstate = dd.bn_critic_state(O, A, 43)   # Linear weights + non-trivial gamma / beta under the keys 0,1,3,4,6,7,9
+
+    # ---- known answer: Q1 / Q2, and dX + parameter-gradient summaries of sum(dq1 * Q1) + sum(dq2 * Q2)
+    q = _ln_critic(O, A); load_state(q, cstate)
+    x = T(np.concatenate([dd.uniform((B, O), 73, -2, 2), dd.uniform((B, A), 74, -1, 1)], axis=1)).requires_grad_(True)
+    dq = dd.uniform((2, B, 1), 75, -1, 1)
+    q1, q2 = q.get_q1_q2(x[:, :O], x[:, O:])
+    grads = torch.autograd.grad((T(dq[0]) * q1).sum() + (T(dq[1]) * q2).sum(), [x, *q.parameters()])
+    out["ln_kat_q1"], out["ln_kat_q2"] = q1.detach().numpy(), q2.detach().numpy()
+    out["ln_kat_dq"] = dq
+    out["ln_kat_dx"] = grads[0].numpy().copy()
+    for (k, _), g in zip(q.named_parameters(), grads[1:]):
+        out[f"ln_kat_g_{k}"] = dd.summarize(g.numpy())
+    out["ln_kat_g_q1_ln0_gamma"] = grads[1:][2].numpy().copy()     # net_q1.net.1.weight
+    out["ln_kat_g_q1_ln0_beta"] = grads[1:][3].numpy().copy()
+
+    def summaries(tag, st, s, names):
+        for short, mod in names:
+            for k, p in mod.named_parameters():
+                out[f"{tag}_s{st}_{short}_{k}"] = dd.summarize(p.detach().numpy())
+
+    # ---- DDPG trace (ddpg.py:119-166), no_tgt_actor=False: critic target and a Polyak-averaged actor target that starts away
+    cfg = NS(info_track_keys=None, device="cpu",
+             algo=NS(batch_size=B, obs_norm=True, gamma=0.99, nstep=3, tau=0.05, max_grad_norm=0.5, no_tgt_actor=False, update_times=1,
+                     noise=NS(tgt_pol_std=0.8, tgt_pol_noise_bound=0.2)))
+    s = R.AgentDDPG.__new__(R.AgentDDPG)
+    s.cfg, s.obs_dim, s.action_dim, s.device = cfg, (O,), A, torch.device("cpu")
+    s.actor = R.TanhMLPPolicy((O,), A); load_state(s.actor, dd.mlp_state(O, A, 11))
+    s.critic = _ln_critic(O, A); load_state(s.critic, cstate)
+    s.critic_target = deepcopy(s.critic)
+    s.actor_target = deepcopy(s.actor); load_state(s.actor_target, dd.mlp_state(O, A, 13))
+    s.actor_optimizer = torch.optim.AdamW(s.actor.parameters(), 5e-4)
+    s.critic_optimizer = torch.optim.AdamW(s.critic.parameters(), 5e-4)
+    s.obs_rms = R.RunningMeanStd(shape=(O,), device="cpu"); s.obs_rms.mean, s.obs_rms.var = T(norm[0]), T(norm[1])
+    closs, aloss, idxs = [], [], []
+    with _Capture(9300) as cap:
+        for st in range(steps):
+            idx = T(dd.integers((B,), 9400 + st, 300)); idxs.append(idx.numpy())
+            obs, act, rew, nobs, done = (d[idx] for d in data)
+            obs, nobs = s.obs_rms.normalize(obs), s.obs_rms.normalize(nobs)
+            cl, _ = s.update_critic(obs, act, rew, nobs, done)
+            al, _ = s.update_actor(obs)
+            R.soft_update(s.critic_target, s.critic, cfg.algo.tau)
+            R.soft_update(s.actor_target, s.actor, cfg.algo.tau)
+            closs.append(cl); aloss.append(al)
+            summaries("ln_ddpg", st, s, (("a", s.actor), ("c", s.critic), ("t", s.critic_target), ("at", s.actor_target)))
+    out["ln_ddpg_closs"] = np.array(closs, np.float64); out["ln_ddpg_aloss"] = np.array(aloss, np.float64)
+    out["ln_ddpg_idx"] = np.stack(idxs); out["ln_ddpg_noise"] = np.stack(cap.noise)
+    out["ln_ddpg_final_actor_last_w"] = s.actor.state_dict()["net.6.weight"].numpy().copy()
+    out["ln_ddpg_final_q1_last_w"] = s.critic.state_dict()["net_q1.net.9.weight"].numpy().copy()
+    out["ln_ddpg_final_tq1_ln0_gamma"] = s.critic_target.state_dict()["net_q1.net.1.weight"].numpy().copy()
+
+    # ---- SAC trace (sac.py:98-108): critic step, actor step, temperature step, Polyak; RNG = idx, eps_next, eps_cur per step
+    cfg = NS(info_track_keys=None, device="cpu",
+             algo=NS(batch_size=B, obs_norm=True, gamma=0.99, nstep=3, tau=0.05, max_grad_norm=0.5, alpha=None, alpha_lr=0.005,
+                     no_tgt_actor=True, update_times=1))
+    s = R.AgentSAC.__new__(R.AgentSAC)
+    s.cfg, s.obs_dim, s.action_dim, s.device = cfg, (O,), A, torch.device("cpu")
+    s.actor = R.TanhDiagGaussianMLPPolicy((O,), A); load_state(s.actor, dd.mlp_state(O, 2 * A, 11))
+    s.critic = _ln_critic(O, A); load_state(s.critic, cstate)
+    s.critic_target = deepcopy(s.critic); s.actor_target = s.actor
+    s.actor_optimizer = torch.optim.AdamW(s.actor.parameters(), 5e-4)
+    s.critic_optimizer = torch.optim.AdamW(s.critic.parameters(), 5e-4)
+    s.log_alpha = nn.Parameter(torch.zeros(1)); s.alpha_optim = torch.optim.AdamW([s.log_alpha], lr=cfg.algo.alpha_lr)
+    s.target_entropy = -A
+    s.obs_rms = R.RunningMeanStd(shape=(O,), device="cpu"); s.obs_rms.mean, s.obs_rms.var = T(norm[0]), T(norm[1])
+    closs, aloss, alphas, idxs = [], [], [], []
+    with _EpsCapture(9500) as cap:
+        for st in range(steps):
+            idx = T(dd.integers((B,), 9600 + st, 300)); idxs.append(idx.numpy())
+            obs, act, rew, nobs, done = (d[idx] for d in data)
+            obs, nobs = s.obs_rms.normalize(obs), s.obs_rms.normalize(nobs)
+            cl, _ = s.update_critic(obs, act, rew, nobs, done)
+            al, _ = s.update_actor(obs)
+            R.soft_update(s.critic_target, s.critic, cfg.algo.tau)
+            closs.append(cl); aloss.append(al); alphas.append(float(s.log_alpha.detach()))
+            summaries("ln_sac", st, s, (("a", s.actor), ("c", s.critic), ("t", s.critic_target)))
+    out["ln_sac_closs"] = np.array(closs, np.float64); out["ln_sac_aloss"] = np.array(aloss, np.float64)
+    out["ln_sac_log_alpha"] = np.array(alphas, np.float64)
+    out["ln_sac_idx"] = np.stack(idxs); out["ln_sac_eps"] = np.stack(cap.draws)   # (2*steps, B, A): next, cur, next, cur, ...
+    out["ln_sac_final_actor_last_w"] = s.actor.state_dict()["net.6.weight"].numpy().copy()
+    out["ln_sac_final_q1_last_w"] = s.critic.state_dict()["net_q1.net.9.weight"].numpy().copy()
+    out["ln_norm_mean"] = norm[0]; out["ln_norm_var"] = norm[1]
+
+
 def gen_ckpt(R, out):
     """f1: the ONE weight file the reference ships (pql/model.pth, a PPO actor / critic pair in the checkpoint format of
     pql/utils/model_util.py:24-36) read with weights_only=True and pushed through the reference's MLPNet (mlp.py:27-40):
@@ -767,7 +894,7 @@ def main():
     only = set(sys.argv[1:])
     for name, fn in (("replay", gen_ring), ("nstep", gen_nstep), ("models", gen_models), ("math", gen_math),
                      ("learners", gen_learners), ("sac", gen_sac), ("crossq", gen_crossq), ("ddpg", gen_ddpg), ("ckpt", gen_ckpt),
-                     ("ppo", gen_ppo)):
+                     ("ppo", gen_ppo), ("layernorm", gen_layernorm)):
         if only and name not in only:
             continue
         out = {}

@@ -18,6 +18,7 @@ are the same, the episode length is 128 and the upper yardstick is the energy co
     python tools/learn_pointmass.py --algos ddpg --shapes small --seeds 1 --iters 200      # a quick look
     python tools/learn_pointmass.py --override algo.replay_obs_dtype=float16 --out profiles/pointmass_learning_fp16.json
     python tools/learn_pointmass.py --algos pql --override algo.target_dtype=bfloat16 --versus-default --out profiles/pointmass_learning_bf16.json
+    python tools/learn_pointmass.py --algos ddpg --shapes small --override algo.cri_class=DoubleQLayerNorm --versus-default --curve 125,250,500 --out profiles/pointmass_learning_ln.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --curve 500,1000,2000,4000,8000 --out profiles/swingup_learning.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.distl=True --out profiles/swingup_learning_distl.json
 """
