@@ -428,6 +428,69 @@ int pqlk_dpg_loss(const float* q, int64_t ld, int32_t k, const float* support /*
                   pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Prioritized experience replay (Schaul et al. 2016, proportional variant) on a device sum tree.  The reference has no
+ * prioritized replay; the formulas below are the paper's.
+ *
+ * `tree` is ONE flat fp32 device buffer of pqlk_per_tree_floats(capacity) floats, zeroed once by the caller, that holds a
+ * radix-64 sum tree over the ring's rows:
+ *     level 0    : n_0 = capacity leaves, leaf r = priority_r ^ alpha (0 for a row never written);
+ *     level l + 1: n_{l+1} = ceil(n_l / 64) nodes, node j = the sum of nodes [64 j, 64 j + 64) of level l;
+ *     levels go on until one has at most 64 nodes: pqlk_per_levels(capacity) of them (5 000 000 rows: 4); the total is the sum
+ *     of that top level, formed where it is needed and stored nowhere.
+ * Every level is padded with zeros to a multiple of 64 floats and the levels lie one after the other, level 0 first:
+ * pqlk_per_tree_floats = sum_l roundup(n_l, 64).  Pads are never written.  Every sum of 64 is one wave's xor-butterfly (offsets
+ * 32, 16, 8, 4, 2, 1; pql_amd/csrc/per.hip's header writes the association out), so the upper levels after any sequence of
+ * calls are a pure function of the leaves: pqlk_per_rebuild of the same leaves gives the same bits.
+ * `pmax` is one device float beside the tree: the largest priority ever assigned, before ^alpha; the caller sets it to 1 once.
+ * x ^ e below means: e == 0 -> 1, e == 1 -> x, e == -1 -> 1.0f / x (one IEEE division), e == 0.5 -> sqrtf(x), else powf(x, e).
+ * Errors, before any launch: PQLK_E_NULL a NULL pointer; PQLK_E_SHAPE capacity <= 0, m <= 0, b <= 0 or n_valid <= 0;
+ * PQLK_E_RANGE dst_start < 0, dst_start + m > capacity or n_valid > capacity.  An index outside [0, capacity) in `idx` is
+ * skipped by the kernels (weight 0), never dereferenced.  No float atomic adds anywhere: results are bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t pqlk_per_levels(int64_t capacity);       /* 0 for capacity <= 0.  Host only: no GPU needed. */
+int64_t pqlk_per_tree_floats(int64_t capacity);  /* 0 for capacity <= 0.  Host only. */
+
+/* New rows enter with the largest priority seen so far (Schaul et al., algorithm 1 line 6: p_t = max_{i<t} p_i):
+ * leaf[r] = pmax ^ alpha for r in [dst_start, dst_start + m), pmax read on the device; then every ancestor of that range is
+ * recomputed, one launch per level.  One call per ring_plan segment, like pqlk_replay_insert. */
+int pqlk_per_insert(float* tree, int64_t capacity, const float* pmax, int64_t dst_start, int64_t m, float alpha,
+                    pqlk_stream_t stream);
+
+/* Every node of every upper level from its 64 children, bottom up (node j of level l + 1 = sum of level l's [64 j, 64 j + 64)). */
+int pqlk_per_rebuild(float* tree, int64_t capacity, pqlk_stream_t stream);
+
+/* Stratified proportional sampling (Schaul et al. 3.3 / appendix B.2.1: P(i) = p_i^alpha / sum_k p_k^alpha, one draw from each
+ * of b equal segments of the total mass).  u: b floats in [0, 1).  Sample k, one wave: seg = total / (float)b,
+ * t_k = ((float)k + u[k]) * seg; residual = t_k; from the top level down, lane j loads child j of the current node (at the top:
+ * node j of the top level), an inclusive prefix over the 64 lanes is formed (Hillis-Steele: for d = 1, 2, 4, 8, 16, 32,
+ * lane j >= d adds lane j - d's value of the previous round), the chosen child is the first with a non-zero sum whose inclusive
+ * prefix exceeds the residual, or, when rounding leaves none, the last child with a non-zero sum; the residual drops by the
+ * chosen child's exclusive prefix.  idx_out[k] (int64) = the leaf reached: never a row whose leaf is 0 while total > 0. */
+int pqlk_per_sample(const float* tree, int64_t capacity, const float* u, int64_t b, int64_t* idx_out, pqlk_stream_t stream);
+
+/* Importance weights (Schaul et al. 3.4: w_i = (N P(i))^-beta, normalised by the batch maximum where they are used):
+ * w_out[i] = (((float)n_valid * leaf[idx[i]]) / total) ^ (-beta); wmax_out[0] = max_i w_out[i], taken with an integer atomic
+ * max on the bit patterns of the non-negative floats (wmax_out is zeroed on the stream first).  beta == 0: exactly 1.0. */
+int pqlk_per_weights(const float* tree, int64_t capacity, const int64_t* idx, int64_t b, int64_t n_valid, float beta,
+                     float* w_out, float* wmax_out, pqlk_stream_t stream);
+
+/* pqlk_td_mse_loss with the per-sample weight wh_i = w[i] / wmax[0] (Schaul et al. algorithm 1 lines 10-12):
+ * loss = mean(wh (q1-y)^2) + mean(wh (q2-y)^2), dy = ((2/B) wh) (q-y), abs_td_out[i] = max(|q1-y|, |q2-y|) (the new priority,
+ * before eps and ^alpha).  Grid, partials, fold order and loss-ring semantics are pqlk_td_mse_loss's; with every w and wmax 1.0
+ * dy and the loss are its bits. */
+int pqlk_td_mse_loss_per(const float* q, const float* qt, int64_t ld, const float* rew, const float* done, float gamma_n,
+                         int64_t b, float* dy, float* loss_out, const int32_t* slot_dev, int32_t ring_len, float* scratch,
+                         const float* w, const float* wmax, float* abs_td_out, pqlk_stream_t stream);
+
+/* Priority write-back (Schaul et al. algorithm 1 line 11, proportional: p_i = |delta_i| + eps):
+ * leaf[idx[i]] = (abs_td[i] + eps) ^ alpha; pmax = max(pmax, max_i(abs_td[i] + eps)); then every touched ancestor is recomputed
+ * from its 64 children, one launch per level (recomputed redundantly, a node gets identical bits).  A row drawn more than once ends
+ * with the largest of its candidates whatever order the threads run in: the sampled leaves are cleared in one launch and raised
+ * with an integer atomic max on the bit pattern in the next.  abs_td >= 0. */
+int pqlk_per_update(float* tree, int64_t capacity, float* pmax, const int64_t* idx, const float* abs_td, int64_t b, float eps,
+                    float alpha, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser: clip_grad_norm_ + AdamW (+ Polyak) over flat arenas
  * (pql_v_learner.py:124-133, pql_p_learner.py:87-96, pql/utils/torch_util.py:9-12).
  *   g *= grad_scale   (1/world_size after a data-parallel sum all-reduce; 1.0 otherwise)

@@ -92,6 +92,14 @@ PROTOTYPES = {
     "pqlk_c51_bce_loss": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _F, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P]),
     "pqlk_c51_project": (C.c_int, [_P, _P, _P, _P, _F, _F, _F, _I32, _I64, _P, _P]),
     "pqlk_dpg_loss": (C.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _P, _I32, _P, _P]),
+    "pqlk_per_levels": (_I32, [_I64]),
+    "pqlk_per_tree_floats": (_I64, [_I64]),
+    "pqlk_per_insert": (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _P]),
+    "pqlk_per_rebuild": (C.c_int, [_P, _I64, _P]),
+    "pqlk_per_sample": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
+    "pqlk_per_weights": (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _P, _P, _P]),
+    "pqlk_td_mse_loss_per": (C.c_int, [_P, _P, _I64, _P, _P, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "pqlk_per_update": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _F, _F, _P]),
     "pqlk_clip_adamw_polyak": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pqlk_clip_adamw_polyak_pack": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pqlk_adamw_polyak_fused": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P,

@@ -15,7 +15,16 @@ from pql_amd import _lib as L
 from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, make_actor, make_critic
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
+from pql_amd.replay.prioritized_replay import per_cfg
 from pql_amd.replay.simple_replay import cfg_obs_dtype
+
+
+def per_beta(beta0, beta_iters, calls):
+    """The importance-sampling exponent of prioritized replay after `calls` calls of `update_net`: linear from beta0 to 1 over
+    `beta_iters` calls, exactly 1.0 from there on."""
+    if calls >= beta_iters:
+        return 1.0
+    return float(beta0) + (1.0 - float(beta0)) * (calls / float(beta_iters))
 
 
 class ActorCriticBase(PQLActor):
@@ -39,6 +48,8 @@ class ActorCriticBase(PQLActor):
         self.closs = torch.zeros(LOSS_RING, device=self.device)
         self.aloss = torch.zeros(LOSS_RING, device=self.device)
         self._ws = None
+        self.per = per_cfg(algo)   # algo.per when prioritized replay is on (None: every launch below is the plain one)
+        self.per_calls = 0         # calls of update_net so far: the position on the beta schedule (host side, saved)
 
     # ---- training state ----------------------------------------------------------------------------
     def _own_state(self):
@@ -58,9 +69,23 @@ class ActorCriticBase(PQLActor):
             out.update({f"{name}.m": opt.m, f"{name}.v": opt.v, f"{name}.step": opt.step})
         return out
 
+    def training_state(self):
+        st = super().training_state()
+        if self.per is not None:
+            st["per_calls"] = int(self.per_calls)
+        return st
+
+    def load_training_state(self, st, nstep=True):
+        super().load_training_state(st, nstep=nstep)
+        if self.per is not None:
+            self.per_calls = int(st.get("per_calls", 0))
+
     def explore_env(self, env, timesteps, random=False):
         _, cri_data, steps = super().explore_env(env, timesteps, random)
         return cri_data, steps
+
+    def beta(self):
+        return per_beta(self.per.beta0, int(self.per.beta_iters), self.per_calls) if self.per is not None else 1.0
 
     # ---- learning ----------------------------------------------------------------------------------
     def _own_tiles(self, ws, zeros, empty):
@@ -99,7 +124,15 @@ class ActorCriticBase(PQLActor):
         """Draw (or take) B replay indices and gather: [obs | action] -> x_sa, normalised next obs -> xn_sa / xn_obs, reward, done;
         obs_rms.normalize WITHOUT clamp.  x_obs (= norm(obs), the actor-step input) and x_pi's observation columns are copies."""
         B, O = ws["B"], self.obs_dim[0]
+        ws["per"] = memory if getattr(memory, "prioritized", False) else None
+        if ws["per"] is not None:   # the weights at this call's beta ride with the indices: drawn with them, or computed for injected ones
+            memory.beta = self.beta()
         idx = memory.draw_indices(B) if indices is None else indices.to(self.device, torch.int64).contiguous()
+        if ws["per"] is not None:
+            ws["w"], ws["wmax"] = (memory.w, memory.wmax) if indices is None else memory.weights_for(idx)
+            ws["idx"] = idx
+            if "abs_td" not in ws:
+                ws["abs_td"] = torch.zeros(B, dtype=torch.float32, device=self.device)
         mean = var = None
         eps = 0.0
         if self.cfg.algo.obs_norm:
@@ -157,9 +190,18 @@ class ActorCriticBase(PQLActor):
     def _td_mse_loss(self, ws, q, qt, ld):
         """Twin MSE against r + (1 - d) gamma^n min(qt): d loss / d q -> ws["dy"], the loss -> the critic's ring."""
         algo = self.cfg.algo
-        L.check(L.lib.pqlk_td_mse_loss(L.ptr(q), L.ptr(qt), ld, L.ptr(ws["rew"]), L.ptr(ws["done"]), float(algo.gamma) ** int(algo.nstep),
-                                       ws["B"], L.ptr(ws["dy"]), L.ptr(self.closs), L.ptr(self.copt.step), LOSS_RING,
-                                       L.ptr(ws["scratch"]), L.stream(self.device)))
+        memory = ws.get("per")
+        if memory is None:
+            L.check(L.lib.pqlk_td_mse_loss(L.ptr(q), L.ptr(qt), ld, L.ptr(ws["rew"]), L.ptr(ws["done"]), float(algo.gamma) ** int(algo.nstep),
+                                           ws["B"], L.ptr(ws["dy"]), L.ptr(self.closs), L.ptr(self.copt.step), LOSS_RING,
+                                           L.ptr(ws["scratch"]), L.stream(self.device)))
+            return
+        # prioritized replay: the importance weights on the loss and its gradient, then |TD| back into the tree
+        L.check(L.lib.pqlk_td_mse_loss_per(L.ptr(q), L.ptr(qt), ld, L.ptr(ws["rew"]), L.ptr(ws["done"]), float(algo.gamma) ** int(algo.nstep),
+                                           ws["B"], L.ptr(ws["dy"]), L.ptr(self.closs), L.ptr(self.copt.step), LOSS_RING,
+                                           L.ptr(ws["scratch"]), L.ptr(ws["w"]), L.ptr(ws["wmax"]), L.ptr(ws["abs_td"]),
+                                           L.stream(self.device)))
+        memory.update_priorities(ws["idx"], ws["abs_td"])
 
     def _dpg_loss(self, ws, q, ld):
         """-mean(min q): d loss / d q -> ws["dy"], the loss -> the actor's ring."""
@@ -192,6 +234,7 @@ class ActorCriticBase(PQLActor):
         n = int(self.cfg.algo.update_times)
         for _ in range(n):
             self.update_once(memory)
+        self.per_calls += 1
         c, a = self.closs.tolist(), self.aloss.tolist()
         k = min(n, LOSS_RING)
         return {"train/critic_loss": float(np.mean(c[:k])), "train/actor_loss": float(np.mean(a[:k])),

@@ -212,9 +212,14 @@ def pump(learner, stop_event=None, max_in_flight=2):
 
 
 def check_critic_class(cfg, fused_learner=None):
-    """Refusals that follow from `algo.cri_class` alone, raised before anything is allocated.  fused_learner: the name of a component
+    """Refusals that follow from `algo.cri_class` (and, for the fused learners, `algo.per.enabled`) alone, raised before anything is allocated.  fused_learner: the name of a component
     whose launch sequences are built on the fused MLP kernels (scripts/train_pql.py, PQLVLearner, PQLPLearner)."""
     algo = cfg.algo
+    per = _cfg_get(algo, "per")
+    if fused_learner is not None and per is not None and bool(per.get("enabled") or False):
+        raise ValueError(f"algo.per.enabled=True cannot run in {fused_learner}: the PQL learners gather batches ahead and replay steps as one "
+                         f"hipGraph, which assumes a sampling distribution that does not change between hand-offs; prioritized replay works "
+                         f"in scripts/train_baselines.py (algo=ddpg_algo / sac_algo / crossq_algo)")
     cri = str(_cfg_get(algo, "cri_class"))
     if cri.endswith("DoubleQLayerNorm"):
         if _cfg_get(algo, "distl", False):

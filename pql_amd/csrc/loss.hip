@@ -67,6 +67,52 @@ extern "C" int pqlk_td_mse_loss(const float* q, const float* qt, int64_t ld, con
   return PQLK_OK;
 }
 
+// k_td_mse with the importance weight wh = w[i] / wmax[0] of prioritized replay on each sample (and |TD| out, the new priority).
+// The same loop, grid, partials and fold as k_td_mse: with every w and wmax 1.0 the multiplications by wh change no bit.
+__global__ __launch_bounds__(256) void k_td_mse_per(const float* __restrict__ q, const float* __restrict__ qt, int64_t ld,
+                                                    const float* __restrict__ rew, const float* __restrict__ done,
+                                                    float gamma_n, int64_t b, float* __restrict__ dy, float* __restrict__ part,
+                                                    const float* __restrict__ w, const float* __restrict__ wmax,
+                                                    float* __restrict__ abs_td) {
+  const float two_over_b = 2.0f / (float)b;
+  const float wm = wmax[0];
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < b; i += (int64_t)gridDim.x * 256) {
+    const float t1 = qt[i * ld], t2 = qt[(b + i) * ld];
+    const float tq = fminf(t1, t2);
+    const float y = rew[i] + ((1.f - done[i]) * gamma_n) * tq;
+    const float d1 = q[i * ld] - y, d2 = q[(b + i) * ld] - y;
+    const float wh = w[i] / wm;
+    acc += wh * (d1 * d1 + d2 * d2);
+    const float g = two_over_b * wh;
+    dy[i * ld] = g * d1;
+    dy[(b + i) * ld] = g * d2;
+    abs_td[i] = fmaxf(fabsf(d1), fabsf(d2));
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+extern "C" int pqlk_td_mse_loss_per(const float* q, const float* qt, int64_t ld, const float* rew, const float* done,
+                                    float gamma_n, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                                    int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out,
+                                    pqlk_stream_t stream) {
+  PQLK_REQUIRE(q && qt && rew && done && dy && scratch && w && wmax && abs_td_out, PQLK_E_NULL);
+  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(ld >= 32 && ld % 32 == 0, PQLK_E_ALIGN);
+  int blocks = (int)((b + 255) / 256);
+  if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
+  hipLaunchKernelGGL(k_td_mse_per, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, qt, ld, rew, done, gamma_n, b, dy, scratch, w, wmax,
+                     abs_td_out);
+  PQLK_LAUNCH_CHECK();
+  if (!loss_out) return PQLK_OK;   // as pqlk_td_mse_loss: the partials stay in scratch
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks, 1.0f / (float)b, loss_out,
+                     slot_dev, (int)ring_len);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // C51.  One wave per batch row, lane k <-> atom k (K <= 64; more atoms: the k_*_wide kernels below).
 __device__ __forceinline__ float wave_softmax(float x, bool valid) {

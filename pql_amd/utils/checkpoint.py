@@ -229,6 +229,8 @@ def structure(cfg, obs_dim, act_dim):
     if cri.startswith("Distributional"):   # the V-learner rewrites cri_class when algo.distl is set
         cri = cri[len("Distributional"):]
     distl = bool(algo.get("distl") or False)
+    per = algo.get("per") or {}
+    per_on = bool(per.get("enabled") or False)
     return {"task.obs_dim": int(obs_dim), "task.act_dim": int(act_dim), "num_envs": int(cfg.num_envs),
             "algo.hidden_layers": None if hidden is None else [int(h) for h in hidden],
             "algo.act_class": str(algo.get("act_class")), "algo.cri_class": cri, "algo.distl": distl,
@@ -236,11 +238,14 @@ def structure(cfg, obs_dim, act_dim):
             "algo.memory_size": int(algo.get("memory_size") or 0),
             "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32"),
             # (the V-learner's target forwards: bf16 targets change every later step, so a run resumes in the dtype it was saved in)
-            "algo.target_dtype": str(algo.get("target_dtype") or "float32")}
+            "algo.target_dtype": str(algo.get("target_dtype") or "float32"),
+            # (prioritized replay: the ring carries a sum tree of priority^alpha; alpha counts only when it is on)
+            "algo.per.enabled": per_on, "algo.per.alpha": float(per.get("alpha")) if per_on else None}
 
 
 def check_structure(saved, current, has_rings=True):
-    saved = {"algo.target_dtype": "float32", **saved}   # (a checkpoint from before the key existed was written with float32 targets)
+    # (a checkpoint from before a key existed was written with float32 targets and uniform replay)
+    saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, **saved}
     for key, want in saved.items():
         if key in ("algo.memory_size", "algo.replay_obs_dtype") and not has_rings:
             continue

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Single-process baseline loop -- same shape as the reference's scripts/train_baselines.py:39-72.
 Off-policy (DDPG, SAC, CrossQ: `algo=ddpg_algo` / `sac_algo` / `crossq_algo`): warm-up rollout -> replay, then per iteration:
-rollout, insert, `agent.update_net(memory)`.  On-policy (PPO: `algo=ppo_algo`): per iteration rollout, `agent.update_net(trajectory)`.
+rollout, insert, `agent.update_net(memory)`; `algo.per.enabled=True` makes the replay prioritized (a device sum tree beside the ring).
+On-policy (PPO: `algo=ppo_algo`): per iteration rollout, `agent.update_net(trajectory)`.
     python scripts/train_baselines.py algo=ddpg_algo task.name=Toy num_envs=64 algo.batch_size=256 algo.memory_size=100000 max_step=20000
     python scripts/train_baselines.py algo=ppo_algo task.name=Toy num_envs=64 max_step=20000
 """
@@ -14,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from pql_amd.algo import alg_name_to_path  # noqa: E402
 from pql_amd.envs.synthetic import create_task_env  # noqa: E402
+from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer, per_cfg  # noqa: E402
 from pql_amd.replay.simple_replay import ReplayBuffer  # noqa: E402
 from pql_amd.utils import checkpoint as CK  # noqa: E402
 from pql_amd.utils.cfg import load_cfg  # noqa: E402
@@ -73,9 +75,12 @@ def main(cfg, on_finish=None):
     start, global_steps, start_iter, resumed_from = time.time(), 0, 0, None
     agent.reset_agent()
     is_off_policy = cfg.algo.name != "PPO"
+    per = None
     if is_off_policy:
-        memory = ReplayBuffer(capacity=int(cfg.algo.memory_size), obs_dim=agent.obs_dim, action_dim=agent.action_dim, device=cfg.device,
-                              obs_dtype=agent.replay_obs_dtype)
+        ring = dict(capacity=int(cfg.algo.memory_size), obs_dim=agent.obs_dim, action_dim=agent.action_dim, device=cfg.device,
+                    obs_dtype=agent.replay_obs_dtype)
+        per = per_cfg(cfg.algo)   # algo.per.enabled=True: priorities on a device sum tree beside the ring
+        memory = ReplayBuffer(**ring) if per is None else PrioritizedReplayBuffer(alpha=float(per.alpha), eps=float(per.eps), **ring)
         saved = None
         if opt["resume"] is not None:
             ckpt, saved = load_checkpoint(opt, cfg, env, agent, memory)
@@ -115,6 +120,8 @@ def main(cfg, on_finish=None):
         torch.cuda.synchronize(agent.device)
         result.update(actor_sha=CK.sha(agent.actor.arena.data), critic_sha=CK.sha(agent.critic.arena.data),
                       replay_sha=CK.sha_stream(memory.rows()), resumed_from=resumed_from)
+        if per is not None:   # the priorities the run ends with
+            result.update(per_sha=CK.sha(memory.leaves), per_pmax=float(memory.pmax))
     return result
 
 
