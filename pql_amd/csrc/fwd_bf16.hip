@@ -219,15 +219,6 @@ __global__ __launch_bounds__(256) void k_pack_bf16(PackBf16P p) {
   }
 }
 
-static int bf_desc_ok(const PqlMlpDesc* d) {
-  if (!d) return PQLK_E_NULL;
-  if (d->n_layers < 1 || d->n_layers > PQLK_MAX_LAYERS) return PQLK_E_SHAPE;
-  if (d->n_nets < 1 || d->n_nets > 2) return PQLK_E_UNSUPPORTED;
-  for (int i = 0; i <= d->n_layers; ++i)
-    if (d->dims[i] <= 0) return PQLK_E_SHAPE;
-  return PQLK_OK;
-}
-
 // LDS row length in bf16 elements: the widest layer input (K padded to 16) plus the padding
 static int bf_lds_ld(const PqlMlpDesc* d) {
   int w = 0;
@@ -237,7 +228,7 @@ static int bf_lds_ld(const PqlMlpDesc* d) {
 static size_t bf_lds_bytes(const PqlMlpDesc* d, int mt) { return (size_t)2 * 32 * mt * bf_lds_ld(d) * sizeof(uint16_t); }
 
 static bool bf_ok(const PqlMlpDesc* d) {
-  if (bf_desc_ok(d) != PQLK_OK || d->n_layers < 2) return false;
+  if (desc_ok(d) != PQLK_OK || d->n_layers < 2) return false;
   for (int l = 1; l < d->n_layers; ++l)
     if (d->dims[l] % 32 != 0 || d->dims[l] > 1024) return false;
   if (d->dims[d->n_layers] > 64) return false;
@@ -258,7 +249,7 @@ extern "C" int pqlk_mlp_bf16_ok(const PqlMlpDesc* d) { return bf_ok(d) ? 1 : 0; 
 extern "C" int64_t pqlk_mlp_packed_bf16_elems(const PqlMlpDesc* d) { return bf_ok(d) ? bf_net_elems(d) * d->n_nets : 0; }
 
 extern "C" int pqlk_mlp_pack_bf16(const PqlMlpDesc* d, const float* params, uint16_t* packed, pqlk_stream_t stream) {
-  int rc = bf_desc_ok(d);
+  int rc = desc_ok(d);
   if (rc) return rc;
   PQLK_REQUIRE(params && packed, PQLK_E_NULL);
   PQLK_REQUIRE(pqlk_aligned16(params) && pqlk_aligned16(packed), PQLK_E_ALIGN);
@@ -284,7 +275,7 @@ extern "C" int pqlk_mlp_pack_bf16(const PqlMlpDesc* d, const float* params, uint
 extern "C" int pqlk_mlp_forward_bf16(const PqlMlpDesc* d, const float* params, const uint16_t* packed, const float* x, int64_t ldx,
                                      int64_t b, int32_t out_act, const float* draw, float noise_std, float noise_clip, float* out,
                                      float* out2, int64_t ld_out2, pqlk_stream_t stream) {
-  int rc = bf_desc_ok(d);
+  int rc = desc_ok(d);
   if (rc) return rc;
   PQLK_REQUIRE(params && packed && x && out, PQLK_E_NULL);
   PQLK_REQUIRE(b > 0 && b < (1LL << 30), PQLK_E_SHAPE);

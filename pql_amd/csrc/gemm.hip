@@ -855,72 +855,85 @@ static int launch_auto(const GemmP& p, int gz, hipStream_t st) {
 }
 
 // ================================================================================================
-// descriptor helpers
-static int desc_ok(const PqlMlpDesc* d) {
-  if (!d) return PQLK_E_NULL;
-  if (d->n_layers < 1 || d->n_layers > PQLK_MAX_LAYERS) return PQLK_E_SHAPE;
-  if (d->n_nets < 1 || d->n_nets > 2) return PQLK_E_UNSUPPORTED;
-  for (int i = 0; i <= d->n_layers; ++i)
-    if (d->dims[i] <= 0) return PQLK_E_SHAPE;
-  return PQLK_OK;
+// geometry: the one definition of the parameter arena and the activation stash of (d, b), built once per call
+//   arena: n_nets blocks of net_stride floats; layer l of a net is W (dims[l + 1], ld[l]) at w_off[l], then b (ld[l + 1]) at b_off[l]
+//   stash: layer l's output is (n_nets, b, ld[l + 1]) at a_off[l]
+struct MlpGeom {
+  const PqlMlpDesc* d; int64_t b;
+  int L, n_nets;
+  int64_t ld[PQLK_MAX_LAYERS + 1];   // pqlk_ld(dims[l]): layer l reads rows of ld[l] floats (ld_in) and writes rows of ld[l + 1] (ld_out)
+  int64_t w_off[PQLK_MAX_LAYERS], b_off[PQLK_MAX_LAYERS], a_off[PQLK_MAX_LAYERS];
+  int64_t net_stride, arena, acts_floats, max_hidden_ld;
+  int64_t head_floats;               // the last layer's W and b of one net: what a head partial holds
+};
+
+static MlpGeom mlp_geom(const PqlMlpDesc* d, int64_t b) {   // d has passed desc_ok
+  MlpGeom g = {};
+  g.d = d; g.b = b; g.L = d->n_layers; g.n_nets = d->n_nets;
+  for (int l = 0; l <= g.L; ++l) g.ld[l] = pqlk_ld(d->dims[l]);
+  for (int l = 0; l < g.L; ++l) {
+    g.w_off[l] = g.net_stride; g.b_off[l] = g.w_off[l] + (int64_t)d->dims[l + 1] * g.ld[l];
+    g.net_stride = g.b_off[l] + g.ld[l + 1];
+    g.a_off[l] = g.acts_floats; g.acts_floats += (int64_t)g.n_nets * b * g.ld[l + 1];
+    g.max_hidden_ld = g.ld[l + 1] > g.max_hidden_ld ? g.ld[l + 1] : g.max_hidden_ld;
+  }
+  g.arena = g.net_stride * g.n_nets; g.head_floats = g.net_stride - g.w_off[g.L - 1];
+  return g;
 }
 
-extern "C" int64_t pqlk_mlp_net_stride(const PqlMlpDesc* d) {
-  if (desc_ok(d)) return 0;
-  int64_t n = 0;
-  for (int l = 0; l < d->n_layers; ++l) n += (int64_t)d->dims[l + 1] * pqlk_ld(d->dims[l]) + pqlk_ld(d->dims[l + 1]);
-  return n;
-}
-extern "C" int64_t pqlk_mlp_param_floats(const PqlMlpDesc* d) { return pqlk_mlp_net_stride(d) * (d ? d->n_nets : 0); }
+extern "C" int64_t pqlk_mlp_net_stride(const PqlMlpDesc* d) { return desc_ok(d) ? 0 : mlp_geom(d, 0).net_stride; }
+extern "C" int64_t pqlk_mlp_param_floats(const PqlMlpDesc* d) { return desc_ok(d) ? 0 : mlp_geom(d, 0).arena; }
 
 extern "C" int pqlk_mlp_layer_offsets(const PqlMlpDesc* d, int32_t layer, int64_t* w_off, int64_t* b_off) {
   int rc = desc_ok(d);
   if (rc) return rc;
   PQLK_REQUIRE(layer >= 0 && layer < d->n_layers, PQLK_E_RANGE);
-  int64_t n = 0;
-  for (int l = 0; l < layer; ++l) n += (int64_t)d->dims[l + 1] * pqlk_ld(d->dims[l]) + pqlk_ld(d->dims[l + 1]);
-  if (w_off) *w_off = n;
-  if (b_off) *b_off = n + (int64_t)d->dims[layer + 1] * pqlk_ld(d->dims[layer]);
+  const MlpGeom g = mlp_geom(d, 0);
+  if (w_off) *w_off = g.w_off[layer];
+  if (b_off) *b_off = g.b_off[layer];
   return PQLK_OK;
 }
 
-extern "C" int64_t pqlk_mlp_acts_floats(const PqlMlpDesc* d, int64_t b) {
-  if (desc_ok(d) || b <= 0) return 0;
-  int64_t n = 0;
-  for (int l = 0; l < d->n_layers; ++l) n += (int64_t)d->n_nets * b * pqlk_ld(d->dims[l + 1]);
-  return n;
-}
+extern "C" int64_t pqlk_mlp_acts_floats(const PqlMlpDesc* d, int64_t b) { return desc_ok(d) || b <= 0 ? 0 : mlp_geom(d, b).acts_floats; }
 
 extern "C" int pqlk_mlp_act_offset(const PqlMlpDesc* d, int64_t b, int32_t net, int32_t layer, int64_t* off, int64_t* ld) {
   int rc = desc_ok(d);
   if (rc) return rc;
   PQLK_REQUIRE(layer >= 0 && layer < d->n_layers && net >= 0 && net < d->n_nets && b > 0, PQLK_E_RANGE);
-  int64_t n = 0;
-  for (int l = 0; l < layer; ++l) n += (int64_t)d->n_nets * b * pqlk_ld(d->dims[l + 1]);
-  n += (int64_t)net * b * pqlk_ld(d->dims[layer + 1]);
-  if (off) *off = n;
-  if (ld) *ld = pqlk_ld(d->dims[layer + 1]);
+  const MlpGeom g = mlp_geom(d, b);
+  if (off) *off = g.a_off[layer] + (int64_t)net * b * g.ld[layer + 1];
+  if (ld) *ld = g.ld[layer + 1];
   return PQLK_OK;
 }
 
-static int64_t max_hidden_ld(const PqlMlpDesc* d) {
-  int64_t m = 0;
-  for (int l = 1; l <= d->n_layers; ++l) m = pqlk_ld(d->dims[l]) > m ? pqlk_ld(d->dims[l]) : m;
-  return m;
+// ---- the two workspace formats: every pointer into a workspace and every size check comes from these -----------------------------
+// compact DPG workspace (minnet.h), in floats: [dz0 | dz1 | perm (rows_cap ints) | mn (64 ints) | tie0 (rows_cap ints)]
+struct CompactWs { int64_t rows_cap, dz[2], perm, mn, tie0, total; };
+static CompactWs compact_ws(int64_t max_hidden_ld, int64_t b) {
+  CompactWs w = {};
+  w.rows_cap = 2 * pqlk_round_up(b, MN_TILE);   // every sample a tie: both runs full
+  w.dz[1] = w.rows_cap * max_hidden_ld; w.perm = 2 * w.dz[1]; w.mn = w.perm + w.rows_cap; w.tie0 = w.mn + 64;
+  w.total = w.tie0 + w.rows_cap;
+  return w;
 }
 
-static int64_t head_part_floats(const PqlMlpDesc* d, int64_t b) {   // room for k_skinny_bwd's per-block partials
-  const int L = d->n_layers;
-  const int64_t hf = (int64_t)d->dims[L] * pqlk_ld(d->dims[L - 1]) + pqlk_ld(d->dims[L]);
-  // k_skinny_bwd's blocks; the fused forward's TD head leaves one per row tile of 32 or 64; the DPG slice kernel (k_dx_slice<D, QPW>)
-  // one per 32-row tile of the compact layout (2 x b rounded up to 128 rows)
-  const int64_t skinny = skinny_bwd_blocks(b, d->n_nets), tiles = 2 * pqlk_round_up(b, 128) / 32;
-  return (skinny > tiles ? skinny : tiles) * d->n_nets * hf;
+// backward workspace, in floats: [dZ0 | dZ1 | splits x arena slabs | head partials].  splits = 0 is a call without `grads`: it needs
+// neither slabs nor head partials
+struct BwdWs { int64_t dz[2], slabs, head_part, head_part_floats, total; };
+static BwdWs bwd_ws(const MlpGeom& g, int splits) {
+  BwdWs w = {};
+  w.dz[1] = (int64_t)g.n_nets * g.b * g.max_hidden_ld; w.slabs = 2 * w.dz[1]; w.head_part = w.slabs + (int64_t)splits * g.arena;
+  // room for k_skinny_bwd's per-block partials: k_skinny_bwd's blocks; the fused forward's TD head leaves one per row tile of 32 or
+  // 64; the DPG slice kernel (k_dx_slice<D, QPW>) one per 32-row tile of the compact layout (2 x b rounded up to 128 rows)
+  const int64_t skinny = skinny_bwd_blocks(g.b, g.n_nets), tiles = compact_ws(0, g.b).rows_cap / 32;
+  w.head_part_floats = (skinny > tiles ? skinny : tiles) * g.n_nets * g.head_floats;
+  w.total = w.head_part + (splits ? w.head_part_floats : 0);
+  return w;
 }
 
 extern "C" int64_t pqlk_mlp_bwd_ws_floats(const PqlMlpDesc* d, int64_t b, int32_t splits) {
   if (desc_ok(d) || b <= 0 || splits < 1) return 0;
-  return 2 * (int64_t)d->n_nets * b * max_hidden_ld(d) + (int64_t)splits * pqlk_mlp_param_floats(d) + head_part_floats(d, b);
+  return bwd_ws(mlp_geom(d, b), splits).total;
 }
 
 // ================================================================================================
@@ -962,14 +975,12 @@ extern "C" int pqlk_mlp_pack(const PqlMlpDesc* d, const float* params, float* pa
   if (rc) return rc;
   PQLK_REQUIRE(params && packed, PQLK_E_NULL);
   PQLK_REQUIRE(fusable(d, nullptr), PQLK_E_UNSUPPORTED);
-  const int64_t net_stride = pqlk_mlp_net_stride(d), pstride = packed_net_stride(d);
+  const MlpGeom g = mlp_geom(d, 0);
   PackP pp = {};
   int64_t p_off = 0, most = 0;
   for (int l = 0; l + 1 < d->n_layers; ++l) {
-    int64_t w_off, b_off;
-    pqlk_mlp_layer_offsets(d, l, &w_off, &b_off);
-    pp.w_off[l] = w_off; pp.p_off[l] = p_off;
-    pp.N[l] = d->dims[l + 1]; pp.K[l] = (int)pqlk_ld(d->dims[l]);
+    pp.w_off[l] = g.w_off[l]; pp.p_off[l] = p_off;
+    pp.N[l] = d->dims[l + 1]; pp.K[l] = (int)g.ld[l];
     const int64_t elems = (int64_t)pp.N[l] * pp.K[l];
     if (elems > most) most = elems;
     p_off += elems;
@@ -978,7 +989,7 @@ extern "C" int pqlk_mlp_pack(const PqlMlpDesc* d, const float* params, float* pa
   int blocks = (int)((most + 255) / 256);   // sized for the largest layer; the kernel's loop is grid-strided
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(k_mlp_pack, dim3(blocks, d->n_nets, pp.n_layers), dim3(256), 0, pqlk_s(stream), params, packed, pp,
-                     (long long)net_stride, (long long)pstride);
+                     (long long)g.net_stride, (long long)packed_net_stride(d));
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }
@@ -1000,6 +1011,14 @@ struct FusedHead {   // output layer to run inside the fused launch (n = 0: none
 static bool head_fusable(const PqlMlpDesc* d) {
   return d->n_layers >= 2 && d->dims[d->n_layers] <= 32 && d->dims[d->n_layers - 1] % 32 == 0;
 }
+static bool fused_head_enabled() {   // PQLK_NO_FUSED_HEAD: tuning / A-B switch, read once per process
+  static const bool off = getenv("PQLK_NO_FUSED_HEAD") != nullptr;
+  return !off;
+}
+// the hidden stack AND the output layer in one launch
+static bool fused_with_head(const PqlMlpDesc* d, int* buf_ld_out = nullptr) {
+  return fusable(d, buf_ld_out) && head_fusable(d) && fused_head_enabled();
+}
 
 // rows per block of the fused forward, in tiles of 32: 2 (64 rows) when no hidden layer is wider than 512 (two output tiles per
 // wave, 132 KB of LDS) and the halved grid still fills the 256 CUs about as well -- cost model: rounds x rows per block, 32-row
@@ -1019,31 +1038,27 @@ static int fused_rows(const PqlMlpDesc* d, int buf_ld, int64_t b) {
   return R;
 }
 
-static int launch_fused_hidden(const PqlMlpDesc* d, const float* params, const float* packed, const float* x, int64_t ldx,
-                               int64_t b, float* acts, int stash_all, hipStream_t st, const FusedHead* head = nullptr,
-                               bool out_only = false) {
+static int launch_fused_hidden(const MlpGeom& g, const float* params, const float* packed, const float* x, int64_t ldx, float* acts,
+                               int stash_all, hipStream_t st, const FusedHead* head = nullptr, bool out_only = false) {
+  const PqlMlpDesc* d = g.d;
+  const int64_t b = g.b;
   FusedP p = {};
   int buf_ld = 0;
   if (!fusable(d, &buf_ld)) return PQLK_E_UNSUPPORTED;
   p.X = x; p.params = params; p.packed = packed; p.acts = acts;
   p.B = (int)b; p.ldx = (int)ldx; p.n_hidden = d->n_layers - 1; p.stash_all = stash_all; p.buf_ld = buf_ld; p.n_nets = d->n_nets;
-  p.net_stride = pqlk_mlp_net_stride(d); p.packed_net_stride = packed_net_stride(d);
+  p.net_stride = g.net_stride; p.packed_net_stride = packed_net_stride(d);
   int64_t p_off = 0;
   for (int l = 0; l <= d->n_layers; ++l) p.dims[l] = d->dims[l];
   for (int l = 0; l + 1 < d->n_layers; ++l) {
-    int64_t w_off, b_off, a_off, a_ld;
-    pqlk_mlp_layer_offsets(d, l, &w_off, &b_off);
-    pqlk_mlp_act_offset(d, b, 0, l, &a_off, &a_ld);
-    p.b_off[l] = b_off; p.p_off[l] = p_off; p.a_off[l] = a_off;
-    p_off += (int64_t)d->dims[l + 1] * pqlk_ld(d->dims[l]);
+    p.b_off[l] = g.b_off[l]; p.p_off[l] = p_off; p.a_off[l] = g.a_off[l];
+    p_off += (int64_t)d->dims[l + 1] * g.ld[l];
   }
   if (head && head->n > 0) {
     const int L = d->n_layers;
-    int64_t w_off, b_off, a_off, a_ld;
-    pqlk_mlp_layer_offsets(d, L - 1, &w_off, &b_off);
-    pqlk_mlp_act_offset(d, b, 0, L - 1, &a_off, &a_ld);
-    p.head_n = head->n; p.head_epi = head->epi; p.head_ld = (int)a_ld; p.ld_out2 = (int)head->ld_out2;
-    p.head_w_off = w_off; p.head_b_off = b_off; p.head_a_off = out_only ? 0 : a_off;   // out_only: `acts` IS the output block
+    p.head_n = head->n; p.head_epi = head->epi; p.head_ld = (int)g.ld[L]; p.ld_out2 = (int)head->ld_out2;
+    p.head_w_off = g.w_off[L - 1]; p.head_b_off = g.b_off[L - 1];
+    p.head_a_off = out_only ? 0 : g.a_off[L - 1];   // out_only: `acts` IS the output block
     p.draw = head->draw; p.out2 = head->out2; p.noise_std = head->noise_std; p.noise_clip = head->noise_clip;
     p.qc = head->n == 1 ? head->qc : nullptr;
     p.X2 = head->x2; p.ldx2 = (int)head->ldx2; p.x2_col0 = head->x2_col0;
@@ -1051,7 +1066,7 @@ static int launch_fused_hidden(const PqlMlpDesc* d, const float* params, const f
       p.td_qt = head->td_qt; p.td_rew = head->td_rew; p.td_done = head->td_done; p.td_gamma_n = head->td_gamma_n;
       p.td_two_over_b = 2.0f / (float)b;
       p.td_dz = head->td_dz; p.td_head_part = head->td_head_part; p.td_loss_part = head->td_loss_part;
-      p.td_part_floats = p.net_stride - w_off;
+      p.td_part_floats = g.head_floats;
     }
   }
   bool wide = false;
@@ -1095,40 +1110,35 @@ extern "C" int pqlk_mlp_forward(const PqlMlpDesc* d, const float* params, const 
   if (out_act == PQLK_ACT_TANH_NOISE) PQLK_REQUIRE(draw, PQLK_E_NULL);
   if (out2) PQLK_REQUIRE(d->n_nets == 1 && ld_out2 >= d->dims[d->n_layers], PQLK_E_SHAPE);
   PQLK_REQUIRE(stash_all >= 0 && stash_all <= PQLK_STASH_OUTPUT_ONLY, PQLK_E_RANGE);
-  const int64_t net_stride = pqlk_mlp_net_stride(d);
+  const MlpGeom g = mlp_geom(d, b);
   const int L = d->n_layers;
   int l_first = 0;
-  static const bool no_head = getenv("PQLK_NO_FUSED_HEAD") != nullptr;   // tuning / A-B switch
   const bool out_only = stash_all == PQLK_STASH_OUTPUT_ONLY;   // `acts` = the output block alone: fused stack + fused head only
-  if (out_only) PQLK_REQUIRE(packed && fusable(d, nullptr) && head_fusable(d) && !no_head, PQLK_E_UNSUPPORTED);
+  if (out_only) PQLK_REQUIRE(packed && fused_with_head(d), PQLK_E_UNSUPPORTED);
   if (packed && fusable(d, nullptr)) {  // all hidden layers in one launch, activations resident in LDS
     PQLK_REQUIRE(pqlk_aligned16(packed), PQLK_E_ALIGN);
     FusedHead head = {};
-    if (head_fusable(d) && !no_head) {   // ... and the output layer too
+    if (head_fusable(d) && fused_head_enabled()) {   // ... and the output layer too
       head.n = d->dims[L]; head.epi = out_act; head.draw = draw; head.noise_std = noise_std; head.noise_clip = noise_clip;
       head.out2 = out2; head.ld_out2 = ld_out2;
     }
-    rc = launch_fused_hidden(d, params, packed, x, ldx, b, acts, stash_all == 1 ? 1 : 0, pqlk_s(stream), &head, out_only);
+    rc = launch_fused_hidden(g, params, packed, x, ldx, acts, stash_all == 1 ? 1 : 0, pqlk_s(stream), &head, out_only);
     if (rc) return rc;
     l_first = head.n > 0 ? L : L - 1;
   }
   for (int l = l_first; l < L; ++l) {
-    int64_t w_off, b_off, a_off, a_ld;
-    pqlk_mlp_layer_offsets(d, l, &w_off, &b_off);
-    pqlk_mlp_act_offset(d, b, 0, l, &a_off, &a_ld);
+    const int64_t ld_in = g.ld[l], ld_out = g.ld[l + 1];
     GemmP p = {};
     if (l == 0) {
       p.A = x; p.lda = (int)ldx; p.sA = 0;
     } else {
-      int64_t i_off, i_ld;
-      pqlk_mlp_act_offset(d, b, 0, l - 1, &i_off, &i_ld);
-      p.A = acts + i_off; p.lda = (int)i_ld; p.sA = b * i_ld;
+      p.A = acts + g.a_off[l - 1]; p.lda = (int)ld_in; p.sA = b * ld_in;
     }
-    p.B = params + w_off; p.ldb = (int)pqlk_ld(d->dims[l]); p.sB = net_stride;
-    p.bias = params + b_off; p.sBias = net_stride;
-    p.C = acts + a_off; p.ldc = (int)a_ld; p.sC = b * a_ld;
-    p.M = (int)b; p.N = d->dims[l + 1]; p.K = (int)pqlk_ld(d->dims[l]);
-    p.ncols_store = (int)a_ld;
+    p.B = params + g.w_off[l]; p.ldb = (int)ld_in; p.sB = g.net_stride;
+    p.bias = params + g.b_off[l]; p.sBias = g.net_stride;
+    p.C = acts + g.a_off[l]; p.ldc = (int)ld_out; p.sC = b * ld_out;
+    p.M = (int)b; p.N = d->dims[l + 1]; p.K = (int)ld_in;
+    p.ncols_store = (int)ld_out;
     p.groups = d->n_nets;
     p.epi = EPI_ELU;
     if (l == L - 1) {
@@ -1223,14 +1233,16 @@ __global__ __launch_bounds__(256) void k_reduce_slabs(ReduceP p) {
   }
 }
 
-static int64_t head_quads(const PqlMlpDesc* d) {
-  const int L = d->n_layers;
-  return ((int64_t)d->dims[L] * pqlk_ld(d->dims[L - 1]) + pqlk_ld(d->dims[L])) / 4 * d->n_nets;
+// The output layer's backward takes one of three kernels; decided HERE and nowhere else (pqlk_mlp_norm_parts, the TD entry points
+// and the DPG predicates read it through head_is_fused)
+enum HeadBwd { HEAD_GEMM, HEAD_SKINNY, HEAD_FUSED };   // k_gemm dW + dX | k_skinny_dw + k_skinny_dx | k_skinny_bwd (with grads only)
+static HeadBwd head_bwd_kind(const PqlMlpDesc* d) {
+  const int L = d->n_layers, N = d->dims[L], K = (int)pqlk_ld(d->dims[L - 1]);
+  if (!skinny_bwd_ok(N, K)) return HEAD_GEMM;
+  return L >= 2 && skinny_bwd_fused_ok(N, K) ? HEAD_FUSED : HEAD_SKINNY;
 }
-static bool head_is_fused(const PqlMlpDesc* d) {   // must mirror the choice in mlp_backward_impl
-  const int L = d->n_layers;
-  return L >= 2 && skinny_bwd_ok(d->dims[L], (int)pqlk_ld(d->dims[L - 1])) && skinny_bwd_fused_ok(d->dims[L], (int)pqlk_ld(d->dims[L - 1]));
-}
+static bool head_is_fused(const PqlMlpDesc* d) { return head_bwd_kind(d) == HEAD_FUSED; }
+static int head_fold_blocks(const MlpGeom& g) { return (int)((g.head_floats / 4 * g.n_nets + 3) / 4); }   // one wave per quad
 static int reduce_main_blocks(int64_t arena, bool for_norm) {
   int64_t blocks = (arena / 4 + 255) / 256;
   if (blocks < 1) blocks = 1;
@@ -1241,173 +1253,197 @@ static int reduce_main_blocks(int64_t arena, bool for_norm) {
 // number of squared-norm partials pqlk_mlp_backward_norm leaves for pqlk_adamw_polyak_fused(prenorm = this)
 extern "C" int32_t pqlk_mlp_norm_parts(const PqlMlpDesc* d) {
   if (desc_ok(d)) return 0;
-  const int main_blocks = reduce_main_blocks(pqlk_mlp_param_floats(d), true);
-  return main_blocks + (head_is_fused(d) ? (int)((head_quads(d) + 3) / 4) : 0);
+  const MlpGeom g = mlp_geom(d, 0);
+  return reduce_main_blocks(g.arena, true) + (head_is_fused(d) ? head_fold_blocks(g) : 0);
 }
 
 struct TdHead {   // the scalar twin-Q head forms dL/dQ itself (pqlk_mlp_backward_td)
   const float* qt; const float* rew; const float* done; float gamma_n; float* loss_part;
 };
 
-static int mlp_backward_impl(const PqlMlpDesc* d, const float* params, const float* x, int64_t ldx, int64_t b,
-                             const float* acts, const float* dy, float* grads, int32_t splits, float* dx,
-                             int64_t ld_dx, int32_t dx_col0, int32_t dx_cols, const float* dx_tanh_of,
-                             int64_t ld_tanh, float* ws, int64_t ws_floats, float* sq_part, int32_t* step_dev,
-                             pqlk_stream_t stream, const TdHead* td = nullptr, int l_hi = -1, int l_lo = 0, int head_done = 0,
-                             const int* head_parts_dev = nullptr) {
-  // head_done > 0: the last layer's backward already ran inside the fused forward (pqlk_mlp_forward_td): dL/dZ of the last hidden
-  // layer sits in the first dZ buffer and `head_done` row-tile partials of the head's dW / db in the partial area
-  // l_hi >= 0: only layers l_hi >= l >= l_lo of the chain (dW_l, dX_l) and the slab reduction of exactly those layers (the
+// One backward call.  Filled field by field; a mode that is not in use stays zero.
+struct BwdCall {
+  const PqlMlpDesc* d; const float* params; const float* x; int64_t ldx, b; const float* acts;
+  const float* dy;             // dL/dZ of the last layer; not read with td, head_done or a layer range below the last layer
+  float* grads; int splits;    // parameter gradient through `splits` slabs of the workspace
+  float* dx; int64_t ld_dx;    // input gradient, summed over nets ...
+  int dx_col0, dx_cols; const float* dx_tanh_of; int64_t ld_tanh;   // ... or columns [dx_col0, dx_col0 + dx_cols) of it through tanh'
+  float* ws; int64_t ws_floats;
+  float* sq_part; int32_t* step_dev;   // squared-norm partials and the step increment out of the reduction (pqlk_mlp_backward_norm)
+  pqlk_stream_t stream;
+  const TdHead* td;            // TD head: the fused head kernel forms dL/dQ itself
+  // layer range: only layers l_hi >= l >= l_lo of the chain (dW_l, dX_l) and the slab reduction of exactly those layers (the
   // data-parallel buckets of pqlk_mlp_backward_layers); calls must walk the layers downwards over the same workspace
+  bool ranged; int l_hi, l_lo;
+  // head_done > 0: the last layer's backward already ran elsewhere (pqlk_mlp_forward_td, pqlk_dpg_backward_fused): dL/dZ of the last
+  // hidden layer sits in the first dZ buffer and `head_done` row-tile partials of the head's dW / db in the partial area, of which
+  // only the first (head_parts_dev[3] + 31) / 32 exist when head_parts_dev is given
+  int head_done; const int* head_parts_dev;
+};
+
+static BwdCall bwd_call(const PqlMlpDesc* d, const float* params, const float* x, int64_t ldx, int64_t b, const float* acts,
+                        float* grads, int32_t splits, float* ws, int64_t ws_floats, pqlk_stream_t stream) {
+  BwdCall c = {};
+  c.d = d; c.params = params; c.x = x; c.ldx = ldx; c.b = b; c.acts = acts;
+  c.grads = grads; c.splits = splits; c.ws = ws; c.ws_floats = ws_floats; c.stream = stream;
+  return c;
+}
+
+struct BwdRun {   // what the steps of one call share
+  const BwdCall& c; MlpGeom g; int splits;
+  float* dact[2]; float* slabs; float* head_part;
+  hipStream_t st;
+};
+struct LayerIO {   // layer l reads dL/dZ_l from where layer l + 1 left it and writes dL/dZ_{l-1} into the other buffer
+  const float* dy;                                     // (n_nets, b, ld_out)
+  const float* in; int64_t in_ld, in_stride;           // the layer's input: x or the stash
+  float* dz;
+};
+static LayerIO bwd_layer_io(const BwdRun& r, int l) {
+  const int L = r.g.L;
+  LayerIO io = {};
+  io.dy = l == L - 1 ? r.c.dy : r.dact[(L - 2 - l) & 1];
+  io.dz = r.dact[(L - 1 - l) & 1];
+  if (l == 0) {
+    io.in = r.c.x; io.in_ld = r.c.ldx; io.in_stride = 0;
+  } else {
+    io.in = r.c.acts + r.g.a_off[l - 1]; io.in_ld = r.g.ld[l]; io.in_stride = r.c.b * r.g.ld[l];
+  }
+  return io;
+}
+
+static int bwd_layer_dw(const BwdRun& r, int l, const LayerIO& io) {   // dW_l, db_l into the slabs
+  const MlpGeom& g = r.g;
+  GemmP p = {};
+  p.A = io.dy; p.lda = (int)g.ld[l + 1]; p.sA = g.b * g.ld[l + 1];
+  p.B = io.in; p.ldb = (int)io.in_ld; p.sB = io.in_stride;
+  p.C = r.slabs + g.w_off[l]; p.ldc = (int)g.ld[l]; p.sC = g.net_stride;
+  p.dbias = r.slabs + g.b_off[l]; p.sBias = g.net_stride;
+  p.M = g.d->dims[l + 1]; p.N = (int)g.ld[l]; p.K = (int)g.b;
+  p.ncols_store = (int)g.ld[l + 1];
+  p.groups = g.n_nets; p.splits = r.splits;
+  p.rows_per_split = (int)pqlk_round_up((g.b + r.splits - 1) / r.splits, KT_MAX);
+  p.sSplit = g.arena;
+  // B operand limit: X has ldx >= ld_in columns; only the first ld_in are wanted.  The loader bounds
+  // columns by p.ldb, so clamp through N: tiles never start beyond N and pads inside ldb are zero.
+  return launch_auto<MODE_DW>(p, g.n_nets * r.splits, r.st);
+}
+
+static int bwd_layer_dx(const BwdRun& r, int l, const LayerIO& io) {
+  const MlpGeom& g = r.g;
+  const BwdCall& c = r.c;
+  if (l == 0 && !c.dx) return PQLK_OK;
+  GemmP p = {};
+  p.A = io.dy; p.lda = (int)g.ld[l + 1]; p.sA = g.b * g.ld[l + 1];
+  p.B = c.params + g.w_off[l]; p.ldb = (int)g.ld[l]; p.sB = g.net_stride;
+  p.M = (int)g.b; p.N = g.d->dims[l]; p.K = g.d->dims[l + 1];
+  p.ncols_store = (int)g.ld[l];
+  p.groups = g.n_nets;
+  if (l > 0) {  // dH_{l-1} = (dY_l W_l) * ELU'(H_{l-1})
+    p.C = io.dz; p.ldc = (int)g.ld[l]; p.sC = g.b * g.ld[l];
+    p.aux = io.in; p.ldaux = (int)io.in_ld; p.sAux = io.in_stride;
+    p.zsum = 0; p.epi = EPI_DELU;
+    return launch_auto<MODE_DX>(p, g.n_nets, r.st);
+  }
+  // input gradient, summed over nets
+  p.C = c.dx; p.ldc = (int)c.ld_dx; p.sC = 0;
+  p.zsum = 1; p.epi = EPI_NONE;
+  if (c.dx_tanh_of) {
+    p.epi = EPI_DTANH_SLICE; p.aux = c.dx_tanh_of; p.ldaux = (int)c.ld_tanh; p.col0 = c.dx_col0; p.ncol = c.dx_cols;
+  }
+  if (dx_slice_ok(p)) return launch_dx_slice(p, r.st);   // narrow slice: split-reduction MFMA kernel (narrow.h)
+  return launch_auto<MODE_DX>(p, 1, r.st);
+}
+
+// the last layer; *head_blocks = number of per-block partials of its dW / db left in head_part (0: they went into the slabs)
+static int bwd_head(const BwdRun& r, const LayerIO& io, int* head_blocks) {
+  const MlpGeom& g = r.g;
+  const BwdCall& c = r.c;
+  const int l = g.L - 1;
+  const HeadBwd kind = head_bwd_kind(g.d);
+  int rc = PQLK_OK;
+  if (kind == HEAD_GEMM || io.in_ld < g.ld[l]) {
+    if (c.grads) rc = bwd_layer_dw(r, l, io);
+    return rc ? rc : bwd_layer_dx(r, l, io);
+  }
+  SkinnyP q = {};
+  q.X = io.in; q.ldx = (int)io.in_ld; q.sX = io.in_stride;
+  q.dY = io.dy; q.ldy = (int)g.ld[l + 1]; q.sY = g.b * g.ld[l + 1];
+  q.M = (int)g.b; q.N = g.d->dims[l + 1]; q.K = (int)g.ld[l]; q.ldk = (int)g.ld[l]; q.ldc = (int)g.ld[l + 1];
+  if (c.grads && kind == HEAD_FUSED) {   // dX + dW + db in one pass over the activations
+    q.W = c.params + g.w_off[l]; q.sW = g.net_stride;
+    q.C = io.dz; q.sC = g.b * g.ld[l];
+    q.epi = SK_EPI_DELU;
+    *head_blocks = skinny_bwd_blocks(g.b, g.n_nets);
+    if (c.td) {
+      q.td_q = c.acts + g.a_off[l]; q.td_qt = c.td->qt; q.td_rew = c.td->rew; q.td_done = c.td->done;
+      q.td_gamma_n = c.td->gamma_n; q.td_two_over_b = 2.0f / (float)g.b; q.td_part = c.td->loss_part;
+    }
+    return launch_skinny_bwd(q, g.n_nets, r.head_part, (long long)g.head_floats, r.st);
+  }
+  if (c.grads) {
+    q.dW = r.slabs + g.w_off[l]; q.dB = r.slabs + g.b_off[l]; q.sW = g.net_stride; q.sBias = g.net_stride; q.sSplit = g.arena;
+    q.splits = r.splits; q.rows_per_split = (int)pqlk_round_up((g.b + r.splits - 1) / r.splits, KT_MAX);
+    rc = launch_skinny_dw(q, g.n_nets, r.st);
+    if (rc) return rc;
+  }
+  if (l == 0) return bwd_layer_dx(r, l, io);   // a one-layer net: the input gradient is a GEMM
+  q.W = c.params + g.w_off[l]; q.sW = g.net_stride;
+  q.C = io.dz; q.sC = g.b * g.ld[l];
+  q.epi = SK_EPI_DELU;
+  return launch_skinny_dx(q, g.n_nets, r.st);
+}
+
+static int mlp_backward_impl(const BwdCall& c) {
+  const PqlMlpDesc* d = c.d;
   int rc = desc_ok(d);
   if (rc) return rc;
-  const bool ranged = l_hi >= 0;
-  if (!ranged) l_hi = d->n_layers - 1;
-  PQLK_REQUIRE(l_lo >= 0 && l_lo <= l_hi && l_hi < d->n_layers, PQLK_E_RANGE);
-  PQLK_REQUIRE(!ranged || (grads && !dx && !sq_part), PQLK_E_UNSUPPORTED);
-  PQLK_REQUIRE(params && x && acts && (dy || td || head_done || l_hi < d->n_layers - 1) && ws, PQLK_E_NULL);
-  PQLK_REQUIRE(!head_done || (!ranged && grads && !dx && !td && d->n_layers >= 2), PQLK_E_UNSUPPORTED);
-  if (td) PQLK_REQUIRE(grads && d->n_nets == 2 && d->dims[d->n_layers] == 1 && head_is_fused(d), PQLK_E_UNSUPPORTED);
-  PQLK_REQUIRE(b > 0 && b < (1LL << 30), PQLK_E_SHAPE);
-  PQLK_REQUIRE(ldx % 32 == 0 && ldx >= pqlk_ld(d->dims[0]), PQLK_E_ALIGN);
-  PQLK_REQUIRE(grads || dx, PQLK_E_NULL);
-  if (grads) PQLK_REQUIRE(splits >= 1 && splits <= 64, PQLK_E_SHAPE);
-  if (!grads) splits = 0;
-  PQLK_REQUIRE(ws_floats >= 2 * (int64_t)d->n_nets * b * max_hidden_ld(d) + (int64_t)splits * pqlk_mlp_param_floats(d) +
-                                (grads ? head_part_floats(d, b) : 0), PQLK_E_WORKSPACE);
-  PQLK_REQUIRE(!sq_part || grads, PQLK_E_NULL);
-  if (dx) {
-    PQLK_REQUIRE(ld_dx % 32 == 0, PQLK_E_ALIGN);
-    if (dx_tanh_of) PQLK_REQUIRE(dx_col0 >= 0 && dx_cols > 0 && dx_col0 + dx_cols <= d->dims[0] && ld_dx >= dx_cols,
-                                 PQLK_E_RANGE);
-    else PQLK_REQUIRE(ld_dx >= pqlk_ld(d->dims[0]), PQLK_E_SHAPE);
+  const int L = d->n_layers, l_hi = c.ranged ? c.l_hi : L - 1, l_lo = c.l_lo;
+  PQLK_REQUIRE(l_lo >= 0 && l_lo <= l_hi && l_hi < L, PQLK_E_RANGE);
+  PQLK_REQUIRE(!c.ranged || (c.grads && !c.dx && !c.sq_part), PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(c.params && c.x && c.acts && (c.dy || c.td || c.head_done || l_hi < L - 1) && c.ws, PQLK_E_NULL);
+  PQLK_REQUIRE(!c.head_done || (!c.ranged && c.grads && !c.dx && !c.td && L >= 2), PQLK_E_UNSUPPORTED);
+  if (c.td) PQLK_REQUIRE(c.grads && d->n_nets == 2 && d->dims[L] == 1 && head_is_fused(d), PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(c.b > 0 && c.b < (1LL << 30), PQLK_E_SHAPE);
+  PQLK_REQUIRE(c.ldx % 32 == 0 && c.ldx >= pqlk_ld(d->dims[0]), PQLK_E_ALIGN);
+  PQLK_REQUIRE(c.grads || c.dx, PQLK_E_NULL);
+  if (c.grads) PQLK_REQUIRE(c.splits >= 1 && c.splits <= 64, PQLK_E_SHAPE);
+  BwdRun r = {c, mlp_geom(d, c.b), c.grads ? c.splits : 0};
+  const MlpGeom& g = r.g;
+  const BwdWs w = bwd_ws(g, r.splits);
+  PQLK_REQUIRE(c.ws_floats >= w.total, PQLK_E_WORKSPACE);
+  PQLK_REQUIRE(!c.sq_part || c.grads, PQLK_E_NULL);
+  if (c.dx) {
+    PQLK_REQUIRE(c.ld_dx % 32 == 0, PQLK_E_ALIGN);
+    if (c.dx_tanh_of) PQLK_REQUIRE(c.dx_col0 >= 0 && c.dx_cols > 0 && c.dx_col0 + c.dx_cols <= d->dims[0] && c.ld_dx >= c.dx_cols,
+                                   PQLK_E_RANGE);
+    else PQLK_REQUIRE(c.ld_dx >= pqlk_ld(d->dims[0]), PQLK_E_SHAPE);
   }
-  const int64_t net_stride = pqlk_mlp_net_stride(d);
-  const int64_t arena = net_stride * d->n_nets;
-  const int L = d->n_layers;
-  const int64_t dbuf = (int64_t)d->n_nets * b * max_hidden_ld(d);
-  float* dact[2] = {ws, ws + dbuf};
-  float* slabs = ws + 2 * dbuf;
-  float* head_part = slabs + (int64_t)splits * arena;
-  int head_blocks = head_done;   // > 0: the last layer's dW / db are per-block partials in head_part
-  hipStream_t st = pqlk_s(stream);
+  r.dact[0] = c.ws + w.dz[0]; r.dact[1] = c.ws + w.dz[1]; r.slabs = c.ws + w.slabs; r.head_part = c.ws + w.head_part;
+  r.st = pqlk_s(c.stream);
+  int head_blocks = c.head_done;   // > 0: the last layer's dW / db are per-block partials in head_part
 
-  for (int l = head_done ? l_hi - 1 : l_hi; l >= l_lo; --l) {
-    // layer l reads dL/dZ_l from where layer l + 1 left it and writes dL/dZ_{l-1} into the other buffer
-    const float* cur_dy = l == L - 1 ? dy : dact[(L - 2 - l) & 1];  // (n_nets, b, ld(out_l))
-    const int flip = (L - 1 - l) & 1;
-    int64_t w_off, b_off;
-    pqlk_mlp_layer_offsets(d, l, &w_off, &b_off);
-    const int64_t ld_out = pqlk_ld(d->dims[l + 1]);
-    const int64_t ld_in = pqlk_ld(d->dims[l]);
-    const float* in;
-    int64_t in_ld, in_stride;
-    if (l == 0) {
-      in = x; in_ld = ldx; in_stride = 0;
+  for (int l = c.head_done ? l_hi - 1 : l_hi; l >= l_lo; --l) {
+    const LayerIO io = bwd_layer_io(r, l);
+    if (l == L - 1) {
+      rc = bwd_head(r, io, &head_blocks);
     } else {
-      int64_t i_off;
-      pqlk_mlp_act_offset(d, b, 0, l - 1, &i_off, &in_ld);
-      in = acts + i_off; in_stride = b * in_ld;
+      if (c.grads) rc = bwd_layer_dw(r, l, io);
+      if (!rc) rc = bwd_layer_dx(r, l, io);
     }
-    const bool skinny = (l == L - 1) && skinny_bwd_ok(d->dims[l + 1], (int)ld_in) && in_ld >= ld_in;
-    if (skinny) {
-      SkinnyP q = {};
-      q.X = in; q.ldx = (int)in_ld; q.sX = in_stride;
-      q.dY = cur_dy; q.ldy = (int)ld_out; q.sY = b * ld_out;
-      q.M = (int)b; q.N = d->dims[l + 1]; q.K = (int)ld_in; q.ldk = (int)ld_in; q.ldc = (int)ld_out;
-      if (grads && head_is_fused(d)) {   // dX + dW + db in one pass over the activations
-        q.W = params + w_off; q.sW = net_stride;
-        q.C = dact[flip]; q.sC = b * ld_in;
-        q.epi = SK_EPI_DELU;
-        head_blocks = skinny_bwd_blocks(b, d->n_nets);
-        if (td) {
-          int64_t q_off, q_ld;
-          pqlk_mlp_act_offset(d, b, 0, L - 1, &q_off, &q_ld);
-          PQLK_REQUIRE(in_ld >= ld_in && q_ld == ld_out, PQLK_E_SHAPE);
-          q.td_q = acts + q_off; q.td_qt = td->qt; q.td_rew = td->rew; q.td_done = td->done;
-          q.td_gamma_n = td->gamma_n; q.td_two_over_b = 2.0f / (float)b; q.td_part = td->loss_part;
-        }
-        rc = launch_skinny_bwd(q, d->n_nets, head_part, (long long)(net_stride - w_off), st);
-        if (rc) return rc;
-        continue;
-      }
-      if (grads) {
-        q.dW = slabs + w_off; q.dB = slabs + b_off; q.sW = net_stride; q.sBias = net_stride; q.sSplit = arena;
-        q.splits = splits; q.rows_per_split = (int)pqlk_round_up((b + splits - 1) / splits, KT_MAX);
-        rc = launch_skinny_dw(q, d->n_nets, st);
-        if (rc) return rc;
-      }
-      if (l > 0) {
-        q.W = params + w_off; q.sW = net_stride;
-        q.C = dact[flip]; q.sC = b * ld_in;
-        q.epi = SK_EPI_DELU;
-        rc = launch_skinny_dx(q, d->n_nets, st);
-        if (rc) return rc;
-        continue;
-      }
-      if (!dx) continue;
-    }
-    if (grads && !skinny) {  // dW_l, db_l
-      GemmP p = {};
-      p.A = cur_dy; p.lda = (int)ld_out; p.sA = b * ld_out;
-      p.B = in; p.ldb = (int)in_ld; p.sB = in_stride;
-      p.C = slabs + w_off; p.ldc = (int)ld_in; p.sC = net_stride;
-      p.dbias = slabs + b_off; p.sBias = net_stride;
-      p.M = d->dims[l + 1]; p.N = (int)ld_in; p.K = (int)b;
-      p.ncols_store = (int)ld_out;
-      p.groups = d->n_nets; p.splits = splits;
-      p.rows_per_split = (int)pqlk_round_up((b + splits - 1) / splits, KT_MAX);
-      p.sSplit = arena;
-      // B operand limit: X has ldx >= ld_in columns; only the first ld_in are wanted.  The loader bounds
-      // columns by p.ldb, so clamp through N: tiles never start beyond N and pads inside ldb are zero.
-      rc = launch_auto<MODE_DW>(p, d->n_nets * splits, st);
-      if (rc) return rc;
-    }
-    if (l > 0) {  // dH_{l-1} = (dY_l W_l) * ELU'(H_{l-1})
-      GemmP p = {};
-      p.A = cur_dy; p.lda = (int)ld_out; p.sA = b * ld_out;
-      p.B = params + w_off; p.ldb = (int)ld_in; p.sB = net_stride;
-      p.C = dact[flip]; p.ldc = (int)ld_in; p.sC = b * ld_in;
-      p.aux = in; p.ldaux = (int)in_ld; p.sAux = in_stride;
-      p.M = (int)b; p.N = d->dims[l]; p.K = d->dims[l + 1];
-      p.ncols_store = (int)ld_in;
-      p.groups = d->n_nets; p.zsum = 0;
-      p.epi = EPI_DELU;
-      rc = launch_auto<MODE_DX>(p, d->n_nets, st);
-      if (rc) return rc;
-    } else if (dx) {  // input gradient, summed over nets
-      GemmP p = {};
-      p.A = cur_dy; p.lda = (int)ld_out; p.sA = b * ld_out;
-      p.B = params + w_off; p.ldb = (int)ld_in; p.sB = net_stride;
-      p.C = dx; p.ldc = (int)ld_dx; p.sC = 0;
-      p.M = (int)b; p.N = d->dims[0]; p.K = d->dims[1];
-      p.ncols_store = (int)ld_in;
-      p.groups = d->n_nets; p.zsum = 1;
-      if (dx_tanh_of) {
-        p.epi = EPI_DTANH_SLICE; p.aux = dx_tanh_of; p.ldaux = (int)ld_tanh; p.col0 = dx_col0; p.ncol = dx_cols;
-      } else {
-        p.epi = EPI_NONE;
-      }
-      if (dx_slice_ok(p)) rc = launch_dx_slice(p, st);   // narrow slice: split-reduction MFMA kernel (narrow.h)
-      else rc = launch_auto<MODE_DX>(p, 1, st);
-      if (rc) return rc;
-    }
+    if (rc) return rc;
   }
-  if (grads) {
-    ReduceP r = {};
-    r.slabs = slabs; r.splits = splits; r.n = arena; r.out = grads;
-    r.head_part = head_part; r.head_parts = head_blocks; r.n_nets = d->n_nets; r.net_stride = net_stride;
-    int64_t w_last, b_last, w_lo, w_next, b_tmp;
-    pqlk_mlp_layer_offsets(d, L - 1, &w_last, &b_last);
-    r.head_off = w_last; r.head_floats = net_stride - w_last;
-    pqlk_mlp_layer_offsets(d, l_lo, &w_lo, &b_tmp);
-    w_next = net_stride;
-    if (l_hi < L - 1) pqlk_mlp_layer_offsets(d, l_hi + 1, &w_next, &b_tmp);
-    r.seg_off = w_lo; r.seg_len = w_next - w_lo;   // layers sit in ascending order inside a net's block
-    r.sq_part = sq_part; r.step_dev = step_dev; r.parts_dev = head_parts_dev;
-    r.main_blocks = reduce_main_blocks(r.seg_len * d->n_nets, sq_part != nullptr);   // with sq_part: at most 1024 + head blocks partials
-    const int extra = head_blocks > 0 ? (int)((head_quads(d) + 3) / 4) : 0;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(r.main_blocks + extra), dim3(256), 0, st, r);
+  if (c.grads) {
+    ReduceP p = {};
+    p.slabs = r.slabs; p.splits = r.splits; p.n = g.arena; p.out = c.grads;
+    p.head_part = r.head_part; p.head_parts = head_blocks; p.n_nets = g.n_nets; p.net_stride = g.net_stride;
+    p.head_off = g.w_off[L - 1]; p.head_floats = g.head_floats;
+    p.seg_off = g.w_off[l_lo];   // layers sit in ascending order inside a net's block
+    p.seg_len = (l_hi < L - 1 ? g.w_off[l_hi + 1] : g.net_stride) - p.seg_off;
+    p.sq_part = c.sq_part; p.step_dev = c.step_dev; p.parts_dev = c.head_parts_dev;
+    p.main_blocks = reduce_main_blocks(p.seg_len * g.n_nets, c.sq_part != nullptr);   // with sq_part: at most 1024 + head blocks partials
+    const int extra = head_blocks > 0 ? head_fold_blocks(g) : 0;
+    hipLaunchKernelGGL(k_reduce_slabs, dim3(p.main_blocks + extra), dim3(256), 0, r.st, p);
     PQLK_LAUNCH_CHECK();
   }
   return PQLK_OK;
@@ -1418,9 +1454,9 @@ static int mlp_backward_impl(const PqlMlpDesc* d, const float* params, const flo
 // through the actor's tanh.  With scalar Q heads the samples are partitioned by the net that attained min(Q1, Q2) and the dX
 // chain runs over compact rows (minnet.h): half the MFMA work of the dense chain, same per-sample bits.  Anything else
 // (distributional heads, widths that are not multiples of 128, a single net) takes the dense chain of pqlk_mlp_backward.
-static bool minnet_ok(const PqlMlpDesc* d, const float* dx, const float* dx_tanh_of, int dx_cols) {
+static bool compact_chain_ok(const PqlMlpDesc* d) {
   const int L = d->n_layers;
-  if (d->n_nets != 2 || L < 3 || d->dims[L] != 1 || !dx || !dx_tanh_of || dx_cols > 32) return false;
+  if (d->n_nets != 2 || L < 3 || d->dims[L] != 1) return false;
   if (!skinny_bwd_ok(1, (int)pqlk_ld(d->dims[L - 1]))) return false;
   for (int l = 1; l < L; ++l)
     if (d->dims[l] % 32 != 0) return false;
@@ -1428,7 +1464,9 @@ static bool minnet_ok(const PqlMlpDesc* d, const float* dx, const float* dx_tanh
     if (d->dims[l] % 128 != 0) return false;   // output width of the dX GEMM of layer l + 1: whole 128-column tiles
   return true;
 }
-static int64_t minnet_rows_cap(int64_t b) { return 2 * pqlk_round_up(b, MN_TILE); }
+static bool minnet_ok(const PqlMlpDesc* d, const float* dx, const float* dx_tanh_of, int dx_cols) {
+  return dx && dx_tanh_of && dx_cols <= 32 && compact_chain_ok(d);
+}
 
 // Tile shape of the compact dX products (rows = samples partitioned by owning net: b + ties + up to 254 pad rows instead of 2 b).
 // 128 x 128 tiles at two per CU leave a handful of CUs with twice the work (82 -> 63 us on the 512-wide layer with 128 x 64 tiles,
@@ -1443,12 +1481,56 @@ static int launch_compact_dx(const GemmP& p, bool first, hipStream_t st) {
   if (small) return launch_gemm<MODE_DX, 64, 64, EPI_DELU>(p, 1, st);
   return launch_gemm<MODE_DX, 128, 64, EPI_DELU>(p, 1, st);
 }
-   // every sample a tie: both runs full
+
+struct CompactRun {   // the critic's side of a compact chain: its geometry, arena, stash and the pieces of its workspace
+  const MlpGeom& g; const float* params; const float* acts;
+  int64_t rows_cap; float* dz[2]; int* perm; int* mn; int* tie0;
+};
+static CompactRun compact_run(const MlpGeom& g, const float* params, const float* acts, float* ws) {
+  const CompactWs w = compact_ws(g.max_hidden_ld, g.b);
+  return {g, params, acts, w.rows_cap, {ws + w.dz[0], ws + w.dz[1]}, reinterpret_cast<int*>(ws + w.perm),
+          reinterpret_cast<int*>(ws + w.mn), reinterpret_cast<int*>(ws + w.tie0)};
+}
+
+// hidden layers: dH_{l-1} = (dZ_l W_l) * ELU'(H_{l-1}) over compact rows, one net per 128-row tile; dZ_{L-1} is in dz[0] and dZ_1
+// ends up in dz[L & 1]
+static int compact_dx_chain(const CompactRun& r, hipStream_t st) {
+  const MlpGeom& g = r.g;
+  int flip = 0;
+  for (int l = g.L - 2; l >= 1; --l, flip ^= 1) {
+    GemmP p = {};
+    p.A = r.dz[flip]; p.lda = (int)g.ld[l + 1]; p.sA = 0;
+    p.B = r.params + g.w_off[l]; p.ldb = (int)g.ld[l]; p.sB = g.net_stride;
+    p.C = r.dz[flip ^ 1]; p.ldc = (int)g.ld[l]; p.sC = 0;
+    p.aux = r.acts + g.a_off[l - 1]; p.ldaux = (int)g.ld[l]; p.sAux = g.b * g.ld[l];
+    p.M = (int)r.rows_cap; p.N = g.d->dims[l]; p.K = g.d->dims[l + 1];
+    p.ncols_store = p.ldc;
+    p.groups = 2; p.zsum = 0; p.epi = EPI_DELU;
+    p.perm = r.perm; p.mn = r.mn;
+    if (int rc = launch_compact_dx(p, l == g.L - 2, st)) return rc;
+  }
+  return PQLK_OK;
+}
+
+// first layer: columns [col0, col0 + ncol) only, through tanh', scattered back to batch rows of `out`
+static GemmP compact_slice(const CompactRun& r, float* out, int64_t ld_out, int col0, int ncol, const float* tanh_of, int64_t ld_tanh) {
+  const MlpGeom& g = r.g;
+  GemmP p = {};
+  p.A = r.dz[g.L & 1]; p.lda = (int)g.ld[1]; p.sA = 0;
+  p.B = r.params + g.w_off[0]; p.ldb = (int)g.ld[0]; p.sB = g.net_stride;
+  p.C = out; p.ldc = (int)ld_out; p.sC = 0;
+  p.M = (int)r.rows_cap; p.N = g.d->dims[0]; p.K = g.d->dims[1];
+  p.ncols_store = p.ldb;
+  p.groups = 1; p.zsum = 1;
+  p.epi = EPI_DTANH_SLICE; p.aux = tanh_of; p.ldaux = (int)ld_tanh; p.col0 = col0; p.ncol = ncol;
+  p.perm = r.perm; p.mn = r.mn;
+  return p;
+}
 
 extern "C" int64_t pqlk_dpg_backward_ws_floats(const PqlMlpDesc* d, int64_t b) {
   if (desc_ok(d) || b <= 0) return 0;
-  const int64_t dense = pqlk_mlp_bwd_ws_floats(d, b, 1);
-  const int64_t compact = 2 * minnet_rows_cap(b) * max_hidden_ld(d) + 2 * minnet_rows_cap(b) + 64;   // two dZ buffers, perm, mn, tie0
+  const MlpGeom g = mlp_geom(d, b);
+  const int64_t dense = bwd_ws(g, 1).total, compact = compact_ws(g.max_hidden_ld, b).total;
   return dense > compact ? dense : compact;
 }
 
@@ -1459,97 +1541,52 @@ extern "C" int pqlk_dpg_critic_backward(const PqlMlpDesc* d, const float* params
   int rc = desc_ok(d);
   if (rc) return rc;
   PQLK_REQUIRE(ws_floats >= pqlk_dpg_backward_ws_floats(d, b), PQLK_E_WORKSPACE);
-  if (!minnet_ok(d, dx, dx_tanh_of, dx_cols) || b > 131072)   // (the one-block partition holds <= 128 samples per thread)
-    return mlp_backward_impl(d, params, x, ldx, b, acts, dy, nullptr, 1, dx, ld_dx, dx_col0, dx_cols, dx_tanh_of, ld_tanh, ws, ws_floats,
-                             nullptr, nullptr, stream);
+  if (!minnet_ok(d, dx, dx_tanh_of, dx_cols) || b > 131072) {   // (the one-block partition holds <= 128 samples per thread)
+    BwdCall c = bwd_call(d, params, x, ldx, b, acts, nullptr, 1, ws, ws_floats, stream);
+    c.dy = dy; c.dx = dx; c.ld_dx = ld_dx; c.dx_col0 = dx_col0; c.dx_cols = dx_cols; c.dx_tanh_of = dx_tanh_of; c.ld_tanh = ld_tanh;
+    return mlp_backward_impl(c);
+  }
   PQLK_REQUIRE(params && acts && dy && ws, PQLK_E_NULL);
   PQLK_REQUIRE(b > 0 && b < (1LL << 29), PQLK_E_SHAPE);
   PQLK_REQUIRE(ld_dx % 32 == 0 && dx_col0 >= 0 && dx_cols > 0 && dx_col0 + dx_cols <= d->dims[0] && ld_dx >= dx_cols, PQLK_E_RANGE);
-  const int L = d->n_layers;
-  const int64_t net_stride = pqlk_mlp_net_stride(d);
-  const int64_t rows_cap = minnet_rows_cap(b), mld = max_hidden_ld(d);
-  float* dz[2] = {ws, ws + rows_cap * mld};
-  int* perm = reinterpret_cast<int*>(ws + 2 * rows_cap * mld);
-  int* mn = perm + rows_cap;
+  const MlpGeom g = mlp_geom(d, b);
+  const CompactRun r = compact_run(g, params, acts, ws);
+  const int L = g.L;
   hipStream_t st = pqlk_s(stream);
   // 1. partition by owning net
-  int64_t q_off, q_ld;
-  pqlk_mlp_act_offset(d, b, 0, L - 1, &q_off, &q_ld);
-  hipLaunchKernelGGL(k_minnet_partition, dim3(1), dim3(1024), 0, st, owner, acts + q_off, q_ld, b, perm, rows_cap, mn);
+  hipLaunchKernelGGL(k_minnet_partition, dim3(1), dim3(1024), 0, st, owner, acts + g.a_off[L - 1], g.ld[L], b, r.perm, r.rows_cap, r.mn);
   PQLK_LAUNCH_CHECK();
   // 2. head: dZ_{L-1} in compact rows
   {
-    int64_t w_off, b_off, h_off, h_ld;
-    pqlk_mlp_layer_offsets(d, L - 1, &w_off, &b_off);
-    pqlk_mlp_act_offset(d, b, 0, L - 2, &h_off, &h_ld);
     MinnetHeadP h = {};
-    h.H = acts + h_off; h.sH = b * h_ld; h.ldh = (int)h_ld;
-    h.W = params + w_off; h.sW = net_stride; h.ldk = (int)pqlk_ld(d->dims[L - 1]);
-    h.dY = dy; h.sY = b * pqlk_ld(1); h.ldy = (int)pqlk_ld(1);
-    h.C = dz[0]; h.perm = perm; h.mn = mn; h.N = 1; h.K = h.ldk; h.rows_cap = rows_cap;
+    h.H = acts + g.a_off[L - 2]; h.sH = b * g.ld[L - 1]; h.ldh = (int)g.ld[L - 1];
+    h.W = params + g.w_off[L - 1]; h.sW = g.net_stride; h.ldk = (int)g.ld[L - 1];
+    h.dY = dy; h.sY = b * g.ld[L]; h.ldy = (int)g.ld[L];
+    h.C = r.dz[0]; h.perm = r.perm; h.mn = r.mn; h.N = 1; h.K = h.ldk; h.rows_cap = r.rows_cap;
     h.zero_out = dx; h.zero_floats = b * ld_dx;
-    int64_t blocks = rows_cap / 4;
+    int64_t blocks = r.rows_cap / 4;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_minnet_head_dx, dim3((unsigned)blocks), dim3(256), (size_t)2 * h.N * h.K * sizeof(float), st, h);
     PQLK_LAUNCH_CHECK();
   }
-  // 3. hidden layers: dH_{l-1} = (dZ_l W_l) * ELU'(H_{l-1}) over compact rows, one net per 128-row tile
-  int flip = 0;
-  for (int l = L - 2; l >= 1; --l) {
-    int64_t w_off, b_off, a_off, a_ld;
-    pqlk_mlp_layer_offsets(d, l, &w_off, &b_off);
-    pqlk_mlp_act_offset(d, b, 0, l - 1, &a_off, &a_ld);
-    GemmP p = {};
-    p.A = dz[flip]; p.lda = (int)pqlk_ld(d->dims[l + 1]); p.sA = 0;
-    p.B = params + w_off; p.ldb = (int)pqlk_ld(d->dims[l]); p.sB = net_stride;
-    p.C = dz[flip ^ 1]; p.ldc = (int)pqlk_ld(d->dims[l]); p.sC = 0;
-    p.aux = acts + a_off; p.ldaux = (int)a_ld; p.sAux = b * a_ld;
-    p.M = (int)rows_cap; p.N = d->dims[l]; p.K = d->dims[l + 1];
-    p.ncols_store = p.ldc;
-    p.groups = 2; p.zsum = 0; p.epi = EPI_DELU;
-    p.perm = perm; p.mn = mn;
-    rc = launch_compact_dx(p, l == L - 2, st);
-    if (rc) return rc;
-    flip ^= 1;
-  }
-  // 4. first layer: action columns only, through tanh', scattered back to batch rows
-  {
-    int64_t w_off, b_off;
-    pqlk_mlp_layer_offsets(d, 0, &w_off, &b_off);
-    GemmP p = {};
-    p.A = dz[flip]; p.lda = (int)pqlk_ld(d->dims[1]); p.sA = 0;
-    p.B = params + w_off; p.ldb = (int)pqlk_ld(d->dims[0]); p.sB = net_stride;
-    p.C = dx; p.ldc = (int)ld_dx; p.sC = 0;
-    p.M = (int)rows_cap; p.N = d->dims[0]; p.K = d->dims[1];
-    p.ncols_store = p.ldb;
-    p.groups = 1; p.zsum = 1;
-    p.epi = EPI_DTANH_SLICE; p.aux = dx_tanh_of; p.ldaux = (int)ld_tanh; p.col0 = dx_col0; p.ncol = dx_cols;
-    p.perm = perm; p.mn = mn;
-    PQLK_REQUIRE(dx_slice_ok(p), PQLK_E_UNSUPPORTED);
-    rc = launch_dx_slice(p, st);
-    if (rc) return rc;
-  }
-  return PQLK_OK;
+  // 3. hidden layers, 4. first layer
+  rc = compact_dx_chain(r, st);
+  if (rc) return rc;
+  const GemmP p = compact_slice(r, dx, ld_dx, dx_col0, dx_cols, dx_tanh_of, ld_tanh);
+  PQLK_REQUIRE(dx_slice_ok(p), PQLK_E_UNSUPPORTED);
+  return launch_dx_slice(p, st);
 }
 
 // ---- round 4: the P-learner's backward through the frozen critic in FOUR launches (was seven) -----------------------------------
 // k_dpg_minnet_head (DPG loss partials + partition + compact head, off the compact Q the fused forward left), two compact dX GEMMs,
 // k_dx_slice<D, QPW> (action slice through tanh' + the ACTOR's head backward).  Needs: twin scalar-head critic that the min-net
-// chain takes (minnet_ok) with a fused forward + fused head (so that qc exists), first hidden width a multiple of 128 (slice ring),
-// an actor whose head is <= 16 wide over 128 or 256 inputs and whose backward takes per-tile head partials (head_is_fused).
+// chain takes (compact_chain_ok) with a fused forward + fused head (so that qc exists), first hidden width a multiple of 128 (slice
+// ring), an actor whose head is <= 16 wide over 128 or 256 inputs and whose backward takes per-tile head partials (head_is_fused).
 static bool dpg_fused_ok(const PqlMlpDesc* c, const PqlMlpDesc* a, int64_t b) {
   if (desc_ok(c) || desc_ok(a) || b <= 0 || b > 131072) return false;
-  const int Lc = c->n_layers, La = a->n_layers;
-  if (c->n_nets != 2 || Lc < 3 || c->dims[Lc] != 1 || a->n_nets != 1 || La < 2) return false;
-  if (!skinny_bwd_ok(1, (int)pqlk_ld(c->dims[Lc - 1]))) return false;
-  for (int l = 1; l < Lc; ++l)
-    if (c->dims[l] % 32 != 0) return false;
-  for (int l = 1; l < Lc - 1; ++l)
-    if (c->dims[l] % 128 != 0) return false;
-  if (!fusable(c, nullptr) || !head_fusable(c) || getenv("PQLK_NO_FUSED_HEAD")) return false;
-  const int A = a->dims[La];
-  if (A > 16 || c->dims[0] < A || !head_is_fused(a) || !dx_slice_head_ok(A, (int)pqlk_ld(a->dims[La - 1])) || a->dims[La - 1] % 32 != 0) return false;
-  return true;
+  const int La = a->n_layers, A = a->dims[La];
+  if (!compact_chain_ok(c) || a->n_nets != 1 || La < 2 || !fused_with_head(c)) return false;
+  return A <= 16 && c->dims[0] >= A && head_is_fused(a) && dx_slice_head_ok(A, (int)pqlk_ld(a->dims[La - 1])) && a->dims[La - 1] % 32 == 0;
 }
 
 extern "C" int32_t pqlk_dpg_fused_ok(const PqlMlpDesc* critic, const PqlMlpDesc* actor, int64_t b) {
@@ -1560,7 +1597,7 @@ extern "C" int32_t pqlk_dpg_fused_ok(const PqlMlpDesc* critic, const PqlMlpDesc*
 extern "C" int32_t pqlk_dpg_fused_loss_parts(void) { return DPG_LOSS_PARTS; }
 
 // number of head partials (one per compact 32-row tile) pqlk_mlp_backward_tail has to be told about
-extern "C" int32_t pqlk_dpg_fused_head_parts(int64_t b) { return b > 0 ? (int32_t)(minnet_rows_cap(b) / 32) : 0; }
+extern "C" int32_t pqlk_dpg_fused_head_parts(int64_t b) { return b > 0 ? (int32_t)(compact_ws(0, b).rows_cap / 32) : 0; }
 
 // The twin scalar-head critic's forward that ALSO leaves the head outputs compact: qc (2, B) = Q1 | Q2 (mlp.py:186-203).
 extern "C" int pqlk_mlp_forward_qc(const PqlMlpDesc* d, const float* params, const float* packed, int32_t stash_all, const float* x,
@@ -1577,11 +1614,11 @@ extern "C" int pqlk_mlp_forward_qc(const PqlMlpDesc* d, const float* params, con
   } else {
     PQLK_REQUIRE(ldx % 32 == 0 && ldx >= pqlk_ld(d->dims[0]), PQLK_E_ALIGN);
   }
-  PQLK_REQUIRE(d->dims[d->n_layers] == 1 && fusable(d, nullptr) && head_fusable(d) && !getenv("PQLK_NO_FUSED_HEAD"), PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(d->dims[d->n_layers] == 1 && fused_with_head(d), PQLK_E_UNSUPPORTED);
   FusedHead head = {};
   head.n = 1; head.epi = PQLK_ACT_NONE; head.qc = qc;
   head.x2 = x2; head.ldx2 = ldx2; head.x2_col0 = x2_col0;
-  return launch_fused_hidden(d, params, packed, x, ldx, b, acts, stash_all ? 1 : 0, pqlk_s(stream), &head);
+  return launch_fused_hidden(mlp_geom(d, b), params, packed, x, ldx, acts, stash_all ? 1 : 0, pqlk_s(stream), &head);
 }
 
 // DPG loss + the dX chain through the frozen critic + the actor's head backward (pql_p_learner.py:55-58).
@@ -1598,86 +1635,43 @@ extern "C" int pqlk_dpg_backward_fused(const PqlMlpDesc* d, const float* params,
   PQLK_REQUIRE(d && ad && params && acts && qc && dz_a && a_out && loss_part && ws && a_params && a_acts && a_ws, PQLK_E_NULL);   // (x: not read)
   PQLK_REQUIRE(dpg_fused_ok(d, ad, b), PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(ws_floats >= pqlk_dpg_backward_ws_floats(d, b), PQLK_E_WORKSPACE);
-  PQLK_REQUIRE(a_splits >= 1 && a_splits <= 64 && a_ws_floats >= pqlk_mlp_bwd_ws_floats(ad, b, a_splits), PQLK_E_WORKSPACE);
-  const int L = d->n_layers, La = ad->n_layers, A = ad->dims[La];
+  const MlpGeom g = mlp_geom(d, b), ga = mlp_geom(ad, b);
+  const BwdWs aw = bwd_ws(ga, a_splits);   // the actor's workspace is the one its pqlk_mlp_backward_tail call reads
+  PQLK_REQUIRE(a_splits >= 1 && a_splits <= 64 && a_ws_floats >= aw.total, PQLK_E_WORKSPACE);
+  const int L = g.L, La = ga.L, A = ad->dims[La];
   PQLK_REQUIRE(ld_dz % 32 == 0 && ld_dz >= A && ld_tanh >= A && dx_col0 >= 0 && dx_col0 + A <= d->dims[0], PQLK_E_RANGE);
   (void)x; (void)ldx;
   PQLK_REQUIRE(pqlk_aligned16(qc) && pqlk_aligned16(ws) && pqlk_aligned16(a_ws) && pqlk_aligned16(acts) && pqlk_aligned16(a_acts), PQLK_E_ALIGN);
-  const int64_t net_stride = pqlk_mlp_net_stride(d);
-  const int64_t rows_cap = minnet_rows_cap(b), mld = max_hidden_ld(d);
-  float* dz[2] = {ws, ws + rows_cap * mld};
-  int* perm = reinterpret_cast<int*>(ws + 2 * rows_cap * mld);
-  int* mn = perm + rows_cap;          // 64 ints
-  int* tie0 = mn + 64;                // rows_cap ints (pqlk_dpg_backward_ws_floats)
+  const CompactRun r = compact_run(g, params, acts, ws);
   hipStream_t st = pqlk_s(stream);
-  int rc;
   // 1. loss partials + partition + compact head
   {
-    int64_t w_off, b_off, h_off, h_ld;
-    pqlk_mlp_layer_offsets(d, L - 1, &w_off, &b_off);
-    pqlk_mlp_act_offset(d, b, 0, L - 2, &h_off, &h_ld);
     DpgHeadP h = {};
     h.qc = qc; h.B = b;
-    h.H = acts + h_off; h.sH = b * h_ld; h.ldh = (int)h_ld;
-    h.W = params + w_off; h.sW = net_stride;
-    h.C = dz[0]; h.K = (int)pqlk_ld(d->dims[L - 1]);
-    h.perm = perm; h.tie0 = tie0; h.perm_len = rows_cap; h.mn = mn;
+    h.H = acts + g.a_off[L - 2]; h.sH = b * g.ld[L - 1]; h.ldh = (int)g.ld[L - 1];
+    h.W = params + g.w_off[L - 1]; h.sW = g.net_stride;
+    h.C = r.dz[0]; h.K = (int)g.ld[L - 1];
+    h.perm = r.perm; h.tie0 = r.tie0; h.perm_len = r.rows_cap; h.mn = r.mn;
     h.loss_part = loss_part; h.gb = -1.0f / (float)b;
-    int64_t blocks = rows_cap / 16;
+    int64_t blocks = r.rows_cap / 16;
     if (blocks > 256) blocks = 256;
     if (blocks < 1) blocks = 1;
-    h.rows_cap_blk = (int)((rows_cap + blocks - 1) / blocks);
+    h.rows_cap_blk = (int)((r.rows_cap + blocks - 1) / blocks);
     const size_t sh = ((size_t)2 * h.rows_cap_blk + (size_t)2 * h.K) * sizeof(float);
     hipLaunchKernelGGL(k_dpg_minnet_head, dim3((unsigned)blocks), dim3(1024), sh, st, h);
     PQLK_LAUNCH_CHECK();
   }
-  // 2. hidden layers over compact rows (as pqlk_dpg_critic_backward)
-  int flip = 0;
-  for (int l = L - 2; l >= 1; --l) {
-    int64_t w_off, b_off, a_off, a_ld;
-    pqlk_mlp_layer_offsets(d, l, &w_off, &b_off);
-    pqlk_mlp_act_offset(d, b, 0, l - 1, &a_off, &a_ld);
-    GemmP p = {};
-    p.A = dz[flip]; p.lda = (int)pqlk_ld(d->dims[l + 1]); p.sA = 0;
-    p.B = params + w_off; p.ldb = (int)pqlk_ld(d->dims[l]); p.sB = net_stride;
-    p.C = dz[flip ^ 1]; p.ldc = (int)pqlk_ld(d->dims[l]); p.sC = 0;
-    p.aux = acts + a_off; p.ldaux = (int)a_ld; p.sAux = b * a_ld;
-    p.M = (int)rows_cap; p.N = d->dims[l]; p.K = d->dims[l + 1];
-    p.ncols_store = p.ldc;
-    p.groups = 2; p.zsum = 0; p.epi = EPI_DELU;
-    p.perm = perm; p.mn = mn;
-    rc = launch_compact_dx(p, l == L - 2, st);
-    if (rc) return rc;
-    flip ^= 1;
-  }
+  // 2. hidden layers over compact rows
+  if (int rc = compact_dx_chain(r, st)) return rc;
   // 3. action slice through tanh' + the actor head's backward
-  {
-    int64_t w_off, b_off, aw_off, ab_off, ah_off, ah_ld;
-    pqlk_mlp_layer_offsets(d, 0, &w_off, &b_off);
-    pqlk_mlp_layer_offsets(ad, La - 1, &aw_off, &ab_off);
-    pqlk_mlp_act_offset(ad, b, 0, La - 2, &ah_off, &ah_ld);
-    GemmP p = {};
-    p.A = dz[flip]; p.lda = (int)pqlk_ld(d->dims[1]); p.sA = 0;
-    p.B = params + w_off; p.ldb = (int)pqlk_ld(d->dims[0]); p.sB = net_stride;
-    p.C = dz_a; p.ldc = (int)ld_dz; p.sC = 0;
-    p.M = (int)rows_cap; p.N = d->dims[0]; p.K = d->dims[1];
-    p.ncols_store = p.ldb;
-    p.groups = 1; p.zsum = 1;
-    p.epi = EPI_DTANH_SLICE; p.aux = a_out; p.ldaux = (int)ld_tanh; p.col0 = dx_col0; p.ncol = A;
-    p.perm = perm; p.mn = mn;
-    PQLK_REQUIRE(dx_slice_ok(p), PQLK_E_UNSUPPORTED);
-    SliceHeadX hx = {};
-    hx.tie0 = tie0;
-    hx.Hh = a_acts + ah_off; hx.ldh = (int)ah_ld;
-    hx.Wh = a_params + aw_off; hx.N = A; hx.Kh = (int)pqlk_ld(ad->dims[La - 1]);
-    PQLK_REQUIRE(ah_ld == hx.Kh, PQLK_E_SHAPE);
-    hx.dXh = a_ws;   // mlp_backward_impl's first dZ buffer
-    hx.part = a_ws + 2 * (int64_t)ad->n_nets * b * max_hidden_ld(ad) + (int64_t)a_splits * pqlk_mlp_param_floats(ad);
-    hx.part_floats = pqlk_mlp_net_stride(ad) - aw_off;
-    rc = launch_dx_slice(p, st, &hx);
-    if (rc) return rc;
-  }
-  return PQLK_OK;
+  const GemmP p = compact_slice(r, dz_a, ld_dz, dx_col0, A, a_out, ld_tanh);
+  PQLK_REQUIRE(dx_slice_ok(p), PQLK_E_UNSUPPORTED);
+  SliceHeadX hx = {};
+  hx.tie0 = r.tie0;
+  hx.Hh = a_acts + ga.a_off[La - 2]; hx.ldh = (int)ga.ld[La - 1];
+  hx.Wh = a_params + ga.w_off[La - 1]; hx.N = A; hx.Kh = (int)ga.ld[La - 1];
+  hx.dXh = a_ws + aw.dz[0]; hx.part = a_ws + aw.head_part; hx.part_floats = ga.head_floats;
+  return launch_dx_slice(p, st, &hx);
 }
 
 // The rest of a backward whose LAST layer has already been done elsewhere (pqlk_dpg_backward_fused: dL/dZ of the last hidden layer in
@@ -1692,26 +1686,27 @@ extern "C" int pqlk_mlp_backward_tail(const PqlMlpDesc* d, const float* params, 
   PQLK_REQUIRE(grads, PQLK_E_NULL);
   PQLK_REQUIRE((sumsq_part == nullptr) == (step_dev == nullptr), PQLK_E_NULL);
   PQLK_REQUIRE(head_parts > 0 && head_is_fused(d), PQLK_E_UNSUPPORTED);
-  const int L = d->n_layers;
-  const int64_t hf = (int64_t)d->dims[L] * pqlk_ld(d->dims[L - 1]) + pqlk_ld(d->dims[L]);
-  PQLK_REQUIRE((int64_t)head_parts * d->n_nets * hf <= head_part_floats(d, b), PQLK_E_WORKSPACE);
-  return mlp_backward_impl(d, params, x, ldx, b, acts, nullptr, grads, splits, nullptr, 0, 0, 0, nullptr, 0, ws, ws_floats, sumsq_part,
-                           step_dev, stream, nullptr, -1, 0, (int)head_parts, head_parts_dev);
+  const MlpGeom g = mlp_geom(d, b);
+  PQLK_REQUIRE((int64_t)head_parts * g.n_nets * g.head_floats <= bwd_ws(g, splits).head_part_floats, PQLK_E_WORKSPACE);
+  BwdCall c = bwd_call(d, params, x, ldx, b, acts, grads, splits, ws, ws_floats, stream);
+  c.sq_part = sumsq_part; c.step_dev = step_dev; c.head_done = head_parts; c.head_parts_dev = head_parts_dev;
+  return mlp_backward_impl(c);
 }
 
 // float offset of mn = {c0, c1, first row of net 1, compact rows in use} inside pqlk_dpg_backward_fused's critic workspace: the
 // `head_parts_dev` of the pqlk_mlp_backward_tail call that follows it
 extern "C" int64_t pqlk_dpg_fused_mn_offset(const PqlMlpDesc* critic, int64_t b) {
   if (desc_ok(critic) || b <= 0) return -1;
-  return 2 * minnet_rows_cap(b) * max_hidden_ld(critic) + minnet_rows_cap(b);
+  return compact_ws(mlp_geom(critic, b).max_hidden_ld, b).mn;
 }
 
 extern "C" int pqlk_mlp_backward(const PqlMlpDesc* d, const float* params, const float* x, int64_t ldx, int64_t b,
                                  const float* acts, const float* dy, float* grads, int32_t splits, float* dx,
                                  int64_t ld_dx, int32_t dx_col0, int32_t dx_cols, const float* dx_tanh_of,
                                  int64_t ld_tanh, float* ws, int64_t ws_floats, pqlk_stream_t stream) {
-  return mlp_backward_impl(d, params, x, ldx, b, acts, dy, grads, splits, dx, ld_dx, dx_col0, dx_cols, dx_tanh_of, ld_tanh, ws,
-                           ws_floats, nullptr, nullptr, stream);
+  BwdCall c = bwd_call(d, params, x, ldx, b, acts, grads, splits, ws, ws_floats, stream);
+  c.dy = dy; c.dx = dx; c.ld_dx = ld_dx; c.dx_col0 = dx_col0; c.dx_cols = dx_cols; c.dx_tanh_of = dx_tanh_of; c.ld_tanh = ld_tanh;
+  return mlp_backward_impl(c);
 }
 
 // The V-learner's scalar-head step: TD target + twin MSE (pql_v_learner.py:104-108) are formed INSIDE the head's backward pass
@@ -1728,12 +1723,10 @@ extern "C" int pqlk_mlp_backward_td(const PqlMlpDesc* d, const float* params, co
   PQLK_REQUIRE(acts_target && rew && done && loss_part && grads, PQLK_E_NULL);
   PQLK_REQUIRE((sumsq_part == nullptr) == (step_dev == nullptr), PQLK_E_NULL);
   PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
-  int64_t q_off, q_ld;
-  rc = pqlk_mlp_act_offset(d, b, 0, d->n_layers - 1, &q_off, &q_ld);
-  if (rc) return rc;
-  const TdHead td = {acts_target + q_off, rew, done, gamma_n, loss_part};
-  return mlp_backward_impl(d, params, x, ldx, b, acts, nullptr, grads, splits, nullptr, 0, 0, 0, nullptr, 0, ws, ws_floats, sumsq_part,
-                           step_dev, stream, &td);
+  const TdHead td = {acts_target + mlp_geom(d, b).a_off[d->n_layers - 1], rew, done, gamma_n, loss_part};
+  BwdCall c = bwd_call(d, params, x, ldx, b, acts, grads, splits, ws, ws_floats, stream);
+  c.sq_part = sumsq_part; c.step_dev = step_dev; c.td = &td;
+  return mlp_backward_impl(c);
 }
 
 // Data-parallel buckets: layers layer_hi >= l >= layer_lo of the same backward (dW_l, dX_l) followed by the slab reduction of
@@ -1753,18 +1746,18 @@ extern "C" int pqlk_mlp_backward_layers(const PqlMlpDesc* d, const float* params
   PQLK_REQUIRE(layer_lo >= 0 && layer_lo <= layer_hi && layer_hi < d->n_layers, PQLK_E_RANGE);
   const bool any_td = acts_target || rew || done || loss_part, all_td = acts_target && rew && done && loss_part;
   PQLK_REQUIRE(any_td == all_td, PQLK_E_NULL);
+  BwdCall c = bwd_call(d, params, x, ldx, b, acts, grads, splits, ws, ws_floats, stream);
+  c.ranged = true; c.l_hi = layer_hi; c.l_lo = layer_lo;
+  TdHead td = {};
   if (all_td && layer_hi == d->n_layers - 1) {
     PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
-    int64_t q_off, q_ld;
-    rc = pqlk_mlp_act_offset(d, b, 0, d->n_layers - 1, &q_off, &q_ld);
-    if (rc) return rc;
-    const TdHead td = {acts_target + q_off, rew, done, gamma_n, loss_part};
-    return mlp_backward_impl(d, params, x, ldx, b, acts, nullptr, grads, splits, nullptr, 0, 0, 0, nullptr, 0, ws, ws_floats, nullptr,
-                             nullptr, stream, &td, layer_hi, layer_lo);
+    td = {acts_target + mlp_geom(d, b).a_off[d->n_layers - 1], rew, done, gamma_n, loss_part};
+    c.td = &td;
+  } else {
+    PQLK_REQUIRE(all_td || dy || layer_hi < d->n_layers - 1, PQLK_E_NULL);
+    c.dy = dy;
   }
-  PQLK_REQUIRE(all_td || dy || layer_hi < d->n_layers - 1, PQLK_E_NULL);
-  return mlp_backward_impl(d, params, x, ldx, b, acts, dy, grads, splits, nullptr, 0, 0, 0, nullptr, 0, ws, ws_floats, nullptr, nullptr,
-                           stream, nullptr, layer_hi, layer_lo);
+  return mlp_backward_impl(c);
 }
 
 // ---- the same step with the head's backward inside the critic's fused FORWARD launch (fused.h, fused_head's TD part): the
@@ -1774,7 +1767,7 @@ extern "C" int pqlk_mlp_backward_layers(const PqlMlpDesc* d, const float* params
 static int64_t td_forward_tiles(const PqlMlpDesc* d, int64_t b) {
   int buf_ld = 0;
   const int L = d->n_layers;
-  if (b <= 0 || !fusable(d, &buf_ld) || !head_fusable(d) || getenv("PQLK_NO_FUSED_HEAD")) return 0;
+  if (b <= 0 || !fused_with_head(d, &buf_ld)) return 0;
   if (d->n_nets != 2 || d->dims[L] != 1 || !head_is_fused(d)) return 0;
   if (buf_ld - d->dims[L - 1] < 256 || (int64_t)(L - 1) * (buf_ld - 4) < 128) return 0;
   const int R = fused_rows(d, buf_ld, b);
@@ -1788,30 +1781,25 @@ extern "C" int32_t pqlk_td_forward_loss_parts(const PqlMlpDesc* d, int64_t b) {
 
 extern "C" int pqlk_mlp_forward_td(const PqlMlpDesc* d, const float* params, const float* packed, const float* x, int64_t ldx,
                                    int64_t b, float* acts, const float* acts_target, const float* rew, const float* done,
-                                   float gamma_n, float* loss_part, float* bwd_ws, int64_t bwd_ws_floats, int32_t splits,
+                                   float gamma_n, float* loss_part, float* bwd_ws_p, int64_t bwd_ws_floats, int32_t splits,
                                    pqlk_stream_t stream) {
   int rc = desc_ok(d);
   if (rc) return rc;
-  PQLK_REQUIRE(params && packed && x && acts && acts_target && rew && done && loss_part && bwd_ws, PQLK_E_NULL);
+  PQLK_REQUIRE(params && packed && x && acts && acts_target && rew && done && loss_part && bwd_ws_p, PQLK_E_NULL);
   PQLK_REQUIRE(b > 0 && b < (1LL << 30), PQLK_E_SHAPE);
   PQLK_REQUIRE(ldx % 32 == 0 && ldx >= pqlk_ld(d->dims[0]), PQLK_E_ALIGN);
-  PQLK_REQUIRE(pqlk_aligned16(params) && pqlk_aligned16(packed) && pqlk_aligned16(x) && pqlk_aligned16(acts) && pqlk_aligned16(bwd_ws),
+  PQLK_REQUIRE(pqlk_aligned16(params) && pqlk_aligned16(packed) && pqlk_aligned16(x) && pqlk_aligned16(acts) && pqlk_aligned16(bwd_ws_p),
                PQLK_E_ALIGN);
   PQLK_REQUIRE(td_forward_tiles(d, b) > 0, PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(splits >= 1 && splits <= 64, PQLK_E_SHAPE);
-  PQLK_REQUIRE(bwd_ws_floats >= pqlk_mlp_bwd_ws_floats(d, b, splits), PQLK_E_WORKSPACE);
-  const int L = d->n_layers;
-  int64_t q_off, q_ld;
-  rc = pqlk_mlp_act_offset(d, b, 0, L - 1, &q_off, &q_ld);
-  if (rc) return rc;
+  const MlpGeom g = mlp_geom(d, b);
+  const BwdWs w = bwd_ws(g, splits);   // of the pqlk_mlp_backward_td_tail call that follows
+  PQLK_REQUIRE(bwd_ws_floats >= w.total, PQLK_E_WORKSPACE);
   FusedHead head = {};
   head.n = 1; head.epi = PQLK_ACT_NONE;
-  head.td_qt = acts_target + q_off; head.td_rew = rew; head.td_done = done; head.td_gamma_n = gamma_n;
-  // the workspace layout of mlp_backward_impl: two dZ buffers, the split slabs, the head's partials
-  head.td_dz = bwd_ws;
-  head.td_head_part = bwd_ws + 2 * (int64_t)d->n_nets * b * max_hidden_ld(d) + (int64_t)splits * pqlk_mlp_param_floats(d);
-  head.td_loss_part = loss_part;
-  return launch_fused_hidden(d, params, packed, x, ldx, b, acts, 1, pqlk_s(stream), &head);
+  head.td_qt = acts_target + g.a_off[g.L - 1]; head.td_rew = rew; head.td_done = done; head.td_gamma_n = gamma_n;
+  head.td_dz = bwd_ws_p + w.dz[0]; head.td_head_part = bwd_ws_p + w.head_part; head.td_loss_part = loss_part;
+  return launch_fused_hidden(g, params, packed, x, ldx, acts, 1, pqlk_s(stream), &head);
 }
 
 extern "C" int pqlk_mlp_backward_td_tail(const PqlMlpDesc* d, const float* params, const float* x, int64_t ldx, int64_t b,
@@ -1823,8 +1811,9 @@ extern "C" int pqlk_mlp_backward_td_tail(const PqlMlpDesc* d, const float* param
   PQLK_REQUIRE((sumsq_part == nullptr) == (step_dev == nullptr), PQLK_E_NULL);
   const int64_t tiles = td_forward_tiles(d, b);
   PQLK_REQUIRE(tiles > 0, PQLK_E_UNSUPPORTED);
-  return mlp_backward_impl(d, params, x, ldx, b, acts, nullptr, grads, splits, nullptr, 0, 0, 0, nullptr, 0, ws, ws_floats, sumsq_part,
-                           step_dev, stream, nullptr, -1, 0, (int)tiles);
+  BwdCall c = bwd_call(d, params, x, ldx, b, acts, grads, splits, ws, ws_floats, stream);
+  c.sq_part = sumsq_part; c.step_dev = step_dev; c.head_done = (int)tiles;
+  return mlp_backward_impl(c);
 }
 
 extern "C" int32_t pqlk_td_head_loss_parts(const PqlMlpDesc* d, int64_t b) {
@@ -1841,6 +1830,8 @@ extern "C" int pqlk_mlp_backward_norm(const PqlMlpDesc* d, const float* params, 
                                       int64_t ld_tanh, float* ws, int64_t ws_floats, float* sumsq_part, int32_t* step_dev,
                                       pqlk_stream_t stream) {
   PQLK_REQUIRE(grads && sumsq_part && step_dev, PQLK_E_NULL);
-  return mlp_backward_impl(d, params, x, ldx, b, acts, dy, grads, splits, dx, ld_dx, dx_col0, dx_cols, dx_tanh_of, ld_tanh, ws,
-                           ws_floats, sumsq_part, step_dev, stream);
+  BwdCall c = bwd_call(d, params, x, ldx, b, acts, grads, splits, ws, ws_floats, stream);
+  c.dy = dy; c.dx = dx; c.ld_dx = ld_dx; c.dx_col0 = dx_col0; c.dx_cols = dx_cols; c.dx_tanh_of = dx_tanh_of; c.ld_tanh = ld_tanh;
+  c.sq_part = sumsq_part; c.step_dev = step_dev;
+  return mlp_backward_impl(c);
 }

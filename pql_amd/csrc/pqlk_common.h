@@ -26,6 +26,16 @@ static inline int64_t pqlk_round_up(int64_t x, int64_t m) { return (x + m - 1) /
 static inline hipStream_t pqlk_s(pqlk_stream_t s) { return (hipStream_t)s; }
 static inline bool pqlk_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// PQLK_OK, or the error code every entry point that takes a PqlMlpDesc returns for a malformed one
+static inline int desc_ok(const PqlMlpDesc* d) {
+  if (!d) return PQLK_E_NULL;
+  if (d->n_layers < 1 || d->n_layers > PQLK_MAX_LAYERS) return PQLK_E_SHAPE;
+  if (d->n_nets < 1 || d->n_nets > 2) return PQLK_E_UNSUPPORTED;
+  for (int i = 0; i <= d->n_layers; ++i)
+    if (d->dims[i] <= 0) return PQLK_E_SHAPE;
+  return PQLK_OK;
+}
+
 // Record layout shared by the replay ring and the n-step window: every field starts on a 16-B
 // boundary so a record can be moved with dwordx4 accesses whatever O and A are.
 //   [ obs (O) pad4 | next_obs (O) pad4 | action (A) pad4 | reward, done, 0, 0 | zero pad to 32 floats ]

@@ -106,7 +106,7 @@ def skinny_dx_blocks(m):
 
 
 def head_is_fused(dims):
-    """gemm.hip:1230-1233."""
+    """gemm.hip, head_is_fused (head_bwd_kind == HEAD_FUSED)."""
     L = len(dims) - 1
     return L >= 2 and skinny_bwd_ok(dims[L], ld(dims[L - 1])) and skinny_bwd_fused_ok(dims[L], ld(dims[L - 1]))
 
@@ -166,9 +166,9 @@ def dx_slice_depth(groups, K):
     return 16 if K8 % 16 == 0 else 4 if K8 % 4 == 0 else 1
 
 
-# ---------------------------------------------------------------- mirror: pqlk_mlp_backward (gemm.hip:1252-1414)
+# ---------------------------------------------------------------- mirror: pqlk_mlp_backward (gemm.hip, mlp_backward_impl)
 def rows_per_split(B, splits):
-    """gemm.hip:1336, :1359."""
+    """gemm.hip, bwd_head and bwd_layer_dw."""
     return round_up(cdiv(B, splits), KT_MAX)
 
 
@@ -184,93 +184,93 @@ def backward_plan(dims, nets, B, splits, want_grads, dx_form, ldx=None):
     L = len(dims) - 1
     ldx = ld(dims[0]) if ldx is None else ldx
     plan, head_parts = [], False
-    for l in range(L - 1, -1, -1):                                 # :1295
-        ld_out, ld_in = ld(dims[l + 1]), ld(dims[l])               # :1301-1302
-        in_ld = ldx if l == 0 else ld_in                           # :1305-1311
-        skinny = l == L - 1 and skinny_bwd_ok(dims[l + 1], ld_in) and in_ld >= ld_in   # :1312
+    for l in range(L - 1, -1, -1):                                 # mlp_backward_impl
+        ld_out, ld_in = ld(dims[l + 1]), ld(dims[l])               # MlpGeom::ld
+        in_ld = ldx if l == 0 else ld_in                           # bwd_layer_io
+        skinny = l == L - 1 and skinny_bwd_ok(dims[l + 1], ld_in) and in_ld >= ld_in   # bwd_head
         if skinny:
-            if want_grads and head_is_fused(dims):                 # :1318
+            if want_grads and head_is_fused(dims):                 # HEAD_FUSED
                 plan.append(("skinny_bwd",) + skinny_bwd_kernel(dims[l + 1], ld_in) + (skinny_bwd_rows(B, nets),))
                 head_parts = True
-                continue                                           # :1332
-            if want_grads:                                         # :1334
+                continue
+            if want_grads:                                         # HEAD_SKINNY
                 plan.append(("skinny_dw", skinny_dw_cls(ld_in, splits, nets)))
-            if l > 0:                                              # :1340
+            if l > 0:
                 plan.append(("skinny_dx",))
                 continue
-            if dx_form is None:                                    # :1348
+            if dx_form is None:                                    # bwd_layer_dx
                 continue
-        if want_grads and not skinny:                              # :1350
+        if want_grads and not skinny:                              # bwd_layer_dw
             plan.append(gemm_launch("dW", "NONE", dims[l + 1], ld_in, B, ld_out, in_ld, ld_out, nets * splits, splits=splits,
                                     rows_per_split=rows_per_split(B, splits)))
-        if l > 0:                                                  # :1366
+        if l > 0:                                                  # bwd_layer_dx
             plan.append(gemm_launch("dX", "DELU", B, dims[l], dims[l + 1], ld_out, ld_in, ld_in, nets))
-        elif dx_form is not None:                                  # :1378
+        elif dx_form is not None:
             if dx_form == "full":
                 plan.append(gemm_launch("dX", "NONE", B, dims[0], dims[1], ld_out, ld_in, ld_in, 1))
             else:
                 _, col0, cols = dx_form
-                if dx_slice_ok(nets, dims[1], cols, ld_out):       # :1391
+                if dx_slice_ok(nets, dims[1], cols, ld_out):
                     plan.append(("dx_slice", dx_slice_depth(nets, dims[1]), nets))
                 else:
                     plan.append(gemm_launch("dX", "DTANH_SLICE", B, dims[0], dims[1], ld_out, ld_in, ld_in, 1, col0=col0, ncol=cols))
-    if want_grads:                                                 # :1396
+    if want_grads:                                                 # k_reduce_slabs
         plan.append(("reduce", head_parts))
     return plan
 
 
 # ---------------------------------------------------------------- mirror: the host-side sizes
 def net_stride(dims):
-    """gemm.hip:868-873."""
+    """gemm.hip, mlp_geom (pqlk_mlp_net_stride)."""
     return sum(dims[l + 1] * ld(dims[l]) + ld(dims[l + 1]) for l in range(len(dims) - 1))
 
 
 def layer_offsets(dims, layer):
-    """gemm.hip:876-885: (w_off, b_off) inside one net's block."""
+    """gemm.hip, mlp_geom (pqlk_mlp_layer_offsets): (w_off, b_off) inside one net's block."""
     n = sum(dims[l + 1] * ld(dims[l]) + ld(dims[l + 1]) for l in range(layer))
     return n, n + dims[layer + 1] * ld(dims[layer])
 
 
 def acts_floats(dims, nets, B):
-    """gemm.hip:887-892."""
+    """gemm.hip, mlp_geom (pqlk_mlp_acts_floats)."""
     return sum(nets * B * ld(dims[l + 1]) for l in range(len(dims) - 1))
 
 
 def act_offset(dims, nets, B, net, layer):
-    """gemm.hip:894-904: (offset, row stride) of one net's block of one layer's activations in the stash."""
+    """gemm.hip, mlp_geom (pqlk_mlp_act_offset): (offset, ld) of one net's block of one layer's activations in the stash."""
     return sum(nets * B * ld(dims[l + 1]) for l in range(layer)) + net * B * ld(dims[layer + 1]), ld(dims[layer + 1])
 
 
 def max_hidden_ld(dims):
-    """gemm.hip:906-910."""
+    """gemm.hip, mlp_geom (MlpGeom::max_hidden_ld)."""
     return max(ld(d) for d in dims[1:])
 
 
 def head_part_floats(dims, nets, B):
-    """gemm.hip:912-919."""
+    """gemm.hip, bwd_ws (BwdWs::head_part_floats)."""
     hf = dims[-1] * ld(dims[-2]) + ld(dims[-1])
     return max(skinny_bwd_blocks(B, nets), 2 * round_up(B, 128) // 32) * nets * hf
 
 
 def bwd_ws_floats(dims, nets, B, splits):
-    """gemm.hip:921-924 (pqlk_mlp_bwd_ws_floats)."""
+    """gemm.hip, bwd_ws (pqlk_mlp_bwd_ws_floats)."""
     return 2 * nets * B * max_hidden_ld(dims) + splits * net_stride(dims) * nets + head_part_floats(dims, nets, B)
 
 
 def bwd_ws_required(dims, nets, B, splits, want_grads):
-    """gemm.hip:1275-1277: what the call itself insists on (without grads neither slabs nor head partials)."""
+    """gemm.hip, bwd_ws as mlp_backward_impl asks for it: what the call itself insists on (without grads neither slabs nor head partials)."""
     return bwd_ws_floats(dims, nets, B, splits) if want_grads else 2 * nets * B * max_hidden_ld(dims)
 
 
 def norm_parts(dims, nets):
-    """gemm.hip:1226-1246 (pqlk_mlp_norm_parts): the head's fold blocks exist when head_is_fused."""
+    """gemm.hip, pqlk_mlp_norm_parts (reduce_main_blocks, head_fold_blocks): the head's fold blocks exist when head_is_fused."""
     main = min(max(cdiv(net_stride(dims) * nets // 4, 256), 1), 1024)
     hq = (dims[-1] * ld(dims[-2]) + ld(dims[-1])) // 4 * nets
     return main + (cdiv(hq, 4) if head_is_fused(dims) else 0)
 
 
 def minnet_ok(dims, nets, dx_cols):
-    """gemm.hip:1421-1430 with dx and dx_tanh_of given."""
+    """gemm.hip, minnet_ok (compact_chain_ok) with dx and dx_tanh_of given."""
     L = len(dims) - 1
     if nets != 2 or L < 3 or dims[L] != 1 or dx_cols > 32 or not skinny_bwd_ok(1, ld(dims[L - 1])):
         return False
@@ -278,7 +278,7 @@ def minnet_ok(dims, nets, dx_cols):
 
 
 def dpg_ws_floats(dims, nets, B):
-    """gemm.hip:1431, :1448-1453 (pqlk_dpg_backward_ws_floats)."""
+    """gemm.hip, compact_ws and pqlk_dpg_backward_ws_floats."""
     cap = 2 * round_up(B, MN_TILE)
     return max(bwd_ws_floats(dims, nets, B, 1), 2 * cap * max_hidden_ld(dims) + 2 * cap + 64)
 

@@ -21,7 +21,7 @@ ACTS = (ACT_NONE, ACT_TANH, ACT_TANH_NOISE)
 NOISE_STD, NOISE_CLIP = 0.8, 0.2
 
 # ---------------------------------------------------------------- the library's constants
-LDS_BYTES = 160 * 1024          # gemm.hip:944, :1011
+LDS_BYTES = 160 * 1024          # gemm.hip, fusable and fused_rows
 FUSED_NW = 8                    # fused.h:70, waves per block of the fused forward
 SKINNY_MAX_K = 1024             # skinny.h:10
 
@@ -33,43 +33,43 @@ def ld(cols):
 
 # ---------------------------------------------------------------- mirror of the forward's dispatch
 def fused_lds_bytes(dims, buf_ld, R):
-    """gemm.hip:930-934 (fused_lds_bytes)."""
+    """gemm.hip, fused_lds_bytes."""
     acts = (32 * R * buf_ld + (len(dims) - 2) * (buf_ld - 4)) * 4
     head = 8 * R * 16 * 64 * 4
     return max(acts, head)
 
 
 def fusable(dims):
-    """gemm.hip:936-947 (fusable): the LDS row stride buf_ld of the fused hidden stack, or 0 when it cannot run."""
+    """gemm.hip, fusable: the LDS row stride buf_ld of the fused hidden stack, or 0 when it cannot run."""
     L = len(dims) - 1
-    if L < 2:                                                      # :937
+    if L < 2:
         return 0
-    w = ld(dims[0])                                                # :938
+    w = ld(dims[0])
     for l in range(1, L):
-        if dims[l] % 32 != 0 or dims[l] > 1024:                    # :940
+        if dims[l] % 32 != 0 or dims[l] > 1024:
             return 0
         w = max(w, dims[l])
-    buf_ld = w + 4                                                 # :943
-    return buf_ld if fused_lds_bytes(dims, buf_ld, 1) <= LDS_BYTES else 0   # :944
+    buf_ld = w + 4
+    return buf_ld if fused_lds_bytes(dims, buf_ld, 1) <= LDS_BYTES else 0
 
 
 def head_fusable(dims):
-    """gemm.hip:1000-1002 (head_fusable)."""
+    """gemm.hip, head_fusable."""
     return len(dims) - 1 >= 2 and dims[-1] <= 32 and dims[-2] % 32 == 0
 
 
 def fused_wide(dims):
-    """gemm.hip:1057-1058: a hidden layer wider than 512 selects k_mlp_fwd_fused<1, 4> (:1078)."""
+    """gemm.hip, launch_fused_hidden (`wide`): a hidden layer wider than 512 selects k_mlp_fwd_fused<1, 4>."""
     return any(d > 512 for d in dims[1:-1])
 
 
 def fused_rows(dims, nets, buf_ld, B):
-    """gemm.hip:1007-1020 (fused_rows) without the PQLK_FUSED_ROWS override: 32-row tiles per block."""
+    """gemm.hip, fused_rows without the PQLK_FUSED_ROWS override: 32-row tiles per block."""
     R = 1
-    if not fused_wide(dims) and fused_lds_bytes(dims, buf_ld, 2) <= LDS_BYTES:          # :1011
-        b1, b2 = (B + 31) // 32 * nets, (B + 63) // 64 * nets                           # :1012
-        c1, c2 = 1.15 * ((b1 + 255) // 256), 2.0 * ((b2 + 255) // 256)                  # :1013
-        if c2 <= c1:                                                                    # :1014
+    if not fused_wide(dims) and fused_lds_bytes(dims, buf_ld, 2) <= LDS_BYTES:
+        b1, b2 = (B + 31) // 32 * nets, (B + 63) // 64 * nets
+        c1, c2 = 1.15 * ((b1 + 255) // 256), 2.0 * ((b2 + 255) // 256)
+        if c2 <= c1:
             R = 2
     return R
 
@@ -99,26 +99,26 @@ def gemm_tile(M, ncols_store, gz):
 
 
 def hidden_path(dims, packed):
-    """gemm.hip:1104: "fused" (one launch, fused.h), "gemm" (one k_gemm<FWD, EPI_ELU> launch per hidden layer), or None."""
+    """pqlk_mlp_forward: "fused" (one launch, fused.h), "gemm" (one k_gemm<FWD, EPI_ELU> launch per hidden layer), or None."""
     if len(dims) == 2:
         return None
     return "fused" if packed and fusable(dims) else "gemm"
 
 
 def head_path(dims, nets, packed, B):
-    """The output layer's kernel in pqlk_mlp_forward (gemm.hip:1085-1159; PQLK_NO_FUSED_HEAD unset):
+    """The output layer's kernel in pqlk_mlp_forward (gemm.hip; PQLK_NO_FUSED_HEAD unset):
     ("fused", R, wide) | ("skinny",) | ("narrow", NT, D) | ("gemm", 64 | 128)."""
     N = dims[-1]
     buf_ld = fusable(dims)
-    if packed and buf_ld and head_fusable(dims):                   # :1104, :1107
-        return ("fused", fused_rows(dims, nets, buf_ld, B), fused_wide(dims))   # :1075-1080
-    K = ld(dims[-2])                                               # :1130
-    lda = ldb = K                                                  # :1121 (x with ldx = pqlk_ld(in)), :1125, :1127
-    if skinny_fwd_ok(N, K):                                        # :1140
+    if packed and buf_ld and head_fusable(dims):                   # fused_with_head
+        return ("fused", fused_rows(dims, nets, buf_ld, B), fused_wide(dims))   # launch_fused_hidden
+    K = ld(dims[-2])                                               # MlpGeom::ld
+    lda = ldb = K                                                  # x with ldx = pqlk_ld(in), else the stash; the arena
+    if skinny_fwd_ok(N, K):
         return ("skinny",)
-    if narrow_fwd_ok(N, K, lda, ldb):                              # :1151
+    if narrow_fwd_ok(N, K, lda, ldb):
         return ("narrow",) + narrow_kernel(N, K)
-    return ("gemm", gemm_tile(B, ld(N), nets))                     # :1154, ncols_store = pqlk_ld(out) :1131
+    return ("gemm", gemm_tile(B, ld(N), nets))                     # launch_auto<MODE_FWD>, ncols_store = pqlk_ld(out)
 
 
 def narrow_vec(N, place):
