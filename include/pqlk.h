@@ -474,6 +474,18 @@ int pqlk_per_sample(const float* tree, int64_t capacity, const float* u, int64_t
 int pqlk_per_weights(const float* tree, int64_t capacity, const int64_t* idx, int64_t b, int64_t n_valid, float beta,
                      float* w_out, float* wmax_out, pqlk_stream_t stream);
 
+/* pqlk_per_sample and pqlk_per_weights for `steps` batches of b in ONE launch, all on the tree as it stands (the PQL V-learner's
+ * run of steps between two hand-offs: the distribution is frozen for the run).  r: steps * b integers in [0, 2^24)
+ * (torch.randint(1 << 24) draws).  Step s, sample k, one wave: u = (float)r[s b + k] * 2^-24 (exact); then pqlk_per_sample's walk
+ * for stratum k of b -- seg = total / (float)b, t = ((float)k + u) * seg, the same prefix, ballot and choice of child -- and
+ * pqlk_per_weights' w = (((float)n_valid * leaf) / total) ^ (-beta) on the leaf value the wave loaded at level 0, with the same
+ * total and the same x ^ e.  idx_out, w_out: steps * b entries, step-major.  wmax_out: `steps` floats, wmax_out[s] = the maximum
+ * of step s's b weights (integer atomic max on the bit patterns; steps * 4 bytes are zeroed on the stream first).  Bit-equal, on
+ * one device, to `steps` pairs of pqlk_per_sample (given u) and pqlk_per_weights.  Errors, before any launch: PQLK_E_NULL a NULL
+ * pointer; PQLK_E_SHAPE capacity, b, steps or n_valid <= 0, or steps > 65535; PQLK_E_RANGE n_valid > capacity. */
+int pqlk_per_sample_steps(const float* tree, int64_t capacity, const int64_t* r, int64_t b, int64_t steps, int64_t n_valid,
+                          float beta, int64_t* idx_out, float* w_out, float* wmax_out, pqlk_stream_t stream);
+
 /* pqlk_td_mse_loss with the per-sample weight wh_i = w[i] / wmax[0] (Schaul et al. algorithm 1 lines 10-12):
  * loss = mean(wh (q1-y)^2) + mean(wh (q2-y)^2), dy = ((2/B) wh) (q-y), abs_td_out[i] = max(|q1-y|, |q2-y|) (the new priority,
  * before eps and ^alpha).  Grid, partials, fold order and loss-ring semantics are pqlk_td_mse_loss's; with every w and wmax 1.0

@@ -98,6 +98,7 @@ PROTOTYPES = {
     "pqlk_per_rebuild": (C.c_int, [_P, _I64, _P]),
     "pqlk_per_sample": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
     "pqlk_per_weights": (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _P, _P, _P]),
+    "pqlk_per_sample_steps": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _F, _P, _P, _P, _P]),
     "pqlk_td_mse_loss_per": (C.c_int, [_P, _P, _I64, _P, _P, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "pqlk_per_update": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _F, _F, _P]),
     "pqlk_clip_adamw_polyak": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),

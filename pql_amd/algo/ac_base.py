@@ -12,19 +12,11 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, make_actor, make_critic
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
-from pql_amd.replay.prioritized_replay import per_cfg
+from pql_amd.replay.prioritized_replay import per_beta, per_cfg  # noqa: F401  (per_beta: imported from here by its users)
 from pql_amd.replay.simple_replay import cfg_obs_dtype
-
-
-def per_beta(beta0, beta_iters, calls):
-    """The importance-sampling exponent of prioritized replay after `calls` calls of `update_net`: linear from beta0 to 1 over
-    `beta_iters` calls, exactly 1.0 from there on."""
-    if calls >= beta_iters:
-        return 1.0
-    return float(beta0) + (1.0 - float(beta0)) * (calls / float(beta_iters))
 
 
 class ActorCriticBase(PQLActor):
@@ -32,6 +24,7 @@ class ActorCriticBase(PQLActor):
 
     def __init__(self, env, cfg):
         check_critic_class(cfg)   # before anything is allocated
+        check_per_refresh(cfg, f"algo={cfg.algo.name}")
         cfg.algo.v_learner_gpu = cfg.algo.get("v_learner_gpu", 0) or 0
         cfg.algo.p_learner_gpu = cfg.algo.get("p_learner_gpu", 0) or 0
         super().__init__(env, cfg)

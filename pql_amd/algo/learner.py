@@ -19,6 +19,7 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.models import model_name_to_path
 from pql_amd.models.mlp import PackedWeights, check_num_atoms
+from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
 from pql_amd.utils import rng as R
@@ -211,15 +212,25 @@ def pump(learner, stop_event=None, max_in_flight=2):
         pending.popleft().synchronize()
 
 
+def check_per_refresh(cfg, where):
+    """The synchronous baselines sample from the live tree every step: `algo.per.refresh=run` is refused, naming the key."""
+    per = per_cfg(cfg.algo)
+    if per is not None and per_refresh(per) != "step":
+        raise ValueError(f"algo.per.refresh=run cannot run in {where}: it samples from the live tree and writes priorities back every step "
+                         f"(algo.per.refresh=step); run is the PQL V-learner's mode (scripts/train_pql.py)")
+
+
 def check_critic_class(cfg, fused_learner=None):
-    """Refusals that follow from `algo.cri_class` (and, for the fused learners, `algo.per.enabled`) alone, raised before anything is allocated.  fused_learner: the name of a component
-    whose launch sequences are built on the fused MLP kernels (scripts/train_pql.py, PQLVLearner, PQLPLearner)."""
+    """Refusals that follow from `algo.cri_class` (and, for the fused learners, `algo.per.enabled` with `algo.per.refresh`) alone, raised
+    before anything is allocated.  fused_learner: the name of a component whose launch sequences are built on the fused MLP kernels
+    (scripts/train_pql.py, PQLVLearner, PQLPLearner)."""
     algo = cfg.algo
-    per = _cfg_get(algo, "per")
-    if fused_learner is not None and per is not None and bool(per.get("enabled") or False):
+    per = per_cfg(algo)
+    if fused_learner is not None and per is not None and per_refresh(per) != "run":
         raise ValueError(f"algo.per.enabled=True cannot run in {fused_learner}: the PQL learners gather batches ahead and replay steps as one "
                          f"hipGraph, which assumes a sampling distribution that does not change between hand-offs; prioritized replay works "
-                         f"in scripts/train_baselines.py (algo=ddpg_algo / sac_algo / crossq_algo)")
+                         f"in scripts/train_baselines.py (algo=ddpg_algo / sac_algo / crossq_algo), and in the PQL V-learner with "
+                         f"algo.per.refresh=run (the distribution frozen for each run of prefetched steps)")
     cri = str(_cfg_get(algo, "cri_class"))
     if cri.endswith("DoubleQLayerNorm"):
         if _cfg_get(algo, "distl", False):
@@ -417,6 +428,10 @@ class Learner:
         if self._ahead is not None:
             self._ahead.invalidate()
 
+    def _after_step(self, ws, slot):
+        """Called once a step (or, from `learn_many`, a run of steps ending with `slot`) is enqueued; slot None = a per-step or
+        injected one.  The V-learner's prioritized replay keeps count of the |TD| slabs that wait for their write-back."""
+
     def _check_ahead(self):
         if self._ahead is not None and self._ahead.valid and self._ahead_stamp != self._data_stamp():
             self._drop_ahead()
@@ -492,6 +507,7 @@ class Learner:
             ws = self._workspace(B)
             if injected is not None:
                 self._learn_injected(ws, injected, home)
+                self._after_step(ws, None)
             elif self._ahead is not None and self._bound() < DRAWS_AHEAD_BOUND:
                 # draws + input tiles of the next K steps come from one launch pair (`_prefetch`), the step itself has no RNG
                 # and no gather launch left; one hipGraph per slot (the tiles' addresses are baked in)
@@ -507,6 +523,7 @@ class Learner:
                     self._replay(ws, self._slot_graphs[slot])
                 else:
                     self._step(ws, slot)
+                self._after_step(ws, slot)
             elif self.use_graph:
                 key = (B, self._bound() if self._graph_rng else 0, id(self._partner()), self._norm_key())
                 if self._graph is None or self._graph_key != key:
@@ -515,8 +532,10 @@ class Learner:
                 if not self._graph_rng:   # draws in front of the graph (see __init__)
                     self._draws(ws)
                 self._replay(ws, self._graph)
+                self._after_step(ws, None)
             else:
                 self._draw_and_step(ws)
+                self._after_step(ws, None)
             self.update_count += 1   # under the lock: update() reads it together with the device loss ring (free-running threads)
         return self.sleep_time
 
@@ -550,6 +569,7 @@ class Learner:
                 for _ in range(n):
                     self._ahead.take()
                 self._run_graph.replay()
+                self._after_step(ws, n - 1)
                 self.update_count += n
                 return self.sleep_time
             if self._ahead is not None and self._ahead.valid == 0 and n < ws["K"] and self._bound() < DRAWS_AHEAD_BOUND:

@@ -24,6 +24,7 @@ from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _c
                                   check_critic_class, graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
                                 output_view)
+from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer, per_beta, per_cfg
 from pql_amd.replay.simple_replay import ReplayBuffer, cfg_obs_dtype
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
@@ -35,6 +36,19 @@ class PQLVLearner(Learner):
 
     def __init__(self, obs_dim, action_dim, cfg, process_group=None):
         check_critic_class(cfg, "PQLVLearner")
+        # algo.per.enabled=True with algo.per.refresh=run (anything else was refused above): prioritized replay whose distribution is
+        # frozen for each run of prefetched steps.  What it cannot be combined with is refused before anything is allocated.
+        self._per = per_cfg(cfg.algo)
+        self._per_pending = 0   # steps taken since the last write-back: rows [0, n) of the |TD| slabs wait for `flush_priorities`
+        if self._per is not None:
+            if _cfg_get(cfg.algo, "distl", False):
+                raise ValueError("algo.distl=True is not supported with algo.per.enabled=True (algo.per.refresh=run): there is no weighted C51 loss")
+            if process_group is not None:
+                raise ValueError("algo.per.enabled=True (algo.per.refresh=run) is single-GPU only: PQLVLearner was given a process group "
+                                 "(data parallel), and the ranks' sum trees would have to agree on the priorities")
+            if bool(_cfg_get(cfg.algo, "graph_rng", False)):
+                raise ValueError("algo.graph_rng=True is not supported with algo.per.enabled=True (algo.per.refresh=run): the sample launch takes "
+                                 "beta from the host and the rows in the ring, neither of which may be baked into a captured step")
         if not torch.cuda.is_available():
             raise L.PqlkError("PQLVLearner needs an MI355X (no CPU path)")
         device = torch.device(f"cuda:{int(cfg.algo.v_learner_gpu)}")
@@ -47,8 +61,11 @@ class PQLVLearner(Learner):
         self.pk_critic = PackedWeights(self.critic.layout, self.device) if self._fused else None
         self.pk_target = PackedWeights(self.critic.layout, self.device) if self._fused else None
         self._td_in_head = bool(_cfg_get(algo, "td_in_head", True))   # TD target + MSE inside the head's backward launch
-        self.memory = ReplayBuffer(capacity=int(algo.memory_size), obs_dim=self.obs_dim, action_dim=self.action_dim,
-                                   device=self.device, obs_dtype=cfg_obs_dtype(algo))
+        ring = dict(capacity=int(algo.memory_size), obs_dim=self.obs_dim, action_dim=self.action_dim, device=self.device,
+                    obs_dtype=cfg_obs_dtype(algo))
+        # (prioritized: `update()`'s add_to_buffer then gives new rows pmax^alpha, as in the baselines)
+        self.memory = ReplayBuffer(**ring) if self._per is None else PrioritizedReplayBuffer(alpha=float(self._per.alpha),
+                                                                                             eps=float(self._per.eps), **ring)
         self.sleep_time = 0
         # data parallel, algo.dp_buckets: "layer" = the gradient travels in per-layer buckets, each all-reduced as soon as its dW
         # slabs are summed, under the MFMA launches of the layers below (pql_amd/utils/dp.py); "one" = a single collective after
@@ -77,6 +94,7 @@ class PQLVLearner(Learner):
         value = str(value)
         if value not in ("float32", "bfloat16"):
             raise ValueError(f"algo.target_dtype must be float32 or bfloat16, got {value!r}")
+        self.flush_priorities()   # (the workspace, and with it the |TD| slabs, is rebuilt below)
         if value == "bfloat16":
             if not self._fused:
                 raise ValueError("algo.target_dtype=bfloat16 needs the fused path (algo.fused=True)")
@@ -131,6 +149,7 @@ class PQLVLearner(Learner):
     def _workspace(self, B):
         if self._ws is not None and self._ws["B"] == B:
             return self._ws
+        self.flush_priorities()
         dev, f = self.device, dict(dtype=torch.float32, device=self.device)
         O, A = self.memory.ring.O, self.action_dim
         cl, al = self.critic.layout, self.actor.layout
@@ -154,6 +173,13 @@ class PQLVLearner(Learner):
         ws["done_all"] = torch.zeros((K, B), **f)
         ws["slots"] = [dict(x_sa=ws["x_sa_all"][k], xn_sa=ws["xn_sa_all"][k], rew=ws["rew_all"][k], done=ws["done_all"][k])
                        for k in range(K)]
+        if self._per is not None:
+            # prioritized replay: the rows, importance weights and their per-step maxima one sample launch leaves for the K steps of a
+            # run, and the |TD| each step leaves for the run's one write-back
+            ws["per_idx_all"] = torch.zeros((K, B), dtype=torch.int64, device=dev)
+            ws["w_all"], ws["wmax_all"], ws["abs_td_all"] = torch.zeros((K, B), **f), torch.zeros(K, **f), torch.zeros((K, B), **f)
+            for k, slot in enumerate(ws["slots"]):
+                slot.update(per_idx=ws["per_idx_all"][k], w=ws["w_all"][k], wmax=ws["wmax_all"][k:k + 1], abs_td=ws["abs_td_all"][k])
         ws.update(ws["slots"][0])
         ws["xn_obs"] = torch.zeros((B, ws["ld_o"]), **f)
         ws["idx"] = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -174,7 +200,8 @@ class PQLVLearner(Learner):
         ws["bwd"] = torch.empty(cl.bwd_ws_floats(B, ws["splits"]), **f)
         ws["scratch"] = torch.zeros(2048, **f)
         # scalar twin heads: TD target + MSE + dL/dQ are formed inside the head's backward pass (one launch less)
-        ws["td_parts"] = int(L.lib.pqlk_td_head_loss_parts(C.byref(cl.desc), B)) if (self._fold_loss and self._td_in_head
+        # (not with prioritized replay: the fused TD heads cannot weight rows, the step takes the separate weighted loss launch)
+        ws["td_parts"] = int(L.lib.pqlk_td_head_loss_parts(C.byref(cl.desc), B)) if (self._fold_loss and self._td_in_head and self._per is None
                                                                                       and not self.cfg.algo.distl) else 0
         # ... and with the fused forward the head's whole backward runs inside the critic's forward launch, off the activations still
         # in LDS: the head-backward launch and its second read of them disappear (algo.td_in_forward; not with gradient buckets)
@@ -225,8 +252,16 @@ class PQLVLearner(Learner):
         target actions -- the rest would be dropped unused at the next `update()`."""
         K, B = ws["K"], ws["B"]
         Kp = K if steps is None else max(1, min(K, int(steps)))
-        self._ahead.refill(self.memory.cur_capacity, Kp)
-        self._gather(ws, self._ahead.idx, Kp * B, ws["x_sa_all"], ws["xn_sa_all"], ws["rew_all"], ws["done_all"])
+        idx = self._ahead.idx
+        if self._per is not None:
+            # the run's rows come from the tree as it stands now, after the last run's |TD| went in: uniform draws in [0, 2^24) (the
+            # same randint consumption per step as the plain learner's) -> Kp stratified batches and their weights in one launch
+            self.flush_priorities()
+            self._ahead.refill(1 << 24, Kp)
+            idx = self._per_draw(ws, self._ahead.idx, Kp)
+        else:
+            self._ahead.refill(self.memory.cur_capacity, Kp)
+        self._gather(ws, idx, Kp * B, ws["x_sa_all"], ws["xn_sa_all"], ws["rew_all"], ws["done_all"])
         if ws["actor_ahead"]:   # a' = clamp(tanh(actor(s')) + clamp(0.8 N(0,1), +-0.2), +-1) of all K steps -> action columns of their tiles
             algo, O = self.cfg.algo, self.memory.ring.O
             xn = ws["xn_sa_all"].view(K * B, ws["ld_sa"])[: Kp * B]
@@ -238,6 +273,36 @@ class PQLVLearner(Learner):
                 mlp_forward_raw(self.actor.layout, self.actor.arena.data, xn, L.ACT_TANH_NOISE, draws,
                                 algo.noise.tgt_pol_std, algo.noise.tgt_pol_noise_bound, ws["a_out_all"], xn[:, O:], packed=self.pk_actor, stash_all=2)
         self._ahead_stamp = self._data_stamp()
+
+    def _per_draw(self, ws, r, steps):
+        """`steps` prioritized batches from the draws `r` (steps x B integers below 2^24) into the first slots' rows / weights; beta
+        is the schedule's value at this learner's step count, one value per launch (host side, outside every graph)."""
+        beta = per_beta(self._per.beta0, int(self._per.beta_iters), self.update_count)
+        self.memory.draw_steps(r, ws["B"], steps, beta, ws["per_idx_all"], ws["w_all"], ws["wmax_all"])
+        return ws["per_idx_all"]
+
+    def flush_priorities(self):
+        """Write the |TD| of the steps taken since the last write-back into the tree (one `pqlk_per_update` over their n x B rows: a
+        row drawn twice keeps the larger candidate), eagerly on this learner's stream.  Runs before the next sample launch, before the
+        ring insert of `update()` (a sampled row the insert overwrites must end with pmax^alpha, not with the old row's |TD|), when
+        what was prepared ahead is dropped, and before the state is saved."""
+        n, self._per_pending = self._per_pending, 0
+        if n > 0:
+            with torch.cuda.device(self.device), self._on_stream():
+                self.memory.update_priorities(self._ws["per_idx_all"][:n], self._ws["abs_td_all"][:n])
+
+    def _drop_ahead(self):
+        self.flush_priorities()
+        super()._drop_ahead()
+
+    def _after_step(self, ws, slot):
+        if self._per is None:
+            return
+        if slot is not None:   # a slot of the run: its |TD| waits with the run's others
+            self._per_pending = slot + 1
+        else:                  # a per-step or injected step: sampled from the live tree, written back at once
+            self._per_pending = 1
+            self.flush_priorities()
 
     def _step_kernels(self, ws, idx, draw, upto_backward=False, tiles=None, part=None):
         """The launch sequence of one critic gradient step; everything asynchronous on the current stream.
@@ -253,6 +318,8 @@ class PQLVLearner(Learner):
         if tiles is None:
             tiles = ws["slots"][0]
             if part in (None, 0):
+                if self._per is not None:   # (per-step path: `_draws` / `_learn_injected` left the rows in slot 0)
+                    idx = tiles["per_idx"]
                 self._gather(ws, idx, B, tiles["x_sa"], tiles["xn_sa"], tiles["rew"], tiles["done"])
         ws = dict(ws, **tiles)   # the step below reads its inputs from `tiles`
         al, cl = self.actor.layout, self.critic.layout
@@ -294,6 +361,10 @@ class PQLVLearner(Learner):
                                                     L.ptr(ws["done"]), L.ptr(self.critic.z_atoms), gamma_n, float(algo.v_min),
                                                     float(algo.v_max), B, L.ptr(ws["dy"]), loss_out, L.ptr(self.opt.step),
                                                     LOSS_RING, None, L.ptr(ws["scratch"]), st))
+                elif self._per is not None:   # importance weights on the loss and its gradient; |TD| -> the slot's slab
+                    L.check(L.lib.pqlk_td_mse_loss_per(L.ptr(q), L.ptr(qt), cl.ld_out, L.ptr(ws["rew"]), L.ptr(ws["done"]), gamma_n, B,
+                                                       L.ptr(ws["dy"]), loss_out, L.ptr(self.opt.step), LOSS_RING, L.ptr(ws["scratch"]),
+                                                       L.ptr(ws["w"]), L.ptr(ws["wmax"]), L.ptr(ws["abs_td"]), st))
                 else:
                     L.check(L.lib.pqlk_td_mse_loss(L.ptr(q), L.ptr(qt), cl.ld_out, L.ptr(ws["rew"]), L.ptr(ws["done"]), gamma_n, B,
                                                    L.ptr(ws["dy"]), loss_out, L.ptr(self.opt.step), LOSS_RING,
@@ -361,8 +432,14 @@ class PQLVLearner(Learner):
     def _draws(self, ws):
         # RNG consumption order of the reference: one randint(cur_capacity,(B,)) then one
         # N(0,1) draw of shape (B, A) on the learner's device generator.
-        torch.randint(self.memory.cur_capacity, (ws["B"],), generator=self.gen, out=ws["idx"])   # straight into the workspace: no copy launch
+        # (prioritized: the same one randint, over [0, 2^24), turned into a stratified batch from the live tree)
+        torch.randint(self._randint_bound(), (ws["B"],), generator=self.gen, out=ws["idx"])   # straight into the workspace: no copy launch
         ws["draw"].normal_(generator=self.gen)
+        if self._per is not None:
+            self._per_draw(ws, ws["idx"], 1)
+
+    def _randint_bound(self):
+        return self.memory.cur_capacity if self._per is None else 1 << 24
 
     def _step(self, ws, slot=None, upto_backward=False, part=None):
         """The step on the draws / tiles `_prefetch` left in `slot`; None = on the per-step draws in ws["idx"] / ws["draw"]."""
@@ -382,13 +459,28 @@ class PQLVLearner(Learner):
             self._drop_ahead()   # the generator is about to be used directly: what was drawn ahead is off the stream now
         if indices is not None:
             self._inject(ws["idx"], indices, home)
+            if self._per is not None:   # injected rows: their weights at this step's beta
+                ws["per_idx_all"][0].copy_(ws["idx"])
+                self.memory.beta = per_beta(self._per.beta0, int(self._per.beta_iters), self.update_count)
+                w, wmax = self.memory.weights_for(ws["per_idx_all"][0])
+                ws["w_all"][0].copy_(w)
+                ws["wmax_all"][:1].copy_(wmax)
         else:
-            torch.randint(self.memory.cur_capacity, (ws["B"],), generator=self.gen, out=ws["idx"])
+            torch.randint(self._randint_bound(), (ws["B"],), generator=self.gen, out=ws["idx"])
+            if self._per is not None:
+                self._per_draw(ws, ws["idx"], 1)
         if noise is not None:
             self._inject(ws["draw"], noise, home)
         else:
             ws["draw"].normal_(generator=self.gen)
         self._step_kernels(ws, ws["idx"], ws["draw"])
+
+    def training_state(self):
+        with self._lock:
+            if self._per_pending:   # the saved leaves hold every step taken so far
+                self.flush_priorities()
+                self.synchronize()
+            return super().training_state()
 
     def _own_state(self):
         return {"critic": _cpu(self.critic.arena.data), "critic_target": _cpu(self.critic_target.arena.data),
@@ -399,6 +491,7 @@ class PQLVLearner(Learner):
         self.critic.arena.data.copy_(st["critic"])
         self.critic_target.arena.data.copy_(st["critic_target"])
         self._load_partner(st["actor"], make_actor)
+        self._per_pending = 0   # (|TD| of steps taken before the load does not belong to the loaded tree)
         if memory:
             self.memory.load_training_state(st["memory"])
 
@@ -417,6 +510,7 @@ class PQLVLearner(Learner):
         with self._lock, torch.cuda.device(self.device), self._on_stream():
             st = torch.cuda.current_stream(self.device)
             self.set_actor(actor, home)
+            self.flush_priorities()   # before the insert: a sampled row it overwrites must end with pmax^alpha
             with H.LOCK:
                 lease = H.acquire(trajectory, st, home)
                 self.memory.add_to_buffer(trajectory)

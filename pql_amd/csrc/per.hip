@@ -246,3 +246,61 @@ extern "C" int pqlk_per_weights(const float* tree, int64_t capacity, const int64
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ a run of steps in one launch
+// The samples and weights of `steps` batches drawn from the tree as it stands: sample k of step s is
+// k_per_sample's walk for stratum k of b with u = r[s b + k] 2^-24, and its weight k_per_weights' expression on the leaf the walk
+// ended at.  One wave per sample, a row of blocks (blockIdx.y) per step.  The maximum of a step's weights is an integer atomic max like k_per_weights'; a wave
+// whose weight does not exceed what it reads there first leaves the atomic out (the word only grows, so whatever it reads is at
+// most the final maximum and the result is the same bits).
+__global__ __launch_bounds__(256) void k_per_sample_steps(const float* __restrict__ tree, PerGeom g, const int64_t* __restrict__ r,
+                                                          int64_t b, float n_valid, float beta,
+                                                          int64_t* __restrict__ idx_out, float* __restrict__ w_out,
+                                                          float* __restrict__ wmax_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t s = blockIdx.y, k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= b) return;   // (whole waves leave)
+  const int64_t i = s * b + k;
+  const float total = per_total(tree + g.off[g.levels - 1], lane);
+  const float seg = total / (float)b;
+  const float u = (float)r[i] * 0x1p-24f;   // exact: r < 2^24
+  float resid = ((float)k + u) * seg;
+  int64_t node = 0;
+  float c = 0.f;
+  for (int l = g.levels - 1; l >= 0; --l) {
+    c = tree[g.off[l] + node * 64 + lane];
+    const float incl = wave_prefix_incl(c, lane);
+    const unsigned long long nonzero = __ballot(c != 0.f);
+    const unsigned long long over = __ballot(incl > resid) & nonzero;
+    int j = 0;
+    if (over) j = __ffsll((long long)over) - 1;
+    else if (nonzero) j = 63 - __clzll((long long)nonzero);
+    const float below = __shfl_up(incl, 1, 64);
+    resid -= __shfl(lane > 0 ? below : 0.f, j, 64);
+    node = node * 64 + j;
+    if (node >= g.n[l]) node = g.n[l] - 1;   // (as in k_per_sample: not while the pads are zero)
+  }
+  const float leaf = __shfl(c, (int)(node & 63), 64);   // level 0's children are the leaves: lane (node mod 64) holds leaf[node]
+  if (lane == 0) {
+    const float w = per_pow((n_valid * leaf) / total, -beta);
+    idx_out[i] = node;
+    w_out[i] = w;
+    unsigned int* m = reinterpret_cast<unsigned int*>(wmax_out + s);
+    const unsigned int bits = __float_as_uint(w);
+    if (bits > *reinterpret_cast<volatile unsigned int*>(m)) atomicMax(m, bits);
+  }
+}
+
+extern "C" int pqlk_per_sample_steps(const float* tree, int64_t capacity, const int64_t* r, int64_t b, int64_t steps, int64_t n_valid,
+                                     float beta, int64_t* idx_out, float* w_out, float* wmax_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(tree && r && idx_out && w_out && wmax_out, PQLK_E_NULL);
+  PQLK_REQUIRE(capacity > 0 && b > 0 && steps > 0 && n_valid > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(steps <= 65535 && b <= 4 * (int64_t)INT32_MAX, PQLK_E_SHAPE);   // (the grid: blocks of 4 samples x steps)
+  PQLK_REQUIRE(n_valid <= capacity, PQLK_E_RANGE);
+  hipError_t e = hipMemsetAsync(wmax_out, 0, (size_t)steps * sizeof(float), pqlk_s(stream));
+  if (e != hipSuccess) return -(int)e;
+  hipLaunchKernelGGL(k_per_sample_steps, dim3(per_wave_blocks(b), (unsigned)steps), dim3(256), 0, pqlk_s(stream), tree, per_geom(capacity), r, b,
+                     (float)n_valid, beta, idx_out, w_out, wmax_out);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}

@@ -6,6 +6,7 @@ The reference has no prioritized replay.  `PrioritizedReplayBuffer` is the plain
     add_to_buffer       gives the new rows the largest priority seen so far (`pqlk_per_insert`, the ring insert's segments),
     draw_indices(B)     draws B rows with probability leaf / total, stratified, and keeps their importance weights,
     weights_for(idx)    the importance weights of given rows (parity tests inject their indices),
+    draw_steps          the rows and weights of several steps' batches in one launch, all on the tree as it stands (`algo.per.refresh=run`),
     update_priorities   writes |TD| + eps back and repairs the tree.
 Nothing here synchronises with the host.  The agent sets `beta` (ActorCriticBase's schedule) before it samples.
 """
@@ -23,6 +24,23 @@ def per_cfg(algo):
     if per is None or not bool(per.get("enabled") or False):
         return None
     return per
+
+
+def per_refresh(per):
+    """`algo.per.refresh`: "step" (sample from the live tree and write back every learner step; a block without the key) or "run"
+    (one sample launch and one write-back per run of prefetched steps: the PQL V-learner)."""
+    value = str(per.get("refresh") or "step")
+    if value not in ("step", "run"):
+        raise ValueError(f"algo.per.refresh must be step or run, got {value!r}")
+    return value
+
+
+def per_beta(beta0, beta_iters, calls):
+    """The importance-sampling exponent of prioritized replay after `calls` calls of `update_net` (PQL V-learner: steps): linear from beta0 to 1 over
+    `beta_iters` calls, exactly 1.0 from there on."""
+    if calls >= beta_iters:
+        return 1.0
+    return float(beta0) + (1.0 - float(beta0)) * (calls / float(beta_iters))
 
 
 class PrioritizedReplayBuffer(ReplayBuffer):
@@ -103,8 +121,16 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         self.idx = idx
         return self.w, self.wmax
 
+    def draw_steps(self, r, b, steps, beta, idx_out, w_out, wmax_out):
+        """`steps` batches of `b` rows from the tree as it stands, with their weights at `beta`, in one launch (`pqlk_per_sample_steps`).
+        r: steps * b int64 draws of torch.randint(1 << 24); idx_out / w_out: steps * b entries, wmax_out: one float per step.  The
+        caller keeps the outputs (nothing is remembered here) and hands idx_out with the steps' |TD| to `update_priorities`."""
+        with torch.cuda.device(self.device):
+            L.check(L.lib.pqlk_per_sample_steps(L.ptr(self.tree), self.capacity, L.ptr(r), int(b), int(steps), int(self.cur_capacity),
+                                                float(beta), L.ptr(idx_out), L.ptr(w_out), L.ptr(wmax_out), L.stream(self.device)))
+
     def update_priorities(self, idx, abs_td):
         """priority[idx] = |TD| + eps (a row drawn twice keeps the larger one); raises `pmax`; repairs the touched ancestors."""
         with torch.cuda.device(self.device):
-            L.check(L.lib.pqlk_per_update(L.ptr(self.tree), self.capacity, L.ptr(self.pmax), L.ptr(idx), L.ptr(abs_td), idx.shape[0],
+            L.check(L.lib.pqlk_per_update(L.ptr(self.tree), self.capacity, L.ptr(self.pmax), L.ptr(idx), L.ptr(abs_td), idx.numel(),
                                           self.eps, self.alpha, L.stream(self.device)))

@@ -239,13 +239,16 @@ def structure(cfg, obs_dim, act_dim):
             "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32"),
             # (the V-learner's target forwards: bf16 targets change every later step, so a run resumes in the dtype it was saved in)
             "algo.target_dtype": str(algo.get("target_dtype") or "float32"),
-            # (prioritized replay: the ring carries a sum tree of priority^alpha; alpha counts only when it is on)
-            "algo.per.enabled": per_on, "algo.per.alpha": float(per.get("alpha")) if per_on else None}
+            # (prioritized replay: the ring carries a sum tree of priority^alpha; alpha, and when the priorities are refreshed --
+            #  every step, or once per run of prefetched steps -- count only when it is on)
+            "algo.per.enabled": per_on, "algo.per.alpha": float(per.get("alpha")) if per_on else None,
+            "algo.per.refresh": str(per.get("refresh") or "step") if per_on else None}
 
 
 def check_structure(saved, current, has_rings=True):
-    # (a checkpoint from before a key existed was written with float32 targets and uniform replay)
+    # (a checkpoint from before a key existed was written with float32 targets and uniform replay; prioritized, with per-step refresh)
     saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, **saved}
+    saved.setdefault("algo.per.refresh", "step" if saved["algo.per.enabled"] else None)
     for key, want in saved.items():
         if key in ("algo.memory_size", "algo.replay_obs_dtype") and not has_rings:
             continue

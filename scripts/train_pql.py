@@ -280,6 +280,10 @@ def main(cfg, on_finish=None):
                         obs_ring_sha=CK.sha_stream(p_learner.ring.rows(p_learner.cur_capacity), staging),
                         rms_sha=None if pql_actor.obs_rms is None else CK.sha(torch.cat([pql_actor.obs_rms.mean.reshape(-1),
                                                                                          pql_actor.obs_rms.var.reshape(-1)])))
+    if getattr(v_learner.memory, "prioritized", False):   # the priorities the run ends with, every step's |TD| written back
+        v_learner.flush_priorities()
+        v_learner.synchronize()
+        fingerprints.update(per_sha=CK.sha(v_learner.memory.leaves), per_pmax=float(v_learner.memory.pmax))
     if world > 1:
         torch.distributed.barrier(group=pg)
         torch.distributed.destroy_process_group()

@@ -11,7 +11,7 @@ PointMass for a fixed number of rollout iterations, several seeds each, at two s
 everything else at the defaults (nstep 3, gamma 0.99, tau 0.05, lr 5e-4, mixed exploration noise).  Per run it records the return of
 the trained deterministic policy over one full episode on 256 fresh envs (R), the same for the zero action (R_zero) and for the PD
 controller a = clamp(4 (g - x) - 4 v, -1, 1) (R_pd), the gap fraction f = (R - R_zero) / (R_pd - R_zero) and the wall time.
-`--curve` adds DDPG at the small shape over a ladder of iteration counts (where does it plateau?).  With `--task swingup` the shapes
+`--curve` adds DDPG (`--curve-algo pql`: PQL) at the small shape over a ladder of iteration counts (where does it plateau?).  With `--task swingup` the shapes
 are the same, the episode length is 128 and the upper yardstick is the energy controller (`energy_policy`), recorded as R_ctrl.
 
     python tools/learn_pointmass.py --out profiles/pointmass_learning.json
@@ -21,6 +21,7 @@ are the same, the episode length is 128 and the upper yardstick is the energy co
     python tools/learn_pointmass.py --algos ddpg --shapes small --override algo.cri_class=DoubleQLayerNorm --versus-default --curve 125,250,500 --out profiles/pointmass_learning_ln.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --curve 500,1000,2000,4000,8000 --out profiles/swingup_learning.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.distl=True --out profiles/swingup_learning_distl.json
+    python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.per.enabled=True --override algo.per.refresh=run --versus-default --curve 250,500,1000 --curve-algo pql --out profiles/per_pql_learning.json
 """
 import argparse
 import importlib.util
@@ -137,7 +138,8 @@ def main():
     ap.add_argument("--shapes", default="small,large")
     ap.add_argument("--seeds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=1000, help="rollout iterations per run (8 critic updates each)")
-    ap.add_argument("--curve", default=None, help="comma-separated iteration counts: DDPG at the small shape, every seed, at each of them")
+    ap.add_argument("--curve", default=None, help="comma-separated iteration counts: --curve-algo (default DDPG) at the small shape, every seed, at each of them")
+    ap.add_argument("--curve-algo", default="ddpg", choices=sorted(ALGOS), help="the algorithm of the --curve runs")
     ap.add_argument("--override", action="append", default=[], help="a further config override for every run (repeatable)")
     ap.add_argument("--versus-default", action="store_true", help="with --override: every run is preceded by the same run WITHOUT the "
                     "overrides (no `overrides` key in its record), so the two variants alternate inside one call")
@@ -165,7 +167,7 @@ def main():
                 record("runs", run(algo, shape, seed, a.iters, tuple(a.override), task=a.task))
     for iters in ([int(x) for x in a.curve.split(",")] if a.curve else []):
         for seed in range(a.seeds):
-            record("curve", run("ddpg", "small", seed, iters, tuple(a.override), task=a.task))
+            record("curve", run(a.curve_algo, "small", seed, iters, tuple(a.override), task=a.task))
 
 
 if __name__ == "__main__":
