@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic, td_mse_loss
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.prioritized_replay import per_beta, per_cfg  # noqa: F401  (per_beta: imported from here by its users)
@@ -184,17 +184,12 @@ class ActorCriticBase(PQLActor):
         """Twin MSE against r + (1 - d) gamma^n min(qt): d loss / d q -> ws["dy"], the loss -> the critic's ring."""
         algo = self.cfg.algo
         memory = ws.get("per")
-        if memory is None:
-            L.check(L.lib.pqlk_td_mse_loss(L.ptr(q), L.ptr(qt), ld, L.ptr(ws["rew"]), L.ptr(ws["done"]), float(algo.gamma) ** int(algo.nstep),
-                                           ws["B"], L.ptr(ws["dy"]), L.ptr(self.closs), L.ptr(self.copt.step), LOSS_RING,
-                                           L.ptr(ws["scratch"]), L.stream(self.device)))
-            return
-        # prioritized replay: the importance weights on the loss and its gradient, then |TD| back into the tree
-        L.check(L.lib.pqlk_td_mse_loss_per(L.ptr(q), L.ptr(qt), ld, L.ptr(ws["rew"]), L.ptr(ws["done"]), float(algo.gamma) ** int(algo.nstep),
-                                           ws["B"], L.ptr(ws["dy"]), L.ptr(self.closs), L.ptr(self.copt.step), LOSS_RING,
-                                           L.ptr(ws["scratch"]), L.ptr(ws["w"]), L.ptr(ws["wmax"]), L.ptr(ws["abs_td"]),
-                                           L.stream(self.device)))
-        memory.update_priorities(ws["idx"], ws["abs_td"])
+        # with prioritized replay: the importance weights on the loss and its gradient, then |TD| back into the tree
+        per = {} if memory is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
+        td_mse_loss(q, qt, ld, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep), ws["B"], ws["dy"], self.closs, self.copt.step,
+                    ws["scratch"], self.device, **per)
+        if memory is not None:
+            memory.update_priorities(ws["idx"], ws["abs_td"])
 
     def _dpg_loss(self, ws, q, ld):
         """-mean(min q): d loss / d q -> ws["dy"], the loss -> the actor's ring."""

@@ -88,6 +88,18 @@ def apply_optimizer_fused(layout, arena, grads, st: _AdamState, target, lr, max_
                                           float(loss_scale), L.ptr(loss_ring), LOSS_RING, L.stream(device)))
 
 
+def td_mse_loss(q, qt, ld, rew, done, gamma_n, B, dy, loss_out, step, scratch, device, w=None, wmax=None, abs_td=None):
+    """Twin MSE against r + (1 - d) gamma^n min(qt): d loss / d q -> dy, the partials -> scratch, the loss -> slot `step` of the ring
+    `loss_out` (None: the partials are folded later).  With `w`, `wmax`, `abs_td` (prioritized replay) the importance weights
+    w / wmax lie on the loss and its gradient, and |TD| goes to `abs_td`."""
+    head = (L.ptr(q), L.ptr(qt), ld, L.ptr(rew), L.ptr(done), gamma_n, B, L.ptr(dy), L.ptr(loss_out), L.ptr(step), LOSS_RING,
+            L.ptr(scratch))
+    if w is None:
+        L.check(L.lib.pqlk_td_mse_loss(*head, L.stream(device)))
+    else:
+        L.check(L.lib.pqlk_td_mse_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), L.stream(device)))
+
+
 def f32_recip(*factors, sign=1.0):
     """sign / (f0 * f1 ...) evaluated in fp32, like the kernels' `1.0f / ((float)b * (float)k)`."""
     import numpy as np

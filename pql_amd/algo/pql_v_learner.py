@@ -21,7 +21,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
-                                  check_critic_class, graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
+                                  check_critic_class, graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm, td_mse_loss)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
                                 output_view)
 from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer, per_beta, per_cfg
@@ -361,14 +361,10 @@ class PQLVLearner(Learner):
                                                     L.ptr(ws["done"]), L.ptr(self.critic.z_atoms), gamma_n, float(algo.v_min),
                                                     float(algo.v_max), B, L.ptr(ws["dy"]), loss_out, L.ptr(self.opt.step),
                                                     LOSS_RING, None, L.ptr(ws["scratch"]), st))
-                elif self._per is not None:   # importance weights on the loss and its gradient; |TD| -> the slot's slab
-                    L.check(L.lib.pqlk_td_mse_loss_per(L.ptr(q), L.ptr(qt), cl.ld_out, L.ptr(ws["rew"]), L.ptr(ws["done"]), gamma_n, B,
-                                                       L.ptr(ws["dy"]), loss_out, L.ptr(self.opt.step), LOSS_RING, L.ptr(ws["scratch"]),
-                                                       L.ptr(ws["w"]), L.ptr(ws["wmax"]), L.ptr(ws["abs_td"]), st))
-                else:
-                    L.check(L.lib.pqlk_td_mse_loss(L.ptr(q), L.ptr(qt), cl.ld_out, L.ptr(ws["rew"]), L.ptr(ws["done"]), gamma_n, B,
-                                                   L.ptr(ws["dy"]), loss_out, L.ptr(self.opt.step), LOSS_RING,
-                                                   L.ptr(ws["scratch"]), st))
+                else:   # (with prioritized replay: importance weights on the loss and its gradient; |TD| -> the slot's slab)
+                    per = {} if self._per is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
+                    td_mse_loss(q, qt, cl.ld_out, ws["rew"], ws["done"], gamma_n, B, ws["dy"], None if self._fold_loss else self.loss_ring,
+                                self.opt.step, ws["scratch"], self.device, **per)
         if self._buckets is not None:
             # data parallel: the chain in pieces, each ending with the sum of its layers' dW slabs; that piece's collective goes
             # out right behind it and runs under the launches of the layers below

@@ -29,161 +29,185 @@ __device__ __forceinline__ float block_sum_256(float v) {
   return (shw[0] + shw[1]) + (shw[2] + shw[3]);
 }
 
+// blocks of a loss kernel = per-block partials it leaves in `scratch` (k = 1: scalar heads, one row per thread; k > 1: one wave per row)
+static int loss_blocks(int64_t b, int32_t k) {
+  const int64_t blocks = k <= 1 ? (b + 255) / 256 : (b + 3) / 4;
+  return (int)(blocks < LOSS_MAX_BLOCKS ? blocks : LOSS_MAX_BLOCKS);
+}
+extern "C" int32_t pqlk_loss_parts(int64_t b, int32_t k) { return loss_blocks(b, k); }
+
+// tail of every loss entry point: scale * (sum of the partials) -> the loss ring; without a ring the partials stay in
+// scratch[0, pqlk_loss_parts(b, k)) and pqlk_adamw_polyak_fused folds them
+static int fold_partials(const float* scratch, int blocks, float scale, float* loss_out, const int32_t* slot_dev, int32_t ring_len,
+                         pqlk_stream_t stream) {
+  if (!loss_out) return PQLK_OK;
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks, scale, loss_out, slot_dev, (int)ring_len);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
+// PER: the importance weight wh = w[i] / wmax[0] of prioritized replay on each sample (and |TD| out, the new priority).  The plain
+// instance never touches w, wmax or abs_td; with every w and wmax 1.0 the multiplications by wh change no bit.
+template <bool PER>
 __global__ __launch_bounds__(256) void k_td_mse(const float* __restrict__ q, const float* __restrict__ qt, int64_t ld,
                                                 const float* __restrict__ rew, const float* __restrict__ done,
-                                                float gamma_n, int64_t b, float* __restrict__ dy,
-                                                float* __restrict__ part) {
+                                                float gamma_n, int64_t b, float* __restrict__ dy, float* __restrict__ part,
+                                                const float* __restrict__ w, const float* __restrict__ wmax,
+                                                float* __restrict__ abs_td) {
   const float two_over_b = 2.0f / (float)b;
+  float wm = 1.f;
+  if constexpr (PER) wm = wmax[0];
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < b; i += (int64_t)gridDim.x * 256) {
     const float t1 = qt[i * ld], t2 = qt[(b + i) * ld];
     const float tq = fminf(t1, t2);
     const float y = rew[i] + ((1.f - done[i]) * gamma_n) * tq;  // r + (1-d)*gamma^n*minQ'  (:105)
     const float d1 = q[i * ld] - y, d2 = q[(b + i) * ld] - y;
-    acc += d1 * d1 + d2 * d2;
-    dy[i * ld] = two_over_b * d1;
-    dy[(b + i) * ld] = two_over_b * d2;
+    float sq = d1 * d1 + d2 * d2, g = two_over_b;
+    if constexpr (PER) {
+      const float wh = w[i] / wm;
+      sq = wh * sq;
+      g = two_over_b * wh;
+    }
+    acc += sq;
+    dy[i * ld] = g * d1;
+    dy[(b + i) * ld] = g * d2;
+    if constexpr (PER) abs_td[i] = fmaxf(fabsf(d1), fabsf(d2));
   }
   const float s = block_sum_256(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+template <bool PER>
+static int td_mse_impl(const float* q, const float* qt, int64_t ld, const float* rew, const float* done, float gamma_n, int64_t b,
+                       float* dy, float* loss_out, const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w,
+                       const float* wmax, float* abs_td_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(q && qt && rew && done && dy && scratch, PQLK_E_NULL);
+  PQLK_REQUIRE(!PER || (w && wmax && abs_td_out), PQLK_E_NULL);
+  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(ld >= 32 && ld % 32 == 0, PQLK_E_ALIGN);
+  const int blocks = loss_blocks(b, 1);
+  hipLaunchKernelGGL(k_td_mse<PER>, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, qt, ld, rew, done, gamma_n, b, dy, scratch, w, wmax,
+                     abs_td_out);
+  PQLK_LAUNCH_CHECK();
+  return fold_partials(scratch, blocks, 1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
 }
 
 extern "C" int pqlk_td_mse_loss(const float* q, const float* qt, int64_t ld, const float* rew, const float* done,
                                 float gamma_n, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
                                 int32_t ring_len, float* scratch, pqlk_stream_t stream) {
-  PQLK_REQUIRE(q && qt && rew && done && dy && scratch, PQLK_E_NULL);
-  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
-  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
-  PQLK_REQUIRE(ld >= 32 && ld % 32 == 0, PQLK_E_ALIGN);
-  int blocks = (int)((b + 255) / 256);
-  if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
-  hipLaunchKernelGGL(k_td_mse, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, qt, ld, rew, done, gamma_n, b, dy, scratch);
-  PQLK_LAUNCH_CHECK();
-  if (!loss_out) return PQLK_OK;   // partials stay in scratch[0, pqlk_loss_parts(b, 1)): folded by pqlk_adamw_polyak_fused
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks, 1.0f / (float)b, loss_out,
-                     slot_dev, (int)ring_len);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
-}
-
-// k_td_mse with the importance weight wh = w[i] / wmax[0] of prioritized replay on each sample (and |TD| out, the new priority).
-// The same loop, grid, partials and fold as k_td_mse: with every w and wmax 1.0 the multiplications by wh change no bit.
-__global__ __launch_bounds__(256) void k_td_mse_per(const float* __restrict__ q, const float* __restrict__ qt, int64_t ld,
-                                                    const float* __restrict__ rew, const float* __restrict__ done,
-                                                    float gamma_n, int64_t b, float* __restrict__ dy, float* __restrict__ part,
-                                                    const float* __restrict__ w, const float* __restrict__ wmax,
-                                                    float* __restrict__ abs_td) {
-  const float two_over_b = 2.0f / (float)b;
-  const float wm = wmax[0];
-  float acc = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < b; i += (int64_t)gridDim.x * 256) {
-    const float t1 = qt[i * ld], t2 = qt[(b + i) * ld];
-    const float tq = fminf(t1, t2);
-    const float y = rew[i] + ((1.f - done[i]) * gamma_n) * tq;
-    const float d1 = q[i * ld] - y, d2 = q[(b + i) * ld] - y;
-    const float wh = w[i] / wm;
-    acc += wh * (d1 * d1 + d2 * d2);
-    const float g = two_over_b * wh;
-    dy[i * ld] = g * d1;
-    dy[(b + i) * ld] = g * d2;
-    abs_td[i] = fmaxf(fabsf(d1), fabsf(d2));
-  }
-  const float s = block_sum_256(acc);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
+  return td_mse_impl<false>(q, qt, ld, rew, done, gamma_n, b, dy, loss_out, slot_dev, ring_len, scratch, nullptr, nullptr, nullptr,
+                            stream);
 }
 
 extern "C" int pqlk_td_mse_loss_per(const float* q, const float* qt, int64_t ld, const float* rew, const float* done,
                                     float gamma_n, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
                                     int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out,
                                     pqlk_stream_t stream) {
-  PQLK_REQUIRE(q && qt && rew && done && dy && scratch && w && wmax && abs_td_out, PQLK_E_NULL);
-  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
-  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
-  PQLK_REQUIRE(ld >= 32 && ld % 32 == 0, PQLK_E_ALIGN);
-  int blocks = (int)((b + 255) / 256);
-  if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
-  hipLaunchKernelGGL(k_td_mse_per, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, qt, ld, rew, done, gamma_n, b, dy, scratch, w, wmax,
-                     abs_td_out);
-  PQLK_LAUNCH_CHECK();
-  if (!loss_out) return PQLK_OK;   // as pqlk_td_mse_loss: the partials stay in scratch
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks, 1.0f / (float)b, loss_out,
-                     slot_dev, (int)ring_len);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
+  return td_mse_impl<true>(q, qt, ld, rew, done, gamma_n, b, dy, loss_out, slot_dev, ring_len, scratch, w, wmax, abs_td_out, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
-// C51.  One wave per batch row, lane k <-> atom k (K <= 64; more atoms: the k_*_wide kernels below).
-__device__ __forceinline__ float wave_softmax(float x, bool valid) {
-  const float m = wave_max(valid ? x : -INFINITY);
-  const float e = valid ? expf(x - m) : 0.f;
-  const float s = wave_sum(e);
-  return e / s;
+// C51 with 2 ... PQLK_C51_MAX_ATOMS atoms.  One wave per batch row and four rows per block; a lane holds atoms lane + 64 j,
+// j < NJ = ceil(K / 64): coalesced row reads (NJ = 1, K <= 64: lane k <-> atom k).  Softmax, E[z] and the softmax backward's dot
+// product reduce over the lane's own atoms first, then with wave_max / wave_sum.  The lane's own reduction starts from -inf / 0.f
+// at every NJ: against starting from atom j = 0 that can move the sign of a zero sum, and only of one whose 64 lanes all hold -0
+// (DESIGN 10 f16 shows that no input with a finite non-zero support gets there).
+template <int NJ>
+__device__ __forceinline__ void load_row(const float* __restrict__ row, int K, int lane, float (&x)[NJ]) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) x[j] = lane + 64 * j < K ? row[lane + 64 * j] : 0.f;
 }
 
-// projection of one row's pmf p (lane k) -> projected pmf (lane j).  Deposits are accumulated per bin
-// in atom order, all lower-neighbour deposits first, then all upper ones: the order of the reference's
-// two sequential index_add_ passes (distl_util.py:18-19), so the result is deterministic.
-template <int KMAX>
-__device__ __forceinline__ float project_row(float p, float zk, float r, float d, float gamma_n, float v_min, float v_max,
-                                             float dz, int K, int lane) {
+// one row of dy: columns [0, K) <- v, pad columns [K, ld) <- 0
+template <int NJ>
+__device__ __forceinline__ void store_dy_row(float* __restrict__ row, int64_t ld, int K, int lane, const float (&v)[NJ]) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = lane + 64 * j;
+    if (c < ld) row[c] = c < K ? v[j] : 0.f;
+  }
+  for (int64_t c = 64 * NJ + lane; c < ld; c += 64) row[c] = 0.f;
+}
+
+// softmax over the K values a wave holds as x[j] <-> atom lane + 64 j (x[j] is ignored where the atom is >= K)
+template <int NJ>
+__device__ __forceinline__ void wave_softmax(float (&x)[NJ], int K, int lane) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (lane + 64 * j < K) m = fmaxf(m, x[j]);
+  m = wave_max(m);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) x[j] = lane + 64 * j < K ? expf(x[j] - m) : 0.f;
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) s += x[j];
+  s = wave_sum(s);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) x[j] = x[j] / s;
+}
+
+// sum over a row of a[j] * b[j]
+template <int NJ>
+__device__ __forceinline__ float wave_dot(const float (&a)[NJ], const float (&b)[NJ]) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) s += a[j] * b[j];
+  return wave_sum(s);
+}
+
+// Projection.  Atom a of a row with pmf value p deposits w_lo into bin lo and w_up into bin up:
+struct C51Deposit {
+  int lo, up;
+  float w_lo, w_up;
+};
+__device__ __forceinline__ C51Deposit c51_deposit(float p, float zk, float r, float d, float gamma_n, float v_min, float v_max,
+                                                  float dz, int K) {
   float tz = r + ((1.f - d) * gamma_n) * zk;
   tz = fminf(fmaxf(tz, v_min), v_max);
   const float bpos = (tz - v_min) / dz;
   int lo = (int)floorf(bpos), up = (int)ceilf(bpos);
   if (up > 0 && lo == up) lo -= 1;
   if (lo < K - 1 && lo == up) up += 1;
-  const float w_lo = p * ((float)up - bpos);
-  const float w_up = p * (bpos - (float)lo);
+  return {lo, up, p * ((float)up - bpos), p * (bpos - (float)lo)};
+}
+
+// K <= 64: one row's pmf p (lane k) -> projected pmf (lane j) by cross-lane shuffles.  Deposits are accumulated per bin
+// in atom order, all lower-neighbour deposits first, then all upper ones: the order of the reference's
+// two sequential index_add_ passes (distl_util.py:18-19), so the result is deterministic.
+template <int KMAX>
+__device__ __forceinline__ float project_row(float p, float zk, float r, float d, float gamma_n, float v_min, float v_max,
+                                             float dz, int K, int lane) {
+  const C51Deposit a = c51_deposit(p, zk, r, d, gamma_n, v_min, v_max, dz, K);
   float out = 0.f;
 #pragma unroll
   for (int kk = 0; kk < KMAX; ++kk) {
     if (kk < K) {
-      const int l2 = __shfl(lo, kk, 64);
-      const float w2 = __shfl(w_lo, kk, 64);
+      const int l2 = __shfl(a.lo, kk, 64);
+      const float w2 = __shfl(a.w_lo, kk, 64);
       if (l2 == lane) out += w2;
     }
   }
 #pragma unroll
   for (int kk = 0; kk < KMAX; ++kk) {
     if (kk < K) {
-      const int u2 = __shfl(up, kk, 64);
-      const float w2 = __shfl(w_up, kk, 64);
+      const int u2 = __shfl(a.up, kk, 64);
+      const float w2 = __shfl(a.w_up, kk, 64);
       if (u2 == lane) out += w2;
     }
   }
   return out;
 }
 
-__global__ __launch_bounds__(256) void k_c51_project(const float* __restrict__ p, const float* __restrict__ rew,
-                                                     const float* __restrict__ done, const float* __restrict__ support,
-                                                     float gamma_n, float v_min, float v_max, float dz, int K, int64_t b,
-                                                     float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nw = (int64_t)gridDim.x * 4;
-  const bool valid = lane < K;
-  const float zk = valid ? support[lane] : 0.f;
-  for (int64_t i = wave; i < b; i += nw) {
-    const float pv = valid ? p[i * K + lane] : 0.f;
-    const float o = project_row<64>(pv, zk, rew[i], done[i], gamma_n, v_min, v_max, dz, K, lane);
-    if (valid) out[i * K + lane] = o;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// C51 with 65 ... PQLK_C51_MAX_ATOMS atoms.  Still one wave per batch row and four rows per block (same grids, same loss
-// partials); a lane holds atoms lane + 64 j, j < NJ = ceil(K / 64): coalesced row reads.  Softmax, E[z] and the softmax
-// backward's dot product reduce over the lane's own atoms first, then with wave_max / wave_sum.
-//
-// Projection: the per-atom arithmetic is project_row's, expression for expression.  The wave writes (lo, w_lo, up, w_up) of its K
-// atoms into its own 4 KiB LDS image.  lo and up are non-decreasing in the atom index (precondition in pqlk.h), so the atoms that
-// deposit into bin j are a contiguous range: the lane that owns the bin finds the first atom with lo >= j by binary search, walks
-// while lo == j, then does the same for up -- all lower-neighbour deposits in atom order, then all upper ones, a plain
-// left-to-right fp32 sum: the order of project_row and of the reference's two index_add_ passes.  O(K) LDS reads per bin at worst
-// (a terminal row: one bin collects every atom), O(log K) typically.  lo / up are only ever COMPARED, never used as an address:
-// a non-finite reward can drop mass, as in project_row, but cannot index outside the image.
+// K > 64.  The wave writes the deposits of its K atoms into its own 4 KiB LDS image.  lo and up are non-decreasing in the atom
+// index (precondition in pqlk.h), so the atoms that deposit into bin j are a contiguous range: the lane that owns the bin finds the
+// first atom with lo >= j by binary search, walks while lo == j, then does the same for up -- all lower-neighbour deposits in atom
+// order, then all upper ones, a plain left-to-right fp32 sum: the order of project_row and of the reference's two index_add_
+// passes.  O(K) LDS reads per bin at worst (a terminal row: one bin collects every atom), O(log K) typically.  lo / up are only ever
+// COMPARED, never used as an address: a non-finite reward can drop mass, as in project_row, but cannot index outside the image.
 //
 // The image belongs to one wave and the row loop's trip count differs between the waves of a block (ragged last trip; B < 4 leaves
 // waves idle): no __syncthreads() inside that loop.  A wave's LDS accesses execute in order; wave_lds_fence() keeps the compiler
@@ -214,91 +238,55 @@ __device__ __forceinline__ int first_ge(const int* v, int K, int bin) {
   return pos;
 }
 
+// the projection of the kernels below: pmf p -> projected pmf out, both as load_row holds a row.  NJ == 1 never touches img (the
+// compiler then drops the kernel's image: tests/test_host_cpu.py holds the LDS sizes)
 template <int NJ>
-__device__ __forceinline__ void project_row_wide(const float (&p)[NJ], const float (&zk)[NJ], float r, float d, float gamma_n,
-                                                 float v_min, float v_max, float dz, int K, int lane, C51Image& img,
-                                                 float (&out)[NJ]) {
+__device__ __forceinline__ void project(const float (&p)[NJ], const float (&zk)[NJ], float r, float d, float gamma_n, float v_min,
+                                        float v_max, float dz, int K, int lane, C51Image& img, float (&out)[NJ]) {
+  if constexpr (NJ == 1) {
+    out[0] = project_row<64>(p[0], zk[0], r, d, gamma_n, v_min, v_max, dz, K, lane);
+  } else {
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int a = lane + 64 * j;
-    if (a < K) {
-      float tz = r + ((1.f - d) * gamma_n) * zk[j];
-      tz = fminf(fmaxf(tz, v_min), v_max);
-      const float bpos = (tz - v_min) / dz;
-      int lo = (int)floorf(bpos), up = (int)ceilf(bpos);
-      if (up > 0 && lo == up) lo -= 1;
-      if (lo < K - 1 && lo == up) up += 1;
-      img.lo[a] = lo;
-      img.w_lo[a] = p[j] * ((float)up - bpos);
-      img.up[a] = up;
-      img.w_up[a] = p[j] * (bpos - (float)lo);
+    for (int j = 0; j < NJ; ++j) {
+      const int a = lane + 64 * j;
+      if (a < K) {
+        const C51Deposit dep = c51_deposit(p[j], zk[j], r, d, gamma_n, v_min, v_max, dz, K);
+        img.lo[a] = dep.lo;
+        img.w_lo[a] = dep.w_lo;
+        img.up[a] = dep.up;
+        img.w_up[a] = dep.w_up;
+      }
     }
-  }
-  wave_lds_fence();
+    wave_lds_fence();
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int bin = lane + 64 * j;
-    float o = 0.f;
-    if (bin < K) {
-      for (int a = first_ge(img.lo, K, bin); a < K && img.lo[a] == bin; ++a) o += img.w_lo[a];
-      for (int a = first_ge(img.up, K, bin); a < K && img.up[a] == bin; ++a) o += img.w_up[a];
+    for (int j = 0; j < NJ; ++j) {
+      const int bin = lane + 64 * j;
+      float o = 0.f;
+      if (bin < K) {
+        for (int a = first_ge(img.lo, K, bin); a < K && img.lo[a] == bin; ++a) o += img.w_lo[a];
+        for (int a = first_ge(img.up, K, bin); a < K && img.up[a] == bin; ++a) o += img.w_up[a];
+      }
+      out[j] = o;
     }
-    out[j] = o;
+    wave_lds_fence();   // the next projection's writes stay behind these reads
   }
-  wave_lds_fence();   // the next projection's writes stay behind these reads
-}
-
-// softmax over the K values a wave holds as x[j] <-> atom lane + 64 j (x[j] is ignored where the atom is >= K)
-template <int NJ>
-__device__ __forceinline__ void wave_softmax_wide(float (&x)[NJ], int K, int lane) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-    if (lane + 64 * j < K) m = fmaxf(m, x[j]);
-  m = wave_max(m);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    x[j] = lane + 64 * j < K ? expf(x[j] - m) : 0.f;
-    s += x[j];
-  }
-  s = wave_sum(s);
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) x[j] = x[j] / s;
 }
 
 template <int NJ>
-__device__ __forceinline__ void load_row_wide(const float* __restrict__ row, int K, int lane, float (&x)[NJ]) {
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) x[j] = lane + 64 * j < K ? row[lane + 64 * j] : 0.f;
-}
-
-// one row of dy: columns [0, K) <- v, pad columns [K, ld) <- 0
-template <int NJ>
-__device__ __forceinline__ void store_dy_row_wide(float* __restrict__ row, int64_t ld, int K, int lane, const float (&v)[NJ]) {
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
-    if (c < ld) row[c] = c < K ? v[j] : 0.f;
-  }
-  for (int64_t c = 64 * NJ + lane; c < ld; c += 64) row[c] = 0.f;
-}
-
-template <int NJ>
-__global__ __launch_bounds__(256) void k_c51_project_wide(const float* __restrict__ p, const float* __restrict__ rew,
-                                                          const float* __restrict__ done, const float* __restrict__ support,
-                                                          float gamma_n, float v_min, float v_max, float dz, int K, int64_t b,
-                                                          float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_c51_project(const float* __restrict__ p, const float* __restrict__ rew,
+                                                     const float* __restrict__ done, const float* __restrict__ support,
+                                                     float gamma_n, float v_min, float v_max, float dz, int K, int64_t b,
+                                                     float* __restrict__ out) {
   __shared__ C51Image image[4];
   C51Image& img = image[threadIdx.x >> 6];
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nw = (int64_t)gridDim.x * 4;
   float zk[NJ], pv[NJ], o[NJ];
-  load_row_wide<NJ>(support, K, lane, zk);
+  load_row<NJ>(support, K, lane, zk);
   for (int64_t i = wave; i < b; i += nw) {
-    load_row_wide<NJ>(p + i * K, K, lane, pv);
-    project_row_wide<NJ>(pv, zk, rew[i], done[i], gamma_n, v_min, v_max, dz, K, lane, img, o);
+    load_row<NJ>(p + i * K, K, lane, pv);
+    project<NJ>(pv, zk, rew[i], done[i], gamma_n, v_min, v_max, dz, K, lane, img, o);
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
       if (lane + 64 * j < K) out[i * K + lane + 64 * j] = o[j];
@@ -306,12 +294,12 @@ __global__ __launch_bounds__(256) void k_c51_project_wide(const float* __restric
 }
 
 template <int NJ>
-__global__ __launch_bounds__(256) void k_c51_bce_wide(const float* __restrict__ logits, const float* __restrict__ logits_t,
-                                                      int64_t ld, int K, const float* __restrict__ rew,
-                                                      const float* __restrict__ done, const float* __restrict__ support,
-                                                      float gamma_n, float v_min, float v_max, float dz, int64_t b,
-                                                      float* __restrict__ dy, float* __restrict__ proj_out,
-                                                      float* __restrict__ part) {
+__global__ __launch_bounds__(256) void k_c51_bce(const float* __restrict__ logits, const float* __restrict__ logits_t,
+                                                 int64_t ld, int K, const float* __restrict__ rew,
+                                                 const float* __restrict__ done, const float* __restrict__ support,
+                                                 float gamma_n, float v_min, float v_max, float dz, int64_t b,
+                                                 float* __restrict__ dy, float* __restrict__ proj_out,
+                                                 float* __restrict__ part) {
   __shared__ C51Image image[4];
   C51Image& img = image[threadIdx.x >> 6];
   const int lane = threadIdx.x & 63;
@@ -319,17 +307,18 @@ __global__ __launch_bounds__(256) void k_c51_bce_wide(const float* __restrict__ 
   const int64_t nw = (int64_t)gridDim.x * 4;
   const float inv_numel = 1.0f / ((float)b * (float)K);
   float zk[NJ];
-  load_row_wide<NJ>(support, K, lane, zk);
+  load_row<NJ>(support, K, lane, zk);
   float acc = 0.f;
   for (int64_t i = wave; i < b; i += nw) {
     const float r = rew[i], d = done[i];
+    // target pmf: min of the two projected target distributions (pql_v_learner.py:83-102)
     float pt[NJ], t[NJ], pr[NJ];
-    load_row_wide<NJ>(logits_t + i * ld, K, lane, pt);
-    wave_softmax_wide<NJ>(pt, K, lane);
-    project_row_wide<NJ>(pt, zk, r, d, gamma_n, v_min, v_max, dz, K, lane, img, t);
-    load_row_wide<NJ>(logits_t + (b + i) * ld, K, lane, pt);
-    wave_softmax_wide<NJ>(pt, K, lane);
-    project_row_wide<NJ>(pt, zk, r, d, gamma_n, v_min, v_max, dz, K, lane, img, pr);
+    load_row<NJ>(logits_t + i * ld, K, lane, pt);
+    wave_softmax<NJ>(pt, K, lane);
+    project<NJ>(pt, zk, r, d, gamma_n, v_min, v_max, dz, K, lane, img, t);
+    load_row<NJ>(logits_t + (b + i) * ld, K, lane, pt);
+    wave_softmax<NJ>(pt, K, lane);
+    project<NJ>(pt, zk, r, d, gamma_n, v_min, v_max, dz, K, lane, img, pr);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       t[j] = fminf(t[j], pr[j]);
@@ -339,75 +328,35 @@ __global__ __launch_bounds__(256) void k_c51_bce_wide(const float* __restrict__ 
     for (int net = 0; net < 2; ++net) {
       const int64_t row = (int64_t)net * b + i;
       float pc[NJ], gp[NJ];
-      load_row_wide<NJ>(logits + row * ld, K, lane, pc);
-      wave_softmax_wide<NJ>(pc, K, lane);
-      float dot = 0.f;
+      load_row<NJ>(logits + row * ld, K, lane, pc);
+      wave_softmax<NJ>(pc, K, lane);
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         float le = 0.f;
         gp[j] = 0.f;
         if (lane + 64 * j < K) {
+          // F.binary_cross_entropy: (t-1)*max(log(1-p),-100) - t*max(log(p),-100); grad (p-t)/max((1-p)p,1e-12)
           le = (t[j] - 1.f) * fmaxf(logf(1.f - pc[j]), -100.f) - t[j] * fmaxf(logf(pc[j]), -100.f);
           gp[j] = (pc[j] - t[j]) / fmaxf((1.f - pc[j]) * pc[j], 1e-12f) * inv_numel;
         }
         acc += le;
-        dot += gp[j] * pc[j];
       }
-      dot = wave_sum(dot);
+      const float dot = wave_dot<NJ>(gp, pc);
 #pragma unroll
       for (int j = 0; j < NJ; ++j) gp[j] = (gp[j] - dot) * pc[j];  // softmax backward (pc is 0 past K)
-      store_dy_row_wide<NJ>(dy + row * ld, ld, K, lane, gp);
+      store_dy_row<NJ>(dy + row * ld, ld, K, lane, gp);
     }
   }
   const float s = block_sum_256(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-template <int NJ>
-__global__ __launch_bounds__(256) void k_dpg_dist_wide(const float* __restrict__ logits, int64_t ld, int K,
-                                                       const float* __restrict__ support, int64_t b, float* __restrict__ dy,
-                                                       float* __restrict__ part) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nw = (int64_t)gridDim.x * 4;
-  const float g = -1.0f / (float)b;
-  float zk[NJ];
-  load_row_wide<NJ>(support, K, lane, zk);
-  float acc = 0.f;
-  for (int64_t i = wave; i < b; i += nw) {
-    float p1[NJ], p2[NJ];
-    load_row_wide<NJ>(logits + i * ld, K, lane, p1);
-    load_row_wide<NJ>(logits + (b + i) * ld, K, lane, p2);
-    wave_softmax_wide<NJ>(p1, K, lane);
-    wave_softmax_wide<NJ>(p2, K, lane);
-    float q1 = 0.f, q2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      q1 += p1[j] * zk[j];
-      q2 += p2[j] * zk[j];
-    }
-    q1 = wave_sum(q1);
-    q2 = wave_sum(q2);
-    if (lane == 0) acc += fminf(q1, q2);
-    const float g1 = q1 < q2 ? g : (q1 == q2 ? 0.5f * g : 0.f);
-    const float g2 = q2 < q1 ? g : (q1 == q2 ? 0.5f * g : 0.f);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {   // dQ/dlogit_k = p_k (z_k - Q)
-      p1[j] = g1 * p1[j] * (zk[j] - q1);
-      p2[j] = g2 * p2[j] * (zk[j] - q2);
-    }
-    store_dy_row_wide<NJ>(dy + i * ld, ld, K, lane, p1);
-    store_dy_row_wide<NJ>(dy + (b + i) * ld, ld, K, lane, p2);
-  }
-  const float s = block_sum_256(acc);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// launch KERNEL<ceil(k / 64)> for 64 < k <= PQLK_C51_MAX_ATOMS
-#define C51_WIDE_LAUNCH(KERNEL, k, blocks, stream, ...)                                                               \
+// launch KERNEL<ceil(k / 64)> for 2 <= k <= PQLK_C51_MAX_ATOMS
+#define C51_LAUNCH(KERNEL, k, blocks, stream, ...)                                                                    \
   do {                                                                                                                \
     const int nj__ = ((int)(k) + 63) / 64;                                                                            \
-    if (nj__ == 2) hipLaunchKernelGGL(KERNEL<2>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);            \
+    if (nj__ == 1) hipLaunchKernelGGL(KERNEL<1>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);            \
+    else if (nj__ == 2) hipLaunchKernelGGL(KERNEL<2>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);       \
     else if (nj__ == 3) hipLaunchKernelGGL(KERNEL<3>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);       \
     else hipLaunchKernelGGL(KERNEL<4>, dim3(blocks), dim3(256), 0, pqlk_s(stream), __VA_ARGS__);                      \
   } while (0)
@@ -420,56 +369,9 @@ extern "C" int pqlk_c51_project(const float* p, const float* rew, const float* d
   const float dz = (float)(((double)v_max - (double)v_min) / (double)(k - 1));
   int blocks = (int)((b + 3) / 4);
   if (blocks > 4096) blocks = 4096;
-  if (k <= 64)
-    hipLaunchKernelGGL(k_c51_project, dim3(blocks), dim3(256), 0, pqlk_s(stream), p, rew, done, support, gamma_n, v_min,
-                       v_max, dz, (int)k, b, out);
-  else
-    C51_WIDE_LAUNCH(k_c51_project_wide, k, blocks, stream, p, rew, done, support, gamma_n, v_min, v_max, dz, (int)k, b, out);
+  C51_LAUNCH(k_c51_project, k, blocks, stream, p, rew, done, support, gamma_n, v_min, v_max, dz, (int)k, b, out);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
-}
-
-__global__ __launch_bounds__(256) void k_c51_bce(const float* __restrict__ logits, const float* __restrict__ logits_t,
-                                                 int64_t ld, int K, const float* __restrict__ rew,
-                                                 const float* __restrict__ done, const float* __restrict__ support,
-                                                 float gamma_n, float v_min, float v_max, float dz, int64_t b,
-                                                 float* __restrict__ dy, float* __restrict__ proj_out,
-                                                 float* __restrict__ part) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nw = (int64_t)gridDim.x * 4;
-  const bool valid = lane < K;
-  const float zk = valid ? support[lane] : 0.f;
-  const float inv_numel = 1.0f / ((float)b * (float)K);
-  float acc = 0.f;
-  for (int64_t i = wave; i < b; i += nw) {
-    const float r = rew[i], d = done[i];
-    // target pmf: min of the two projected target distributions (pql_v_learner.py:83-102)
-    const float pt1 = wave_softmax(valid ? logits_t[i * ld + lane] : 0.f, valid);
-    const float pt2 = wave_softmax(valid ? logits_t[(b + i) * ld + lane] : 0.f, valid);
-    const float pr1 = project_row<64>(pt1, zk, r, d, gamma_n, v_min, v_max, dz, K, lane);
-    const float pr2 = project_row<64>(pt2, zk, r, d, gamma_n, v_min, v_max, dz, K, lane);
-    const float t = fminf(pr1, pr2);
-    if (proj_out && valid) proj_out[i * K + lane] = t;
-#pragma unroll
-    for (int net = 0; net < 2; ++net) {
-      const int64_t row = (int64_t)net * b + i;
-      const float pc = wave_softmax(valid ? logits[row * ld + lane] : 0.f, valid);
-      float le = 0.f, gp = 0.f;
-      if (valid) {
-        // F.binary_cross_entropy: (t-1)*max(log(1-p),-100) - t*max(log(p),-100); grad (p-t)/max((1-p)p,1e-12)
-        le = (t - 1.f) * fmaxf(logf(1.f - pc), -100.f) - t * fmaxf(logf(pc), -100.f);
-        gp = (pc - t) / fmaxf((1.f - pc) * pc, 1e-12f) * inv_numel;
-      }
-      acc += le;
-      const float dot = wave_sum(gp * pc);
-      const float dl = valid ? (gp - dot) * pc : 0.f;  // softmax backward
-      if (lane < ld) dy[row * ld + lane] = dl;
-      for (int c = 64 + lane; c < ld; c += 64) dy[row * ld + c] = 0.f;
-    }
-  }
-  const float s = block_sum_256(acc);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 extern "C" int pqlk_c51_bce_loss(const float* logits, const float* logits_t, int64_t ld, int32_t k, const float* rew,
@@ -482,20 +384,11 @@ extern "C" int pqlk_c51_bce_loss(const float* logits, const float* logits_t, int
   PQLK_REQUIRE(k <= PQLK_C51_MAX_ATOMS, PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(ld % 32 == 0 && ld >= k, PQLK_E_ALIGN);
   const float dz = (float)(((double)v_max - (double)v_min) / (double)(k - 1));
-  int blocks = (int)((b + 3) / 4);
-  if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
-  if (k <= 64)
-    hipLaunchKernelGGL(k_c51_bce, dim3(blocks), dim3(256), 0, pqlk_s(stream), logits, logits_t, ld, (int)k, rew, done,
-                       support, gamma_n, v_min, v_max, dz, b, dy, proj_out, scratch);
-  else
-    C51_WIDE_LAUNCH(k_c51_bce_wide, k, blocks, stream, logits, logits_t, ld, (int)k, rew, done, support, gamma_n, v_min, v_max,
-                    dz, b, dy, proj_out, scratch);
+  const int blocks = loss_blocks(b, k);
+  C51_LAUNCH(k_c51_bce, k, blocks, stream, logits, logits_t, ld, (int)k, rew, done, support, gamma_n, v_min, v_max, dz, b, dy,
+             proj_out, scratch);
   PQLK_LAUNCH_CHECK();
-  if (!loss_out) return PQLK_OK;   // partials stay in scratch[0, pqlk_loss_parts(b, k))
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks,
-                     1.0f / ((float)b * (float)k), loss_out, slot_dev, (int)ring_len);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
+  return fold_partials(scratch, blocks, 1.0f / ((float)b * (float)k), loss_out, slot_dev, ring_len, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -518,34 +411,34 @@ __global__ __launch_bounds__(256) void k_dpg_scalar(const float* __restrict__ q,
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
+template <int NJ>
 __global__ __launch_bounds__(256) void k_dpg_dist(const float* __restrict__ logits, int64_t ld, int K,
                                                   const float* __restrict__ support, int64_t b, float* __restrict__ dy,
                                                   float* __restrict__ part) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nw = (int64_t)gridDim.x * 4;
-  const bool valid = lane < K;
-  const float zk = valid ? support[lane] : 0.f;
   const float g = -1.0f / (float)b;
+  float zk[NJ];
+  load_row<NJ>(support, K, lane, zk);
   float acc = 0.f;
   for (int64_t i = wave; i < b; i += nw) {
-    const float p1 = wave_softmax(valid ? logits[i * ld + lane] : 0.f, valid);
-    const float p2 = wave_softmax(valid ? logits[(b + i) * ld + lane] : 0.f, valid);
-    const float q1 = wave_sum(p1 * zk), q2 = wave_sum(p2 * zk);  // E[z] (mlp.py:258-259)
+    float p1[NJ], p2[NJ];
+    load_row<NJ>(logits + i * ld, K, lane, p1);
+    load_row<NJ>(logits + (b + i) * ld, K, lane, p2);
+    wave_softmax<NJ>(p1, K, lane);
+    wave_softmax<NJ>(p2, K, lane);
+    const float q1 = wave_dot<NJ>(p1, zk), q2 = wave_dot<NJ>(p2, zk);  // E[z] (mlp.py:258-259)
     if (lane == 0) acc += fminf(q1, q2);
     const float g1 = q1 < q2 ? g : (q1 == q2 ? 0.5f * g : 0.f);
     const float g2 = q2 < q1 ? g : (q1 == q2 ? 0.5f * g : 0.f);
-    // dQ/dlogit_k = p_k (z_k - Q)
-    const float d1 = valid ? g1 * p1 * (zk - q1) : 0.f;
-    const float d2 = valid ? g2 * p2 * (zk - q2) : 0.f;
-    if (lane < ld) {
-      dy[i * ld + lane] = d1;
-      dy[(b + i) * ld + lane] = d2;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {   // dQ/dlogit_k = p_k (z_k - Q)
+      p1[j] = g1 * p1[j] * (zk[j] - q1);
+      p2[j] = g2 * p2[j] * (zk[j] - q2);
     }
-    for (int c = 64 + lane; c < ld; c += 64) {
-      dy[i * ld + c] = 0.f;
-      dy[(b + i) * ld + c] = 0.f;
-    }
+    store_dy_row<NJ>(dy + i * ld, ld, K, lane, p1);
+    store_dy_row<NJ>(dy + (b + i) * ld, ld, K, lane, p2);
   }
   const float s = block_sum_256(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
@@ -559,26 +452,14 @@ static int dpg_loss_impl(const float* q, int64_t ld, int32_t k, const float* sup
   PQLK_REQUIRE(b > 0 && k >= 1, PQLK_E_SHAPE);
   PQLK_REQUIRE(k <= PQLK_C51_MAX_ATOMS, PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(ld % 32 == 0 && ld >= k, PQLK_E_ALIGN);
-  int blocks;
-  if (k == 1) {
-    blocks = (int)((b + 255) / 256);
-    if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
+  PQLK_REQUIRE(k == 1 || support, PQLK_E_NULL);
+  const int blocks = loss_blocks(b, k);
+  if (k == 1)
     hipLaunchKernelGGL(k_dpg_scalar, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, ld, b, dy, scratch, owner);
-  } else {
-    PQLK_REQUIRE(support, PQLK_E_NULL);
-    blocks = (int)((b + 3) / 4);
-    if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
-    if (k <= 64)
-      hipLaunchKernelGGL(k_dpg_dist, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, ld, (int)k, support, b, dy, scratch);
-    else
-      C51_WIDE_LAUNCH(k_dpg_dist_wide, k, blocks, stream, q, ld, (int)k, support, b, dy, scratch);
-  }
+  else
+    C51_LAUNCH(k_dpg_dist, k, blocks, stream, q, ld, (int)k, support, b, dy, scratch);
   PQLK_LAUNCH_CHECK();
-  if (!loss_out) return PQLK_OK;   // partials stay in scratch[0, pqlk_loss_parts(b, k))
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks, -1.0f / (float)b, loss_out,
-                     slot_dev, (int)ring_len);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
+  return fold_partials(scratch, blocks, -1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
 }
 
 extern "C" int pqlk_dpg_loss(const float* q, int64_t ld, int32_t k, const float* support, int64_t b, float* dy,
@@ -593,11 +474,4 @@ extern "C" int pqlk_dpg_loss_owner(const float* q, int64_t ld, int32_t k, const 
                                    float* loss_out, const int32_t* slot_dev, int32_t ring_len, float* scratch,
                                    uint8_t* owner, pqlk_stream_t stream) {
   return dpg_loss_impl(q, ld, k, support, b, dy, loss_out, slot_dev, ring_len, scratch, owner, stream);
-}
-
-// number of per-block loss partials the loss entry points leave in `scratch` (k = 1: scalar heads; k > 1: one wave per row)
-extern "C" int32_t pqlk_loss_parts(int64_t b, int32_t k) {
-  int64_t blocks = k <= 1 ? (b + 255) / 256 : (b + 3) / 4;
-  if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
-  return (int32_t)blocks;
 }

@@ -183,17 +183,13 @@ extern "C" int pqlk_per_update(float* tree, int64_t capacity, float* pmax, const
 }
 
 // ------------------------------------------------------------------------------------------------ sampling and weights
-__global__ __launch_bounds__(256) void k_per_sample(const float* __restrict__ tree, PerGeom g, const float* __restrict__ u, int64_t b,
-                                                    int64_t* __restrict__ idx_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (k >= b) return;
-  const float total = per_total(tree + g.off[g.levels - 1], lane);
-  const float seg = total / (float)b;
-  float resid = ((float)k + u[k]) * seg;
+// One wave's walk from the top level to a leaf: at each level the first child with a non-zero value whose inclusive prefix
+// exceeds the residual (else the last non-zero child).  -> the row, and in every lane that row's leaf value.
+__device__ __forceinline__ int64_t per_walk(const float* __restrict__ tree, const PerGeom& g, float resid, int lane, float* leaf) {
   int64_t node = 0;   // the node whose children are being looked at (at the top level: the virtual root)
+  float c = 0.f;
   for (int l = g.levels - 1; l >= 0; --l) {
-    const float c = tree[g.off[l] + node * 64 + lane];
+    c = tree[g.off[l] + node * 64 + lane];
     const float incl = wave_prefix_incl(c, lane);
     const unsigned long long nonzero = __ballot(c != 0.f);
     const unsigned long long over = __ballot(incl > resid) & nonzero;
@@ -205,6 +201,24 @@ __global__ __launch_bounds__(256) void k_per_sample(const float* __restrict__ tr
     node = node * 64 + j;
     if (node >= g.n[l]) node = g.n[l] - 1;   // (cannot happen while the pads are zero; keeps a corrupted buffer from leading out of it)
   }
+  *leaf = __shfl(c, (int)(node & 63), 64);   // level 0's children are the leaves: lane (node mod 64) holds leaf[node]
+  return node;
+}
+
+// importance weight of a row with leaf value `leaf` = priority^alpha: (N P(i))^-beta
+__device__ __forceinline__ float per_weight(float n_valid, float leaf, float total, float beta) {
+  return per_pow((n_valid * leaf) / total, -beta);
+}
+
+__global__ __launch_bounds__(256) void k_per_sample(const float* __restrict__ tree, PerGeom g, const float* __restrict__ u, int64_t b,
+                                                    int64_t* __restrict__ idx_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= b) return;
+  const float total = per_total(tree + g.off[g.levels - 1], lane);
+  const float seg = total / (float)b;
+  float leaf;
+  const int64_t node = per_walk(tree, g, ((float)k + u[k]) * seg, lane, &leaf);
   if (lane == 0) idx_out[k] = node;
 }
 
@@ -217,7 +231,7 @@ __global__ __launch_bounds__(256) void k_per_weights(const float* __restrict__ t
   float w = 0.f;
   if (i < b) {
     const int64_t r = idx[i];
-    if (r >= 0 && r < capacity) w = per_pow((n_valid * tree[r]) / total, -beta);
+    if (r >= 0 && r < capacity) w = per_weight(n_valid, tree[r], total, beta);
     w_out[i] = w;
   }
   w = wave_max(w);
@@ -249,8 +263,8 @@ extern "C" int pqlk_per_weights(const float* tree, int64_t capacity, const int64
 
 // ------------------------------------------------------------------------------------------------ a run of steps in one launch
 // The samples and weights of `steps` batches drawn from the tree as it stands: sample k of step s is
-// k_per_sample's walk for stratum k of b with u = r[s b + k] 2^-24, and its weight k_per_weights' expression on the leaf the walk
-// ended at.  One wave per sample, a row of blocks (blockIdx.y) per step.  The maximum of a step's weights is an integer atomic max like k_per_weights'; a wave
+// per_walk for stratum k of b with u = r[s b + k] 2^-24, and its weight per_weight on the leaf the walk ended at.  One wave per
+// sample, a row of blocks (blockIdx.y) per step.  The maximum of a step's weights is an integer atomic max like k_per_weights'; a wave
 // whose weight does not exceed what it reads there first leaves the atomic out (the word only grows, so whatever it reads is at
 // most the final maximum and the result is the same bits).
 __global__ __launch_bounds__(256) void k_per_sample_steps(const float* __restrict__ tree, PerGeom g, const int64_t* __restrict__ r,
@@ -264,25 +278,10 @@ __global__ __launch_bounds__(256) void k_per_sample_steps(const float* __restric
   const float total = per_total(tree + g.off[g.levels - 1], lane);
   const float seg = total / (float)b;
   const float u = (float)r[i] * 0x1p-24f;   // exact: r < 2^24
-  float resid = ((float)k + u) * seg;
-  int64_t node = 0;
-  float c = 0.f;
-  for (int l = g.levels - 1; l >= 0; --l) {
-    c = tree[g.off[l] + node * 64 + lane];
-    const float incl = wave_prefix_incl(c, lane);
-    const unsigned long long nonzero = __ballot(c != 0.f);
-    const unsigned long long over = __ballot(incl > resid) & nonzero;
-    int j = 0;
-    if (over) j = __ffsll((long long)over) - 1;
-    else if (nonzero) j = 63 - __clzll((long long)nonzero);
-    const float below = __shfl_up(incl, 1, 64);
-    resid -= __shfl(lane > 0 ? below : 0.f, j, 64);
-    node = node * 64 + j;
-    if (node >= g.n[l]) node = g.n[l] - 1;   // (as in k_per_sample: not while the pads are zero)
-  }
-  const float leaf = __shfl(c, (int)(node & 63), 64);   // level 0's children are the leaves: lane (node mod 64) holds leaf[node]
+  float leaf;
+  const int64_t node = per_walk(tree, g, ((float)k + u) * seg, lane, &leaf);
   if (lane == 0) {
-    const float w = per_pow((n_valid * leaf) / total, -beta);
+    const float w = per_weight(n_valid, leaf, total, beta);
     idx_out[i] = node;
     w_out[i] = w;
     unsigned int* m = reinterpret_cast<unsigned int*>(wmax_out + s);

@@ -19,9 +19,9 @@ SLACK = 64            # floats behind every buffer
 
 # ---------------------------------------------------------------- caps (loss.hip, optim.hip) and the shapes that cross them
 LOSS_MAX_BLOCKS = 1024
-TD_ROWS_PER_BLOCK = 256                                   # k_td_mse, k_dpg_scalar: one row per thread
-C51_ROWS_PER_BLOCK = 4                                    # k_c51_bce, k_dpg_dist: one row per wave
-PROJECT_MAX_BLOCKS, PROJECT_ROWS_PER_BLOCK = 4096, 4      # k_c51_project
+TD_ROWS_PER_BLOCK = 256                                   # k_td_mse<PER>, k_dpg_scalar: one row per thread
+C51_ROWS_PER_BLOCK = 4                                    # k_c51_bce<NJ>, k_dpg_dist<NJ>: one row per wave
+PROJECT_MAX_BLOCKS, PROJECT_ROWS_PER_BLOCK = 4096, 4      # k_c51_project<NJ>
 SUMSQ_TRIP = 1024 * 256 * 4                               # k_sumsq: floats covered by one trip
 ADAMW_VEC_TRIP = 2048 * 256 * 4                           # k_adamw, 16-byte path
 ADAMW_SCALAR_TRIP = 2048 * 256                            # k_adamw, scalar path

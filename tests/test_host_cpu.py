@@ -537,6 +537,25 @@ def test_no_kernel_of_the_library_goes_through_scratch():
         assert v.get("vgpr_count", 0) <= 512 and v.get("max_flat_workgroup_size", 0) <= 1024, k
 
 
+def test_c51_kernels_with_one_atom_per_lane_hold_no_lds_image():
+    """The C51 kernels are one template over NJ = atoms per lane.  NJ = 1 (K <= 64) projects with cross-lane shuffles and must not
+    allocate the LDS image of the NJ > 1 instances, which would cost the shipped 51-atom path its occupancy: static LDS is
+    block_sum_256's four floats, or nothing.  NJ > 1: sizeof(C51Image) * 4 waves (+ those four floats)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources as kr
+    if not os.path.exists(f"{kr.LLVM}/llvm-readelf"):
+        pytest.skip("no llvm-readelf")
+    res = kr.resources()
+    lds = lambda name: res[f"void {name}"]["group_segment_fixed_size"]  # noqa: E731
+    assert lds("k_c51_project<1>") == 0
+    assert lds("k_c51_bce<1>") == 16 and lds("k_dpg_dist<1>") == 16
+    for nj in (2, 3, 4):
+        assert lds(f"k_c51_bce<{nj}>") == 4096 * 4 + 16
+        assert lds(f"k_c51_project<{nj}>") == 4096 * 4
+        assert lds(f"k_dpg_dist<{nj}>") == 16
+
+
 def test_gather_kernels_keep_their_counted_waits():
     """The gather kernels are chains of loads and stores on gfx9's one in-order vector-memory counter; what they cost hangs on the
     compiler waiting with COUNTED `s_waitcnt vmcnt(n)`.  Round 4 twice produced a kernel with the same bits and 14 full drains

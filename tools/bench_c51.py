@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Times the C51 loss kernels across the 64-atom seam: `pqlk_c51_bce_loss` and `pqlk_c51_project` at K = 51 (one atom per lane,
-cross-lane projection), 101 and 256 (several atoms per lane, projection through the wave's LDS image), B = 8192.  Each point is
+"""Times the C51 loss kernels across the 64-atom seam: `pqlk_c51_bce_loss`, `pqlk_c51_project` and the distributional
+`pqlk_dpg_loss` at K = 51 (the NJ = 1 instances: one atom per lane, cross-lane projection), 101 and 256 (several atoms per lane,
+projection through the wave's LDS image), B = 8192.  Each point is
 one hipGraph of ITERS back-to-back launches timed with HIP events; the points are replayed in turn, ROUNDS times, in one
 process, so that they share whatever else the card is doing.  Inputs as a learner meets them: logits N(0, 1), rewards over
 1.2 x the support, one row in ten terminal (a terminal row is the projection's longest walk: one bin collects every atom).
@@ -18,6 +19,7 @@ import torch  # noqa: E402
 from pql_amd import _lib as L  # noqa: E402
 
 KS = (51, 101, 256)
+ENTRY = dict(bce="pqlk_c51_bce_loss", project="pqlk_c51_project", dpg="pqlk_dpg_loss")
 V_MIN, V_MAX, GAMMA_N = -10.0, 10.0, 0.99 ** 3
 
 
@@ -39,6 +41,14 @@ def make_point(kind, K, B, dev):
             L.check(L.lib.pqlk_c51_bce_loss(L.ptr(lg), L.ptr(lt), ld, K, L.ptr(rew), L.ptr(done), L.ptr(z), GAMMA_N, V_MIN, V_MAX, B,
                                             L.ptr(dy), L.ptr(lo), None, 0, None, L.ptr(scr), st()))
         nbytes = B * (4 * K * 4 + 8 + 2 * ld * 4)          # four logit rows in, two dy rows (pads included) out
+    elif kind == "dpg":
+        lg = torch.zeros((2, B, ld), **f)
+        lg[:, :, :K].normal_(generator=g)
+        dy, scr, lo = torch.empty((2, B, ld), **f), torch.empty(1024, **f), torch.empty(1, **f)
+
+        def launch():
+            L.check(L.lib.pqlk_dpg_loss(L.ptr(lg), ld, K, L.ptr(z), B, L.ptr(dy), L.ptr(lo), None, 0, L.ptr(scr), st()))
+        nbytes = B * (2 * K * 4 + 2 * ld * 4)              # two logit rows in, two dy rows (pads included) out
     else:
         p = torch.softmax(torch.randn((B, K), generator=g, **f), 1).contiguous()
         out = torch.empty((B, K), **f)
@@ -62,7 +72,7 @@ def main():
     torch.cuda.set_device(dev)
     points = []
     side = torch.cuda.Stream()
-    for kind in ("bce", "project"):
+    for kind in ("bce", "project", "dpg"):
         for K in KS:
             launch, nbytes = make_point(kind, K, a.rows, dev)
             launch()                                       # first launch outside the capture (loads the code object)
@@ -72,8 +82,8 @@ def main():
             with torch.cuda.graph(graph, stream=side):
                 for _ in range(a.iters):
                     launch()
-            # the BCE entry point is two launches (the loss kernel and the one-block fold of its partials): both are in the figure
-            points.append(dict(kernel="pqlk_c51_bce_loss" if kind == "bce" else "pqlk_c51_project", K=K, ld=L.ld(K) if kind == "bce" else K,
+            # the loss entry points are two launches (the loss kernel and the one-block fold of its partials): both are in the figure
+            points.append(dict(kernel=ENTRY[kind], K=K, ld=K if kind == "project" else L.ld(K),
                                bytes=nbytes, graph=graph, launch=launch, us=[]))
     for p in points:                                       # warm-up replay of every graph
         p["graph"].replay()
@@ -87,7 +97,8 @@ def main():
     for p in points:
         med = statistics.median(p["us"])
         res.append(dict(kernel=p["kernel"], K=p["K"], ld=p["ld"], rows=a.rows, bytes_moved=p["bytes"], us_median=round(med, 3),
-                        us_min=round(min(p["us"]), 3), us_max=round(max(p["us"]), 3), tb_per_s=round(p["bytes"] / med / 1e6, 3)))
+                        us_min=round(min(p["us"]), 3), us_max=round(max(p["us"]), 3), us_rounds=[round(t, 3) for t in p["us"]],
+                        tb_per_s=round(p["bytes"] / med / 1e6, 3)))
         print(f"{p['kernel']:18s} K={p['K']:3d}: {med:8.2f} us per call (min {min(p['us']):.2f}, max {max(p['us']):.2f}), "
               f"{p['bytes'] / 1e6:.2f} MB -> {p['bytes'] / med / 1e6:.3f} TB/s", flush=True)
     doc = dict(tool="tools/bench_c51.py", device=torch.cuda.get_device_name(dev), rows=a.rows, launches_per_graph=a.iters, rounds=a.rounds,

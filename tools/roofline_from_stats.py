@@ -86,7 +86,7 @@ def main():
             ("k_adamw", "clip + AdamW + Polyak + re-pack (+ loss fold)", params_c * 36.0, "byte"),
             ("void k_replay_gather_fast", "fused replay gather + normalise + cat (one launch per 8 steps)", per_batch, "byte"),
             ("k_philox_draws", "randint + normal draws of 8 steps (torch's numbers)", B * 8 + B * A * 4, "byte"),
-            ("k_td_mse", "TD target + MSE loss + dL/dQ", B * (4 * 4 + 2 * 4 + 2 * 4), "byte"),
+            ("void k_td_mse<", "TD target + MSE loss + dL/dQ", B * (4 * 4 + 2 * 4 + 2 * 4), "byte"),
         ]
     print(f"| kernel | role | launches / {who} step | avg us / launch | us / {who} step | work / step | achieved | roof | frac |")
     print("|---|---|---|---|---|---|---|---|---|")
