@@ -15,6 +15,7 @@ import torch
 
 import detdata as dd
 import reduction_cases as rc
+from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -33,27 +34,6 @@ def dev():
 def ref():
     from oracle import pql_ref_cpu
     return pql_ref_cpu
-
-
-class Guarded:
-    """A device tensor of `shape` with `fill` in SLACK elements behind it and in `off` elements in front (off = 1 also puts the
-    tensor one float past a 16-byte boundary)."""
-
-    def __init__(self, dev, shape, fill, init=None, off=0, dtype=torch.float32):
-        n = int(np.prod(shape))
-        self.full = torch.full((off + n + SLACK,), fill, dtype=dtype, device=dev)
-        self.t = self.full[off: off + n].view(*shape)
-        self.n, self.off, self.fill = n, off, fill
-        if init is not None:
-            self.t.copy_(init if torch.is_tensor(init) else T(np.asarray(init)))
-        assert self.t.data_ptr() % 16 == (4 * off) % 16
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.t.data_ptr())
-
-    def intact(self):
-        return bool((self.full[: self.off] == self.fill).all()) and bool((self.full[self.off + self.n:] == self.fill).all())
 
 
 def _g(dev, arr, fill, off=0):
