@@ -503,6 +503,48 @@ int pqlk_per_update(float* tree, int64_t capacity, float* pmax, const int64_t* i
                     float alpha, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Quantile-regression twin critic (QR-DQN, Dabney et al. 2018).  The reference has no such critic; the formulas below are the
+ * paper's, adapted to twin critics.  No support, no projection, no v_min / v_max: a head learns the locations of N quantiles of
+ * fixed probability.
+ *
+ * Inputs.  N = n quantiles, 2 <= N <= PQLK_QR_MAX_QUANTILES; kappa > 0, the Huber threshold; tau_j = (2 j + 1) / (2 N), formed
+ * in fp32 as (float)(2 j + 1) / (float)(2 N).  theta: the current heads, (2, B, ld) with quantile j in column j, ld = pqlk_ld(N)
+ * (any multiple of 32 >= N is taken); theta_t: the target heads, same layout.
+ * Target net.  S_i = sum_j theta_t[i, b, j], one wave butterfly over 64 lanes (offsets 32, 16, 8, 4, 2, 1; lanes >= N hold 0).
+ * i* = 1 if S_1 < S_0, else 0: a tie takes net 0.  Clipped double-Q at the level of the means: one choice per row, no sorting.
+ * Target quantiles.  T_k = r + ((1 - d) * gamma_n) * theta_t[i*, b, k], in this order (pqlk_td_mse_loss's).
+ * Loss.  u_ijk = T_k - theta[i, b, j];  rho(u; tau) = |tau - 1{u < 0}| * H(u) / kappa;  H(u) = 0.5 u^2 for |u| <= kappa, else
+ * kappa (|u| - 0.5 kappa);  L = sum_i (1 / (B N)) sum_{b, j, k} rho(u_ijk; tau_j): the paper's sum over current quantiles and mean
+ * over target quantiles, then a batch mean, then the twin nets added.  Per (i, b, j) the k terms |tau_j - 1{u < 0}| * H(u) are
+ * added in increasing k; per (b, j) the two nets' sums are added and divided by kappa once.  Each per-block partial is a plain sum
+ * of these; the fold scale is 1 / (B N), formed as 1.0f / ((float)B * (float)N): the convention of pqlk_loss_parts(b, k > 1).
+ * Gradient.  dy[i, b, j] = -(1 / (B N)) * sum_k |tau_j - 1{u_ijk < 0}| * clamp(u_ijk, -kappa, kappa) / kappa: the k terms
+ * |tau_j - 1{u < 0}| * clamp(u) are added in increasing k, the sum is divided by kappa, multiplied by 1 / (B N) and negated.
+ * Pad columns [N, ld) of dy are written as zero.
+ * Prioritized variant (_per).  wh = w[b] / wmax[0] multiplies the row's loss terms ((l_0 + l_1) / kappa, before it joins the
+ * partial) and the row's dy (before the negation); abs_td_out[b] = max_i |mean_k T_k - mean_j theta[i, b, j]|, each mean a wave
+ * butterfly times 1.0f / (float)N.  The plain entry never reads w, wmax or abs_td_out; with every w and wmax 1.0 the weighted one
+ * gives its bits.
+ * DPG.  Q_i = (sum_j theta[i, b, j]) * (1 / N);  L = -(1 / B) sum_b min(Q_0, Q_1);  dy[i, b, j] = -share_i / (B N), share_i = 1
+ * for the smaller net and 0 for the other, 0.5 each on a tie (torch.min's backward, as pqlk_dpg_loss); pad columns zero.
+ *
+ * loss_out / slot_dev / ring_len / scratch: as for every loss above; loss_out = NULL leaves pqlk_loss_parts(b, n) partials in
+ * scratch.  No float atomics, every reduction in a fixed order: two launches on the same inputs give the same bits.
+ * Errors, before any launch: PQLK_E_NULL a NULL pointer; PQLK_E_SHAPE b <= 0, kappa <= 0 or a ring without a length;
+ * PQLK_E_UNSUPPORTED n < 2 or n > PQLK_QR_MAX_QUANTILES; PQLK_E_ALIGN ld not a multiple of 32 or ld < n.
+ * ---------------------------------------------------------------------------------------------- */
+#define PQLK_QR_MAX_QUANTILES 64
+int pqlk_qr_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew, const float* done,
+                       float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                       int32_t ring_len, float* scratch, pqlk_stream_t stream);
+int pqlk_qr_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew, const float* done,
+                           float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                           int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out,
+                           pqlk_stream_t stream);
+int pqlk_dpg_loss_quantile(const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
+                           const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser: clip_grad_norm_ + AdamW (+ Polyak) over flat arenas
  * (pql_v_learner.py:124-133, pql_p_learner.py:87-96, pql/utils/torch_util.py:9-12).
  *   g *= grad_scale   (1/world_size after a data-parallel sum all-reduce; 1.0 otherwise)

@@ -21,6 +21,7 @@ INFO_F32, INFO_U8 = 0, 1  # PqlInfoKey.dtype (PQLK_INFO_*)
 INFO_LAST, INFO_ALL_EPISODE, INFO_ALL_STEP = 0, 1, 2   # PqlInfoKey.mode
 ACT_NONE, ACT_TANH, ACT_TANH_NOISE = 0, 1, 2
 C51_MAX_ATOMS = 256       # PQLK_C51_MAX_ATOMS: the C51 loss kernels hold one row's atoms in one wave, four per lane at most
+QR_MAX_QUANTILES = 64     # PQLK_QR_MAX_QUANTILES: the quantile loss kernels hold one quantile of both nets per lane
 
 
 class PqlReplayDesc(C.Structure):
@@ -101,6 +102,9 @@ PROTOTYPES = {
     "pqlk_per_sample_steps": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _F, _P, _P, _P, _P]),
     "pqlk_td_mse_loss_per": (C.c_int, [_P, _P, _I64, _P, _P, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "pqlk_per_update": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _F, _F, _P]),
+    "pqlk_qr_huber_loss": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P]),
+    "pqlk_qr_huber_loss_per": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "pqlk_dpg_loss_quantile": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P, _I32, _P, _P]),
     "pqlk_clip_adamw_polyak": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pqlk_clip_adamw_polyak_pack": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pqlk_adamw_polyak_fused": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P,

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic, td_mse_loss
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic, qr_huber_loss, td_mse_loss
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.prioritized_replay import per_beta, per_cfg  # noqa: F401  (per_beta: imported from here by its users)
@@ -144,6 +144,10 @@ class ActorCriticBase(PQLActor):
     def _one_layout(self):
         return hasattr(self.critic, "layout")
 
+    @property
+    def _quantile(self):
+        return getattr(self.critic, "head", "scalar") == "quantile"
+
     def _critic_forward(self, ws, net, x, slot):
         """Q of `net` (the critic or its target) on x (B, ld_sa) -> ((2, B, ld) output, ld).  slot: "c" (the stash `_critic_grads` /
         `_critic_dx` read) or "t" (the target's)."""
@@ -186,13 +190,21 @@ class ActorCriticBase(PQLActor):
         memory = ws.get("per")
         # with prioritized replay: the importance weights on the loss and its gradient, then |TD| back into the tree
         per = {} if memory is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
-        td_mse_loss(q, qt, ld, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep), ws["B"], ws["dy"], self.closs, self.copt.step,
-                    ws["scratch"], self.device, **per)
+        if self._quantile:   # twin quantile heads: the quantile Huber loss against the target net with the smaller mean
+            qr_huber_loss(q, qt, ld, self.critic.num_quantiles, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep),
+                          float(algo.get("huber_kappa", 1.0)), ws["B"], ws["dy"], self.closs, self.copt.step, ws["scratch"], self.device, **per)
+        else:
+            td_mse_loss(q, qt, ld, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep), ws["B"], ws["dy"], self.closs, self.copt.step,
+                        ws["scratch"], self.device, **per)
         if memory is not None:
             memory.update_priorities(ws["idx"], ws["abs_td"])
 
     def _dpg_loss(self, ws, q, ld):
         """-mean(min q): d loss / d q -> ws["dy"], the loss -> the actor's ring."""
+        if self._quantile:   # q of a net = the mean of its quantile head
+            L.check(L.lib.pqlk_dpg_loss_quantile(L.ptr(q), ld, self.critic.num_quantiles, ws["B"], L.ptr(ws["dy"]), L.ptr(self.aloss),
+                                                 L.ptr(self.aopt.step), LOSS_RING, L.ptr(ws["scratch"]), L.stream(self.device)))
+            return
         L.check(L.lib.pqlk_dpg_loss(L.ptr(q), ld, 1, None, ws["B"], L.ptr(ws["dy"]), L.ptr(self.aloss), L.ptr(self.aopt.step), LOSS_RING,
                                     L.ptr(ws["scratch"]), L.stream(self.device)))
 

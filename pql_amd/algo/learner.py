@@ -18,7 +18,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.models import model_name_to_path
-from pql_amd.models.mlp import PackedWeights, check_num_atoms
+from pql_amd.models.mlp import PackedWeights, check_num_atoms, check_num_quantiles
 from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
@@ -98,6 +98,18 @@ def td_mse_loss(q, qt, ld, rew, done, gamma_n, B, dy, loss_out, step, scratch, d
         L.check(L.lib.pqlk_td_mse_loss(*head, L.stream(device)))
     else:
         L.check(L.lib.pqlk_td_mse_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), L.stream(device)))
+
+
+def qr_huber_loss(theta, theta_t, ld, n, rew, done, gamma_n, kappa, B, dy, loss_out, step, scratch, device, w=None, wmax=None, abs_td=None):
+    """The quantile Huber loss of twin quantile heads (n columns of the (2, B, ld) blocks) against the target net with the smaller
+    mean (include/pqlk.h): d loss / d theta -> dy, the partials -> scratch, the loss -> the ring as in `td_mse_loss`; with `w`, `wmax`,
+    `abs_td` the prioritized instance."""
+    head = (L.ptr(theta), L.ptr(theta_t), ld, int(n), L.ptr(rew), L.ptr(done), gamma_n, float(kappa), B, L.ptr(dy), L.ptr(loss_out), L.ptr(step),
+            LOSS_RING, L.ptr(scratch))
+    if w is None:
+        L.check(L.lib.pqlk_qr_huber_loss(*head, L.stream(device)))
+    else:
+        L.check(L.lib.pqlk_qr_huber_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), L.stream(device)))
 
 
 def f32_recip(*factors, sign=1.0):
@@ -250,6 +262,27 @@ def check_critic_class(cfg, fused_learner=None):
         if fused_learner is not None:
             raise ValueError(f"algo.cri_class=DoubleQLayerNorm cannot run in {fused_learner}, whose launch sequences are built on the fused "
                              f"MLP kernels: the class is for algo=ddpg_algo / algo=sac_algo (scripts/train_baselines.py)")
+    if is_quantile(algo):
+        if _cfg_get(algo, "distl", False):
+            raise ValueError("algo.distl=True is not supported with algo.cri_class=QuantileDoubleQ: algo.distl selects the C51 head and "
+                             "the class the quantile head -- drop algo.distl=True to train the quantile critic")
+        name = str(_cfg_get(algo, "name", ""))
+        if name in ("SAC", "CrossQ"):
+            why = "the entropy shift of the SAC target has" if name == "SAC" else "the BatchNorm critic has"
+            raise ValueError(f"algo.cri_class=QuantileDoubleQ cannot run with algo={name.lower()}_algo: {why} no N-wide head; the class "
+                             f"is for algo=pql_algo and algo=ddpg_algo")
+        if str(_cfg_get(algo, "target_dtype", "float32")) == "bfloat16":
+            raise ValueError("algo.target_dtype=bfloat16 is not supported with algo.cri_class=QuantileDoubleQ: the bf16 target forward "
+                             "has not been taken to the quantile head (use algo.target_dtype=float32)")
+        check_num_quantiles(_cfg_get(algo, "num_quantiles", 32))
+        kappa = _cfg_get(algo, "huber_kappa", 1.0)
+        if not float(kappa) > 0.0:
+            raise ValueError(f"algo.huber_kappa must be > 0, got {kappa!r}")
+
+
+def is_quantile(algo):
+    """Whether `algo.cri_class` names the quantile-regression critic."""
+    return str(_cfg_get(algo, "cri_class")).endswith("QuantileDoubleQ")
 
 
 def make_critic(cfg, obs_dim, action_dim, device):
@@ -268,6 +301,8 @@ def make_critic(cfg, obs_dim, action_dim, device):
         if distl:
             return cri_class(obs_dim, action_dim, v_min=algo.v_min, v_max=algo.v_max, num_atoms=algo.num_atoms, device=device,
                              hidden_layers=hidden).to(device)
+        if is_quantile(algo):
+            return cri_class(obs_dim, action_dim, num_quantiles=int(_cfg_get(algo, "num_quantiles", 32)), hidden_layers=hidden).to(device)
         return cri_class(obs_dim, action_dim, hidden_layers=hidden).to(device)
 
 

@@ -83,7 +83,8 @@ class PQLPLearner(Learner):
         # round 4: loss + partition + compact head in one launch, the actor's head backward inside the action-slice launch
         # (pqlk_dpg_backward_fused: 16 -> 13 launches per step); needs the loss fold of the optimiser launch and a fused critic forward
         K_atoms = int(getattr(self.critic, "num_atoms", 1))
-        ws["dpg_fused"] = bool(_cfg_get(self.cfg.algo, "dpg_fused", True) and self._fold_loss and K_atoms == 1 and self.pk_critic is not None
+        scalar = K_atoms == 1 and getattr(self.critic, "head", "scalar") == "scalar"
+        ws["dpg_fused"] = bool(_cfg_get(self.cfg.algo, "dpg_fused", True) and self._fold_loss and scalar and self.pk_critic is not None
                                and self.pk_critic.tensor is not None and self.pk_actor is not None and self.pk_actor.tensor is not None
                                and L.lib.pqlk_dpg_fused_ok(C.byref(cl.desc), C.byref(al.desc), B))
         # ... and then the critic reads its input where the two halves of torch.cat((obs, action)) already lie -- the actor's input
@@ -174,8 +175,14 @@ class PQLPLearner(Learner):
         q = output_view(cl, ws["acts_c"], B)
         K = int(getattr(self.critic, "num_atoms", 1))
         z = getattr(self.critic, "z_atoms", None) if K > 1 else None
-        L.check(L.lib.pqlk_dpg_loss_owner(L.ptr(q), cl.ld_out, K, L.ptr(z), B, L.ptr(ws["dy_c"]), None if self._fold_loss else L.ptr(self.loss_ring),
-                                          L.ptr(self.opt.step), LOSS_RING, L.ptr(ws["scratch"]), C.c_void_p(ws["owner"].data_ptr()), st))
+        quantile = getattr(self.critic, "head", "scalar") == "quantile"
+        if quantile:   # -mean(min of the two heads' means); no owner partition (K below: not the scalar head's)
+            K = self.critic.num_quantiles
+            L.check(L.lib.pqlk_dpg_loss_quantile(L.ptr(q), cl.ld_out, K, B, L.ptr(ws["dy_c"]), None if self._fold_loss else L.ptr(self.loss_ring),
+                                                 L.ptr(self.opt.step), LOSS_RING, L.ptr(ws["scratch"]), st))
+        else:
+            L.check(L.lib.pqlk_dpg_loss_owner(L.ptr(q), cl.ld_out, K, L.ptr(z), B, L.ptr(ws["dy_c"]), None if self._fold_loss else L.ptr(self.loss_ring),
+                                              L.ptr(self.opt.step), LOSS_RING, L.ptr(ws["scratch"]), C.c_void_p(ws["owner"].data_ptr()), st))
         # dX-only chain through the frozen critic; with scalar Q heads it runs over the samples partitioned by the net that
         # attained min(Q1, Q2): the other net's rows of every dZ are exactly zero (csrc/minnet.h)
         L.check(L.lib.pqlk_dpg_critic_backward(C.byref(cl.desc), L.ptr(self.critic.arena.data), L.ptr(ws["x_sa"]), ws["ld_sa"], B,
@@ -198,6 +205,8 @@ class PQLPLearner(Learner):
         algo = self.cfg.algo
         if self._fold_loss:
             K = int(getattr(self.critic, "num_atoms", 1))
+            if getattr(self.critic, "head", "scalar") == "quantile":
+                K = self.critic.num_quantiles
             apply_optimizer_fused(self.actor.layout, self.actor.arena.data, ws["grads"], self.opt, None, algo.actor_lr,
                                   algo.max_grad_norm, 0.0, self.pk_actor, None, ws["scratch"],
                                   ws["loss_parts"] if ws["dpg_fused"] else L.lib.pqlk_loss_parts(ws["B"], K),

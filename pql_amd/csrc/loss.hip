@@ -475,3 +475,151 @@ extern "C" int pqlk_dpg_loss_owner(const float* q, int64_t ld, int32_t k, const 
                                    uint8_t* owner, pqlk_stream_t stream) {
   return dpg_loss_impl(q, ld, k, support, b, dy, loss_out, slot_dev, ring_len, scratch, owner, stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Quantile regression (QR-DQN, Dabney et al. 2018) on twin critics: the law is written out in include/pqlk.h.  The reference has
+// no such critic.  Geometry of the C51 kernels: one wave per batch row, four rows per block, a row loop above LOSS_MAX_BLOCKS;
+// lane j holds quantile j of both nets (N <= 64), lanes >= N hold zeros and store the pad columns.  The target quantile T_k
+// lives in lane k; the k loop fetches it with a wave-uniform lane read (v_readlane: no LDS, no cross-lane traffic).
+//
+// Reduction order (what the tests' bounds count):
+//   S_i, the means of abs_td : wave_sum, the xor butterfly of pqlk_common.h (offsets 32 ... 1) over the 64 lanes;
+//   dy[i, b, j]             : one chain over k = 0 ... N-1 in lane j, then / kappa, * 1/(B N), (* wh), negated;
+//   loss                    : per lane and net one chain over k; (l0 + l1) / kappa (* wh) joins the lane's accumulator, one add
+//                             per row of the wave's row loop; then block_sum_256 (butterfly, then the four waves as
+//                             (w0 + w1) + (w2 + w3)) -> part[block]; then k_sum_partials / the optimiser's fold.
+__device__ __forceinline__ float lane_read(float v, int k) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+}
+
+// one (j, k) pair of one net: u = T_k - theta_j -> the gradient chain g and the loss chain l of lane j
+__device__ __forceinline__ void qr_term(float u, float tau, float kappa, float& g, float& l) {
+  const float wgt = fabsf(tau - (u < 0.f ? 1.f : 0.f));
+  const float a = fabsf(u);
+  const float h = a <= kappa ? 0.5f * (u * u) : kappa * (a - 0.5f * kappa);
+  g += wgt * fminf(fmaxf(u, -kappa), kappa);
+  l += wgt * h;
+}
+
+template <bool PER>
+__global__ __launch_bounds__(256) void k_qr_huber(const float* __restrict__ theta, const float* __restrict__ theta_t, int64_t ld,
+                                                  int N, const float* __restrict__ rew, const float* __restrict__ done,
+                                                  float gamma_n, float kappa, int64_t b, float* __restrict__ dy,
+                                                  float* __restrict__ part, const float* __restrict__ w,
+                                                  const float* __restrict__ wmax, float* __restrict__ abs_td) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const float inv_bn = 1.0f / ((float)b * (float)N);
+  const float tau = (float)(2 * lane + 1) / (float)(2 * N);
+  const bool on = lane < N;
+  float wm = 1.f;
+  if constexpr (PER) wm = wmax[0];
+  float acc = 0.f;
+  for (int64_t i = wave; i < b; i += nw) {
+    const float r = rew[i], d = done[i];
+    const float th0 = on ? theta[i * ld + lane] : 0.f, th1 = on ? theta[(b + i) * ld + lane] : 0.f;
+    const float t0 = on ? theta_t[i * ld + lane] : 0.f, t1 = on ? theta_t[(b + i) * ld + lane] : 0.f;
+    const float s0 = wave_sum(t0), s1 = wave_sum(t1);
+    const float ts = s1 < s0 ? t1 : t0;                 // clipped double-Q on the means: one net per row, a tie takes net 0
+    const float T = r + ((1.f - d) * gamma_n) * ts;     // lane k: T_k (k_td_mse's operation order)
+    float g0 = 0.f, g1 = 0.f, l0 = 0.f, l1 = 0.f;
+    for (int k = 0; k < N; ++k) {
+      const float tk = lane_read(T, k);
+      qr_term(tk - th0, tau, kappa, g0, l0);
+      qr_term(tk - th1, tau, kappa, g1, l1);
+    }
+    float row = (l0 + l1) / kappa;
+    float v0[1] = {(g0 / kappa) * inv_bn}, v1[1] = {(g1 / kappa) * inv_bn};
+    if constexpr (PER) {
+      const float wh = w[i] / wm;
+      row = wh * row;
+      v0[0] = wh * v0[0];
+      v1[0] = wh * v1[0];
+    }
+    if (on) acc += row;
+    v0[0] = -v0[0];
+    v1[0] = -v1[0];
+    store_dy_row<1>(dy + i * ld, ld, N, lane, v0);
+    store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v1);
+    if constexpr (PER) {   // |mean_k T_k - mean_j theta_j| of either net, the larger: the row's new priority
+      const float inv_n = 1.0f / (float)N;
+      const float mt = wave_sum(on ? T : 0.f) * inv_n;
+      const float m0 = wave_sum(th0) * inv_n, m1 = wave_sum(th1) * inv_n;
+      if (lane == 0) abs_td[i] = fmaxf(fabsf(mt - m0), fabsf(mt - m1));
+    }
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+template <bool PER>
+static int qr_huber_impl(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew, const float* done,
+                         float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev, int32_t ring_len,
+                         float* scratch, const float* w, const float* wmax, float* abs_td_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(theta && theta_t && rew && done && dy && scratch, PQLK_E_NULL);
+  PQLK_REQUIRE(!PER || (w && wmax && abs_td_out), PQLK_E_NULL);
+  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(b > 0 && kappa > 0.f, PQLK_E_SHAPE);
+  PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
+  const int blocks = loss_blocks(b, n);
+  hipLaunchKernelGGL(k_qr_huber<PER>, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, rew, done, gamma_n, kappa,
+                     b, dy, scratch, w, wmax, abs_td_out);
+  PQLK_LAUNCH_CHECK();
+  return fold_partials(scratch, blocks, 1.0f / ((float)b * (float)n), loss_out, slot_dev, ring_len, stream);
+}
+
+extern "C" int pqlk_qr_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                  const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                  const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
+  return qr_huber_impl<false>(theta, theta_t, ld, n, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, nullptr,
+                              nullptr, nullptr, stream);
+}
+
+extern "C" int pqlk_qr_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                      const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                      const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w, const float* wmax,
+                                      float* abs_td_out, pqlk_stream_t stream) {
+  return qr_huber_impl<true>(theta, theta_t, ld, n, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w, wmax,
+                             abs_td_out, stream);
+}
+
+// DPG on the quantile heads: Q_i = (sum_j theta[i, b, j]) * (1 / N) (wave_sum), L = -mean_b min(Q_0, Q_1); every quantile of the
+// smaller net gets -1 / (B N), on a tie both nets half of it (torch.min's backward, k_dpg_scalar).  Lane 0 carries the row's
+// min into the block's partial; the fold scale is -1 / B.
+__global__ __launch_bounds__(256) void k_dpg_quantile(const float* __restrict__ theta, int64_t ld, int N, int64_t b,
+                                                      float* __restrict__ dy, float* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const float g = -(1.0f / ((float)b * (float)N));
+  const float inv_n = 1.0f / (float)N;
+  float acc = 0.f;
+  for (int64_t i = wave; i < b; i += nw) {
+    float th0[1], th1[1];
+    load_row<1>(theta + i * ld, N, lane, th0);
+    load_row<1>(theta + (b + i) * ld, N, lane, th1);
+    const float q0 = wave_sum(th0[0]) * inv_n, q1 = wave_sum(th1[0]) * inv_n;
+    if (lane == 0) acc += fminf(q0, q1);
+    const float v0[1] = {q0 < q1 ? g : (q0 == q1 ? 0.5f * g : 0.f)};
+    const float v1[1] = {q1 < q0 ? g : (q0 == q1 ? 0.5f * g : 0.f)};
+    store_dy_row<1>(dy + i * ld, ld, N, lane, v0);
+    store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v1);
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+extern "C" int pqlk_dpg_loss_quantile(const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
+                                      const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
+  PQLK_REQUIRE(theta && dy && scratch, PQLK_E_NULL);
+  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
+  const int blocks = loss_blocks(b, n);
+  hipLaunchKernelGGL(k_dpg_quantile, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, ld, (int)n, b, dy, scratch);
+  PQLK_LAUNCH_CHECK();
+  return fold_partials(scratch, blocks, -1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
+}

@@ -511,6 +511,7 @@ class DoubleQ(FusedMLP):
 
     key_prefixes = ("net_q1.net.", "net_q2.net.")
     num_atoms = 1
+    head = "scalar"   # what the output columns mean, and with it which loss kernels a learner launches: scalar | categorical | quantile
 
     def __init__(self, state_dim, act_dim, hidden_layers=None, out_dim=1):
         self.state_dim, self.act_dim = _first(state_dim), int(act_dim)
@@ -542,6 +543,8 @@ def check_num_atoms(num_atoms):
 class DistributionalDoubleQ(DoubleQ):
     """mlp.py:244-267: twin categorical critics, softmax over `num_atoms` on a fixed support."""
 
+    head = "categorical"
+
     def __init__(self, state_dim, act_dim, v_min=-10, v_max=10, num_atoms=51, device="cuda", hidden_layers=None):
         check_num_atoms(num_atoms)
         super().__init__(state_dim, act_dim, hidden_layers, out_dim=num_atoms)
@@ -562,3 +565,31 @@ class DistributionalDoubleQ(DoubleQ):
 
     def get_q1(self, state, action):
         return torch.softmax(self._heads(state, action)[0], dim=1)
+
+
+def check_num_quantiles(num_quantiles):
+    """The quantile loss kernels take 2 ... 64 quantiles (PQLK_QR_MAX_QUANTILES): anything else is an error where the critic is
+    built, not a PQLK_E_UNSUPPORTED at the first learner step."""
+    ok = isinstance(num_quantiles, (int, float)) and not isinstance(num_quantiles, bool) and int(num_quantiles) == num_quantiles
+    if not ok or not 2 <= int(num_quantiles) <= L.QR_MAX_QUANTILES:
+        raise ValueError(f"algo.num_quantiles must be an integer from 2 to {L.QR_MAX_QUANTILES} (the limit of the quantile loss kernels), "
+                         f"got {num_quantiles!r}")
+
+
+class QuantileDoubleQ(DoubleQ):
+    """Twin quantile-regression critics (QR-DQN, Dabney et al. 2018; the reference has no such class): head j of a net is the
+    location of the quantile of probability (2 j + 1) / (2 N) of the return distribution, Q its mean.  No support and no
+    projection: nothing to configure but N.  `num_atoms` stays 1 -- nothing mistakes the head for C51's."""
+
+    head = "quantile"
+
+    def __init__(self, state_dim, act_dim, num_quantiles=32, hidden_layers=None):
+        check_num_quantiles(num_quantiles)
+        super().__init__(state_dim, act_dim, hidden_layers, out_dim=int(num_quantiles))
+        self.num_quantiles = int(num_quantiles)
+        self.init_kwargs = dict(state_dim=self.state_dim, act_dim=self.act_dim, num_quantiles=self.num_quantiles,
+                                hidden_layers=self.layout.dims[1:-1])
+
+    def get_q_min(self, state, action):
+        t1, t2 = self.get_q1_q2(state, action)
+        return torch.min(t1.mean(dim=1), t2.mean(dim=1))

@@ -234,7 +234,9 @@ def structure(cfg, obs_dim, act_dim):
     return {"task.obs_dim": int(obs_dim), "task.act_dim": int(act_dim), "num_envs": int(cfg.num_envs),
             "algo.hidden_layers": None if hidden is None else [int(h) for h in hidden],
             "algo.act_class": str(algo.get("act_class")), "algo.cri_class": cri, "algo.distl": distl,
-            "algo.num_atoms": int(algo.get("num_atoms") or 0) if distl else 0, "algo.nstep": int(algo.get("nstep") or 1),
+            "algo.num_atoms": int(algo.get("num_atoms") or 0) if distl else 0,
+            # (the width of the quantile critic's heads; 0 for every other class)
+            "algo.num_quantiles": int(algo.get("num_quantiles") or 0) if cri.endswith("QuantileDoubleQ") else 0, "algo.nstep": int(algo.get("nstep") or 1),
             "algo.memory_size": int(algo.get("memory_size") or 0),
             "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32"),
             # (the V-learner's target forwards: bf16 targets change every later step, so a run resumes in the dtype it was saved in)
@@ -246,8 +248,9 @@ def structure(cfg, obs_dim, act_dim):
 
 
 def check_structure(saved, current, has_rings=True):
-    # (a checkpoint from before a key existed was written with float32 targets and uniform replay; prioritized, with per-step refresh)
-    saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, **saved}
+    # (a checkpoint from before a key existed was written with float32 targets, uniform replay and no quantile critic; prioritized, with
+    #  per-step refresh)
+    saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, "algo.num_quantiles": 0, **saved}
     saved.setdefault("algo.per.refresh", "step" if saved["algo.per.enabled"] else None)
     for key, want in saved.items():
         if key in ("algo.memory_size", "algo.replay_obs_dtype") and not has_rings:
