@@ -545,6 +545,41 @@ int pqlk_dpg_loss_quantile(const float* theta, int64_t ld, int32_t n, int64_t b,
                            const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Truncated pooled targets for the quantile twin critic (TQC, Kuznetsov et al. 2020).  The reference has no such critic; the law
+ * is the paper's, adapted to twin heads, in the conventions of the block above: N, kappa, tau_j, theta, theta_t, ld as there;
+ * drop = d, 0 <= d <= N - 1, the atoms dropped per net; M = 2 (N - d) of the 2 N pooled atoms are kept; c = (1 - done_b) * gamma_n.
+ * Pool.  p = i * N + k for target net i and quantile k;  z_p = theta_t[i, b, k].
+ * Rank.  rank(p) = #{q : z_q < z_p} + #{q < p : z_q = z_p}: on the raw theta_t (comparisons only, no rounding); ties are broken
+ * by the pool index, so the ranks are a permutation of 0 ... 2 N - 1 whatever the values, also on a row with done = 1, whose
+ * targets are all equal.  Inputs are finite.
+ * Kept set.  Atom p is kept iff rank(p) < M: the M smallest, the largest 2 d are dropped.  d = 0 keeps all atoms of both nets
+ * (which is not the law above: that one takes one whole net per row).
+ * Targets.  T_p = r + c * z_p, formed as r + ((1 - d) * gamma_n) * z_p (pqlk_td_mse_loss's order).
+ * Loss.  u_ijp = T_p - theta[i, b, j];  L = sum_i (1 / (B M)) sum_{b, j, kept p} rho(u_ijp; tau_j), rho and H as above.  Per
+ * (i, b, j) the terms |tau_j - 1{u < 0}| * H(u) of the kept atoms are added in increasing pool index p (dropped atoms skipped);
+ * per (b, j) the two nets' sums are added and divided by kappa once.  Each per-block partial is a plain sum of these; the fold
+ * scale is 1 / (B M), formed as 1.0f / ((float)B * (float)M).  The partial count stays pqlk_loss_parts(b, n).
+ * Gradient.  dy[i, b, j] = -(1 / (B M)) * sum_{kept p} |tau_j - 1{u_ijp < 0}| * clamp(u_ijp, -kappa, kappa) / kappa: the terms
+ * added in increasing p, dropped atoms skipped; the sum is divided by kappa, multiplied by 1 / (B M) and negated.  Pad columns
+ * [N, ld) of dy are written as zero.
+ * Prioritized variant (_per).  wh = w[b] / wmax[0] multiplies the row's loss terms and the row's dy, as above;
+ * abs_td_out[b] = max_i |mean_{kept p} T_p - mean_j theta[i, b, j]|: the first mean is a wave butterfly over the per-lane sums
+ * (T_k if kept, else 0) + (T_{N + k} if kept, else 0), times 1.0f / (float)M; the second as above.  With every w and wmax 1.0 the
+ * weighted entry gives the plain one's bits.
+ * The actor's loss stays pqlk_dpg_loss_quantile.
+ *
+ * loss_out / slot_dev / ring_len / scratch, determinism: as above.  Errors, before any launch: those of pqlk_qr_huber_loss, and
+ * PQLK_E_SHAPE drop < 0 or drop >= n (checked after n's own range).
+ * ---------------------------------------------------------------------------------------------- */
+int pqlk_tqc_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew, const float* done,
+                        float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                        int32_t ring_len, float* scratch, int32_t drop, pqlk_stream_t stream);
+int pqlk_tqc_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew, const float* done,
+                            float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                            int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out, int32_t drop,
+                            pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser: clip_grad_norm_ + AdamW (+ Polyak) over flat arenas
  * (pql_v_learner.py:124-133, pql_p_learner.py:87-96, pql/utils/torch_util.py:9-12).
  *   g *= grad_scale   (1/world_size after a data-parallel sum all-reduce; 1.0 otherwise)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic, qr_huber_loss, td_mse_loss
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic, qr_drop, qr_huber_loss, td_mse_loss
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.prioritized_replay import per_beta, per_cfg  # noqa: F401  (per_beta: imported from here by its users)
@@ -192,7 +192,8 @@ class ActorCriticBase(PQLActor):
         per = {} if memory is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
         if self._quantile:   # twin quantile heads: the quantile Huber loss against the target net with the smaller mean
             qr_huber_loss(q, qt, ld, self.critic.num_quantiles, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep),
-                          float(algo.get("huber_kappa", 1.0)), ws["B"], ws["dy"], self.closs, self.copt.step, ws["scratch"], self.device, **per)
+                          float(algo.get("huber_kappa", 1.0)), ws["B"], ws["dy"], self.closs, self.copt.step, ws["scratch"], self.device,
+                          drop=qr_drop(algo), **per)
         else:
             td_mse_loss(q, qt, ld, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep), ws["B"], ws["dy"], self.closs, self.copt.step,
                         ws["scratch"], self.device, **per)

@@ -100,16 +100,35 @@ def td_mse_loss(q, qt, ld, rew, done, gamma_n, B, dy, loss_out, step, scratch, d
         L.check(L.lib.pqlk_td_mse_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), L.stream(device)))
 
 
-def qr_huber_loss(theta, theta_t, ld, n, rew, done, gamma_n, kappa, B, dy, loss_out, step, scratch, device, w=None, wmax=None, abs_td=None):
+def qr_huber_loss(theta, theta_t, ld, n, rew, done, gamma_n, kappa, B, dy, loss_out, step, scratch, device, w=None, wmax=None, abs_td=None,
+                  drop=None):
     """The quantile Huber loss of twin quantile heads (n columns of the (2, B, ld) blocks) against the target net with the smaller
     mean (include/pqlk.h): d loss / d theta -> dy, the partials -> scratch, the loss -> the ring as in `td_mse_loss`; with `w`, `wmax`,
-    `abs_td` the prioritized instance."""
+    `abs_td` the prioritized instance.  drop (algo.qr_drop) not None: against the pooled atoms of both target nets without the
+    2 * drop largest (the truncated pooled target; its own entries)."""
     head = (L.ptr(theta), L.ptr(theta_t), ld, int(n), L.ptr(rew), L.ptr(done), gamma_n, float(kappa), B, L.ptr(dy), L.ptr(loss_out), L.ptr(step),
             LOSS_RING, L.ptr(scratch))
-    if w is None:
+    if drop is not None:
+        if w is None:
+            L.check(L.lib.pqlk_tqc_huber_loss(*head, int(drop), L.stream(device)))
+        else:
+            L.check(L.lib.pqlk_tqc_huber_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), int(drop), L.stream(device)))
+    elif w is None:
         L.check(L.lib.pqlk_qr_huber_loss(*head, L.stream(device)))
     else:
         L.check(L.lib.pqlk_qr_huber_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), L.stream(device)))
+
+
+def qr_drop(algo):
+    """`algo.qr_drop` as the loss entries take it: None (the key absent or null: one whole target net per row) or the int d."""
+    d = _cfg_get(algo, "qr_drop", None)
+    return None if d is None else int(d)
+
+
+def qr_targets(algo, n):
+    """Target atoms a quantile head of n quantiles is regressed on per row, the divisor of its loss: n, or 2 (n - algo.qr_drop)."""
+    d = qr_drop(algo)
+    return int(n) if d is None else 2 * (int(n) - d)
 
 
 def f32_recip(*factors, sign=1.0):
@@ -256,6 +275,10 @@ def check_critic_class(cfg, fused_learner=None):
                          f"in scripts/train_baselines.py (algo=ddpg_algo / sac_algo / crossq_algo), and in the PQL V-learner with "
                          f"algo.per.refresh=run (the distribution frozen for each run of prefetched steps)")
     cri = str(_cfg_get(algo, "cri_class"))
+    drop = _cfg_get(algo, "qr_drop", None)
+    if drop is not None and not is_quantile(algo):
+        raise ValueError(f"algo.qr_drop={drop!r} needs algo.cri_class=QuantileDoubleQ (got algo.cri_class={cri}): it truncates the pooled "
+                         f"target atoms of the quantile critic; leave algo.qr_drop null with any other critic")
     if cri.endswith("DoubleQLayerNorm"):
         if _cfg_get(algo, "distl", False):
             raise ValueError("algo.distl=True is not supported with algo.cri_class=DoubleQLayerNorm: the LayerNorm critic has no C51 head")
@@ -278,6 +301,12 @@ def check_critic_class(cfg, fused_learner=None):
         kappa = _cfg_get(algo, "huber_kappa", 1.0)
         if not float(kappa) > 0.0:
             raise ValueError(f"algo.huber_kappa must be > 0, got {kappa!r}")
+        if drop is not None:
+            n = int(_cfg_get(algo, "num_quantiles", 32))
+            ok = isinstance(drop, (int, float)) and not isinstance(drop, bool) and int(drop) == drop
+            if not ok or not 0 <= int(drop) <= n - 1:
+                raise ValueError(f"algo.qr_drop must be null or an integer from 0 to algo.num_quantiles - 1 = {n - 1} (the atoms dropped "
+                                 f"per target net; at least one per net is kept), got {drop!r}")
 
 
 def is_quantile(algo):

@@ -21,7 +21,8 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
-                                  check_critic_class, graph_collective_enabled, load_artifact, make_actor, make_critic, pump, qr_huber_loss, resident_norm, td_mse_loss)
+                                  check_critic_class, graph_collective_enabled, load_artifact, make_actor, make_critic, pump, qr_drop, qr_huber_loss,
+                                  qr_targets, resident_norm, td_mse_loss)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
                                 output_view)
 from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer, per_beta, per_cfg
@@ -362,7 +363,8 @@ class PQLVLearner(Learner):
                 if self._head == "quantile":   # (prioritized replay: as for the scalar heads below)
                     per = {} if self._per is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
                     qr_huber_loss(q, qt, cl.ld_out, self.critic.num_quantiles, ws["rew"], ws["done"], gamma_n, float(_cfg_get(algo, "huber_kappa", 1.0)),
-                                  B, ws["dy"], None if self._fold_loss else self.loss_ring, self.opt.step, ws["scratch"], self.device, **per)
+                                  B, ws["dy"], None if self._fold_loss else self.loss_ring, self.opt.step, ws["scratch"], self.device,
+                                  drop=qr_drop(algo), **per)
                 elif algo.distl:
                     L.check(L.lib.pqlk_c51_bce_loss(L.ptr(q), L.ptr(qt), cl.ld_out, int(algo.num_atoms), L.ptr(ws["rew"]),
                                                     L.ptr(ws["done"]), L.ptr(self.critic.z_atoms), gamma_n, float(algo.v_min),
@@ -422,9 +424,10 @@ class PQLVLearner(Learner):
         algo, dev = self.cfg.algo, self.device
         if self._fold_loss:
             K = self.critic.num_quantiles if self._head == "quantile" else (int(algo.num_atoms) if algo.distl else 1)
+            D = qr_targets(algo, K) if self._head == "quantile" else K   # the loss's divisor: with algo.qr_drop the kept atoms, not K
             apply_optimizer_fused(self.critic.layout, self.critic.arena.data, ws["grads"], self.opt, self.critic_target.arena.data,
                                   algo.critic_lr, algo.max_grad_norm, algo.tau, self.pk_critic, self.pk_target, ws["scratch"],
-                                  ws["td_parts"] or L.lib.pqlk_loss_parts(ws["B"], K), f32_recip(ws["B"], K) if K > 1 else f32_recip(ws["B"]),
+                                  ws["td_parts"] or L.lib.pqlk_loss_parts(ws["B"], K), f32_recip(ws["B"], D) if K > 1 else f32_recip(ws["B"]),
                                   self.loss_ring, dev, norm_in_backward=self._fused_tail, grad_scale=1.0 / self.world)
             return
         # optimiser + Polyak + refresh of the fragment-ordered weight copies (critic and target) in one launch pair

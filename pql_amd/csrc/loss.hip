@@ -585,6 +585,117 @@ extern "C" int pqlk_qr_huber_loss_per(const float* theta, const float* theta_t, 
                              abs_td_out, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Truncated pooled targets (TQC, Kuznetsov et al. 2020) on the same heads: the law is written out in include/pqlk.h.  k_qr_huber's
+// geometry; lane k holds quantile k of both nets and of BOTH target nets, i.e. the pooled atoms p = k (net 0) and p = N + k (net 1).
+// Rank by counting, no sort and no LDS: over a wave-uniform loop of 2 N lane reads every lane counts the pooled atoms that precede
+// its two (smaller, or equal with a smaller pool index); atom p is kept iff that count is below M = 2 (N - drop).  The two keep
+// bits become two wave-wide ballots (SGPR pairs); the main loop walks their set bits in increasing p -- dropped atoms cost nothing
+// -- and fetches T_p with a lane read, as k_qr_huber does.
+//
+// Reduction order: k_qr_huber's with "kept p in increasing p" in place of "k = 0 ... N-1" (chains of M terms) and 1 / (B M) in place
+// of 1 / (B N); the mean of the kept targets is wave_sum over lanes of ((keep_0 ? T_0 : 0) + (keep_1 ? T_1 : 0)) times 1.0f / (float)M.
+template <bool PER>
+__global__ __launch_bounds__(256) void k_tqc_huber(const float* __restrict__ theta, const float* __restrict__ theta_t, int64_t ld,
+                                                   int N, int drop, const float* __restrict__ rew, const float* __restrict__ done,
+                                                   float gamma_n, float kappa, int64_t b, float* __restrict__ dy,
+                                                   float* __restrict__ part, const float* __restrict__ w,
+                                                   const float* __restrict__ wmax, float* __restrict__ abs_td) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const int M = 2 * (N - drop);
+  const float inv_bm = 1.0f / ((float)b * (float)M);
+  const float tau = (float)(2 * lane + 1) / (float)(2 * N);
+  const bool on = lane < N;
+  float wm = 1.f;
+  if constexpr (PER) wm = wmax[0];
+  float acc = 0.f;
+  for (int64_t i = wave; i < b; i += nw) {
+    const float r = rew[i], d = done[i];
+    const float th0 = on ? theta[i * ld + lane] : 0.f, th1 = on ? theta[(b + i) * ld + lane] : 0.f;
+    const float t0 = on ? theta_t[i * ld + lane] : 0.f, t1 = on ? theta_t[(b + i) * ld + lane] : 0.f;
+    // ranks of this lane's atoms p = lane (z = t0) and p = N + lane (z = t1) among the 2 N pooled raw target quantiles
+    int c0 = 0, c1 = 0;
+    for (int q = 0; q < N; ++q) {
+      const float a0 = lane_read(t0, q), a1 = lane_read(t1, q);       // pool indices q and N + q
+      c0 += (a0 < t0 || (a0 == t0 && q < lane)) ? 1 : 0;
+      c0 += a1 < t0 ? 1 : 0;                                           // (N + q > lane: an equal atom of net 1 comes after)
+      c1 += a0 <= t1 ? 1 : 0;                                          // (q < N + lane: an equal atom of net 0 comes before)
+      c1 += (a1 < t1 || (a1 == t1 && q < lane)) ? 1 : 0;
+    }
+    const bool keep0 = on && c0 < M, keep1 = on && c1 < M;
+    const unsigned long long m0 = __ballot(keep0), m1 = __ballot(keep1);
+    const float c = (1.f - d) * gamma_n;
+    const float T0 = r + c * t0, T1 = r + c * t1;        // lane k: T_k and T_{N + k} (k_td_mse's operation order)
+    float g0 = 0.f, g1 = 0.f, l0 = 0.f, l1 = 0.f;
+    for (unsigned long long m = m0; m; m &= m - 1) {     // kept atoms of net 0, increasing p
+      const float tp = lane_read(T0, __builtin_ctzll(m));
+      qr_term(tp - th0, tau, kappa, g0, l0);
+      qr_term(tp - th1, tau, kappa, g1, l1);
+    }
+    for (unsigned long long m = m1; m; m &= m - 1) {     // then those of net 1
+      const float tp = lane_read(T1, __builtin_ctzll(m));
+      qr_term(tp - th0, tau, kappa, g0, l0);
+      qr_term(tp - th1, tau, kappa, g1, l1);
+    }
+    float row = (l0 + l1) / kappa;
+    float v0[1] = {(g0 / kappa) * inv_bm}, v1[1] = {(g1 / kappa) * inv_bm};
+    if constexpr (PER) {
+      const float wh = w[i] / wm;
+      row = wh * row;
+      v0[0] = wh * v0[0];
+      v1[0] = wh * v1[0];
+    }
+    if (on) acc += row;
+    v0[0] = -v0[0];
+    v1[0] = -v1[0];
+    store_dy_row<1>(dy + i * ld, ld, N, lane, v0);
+    store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v1);
+    if constexpr (PER) {   // |mean_{kept p} T_p - mean_j theta_j| of either net, the larger: the row's new priority
+      const float mt = wave_sum((keep0 ? T0 : 0.f) + (keep1 ? T1 : 0.f)) * (1.0f / (float)M);
+      const float inv_n = 1.0f / (float)N;
+      const float mq0 = wave_sum(th0) * inv_n, mq1 = wave_sum(th1) * inv_n;
+      if (lane == 0) abs_td[i] = fmaxf(fabsf(mt - mq0), fabsf(mt - mq1));
+    }
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+template <bool PER>
+static int tqc_huber_impl(const float* theta, const float* theta_t, int64_t ld, int32_t n, int32_t drop, const float* rew,
+                          const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                          int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(theta && theta_t && rew && done && dy && scratch, PQLK_E_NULL);
+  PQLK_REQUIRE(!PER || (w && wmax && abs_td_out), PQLK_E_NULL);
+  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(b > 0 && kappa > 0.f, PQLK_E_SHAPE);
+  PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(drop >= 0 && drop < n, PQLK_E_SHAPE);
+  PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
+  const int blocks = loss_blocks(b, n);
+  hipLaunchKernelGGL(k_tqc_huber<PER>, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, (int)drop, rew, done, gamma_n,
+                     kappa, b, dy, scratch, w, wmax, abs_td_out);
+  PQLK_LAUNCH_CHECK();
+  return fold_partials(scratch, blocks, 1.0f / ((float)b * (float)(2 * (n - drop))), loss_out, slot_dev, ring_len, stream);
+}
+
+extern "C" int pqlk_tqc_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                   const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                   const int32_t* slot_dev, int32_t ring_len, float* scratch, int32_t drop, pqlk_stream_t stream) {
+  return tqc_huber_impl<false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
+                               nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int pqlk_tqc_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                       const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                       const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w, const float* wmax,
+                                       float* abs_td_out, int32_t drop, pqlk_stream_t stream) {
+  return tqc_huber_impl<true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
+                              wmax, abs_td_out, stream);
+}
+
 // DPG on the quantile heads: Q_i = (sum_j theta[i, b, j]) * (1 / N) (wave_sum), L = -mean_b min(Q_0, Q_1); every quantile of the
 // smaller net gets -1 / (B N), on a tie both nets half of it (torch.min's backward, k_dpg_scalar).  Lane 0 carries the row's
 // min into the block's partial; the fold scale is -1 / B.

@@ -6,8 +6,10 @@ learner pair, so this builds the three systems in one process and times them in 
 24: deltas come from interleaved rounds in one process).  A point is kbench's `rate`: free-running `learn()` calls on the learner's
 own stream (hipGraph replay), wall clock around a full device synchronise, best of three windows of --steps steps; the table and
 the JSON hold median and min over the rounds.  Recorded, not gated.  GPU only.
+--drop d [d ...] times the quantile critic alone: without `algo.qr_drop` and with each d (the truncated pooled target), in turn.
 
-    python tools/bench_quantile.py [--out profiles/quantile_bench.json] [--rounds 5] [--steps 200] [bench.py flags ...]"""
+    python tools/bench_quantile.py [--out profiles/quantile_bench.json] [--rounds 5] [--steps 200] [bench.py flags ...]
+    python tools/bench_quantile.py --drop 0 2 --out profiles/tqc_bench.json"""
 import argparse
 import json
 import os
@@ -45,13 +47,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--drop", type=int, nargs="+", default=None, help="time QuantileDoubleQ without algo.qr_drop and with each of these values")
     ns, rest = ap.parse_known_args()
+    variants = VARIANTS
+    if ns.drop is not None:
+        name, qr = "QuantileDoubleQ (N = 32)", VARIANTS["QuantileDoubleQ (N = 32)"]
+        variants = {name: qr, **{f"{name}, qr_drop = {d}": [*qr, f"algo.qr_drop={d}"] for d in ns.drop}}
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_quantile.py needs an MI355X (no CPU path)")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     systems = {}
-    for name, override in VARIANTS.items():
+    for name, override in variants.items():
         sys.argv = ["bench.py", "--no-cpu-baseline", *rest, *[x for o in override for x in ("--override", o)]]
         args = bench.parse()
         torch.manual_seed(42)
@@ -69,7 +76,7 @@ def main():
             res[name]["pstep"].append(rate(p.learn, ns.steps))
         print(f"round {r} done", file=sys.stderr, flush=True)
     cfg = next(iter(systems.values()))[0]
-    print(f"{'critic':28s} {'vstep us (median / min)':>26s} {'pstep us (median / min)':>26s}")
+    print(f"{'critic':42s} {'vstep us (median / min)':>26s} {'pstep us (median / min)':>26s}")
     out = {"device": torch.cuda.get_device_name(dev), "batch": int(cfg.algo.batch_size), "hidden": list(cfg.algo.hidden_layers),
            "rounds": ns.rounds, "steps": ns.steps, "argv": rest, "unit": "us per learner step", "critics": {}}
     for name, r in res.items():
@@ -77,7 +84,7 @@ def main():
         _, v, p, _, _ = systems[name]
         row["td_in_forward"], row["dpg_fused"] = bool(v._ws["td_fwd"] > 0), bool(p._ws["dpg_fused"])
         out["critics"][name] = row
-        print(f"{name:28s} {row['vstep']['median']:14.1f} /{row['vstep']['min']:9.1f} {row['pstep']['median']:14.1f} /{row['pstep']['min']:9.1f}")
+        print(f"{name:42s} {row['vstep']['median']:14.1f} /{row['vstep']['min']:9.1f} {row['pstep']['median']:14.1f} /{row['pstep']['min']:9.1f}")
     if ns.out:
         with open(ns.out, "w") as f:
             json.dump(out, f, indent=1)

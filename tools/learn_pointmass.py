@@ -22,6 +22,7 @@ are the same, the episode length is 128 and the upper yardstick is the energy co
     python tools/learn_pointmass.py --task swingup --iters 2000 --curve 500,1000,2000,4000,8000 --out profiles/swingup_learning.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.distl=True --out profiles/swingup_learning_distl.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.per.enabled=True --override algo.per.refresh=run --versus-default --curve 250,500,1000 --curve-algo pql --out profiles/per_pql_learning.json
+    python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.cri_class=QuantileDoubleQ --versus algo.cri_class=QuantileDoubleQ --sweep algo.qr_drop=0,2,4 --out profiles/tqc_learning_swingup.json
 """
 import argparse
 import importlib.util
@@ -143,8 +144,13 @@ def main():
     ap.add_argument("--override", action="append", default=[], help="a further config override for every run (repeatable)")
     ap.add_argument("--versus-default", action="store_true", help="with --override: every run is preceded by the same run WITHOUT the "
                     "overrides (no `overrides` key in its record), so the two variants alternate inside one call")
+    ap.add_argument("--versus", action="append", default=[], help="like --versus-default, but the preceding run takes THESE overrides "
+                    "(repeatable): a baseline that is itself not the default")
+    ap.add_argument("--sweep", default=None, help="KEY=v1,v2,...: every run (and the run that precedes it) once per value, KEY=value "
+                    "as a further override of the run itself")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    sweep = [()] if a.sweep is None else [(f"{a.sweep.split('=', 1)[0]}={v}",) for v in a.sweep.split("=", 1)[1].split(",")]
     assert torch.cuda.is_available(), "learn_pointmass needs a GPU"
     tk = TASKS[a.task]
     out = dict(**({"task": a.task} if a.task != "pointmass" else {}), device=torch.cuda.get_device_name(0), torch=torch.__version__,
@@ -162,9 +168,10 @@ def main():
     for algo in a.algos.split(","):
         for shape in a.shapes.split(","):
             for seed in range(a.seeds):
-                if a.versus_default and a.override:
-                    record("runs", run(algo, shape, seed, a.iters, task=a.task))
-                record("runs", run(algo, shape, seed, a.iters, tuple(a.override), task=a.task))
+                for sw in sweep:
+                    if (a.versus_default or a.versus) and (a.override or sw):
+                        record("runs", run(algo, shape, seed, a.iters, tuple(a.versus), task=a.task))
+                    record("runs", run(algo, shape, seed, a.iters, tuple(a.override) + sw, task=a.task))
     for iters in ([int(x) for x in a.curve.split(",")] if a.curve else []):
         for seed in range(a.seeds):
             record("curve", run(a.curve_algo, "small", seed, iters, tuple(a.override), task=a.task))
