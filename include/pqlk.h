@@ -777,16 +777,42 @@ int pqlk_swingup_step(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed
                       int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k, int32_t* ep,
                       float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, pqlk_stream_t stream);
 
-/* The two steps above with the task's info channels (pql_amd/envs/base.py `info_keys`): the same launch, the same argument list
+/* ------------------------------------------------------------------------------------------------
+ * Reacher vectorised environment step (the coupled learnable task of pql_amd/envs/reacher.py; not a reference component): a
+ * planar arm of act_dim links of length 1 / act_dim per env, joint j held as (c, s) = (cos, sin) of its angle relative to the
+ * link before it (joint 0: to the world x axis) and its angular velocity w; the tip has to reach (0.6, 0).  Every output is
+ * bit-equal to `ReacherVecEnv._step_torch` (one fp32 rounding per operation, no contraction, the sums over act_dim taken in
+ * index order, no atomics, no transcendental function or square root), rot as for SwingUp:
+ *   a = clamp(action, -1, 1); w' = clamp(0.9 w + 0.3 a, -3, 3); (c', s') = rot(c, s, 0.05 w'); k' = k + 1;
+ *   tip(c, s): C = c_0, S = s_0, x = C, y = S; for j = 1 .. act_dim - 1: (C, S) = (C c_j - S s_j, S c_j + C s_j), x += C, y += S;
+ *              ex = x / act_dim - 0.6, ey = y / act_dim        (a product with the fp32 constant 1.0f / act_dim)
+ *   (ex, ey) = tip(c', s'); d2 = ex ex + ey ey; reward = -0.05 ((d2 + 0.01 mean_j w'^2) + 0.01 mean_j a^2);
+ *   truncated = k' >= episode_length; done = truncated.
+ * State (c, s, w: (N, act_dim) floats; k, ep: (N) int32) is updated IN PLACE; a done env moves to episode ep + 1 and is reset
+ * from the counter-based uniform u of the synthetic env keyed by (seed, env_offset + env, ep + 1): (c, s) = rot applied six
+ * times to (1, 0) with d = 0.5 (2 u_15 - 1), w = 0.5 (2 u_16 - 1), k = 0.
+ * next_obs (N, obs_dim) = [c | s | 0.25 w | ex | ey | 0 ...] AFTER the reset, (ex, ey) = tip of the state the row holds (16-byte
+ * stores when obs_dim % 4 == 0 and next_obs is 16-byte aligned); reward (N) floats; done / truncated (N) bytes.
+ * PQLK_E_NULL: any pointer NULL.  PQLK_E_SHAPE: n <= 0, act_dim <= 0, obs_dim < 3 * act_dim + 2. */
+int pqlk_reacher_step(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                      int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k, int32_t* ep,
+                      float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, pqlk_stream_t stream);
+
+/* The three steps above with the task's info channels (pql_amd/envs/base.py `info_keys`): the same launch, the same argument list
  * plus `info` in front of the stream, every other output bit-identical.  info is channel-major (n_info, N) floats with row stride
  * N; row c holds channel c of the step just taken, for a finished env the value BEFORE its reset:
  *   pointmass: 0 = dist2 = mean_j (x' - g)^2, the very value of the reward; 1 = oob = 1.0 where the step left the box, else 0.0;
  *   swingup:   0 = upright = mean_j c'; 1 = effort = mean_j a^2 of the clamped action; both sums in index order from the j = 0 term.
+ *   reacher:   0 = tip_dist2 = d2 of the reward; 1 = effort = mean_j a^2 of the clamped action, summed in index order;
+ *              2 = reached = 1.0 where d2 < 0.01, else 0.0.
  * PQLK_E_NULL: info NULL, besides the errors of the plain entries. */
 int pqlk_pointmass_step_info(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
                              int32_t episode_length, const float* action, float* x, float* v, float* g, int32_t* k, int32_t* ep,
                              float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, float* info, pqlk_stream_t stream);
 int pqlk_swingup_step_info(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
+                           int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k, int32_t* ep,
+                           float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, float* info, pqlk_stream_t stream);
+int pqlk_reacher_step_info(int64_t n, int32_t obs_dim, int32_t act_dim, uint32_t seed, uint32_t env_offset,
                            int32_t episode_length, const float* action, float* c, float* s, float* w, int32_t* k, int32_t* ep,
                            float* next_obs, float* reward, uint8_t* done, uint8_t* truncated, float* info, pqlk_stream_t stream);
 

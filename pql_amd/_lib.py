@@ -125,8 +125,10 @@ PROTOTYPES = {
     "pqlk_synth_env_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, C.c_uint32, _F, _P, _P, _P, _P, _P]),
     "pqlk_pointmass_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pqlk_swingup_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pqlk_reacher_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pqlk_pointmass_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pqlk_swingup_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pqlk_reacher_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pqlk_rollout_step": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
     "pqlk_rollout_info": (C.c_int, [_I64, _P, _I32, _I32, C.POINTER(PqlInfoKey), _P]),
     "pqlk_batch_moments": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _P, _P]),

@@ -10,28 +10,16 @@
 //   reset:   (c, s) = four rotations of hanging by a draw from the counter-based uniform of envhash.h, w another draw;
 //   obs:     [c | s | 0.125 w | 0 ...].
 //
-// The rotation is a polynomial followed by one Newton step back to the unit circle: no transcendental function, no division,
+// The rotation (rot.h) is a polynomial followed by one Newton step back to the unit circle: no transcendental function, no division,
 // no square root.  No atomics and no contraction: every operation rounds once to fp32 exactly like the separate torch ops,
 // so every output is bit-equal to the definition.
 #include "taskstep.h"
+#include "rot.h"
 
 #pragma clang fp contract(off)
 
 #define SU_STREAM_TH 13u
 #define SU_STREAM_W 14u
-
-// (c, s) rotated by the angle d, |d| <= 0.5: cos d and sin d to degree 4 / 5, then m = 1.5 - 0.5 |.|^2 pulls the result back
-// to the unit circle.  The operation order is the one of `_rot` in pql_amd/envs/swingup.py.
-__device__ __forceinline__ void su_rot(float& c, float& s, float d) {
-  const float d2 = d * d;
-  const float cd = 1.0f - d2 * (0.5f - d2 * 0.041666668f);
-  const float sd = d * (1.0f - d2 * (0.16666667f - d2 * 0.008333334f));
-  const float cn = c * cd - s * sd;
-  const float sn = s * cd + c * sd;
-  const float m = 1.5f - 0.5f * (cn * cn + sn * sn);
-  c = cn * m;
-  s = sn * m;
-}
 
 struct SwingUpTask {
   float *c, *s, *w;
@@ -46,7 +34,7 @@ struct SwingUpTask {
       float cj = ce[j], sj = se[j];
       float wn = we[j] + 0.05f * (15.0f * sj + 6.0f * a);
       wn = wn < -8.f ? -8.f : (wn > 8.f ? 8.f : wn);
-      su_rot(cj, sj, 0.05f * wn);
+      task_rot(cj, sj, 0.05f * wn);
       const float cost_j = ((1.0f - cj) + 0.01f * (wn * wn)) + 0.01f * (a * a);
       cost = j == 0 ? cost_j : cost + cost_j;
       up = j == 0 ? cj : up + cj;
@@ -67,10 +55,10 @@ struct SwingUpTask {
     for (int j = 0; j < A; ++j) {
       const float d = 0.5f * (2.0f * uni_col(kt, (uint32_t)j) - 1.0f);
       float cj = -1.f, sj = 0.f;   // hanging; four rotations by d: up to +-2 rad away from it
-      su_rot(cj, sj, d);
-      su_rot(cj, sj, d);
-      su_rot(cj, sj, d);
-      su_rot(cj, sj, d);
+      task_rot(cj, sj, d);
+      task_rot(cj, sj, d);
+      task_rot(cj, sj, d);
+      task_rot(cj, sj, d);
       ce[j] = cj;
       se[j] = sj;
       we[j] = 2.0f * uni_col(kw, (uint32_t)j) - 1.0f;

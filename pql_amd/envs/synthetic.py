@@ -18,6 +18,7 @@ import torch
 
 from pql_amd.envs.base import VecEnvBase, _hash32  # noqa: F401  (`_hash32` is imported from here too)
 from pql_amd.envs.pointmass import PointMassVecEnv
+from pql_amd.envs.reacher import ReacherVecEnv
 from pql_amd.envs.swingup import SwingUpVecEnv
 
 TASK_SHAPES = dict(AllegroHand=(88, 16), ShadowHand=(211, 20), Humanoid=(108, 21), Ant=(60, 8), Anymal=(48, 12), Toy=(8, 2))
@@ -92,12 +93,12 @@ class SyntheticVecEnv(VecEnvBase):
 
 
 # task.kind -> env class: the one place a task is registered (tools/learn_pointmass.py reads it too)
-TASK_ENVS = {"synthetic": SyntheticVecEnv, "pointmass": PointMassVecEnv, "swingup": SwingUpVecEnv}
+TASK_ENVS = {"synthetic": SyntheticVecEnv, "pointmass": PointMassVecEnv, "swingup": SwingUpVecEnv, "reacher": ReacherVecEnv}
 
 
 def create_task_env(cfg, num_envs=None, env_offset=0):
     """Stand-in for pql.utils.isaacgym_util.create_task_env (:8-24).  `task.kind` picks the env from TASK_ENVS: absent / synthetic =
-    the counter-based generator above, pointmass / swingup = the learnable tasks of pql_amd/envs/pointmass.py and pql_amd/envs/swingup.py.  A task with info channels emits them exactly
+    the counter-based generator above, pointmass / swingup / reacher = the learnable tasks of pql_amd/envs/pointmass.py, swingup.py and reacher.py.  A task with info channels emits them exactly
     when `cfg.info_track_keys` is set."""
     task = cfg.task
     name = task.name if task is not None else "AllegroHand"

@@ -82,7 +82,7 @@ def _load_file(path: Path, group_choices=None):
                 from pql_amd.envs.synthetic import TASK_SHAPES   # (torch-only module; imported here to keep cfg import light)
                 if str(option) not in TASK_SHAPES:   # a typo must fail at config load, as Hydra's missing-config error does
                     raise ValueError(f"task={option}: no such task; known tasks: {', '.join(sorted(TASK_SHAPES))} "
-                                     f"(or task=synthetic with task.obs_dim / task.act_dim; task=pointmass and task=swingup are the learnable tasks)")
+                                     f"(or task=synthetic with task.obs_dim / task.act_dim; task=pointmass, task=swingup and task=reacher are the learnable tasks)")
                 sub = _load_file(path.parent / group / "synthetic.yaml")
                 sub["name"] = str(option)
             else:

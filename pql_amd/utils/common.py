@@ -114,7 +114,7 @@ def normalize(input, normalize_tuple):
 
 # ---------------------------------------------------------------------------- cfg mutation
 TASK_REWARD_SCALE = dict(AllegroHand=0.01, Ant=0.01, Humanoid=0.01, Anymal=1., FrankaCubeStack=0.1, ShadowHand=0.01,
-                         BallBalance=0.1, PointMass=1., SwingUp=1.)
+                         BallBalance=0.1, PointMass=1., SwingUp=1., Reacher=1.)
 TASK_MAX_TIME = dict(AllegroHand=4800, Ant=3600, Humanoid=3600, Anymal=1800, FrankaCubeStack=3600, ShadowHand=4800,
                      BallBalance=3600)
 

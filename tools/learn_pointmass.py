@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Learning record on the learnable tasks -- PointMass (pql_amd/envs/pointmass.py), or with `--task swingup` SwingUp
-(pql_amd/envs/swingup.py): do the kernels, assembled into a training run, improve a policy?
+"""Learning record on the learnable tasks -- PointMass (pql_amd/envs/pointmass.py), with `--task swingup` SwingUp
+(pql_amd/envs/swingup.py), with `--task reacher` Reacher (pql_amd/envs/reacher.py): do the kernels, assembled into a training run,
+improve a policy?
 
 Runs the two entry points themselves -- `scripts/train_baselines.py` (DDPG) and the fixed-ratio loop of `scripts/train_pql.py` -- on
 PointMass for a fixed number of rollout iterations, several seeds each, at two shapes:
@@ -13,6 +14,7 @@ the trained deterministic policy over one full episode on 256 fresh envs (R), th
 controller a = clamp(4 (g - x) - 4 v, -1, 1) (R_pd), the gap fraction f = (R - R_zero) / (R_pd - R_zero) and the wall time.
 `--curve` adds DDPG (`--curve-algo pql`: PQL) at the small shape over a ladder of iteration counts (where does it plateau?).  With `--task swingup` the shapes
 are the same, the episode length is 128 and the upper yardstick is the energy controller (`energy_policy`), recorded as R_ctrl.
+With `--task reacher` the episode length is 64 and the upper yardstick is the Jacobian-transpose law (`jacobian_policy`), R_ctrl too.
 
     python tools/learn_pointmass.py --out profiles/pointmass_learning.json
     python tools/learn_pointmass.py --algos ddpg --shapes small --seeds 1 --iters 200      # a quick look
@@ -23,6 +25,8 @@ are the same, the episode length is 128 and the upper yardstick is the energy co
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.distl=True --out profiles/swingup_learning_distl.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.per.enabled=True --override algo.per.refresh=run --versus-default --curve 250,500,1000 --curve-algo pql --out profiles/per_pql_learning.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.cri_class=QuantileDoubleQ --versus algo.cri_class=QuantileDoubleQ --sweep algo.qr_drop=0,2,4 --out profiles/tqc_learning_swingup.json
+    python tools/learn_pointmass.py --task reacher --curve 250,500,1000,2000,4000 --out profiles/reacher_learning.json
+    python tools/learn_pointmass.py --task reacher --algos ddpg --shapes small --seeds 1 --iters 500     # a quick look at the coupled task
 """
 import argparse
 import importlib.util
@@ -38,7 +42,7 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
-from pql_amd.envs import swingup  # noqa: E402
+from pql_amd.envs import reacher, swingup  # noqa: E402
 from pql_amd.envs.pointmass import episode_return, pd_policy, zero_policy  # noqa: E402
 from pql_amd.envs.synthetic import TASK_ENVS  # noqa: E402
 from pql_amd.utils.cfg import load_cfg  # noqa: E402
@@ -49,6 +53,7 @@ EPISODE_LENGTH = 64
 TASKS = {
     "pointmass": dict(env=TASK_ENVS["pointmass"], episode_length=EPISODE_LENGTH, zero=zero_policy, ctrl=pd_policy, ctrl_key="R_pd"),
     "swingup": dict(env=TASK_ENVS["swingup"], episode_length=128, zero=swingup.zero_policy, ctrl=swingup.energy_policy, ctrl_key="R_ctrl"),
+    "reacher": dict(env=TASK_ENVS["reacher"], episode_length=64, zero=reacher.zero_policy, ctrl=reacher.jacobian_policy, ctrl_key="R_ctrl"),
 }
 EVAL_ENVS = 256
 WARM_UP = 32   # algo.warm_up default: random-policy env steps in front of the first iteration
@@ -90,7 +95,7 @@ def yardsticks(shape, seed, device="cuda:0", task="pointmass"):
 def run(algo, shape, seed, iters, extra=(), task="pointmass"):
     """One training run through the entry point's own `main`; the policy is evaluated by its `on_finish` hook.
     extra: further config overrides, e.g. ("algo.replay_obs_dtype=float16",).  task: a key of TASKS; the upper yardstick's return is
-    recorded as R_pd on PointMass and as R_ctrl on SwingUp (a PointMass record has no `task` key, as before the tool knew two tasks)."""
+    recorded as R_pd on PointMass and as R_ctrl on SwingUp and Reacher (a PointMass record has no `task` key, as before the tool knew two tasks)."""
     env, r_zero, r_pd = yardsticks(shape, seed, task=task)
     got = {}
 
