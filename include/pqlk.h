@@ -580,6 +580,45 @@ int pqlk_tqc_huber_loss_per(const float* theta, const float* theta_t, int64_t ld
                             pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * TQC as the paper defines it: a maximum-entropy actor-critic on the truncated pooled target (algo=tqc_algo).  Notation of the
+ * block above: N, kappa, tau_j, theta, theta_t, d, M = 2 (N - d), pool index p = i * N + k, z_p = theta_t[i, b, k],
+ * c = (1 - done_b) * gamma_n.  logp: (B,), log pi(a'_b | s'_b) of the next action the target heads were evaluated at; log_alpha:
+ * (1,), the log of the temperature, read on the device.
+ *
+ * Soft truncated target (pqlk_tqc_huber_loss_soft, pqlk_tqc_huber_loss_soft_per).
+ * Shift.  s_b = alpha * logp[b], alpha = expf(log_alpha[0]): pqlk_sac_entropy_shift's expression, one fp32 product.
+ * Rank, kept set.  Those of the block above, computed on the RAW theta_t.  The shift is the same for every atom of a row, so in
+ * real arithmetic it changes no order; ranking the raw atoms means that rounding after the shift can never create or break a tie.
+ * Targets.  T_p = r + c * (z_p - s_b), in this order: the subtraction, the product with c = fl((1 - d) * gamma_n), the addition;
+ * no contraction, each step rounds.  The entropy bonus sits inside every target atom; on a row with done = 1 every T_p is r.
+ * Loss, gradient, pad columns, the fold scale 1.0f / ((float)B * (float)M), the prioritized weighting wh = w[b] / wmax[0]: as
+ * above, with these T_p.  abs_td_out[b] = max_i |mean_{kept p} T_p - mean_j theta[i, b, j]| with the soft T_p.
+ * With logp = 0 everywhere the entries give the bits of pqlk_tqc_huber_loss{,_per}, whatever log_alpha (z - 0 = z); with every w
+ * and wmax 1.0 the weighted entry gives the plain one's bits.  The shift rides in the loss launch: the target heads are not
+ * rewritten, and a critic step has the launch count of the one above.
+ *
+ * Mean-of-critics actor objective (pqlk_dpg_loss_quantile_mean; arguments of pqlk_dpg_loss_quantile).
+ * Qbar_b = (1 / (2 N)) sum_i sum_j theta[i, b, j]: per lane j theta[0, b, j] + theta[1, b, j], one wave butterfly, times
+ * 1.0f / (float)(2 N).  L_q = -(1 / B) sum_b Qbar_b: lane 0 adds Qbar_b to the block's partial, the fold scale is -1 / B.
+ * dy[i, b, j] = -(1.0f / ((float)B * (float)(2 * N))) for j < N, pad columns [N, ld) zero: no min, so no share and no tie rule.
+ * The agent's actor loss is L_q + alpha * mean_b logp_b: the second term is added to the ring by pqlk_sac_alpha_terms, and the
+ * gradient reaches the policy head through pqlk_sg_head_backward with glp_scale = 1 / B, as in SAC.
+ *
+ * Errors, before any launch: those of pqlk_tqc_huber_loss{,_per} and of pqlk_dpg_loss_quantile; PQLK_E_NULL for logp or
+ * log_alpha NULL.  No float atomics; two launches on the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+int pqlk_tqc_huber_loss_soft(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew, const float* done,
+                             float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                             int32_t ring_len, float* scratch, const float* logp, const float* log_alpha, int32_t drop,
+                             pqlk_stream_t stream);
+int pqlk_tqc_huber_loss_soft_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                 const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                 const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w, const float* wmax,
+                                 float* abs_td_out, const float* logp, const float* log_alpha, int32_t drop, pqlk_stream_t stream);
+int pqlk_dpg_loss_quantile_mean(const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
+                                const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser: clip_grad_norm_ + AdamW (+ Polyak) over flat arenas
  * (pql_v_learner.py:124-133, pql_p_learner.py:87-96, pql/utils/torch_util.py:9-12).
  *   g *= grad_scale   (1/world_size after a data-parallel sum all-reduce; 1.0 otherwise)

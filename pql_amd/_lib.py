@@ -107,6 +107,9 @@ PROTOTYPES = {
     "pqlk_dpg_loss_quantile": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P, _I32, _P, _P]),
     "pqlk_tqc_huber_loss": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _I32, _P]),
     "pqlk_tqc_huber_loss_per": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P]),
+    "pqlk_tqc_huber_loss_soft": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _I32, _P]),
+    "pqlk_tqc_huber_loss_soft_per": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "pqlk_dpg_loss_quantile_mean": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P, _I32, _P, _P]),
     "pqlk_clip_adamw_polyak": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pqlk_clip_adamw_polyak_pack": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
     "pqlk_adamw_polyak_fused": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P,

@@ -276,6 +276,14 @@ def check_critic_class(cfg, fused_learner=None):
                          f"algo.per.refresh=run (the distribution frozen for each run of prefetched steps)")
     cri = str(_cfg_get(algo, "cri_class"))
     drop = _cfg_get(algo, "qr_drop", None)
+    if str(_cfg_get(algo, "name", "")) == "TQC":   # algo=tqc_algo is the quantile critic on the truncated soft target, nothing else
+        if not is_quantile(algo):
+            raise ValueError(f"algo=tqc_algo needs algo.cri_class=QuantileDoubleQ (got algo.cri_class={cri}): its soft truncated target and "
+                             f"its mean-of-critics actor loss are laws of the quantile heads; algo=sac_algo runs the scalar critics")
+        if drop is None:
+            raise ValueError("algo.qr_drop=null cannot run with algo=tqc_algo: the non-truncated soft quantile law (one whole target net "
+                             "per row, shifted by the entropy term) is not built; set algo.qr_drop to an integer from 0 to "
+                             "algo.num_quantiles - 1 (0 keeps every pooled atom)")
     if drop is not None and not is_quantile(algo):
         raise ValueError(f"algo.qr_drop={drop!r} needs algo.cri_class=QuantileDoubleQ (got algo.cri_class={cri}): it truncates the pooled "
                          f"target atoms of the quantile critic; leave algo.qr_drop null with any other critic")
@@ -292,8 +300,9 @@ def check_critic_class(cfg, fused_learner=None):
         name = str(_cfg_get(algo, "name", ""))
         if name in ("SAC", "CrossQ"):
             why = "the entropy shift of the SAC target has" if name == "SAC" else "the BatchNorm critic has"
+            tail = " (the maximum-entropy agent on this class is algo=tqc_algo)" if name == "SAC" else ""
             raise ValueError(f"algo.cri_class=QuantileDoubleQ cannot run with algo={name.lower()}_algo: {why} no N-wide head; the class "
-                             f"is for algo=pql_algo and algo=ddpg_algo")
+                             f"is for algo=pql_algo and algo=ddpg_algo{tail}")
         if str(_cfg_get(algo, "target_dtype", "float32")) == "bfloat16":
             raise ValueError("algo.target_dtype=bfloat16 is not supported with algo.cri_class=QuantileDoubleQ: the bf16 target forward "
                              "has not been taken to the quantile head (use algo.target_dtype=float32)")

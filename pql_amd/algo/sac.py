@@ -61,6 +61,18 @@ class AgentSAC(ActorCriticBase):
                              dy_a=(1, B, self.actor.layout.ld_out), g_alpha=(1,)).items():
             ws[k] = zeros(shape)
 
+    # ---- the two places a maximum-entropy agent on another critic head differs (AgentTQC)
+    def _soft_td_loss(self, ws, q, qt, ld):
+        """The critic loss against the entropy-regularised target: the target heads lowered in place by alpha log pi(a'|s'), then the
+        twin loss of the base class."""
+        B = ws["B"]
+        L.check(L.lib.pqlk_sac_entropy_shift(L.ptr(qt), ld, B * ld, 2, L.ptr(ws["logp_next"]), L.ptr(self.log_alpha), B, L.stream(self.device)))
+        self._td_mse_loss(ws, q, qt, ld)
+
+    def _actor_q_loss(self, ws, q, ld):
+        """The Q term of the actor loss, -mean(min Q): d loss / d q -> ws["dy"], the value -> the actor's ring."""
+        self._dpg_loss(ws, q, ld)
+
     @torch.no_grad()
     def update_once(self, memory, indices=None, eps_next=None, eps_cur=None):
         """One inner iteration of update_net (losses land in device rings).  indices / eps_*: injected draws for parity tests."""
@@ -81,15 +93,14 @@ class AgentSAC(ActorCriticBase):
                                                L.ptr(ws["logp_next"]), st))
             qt, _ = self._critic_forward(ws, self.critic_target, ws["xn_sa"], "t")
             q, ld = self._critic_forward(ws, self.critic, ws["x_sa"], "c")
-            L.check(L.lib.pqlk_sac_entropy_shift(L.ptr(qt), ld, B * ld, 2, L.ptr(ws["logp_next"]), L.ptr(self.log_alpha), B, st))
-            self._td_mse_loss(ws, q, qt, ld)
+            self._soft_td_loss(ws, q, qt, ld)
             self._critic_grads(ws, ws["x_sa"])
             self._critic_step(ws)
             # ---- actor step through the UPDATED critic (sac.py:148-153): L = mean(alpha log pi(a|s) - min Q(s, a)), a ~ pi(.|s)
             mlp_forward_raw(al, self.actor.arena.data, ws["x_obs"], L.ACT_NONE, acts=ws["acts_a"])
             L.check(L.lib.pqlk_sg_head_forward(L.ptr(y_a), al.ld_out, L.ptr(e_cur), B, A, L.ptr(ws["x_pi"][:, O:]), ws["ld_sa"],
                                                L.ptr(ws["logp"]), st))
-            self._dpg_loss(ws, *self._critic_forward(ws, self.critic, ws["x_pi"], "c"))
+            self._actor_q_loss(ws, *self._critic_forward(ws, self.critic, ws["x_pi"], "c"))
             # temperature terms with the alpha the actor loss uses (before its own update): actor loss += alpha mean(log pi),
             # g_alpha = alpha * mean(-log pi - target_entropy)
             L.check(L.lib.pqlk_sac_alpha_terms(L.ptr(ws["logp"]), B, L.ptr(self.log_alpha), self.target_entropy, L.ptr(ws["g_alpha"]),

@@ -595,12 +595,19 @@ extern "C" int pqlk_qr_huber_loss_per(const float* theta, const float* theta_t, 
 //
 // Reduction order: k_qr_huber's with "kept p in increasing p" in place of "k = 0 ... N-1" (chains of M terms) and 1 / (B M) in place
 // of 1 / (B N); the mean of the kept targets is wave_sum over lanes of ((keep_0 ? T_0 : 0) + (keep_1 ? T_1 : 0)) times 1.0f / (float)M.
-template <bool PER>
+//
+// SOFT (the maximum-entropy target of the TQC agent, "Soft truncated target" in include/pqlk.h): every atom of row b is lowered by
+// s_b = expf(log_alpha[0]) * logp[b] (k_sac_entropy_shift's expression) before it is scaled: T_p = r + c * (z_p - s_b).  alpha is
+// read once per wave, logp[b] is a wave-uniform load beside rew[b] and done[b].  The ranks stay on the raw z_p: one shift for the
+// whole row cannot change their order in real arithmetic, and ranking before it keeps rounding from making or breaking a tie.  The
+// plain instances never touch logp or log_alpha and compile to the code they were.
+template <bool PER, bool SOFT>
 __global__ __launch_bounds__(256) void k_tqc_huber(const float* __restrict__ theta, const float* __restrict__ theta_t, int64_t ld,
                                                    int N, int drop, const float* __restrict__ rew, const float* __restrict__ done,
                                                    float gamma_n, float kappa, int64_t b, float* __restrict__ dy,
                                                    float* __restrict__ part, const float* __restrict__ w,
-                                                   const float* __restrict__ wmax, float* __restrict__ abs_td) {
+                                                   const float* __restrict__ wmax, float* __restrict__ abs_td,
+                                                   const float* __restrict__ logp, const float* __restrict__ log_alpha) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nw = (int64_t)gridDim.x * 4;
@@ -610,9 +617,13 @@ __global__ __launch_bounds__(256) void k_tqc_huber(const float* __restrict__ the
   const bool on = lane < N;
   float wm = 1.f;
   if constexpr (PER) wm = wmax[0];
+  float alpha = 0.f;
+  if constexpr (SOFT) alpha = expf(log_alpha[0]);
   float acc = 0.f;
   for (int64_t i = wave; i < b; i += nw) {
     const float r = rew[i], d = done[i];
+    float sh = 0.f;
+    if constexpr (SOFT) sh = alpha * logp[i];            // s_b: one product
     const float th0 = on ? theta[i * ld + lane] : 0.f, th1 = on ? theta[(b + i) * ld + lane] : 0.f;
     const float t0 = on ? theta_t[i * ld + lane] : 0.f, t1 = on ? theta_t[(b + i) * ld + lane] : 0.f;
     // ranks of this lane's atoms p = lane (z = t0) and p = N + lane (z = t1) among the 2 N pooled raw target quantiles
@@ -627,7 +638,14 @@ __global__ __launch_bounds__(256) void k_tqc_huber(const float* __restrict__ the
     const bool keep0 = on && c0 < M, keep1 = on && c1 < M;
     const unsigned long long m0 = __ballot(keep0), m1 = __ballot(keep1);
     const float c = (1.f - d) * gamma_n;
-    const float T0 = r + c * t0, T1 = r + c * t1;        // lane k: T_k and T_{N + k} (k_td_mse's operation order)
+    float T0, T1;                                        // lane k: T_k and T_{N + k} (k_td_mse's operation order)
+    if constexpr (SOFT) {
+      T0 = r + c * (t0 - sh);                            // subtract, multiply, add: each step rounds
+      T1 = r + c * (t1 - sh);
+    } else {
+      T0 = r + c * t0;
+      T1 = r + c * t1;
+    }
     float g0 = 0.f, g1 = 0.f, l0 = 0.f, l1 = 0.f;
     for (unsigned long long m = m0; m; m &= m - 1) {     // kept atoms of net 0, increasing p
       const float tp = lane_read(T0, __builtin_ctzll(m));
@@ -663,20 +681,22 @@ __global__ __launch_bounds__(256) void k_tqc_huber(const float* __restrict__ the
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-template <bool PER>
+template <bool PER, bool SOFT>
 static int tqc_huber_impl(const float* theta, const float* theta_t, int64_t ld, int32_t n, int32_t drop, const float* rew,
                           const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
-                          int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out, pqlk_stream_t stream) {
+                          int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out, const float* logp,
+                          const float* log_alpha, pqlk_stream_t stream) {
   PQLK_REQUIRE(theta && theta_t && rew && done && dy && scratch, PQLK_E_NULL);
   PQLK_REQUIRE(!PER || (w && wmax && abs_td_out), PQLK_E_NULL);
+  PQLK_REQUIRE(!SOFT || (logp && log_alpha), PQLK_E_NULL);
   PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
   PQLK_REQUIRE(b > 0 && kappa > 0.f, PQLK_E_SHAPE);
   PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(drop >= 0 && drop < n, PQLK_E_SHAPE);
   PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
   const int blocks = loss_blocks(b, n);
-  hipLaunchKernelGGL(k_tqc_huber<PER>, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, (int)drop, rew, done, gamma_n,
-                     kappa, b, dy, scratch, w, wmax, abs_td_out);
+  hipLaunchKernelGGL((k_tqc_huber<PER, SOFT>), dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, (int)drop, rew, done,
+                     gamma_n, kappa, b, dy, scratch, w, wmax, abs_td_out, logp, log_alpha);
   PQLK_LAUNCH_CHECK();
   return fold_partials(scratch, blocks, 1.0f / ((float)b * (float)(2 * (n - drop))), loss_out, slot_dev, ring_len, stream);
 }
@@ -684,16 +704,33 @@ static int tqc_huber_impl(const float* theta, const float* theta_t, int64_t ld, 
 extern "C" int pqlk_tqc_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
                                    const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
                                    const int32_t* slot_dev, int32_t ring_len, float* scratch, int32_t drop, pqlk_stream_t stream) {
-  return tqc_huber_impl<false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
-                               nullptr, nullptr, nullptr, stream);
+  return tqc_huber_impl<false, false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
+                                      nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int pqlk_tqc_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
                                        const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
                                        const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w, const float* wmax,
                                        float* abs_td_out, int32_t drop, pqlk_stream_t stream) {
-  return tqc_huber_impl<true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
-                              wmax, abs_td_out, stream);
+  return tqc_huber_impl<true, false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
+                                     wmax, abs_td_out, nullptr, nullptr, stream);
+}
+
+extern "C" int pqlk_tqc_huber_loss_soft(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                        const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                        const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* logp,
+                                        const float* log_alpha, int32_t drop, pqlk_stream_t stream) {
+  return tqc_huber_impl<false, true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
+                                     nullptr, nullptr, nullptr, logp, log_alpha, stream);
+}
+
+extern "C" int pqlk_tqc_huber_loss_soft_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                            const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                            const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w,
+                                            const float* wmax, float* abs_td_out, const float* logp, const float* log_alpha,
+                                            int32_t drop, pqlk_stream_t stream) {
+  return tqc_huber_impl<true, true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
+                                    wmax, abs_td_out, logp, log_alpha, stream);
 }
 
 // DPG on the quantile heads: Q_i = (sum_j theta[i, b, j]) * (1 / N) (wave_sum), L = -mean_b min(Q_0, Q_1); every quantile of the
@@ -731,6 +768,43 @@ extern "C" int pqlk_dpg_loss_quantile(const float* theta, int64_t ld, int32_t n,
   PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
   const int blocks = loss_blocks(b, n);
   hipLaunchKernelGGL(k_dpg_quantile, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, ld, (int)n, b, dy, scratch);
+  PQLK_LAUNCH_CHECK();
+  return fold_partials(scratch, blocks, -1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
+}
+
+// The mean-of-critics actor objective of the TQC agent ("Mean-of-critics actor objective" in include/pqlk.h), k_dpg_quantile's
+// geometry: Qbar_b = wave_sum(th0 + th1) * (1 / (2 N)), L = -mean_b Qbar_b; every quantile of both nets gets -1 / (B 2 N), whatever
+// the values (no min, no tie).  Lane 0 carries Qbar_b into the block's partial; the fold scale is -1 / B.
+__global__ __launch_bounds__(256) void k_dpg_quantile_mean(const float* __restrict__ theta, int64_t ld, int N, int64_t b,
+                                                           float* __restrict__ dy, float* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const float v[1] = {-(1.0f / ((float)b * (float)(2 * N)))};
+  const float inv_2n = 1.0f / (float)(2 * N);
+  float acc = 0.f;
+  for (int64_t i = wave; i < b; i += nw) {
+    float th0[1], th1[1];
+    load_row<1>(theta + i * ld, N, lane, th0);
+    load_row<1>(theta + (b + i) * ld, N, lane, th1);
+    const float qbar = wave_sum(th0[0] + th1[0]) * inv_2n;
+    if (lane == 0) acc += qbar;
+    store_dy_row<1>(dy + i * ld, ld, N, lane, v);
+    store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v);
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+extern "C" int pqlk_dpg_loss_quantile_mean(const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
+                                           const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
+  PQLK_REQUIRE(theta && dy && scratch, PQLK_E_NULL);
+  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
+  const int blocks = loss_blocks(b, n);
+  hipLaunchKernelGGL(k_dpg_quantile_mean, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, ld, (int)n, b, dy, scratch);
   PQLK_LAUNCH_CHECK();
   return fold_partials(scratch, blocks, -1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
 }

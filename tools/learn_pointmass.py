@@ -3,7 +3,7 @@
 (pql_amd/envs/swingup.py), with `--task reacher` Reacher (pql_amd/envs/reacher.py): do the kernels, assembled into a training run,
 improve a policy?
 
-Runs the two entry points themselves -- `scripts/train_baselines.py` (DDPG) and the fixed-ratio loop of `scripts/train_pql.py` -- on
+Runs the two entry points themselves -- `scripts/train_baselines.py` (DDPG; `--algos sac` / `tqc`: SAC and TQC) and the fixed-ratio loop of `scripts/train_pql.py` -- on
 PointMass for a fixed number of rollout iterations, several seeds each, at two shapes:
 
     small  (obs 8, act 2):   64 envs, batch 256, hidden [128, 128]
@@ -25,6 +25,7 @@ With `--task reacher` the episode length is 64 and the upper yardstick is the Ja
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.distl=True --out profiles/swingup_learning_distl.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.per.enabled=True --override algo.per.refresh=run --versus-default --curve 250,500,1000 --curve-algo pql --out profiles/per_pql_learning.json
     python tools/learn_pointmass.py --task swingup --iters 2000 --algos pql --shapes small --override algo.cri_class=QuantileDoubleQ --versus algo.cri_class=QuantileDoubleQ --sweep algo.qr_drop=0,2,4 --out profiles/tqc_learning_swingup.json
+    python tools/learn_pointmass.py --task swingup --iters 2000 --algos tqc --shapes small --versus-algo sac --sweep algo.qr_drop=0,2,5 --out profiles/tqc_sac_learning_swingup.json
     python tools/learn_pointmass.py --task reacher --curve 250,500,1000,2000,4000 --out profiles/reacher_learning.json
     python tools/learn_pointmass.py --task reacher --algos ddpg --shapes small --seeds 1 --iters 500     # a quick look at the coupled task
 """
@@ -61,7 +62,8 @@ SHAPES = {
     "small": dict(obs_dim=8, act_dim=2, num_envs=64, batch=256, hidden=[128, 128]),
     "large": dict(obs_dim=88, act_dim=16, num_envs=1024, batch=8192, hidden=None),
 }
-ALGOS = {"ddpg": ("train_baselines.py", ["algo=ddpg_algo"]), "pql": ("train_pql.py", ["algo=pql_algo", "algo.num_gpus=1"])}
+ALGOS = {"ddpg": ("train_baselines.py", ["algo=ddpg_algo"]), "pql": ("train_pql.py", ["algo=pql_algo", "algo.num_gpus=1"]),
+         "sac": ("train_baselines.py", ["algo=sac_algo"]), "tqc": ("train_baselines.py", ["algo=tqc_algo"])}
 _SCRIPTS = {}
 
 
@@ -99,7 +101,7 @@ def run(algo, shape, seed, iters, extra=(), task="pointmass"):
     env, r_zero, r_pd = yardsticks(shape, seed, task=task)
     got = {}
 
-    def evaluate(agent, *_learners):   # DDPG: the agent; PQL: (rollout actor, V-learner, P-learner)
+    def evaluate(agent, *_learners):   # the baselines (DDPG, SAC, TQC): the agent; PQL: (rollout actor, V-learner, P-learner)
         agent.set_actor(agent.actor)   # the weights were stepped in place: refresh the rollout's packed copy
         got["R"] = episode_return(env, lambda obs: agent.get_actions(obs, sample=False))
 
@@ -110,9 +112,10 @@ def run(algo, shape, seed, iters, extra=(), task="pointmass"):
         res = script(ALGOS[algo][0]).main(cfg, on_finish=evaluate)
         torch.cuda.synchronize()
         wall = time.time() - t0
-    done_iters = res["iters"] if algo == "ddpg" else res["rollout_iterations"]
+    baseline = ALGOS[algo][0] == "train_baselines.py"   # the synchronous loop: update_times updates per iteration
+    done_iters = res["iters"] if baseline else res["rollout_iterations"]
     assert done_iters == iters, (done_iters, iters)
-    updates = iters * int(cfg.algo.update_times) if algo == "ddpg" else int(res["critic_updates"])
+    updates = iters * int(cfg.algo.update_times) if baseline else int(res["critic_updates"])
     return dict(**({"task": task} if task != "pointmass" else {}), algo=algo, shape=shape, seed=seed, iters=iters,
                 **({"overrides": list(extra)} if extra else {}), critic_updates=updates, R=got["R"], R_zero=r_zero,
                 **{TASKS[task]["ctrl_key"]: r_pd}, f=(got["R"] - r_zero) / (r_pd - r_zero), wall_s=round(wall, 2))
@@ -151,6 +154,8 @@ def main():
                     "overrides (no `overrides` key in its record), so the two variants alternate inside one call")
     ap.add_argument("--versus", action="append", default=[], help="like --versus-default, but the preceding run takes THESE overrides "
                     "(repeatable): a baseline that is itself not the default")
+    ap.add_argument("--versus-algo", default=None, choices=sorted(ALGOS), help="every seed's runs are preceded by ONE run of this algorithm "
+                    "at the same shape and seed with the --versus overrides only (no --override, no --sweep): another algorithm as the baseline")
     ap.add_argument("--sweep", default=None, help="KEY=v1,v2,...: every run (and the run that precedes it) once per value, KEY=value "
                     "as a further override of the run itself")
     ap.add_argument("--out", default=None)
@@ -173,6 +178,8 @@ def main():
     for algo in a.algos.split(","):
         for shape in a.shapes.split(","):
             for seed in range(a.seeds):
+                if a.versus_algo:
+                    record("runs", run(a.versus_algo, shape, seed, a.iters, tuple(a.versus), task=a.task))
                 for sw in sweep:
                     if (a.versus_default or a.versus) and (a.override or sw):
                         record("runs", run(algo, shape, seed, a.iters, tuple(a.versus), task=a.task))
