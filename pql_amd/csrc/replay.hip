@@ -18,138 +18,212 @@ extern "C" int64_t pqlk_replay_rec_ld_ex(int32_t obs_dim, int32_t act_dim, int32
   return 0;
 }
 
-// fp16 observation storage (PQLK_OBS_F16): kernels and launchers of their own at the end of this file
-static int replay_insert_f16(const PqlReplayDesc* ring, int64_t dst_start, int64_t m, const float* obs, int64_t ld_obs,
-                             const float* act, int64_t ld_act, const float* rew, int64_t ld_rew, const float* next_obs,
-                             int64_t ld_nobs, const float* done, int64_t ld_done, pqlk_stream_t stream);
-static int replay_gather_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, float* obs, float* act, float* rew,
-                             float* next_obs, float* done, pqlk_stream_t stream);
-static int replay_gather_fused_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, const float* mean, const float* var,
-                                   float eps, int flags, float* x_sa, int64_t ld_sa, float* xn_sa, float* xn_obs, int64_t ld_o,
-                                   float* rew, float* done, pqlk_stream_t stream);
+// ================================================================================================
+// Record formats: fp32 observations (PQLK_OBS_F32, RecLayout) and half-precision ones (PQLK_OBS_F16, RecLayoutH; both layouts in
+// pqlk_common.h).  fp16 records are handled as raw 32-bit words: a word that packs two halves is only ever copied or taken apart with integer
+// shifts, never treated as a float.  fp32 -> fp16 is the hardware's round-to-nearest-even conversion (v_cvt_f16_f32: overflow
+// to +-inf, fp16 subnormals produced, NaN stays NaN), fp16 -> fp32 is exact, so a ring fed x holds q(x) = (float)(half)x.
+// Insert, plain gather, the generic fused gather and the whole host side are written ONCE for both formats, over the traits
+// RecF32 / RecF16 below.  Only the tuned gathers have kernels of their own per format -- k_replay_gather_fast / _obs (fp32) and
+// their _f16 (16-B chunks) and _h8 (8-B chunks) twins: they are latency-bound chains on the one in-order vector-memory counter,
+// and a dtype flag or template argument cost k_replay_gather_fast 20 % (round 4: 2 -> 14 full drains of that counter).  An
+// optimisation tuned for one workload keeps an implementation of its own; nothing is shared between those six bodies.
+__device__ __forceinline__ uint32_t pack_h2(float a, float b) {
+  const _Float16 ha = (_Float16)a, hb = (_Float16)b;
+  return (uint32_t)__builtin_bit_cast(unsigned short, ha) | ((uint32_t)__builtin_bit_cast(unsigned short, hb) << 16);
+}
+__device__ __forceinline__ float h_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float h_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+// the 8 columns of one 16-B observation chunk
+__device__ __forceinline__ void widen8(const uint4& w, float e[8]) {
+  e[0] = h_lo(w.x); e[1] = h_hi(w.x); e[2] = h_lo(w.y); e[3] = h_hi(w.y);
+  e[4] = h_lo(w.z); e[5] = h_hi(w.z); e[6] = h_lo(w.w); e[7] = h_hi(w.w);
+}
+
+// What the two record formats differ in, for the code that is written once: the layout, the type of a record word, whether
+// observations are stored as halves (which tuned kernels the host picks), how many observation columns a 16-B chunk of an
+// observation field holds, how such a chunk becomes columns (widen) and how the COLS / 4 columns of one word become that word
+// (pack).  (The action, reward and done words are raw fp32 in both formats.)
+struct RecF32 {
+  typedef RecLayout Layout;
+  typedef float word;
+  static constexpr bool HALF = false;
+  static constexpr int COLS = 4;
+  static Layout layout(int O, int A) { return rec_layout(O, A); }
+  __device__ __forceinline__ static void widen(const uint4& w, float e[4]) {
+    e[0] = __uint_as_float(w.x); e[1] = __uint_as_float(w.y); e[2] = __uint_as_float(w.z); e[3] = __uint_as_float(w.w);
+  }
+  __device__ __forceinline__ static uint32_t pack(const float e[1]) { return __float_as_uint(e[0]); }
+};
+struct RecF16 {
+  typedef RecLayoutH Layout;
+  typedef uint32_t word;
+  static constexpr bool HALF = true;
+  static constexpr int COLS = 8;
+  static Layout layout(int O, int A) { return rec_layout_h(O, A); }
+  __device__ __forceinline__ static void widen(const uint4& w, float e[8]) { widen8(w, e); }
+  __device__ __forceinline__ static uint32_t pack(const float e[2]) { return pack_h2(e[0], e[1]); }
+};
+
+// PQLK_OK, or the error code every replay entry point returns for a malformed ring: null, shape, dtype, rec_ld, in that order
+// (pointers: the call's other pointers that must never be null are there; rows: its m or b)
+static int ring_ok(const PqlReplayDesc* ring, bool pointers, int64_t rows) {
+  PQLK_REQUIRE(ring && ring->records && pointers, PQLK_E_NULL);
+  PQLK_REQUIRE(ring->obs_dim > 0 && ring->capacity > 0 && rows >= 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(ring->obs_dtype == PQLK_OBS_F32 || ring->obs_dtype == PQLK_OBS_F16, PQLK_E_SHAPE);
+  PQLK_REQUIRE(ring->rec_ld == pqlk_replay_rec_ld_ex(ring->obs_dim, ring->act_dim, ring->obs_dtype), PQLK_E_SHAPE);
+  return PQLK_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
-// insert: row r of the five source arrays -> record (dst_start + r).  One wave per record.
-__global__ __launch_bounds__(256) void k_replay_insert(float* __restrict__ records, RecLayout L, int64_t dst_start,
-                                                       int64_t m, const float* __restrict__ obs, int64_t ld_obs,
-                                                       const float* __restrict__ act, int64_t ld_act,
+// insert: row r of the five source arrays -> record (dst_start + r).  One wave per record, a lane per word over the WHOLE
+// stride (pad columns, pad halves and pad words written as zero): the source rows are read lane-contiguously.  The branches, and
+// the done word as a select of two floats, are those the fp32 insert always had: RecF32 (the default format's hand-off) then
+// compiles to the instructions it always had.
+template <class F>
+__global__ __launch_bounds__(256) void k_replay_insert(typename F::word* __restrict__ records, typename F::Layout L,
+                                                       int64_t dst_start, int64_t m, const float* __restrict__ obs,
+                                                       int64_t ld_obs, const float* __restrict__ act, int64_t ld_act,
                                                        const float* __restrict__ rew, int64_t ld_rew,
                                                        const float* __restrict__ nobs, int64_t ld_nobs,
                                                        const float* __restrict__ done, int64_t ld_done) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * 4;
+  constexpr int W = F::COLS / 4;      // observation columns per word
+  const int ow = (L.O + W - 1) / W;   // words of an observation field that hold a column
+  // word k of an observation field, from the source row s
+  auto field = [&](const float* __restrict__ s, int k) {
+    float e[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) e[j] = k * W + j < L.O ? s[k * W + j] : 0.f;
+    return F::pack(e);
+  };
   for (int64_t r = wave; r < m; r += nwaves) {
-    float* rec = records + (dst_start + r) * L.ld;
+    uint32_t* rec = reinterpret_cast<uint32_t*>(records + (dst_start + r) * L.ld);
     for (int c = lane; c < L.ld; c += 64) {
-      float v = 0.f;
-      if (c < L.O) {
-        v = obs[r * ld_obs + c];
+      uint32_t w = 0u;
+      if (c < ow) {
+        w = field(obs + r * ld_obs, c);
       } else if (L.A >= 0) {
-        if (c >= L.off_nobs && c < L.off_nobs + L.O) v = nobs[r * ld_nobs + (c - L.off_nobs)];
-        else if (c >= L.off_act && c < L.off_act + L.A) v = act[r * ld_act + (c - L.off_act)];
-        else if (c == L.off_rd) v = rew[r * ld_rew];
-        else if (c == L.off_rd + 1) v = (done[r * ld_done] != 0.f) ? 1.f : 0.f;  // .bool() then .float()
+        if (c >= L.off_nobs && c < L.off_nobs + ow) w = field(nobs + r * ld_nobs, c - L.off_nobs);
+        else if (c >= L.off_act && c < L.off_act + L.A) w = __float_as_uint(act[r * ld_act + (c - L.off_act)]);
+        else if (c == L.off_rd) w = __float_as_uint(rew[r * ld_rew]);
+        else if (c == L.off_rd + 1) w = __float_as_uint(done[r * ld_done] != 0.f ? 1.f : 0.f);  // .bool() then .float()
       }
-      rec[c] = v;
+      rec[c] = w;
     }
   }
+}
+
+template <class F>
+static int replay_insert(const PqlReplayDesc* ring, int64_t dst_start, int64_t m, const float* obs, int64_t ld_obs,
+                         const float* act, int64_t ld_act, const float* rew, int64_t ld_rew, const float* next_obs,
+                         int64_t ld_nobs, const float* done, int64_t ld_done, pqlk_stream_t stream) {
+  int64_t blocks = (m + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_replay_insert<F>, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream),
+                     reinterpret_cast<typename F::word*>(ring->records), F::layout(ring->obs_dim, ring->act_dim), dst_start, m,
+                     obs, ld_obs, act, ld_act, rew, ld_rew, next_obs, ld_nobs, done, ld_done);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
 }
 
 extern "C" int pqlk_replay_insert(const PqlReplayDesc* ring, int64_t dst_start, int64_t m, const float* obs,
                                   int64_t ld_obs, const float* act, int64_t ld_act, const float* rew, int64_t ld_rew,
                                   const float* next_obs, int64_t ld_nobs, const float* done, int64_t ld_done,
                                   pqlk_stream_t stream) {
-  PQLK_REQUIRE(ring && ring->records && obs, PQLK_E_NULL);
-  PQLK_REQUIRE(ring->obs_dim > 0 && ring->capacity > 0 && m >= 0, PQLK_E_SHAPE);
-  if (ring->obs_dtype == PQLK_OBS_F16)
-    return replay_insert_f16(ring, dst_start, m, obs, ld_obs, act, ld_act, rew, ld_rew, next_obs, ld_nobs, done, ld_done, stream);
-  PQLK_REQUIRE(ring->obs_dtype == PQLK_OBS_F32, PQLK_E_SHAPE);
-  RecLayout L = rec_layout(ring->obs_dim, ring->act_dim);
-  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
+  if (const int rc = ring_ok(ring, obs != nullptr, m)) return rc;
   PQLK_REQUIRE(dst_start >= 0 && dst_start + m <= ring->capacity, PQLK_E_RANGE);
-  if (L.A >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
-  PQLK_REQUIRE(ld_obs >= L.O, PQLK_E_SHAPE);
+  if (ring->act_dim >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
+  PQLK_REQUIRE(ld_obs >= ring->obs_dim, PQLK_E_SHAPE);
   if (m == 0) return PQLK_OK;
-  int64_t blocks = (m + 3) / 4;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_replay_insert, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream), ring->records, L, dst_start, m,
-                     obs, ld_obs, act, ld_act, rew, ld_rew, next_obs, ld_nobs, done, ld_done);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
+  // (RecF32 first: the instantiations are laid out in this order, and k_replay_insert<RecF32> measured 0.1 us (3 %) slower per
+  //  hand-off as the code object's second kernel than as its first, where the fp32 insert always stood)
+  return ring->obs_dtype == PQLK_OBS_F32
+             ? replay_insert<RecF32>(ring, dst_start, m, obs, ld_obs, act, ld_act, rew, ld_rew, next_obs, ld_nobs, done, ld_done, stream)
+             : replay_insert<RecF16>(ring, dst_start, m, obs, ld_obs, act, ld_act, rew, ld_rew, next_obs, ld_nobs, done, ld_done, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
-// plain gather: five contiguous outputs, byte-exact copies (done already 0.0/1.0).
-__global__ __launch_bounds__(256) void k_replay_gather(const float* __restrict__ records, RecLayout L, int64_t capacity,
-                                                       const int64_t* __restrict__ idx, int64_t b,
+// plain gather: five contiguous fp32 outputs, byte-exact copies of what the ring holds (fp16 observations widened exactly;
+// done already 0.0/1.0).
+template <class F>
+__global__ __launch_bounds__(256) void k_replay_gather(const typename F::word* __restrict__ records, typename F::Layout L,
+                                                       int64_t capacity, const int64_t* __restrict__ idx, int64_t b,
                                                        float* __restrict__ o_obs, float* __restrict__ o_act,
                                                        float* __restrict__ o_rew, float* __restrict__ o_nobs,
                                                        float* __restrict__ o_done) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int nchunk = L.used >> 2;
   for (int64_t r = wave; r < b; r += nwaves) {
     int64_t src = idx[r];
     if (src < 0 || src >= capacity) src = 0;  // never fault on a bad index; host validates in debug paths
-    const float4* rec4 = reinterpret_cast<const float4*>(records + src * L.ld);
-    const int nchunk = L.used >> 2;
+    const uint4* rec4 = reinterpret_cast<const uint4*>(records + src * L.ld);
     for (int q = lane; q < nchunk; q += 64) {
-      float4 v = rec4[q];
-      const float e[4] = {v.x, v.y, v.z, v.w};
+      const uint4 w = rec4[q];
       const int c = q << 2;
-      if (c < L.o4) {
+      if (c < L.off_act) {   // obs / next_obs (an obs-only record ends at off_act)
+        const bool nx = c >= L.off_nobs;
+        float* o = (nx ? o_nobs : o_obs) + r * L.O;
+        const int col = (nx ? c - L.off_nobs : c) * (F::COLS / 4);
+        float e[F::COLS];
+        F::widen(w, e);
+#pragma unroll
+        for (int j = 0; j < F::COLS; ++j)
+          if (col + j < L.O) o[col + j] = e[j];
+      } else if (c < L.off_rd) {
+        const int cc = c - L.off_act;
+        const uint32_t e[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (c + j < L.O) o_obs[r * L.O + c + j] = e[j];
-      } else if (L.A >= 0) {
-        if (c < L.off_act) {
-          const int cc = c - L.off_nobs;
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (cc + j < L.O) o_nobs[r * L.O + cc + j] = e[j];
-        } else if (c < L.off_rd) {
-          const int cc = c - L.off_act;
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (cc + j < L.A) o_act[r * L.A + cc + j] = e[j];
-        } else {
-          o_rew[r] = e[0];
-          o_done[r] = e[1];
-        }
+          if (cc + j < L.A) o_act[r * L.A + cc + j] = __uint_as_float(e[j]);
+      } else {
+        o_rew[r] = __uint_as_float(w.x);
+        o_done[r] = __uint_as_float(w.y);
       }
     }
   }
 }
 
-extern "C" int pqlk_replay_gather(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, float* obs, float* act,
-                                  float* rew, float* next_obs, float* done, pqlk_stream_t stream) {
-  PQLK_REQUIRE(ring && ring->records && idx && obs, PQLK_E_NULL);
-  PQLK_REQUIRE(ring->obs_dim > 0 && ring->capacity > 0 && b >= 0, PQLK_E_SHAPE);
-  if (ring->obs_dtype == PQLK_OBS_F16) return replay_gather_f16(ring, idx, b, obs, act, rew, next_obs, done, stream);
-  PQLK_REQUIRE(ring->obs_dtype == PQLK_OBS_F32, PQLK_E_SHAPE);
-  RecLayout L = rec_layout(ring->obs_dim, ring->act_dim);
-  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
-  if (L.A >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
-  if (b == 0) return PQLK_OK;
+template <class F>
+static int replay_gather(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, float* obs, float* act, float* rew,
+                         float* next_obs, float* done, pqlk_stream_t stream) {
   int64_t blocks = (b + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream), ring->records, L,
+  hipLaunchKernelGGL(k_replay_gather<F>, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream),
+                     reinterpret_cast<const typename F::word*>(ring->records), F::layout(ring->obs_dim, ring->act_dim),
                      ring->capacity, idx, b, obs, act, rew, next_obs, done);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }
 
+extern "C" int pqlk_replay_gather(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, float* obs, float* act,
+                                  float* rew, float* next_obs, float* done, pqlk_stream_t stream) {
+  if (const int rc = ring_ok(ring, idx && obs, b)) return rc;
+  if (ring->act_dim >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
+  if (b == 0) return PQLK_OK;
+  return ring->obs_dtype == PQLK_OBS_F16 ? replay_gather<RecF16>(ring, idx, b, obs, act, rew, next_obs, done, stream)
+                                         : replay_gather<RecF32>(ring, idx, b, obs, act, rew, next_obs, done, stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // fused gather: sample + normalise (+-5 clamp) + concat into the padded GEMM input tiles.
-// IEEE division on purpose.  A reciprocal per column + two fma corrections (Markstein) also gives the correctly rounded
-// quotient and was tried (round 2): with the range / exceptional-significand guards it needs it is ~15 instructions against
-// the hardware sequence's ~11, and measured 0.9 us SLOWER per 32768-row launch.
-__device__ __forceinline__ float norm1(float x, float mean, float sd, int clamp5) {
-  float y = (x - mean) / sd;  // IEEE division: bit-identical to (x-mean)/sqrt(var+eps) evaluated by torch
-  if (clamp5) y = fminf(fmaxf(y, -5.f), 5.f);
-  return y;
-}
+// (A reciprocal per column + two fma corrections (Markstein) also gives the correctly rounded quotient and was tried against the
+// fp32 division sequence in round 2: with the range / exceptional-significand guards it needs it is ~15 instructions against the
+// hardware sequence's ~11, and measured 0.9 us SLOWER per 32768-row launch.  What replaced that sequence is norm_div.)
+// (x - mean) / sd with the division as ONE double-precision product rounded once to fp32 -- bit for bit the IEEE quotient the
+// reference's `(x - mean) / sqrt(var + eps)` rounds to (common.py:139-145), in 3 instructions per element instead of the 12 of the
+// fp32 division sequence (v_div_scale x2, v_rcp, 6 FMAs / multiplies, v_div_fmas, v_div_fixup): the gather kernels spent ~100 VALU
+// instructions per record on four divisions.  rd = 1 / (double)sd is formed once per lane (correctly rounded: relative error
+// <= 2^-53), the product adds <= 2^-53, so the double result is within 2^-51.9 (relative) of a / sd.  The exact quotient of two
+// fp32 numbers is never that close to a boundary between two fp32 results: a boundary m has <= 25 significant bits, a - m sd != 0
+// is a multiple of ulp(m) ulp(sd), which puts |a / sd - m| / |a / sd| above 2^-49 (normal and denormal results alike; the overflow
+// threshold is one more such boundary).  Signed zeros, infinities and NaN come out as IEEE division gives them (a * (1 / inf) =
+// a * 0).  tests: the gather tests are bit-exact against the oracle's fp32 division; test_gather_division_is_the_ieee_quotient.
+__device__ __forceinline__ float norm_div(float a, double rd) { return (float)((double)a * rd); }
 
 #define GATHER_MAX_OBS 1024
 
@@ -165,24 +239,32 @@ __device__ __forceinline__ void store4(float* __restrict__ row, int col, int lim
   }
 }
 
-// R rows per wave per trip with all their record loads in flight at once (memory-level parallelism for the random
-// HBM reads); CH = 16-B chunks per lane per record (1 covers records up to 1 KiB, e.g. cfg #2's 784 used bytes).
-template <bool HAS_NORM, int R, int CH>
-__global__ __launch_bounds__(256) void k_replay_gather_fused(const float* __restrict__ records, RecLayout L,
+// the F::COLS columns [col, col + COLS) of an observation chunk: one store4 per 4 columns (16-B aligned: col is a multiple of 4)
+template <class F>
+__device__ __forceinline__ void store_obs(float* __restrict__ row, int col, int limit, const float e[F::COLS]) {
+#pragma unroll
+  for (int k = 0; k < F::COLS; k += 4) store4(row, col + k, limit, e + k, true);
+}
+
+// Generic fused gather (records of more than one 16-B chunk per lane, tiles wider than the lean kernels' pad bound, unaligned
+// tiles), for both formats.  R rows per wave per trip with all their record loads in flight at once (memory-level parallelism
+// for the random HBM reads); CH = 16-B chunks per lane per record (1 covers records up to 1 KiB, e.g. cfg #2's 784 used bytes).
+template <class F, bool HAS_NORM, int R, int CH>
+__global__ __launch_bounds__(256) void k_replay_gather_fused(const typename F::word* __restrict__ records, typename F::Layout L,
                                                              int64_t capacity, const int64_t* __restrict__ idx, int64_t b,
                                                              const float* __restrict__ mean, const float* __restrict__ var,
                                                              float eps, int clamp5, float* __restrict__ x_sa, int64_t ld_sa,
                                                              float* __restrict__ xn_sa, float* __restrict__ xn_obs,
                                                              int64_t ld_o, float* __restrict__ o_rew,
                                                              float* __restrict__ o_done, int write_pads) {
-  // per-column mean and sd = sqrt(var + eps) (correctly rounded sqrtf) staged once per block: the per-element work
-  // is then one subtract and one IEEE divide instead of a divide AND a square root
+  // per-column mean and 1 / sd, sd = sqrt(var + eps) (correctly rounded sqrtf), staged once per block; 1 / sd as a double
+  // (norm_div: one double-precision product rounded once)
   __shared__ float s_mean[HAS_NORM ? GATHER_MAX_OBS : 1];
-  __shared__ float s_sd[HAS_NORM ? GATHER_MAX_OBS : 1];
+  __shared__ double s_rd[HAS_NORM ? GATHER_MAX_OBS : 1];
   if (HAS_NORM) {
     for (int c = threadIdx.x; c < L.O; c += 256) {
       s_mean[c] = mean[c];
-      s_sd[c] = sqrtf(var[c] + eps);
+      s_rd[c] = 1.0 / (double)sqrtf(var[c] + eps);
     }
     __syncthreads();
   }
@@ -194,17 +276,17 @@ __global__ __launch_bounds__(256) void k_replay_gather_fused(const float* __rest
   const int sa_cols = L.O + A;
   const bool act_aligned = (L.O & 3) == 0;
   for (int64_t r0 = wave * R; r0 < b; r0 += nwaves * R) {
-    float4 v[R][CH];
+    uint4 v[R][CH];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const int64_t r = r0 + i;
       int64_t src = r < b ? idx[r] : 0;
       if (src < 0 || src >= capacity) src = 0;  // never fault on a bad index
-      const float4* rec4 = reinterpret_cast<const float4*>(records + src * L.ld);
+      const uint4* rec4 = reinterpret_cast<const uint4*>(records + src * L.ld);
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         const int q = lane + 64 * c;
-        v[i][c] = q < nchunk ? rec4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[i][c] = q < nchunk ? rec4[q] : make_uint4(0u, 0u, 0u, 0u);
       }
     }
 #pragma unroll
@@ -218,37 +300,36 @@ __global__ __launch_bounds__(256) void k_replay_gather_fused(const float* __rest
       for (int cch = 0; cch < CH; ++cch) {
         const int q = lane + 64 * cch;
         if (q >= nchunk) continue;
-        float e[4] = {v[i][cch].x, v[i][cch].y, v[i][cch].z, v[i][cch].w};
+        const uint4 w = v[i][cch];
         const int c = q << 2;
-        if (c < L.o4) {  // obs
+        if (c < L.off_act) {  // obs / next_obs (an obs-only record ends at off_act)
+          const bool nx = c >= L.off_nobs;
+          const int col = (nx ? c - L.off_nobs : c) * (F::COLS / 4);
+          float e[F::COLS];
+          F::widen(w, e);
           if (HAS_NORM) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (c + j < L.O) e[j] = norm1(e[j], s_mean[c + j], s_sd[c + j], clamp5);
+            for (int j = 0; j < F::COLS; ++j)
+              if (col + j < L.O) {
+                e[j] = norm_div(e[j] - s_mean[col + j], s_rd[col + j]);
+                if (clamp5) e[j] = fminf(fmaxf(e[j], -5.f), 5.f);
+              }
           }
-          if (xs) store4(xs, c, L.O, e, true);
-          if (L.A < 0 && xno) store4(xno, c, L.O, e, true);  // obs-only ring: the sample IS the learner's obs batch
-        } else if (L.A >= 0) {
-          if (c < L.off_act) {  // next_obs
-            const int cc = c - L.off_nobs;
-            if (HAS_NORM) {
-#pragma unroll
-              for (int j = 0; j < 4; ++j)
-                if (cc + j < L.O) e[j] = norm1(e[j], s_mean[cc + j], s_sd[cc + j], clamp5);
-            }
-            if (xns) store4(xns, cc, L.O, e, true);
-            if (xno) store4(xno, cc, L.O, e, true);
-          } else if (c < L.off_rd) {  // action -> columns O.. of the critic input
-            const int cc = c - L.off_act;
-            if (xs) store4(xs + L.O, cc, L.A, e, act_aligned);
+          if (!nx) {
+            if (xs) store_obs<F>(xs, col, L.O, e);
+            if (L.A < 0 && xno) store_obs<F>(xno, col, L.O, e);  // obs-only ring: the sample IS the learner's obs batch
           } else {
-            if (o_rew) o_rew[r] = e[0];
-            if (o_done) o_done[r] = e[1];
+            if (xns) store_obs<F>(xns, col, L.O, e);
+            if (xno) store_obs<F>(xno, col, L.O, e);
           }
+        } else if (c < L.off_rd) {  // action -> columns O.. of the critic input
+          const int cc = c - L.off_act;
+          const float e[4] = {__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w)};
+          if (xs) store4(xs + L.O, cc, L.A, e, act_aligned);
+        } else {
+          if (o_rew) o_rew[r] = __uint_as_float(w.x);
+          if (o_done) o_done[r] = __uint_as_float(w.y);
         }
-      }
-      if (L.A < 0 && xs) {
-        for (int c = L.O + lane; c < sa_cols; c += 64) xs[c] = 0.f;
       }
       if (!write_pads) continue;
       // zero the pad columns so the GEMM K-loop can run over the padded width unchecked
@@ -261,17 +342,6 @@ __global__ __launch_bounds__(256) void k_replay_gather_fused(const float* __rest
     }
   }
 }
-
-// (x - mean) / sd with the division as ONE double-precision product rounded once to fp32 -- bit for bit the IEEE quotient the
-// reference's `(x - mean) / sqrt(var + eps)` rounds to (common.py:139-145), in 3 instructions per element instead of the 12 of the
-// fp32 division sequence (v_div_scale x2, v_rcp, 6 FMAs / multiplies, v_div_fmas, v_div_fixup): the gather kernels spent ~100 VALU
-// instructions per record on four divisions.  rd = 1 / (double)sd is formed once per lane (correctly rounded: relative error
-// <= 2^-53), the product adds <= 2^-53, so the double result is within 2^-51.9 (relative) of a / sd.  The exact quotient of two
-// fp32 numbers is never that close to a boundary between two fp32 results: a boundary m has <= 25 significant bits, a - m sd != 0
-// is a multiple of ulp(m) ulp(sd), which puts |a / sd - m| / |a / sd| above 2^-49 (normal and denormal results alike; the overflow
-// threshold is one more such boundary).  Signed zeros, infinities and NaN come out as IEEE division gives them (a * (1 / inf) =
-// a * 0).  tests: the gather tests are bit-exact against the oracle's fp32 division; test_gather_division_is_the_ieee_quotient.
-__device__ __forceinline__ float norm_div(float a, double rd) { return (float)((double)a * rd); }
 
 // Fast path for transition rings whose record fits one 16-B chunk per lane (<= 1 KiB used, e.g. cfg #2 and #5): the field
 // decode, destination and normalisation constants of a lane depend only on its chunk index, so they are computed ONCE
@@ -508,323 +578,6 @@ __global__ __launch_bounds__(256) void k_replay_gather_obs(const float* __restri
         for (int64_t k = L.O + cl; k < ld_sa; k += P) x_sa[r * ld_sa + k] = 0.f;
       if (x_obs)
         for (int64_t k = L.O + cl; k < ld_o; k += P) x_obs[r * ld_o + k] = 0.f;
-    }
-  }
-}
-
-template <bool HAS_NORM>
-static void launch_gather_fused(int nchunk, unsigned blocks, hipStream_t st, const float* records, RecLayout L, int64_t capacity,
-                                const int64_t* idx, int64_t b, const float* mean, const float* var, float eps, int clamp5,
-                                float* x_sa, int64_t ld_sa, float* xn_sa, float* xn_obs, int64_t ld_o, float* rew, float* done,
-                                int write_pads) {
-#define PQLK_GF(R, CH)                                                                                                   \
-  hipLaunchKernelGGL((k_replay_gather_fused<HAS_NORM, R, CH>), dim3(blocks), dim3(256), 0, st, records, L, capacity, idx, b, \
-                     mean, var, eps, clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads)
-  if (nchunk <= 64) PQLK_GF(4, 1);
-  else if (nchunk <= 128) PQLK_GF(2, 2);
-  else if (nchunk <= 256) PQLK_GF(1, 4);
-  else PQLK_GF(1, 16);
-#undef PQLK_GF
-}
-
-extern "C" int pqlk_replay_gather_fused(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, const float* mean,
-                                        const float* var, float eps, int flags, float* x_sa, int64_t ld_sa,
-                                        float* xn_sa, float* xn_obs, int64_t ld_o, float* rew, float* done,
-                                        pqlk_stream_t stream) {
-  const int clamp5 = flags & PQLK_GATHER_CLAMP5;
-  const int write_pads = (flags & PQLK_GATHER_PADS_ZERO) ? 0 : 1;
-  const int tune_R = (flags >> 8) & 15, tune_wpc = (flags >> 12) & 63;
-  int nt_loads = ((flags & PQLK_GATHER_NT_LOADS) ? 1 : 0) | ((flags & PQLK_GATHER_NT_STORES) ? 2 : 0);
-  PQLK_REQUIRE(ring && ring->records && idx, PQLK_E_NULL);
-  PQLK_REQUIRE(ring->obs_dim > 0 && ring->capacity > 0 && b >= 0, PQLK_E_SHAPE);
-  if (ring->obs_dtype == PQLK_OBS_F16)
-    return replay_gather_fused_f16(ring, idx, b, mean, var, eps, flags, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, stream);
-  PQLK_REQUIRE(ring->obs_dtype == PQLK_OBS_F32, PQLK_E_SHAPE);
-  RecLayout L = rec_layout(ring->obs_dim, ring->act_dim);
-  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
-  PQLK_REQUIRE((mean == nullptr) == (var == nullptr), PQLK_E_NULL);
-  if (mean) PQLK_REQUIRE(L.O <= GATHER_MAX_OBS, PQLK_E_UNSUPPORTED);
-  if (x_sa || xn_sa) PQLK_REQUIRE(ld_sa % 32 == 0 && ld_sa >= L.O + (L.A < 0 ? 0 : L.A), PQLK_E_ALIGN);
-  if (xn_obs) PQLK_REQUIRE(ld_o % 32 == 0 && ld_o >= L.O, PQLK_E_ALIGN);
-  if (L.A < 0) PQLK_REQUIRE(xn_sa == nullptr, PQLK_E_UNSUPPORTED);
-  if (b == 0) return PQLK_OK;
-  PQLK_REQUIRE((L.used >> 2) <= 1024, PQLK_E_UNSUPPORTED);
-  const int nchunk = L.used >> 2;
-  const int rows_per_wave = nchunk <= 64 ? 4 : (nchunk <= 128 ? 2 : 1);
-  int64_t blocks = (b + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
-  if (blocks > 2048) blocks = 2048;
-  // aligned transition-ring shape -> lean kernel (pads: at most 64 16-B chunks in total, one lane each)
-  // (the pad-column bound only matters when this call has to zero the pads: one lane per pad chunk)
-  const bool fast = L.A >= 0 && nchunk <= 128 && (!write_pads || ((ld_sa - L.O - L.A) <= 64 && (!xn_obs || (ld_o - L.O) <= 64))) &&
-                    pqlk_aligned16(x_sa) && pqlk_aligned16(xn_sa) && pqlk_aligned16(xn_obs);
-  if (fast) {
-    // rows in flight per wave: 2 up to 16 Ki rows (more waves, shorter dependent idx -> row chain: 9.3 vs 10.5 us at 8192),
-    // 4 beyond (same time at 32 Ki rows, fewer blocks)
-    // 2 rows in flight per wave, at most 12 (rounds 1-2: 24) resident waves per CU: beyond that the grid-stride loop takes
-    // further trips.  Measured at cfg 5 (32768 rows x 1 KiB, pads not re-zeroed; tools/bench_gather.py): 24 waves/CU x 2 rows
-    // 18.5 us, 16 x 2 19.5, 12 x 2 21.4, 32 x 2 22.3, 16 x 4 20.3, 32 x 4 (one trip per wave, the round-1 shape) 23.0, 8 rows
-    // in flight 30; at cfg 2 (8192 rows, one trip whatever the cap) 2 rows per wave 7.1 us vs 8.1 (4) and 9.0 (1).
-    // Non-temporal record loads: no gain (18.9 vs 18.5).  Requesting trip k+1's records before trip k is normalised and stored
-    // (software pipeline): WORSE, 21.5 us -- on gfx9 stores share the in-order vmcnt queue with loads, so the wait for the
-    // prefetched records also waits for the previous trip's store acknowledgements.  With the ring small enough to sit in the
-    // Infinity Cache (51 MB) the same launch takes 14.9 us: the 5-GB ring's random 1-KiB reads cost ~4 us on top of that, and
-    // ring size hardly matters beyond the cache (0.25 GB 18.0 us, 5 GB 19.3, 20 GB 20.1: not a TLB effect).  A loader / consumer
-    // split (one wave per workgroup issuing LDS-DMA record loads into a 16-slot LDS ring behind a counted vmcnt, three waves
-    // normalising and storing out of the ring, so that no wave ever mixes loads and stores) was built and measured too:
-    // 20.2 us at best -- no better than this kernel, i.e. the limit is the memory system's rate for this mix (about 4 TB/s of
-    // bytes moved), not the way one wave's loads and stores queue.
-    // Round 3 (the K-batch launches: 65 536 rows at cfg 2, five or more trips per wave): with the sample indices loaded one trip
-    // ahead, as SCALAR loads (k_replay_gather_fast), the optimum moved to 12 waves per CU -- 25.1 us at cfg 2 x 8 against 26.5
-    // at 24 and 31.5 at 8 (before: 35.3 at 12, 27.0 at 24); cfg 4 x 8 54.9-57.0 at 12-32; cfg 5 x 8 flat, 145-148 us at 8-32.
-    int R = 2;
-    if (tune_R == 1 || tune_R == 2 || tune_R == 4 || tune_R == 8) R = tune_R;
-    const int halves = nchunk > 64 ? 2 : 1;   // 1-2 KiB records: two waves per row
-    const int rows_blk = 4 / halves * R;
-    int64_t fb = (b + rows_blk - 1) / rows_blk;
-    const int wpc = tune_wpc ? tune_wpc : 12;
-    if (fb > 256 * (int64_t)wpc / 4) fb = 256 * (int64_t)wpc / 4;
-    // Launches whose record reads alone exceed what the 256-MB Infinity Cache can hold beside the output tiles (cfg #5 x 8: 262 144
-    // rows x 1 KiB) take the records with non-temporal loads: they are read once and would only push the tiles out.  Round 4,
-    // tools/bench_gather.py cfg5x8: 150 -> 98 us back to back, 129 -> 123 us one launch at a time; cfg #2 x 8 (59 MB of records):
-    // no difference either way, left alone.
-    if (!tune_R && !tune_wpc && b * (int64_t)L.ld * 4 > ((int64_t)192 << 20)) nt_loads |= 1;
-    const dim3 g((unsigned)fb), t(256);
-#define PQLK_GATHER_FAST(NORM, RR) \
-    hipLaunchKernelGGL((k_replay_gather_fast<NORM, RR>), g, t, 0, pqlk_s(stream), ring->records, L, ring->capacity, idx, b, mean, var, \
-                       eps, clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads, nt_loads, halves)
-#define PQLK_GATHER_FAST_R(NORM) \
-    do { if (R == 1) PQLK_GATHER_FAST(NORM, 1); else if (R == 2) PQLK_GATHER_FAST(NORM, 2); else if (R == 4) PQLK_GATHER_FAST(NORM, 4); \
-         else PQLK_GATHER_FAST(NORM, 8); } while (0)
-    if (mean) PQLK_GATHER_FAST_R(true); else PQLK_GATHER_FAST_R(false);
-#undef PQLK_GATHER_FAST_R
-#undef PQLK_GATHER_FAST
-    PQLK_LAUNCH_CHECK();
-    return PQLK_OK;
-  }
-  // obs-only ring whose record fits one 16-B chunk per lane (O <= 256): several records per wave instruction
-  if (L.A < 0 && nchunk <= 64 && pqlk_aligned16(x_sa) && pqlk_aligned16(xn_obs) && (x_sa || xn_obs)) {
-    int lgp = 0;
-    while ((1 << lgp) < nchunk) ++lgp;
-    const int G = 64 >> lgp;
-    // rows in flight per wave: R x G, R chosen so that the launch still has ~16 waves per CU to issue from (32 768 rows of
-    // cfg #2, G = 2: R = 4, 4096 waves, one trip); waves per CU capped at 16 (grid-stride trips beyond)
-    const int64_t groups = (b + G - 1) / G;
-    int R = groups >= 4 * 4096 ? 4 : (groups >= 2 * 4096 ? 2 : 1);
-    if (tune_R == 1 || tune_R == 2 || tune_R == 4) R = tune_R;
-    const int wpc = tune_wpc ? tune_wpc : 16;
-    int64_t fb = (groups + 4 * R - 1) / (4 * R);
-    if (fb > 256 * (int64_t)wpc / 4) fb = 256 * (int64_t)wpc / 4;
-    const dim3 g((unsigned)fb), t(256);
-#define PQLK_GATHER_OBS(NORM, RR) \
-    hipLaunchKernelGGL((k_replay_gather_obs<NORM, RR>), g, t, 0, pqlk_s(stream), ring->records, L, ring->capacity, idx, b, mean, var, eps, \
-                       clamp5, x_sa, ld_sa, xn_obs, ld_o, write_pads, lgp)
-#define PQLK_GATHER_OBS_R(NORM) \
-    do { if (R == 1) PQLK_GATHER_OBS(NORM, 1); else if (R == 2) PQLK_GATHER_OBS(NORM, 2); else PQLK_GATHER_OBS(NORM, 4); } while (0)
-    if (mean) PQLK_GATHER_OBS_R(true); else PQLK_GATHER_OBS_R(false);
-#undef PQLK_GATHER_OBS_R
-#undef PQLK_GATHER_OBS
-    PQLK_LAUNCH_CHECK();
-    return PQLK_OK;
-  }
-  if (mean)
-    launch_gather_fused<true>(nchunk, (unsigned)blocks, pqlk_s(stream), ring->records, L, ring->capacity, idx, b, mean, var, eps,
-                              clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads);
-  else
-    launch_gather_fused<false>(nchunk, (unsigned)blocks, pqlk_s(stream), ring->records, L, ring->capacity, idx, b, mean, var, eps,
-                               clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
-}
-
-// ================================================================================================
-// Half-precision observation storage (PqlReplayDesc.obs_dtype == PQLK_OBS_F16; layout: RecLayoutH in pqlk_common.h).
-// The kernels below are the fp16 counterparts of the five above, under names of their own: the fp32 kernels carry no dtype flag
-// or template argument (round 4 lost 20 % on k_replay_gather_fast to exactly that), the entry points dispatch on the host.
-// Records are handled as raw 32-bit words: a word that packs two halves is only ever copied or taken apart with integer
-// shifts, never treated as a float.  fp32 -> fp16 is the hardware's round-to-nearest-even conversion (v_cvt_f16_f32: overflow
-// to +-inf, fp16 subnormals produced, NaN stays NaN), fp16 -> fp32 is exact, so a ring fed x holds q(x) = (float)(half)x.
-__device__ __forceinline__ uint32_t pack_h2(float a, float b) {
-  const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-  return (uint32_t)__builtin_bit_cast(unsigned short, ha) | ((uint32_t)__builtin_bit_cast(unsigned short, hb) << 16);
-}
-__device__ __forceinline__ float h_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
-__device__ __forceinline__ float h_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
-// the 8 columns of one 16-B observation chunk
-__device__ __forceinline__ void widen8(const uint4& w, float e[8]) {
-  e[0] = h_lo(w.x); e[1] = h_hi(w.x); e[2] = h_lo(w.y); e[3] = h_hi(w.y);
-  e[4] = h_lo(w.z); e[5] = h_hi(w.z); e[6] = h_lo(w.w); e[7] = h_hi(w.w);
-}
-
-// insert: one wave per record, one 16-B store per lane and chunk over the WHOLE stride (pad halves and words written as zero)
-__global__ __launch_bounds__(256) void k_replay_insert_f16(uint32_t* __restrict__ records, RecLayoutH L, int64_t dst_start,
-                                                           int64_t m, const float* __restrict__ obs, int64_t ld_obs,
-                                                           const float* __restrict__ act, int64_t ld_act,
-                                                           const float* __restrict__ rew, int64_t ld_rew,
-                                                           const float* __restrict__ nobs, int64_t ld_nobs,
-                                                           const float* __restrict__ done, int64_t ld_done) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * 4;
-  const int nq = L.ld >> 2;
-  for (int64_t r = wave; r < m; r += nwaves) {
-    uint4* rec4 = reinterpret_cast<uint4*>(records + (dst_start + r) * L.ld);
-    for (int q = lane; q < nq; q += 64) {
-      const int c = q << 2;
-      uint4 w = make_uint4(0u, 0u, 0u, 0u);
-      if (c < L.off_act) {   // obs, or next_obs (transition ring only: off_nobs == off_act == oh in an obs-only ring)
-        const bool nx = c >= L.off_nobs;
-        const float* s = nx ? nobs + r * ld_nobs : obs + r * ld_obs;
-        const int col = (nx ? c - L.off_nobs : c) << 1;
-        float e[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) e[j] = col + j < L.O ? s[col + j] : 0.f;
-        w = make_uint4(pack_h2(e[0], e[1]), pack_h2(e[2], e[3]), pack_h2(e[4], e[5]), pack_h2(e[6], e[7]));
-      } else if (c < L.off_rd) {
-        const int cc = c - L.off_act;
-        uint32_t e[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = cc + j < L.A ? __float_as_uint(act[r * ld_act + cc + j]) : 0u;
-        w = make_uint4(e[0], e[1], e[2], e[3]);
-      } else if (L.A >= 0 && c == L.off_rd) {
-        w.x = __float_as_uint(rew[r * ld_rew]);
-        w.y = (done[r * ld_done] != 0.f) ? __float_as_uint(1.f) : 0u;   // .bool() then .float()
-      }
-      rec4[q] = w;
-    }
-  }
-}
-
-// plain gather: five contiguous fp32 outputs, the observation fields widened exactly
-__global__ __launch_bounds__(256) void k_replay_gather_f16(const uint32_t* __restrict__ records, RecLayoutH L, int64_t capacity,
-                                                           const int64_t* __restrict__ idx, int64_t b,
-                                                           float* __restrict__ o_obs, float* __restrict__ o_act,
-                                                           float* __restrict__ o_rew, float* __restrict__ o_nobs,
-                                                           float* __restrict__ o_done) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * 4;
-  const int nchunk = L.used >> 2;
-  for (int64_t r = wave; r < b; r += nwaves) {
-    int64_t src = idx[r];
-    if (src < 0 || src >= capacity) src = 0;  // never fault on a bad index
-    const uint4* rec4 = reinterpret_cast<const uint4*>(records + src * L.ld);
-    for (int q = lane; q < nchunk; q += 64) {
-      const uint4 w = rec4[q];
-      const int c = q << 2;
-      if (c < L.off_act) {
-        const bool nx = c >= L.off_nobs;
-        float* o = (nx ? o_nobs : o_obs) + r * L.O;
-        const int col = (nx ? c - L.off_nobs : c) << 1;
-        float e[8];
-        widen8(w, e);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (col + j < L.O) o[col + j] = e[j];
-      } else if (c < L.off_rd) {
-        const int cc = c - L.off_act;
-        const uint32_t e[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (cc + j < L.A) o_act[r * L.A + cc + j] = __uint_as_float(e[j]);
-      } else {
-        o_rew[r] = __uint_as_float(w.x);
-        o_done[r] = __uint_as_float(w.y);
-      }
-    }
-  }
-}
-
-// Generic fused gather for fp16 rings (records of more than one 16-B chunk per lane, unaligned tiles): the structure of
-// k_replay_gather_fused; an observation chunk holds 8 columns and takes two 16-B stores per destination tile.  1 / sd is staged
-// once per block as a double (norm_div: one double-precision product rounded once).
-template <bool HAS_NORM, int R, int CH>
-__global__ __launch_bounds__(256) void k_replay_gather_fused_f16(const uint32_t* __restrict__ records, RecLayoutH L,
-                                                                 int64_t capacity, const int64_t* __restrict__ idx, int64_t b,
-                                                                 const float* __restrict__ mean, const float* __restrict__ var,
-                                                                 float eps, int clamp5, float* __restrict__ x_sa, int64_t ld_sa,
-                                                                 float* __restrict__ xn_sa, float* __restrict__ xn_obs,
-                                                                 int64_t ld_o, float* __restrict__ o_rew,
-                                                                 float* __restrict__ o_done, int write_pads) {
-  __shared__ float s_mean[HAS_NORM ? GATHER_MAX_OBS : 1];
-  __shared__ double s_rd[HAS_NORM ? GATHER_MAX_OBS : 1];
-  if (HAS_NORM) {
-    for (int c = threadIdx.x; c < L.O; c += 256) {
-      s_mean[c] = mean[c];
-      s_rd[c] = 1.0 / (double)sqrtf(var[c] + eps);
-    }
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * 4;
-  const int nchunk = L.used >> 2;
-  const int A = L.A < 0 ? 0 : L.A;
-  const int sa_cols = L.O + A;
-  const bool act_aligned = (L.O & 3) == 0;
-  for (int64_t r0 = wave * R; r0 < b; r0 += nwaves * R) {
-    uint4 v[R][CH];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const int64_t r = r0 + i;
-      int64_t src = r < b ? idx[r] : 0;
-      if (src < 0 || src >= capacity) src = 0;  // never fault on a bad index
-      const uint4* rec4 = reinterpret_cast<const uint4*>(records + src * L.ld);
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        const int q = lane + 64 * c;
-        v[i][c] = q < nchunk ? rec4[q] : make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const int64_t r = r0 + i;
-      if (r >= b) break;
-      float* xs = x_sa ? x_sa + r * ld_sa : nullptr;
-      float* xns = xn_sa ? xn_sa + r * ld_sa : nullptr;
-      float* xno = xn_obs ? xn_obs + r * ld_o : nullptr;
-#pragma unroll
-      for (int cch = 0; cch < CH; ++cch) {
-        const int q = lane + 64 * cch;
-        if (q >= nchunk) continue;
-        const uint4 w = v[i][cch];
-        const int c = q << 2;
-        if (c < L.off_act) {  // obs / next_obs: 8 columns
-          const bool nx = c >= L.off_nobs;
-          const int col = (nx ? c - L.off_nobs : c) << 1;
-          float e[8];
-          widen8(w, e);
-          if (HAS_NORM) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-              if (col + j < L.O) {
-                e[j] = norm_div(e[j] - s_mean[col + j], s_rd[col + j]);
-                if (clamp5) e[j] = fminf(fmaxf(e[j], -5.f), 5.f);
-              }
-          }
-          if (!nx) {
-            if (xs) { store4(xs, col, L.O, e, true); store4(xs, col + 4, L.O, e + 4, true); }
-            if (L.A < 0 && xno) { store4(xno, col, L.O, e, true); store4(xno, col + 4, L.O, e + 4, true); }
-          } else {
-            if (xns) { store4(xns, col, L.O, e, true); store4(xns, col + 4, L.O, e + 4, true); }
-            if (xno) { store4(xno, col, L.O, e, true); store4(xno, col + 4, L.O, e + 4, true); }
-          }
-        } else if (c < L.off_rd) {  // action -> columns O.. of the critic input
-          const int cc = c - L.off_act;
-          const float e[4] = {__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w)};
-          if (xs) store4(xs + L.O, cc, L.A, e, act_aligned);
-        } else {
-          if (o_rew) o_rew[r] = __uint_as_float(w.x);
-          if (o_done) o_done[r] = __uint_as_float(w.y);
-        }
-      }
-      if (!write_pads) continue;
-      // zero the pad columns so the GEMM K-loop can run over the padded width unchecked
-      for (int c = sa_cols + lane; c < ld_sa; c += 64) {
-        if (xs) xs[c] = 0.f;
-        if (xns) xns[c] = 0.f;
-      }
-      if (xno)
-        for (int c = L.O + lane; c < ld_o; c += 64) xno[c] = 0.f;
     }
   }
 }
@@ -1281,151 +1034,142 @@ __global__ __launch_bounds__(256) void k_replay_gather_obs_h8(const uint32_t* __
   }
 }
 
-// ---- host side of the fp16 rings: the entry points above hand over here once they have checked the descriptor ----
-static int replay_insert_f16(const PqlReplayDesc* ring, int64_t dst_start, int64_t m, const float* obs, int64_t ld_obs,
-                             const float* act, int64_t ld_act, const float* rew, int64_t ld_rew, const float* next_obs,
-                             int64_t ld_nobs, const float* done, int64_t ld_done, pqlk_stream_t stream) {
-  RecLayoutH L = rec_layout_h(ring->obs_dim, ring->act_dim);
-  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
-  PQLK_REQUIRE(dst_start >= 0 && dst_start + m <= ring->capacity, PQLK_E_RANGE);
-  if (L.A >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
-  PQLK_REQUIRE(ld_obs >= L.O, PQLK_E_SHAPE);
-  if (m == 0) return PQLK_OK;
-  int64_t blocks = (m + 3) / 4;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_replay_insert_f16, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream),
-                     reinterpret_cast<uint32_t*>(ring->records), L, dst_start, m, obs, ld_obs, act, ld_act, rew, ld_rew, next_obs,
-                     ld_nobs, done, ld_done);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
-}
+// ---- host side of the fused gather: one dispatch for both formats (tests/gather_cases.py gather_launch is its mirror) ----
+// KERNEL<mean != nullptr, R> of a tuned kernel family on grid g.  R is 1, 2, 4 or, in the fast families, RMAX = 8; the obs families have
+// no <., 8> (RMAX = 4: their last rung repeats <., 4> and is never taken).
+#define PQLK_GATHER_TUNED_N(KERNEL, NORM, RMAX, ...)                                                                   \
+  do {                                                                                                                 \
+    if (R == 1) hipLaunchKernelGGL((KERNEL<NORM, 1>), g, dim3(256), 0, st, __VA_ARGS__);                               \
+    else if (R == 2) hipLaunchKernelGGL((KERNEL<NORM, 2>), g, dim3(256), 0, st, __VA_ARGS__);                          \
+    else if (R == 4) hipLaunchKernelGGL((KERNEL<NORM, 4>), g, dim3(256), 0, st, __VA_ARGS__);                          \
+    else hipLaunchKernelGGL((KERNEL<NORM, RMAX>), g, dim3(256), 0, st, __VA_ARGS__);                                   \
+  } while (0)
+#define PQLK_GATHER_TUNED(KERNEL, RMAX, ...)                                    \
+  do {                                                                          \
+    if (mean) PQLK_GATHER_TUNED_N(KERNEL, true, RMAX, __VA_ARGS__);             \
+    else PQLK_GATHER_TUNED_N(KERNEL, false, RMAX, __VA_ARGS__);                 \
+  } while (0)
+// k_replay_gather_fused<F, mean != nullptr, R, CH> on `blocks` blocks
+#define PQLK_GATHER_GENERIC(R, CH)                                                                                     \
+  do {                                                                                                                 \
+    if (mean) hipLaunchKernelGGL((k_replay_gather_fused<F, true, R, CH>), dim3((unsigned)blocks), dim3(256), 0, st,    \
+                                 records, L, ring->capacity, idx, b, mean, var, eps, clamp5, x_sa, ld_sa, xn_sa, xn_obs, \
+                                 ld_o, rew, done, write_pads);                                                         \
+    else hipLaunchKernelGGL((k_replay_gather_fused<F, false, R, CH>), dim3((unsigned)blocks), dim3(256), 0, st,        \
+                            records, L, ring->capacity, idx, b, mean, var, eps, clamp5, x_sa, ld_sa, xn_sa, xn_obs,    \
+                            ld_o, rew, done, write_pads);                                                              \
+  } while (0)
 
-static int replay_gather_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, float* obs, float* act, float* rew,
-                             float* next_obs, float* done, pqlk_stream_t stream) {
-  RecLayoutH L = rec_layout_h(ring->obs_dim, ring->act_dim);
-  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
-  if (L.A >= 0) PQLK_REQUIRE(act && rew && next_obs && done, PQLK_E_NULL);
-  if (b == 0) return PQLK_OK;
-  int64_t blocks = (b + 3) / 4;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(k_replay_gather_f16, dim3((unsigned)blocks), dim3(256), 0, pqlk_s(stream),
-                     reinterpret_cast<const uint32_t*>(ring->records), L, ring->capacity, idx, b, obs, act, rew, next_obs, done);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
-}
-
-// The launch shapes (rows in flight, waves per CU, the two-waves-per-row split, the 192-MB non-temporal threshold) are those of the
-// fp32 path applied to the fp16 record: nchunk and the bytes read come from RecLayoutH, so e.g. cfg #4 (O = 211: 1792 -> 1024 B)
-// moves from the two-waves-per-row shape to one 16-B chunk per lane.  Records with at most 512 B in use (cfg #2, every obs-only ring
-// up to O = 256) go to the 8-B-chunk kernels (`narrow`), the rest to the 16-B-chunk ones: the choice follows from the record alone.
-static int replay_gather_fused_f16(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, const float* mean, const float* var,
-                                   float eps, int flags, float* x_sa, int64_t ld_sa, float* xn_sa, float* xn_obs, int64_t ld_o,
-                                   float* rew, float* done, pqlk_stream_t stream) {
+template <class F>
+static int replay_gather_fused(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, const float* mean, const float* var,
+                               float eps, int flags, float* x_sa, int64_t ld_sa, float* xn_sa, float* xn_obs, int64_t ld_o,
+                               float* rew, float* done, pqlk_stream_t stream) {
+  constexpr bool HALF = F::HALF;
   const int clamp5 = flags & PQLK_GATHER_CLAMP5;
   const int write_pads = (flags & PQLK_GATHER_PADS_ZERO) ? 0 : 1;
   const int tune_R = (flags >> 8) & 15, tune_wpc = (flags >> 12) & 63;
   int nt_loads = ((flags & PQLK_GATHER_NT_LOADS) ? 1 : 0) | ((flags & PQLK_GATHER_NT_STORES) ? 2 : 0);
-  RecLayoutH L = rec_layout_h(ring->obs_dim, ring->act_dim);
-  PQLK_REQUIRE(ring->rec_ld == L.ld, PQLK_E_SHAPE);
-  PQLK_REQUIRE((mean == nullptr) == (var == nullptr), PQLK_E_NULL);
-  if (mean) PQLK_REQUIRE(L.O <= GATHER_MAX_OBS, PQLK_E_UNSUPPORTED);
-  if (x_sa || xn_sa) PQLK_REQUIRE(ld_sa % 32 == 0 && ld_sa >= L.O + (L.A < 0 ? 0 : L.A), PQLK_E_ALIGN);
-  if (xn_obs) PQLK_REQUIRE(ld_o % 32 == 0 && ld_o >= L.O, PQLK_E_ALIGN);
-  if (L.A < 0) PQLK_REQUIRE(xn_sa == nullptr, PQLK_E_UNSUPPORTED);
-  if (b == 0) return PQLK_OK;
+  const typename F::Layout L = F::layout(ring->obs_dim, ring->act_dim);
   const int nchunk = L.used >> 2;
   PQLK_REQUIRE(nchunk <= 1024, PQLK_E_UNSUPPORTED);
-  const uint32_t* records = reinterpret_cast<const uint32_t*>(ring->records);
+  const typename F::word* records = reinterpret_cast<const typename F::word*>(ring->records);
   const hipStream_t st = pqlk_s(stream);
+  // The launch shapes below (rows in flight, waves per CU, the two-waves-per-row split, the 192-MB non-temporal threshold) were
+  // measured on fp32 rings and are applied to the fp16 record as they are: nchunk and the bytes read come from the layout, so e.g.
+  // cfg #4 (O = 211: 1792 -> 1024 B) moves from the two-waves-per-row shape to one 16-B chunk per lane.  fp16 records with at most
+  // 512 B in use (cfg #2, every obs-only ring up to O = 256) go to the 8-B-chunk kernels k_replay_gather_fast_h8 / _obs_h8
+  // (`narrow`), the rest to the 16-B-chunk ones: the choice follows from the record alone.
+  const bool narrow = HALF && (L.used >> 1) <= 64;
+  // aligned transition-ring shape -> lean kernel (pads: at most 64 16-B chunks in total, one lane each)
+  // (the pad-column bound only matters when this call has to zero the pads: one lane per pad chunk)
   const bool fast = L.A >= 0 && nchunk <= 128 && (!write_pads || ((ld_sa - L.O - L.A) <= 64 && (!xn_obs || (ld_o - L.O) <= 64))) &&
                     pqlk_aligned16(x_sa) && pqlk_aligned16(xn_sa) && pqlk_aligned16(xn_obs);
-  const bool narrow = (L.used >> 1) <= 64;   // at most 512 B in use: one 8-B chunk per lane (k_replay_gather_fast_h8 / _obs_h8)
   if (fast) {
+    // rows in flight per wave: 2 up to 16 Ki rows (more waves, shorter dependent idx -> row chain: 9.3 vs 10.5 us at 8192),
+    // 4 beyond (same time at 32 Ki rows, fewer blocks)
+    // 2 rows in flight per wave, at most 12 (rounds 1-2: 24) resident waves per CU: beyond that the grid-stride loop takes
+    // further trips.  Measured at cfg 5 (32768 rows x 1 KiB, pads not re-zeroed; tools/bench_gather.py): 24 waves/CU x 2 rows
+    // 18.5 us, 16 x 2 19.5, 12 x 2 21.4, 32 x 2 22.3, 16 x 4 20.3, 32 x 4 (one trip per wave, the round-1 shape) 23.0, 8 rows
+    // in flight 30; at cfg 2 (8192 rows, one trip whatever the cap) 2 rows per wave 7.1 us vs 8.1 (4) and 9.0 (1).
+    // Non-temporal record loads: no gain (18.9 vs 18.5).  Requesting trip k+1's records before trip k is normalised and stored
+    // (software pipeline): WORSE, 21.5 us -- on gfx9 stores share the in-order vmcnt queue with loads, so the wait for the
+    // prefetched records also waits for the previous trip's store acknowledgements.  With the ring small enough to sit in the
+    // Infinity Cache (51 MB) the same launch takes 14.9 us: the 5-GB ring's random 1-KiB reads cost ~4 us on top of that, and
+    // ring size hardly matters beyond the cache (0.25 GB 18.0 us, 5 GB 19.3, 20 GB 20.1: not a TLB effect).  A loader / consumer
+    // split (one wave per workgroup issuing LDS-DMA record loads into a 16-slot LDS ring behind a counted vmcnt, three waves
+    // normalising and storing out of the ring, so that no wave ever mixes loads and stores) was built and measured too:
+    // 20.2 us at best -- no better than this kernel, i.e. the limit is the memory system's rate for this mix (about 4 TB/s of
+    // bytes moved), not the way one wave's loads and stores queue.
+    // Round 3 (the K-batch launches: 65 536 rows at cfg 2, five or more trips per wave): with the sample indices loaded one trip
+    // ahead, as SCALAR loads (k_replay_gather_fast), the optimum moved to 12 waves per CU -- 25.1 us at cfg 2 x 8 against 26.5
+    // at 24 and 31.5 at 8 (before: 35.3 at 12, 27.0 at 24); cfg 4 x 8 54.9-57.0 at 12-32; cfg 5 x 8 flat, 145-148 us at 8-32.
     int R = 2;
     if (tune_R == 1 || tune_R == 2 || tune_R == 4 || tune_R == 8) R = tune_R;
-    const int halves = nchunk > 64 ? 2 : 1;
+    const int halves = nchunk > 64 ? 2 : 1;   // 1-2 KiB records: two waves per row
     const int rows_blk = 4 / halves * R;
     int64_t fb = (b + rows_blk - 1) / rows_blk;
     const int wpc = tune_wpc ? tune_wpc : 12;
     if (fb > 256 * (int64_t)wpc / 4) fb = 256 * (int64_t)wpc / 4;
-    if (!tune_R && !tune_wpc && b * (int64_t)L.ld * 4 > ((int64_t)192 << 20)) nt_loads |= 1;   // bytes actually read
-    const dim3 g((unsigned)fb), t(256);
-    if (narrow) {
-#define PQLK_GATHER_FAST_H8(NORM, RR) \
-      hipLaunchKernelGGL((k_replay_gather_fast_h8<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
-                         x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads, nt_loads)
-#define PQLK_GATHER_FAST_H8_R(NORM) \
-      do { if (R == 1) PQLK_GATHER_FAST_H8(NORM, 1); else if (R == 2) PQLK_GATHER_FAST_H8(NORM, 2); else if (R == 4) PQLK_GATHER_FAST_H8(NORM, 4); \
-           else PQLK_GATHER_FAST_H8(NORM, 8); } while (0)
-      if (mean) PQLK_GATHER_FAST_H8_R(true); else PQLK_GATHER_FAST_H8_R(false);
-#undef PQLK_GATHER_FAST_H8_R
-#undef PQLK_GATHER_FAST_H8
-      PQLK_LAUNCH_CHECK();
-      return PQLK_OK;
-    }
-#define PQLK_GATHER_FAST_H(NORM, RR) \
-    hipLaunchKernelGGL((k_replay_gather_fast_f16<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
-                       x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads, nt_loads, halves)
-#define PQLK_GATHER_FAST_H_R(NORM) \
-    do { if (R == 1) PQLK_GATHER_FAST_H(NORM, 1); else if (R == 2) PQLK_GATHER_FAST_H(NORM, 2); else if (R == 4) PQLK_GATHER_FAST_H(NORM, 4); \
-         else PQLK_GATHER_FAST_H(NORM, 8); } while (0)
-    if (mean) PQLK_GATHER_FAST_H_R(true); else PQLK_GATHER_FAST_H_R(false);
-#undef PQLK_GATHER_FAST_H_R
-#undef PQLK_GATHER_FAST_H
-    PQLK_LAUNCH_CHECK();
-    return PQLK_OK;
-  }
-  if (L.A < 0 && nchunk <= 64 && pqlk_aligned16(x_sa) && pqlk_aligned16(xn_obs) && (x_sa || xn_obs)) {
+    // Launches whose record reads alone exceed what the 256-MB Infinity Cache can hold beside the output tiles (cfg #5 x 8: 262 144
+    // rows x 1 KiB) take the records with non-temporal loads: they are read once and would only push the tiles out.  Round 4,
+    // tools/bench_gather.py cfg5x8: 150 -> 98 us back to back, 129 -> 123 us one launch at a time; cfg #2 x 8 (59 MB of records):
+    // no difference either way, left alone.  (L.ld: the bytes actually read, in either format.)
+    if (!tune_R && !tune_wpc && b * (int64_t)L.ld * 4 > ((int64_t)192 << 20)) nt_loads |= 1;
+    const dim3 g((unsigned)fb);
+#define PQLK_FAST_ARGS records, L, ring->capacity, idx, b, mean, var, eps, clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads, nt_loads
+    if constexpr (!HALF) PQLK_GATHER_TUNED(k_replay_gather_fast, 8, PQLK_FAST_ARGS, halves);
+    else if (narrow) PQLK_GATHER_TUNED(k_replay_gather_fast_h8, 8, PQLK_FAST_ARGS);   // (<= 64 8-B chunks: never two waves per row)
+    else PQLK_GATHER_TUNED(k_replay_gather_fast_f16, 8, PQLK_FAST_ARGS, halves);
+#undef PQLK_FAST_ARGS
+  } else if (L.A < 0 && nchunk <= 64 && pqlk_aligned16(x_sa) && pqlk_aligned16(xn_obs) && (x_sa || xn_obs)) {
+    // obs-only ring whose record fits one 16-B chunk per lane (O <= 256; fp16: O <= 512): several records per wave instruction
     const int nlane = narrow ? (L.used >> 1) : nchunk;   // lanes a record takes: 8-B chunks when they fit a wave, else 16-B chunks
     int lgp = 0;
     while ((1 << lgp) < nlane) ++lgp;
     const int G = 64 >> lgp;
+    // rows in flight per wave: R x G, R chosen so that the launch still has ~16 waves per CU to issue from (32 768 rows of
+    // cfg #2, G = 2: R = 4, 4096 waves, one trip); waves per CU capped at 16 (grid-stride trips beyond)
     const int64_t groups = (b + G - 1) / G;
     int R = groups >= 4 * 4096 ? 4 : (groups >= 2 * 4096 ? 2 : 1);
     if (tune_R == 1 || tune_R == 2 || tune_R == 4) R = tune_R;
     const int wpc = tune_wpc ? tune_wpc : 16;
     int64_t fb = (groups + 4 * R - 1) / (4 * R);
     if (fb > 256 * (int64_t)wpc / 4) fb = 256 * (int64_t)wpc / 4;
-    const dim3 g((unsigned)fb), t(256);
-    if (narrow) {
-#define PQLK_GATHER_OBS_H8(NORM, RR) \
-      hipLaunchKernelGGL((k_replay_gather_obs_h8<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
-                         x_sa, ld_sa, xn_obs, ld_o, write_pads, lgp)
-#define PQLK_GATHER_OBS_H8_R(NORM) \
-      do { if (R == 1) PQLK_GATHER_OBS_H8(NORM, 1); else if (R == 2) PQLK_GATHER_OBS_H8(NORM, 2); else PQLK_GATHER_OBS_H8(NORM, 4); } while (0)
-      if (mean) PQLK_GATHER_OBS_H8_R(true); else PQLK_GATHER_OBS_H8_R(false);
-#undef PQLK_GATHER_OBS_H8_R
-#undef PQLK_GATHER_OBS_H8
-      PQLK_LAUNCH_CHECK();
-      return PQLK_OK;
-    }
-#define PQLK_GATHER_OBS_H(NORM, RR) \
-    hipLaunchKernelGGL((k_replay_gather_obs_f16<NORM, RR>), g, t, 0, st, records, L, ring->capacity, idx, b, mean, var, eps, clamp5, \
-                       x_sa, ld_sa, xn_obs, ld_o, write_pads, lgp)
-#define PQLK_GATHER_OBS_H_R(NORM) \
-    do { if (R == 1) PQLK_GATHER_OBS_H(NORM, 1); else if (R == 2) PQLK_GATHER_OBS_H(NORM, 2); else PQLK_GATHER_OBS_H(NORM, 4); } while (0)
-    if (mean) PQLK_GATHER_OBS_H_R(true); else PQLK_GATHER_OBS_H_R(false);
-#undef PQLK_GATHER_OBS_H_R
-#undef PQLK_GATHER_OBS_H
-    PQLK_LAUNCH_CHECK();
-    return PQLK_OK;
+    const dim3 g((unsigned)fb);
+#define PQLK_OBS_ARGS records, L, ring->capacity, idx, b, mean, var, eps, clamp5, x_sa, ld_sa, xn_obs, ld_o, write_pads, lgp
+    if constexpr (!HALF) PQLK_GATHER_TUNED(k_replay_gather_obs, 4, PQLK_OBS_ARGS);
+    else if (narrow) PQLK_GATHER_TUNED(k_replay_gather_obs_h8, 4, PQLK_OBS_ARGS);
+    else PQLK_GATHER_TUNED(k_replay_gather_obs_f16, 4, PQLK_OBS_ARGS);
+#undef PQLK_OBS_ARGS
+  } else {
+    const int rows_per_wave = nchunk <= 64 ? 4 : (nchunk <= 128 ? 2 : 1);
+    int64_t blocks = (b + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
+    if (blocks > 2048) blocks = 2048;
+    if (nchunk <= 64) PQLK_GATHER_GENERIC(4, 1);
+    else if (nchunk <= 128) PQLK_GATHER_GENERIC(2, 2);
+    else if (nchunk <= 256) PQLK_GATHER_GENERIC(1, 4);
+    else PQLK_GATHER_GENERIC(1, 16);
   }
-  const int rows_per_wave = nchunk <= 64 ? 4 : (nchunk <= 128 ? 2 : 1);
-  int64_t blocks = (b + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
-  if (blocks > 2048) blocks = 2048;
-#define PQLK_GF_H(NORM, R, CH)                                                                                                  \
-  hipLaunchKernelGGL((k_replay_gather_fused_f16<NORM, R, CH>), dim3((unsigned)blocks), dim3(256), 0, st, records, L, ring->capacity, \
-                     idx, b, mean, var, eps, clamp5, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, write_pads)
-#define PQLK_GF_H_N(NORM)                                     \
-  do {                                                        \
-    if (nchunk <= 64) PQLK_GF_H(NORM, 4, 1);                  \
-    else if (nchunk <= 128) PQLK_GF_H(NORM, 2, 2);            \
-    else if (nchunk <= 256) PQLK_GF_H(NORM, 1, 4);            \
-    else PQLK_GF_H(NORM, 1, 16);                              \
-  } while (0)
-  if (mean) PQLK_GF_H_N(true); else PQLK_GF_H_N(false);
-#undef PQLK_GF_H_N
-#undef PQLK_GF_H
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
+}
+#undef PQLK_GATHER_GENERIC
+#undef PQLK_GATHER_TUNED
+#undef PQLK_GATHER_TUNED_N
+
+extern "C" int pqlk_replay_gather_fused(const PqlReplayDesc* ring, const int64_t* idx, int64_t b, const float* mean,
+                                        const float* var, float eps, int flags, float* x_sa, int64_t ld_sa,
+                                        float* xn_sa, float* xn_obs, int64_t ld_o, float* rew, float* done,
+                                        pqlk_stream_t stream) {
+  if (const int rc = ring_ok(ring, idx != nullptr, b)) return rc;
+  const int O = ring->obs_dim, A = ring->act_dim;
+  PQLK_REQUIRE((mean == nullptr) == (var == nullptr), PQLK_E_NULL);
+  if (mean) PQLK_REQUIRE(O <= GATHER_MAX_OBS, PQLK_E_UNSUPPORTED);
+  if (x_sa || xn_sa) PQLK_REQUIRE(ld_sa % 32 == 0 && ld_sa >= O + (A < 0 ? 0 : A), PQLK_E_ALIGN);
+  if (xn_obs) PQLK_REQUIRE(ld_o % 32 == 0 && ld_o >= O, PQLK_E_ALIGN);
+  if (A < 0) PQLK_REQUIRE(xn_sa == nullptr, PQLK_E_UNSUPPORTED);
+  if (b == 0) return PQLK_OK;   // (before the cap of 1024 chunks, which replay_gather_fused checks: an empty call is no gather)
+  return ring->obs_dtype == PQLK_OBS_F16
+             ? replay_gather_fused<RecF16>(ring, idx, b, mean, var, eps, flags, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, stream)
+             : replay_gather_fused<RecF32>(ring, idx, b, mean, var, eps, flags, x_sa, ld_sa, xn_sa, xn_obs, ld_o, rew, done, stream);
 }

@@ -241,6 +241,92 @@ def test_host_refusals_of_the_fused_gather():
         assert call(O, A, dtype, b=0, mean=None, var=None) == 0
 
 
+def test_host_refusals_of_insert_and_plain_gather():
+    """pqlk_replay_insert and pqlk_replay_gather check in one order whatever the storage format: null, shape, dtype, rec_ld,
+    range / required pointers, and only then the empty call.  The last column is an unknown dtype code: what is checked before
+    the dtype answers as for a known one, everything after it is PQLK_E_SHAPE."""
+    from pql_amd import _lib as L
+    P = C.c_void_p(0x1000)          # never dereferenced: every call below is refused, or is empty, before a launch
+    OK, E_SHAPE, E_RANGE, UNKNOWN = 0, 2, 3, 2
+    O, A = 8, 2
+
+    def ring(dtype, A=A, records=0x1000, cap=100, O=O, off=0):
+        rec_ld = gc.layout(max(O, 1), A, dtype if dtype in (F32, F16) else F32).ld + off
+        return L.PqlReplayDesc(records, cap, O, A, rec_ld, dtype)
+
+    def insert(r, dst=0, m=4, obs=P, ld_obs=O, act=P, rew=P, nobs=P, done=P):
+        return L.lib.pqlk_replay_insert(None if r is None else C.byref(r), dst, m, obs, ld_obs, act, A, rew, 1, nobs, O, done, 1, None)
+
+    def gather(r, idx=P, b=4, obs=P, act=P, rew=P, nobs=P, done=P):
+        return L.lib.pqlk_replay_gather(None if r is None else C.byref(r), idx, b, obs, act, rew, nobs, done, None)
+
+    # (what, call(dtype), code for fp32 and fp16 rings, code for the unknown dtype)
+    rows = [
+        ("insert: null ring", lambda d: insert(None), E_NULL, E_NULL),
+        ("insert: null records", lambda d: insert(ring(d, records=0)), E_NULL, E_NULL),
+        ("insert: null obs", lambda d: insert(ring(d), obs=None), E_NULL, E_NULL),
+        ("insert: null obs before a bad shape", lambda d: insert(ring(d, O=0), obs=None), E_NULL, E_NULL),
+        ("insert: obs_dim 0", lambda d: insert(ring(d, O=0)), E_SHAPE, E_SHAPE),
+        ("insert: obs_dim -3", lambda d: insert(ring(d, O=-3)), E_SHAPE, E_SHAPE),
+        ("insert: capacity 0", lambda d: insert(ring(d, cap=0)), E_SHAPE, E_SHAPE),
+        ("insert: capacity -1", lambda d: insert(ring(d, cap=-1)), E_SHAPE, E_SHAPE),
+        ("insert: m -1", lambda d: insert(ring(d), m=-1), E_SHAPE, E_SHAPE),
+        ("insert: rec_ld + 32", lambda d: insert(ring(d, off=32)), E_SHAPE, E_SHAPE),
+        ("insert: rec_ld - 32", lambda d: insert(ring(d, off=-32)), E_SHAPE, E_SHAPE),
+        ("insert: wrong rec_ld before the range", lambda d: insert(ring(d, off=32), dst=98), E_SHAPE, E_SHAPE),
+        ("insert: rows 98..101 of 100", lambda d: insert(ring(d), dst=98), E_RANGE, E_SHAPE),
+        ("insert: row 100 of 100, m 1", lambda d: insert(ring(d), dst=100, m=1), E_RANGE, E_SHAPE),
+        ("insert: dst_start -1", lambda d: insert(ring(d), dst=-1), E_RANGE, E_SHAPE),
+        ("insert: dst_start -1 of an empty call", lambda d: insert(ring(d), dst=-1, m=0), E_RANGE, E_SHAPE),
+        ("insert: range before a missing pointer", lambda d: insert(ring(d), dst=98, act=None), E_RANGE, E_SHAPE),
+        ("insert: no act", lambda d: insert(ring(d), act=None), E_NULL, E_SHAPE),
+        ("insert: no rew", lambda d: insert(ring(d), rew=None), E_NULL, E_SHAPE),
+        ("insert: no next_obs", lambda d: insert(ring(d), nobs=None), E_NULL, E_SHAPE),
+        ("insert: no done", lambda d: insert(ring(d), done=None), E_NULL, E_SHAPE),
+        ("insert: no done of an empty call", lambda d: insert(ring(d), m=0, done=None), E_NULL, E_SHAPE),
+        ("insert: missing pointer before ld_obs", lambda d: insert(ring(d), act=None, ld_obs=O - 1), E_NULL, E_SHAPE),
+        ("insert: ld_obs < O", lambda d: insert(ring(d), ld_obs=O - 1), E_SHAPE, E_SHAPE),
+        ("insert: ld_obs < O of an empty call", lambda d: insert(ring(d), m=0, ld_obs=O - 1), E_SHAPE, E_SHAPE),
+        ("insert: ld_obs < O, obs-only", lambda d: insert(ring(d, A=-1), ld_obs=O - 1, act=None, rew=None, nobs=None, done=None), E_SHAPE, E_SHAPE),
+        ("insert: empty call", lambda d: insert(ring(d), m=0), OK, E_SHAPE),
+        ("insert: empty call at the end of the ring", lambda d: insert(ring(d), dst=100, m=0), OK, E_SHAPE),
+        ("insert: empty call, obs-only, obs alone", lambda d: insert(ring(d, A=-1), m=0, act=None, rew=None, nobs=None, done=None), OK, E_SHAPE),
+        ("gather: null ring", lambda d: gather(None), E_NULL, E_NULL),
+        ("gather: null records", lambda d: gather(ring(d, records=0)), E_NULL, E_NULL),
+        ("gather: null idx", lambda d: gather(ring(d), idx=None), E_NULL, E_NULL),
+        ("gather: null obs", lambda d: gather(ring(d), obs=None), E_NULL, E_NULL),
+        ("gather: null idx before a bad shape", lambda d: gather(ring(d, cap=0), idx=None), E_NULL, E_NULL),
+        ("gather: obs_dim 0", lambda d: gather(ring(d, O=0)), E_SHAPE, E_SHAPE),
+        ("gather: capacity 0", lambda d: gather(ring(d, cap=0)), E_SHAPE, E_SHAPE),
+        ("gather: b -1", lambda d: gather(ring(d), b=-1), E_SHAPE, E_SHAPE),
+        ("gather: rec_ld + 32", lambda d: gather(ring(d, off=32)), E_SHAPE, E_SHAPE),
+        ("gather: wrong rec_ld before a missing pointer", lambda d: gather(ring(d, off=32), act=None), E_SHAPE, E_SHAPE),
+        ("gather: no act", lambda d: gather(ring(d), act=None), E_NULL, E_SHAPE),
+        ("gather: no rew", lambda d: gather(ring(d), rew=None), E_NULL, E_SHAPE),
+        ("gather: no next_obs", lambda d: gather(ring(d), nobs=None), E_NULL, E_SHAPE),
+        ("gather: no done", lambda d: gather(ring(d), done=None), E_NULL, E_SHAPE),
+        ("gather: no done of an empty call", lambda d: gather(ring(d), b=0, done=None), E_NULL, E_SHAPE),
+        ("gather: empty call", lambda d: gather(ring(d), b=0), OK, E_SHAPE),
+        ("gather: empty call, obs-only, obs alone", lambda d: gather(ring(d, A=-1), b=0, act=None, rew=None, nobs=None, done=None), OK, E_SHAPE),
+    ]
+    for what, call, known, unknown in rows:
+        for dtype, want in ((F32, known), (F16, known), (UNKNOWN, unknown)):
+            assert call(dtype) == want, (what, dtype)
+    assert insert(ring(UNKNOWN)) == E_SHAPE and gather(ring(UNKNOWN)) == E_SHAPE     # nothing wrong but the dtype
+
+    # the fused gather asks the same of the descriptor, in the same order, before its own checks
+    def fused(r, idx=P, b=4, x_sa=P):
+        return L.lib.pqlk_replay_gather_fused(None if r is None else C.byref(r), idx, b, None, None, gc.EPS, 0, x_sa, 32, None, None, 32, None, None, None)
+
+    for dtype in (F32, F16, UNKNOWN):
+        after = (lambda code: E_SHAPE if dtype == UNKNOWN else code)    # noqa: E731
+        assert fused(None) == E_NULL and fused(ring(dtype, records=0)) == E_NULL and fused(ring(dtype), idx=None) == E_NULL
+        assert fused(ring(dtype, O=0)) == E_SHAPE and fused(ring(dtype, cap=0)) == E_SHAPE and fused(ring(dtype), b=-1) == E_SHAPE
+        assert fused(ring(dtype, off=32)) == E_SHAPE and fused(ring(dtype, off=32), b=0) == E_SHAPE
+        assert fused(ring(dtype), b=0) == after(OK) and fused(ring(dtype), b=0, x_sa=None) == after(OK)
+    assert fused(ring(UNKNOWN)) == E_SHAPE
+
+
 # --------------------------------------------------------------------------- the checks fail on wrong outputs
 def _want(name="f32_5_3", b=37, flags=gc.CLAMP5):
     c = gc.CASE_BY_NAME[name]

@@ -9,10 +9,13 @@ GPU only.
 --obs-dtype float32|float16: storage format of the ring's observations (algo.replay_obs_dtype); the `auto` line of every shape is
 also printed as one JSON line.
 A name may carry a ring size, `cfg5x8@150M` (rows; the 1-KiB records of cfg #5 x 150 M = 154 GB): the same launch over a ring that
-takes most of the card.  --auto: only the learner's own flag word (no sweep)."""
+takes most of the card.  --auto: only the learner's own flag word (no sweep).
+    python tools/bench_gather.py cold
+the kernels the shapes above never reach (insert, plain gather, the generic fused gather), both formats, one JSON line: see cold()."""
 import ctypes as C
 import json
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,6 +34,75 @@ CFG = {"cfg2": (88, 16, 8192, 1_000_000), "cfg5": (108, 21, 32768, 5_000_000), "
        # "...s": the obs ring gathered into ONE destination (the actor's input tile: what the P-learner does since round 4)
        "p2s": (88, -1, 8192, 1_000_000), "p2x4s": (88, -1, 4 * 8192, 1_000_000)}
 SETS, N_ISO = 4, 16
+
+
+def graph_us(launch, iters, repeats=1):
+    """[us per launch] of `repeats` replays of one hipGraph of `iters` launches, launch(2 + i) each, HIP events around a replay;
+    launch(0) and one replay run first, untimed"""
+    launch(0)
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.graph(g, stream=side):
+        for i in range(iters):
+            launch(2 + i)
+    g.replay()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); g.replay(); e1.record(); e1.synchronize()
+        out.append(e0.elapsed_time(e1) / iters * 1e3)
+    return out
+
+
+def cold(iters=30, repeats=9):
+    """The kernels nothing else here times -- insert, plain gather and the generic fused gather -- at sizes the project runs, both
+    storage formats, as one JSON line: per point the median of `repeats` back-to-back timings and the timings themselves.  For A/B
+    runs of two builds (`PQLK_LIB`), a fresh process per run: the caller alternates the libraries and compares medians of medians."""
+    dev = torch.device("cuda:0")
+    f = dict(dtype=torch.float32, device=dev)
+    points = {}
+
+    def point(name, launch):
+        us = graph_us(launch, iters, repeats)
+        points[name] = {"median_us": round(statistics.median(us), 3), "us": [round(u, 3) for u in us]}
+
+    def fused_point(name, ring, B, extra):
+        """every destination, statistics + clamp, pads written, tiles `extra` columns wider than pqlk_ld"""
+        O, A = ring.O, ring.A
+        ld_sa, ld_o = L.ld(O + A) + extra, L.ld(O) + extra
+        x_sa, xn_sa, xn_obs = torch.zeros((B, ld_sa), **f), torch.zeros((B, ld_sa), **f), torch.zeros((B, ld_o), **f)
+        rew, done = torch.zeros(B, **f), torch.zeros(B, **f)
+        mean, var = torch.randn(O, device=dev) * 0.1, torch.rand(O, device=dev) + 0.5
+        idx = torch.randint(ring.capacity, (iters + 2, B), device=dev)
+        point(name, lambda i: L.check(L.lib.pqlk_replay_gather_fused(
+            C.byref(ring.desc), L.ptr(idx[i]), B, L.ptr(mean), L.ptr(var), 1e-4, 1, L.ptr(x_sa), ld_sa, L.ptr(xn_sa), L.ptr(xn_obs), ld_o,
+            L.ptr(rew), L.ptr(done), L.stream(dev))))
+
+    for dt in ("float32", "float16"):
+        # cfg #2 records (88, 16): one rollout hand-off of the default benchmark (4096 envs x horizon 1), one batch of 8192
+        O, A, B, M, cap = 88, 16, 8192, 4096, 1_000_000
+        ring = ReplayBuffer(cap, (O,), A, dev, obs_dtype=dt).ring
+        (ring.records.view(torch.float16) if ring.half else ring.records).normal_()
+        src = [torch.randn((M, w), **f) for w in (O, A, 1, O, 1)]       # obs, act, rew, next_obs, done
+        point(f"insert_{dt}", lambda i: L.check(L.lib.pqlk_replay_insert(
+            C.byref(ring.desc), i * M, M, L.ptr(src[0]), O, L.ptr(src[1]), A, L.ptr(src[2]), 1, L.ptr(src[3]), O, L.ptr(src[4]), 1,
+            L.stream(dev))))
+        idx = torch.randint(cap, (iters + 2, B), device=dev)
+        outs = [torch.empty((B, w), **f) for w in (O, A, 1, O, 1)]      # obs, act, rew, next_obs, done
+        point(f"gather_{dt}", lambda i: L.check(L.lib.pqlk_replay_gather(C.byref(ring.desc), L.ptr(idx[i]), B, *[L.ptr(t) for t in outs],
+                                                                          L.stream(dev))))
+        fused_point(f"fused_88_16_wide96_{dt}", ring, B, 96)            # beyond the lean kernel's pad bound: <4, 1>
+        del ring, idx
+        torch.cuda.empty_cache()
+        big = ReplayBuffer(200_000, (600,), 7, dev, obs_dtype=dt).ring  # 303 chunks (fp32: <1, 16>), 153 (fp16: <1, 4>)
+        (big.records.view(torch.float16) if big.half else big.records).normal_()
+        fused_point(f"fused_600_7_{dt}", big, B, 0)
+        del big
+        torch.cuda.empty_cache()
+    print(json.dumps({"mode": "cold", "lib": str(L.LIB_FILE), "iters": iters, "repeats": repeats,
+                      "points": points}), flush=True)
 
 
 def run(name, quick=False, iters=30, auto=False, obs_dtype="float32"):
@@ -73,18 +145,7 @@ def run(name, quick=False, iters=30, auto=False, obs_dtype="float32"):
                                                L.ptr(t["x_obs"]), ld_o, L.ptr(t["rew"]), L.ptr(t["done"]), L.stream(dev)))
 
     def b2b(norm=True, flags=1):
-        one(0, 0, norm, flags)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.graph(g, stream=side):
-            for i in range(iters):
-                one(2 + i, 0, norm, flags)
-        g.replay()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); g.replay(); e1.record(); e1.synchronize()
-        return e0.elapsed_time(e1) / iters * 1e3
+        return graph_us(lambda i: one(i, 0, norm, flags), iters)[0]
 
     def iso(norm=True, flags=1):
         return isolated_launch_ms(lambda i, s: one(i, s, norm, flags), dev, N_ISO, SETS) * 1e3
@@ -120,6 +181,9 @@ if __name__ == "__main__":
         dtype = argv[i + 1]
         del argv[i: i + 2]
     args = [a for a in argv if not a.startswith("--")]
+    if args == ["cold"]:
+        cold()
+        sys.exit(0)
     for n in (args or ["cfg2", "cfg5"]):
         run(n, quick="--quick" in argv, auto="--auto" in argv, obs_dtype=dtype)
         torch.cuda.empty_cache()

@@ -3,6 +3,8 @@
 
     python tools/kernel_resources.py [path/to/libpqlk.so]          # table, spilling kernels marked
     python tools/kernel_resources.py --check                        # exit 1 if any kernel spills or uses scratch
+    python tools/kernel_resources.py --same OTHER_LIB name...       # exit 1 unless the built library and OTHER_LIB hold the same
+                                                                    # instructions for every kernel whose name contains a `name`
 
 A kernel that spills keeps working and keeps passing every parity test; only its speed tells.  tests/test_host_cpu.py runs
 `resources()` over the built library so a spill cannot come back unnoticed (round 3: k_mlp_fwd_fused<1,4> grew to 59 spilled
@@ -55,12 +57,8 @@ def resources(lib=LIB):
     return out
 
 
-def full_drains(lib=LIB, want=()):
-    """-> {demangled kernel name: number of `s_waitcnt vmcnt(0)` instructions} for the kernels whose name contains one of `want`.
-    The gather kernels are latency-bound chains of loads and stores on gfx9's ONE in-order vector-memory counter: their speed hangs
-    on the compiler keeping counted waits.  Round 4: a wave-uniform branch added inside k_replay_gather_fast's per-record loop (and
-    later a template flag + selects in place of a branch) made the compiler drain the queue before every store -- 2 -> 14 full
-    drains, the same bits, 23 -> 28-30 us.  Parity tests cannot see that; this count can."""
+def kernel_code(lib=LIB, want=()):
+    """-> {demangled kernel name: its disassembly} for the kernels whose name contains one of `want`"""
     out = {}
     filt = shutil.which("c++filt")
     with tempfile.TemporaryDirectory() as td:
@@ -77,8 +75,32 @@ def full_drains(lib=LIB, want=()):
                     name = subprocess.run([filt, name], capture_output=True, text=True).stdout.strip() or name
                 name = re.sub(r"\(.*", "", name)
                 if any(w in name for w in want):
-                    out[name] = len(re.findall(r"s_waitcnt vmcnt\(0\)", m.group(2)))
+                    out[name] = m.group(2)
     return out
+
+
+def full_drains(lib=LIB, want=()):
+    """-> {demangled kernel name: number of `s_waitcnt vmcnt(0)` instructions} for the kernels whose name contains one of `want`.
+    The gather kernels are latency-bound chains of loads and stores on gfx9's ONE in-order vector-memory counter: their speed hangs
+    on the compiler keeping counted waits.  Round 4: a wave-uniform branch added inside k_replay_gather_fast's per-record loop (and
+    later a template flag + selects in place of a branch) made the compiler drain the queue before every store -- 2 -> 14 full
+    drains, the same bits, 23 -> 28-30 us.  Parity tests cannot see that; this count can."""
+    return {k: len(re.findall(r"s_waitcnt vmcnt\(0\)", v)) for k, v in kernel_code(lib, want).items()}
+
+
+def same_code(lib_a, lib_b, want):
+    """-> (identical, differing, missing): the kernels whose name contains one of `want`, by whether the two libraries hold the
+    same instructions for them -- the disassembly without its addresses and raw bytes (branch targets are relative: they stay)
+    and without the s_nop padding between a kernel's last s_endpgm and the next symbol.
+    The way to show that a change to a kernel's neighbours left a tuned kernel alone: its speed is then settled without a run."""
+    def text(code):   # "// address: raw bytes" stands behind every instruction
+        lines = [ln.strip() for ln in re.sub(r"//.*", "", code).split("\n") if ln.strip()]
+        while lines and (lines[-1].startswith("s_nop") or lines[-1] == "..."):   # ("...": the disassembler's run of zero bytes)
+            lines.pop()
+        return lines
+    a, b = ({k: text(v) for k, v in kernel_code(lib, want).items()} for lib in (lib_a, lib_b))
+    both = sorted(set(a) & set(b))
+    return [k for k in both if a[k] == b[k]], [k for k in both if a[k] != b[k]], sorted(set(a) ^ set(b))
 
 
 def spilling(res):
@@ -88,6 +110,17 @@ def spilling(res):
 
 
 def main(argv):
+    if argv[:1] == ["--same"]:
+        if len(argv) < 3:
+            print("usage: kernel_resources.py --same OTHER_LIB name...")
+            return 2
+        same, differ, missing = same_code(LIB, argv[1], argv[2:])
+        for k in differ:
+            print(f"DIFFERS  {k}")
+        for k in missing:
+            print(f"MISSING from one library  {k}")
+        print(f"{len(same)} kernels identical, {len(differ)} differ, {len(missing)} in one library only")
+        return 1 if (differ or missing or not same) else 0
     check = "--check" in argv
     args = [a for a in argv if not a.startswith("--")]
     res = resources(args[0] if args else LIB)
