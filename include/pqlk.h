@@ -147,7 +147,13 @@ int pqlk_replay_gather_fused(const PqlReplayDesc* ring, const int64_t* idx, int6
  * Emits, for every step s = count + t with s + 1 >= nstep, one row per env in TIME-MAJOR order
  * (row = (s - first_emit_step) * N + env; nstep_replay.py:65), to five contiguous outputs.
  * gamma_pow: nstep floats (host pointer), gamma^j computed in double, rounded to fp32 (:24).
- * Reward sum order is torch's row-sum order for n <= 5 (see oracle NStepRef._emit).
+ * Reward sum, for every nstep up to 16: terms (r_j * g_j) * keep_j, j = 0 the oldest step, keep_j = 0 behind the first done;
+ * four partial sums A_i over the j with j mod 4 == i, each in increasing j, then ((A0 + A1) + A2) + A3 (a lane without a term is
+ * left out).  That is torch's CPU row sum `.sum(1)` for nstep <= 5 only (and plain left to right for nstep <= 4); from
+ * nstep = 6 on it is this library's own order, stated in oracle NStepRef._emit and tests/rollout_cases.py.
+ * nstep = 1 copies the inputs through (the window is still written).  A call with t_steps <= nstep - 1 - count emits nothing:
+ * the outputs may then be NULL, the window is filled, *rows_out = 0.
+ * PQLK_E_UNSUPPORTED: nstep outside [1, 16].
  * Returns the number of emitted rows through *rows_out (host pointer, may be NULL). */
 int pqlk_nstep_push_emit(float* window, int64_t num_envs, int32_t nstep, int32_t obs_dim, int32_t act_dim,
                          int64_t count, int64_t t_steps,

@@ -976,8 +976,8 @@ def test_rollout_step_kernel_vs_reference_semantics(dev, N, O, A, win, H):
             dq_r.extend(ref_ret[done].tolist()); dq_l.extend(ref_len[done].tolist())
             ref_ret[done] = 0; ref_len[done] = 0
             assert np.array_equal(cur_ret.cpu().numpy(), ref_ret) and np.array_equal(cur_len.cpu().numpy(), ref_len)
-            assert sorted(win_ret[:win].cpu().tolist()) == sorted(np.float32(x) for x in dq_r)
-            assert sorted(win_len[:win].cpu().tolist()) == sorted(np.float32(x) for x in dq_l)
+            assert np.roll(win_ret[:win].cpu().numpy(), -int(ptr_r.item())).tolist() == [np.float32(x) for x in dq_r]   # slot (ptr + i) % win holds deque[i]
+            assert np.roll(win_len[:win].cpu().numpy(), -int(ptr_l.item())).tolist() == [np.float32(x) for x in dq_l]
             assert int(ptr_r.item()) == int(ptr_l.item()) < win
         for got, exp in zip(sl, want):
             assert np.array_equal(got.cpu().numpy(), exp)
