@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic, qr_drop, qr_huber_loss, td_mse_loss
+from pql_amd.algo.heads import CriticHead
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.prioritized_replay import per_beta, per_cfg  # noqa: F401  (per_beta: imported from here by its users)
@@ -33,6 +34,7 @@ class ActorCriticBase(PQLActor):
         self.replay_obs_dtype = cfg_obs_dtype(algo)   # algo.replay_obs_dtype: storage format of the replay ring built for this agent
         self.actor = make_actor(cfg, self.obs_dim, self.action_dim, self.device)   # actor first: both consume the CPU generator
         self.critic = make_critic(cfg, self.obs_dim, self.action_dim, self.device)
+        self.head = CriticHead(self.critic, algo)   # which loss entries the critic's output columns take
         if self.TARGET_CRITIC:
             self.critic_target = deepcopy(self.critic)
         # a Polyak-averaged copy of the actor, or (no_tgt_actor=True, every shipped config) the actor itself
@@ -144,10 +146,6 @@ class ActorCriticBase(PQLActor):
     def _one_layout(self):
         return hasattr(self.critic, "layout")
 
-    @property
-    def _quantile(self):
-        return getattr(self.critic, "head", "scalar") == "quantile"
-
     def _critic_forward(self, ws, net, x, slot):
         """Q of `net` (the critic or its target) on x (B, ld_sa) -> ((2, B, ld) output, ld).  slot: "c" (the stash `_critic_grads` /
         `_critic_dx` read) or "t" (the target's)."""
@@ -184,30 +182,20 @@ class ActorCriticBase(PQLActor):
             a = tanh_of[0]
             dx[0, :, :A] = g[:, O:O + A] * (1.0 - a[:, :A] * a[:, :A])
 
-    def _td_mse_loss(self, ws, q, qt, ld):
-        """Twin MSE against r + (1 - d) gamma^n min(qt): d loss / d q -> ws["dy"], the loss -> the critic's ring."""
+    def _td_mse_loss(self, ws, q, qt, ld, soft=None):
+        """The head's critic loss (`CriticHead.critic_loss`; scalar: twin MSE against the TD target): d loss / d q -> ws["dy"], the loss -> the critic's ring."""
         algo = self.cfg.algo
         memory = ws.get("per")
         # with prioritized replay: the importance weights on the loss and its gradient, then |TD| back into the tree
-        per = {} if memory is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
-        if self._quantile:   # twin quantile heads: the quantile Huber loss against the target net with the smaller mean
-            qr_huber_loss(q, qt, ld, self.critic.num_quantiles, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep),
-                          float(algo.get("huber_kappa", 1.0)), ws["B"], ws["dy"], self.closs, self.copt.step, ws["scratch"], self.device,
-                          drop=qr_drop(algo), **per)
-        else:
-            td_mse_loss(q, qt, ld, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep), ws["B"], ws["dy"], self.closs, self.copt.step,
-                        ws["scratch"], self.device, **per)
+        per = None if memory is None else (ws["w"], ws["wmax"], ws["abs_td"])
+        self.head.critic_loss(q, qt, ld, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep), ws["B"], ws["dy"], self.closs, self.copt.step,
+                              ws["scratch"], self.device, per=per, soft=soft, kappa=float(algo.get("huber_kappa", 1.0)))
         if memory is not None:
             memory.update_priorities(ws["idx"], ws["abs_td"])
 
-    def _dpg_loss(self, ws, q, ld):
-        """-mean(min q): d loss / d q -> ws["dy"], the loss -> the actor's ring."""
-        if self._quantile:   # q of a net = the mean of its quantile head
-            L.check(L.lib.pqlk_dpg_loss_quantile(L.ptr(q), ld, self.critic.num_quantiles, ws["B"], L.ptr(ws["dy"]), L.ptr(self.aloss),
-                                                 L.ptr(self.aopt.step), LOSS_RING, L.ptr(ws["scratch"]), L.stream(self.device)))
-            return
-        L.check(L.lib.pqlk_dpg_loss(L.ptr(q), ld, 1, None, ws["B"], L.ptr(ws["dy"]), L.ptr(self.aloss), L.ptr(self.aopt.step), LOSS_RING,
-                                    L.ptr(ws["scratch"]), L.stream(self.device)))
+    def _dpg_loss(self, ws, q, ld, mean=False):
+        """-mean(min q) (mean=True: see `CriticHead.actor_loss`): d loss / d q -> ws["dy"], the loss -> the actor's ring."""
+        self.head.actor_loss(q, ld, ws["B"], ws["dy"], self.aloss, self.aopt.step, ws["scratch"], self.device, mean=mean)
 
     def _critic_step(self, ws):
         algo = self.cfg.algo

@@ -88,37 +88,6 @@ def apply_optimizer_fused(layout, arena, grads, st: _AdamState, target, lr, max_
                                           float(loss_scale), L.ptr(loss_ring), LOSS_RING, L.stream(device)))
 
 
-def td_mse_loss(q, qt, ld, rew, done, gamma_n, B, dy, loss_out, step, scratch, device, w=None, wmax=None, abs_td=None):
-    """Twin MSE against r + (1 - d) gamma^n min(qt): d loss / d q -> dy, the partials -> scratch, the loss -> slot `step` of the ring
-    `loss_out` (None: the partials are folded later).  With `w`, `wmax`, `abs_td` (prioritized replay) the importance weights
-    w / wmax lie on the loss and its gradient, and |TD| goes to `abs_td`."""
-    head = (L.ptr(q), L.ptr(qt), ld, L.ptr(rew), L.ptr(done), gamma_n, B, L.ptr(dy), L.ptr(loss_out), L.ptr(step), LOSS_RING,
-            L.ptr(scratch))
-    if w is None:
-        L.check(L.lib.pqlk_td_mse_loss(*head, L.stream(device)))
-    else:
-        L.check(L.lib.pqlk_td_mse_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), L.stream(device)))
-
-
-def qr_huber_loss(theta, theta_t, ld, n, rew, done, gamma_n, kappa, B, dy, loss_out, step, scratch, device, w=None, wmax=None, abs_td=None,
-                  drop=None):
-    """The quantile Huber loss of twin quantile heads (n columns of the (2, B, ld) blocks) against the target net with the smaller
-    mean (include/pqlk.h): d loss / d theta -> dy, the partials -> scratch, the loss -> the ring as in `td_mse_loss`; with `w`, `wmax`,
-    `abs_td` the prioritized instance.  drop (algo.qr_drop) not None: against the pooled atoms of both target nets without the
-    2 * drop largest (the truncated pooled target; its own entries)."""
-    head = (L.ptr(theta), L.ptr(theta_t), ld, int(n), L.ptr(rew), L.ptr(done), gamma_n, float(kappa), B, L.ptr(dy), L.ptr(loss_out), L.ptr(step),
-            LOSS_RING, L.ptr(scratch))
-    if drop is not None:
-        if w is None:
-            L.check(L.lib.pqlk_tqc_huber_loss(*head, int(drop), L.stream(device)))
-        else:
-            L.check(L.lib.pqlk_tqc_huber_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), int(drop), L.stream(device)))
-    elif w is None:
-        L.check(L.lib.pqlk_qr_huber_loss(*head, L.stream(device)))
-    else:
-        L.check(L.lib.pqlk_qr_huber_loss_per(*head, L.ptr(w), L.ptr(wmax), L.ptr(abs_td), L.stream(device)))
-
-
 def qr_drop(algo):
     """`algo.qr_drop` as the loss entries take it: None (the key absent or null: one whole target net per row) or the int d."""
     d = _cfg_get(algo, "qr_drop", None)

@@ -16,7 +16,8 @@ import ctypes as C
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
+from pql_amd.algo.heads import CriticHead
+from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
                                   check_critic_class, load_artifact, make_actor, make_critic, pump, resident_norm)
 from pql_amd.models.mlp import PackedWeights, default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.simple_replay import RecordRing, _obs_width, cfg_obs_dtype, ring_plan
@@ -39,6 +40,7 @@ class PQLPLearner(Learner):
             load_artifact(cfg.artifact, actor=self.actor)
         super().__init__(obs_dim, action_dim, cfg, device, process_group, self.actor)
         self.pk_actor = PackedWeights(self.actor.layout, self.device) if self._fused else None
+        self._head = None
         # obs-only replay (reference :32-37: a bare (memory_size, obs) tensor + inline pointer logic)
         self.memory_size = int(algo.memory_size)
         self.ring = RecordRing(self.memory_size, _obs_width(obs_dim), -1, self.device, obs_dtype=cfg_obs_dtype(algo))
@@ -54,6 +56,13 @@ class PQLPLearner(Learner):
     def memory(self):
         """(memory_size, obs_dim) view of the ring, the reference's attribute name (:34)."""
         return self.ring.obs_view()
+
+    @property
+    def head(self):
+        """The frozen critic's head, described once per replica."""
+        if self._head is None or self._head.critic is not self.critic:
+            self._head = CriticHead(self.critic, self.cfg.algo)
+        return self._head
 
     def _bound(self):
         return self.cur_capacity
@@ -82,9 +91,7 @@ class PQLPLearner(Learner):
         ws["K"] = K
         # round 4: loss + partition + compact head in one launch, the actor's head backward inside the action-slice launch
         # (pqlk_dpg_backward_fused: 16 -> 13 launches per step); needs the loss fold of the optimiser launch and a fused critic forward
-        K_atoms = int(getattr(self.critic, "num_atoms", 1))
-        scalar = K_atoms == 1 and getattr(self.critic, "head", "scalar") == "scalar"
-        ws["dpg_fused"] = bool(_cfg_get(self.cfg.algo, "dpg_fused", True) and self._fold_loss and scalar and self.pk_critic is not None
+        ws["dpg_fused"] = bool(_cfg_get(self.cfg.algo, "dpg_fused", True) and self._fold_loss and self.head.kind == "scalar" and self.pk_critic is not None
                                and self.pk_critic.tensor is not None and self.pk_actor is not None and self.pk_actor.tensor is not None
                                and L.lib.pqlk_dpg_fused_ok(C.byref(cl.desc), C.byref(al.desc), B))
         # ... and then the critic reads its input where the two halves of torch.cat((obs, action)) already lie -- the actor's input
@@ -173,21 +180,14 @@ class PQLPLearner(Learner):
         mlp_forward_raw(cl, self.critic.arena.data, ws["x_sa"], L.ACT_NONE, acts=ws["acts_c"], packed=self.pk_critic,
                         stash_all=True)   # the dX chain through the frozen critic needs its activations (ELU')
         q = output_view(cl, ws["acts_c"], B)
-        K = int(getattr(self.critic, "num_atoms", 1))
-        z = getattr(self.critic, "z_atoms", None) if K > 1 else None
-        quantile = getattr(self.critic, "head", "scalar") == "quantile"
-        if quantile:   # -mean(min of the two heads' means); no owner partition (K below: not the scalar head's)
-            K = self.critic.num_quantiles
-            L.check(L.lib.pqlk_dpg_loss_quantile(L.ptr(q), cl.ld_out, K, B, L.ptr(ws["dy_c"]), None if self._fold_loss else L.ptr(self.loss_ring),
-                                                 L.ptr(self.opt.step), LOSS_RING, L.ptr(ws["scratch"]), st))
-        else:
-            L.check(L.lib.pqlk_dpg_loss_owner(L.ptr(q), cl.ld_out, K, L.ptr(z), B, L.ptr(ws["dy_c"]), None if self._fold_loss else L.ptr(self.loss_ring),
-                                              L.ptr(self.opt.step), LOSS_RING, L.ptr(ws["scratch"]), C.c_void_p(ws["owner"].data_ptr()), st))
+        head = self.head   # -mean(min Q) and, of scalar heads, the owner partition (the quantile entry has none, the categorical one leaves it unwritten)
+        head.actor_loss(q, cl.ld_out, B, ws["dy_c"], None if self._fold_loss else self.loss_ring, self.opt.step, ws["scratch"], dev,
+                        owner=None if head.kind == "quantile" else ws["owner"])
         # dX-only chain through the frozen critic; with scalar Q heads it runs over the samples partitioned by the net that
         # attained min(Q1, Q2): the other net's rows of every dZ are exactly zero (csrc/minnet.h)
         L.check(L.lib.pqlk_dpg_critic_backward(C.byref(cl.desc), L.ptr(self.critic.arena.data), L.ptr(ws["x_sa"]), ws["ld_sa"], B,
                                                L.ptr(ws["acts_c"]), L.ptr(ws["dy_c"]), L.ptr(ws["dz_a"]), ws["ld_a"], O, A,
-                                               L.ptr(a_out), ws["ld_a"], C.c_void_p(ws["owner"].data_ptr()) if K == 1 else None,
+                                               L.ptr(a_out), ws["ld_a"], C.c_void_p(ws["owner"].data_ptr()) if head.width == 1 else None,
                                                L.ptr(ws["bwd_c"]), ws["bwd_c"].numel(), st))
         if tail:
             L.check(L.lib.pqlk_mlp_backward_norm(C.byref(al.desc), L.ptr(self.actor.arena.data), L.ptr(ws["x_obs"]), ws["ld_o"], B,
@@ -204,12 +204,9 @@ class PQLPLearner(Learner):
     def _step_post(self, ws):
         algo = self.cfg.algo
         if self._fold_loss:
-            K = int(getattr(self.critic, "num_atoms", 1))
-            if getattr(self.critic, "head", "scalar") == "quantile":
-                K = self.critic.num_quantiles
             apply_optimizer_fused(self.actor.layout, self.actor.arena.data, ws["grads"], self.opt, None, algo.actor_lr,
                                   algo.max_grad_norm, 0.0, self.pk_actor, None, ws["scratch"],
-                                  ws["loss_parts"] if ws["dpg_fused"] else L.lib.pqlk_loss_parts(ws["B"], K),
+                                  ws["loss_parts"] if ws["dpg_fused"] else self.head.loss_parts(ws["B"]),
                                   f32_recip(ws["B"], sign=-1.0), self.loss_ring, self.device, norm_in_backward=self._fused_tail,
                                   grad_scale=1.0 / self.world)
             return

@@ -20,9 +20,9 @@ from copy import deepcopy
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import (GATHER_FLAGS, LOSS_RING, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
-                                  check_critic_class, graph_collective_enabled, load_artifact, make_actor, make_critic, pump, qr_drop, qr_huber_loss,
-                                  qr_targets, resident_norm, td_mse_loss)
+from pql_amd.algo.heads import CriticHead
+from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, check_critic_class,
+                                  graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
                                 output_view)
 from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer, per_beta, per_cfg
@@ -55,7 +55,7 @@ class PQLVLearner(Learner):
         device = torch.device(f"cuda:{int(cfg.algo.v_learner_gpu)}")
         algo = cfg.algo
         self.critic = make_critic(cfg, obs_dim, int(action_dim), device)
-        self._head = self.critic.head   # scalar | categorical | quantile: which loss launch a step takes, and the K of its fold
+        self.head = CriticHead(self.critic, algo)   # which loss launch a step takes, and the parts and the scale of its fold
         if cfg.artifact is not None:   # local warm start (pql_v_learner.py:44-47): the target below is the copy of what was loaded
             load_artifact(cfg.artifact, critic=self.critic)
         super().__init__(obs_dim, action_dim, cfg, device, process_group, self.critic)
@@ -98,7 +98,7 @@ class PQLVLearner(Learner):
             raise ValueError(f"algo.target_dtype must be float32 or bfloat16, got {value!r}")
         self.flush_priorities()   # (the workspace, and with it the |TD| slabs, is rebuilt below)
         if value == "bfloat16":
-            if self._head == "quantile":   # (the config's own refusal: check_critic_class)
+            if self.head.kind == "quantile":   # (the config's own refusal: check_critic_class)
                 raise ValueError("algo.target_dtype=bfloat16 is not supported with algo.cri_class=QuantileDoubleQ")
             if not self._fused:
                 raise ValueError("algo.target_dtype=bfloat16 needs the fused path (algo.fused=True)")
@@ -206,7 +206,7 @@ class PQLVLearner(Learner):
         # scalar twin heads: TD target + MSE + dL/dQ are formed inside the head's backward pass (one launch less)
         # (not with prioritized replay: the fused TD heads cannot weight rows, the step takes the separate weighted loss launch)
         ws["td_parts"] = int(L.lib.pqlk_td_head_loss_parts(C.byref(cl.desc), B)) if (self._fold_loss and self._td_in_head and self._per is None
-                                                                                      and self._head == "scalar") else 0
+                                                                                      and self.head.kind == "scalar") else 0
         # ... and with the fused forward the head's whole backward runs inside the critic's forward launch, off the activations still
         # in LDS: the head-backward launch and its second read of them disappear (algo.td_in_forward; not with gradient buckets)
         ws["td_fwd"] = 0
@@ -359,21 +359,10 @@ class PQLVLearner(Learner):
             if ws["td_parts"] == 0:
                 q = output_view(cl, ws["acts_c"], B)
                 qt = output_view(cl, ws["acts_t"], B)
-                loss_out = None if self._fold_loss else L.ptr(self.loss_ring)
-                if self._head == "quantile":   # (prioritized replay: as for the scalar heads below)
-                    per = {} if self._per is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
-                    qr_huber_loss(q, qt, cl.ld_out, self.critic.num_quantiles, ws["rew"], ws["done"], gamma_n, float(_cfg_get(algo, "huber_kappa", 1.0)),
-                                  B, ws["dy"], None if self._fold_loss else self.loss_ring, self.opt.step, ws["scratch"], self.device,
-                                  drop=qr_drop(algo), **per)
-                elif algo.distl:
-                    L.check(L.lib.pqlk_c51_bce_loss(L.ptr(q), L.ptr(qt), cl.ld_out, int(algo.num_atoms), L.ptr(ws["rew"]),
-                                                    L.ptr(ws["done"]), L.ptr(self.critic.z_atoms), gamma_n, float(algo.v_min),
-                                                    float(algo.v_max), B, L.ptr(ws["dy"]), loss_out, L.ptr(self.opt.step),
-                                                    LOSS_RING, None, L.ptr(ws["scratch"]), st))
-                else:   # (with prioritized replay: importance weights on the loss and its gradient; |TD| -> the slot's slab)
-                    per = {} if self._per is None else dict(w=ws["w"], wmax=ws["wmax"], abs_td=ws["abs_td"])
-                    td_mse_loss(q, qt, cl.ld_out, ws["rew"], ws["done"], gamma_n, B, ws["dy"], None if self._fold_loss else self.loss_ring,
-                                self.opt.step, ws["scratch"], self.device, **per)
+                # (with prioritized replay: importance weights on the loss and its gradient; |TD| -> the slot's slab)
+                per = None if self._per is None else (ws["w"], ws["wmax"], ws["abs_td"])
+                self.head.critic_loss(q, qt, cl.ld_out, ws["rew"], ws["done"], gamma_n, B, ws["dy"], None if self._fold_loss else self.loss_ring,
+                                      self.opt.step, ws["scratch"], self.device, per=per, kappa=float(_cfg_get(algo, "huber_kappa", 1.0)))
         if self._buckets is not None:
             # data parallel: the chain in pieces, each ending with the sum of its layers' dW slabs; that piece's collective goes
             # out right behind it and runs under the launches of the layers below
@@ -423,11 +412,9 @@ class PQLVLearner(Learner):
     def _optimizer(self, ws):
         algo, dev = self.cfg.algo, self.device
         if self._fold_loss:
-            K = self.critic.num_quantiles if self._head == "quantile" else (int(algo.num_atoms) if algo.distl else 1)
-            D = qr_targets(algo, K) if self._head == "quantile" else K   # the loss's divisor: with algo.qr_drop the kept atoms, not K
             apply_optimizer_fused(self.critic.layout, self.critic.arena.data, ws["grads"], self.opt, self.critic_target.arena.data,
                                   algo.critic_lr, algo.max_grad_norm, algo.tau, self.pk_critic, self.pk_target, ws["scratch"],
-                                  ws["td_parts"] or L.lib.pqlk_loss_parts(ws["B"], K), f32_recip(ws["B"], D) if K > 1 else f32_recip(ws["B"]),
+                                  ws["td_parts"] or self.head.loss_parts(ws["B"]), self.head.critic_scale(ws["B"]),
                                   self.loss_ring, dev, norm_in_backward=self._fused_tail, grad_scale=1.0 / self.world)
             return
         # optimiser + Polyak + refresh of the fragment-ordered weight copies (critic and target) in one launch pair

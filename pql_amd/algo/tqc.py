@@ -16,8 +16,6 @@ Two critic nets (the paper uses five: the arena layout is twin); `algo.qr_drop` 
 """
 from __future__ import annotations
 
-from pql_amd import _lib as L
-from pql_amd.algo.learner import LOSS_RING, qr_drop
 from pql_amd.algo.sac import AgentSAC
 
 
@@ -27,19 +25,8 @@ class AgentTQC(AgentSAC):
     def _soft_td_loss(self, ws, q, qt, ld):
         """The truncated quantile Huber loss against T_p = r + c (z_p - alpha log pi(a'|s')): d loss / d theta -> ws["dy"], the loss ->
         the critic's ring; prioritized: the importance weights in, |TD| back into the tree."""
-        algo = self.cfg.algo
-        memory = ws.get("per")
-        head = (L.ptr(q), L.ptr(qt), ld, self.critic.num_quantiles, L.ptr(ws["rew"]), L.ptr(ws["done"]), float(algo.gamma) ** int(algo.nstep),
-                float(algo.get("huber_kappa", 1.0)), ws["B"], L.ptr(ws["dy"]), L.ptr(self.closs), L.ptr(self.copt.step), LOSS_RING,
-                L.ptr(ws["scratch"]))
-        soft = (L.ptr(ws["logp_next"]), L.ptr(self.log_alpha), qr_drop(algo), L.stream(self.device))
-        if memory is None:
-            L.check(L.lib.pqlk_tqc_huber_loss_soft(*head, *soft))
-        else:
-            L.check(L.lib.pqlk_tqc_huber_loss_soft_per(*head, L.ptr(ws["w"]), L.ptr(ws["wmax"]), L.ptr(ws["abs_td"]), *soft))
-            memory.update_priorities(ws["idx"], ws["abs_td"])
+        self._td_mse_loss(ws, q, qt, ld, soft=(ws["logp_next"], self.log_alpha))
 
     def _actor_q_loss(self, ws, q, ld):
         """-mean_b of the mean over all 2 N atoms: d loss / d theta -> ws["dy"], the value -> the actor's ring."""
-        L.check(L.lib.pqlk_dpg_loss_quantile_mean(L.ptr(q), ld, self.critic.num_quantiles, ws["B"], L.ptr(ws["dy"]), L.ptr(self.aloss),
-                                                  L.ptr(self.aopt.step), LOSS_RING, L.ptr(ws["scratch"]), L.stream(self.device)))
+        self._dpg_loss(ws, q, ld, mean=True)

@@ -501,6 +501,45 @@ __device__ __forceinline__ void qr_term(float u, float tau, float kappa, float& 
   l += wgt * h;
 }
 
+// the four guarded loads of a row: lane j < N holds quantile j of both nets (th) and of both target nets (t), the other lanes zeros
+struct QrRow {
+  float th0, th1, t0, t1;
+};
+__device__ __forceinline__ QrRow qr_load_row(const float* __restrict__ theta, const float* __restrict__ theta_t, int64_t ld, int64_t b,
+                                             int64_t i, int lane, bool on) {
+  return {on ? theta[i * ld + lane] : 0.f, on ? theta[(b + i) * ld + lane] : 0.f, on ? theta_t[i * ld + lane] : 0.f,
+          on ? theta_t[(b + i) * ld + lane] : 0.f};
+}
+
+// Tail of a row of either Huber kernel, from the lane's chains g0, g1 (gradient) and l0, l1 (loss) of the two nets: / kappa, the
+// row's scale 1 / (B * target atoms), (* wh), the loss into the lane's accumulator, the negated gradient and the pad columns -> dy,
+// and with PER the row's new priority |mt - mean_j theta_j| of either net, the larger (mt: the mean of the row's targets, formed by
+// the caller; the plain instances never read it, w or abs_td).
+template <bool PER>
+__device__ __forceinline__ void huber_row_epilogue(float g0, float g1, float l0, float l1, float kappa, float scale, float mt, float th0,
+                                                   float th1, bool on, int lane, int N, int64_t i, int64_t b, int64_t ld,
+                                                   float* __restrict__ dy, float& acc, const float* __restrict__ w, float wm,
+                                                   float* __restrict__ abs_td) {
+  float row = (l0 + l1) / kappa;
+  float v0[1] = {(g0 / kappa) * scale}, v1[1] = {(g1 / kappa) * scale};
+  if constexpr (PER) {
+    const float wh = w[i] / wm;
+    row = wh * row;
+    v0[0] = wh * v0[0];
+    v1[0] = wh * v1[0];
+  }
+  if (on) acc += row;
+  v0[0] = -v0[0];
+  v1[0] = -v1[0];
+  store_dy_row<1>(dy + i * ld, ld, N, lane, v0);
+  store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v1);
+  if constexpr (PER) {
+    const float inv_n = 1.0f / (float)N;
+    const float m0 = wave_sum(th0) * inv_n, m1 = wave_sum(th1) * inv_n;
+    if (lane == 0) abs_td[i] = fmaxf(fabsf(mt - m0), fabsf(mt - m1));
+  }
+}
+
 template <bool PER>
 __global__ __launch_bounds__(256) void k_qr_huber(const float* __restrict__ theta, const float* __restrict__ theta_t, int64_t ld,
                                                   int N, const float* __restrict__ rew, const float* __restrict__ done,
@@ -518,8 +557,7 @@ __global__ __launch_bounds__(256) void k_qr_huber(const float* __restrict__ thet
   float acc = 0.f;
   for (int64_t i = wave; i < b; i += nw) {
     const float r = rew[i], d = done[i];
-    const float th0 = on ? theta[i * ld + lane] : 0.f, th1 = on ? theta[(b + i) * ld + lane] : 0.f;
-    const float t0 = on ? theta_t[i * ld + lane] : 0.f, t1 = on ? theta_t[(b + i) * ld + lane] : 0.f;
+    const auto [th0, th1, t0, t1] = qr_load_row(theta, theta_t, ld, b, i, lane, on);
     const float s0 = wave_sum(t0), s1 = wave_sum(t1);
     const float ts = s1 < s0 ? t1 : t0;                 // clipped double-Q on the means: one net per row, a tie takes net 0
     const float T = r + ((1.f - d) * gamma_n) * ts;     // lane k: T_k (k_td_mse's operation order)
@@ -529,60 +567,12 @@ __global__ __launch_bounds__(256) void k_qr_huber(const float* __restrict__ thet
       qr_term(tk - th0, tau, kappa, g0, l0);
       qr_term(tk - th1, tau, kappa, g1, l1);
     }
-    float row = (l0 + l1) / kappa;
-    float v0[1] = {(g0 / kappa) * inv_bn}, v1[1] = {(g1 / kappa) * inv_bn};
-    if constexpr (PER) {
-      const float wh = w[i] / wm;
-      row = wh * row;
-      v0[0] = wh * v0[0];
-      v1[0] = wh * v1[0];
-    }
-    if (on) acc += row;
-    v0[0] = -v0[0];
-    v1[0] = -v1[0];
-    store_dy_row<1>(dy + i * ld, ld, N, lane, v0);
-    store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v1);
-    if constexpr (PER) {   // |mean_k T_k - mean_j theta_j| of either net, the larger: the row's new priority
-      const float inv_n = 1.0f / (float)N;
-      const float mt = wave_sum(on ? T : 0.f) * inv_n;
-      const float m0 = wave_sum(th0) * inv_n, m1 = wave_sum(th1) * inv_n;
-      if (lane == 0) abs_td[i] = fmaxf(fabsf(mt - m0), fabsf(mt - m1));
-    }
+    float mt = 0.f;                                     // mean_k T_k
+    if constexpr (PER) mt = wave_sum(on ? T : 0.f) * (1.0f / (float)N);
+    huber_row_epilogue<PER>(g0, g1, l0, l1, kappa, inv_bn, mt, th0, th1, on, lane, N, i, b, ld, dy, acc, w, wm, abs_td);
   }
   const float s = block_sum_256(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-template <bool PER>
-static int qr_huber_impl(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew, const float* done,
-                         float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev, int32_t ring_len,
-                         float* scratch, const float* w, const float* wmax, float* abs_td_out, pqlk_stream_t stream) {
-  PQLK_REQUIRE(theta && theta_t && rew && done && dy && scratch, PQLK_E_NULL);
-  PQLK_REQUIRE(!PER || (w && wmax && abs_td_out), PQLK_E_NULL);
-  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
-  PQLK_REQUIRE(b > 0 && kappa > 0.f, PQLK_E_SHAPE);
-  PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
-  PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
-  const int blocks = loss_blocks(b, n);
-  hipLaunchKernelGGL(k_qr_huber<PER>, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, rew, done, gamma_n, kappa,
-                     b, dy, scratch, w, wmax, abs_td_out);
-  PQLK_LAUNCH_CHECK();
-  return fold_partials(scratch, blocks, 1.0f / ((float)b * (float)n), loss_out, slot_dev, ring_len, stream);
-}
-
-extern "C" int pqlk_qr_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
-                                  const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
-                                  const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
-  return qr_huber_impl<false>(theta, theta_t, ld, n, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, nullptr,
-                              nullptr, nullptr, stream);
-}
-
-extern "C" int pqlk_qr_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
-                                      const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
-                                      const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w, const float* wmax,
-                                      float* abs_td_out, pqlk_stream_t stream) {
-  return qr_huber_impl<true>(theta, theta_t, ld, n, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w, wmax,
-                             abs_td_out, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -624,8 +614,7 @@ __global__ __launch_bounds__(256) void k_tqc_huber(const float* __restrict__ the
     const float r = rew[i], d = done[i];
     float sh = 0.f;
     if constexpr (SOFT) sh = alpha * logp[i];            // s_b: one product
-    const float th0 = on ? theta[i * ld + lane] : 0.f, th1 = on ? theta[(b + i) * ld + lane] : 0.f;
-    const float t0 = on ? theta_t[i * ld + lane] : 0.f, t1 = on ? theta_t[(b + i) * ld + lane] : 0.f;
+    const auto [th0, th1, t0, t1] = qr_load_row(theta, theta_t, ld, b, i, lane, on);
     // ranks of this lane's atoms p = lane (z = t0) and p = N + lane (z = t1) among the 2 N pooled raw target quantiles
     int c0 = 0, c1 = 0;
     for (int q = 0; q < N; ++q) {
@@ -657,71 +646,77 @@ __global__ __launch_bounds__(256) void k_tqc_huber(const float* __restrict__ the
       qr_term(tp - th0, tau, kappa, g0, l0);
       qr_term(tp - th1, tau, kappa, g1, l1);
     }
-    float row = (l0 + l1) / kappa;
-    float v0[1] = {(g0 / kappa) * inv_bm}, v1[1] = {(g1 / kappa) * inv_bm};
-    if constexpr (PER) {
-      const float wh = w[i] / wm;
-      row = wh * row;
-      v0[0] = wh * v0[0];
-      v1[0] = wh * v1[0];
-    }
-    if (on) acc += row;
-    v0[0] = -v0[0];
-    v1[0] = -v1[0];
-    store_dy_row<1>(dy + i * ld, ld, N, lane, v0);
-    store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v1);
-    if constexpr (PER) {   // |mean_{kept p} T_p - mean_j theta_j| of either net, the larger: the row's new priority
-      const float mt = wave_sum((keep0 ? T0 : 0.f) + (keep1 ? T1 : 0.f)) * (1.0f / (float)M);
-      const float inv_n = 1.0f / (float)N;
-      const float mq0 = wave_sum(th0) * inv_n, mq1 = wave_sum(th1) * inv_n;
-      if (lane == 0) abs_td[i] = fmaxf(fabsf(mt - mq0), fabsf(mt - mq1));
-    }
+    float mt = 0.f;                                      // mean of the kept T_p
+    if constexpr (PER) mt = wave_sum((keep0 ? T0 : 0.f) + (keep1 ? T1 : 0.f)) * (1.0f / (float)M);
+    huber_row_epilogue<PER>(g0, g1, l0, l1, kappa, inv_bm, mt, th0, th1, on, lane, N, i, b, ld, dy, acc, w, wm, abs_td);
   }
   const float s = block_sum_256(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-template <bool PER, bool SOFT>
-static int tqc_huber_impl(const float* theta, const float* theta_t, int64_t ld, int32_t n, int32_t drop, const float* rew,
-                          const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
-                          int32_t ring_len, float* scratch, const float* w, const float* wmax, float* abs_td_out, const float* logp,
-                          const float* log_alpha, pqlk_stream_t stream) {
+// Behind the six Huber entries.  POOLED: the truncated pooled law (k_tqc_huber; drop is checked, the loss's divisor is the kept atoms
+// M = 2 (n - drop)); otherwise one whole target net per row (k_qr_huber; drop, logp and log_alpha are not looked at, the divisor is n).
+template <bool PER, bool POOLED, bool SOFT>
+static int huber_impl(const float* theta, const float* theta_t, int64_t ld, int32_t n, int32_t drop, const float* rew, const float* done,
+                      float gamma_n, float kappa, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev, int32_t ring_len,
+                      float* scratch, const float* w, const float* wmax, float* abs_td_out, const float* logp, const float* log_alpha,
+                      pqlk_stream_t stream) {
+  static_assert(POOLED || !SOFT, "the soft target is a law of the pooled atoms");
   PQLK_REQUIRE(theta && theta_t && rew && done && dy && scratch, PQLK_E_NULL);
   PQLK_REQUIRE(!PER || (w && wmax && abs_td_out), PQLK_E_NULL);
   PQLK_REQUIRE(!SOFT || (logp && log_alpha), PQLK_E_NULL);
   PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
   PQLK_REQUIRE(b > 0 && kappa > 0.f, PQLK_E_SHAPE);
   PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
-  PQLK_REQUIRE(drop >= 0 && drop < n, PQLK_E_SHAPE);
+  PQLK_REQUIRE(!POOLED || (drop >= 0 && drop < n), PQLK_E_SHAPE);
   PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
   const int blocks = loss_blocks(b, n);
-  hipLaunchKernelGGL((k_tqc_huber<PER, SOFT>), dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, (int)drop, rew, done,
-                     gamma_n, kappa, b, dy, scratch, w, wmax, abs_td_out, logp, log_alpha);
+  if constexpr (POOLED)
+    hipLaunchKernelGGL((k_tqc_huber<PER, SOFT>), dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, (int)drop, rew, done,
+                       gamma_n, kappa, b, dy, scratch, w, wmax, abs_td_out, logp, log_alpha);
+  else
+    hipLaunchKernelGGL(k_qr_huber<PER>, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, theta_t, ld, (int)n, rew, done, gamma_n, kappa, b,
+                       dy, scratch, w, wmax, abs_td_out);
   PQLK_LAUNCH_CHECK();
-  return fold_partials(scratch, blocks, 1.0f / ((float)b * (float)(2 * (n - drop))), loss_out, slot_dev, ring_len, stream);
+  return fold_partials(scratch, blocks, 1.0f / ((float)b * (float)(POOLED ? 2 * (n - drop) : n)), loss_out, slot_dev, ring_len, stream);
+}
+
+extern "C" int pqlk_qr_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                  const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                  const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
+  return huber_impl<false, false, false>(theta, theta_t, ld, n, 0, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
+                                         nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int pqlk_qr_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
+                                      const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
+                                      const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w, const float* wmax,
+                                      float* abs_td_out, pqlk_stream_t stream) {
+  return huber_impl<true, false, false>(theta, theta_t, ld, n, 0, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
+                                        wmax, abs_td_out, nullptr, nullptr, stream);
 }
 
 extern "C" int pqlk_tqc_huber_loss(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
                                    const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
                                    const int32_t* slot_dev, int32_t ring_len, float* scratch, int32_t drop, pqlk_stream_t stream) {
-  return tqc_huber_impl<false, false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
-                                      nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  return huber_impl<false, true, false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int pqlk_tqc_huber_loss_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
                                        const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
                                        const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w, const float* wmax,
                                        float* abs_td_out, int32_t drop, pqlk_stream_t stream) {
-  return tqc_huber_impl<true, false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
-                                     wmax, abs_td_out, nullptr, nullptr, stream);
+  return huber_impl<true, true, false>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
+                                       wmax, abs_td_out, nullptr, nullptr, stream);
 }
 
 extern "C" int pqlk_tqc_huber_loss_soft(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
                                         const float* done, float gamma_n, float kappa, int64_t b, float* dy, float* loss_out,
                                         const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* logp,
                                         const float* log_alpha, int32_t drop, pqlk_stream_t stream) {
-  return tqc_huber_impl<false, true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
-                                     nullptr, nullptr, nullptr, logp, log_alpha, stream);
+  return huber_impl<false, true, true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch,
+                                       nullptr, nullptr, nullptr, logp, log_alpha, stream);
 }
 
 extern "C" int pqlk_tqc_huber_loss_soft_per(const float* theta, const float* theta_t, int64_t ld, int32_t n, const float* rew,
@@ -729,29 +724,40 @@ extern "C" int pqlk_tqc_huber_loss_soft_per(const float* theta, const float* the
                                             const int32_t* slot_dev, int32_t ring_len, float* scratch, const float* w,
                                             const float* wmax, float* abs_td_out, const float* logp, const float* log_alpha,
                                             int32_t drop, pqlk_stream_t stream) {
-  return tqc_huber_impl<true, true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
-                                    wmax, abs_td_out, logp, log_alpha, stream);
+  return huber_impl<true, true, true>(theta, theta_t, ld, n, drop, rew, done, gamma_n, kappa, b, dy, loss_out, slot_dev, ring_len, scratch, w,
+                                      wmax, abs_td_out, logp, log_alpha, stream);
 }
 
-// DPG on the quantile heads: Q_i = (sum_j theta[i, b, j]) * (1 / N) (wave_sum), L = -mean_b min(Q_0, Q_1); every quantile of the
-// smaller net gets -1 / (B N), on a tie both nets half of it (torch.min's backward, k_dpg_scalar).  Lane 0 carries the row's
-// min into the block's partial; the fold scale is -1 / B.
-__global__ __launch_bounds__(256) void k_dpg_quantile(const float* __restrict__ theta, int64_t ld, int N, int64_t b,
-                                                      float* __restrict__ dy, float* __restrict__ part) {
+// DPG on the quantile heads, one wave per row.  The min law (MEAN false): Q_i = (sum_j theta[i, b, j]) * (1 / N) (wave_sum),
+// L = -mean_b min(Q_0, Q_1); every quantile of the smaller net gets -1 / (B N), on a tie both nets half of it (torch.min's backward,
+// k_dpg_scalar).  The mean-of-critics objective of the TQC agent (MEAN true, "Mean-of-critics actor objective" in include/pqlk.h):
+// Qbar_b = wave_sum(th0 + th1) * (1 / (2 N)), L = -mean_b Qbar_b; every quantile of both nets gets -1 / (B 2 N), whatever the
+// values (no min, no tie).  Lane 0 carries the row's min / Qbar_b into the block's partial; the fold scale is -1 / B.
+template <bool MEAN>
+__device__ __forceinline__ void dpg_quantile_rows(const float* __restrict__ theta, int64_t ld, int N, int64_t b, float* __restrict__ dy,
+                                                  float* __restrict__ part) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nw = (int64_t)gridDim.x * 4;
-  const float g = -(1.0f / ((float)b * (float)N));
-  const float inv_n = 1.0f / (float)N;
+  const int D = MEAN ? 2 * N : N;                        // atoms a row's Q is the mean of
+  const float g = -(1.0f / ((float)b * (float)D));
+  const float inv_d = 1.0f / (float)D;
   float acc = 0.f;
   for (int64_t i = wave; i < b; i += nw) {
     float th0[1], th1[1];
     load_row<1>(theta + i * ld, N, lane, th0);
     load_row<1>(theta + (b + i) * ld, N, lane, th1);
-    const float q0 = wave_sum(th0[0]) * inv_n, q1 = wave_sum(th1[0]) * inv_n;
-    if (lane == 0) acc += fminf(q0, q1);
-    const float v0[1] = {q0 < q1 ? g : (q0 == q1 ? 0.5f * g : 0.f)};
-    const float v1[1] = {q1 < q0 ? g : (q0 == q1 ? 0.5f * g : 0.f)};
+    float g0 = g, g1 = g;
+    if constexpr (MEAN) {
+      const float qbar = wave_sum(th0[0] + th1[0]) * inv_d;
+      if (lane == 0) acc += qbar;
+    } else {
+      const float q0 = wave_sum(th0[0]) * inv_d, q1 = wave_sum(th1[0]) * inv_d;
+      if (lane == 0) acc += fminf(q0, q1);
+      g0 = q0 < q1 ? g : (q0 == q1 ? 0.5f * g : 0.f);
+      g1 = q1 < q0 ? g : (q0 == q1 ? 0.5f * g : 0.f);
+    }
+    const float v0[1] = {g0}, v1[1] = {g1};
     store_dy_row<1>(dy + i * ld, ld, N, lane, v0);
     store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v1);
   }
@@ -759,52 +765,36 @@ __global__ __launch_bounds__(256) void k_dpg_quantile(const float* __restrict__ 
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-extern "C" int pqlk_dpg_loss_quantile(const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
-                                      const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
+__global__ __launch_bounds__(256) void k_dpg_quantile(const float* __restrict__ theta, int64_t ld, int N, int64_t b,
+                                                      float* __restrict__ dy, float* __restrict__ part) {
+  dpg_quantile_rows<false>(theta, ld, N, b, dy, part);
+}
+
+__global__ __launch_bounds__(256) void k_dpg_quantile_mean(const float* __restrict__ theta, int64_t ld, int N, int64_t b,
+                                                           float* __restrict__ dy, float* __restrict__ part) {
+  dpg_quantile_rows<true>(theta, ld, N, b, dy, part);
+}
+
+static int dpg_quantile_impl(bool mean, const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
+                             const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
   PQLK_REQUIRE(theta && dy && scratch, PQLK_E_NULL);
   PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
   PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
   PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
   PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
   const int blocks = loss_blocks(b, n);
-  hipLaunchKernelGGL(k_dpg_quantile, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, ld, (int)n, b, dy, scratch);
+  hipLaunchKernelGGL(mean ? k_dpg_quantile_mean : k_dpg_quantile, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, ld, (int)n, b, dy,
+                     scratch);
   PQLK_LAUNCH_CHECK();
   return fold_partials(scratch, blocks, -1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
 }
 
-// The mean-of-critics actor objective of the TQC agent ("Mean-of-critics actor objective" in include/pqlk.h), k_dpg_quantile's
-// geometry: Qbar_b = wave_sum(th0 + th1) * (1 / (2 N)), L = -mean_b Qbar_b; every quantile of both nets gets -1 / (B 2 N), whatever
-// the values (no min, no tie).  Lane 0 carries Qbar_b into the block's partial; the fold scale is -1 / B.
-__global__ __launch_bounds__(256) void k_dpg_quantile_mean(const float* __restrict__ theta, int64_t ld, int N, int64_t b,
-                                                           float* __restrict__ dy, float* __restrict__ part) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nw = (int64_t)gridDim.x * 4;
-  const float v[1] = {-(1.0f / ((float)b * (float)(2 * N)))};
-  const float inv_2n = 1.0f / (float)(2 * N);
-  float acc = 0.f;
-  for (int64_t i = wave; i < b; i += nw) {
-    float th0[1], th1[1];
-    load_row<1>(theta + i * ld, N, lane, th0);
-    load_row<1>(theta + (b + i) * ld, N, lane, th1);
-    const float qbar = wave_sum(th0[0] + th1[0]) * inv_2n;
-    if (lane == 0) acc += qbar;
-    store_dy_row<1>(dy + i * ld, ld, N, lane, v);
-    store_dy_row<1>(dy + (b + i) * ld, ld, N, lane, v);
-  }
-  const float s = block_sum_256(acc);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
+extern "C" int pqlk_dpg_loss_quantile(const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
+                                      const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
+  return dpg_quantile_impl(false, theta, ld, n, b, dy, loss_out, slot_dev, ring_len, scratch, stream);
 }
 
 extern "C" int pqlk_dpg_loss_quantile_mean(const float* theta, int64_t ld, int32_t n, int64_t b, float* dy, float* loss_out,
                                            const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
-  PQLK_REQUIRE(theta && dy && scratch, PQLK_E_NULL);
-  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
-  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
-  PQLK_REQUIRE(n >= 2 && n <= PQLK_QR_MAX_QUANTILES, PQLK_E_UNSUPPORTED);
-  PQLK_REQUIRE(ld % 32 == 0 && ld >= n, PQLK_E_ALIGN);
-  const int blocks = loss_blocks(b, n);
-  hipLaunchKernelGGL(k_dpg_quantile_mean, dim3(blocks), dim3(256), 0, pqlk_s(stream), theta, ld, (int)n, b, dy, scratch);
-  PQLK_LAUNCH_CHECK();
-  return fold_partials(scratch, blocks, -1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
+  return dpg_quantile_impl(true, theta, ld, n, b, dy, loss_out, slot_dev, ring_len, scratch, stream);
 }
