@@ -1,151 +1,122 @@
-"""ctypes binding of libpqlk.so (include/pqlk.h).
+"""ctypes binding of libpqlk.so, derived from include/pqlk.h: the header is the only declaration of the C ABI.
 
 The library is the product: if it is missing or fails to load this module raises, there is no
 CPU or eager-PyTorch fallback anywhere in pql_amd.
+
+`parse_header` reads the header once at import.  It accepts, and must consume to the last character, this grammar:
+  /* ... */                               dropped first, so a declaration may carry comments anywhere
+  #ifndef X / #define X (the guard pair), #ifdef, #endif, #include lines; extern "C" { ... }      dropped
+  #define PQLK_NAME <integer>             constant NAME (module attribute `NAME`: ACT_TANH, GATHER_CLAMP5, VERSION, ...)
+  #define PQLK_NAME(args) ...             a function-like macro: skipped
+  enum { PQLK_A = <integer>, ... };       constants; every value is explicit
+  typedef void* name;                     `name` is c_void_p (pqlk_stream_t)
+  typedef struct [Tag] { type field; type field[expr]; ... } Name;
+                                          ctypes.Structure `Name` (module attribute; fields in order); expr is integer arithmetic
+                                          over the constants; a pointer field is c_void_p
+  ret pqlk_name(type arg, ...);           PROTOTYPES[pqlk_name] = (restype, [argtypes]), in header order; may span lines; `(void)`
+Types: int, int32_t, int64_t, uint32_t, uint64_t, float, double -> the ctypes class of that name; a `typedef void*` name ->
+c_void_p; `const char*` as a return -> c_char_p; [const] Struct* -> POINTER(Struct); [const] T* for T one of those scalars, void,
+uint8_t or uint16_t -> c_void_p (device pointers, and host out-pointers given as byref() or a ctypes array).  Anything else --
+size_t, long, a struct the header does not define, text between declarations -- is an ImportError that quotes it.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from pathlib import Path
 
 import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_FILE = Path(os.environ.get("PQLK_LIB", _HERE / "csrc" / "libpqlk.so"))   # PQLK_LIB: A/B a tuning build
+HEADER_FILE = _HERE.parent / "include" / "pqlk.h"   # the file csrc/pqlk_common.h includes
 
-MAX_LAYERS = 8
-OBS_F32, OBS_F16 = 0, 1   # PqlReplayDesc.obs_dtype (PQLK_OBS_*)
-INFO_MAX_KEYS = 8         # PQLK_INFO_MAX_KEYS: keys of one pqlk_rollout_info launch
-INFO_F32, INFO_U8 = 0, 1  # PqlInfoKey.dtype (PQLK_INFO_*)
-INFO_LAST, INFO_ALL_EPISODE, INFO_ALL_STEP = 0, 1, 2   # PqlInfoKey.mode
-ACT_NONE, ACT_TANH, ACT_TANH_NOISE = 0, 1, 2
-C51_MAX_ATOMS = 256       # PQLK_C51_MAX_ATOMS: the C51 loss kernels hold one row's atoms in one wave, four per lane at most
-QR_MAX_QUANTILES = 64     # PQLK_QR_MAX_QUANTILES: the quantile loss kernels hold one quantile of both nets per lane
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double}
+_POINTEES = {*_SCALARS, "void", "uint8_t", "uint16_t"}
+_TYPE = r"(?P<const>const\s+)?(?P<base>\w+)(?P<ptr>\s*\*\s*|\s+)"   # `[const] base` then `*` or the space before the name
+_INT = r"-?(?:0[xX][0-9a-fA-F]+|\d+)"
 
 
-class PqlReplayDesc(C.Structure):
-    _fields_ = [("records", C.c_void_p), ("capacity", C.c_int64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32),
-                ("rec_ld", C.c_int32), ("obs_dtype", C.c_int32)]
+def parse_header(text: str, where="header"):
+    """-> (constants {NAME: int}, structs {Name: Structure class}, prototypes {pqlk_name: (restype, [argtypes])})."""
+    consts, structs, aliases, protos = {}, {}, {}, {}
+
+    def fail(what, decl):
+        raise ImportError(f"{where}: {what}: {' '.join(decl.split())!r}")
+
+    def ctype(m, decl, ret=False, field=False):
+        base, ptr = m["base"], "*" in m["ptr"]
+        if not ptr and base in _SCALARS:
+            return _SCALARS[base]
+        if not ptr and base in aliases:
+            return aliases[base]
+        if not ptr and ret and base == "void":
+            return None
+        if ptr and ret and base == "char" and m["const"]:
+            return C.c_char_p
+        if ptr and base in structs and not field:
+            return C.POINTER(structs[base])
+        if ptr and base in _POINTEES:
+            return C.c_void_p
+        fail(f"type {(m['const'] or '') + base + ('*' if ptr else '')!r} is not in the type law", decl)
+
+    def define(m):
+        consts[m[1]] = int(m[2], 0)
+
+    def enum(m):
+        for item in filter(None, (s.strip() for s in m[1].split(","))):
+            e = re.fullmatch(rf"PQLK_(\w+)\s*=\s*({_INT})", item) or fail("an enumerator needs an explicit integer value", m[0])
+            consts[e[1]] = int(e[2], 0)
+
+    def struct(m):
+        fields = []
+        for item in filter(None, (s.strip() for s in m[1].split(";"))):
+            f = re.fullmatch(_TYPE + r"(?P<name>\w+)\s*(?:\[(?P<n>[^\]]*)\])?", item) or fail("not a `type name;` field", item)
+            t = ctype(f, m[0], field=True)
+            if f["n"] is not None:
+                expr = re.sub(r"PQLK_(\w+)", lambda c: str(consts[c[1]]) if c[1] in consts else fail("unknown constant", item), f["n"])
+                re.fullmatch(r"[\d\s+*()-]+", expr) or fail("an array size is integer arithmetic over the constants", item)
+                t = t * int(eval(expr, {"__builtins__": {}}))
+            fields.append((f["name"], t))
+        structs[m[2]] = type(m[2], (C.Structure,), {"_fields_": fields})
+
+    def alias(m):
+        aliases[m[1]] = C.c_void_p
+
+    def function(m):
+        args = [] if m["args"].strip() == "void" else m["args"].split(",")
+        parsed = [re.fullmatch(_TYPE + r"\w+", a.strip()) or fail("not a `type name` argument", m[0]) for a in args]
+        protos[m["name"]] = (ctype(m, m[0], ret=True), [ctype(a, m[0]) for a in parsed])
+
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#ifndef\s+(\w+)\s*\n[ \t]*#define\s+\1[ \t]*$", "", text, flags=re.M)
+    text = re.sub(r"^[ \t]*#(?:ifndef|ifdef|endif|include)\b.*$", "", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    for pattern, action in ((r"^[ \t]*#define\s+PQLK_\w+\(.*$", lambda m: None),
+                            (rf"^[ \t]*#define\s+PQLK_(\w+)[ \t]+({_INT})[ \t]*$", define),
+                            (r"\benum\s*\{([^{}]*)\}\s*;", enum),
+                            (r"\btypedef\s+void\s*\*\s*(\w+)\s*;", alias),
+                            (r"\btypedef\s+struct\s*(?:\w+\s*)?\{([^{}]*)\}\s*(\w+)\s*;", struct),
+                            (_TYPE + r"(?P<name>pqlk_\w+)\s*\((?P<args>[^()]*)\)\s*;", function)):
+        text = re.sub(pattern, lambda m: action(m) or "", text, flags=re.M)
+    if text.strip():
+        fail("text that is no declaration the binding understands", text.strip()[:120])
+    return consts, structs, protos
 
 
-class PqlMlpDesc(C.Structure):
-    _fields_ = [("n_layers", C.c_int32), ("n_nets", C.c_int32), ("dims", C.c_int32 * (MAX_LAYERS + 1))]
+def load_header(path=HEADER_FILE):
+    try:
+        text = Path(path).read_text()
+    except OSError as e:
+        raise ImportError(f"{path} is missing or unreadable ({e.strerror}): the ctypes binding is derived from it") from e
+    return parse_header(text, where=os.fspath(path))
 
 
-class PqlInfoKey(C.Structure):
-    _fields_ = [("values", C.c_void_p), ("acc", C.c_void_p), ("ring", C.c_void_p), ("ring_ptr", C.c_void_p), ("dtype", C.c_int32),
-                ("mode", C.c_int32)]
-
-
-_P, _I64, _I32, _F, _D = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_double
-
-# name -> (restype, argtypes); kept in the order of include/pqlk.h
-PROTOTYPES = {
-    "pqlk_version": (C.c_int, []),
-    "pqlk_strerror": (C.c_char_p, [C.c_int]),
-    "pqlk_ld": (_I64, [_I64]),
-    "pqlk_replay_rec_ld": (_I64, [_I32, _I32]),
-    "pqlk_replay_rec_ld_ex": (_I64, [_I32, _I32, _I32]),
-    "pqlk_replay_insert": (C.c_int, [C.POINTER(PqlReplayDesc), _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
-    "pqlk_replay_gather": (C.c_int, [C.POINTER(PqlReplayDesc), _P, _I64, _P, _P, _P, _P, _P, _P]),
-    "pqlk_replay_gather_fused": (C.c_int, [C.POINTER(PqlReplayDesc), _P, _I64, _P, _P, _F, C.c_int, _P, _I64, _P, _P, _I64, _P, _P, _P]),
-    "pqlk_philox_draws": (C.c_int, [C.c_uint64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _I32, _I32, _P]),
-    "pqlk_philox_increment": (_I64, [_I64]),
-    "pqlk_nstep_push_emit": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I64, _I64, _P, _P, _P, _P, _P, C.POINTER(C.c_float),
-                                       _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P]),
-    "pqlk_mlp_param_floats": (_I64, [C.POINTER(PqlMlpDesc)]),
-    "pqlk_mlp_net_stride": (_I64, [C.POINTER(PqlMlpDesc)]),
-    "pqlk_mlp_layer_offsets": (C.c_int, [C.POINTER(PqlMlpDesc), _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-    "pqlk_mlp_acts_floats": (_I64, [C.POINTER(PqlMlpDesc), _I64]),
-    "pqlk_mlp_act_offset": (C.c_int, [C.POINTER(PqlMlpDesc), _I64, _I32, _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-    "pqlk_mlp_bwd_ws_floats": (_I64, [C.POINTER(PqlMlpDesc), _I64, _I32]),
-    "pqlk_mlp_packed_floats": (_I64, [C.POINTER(PqlMlpDesc)]),
-    "pqlk_mlp_pack": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P]),
-    "pqlk_mlp_forward": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I32, _P, _I64, _I64, _I32, _P, _F, _F, _P, _P, _I64, _P]),
-    "pqlk_mlp_bf16_ok": (C.c_int, [C.POINTER(PqlMlpDesc)]),
-    "pqlk_mlp_packed_bf16_elems": (_I64, [C.POINTER(PqlMlpDesc)]),
-    "pqlk_mlp_pack_bf16": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P]),
-    "pqlk_mlp_forward_bf16": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _I64, _I64, _I32, _P, _F, _F, _P, _P, _I64, _P]),
-    "pqlk_mlp_backward": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _P, _I64,
-                                    _P, _I64, _P]),
-    "pqlk_mlp_backward_norm": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _I32, _P, _I64, _I32, _I32, _P, _I64,
-                                         _P, _I64, _P, _P, _P]),
-    "pqlk_mlp_norm_parts": (_I32, [C.POINTER(PqlMlpDesc)]),
-    "pqlk_mlp_backward_td": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _P, _F, _P, _P, _I32, _P, _I64, _P, _P, _P]),
-    "pqlk_td_head_loss_parts": (_I32, [C.POINTER(PqlMlpDesc), _I64]),
-    "pqlk_td_forward_loss_parts": (_I32, [C.POINTER(PqlMlpDesc), _I64]),
-    "pqlk_mlp_forward_td": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _F, _P, _P, _I64, _I32, _P]),
-    "pqlk_mlp_backward_td_tail": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _I32, _P, _I64, _P, _P, _P]),
-    "pqlk_mlp_backward_layers": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _F, _P, _P, _I32, _P, _I64, _I32, _I32, _P]),
-    "pqlk_dpg_backward_ws_floats": (_I64, [C.POINTER(PqlMlpDesc), _I64]),
-    "pqlk_dpg_critic_backward": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _I64, _P]),
-    "pqlk_dpg_fused_ok": (_I32, [C.POINTER(PqlMlpDesc), C.POINTER(PqlMlpDesc), _I64]),
-    "pqlk_dpg_fused_loss_parts": (_I32, []),
-    "pqlk_dpg_fused_head_parts": (_I32, [_I64]),
-    "pqlk_dpg_fused_mn_offset": (_I64, [C.POINTER(PqlMlpDesc), _I64]),
-    "pqlk_mlp_forward_qc": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I32, _P, _I64, _P, _I64, _I32, _I64, _P, _P, _P]),
-    "pqlk_dpg_backward_fused": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _P, _I64, _I32, _P, _I64, _P, _P, _I64,
-                                          C.POINTER(PqlMlpDesc), _P, _P, _P, _I64, _I32, _P]),
-    "pqlk_mlp_backward_tail": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _I64, _I64, _P, _P, _I32, _P, _I64, _P, _P, _I32, _P, _P]),
-    "pqlk_dpg_loss_owner": (C.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _P, _I32, _P, _P, _P]),
-    "pqlk_td_mse_loss": (C.c_int, [_P, _P, _I64, _P, _P, _F, _I64, _P, _P, _P, _I32, _P, _P]),
-    "pqlk_c51_bce_loss": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _F, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P]),
-    "pqlk_c51_project": (C.c_int, [_P, _P, _P, _P, _F, _F, _F, _I32, _I64, _P, _P]),
-    "pqlk_dpg_loss": (C.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _P, _I32, _P, _P]),
-    "pqlk_per_levels": (_I32, [_I64]),
-    "pqlk_per_tree_floats": (_I64, [_I64]),
-    "pqlk_per_insert": (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _P]),
-    "pqlk_per_rebuild": (C.c_int, [_P, _I64, _P]),
-    "pqlk_per_sample": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
-    "pqlk_per_weights": (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _P, _P, _P]),
-    "pqlk_per_sample_steps": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _F, _P, _P, _P, _P]),
-    "pqlk_td_mse_loss_per": (C.c_int, [_P, _P, _I64, _P, _P, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
-    "pqlk_per_update": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _F, _F, _P]),
-    "pqlk_qr_huber_loss": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P]),
-    "pqlk_qr_huber_loss_per": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
-    "pqlk_dpg_loss_quantile": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P, _I32, _P, _P]),
-    "pqlk_tqc_huber_loss": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _I32, _P]),
-    "pqlk_tqc_huber_loss_per": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _P]),
-    "pqlk_tqc_huber_loss_soft": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _I32, _P]),
-    "pqlk_tqc_huber_loss_soft_per": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _F, _F, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _P]),
-    "pqlk_dpg_loss_quantile_mean": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P, _I32, _P, _P]),
-    "pqlk_clip_adamw_polyak": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
-    "pqlk_clip_adamw_polyak_pack": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P]),
-    "pqlk_adamw_polyak_fused": (C.c_int, [C.POINTER(PqlMlpDesc), _P, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _D, _D, _P, _P, _P,
-                                          _I32, _P, _I32, _F, _P, _I32, _P]),
-    "pqlk_loss_parts": (_I32, [_I64, _I32]),
-    "pqlk_polyak": (C.c_int, [_P, _P, _I64, _F, _P]),
-    "pqlk_sg_head_forward": (C.c_int, [_P, _I64, _P, _I64, _I32, _P, _I64, _P, _P]),
-    "pqlk_sg_head_backward": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _P, _F, _I64, _I32, _P, _P]),
-    "pqlk_sac_entropy_shift": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _I64, _P]),
-    "pqlk_sac_alpha_terms": (C.c_int, [_P, _I64, _P, _F, _P, _P, _P, _P, _I32, _P]),
-    "pqlk_bn_elu_forward": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _P, _P, _F, _I32, _F, _P, _P, _P, _P]),
-    "pqlk_bn_elu_backward": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
-    "pqlk_ln_scratch_floats": (_I64, [_I32]),
-    "pqlk_ln_elu_forward": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _F, _P, _P, _P, _P]),
-    "pqlk_ln_elu_backward": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_synth_env_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, C.c_uint32, _F, _P, _P, _P, _P, _P]),
-    "pqlk_pointmass_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_swingup_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_reacher_step": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_pointmass_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_swingup_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_reacher_step_info": (C.c_int, [_I64, _I32, _I32, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_rollout_step": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
-    "pqlk_rollout_info": (C.c_int, [_I64, _P, _I32, _I32, C.POINTER(PqlInfoKey), _P]),
-    "pqlk_batch_moments": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _P, _P]),
-    "pqlk_rms_merge": (C.c_int, [_P, _P, _P, _P, _F, _F, _F, _I32, _P, _P, _P]),
-    "pqlk_rms_normalize": (C.c_int, [_P, _I64, _I32, _P, _P, _F, _P, _I64, _P]),
-    "pqlk_action_noise": (C.c_int, [_P, _P, _P, _F, _I64, _I32, _F, _F, _P, _P]),
-    "pqlk_gae": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I64, C.c_double, C.c_double, _I32, _P, _P, _P]),
-    "pqlk_ppo_gauss_head": (C.c_int, [_P, _I64, _P, _P, _I64, _I32, _P, _I64, _P, _P, _P]),
-    "pqlk_ppo_gather_parts": (_I32, [_I64]),
-    "pqlk_ppo_gather": (C.c_int, [_P, _I64, _I64, _P, _I32, _P, _P, _F, _P, _I64, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pqlk_ppo_scratch_floats": (_I64, [_I64, _I32]),
-    "pqlk_ppo_policy_loss": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, _I64, _I32, _F, _F, _P, _P, _P, _P, _I64, _P, _P, _I32, _P]),
-    "pqlk_ppo_value_loss": (C.c_int, [_P, _I64, _P, _P, _I64, _I32, _F, _P, _I64, _P, _I64, _P, _P, _I32, _P]),
-}
+CONSTANTS, STRUCTS, PROTOTYPES = load_header()   # PROTOTYPES: name -> (restype, argtypes), in the header's order
+globals().update(CONSTANTS)   # PQLK_X -> X: MAX_LAYERS, OBS_*, INFO_*, ACT_*, GATHER_*, STASH_OUTPUT_ONLY, E_*, VERSION, ...
+globals().update(STRUCTS)     # PqlReplayDesc, PqlMlpDesc, PqlInfoKey
 
 
 def _load():

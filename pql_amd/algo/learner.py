@@ -28,7 +28,7 @@ from pql_amd.utils.common import Tracker, load_class_from_path
 LOSS_RING = 5  # Tracker(5) of the reference (:54)
 # gather: +-5 clamp (bit 0); the learners' input tiles are allocated zeroed and nothing else writes their pad columns (bit 1)
 # (PQL_GATHER_FLAGS: A/B switch for the launch-shape / cache-policy bits of include/pqlk.h, tools/ab_bench.sh)
-GATHER_FLAGS = int(os.environ.get("PQL_GATHER_FLAGS", 1 | 2))
+GATHER_FLAGS = int(os.environ.get("PQL_GATHER_FLAGS", L.GATHER_CLAMP5 | L.GATHER_PADS_ZERO))
 # From this bound on torch.randint draws 64-bit indices (another Philox consumption per sample), which the draws made ahead
 # (pql_amd/utils/rng.py) do not reproduce: a ring that large takes the per-step torch draws.
 DRAWS_AHEAD_BOUND = 1 << 28

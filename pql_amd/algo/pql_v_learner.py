@@ -275,7 +275,8 @@ class PQLVLearner(Learner):
                                      algo.noise.tgt_pol_std, algo.noise.tgt_pol_noise_bound, ws["a_out_all"], xn[:, O:])
             else:
                 mlp_forward_raw(self.actor.layout, self.actor.arena.data, xn, L.ACT_TANH_NOISE, draws,
-                                algo.noise.tgt_pol_std, algo.noise.tgt_pol_noise_bound, ws["a_out_all"], xn[:, O:], packed=self.pk_actor, stash_all=2)
+                                algo.noise.tgt_pol_std, algo.noise.tgt_pol_noise_bound, ws["a_out_all"], xn[:, O:], packed=self.pk_actor,
+                                stash_all=L.STASH_OUTPUT_ONLY)
         self._ahead_stamp = self._data_stamp()
 
     def _per_draw(self, ws, r, steps):

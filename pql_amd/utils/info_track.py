@@ -25,8 +25,10 @@ from __future__ import annotations
 
 import torch
 
-MODES = {"last": 0, "all-episode": 1, "all": 1, "all-step": 2}   # -> PqlInfoKey.mode (include/pqlk.h)
-LAST, ALL_EPISODE, ALL_STEP = 0, 1, 2
+from pql_amd import _lib as L
+
+LAST, ALL_EPISODE, ALL_STEP = L.INFO_LAST, L.INFO_ALL_EPISODE, L.INFO_ALL_STEP   # PqlInfoKey.mode (include/pqlk.h)
+MODES = {"last": LAST, "all-episode": ALL_EPISODE, "all": ALL_EPISODE, "all-step": ALL_STEP}
 ALWAYS_OFFERED = ("TimeLimit.truncated",)   # every env of this project reports it
 
 
@@ -112,7 +114,6 @@ class InfoTrackers:
 
     def _update_hip(self, done, entries):
         """`pqlk_rollout_info`: one launch per 8 entries, one block each."""
-        from pql_amd import _lib as L
         with torch.cuda.device(self.device):
             for s in range(0, len(entries), L.INFO_MAX_KEYS):
                 part = entries[s:s + L.INFO_MAX_KEYS]
