@@ -469,7 +469,8 @@ __global__ __launch_bounds__(64 * FUSED_NW) void k_mlp_fwd_fused(FusedP p) {
     const bool defer = pstash && full_tile;
     // (a forward-only call whose output layer is fused needs no HBM copy of the last hidden layer at all)
     const bool keep_last = last && (pstash || p.head_n == 0) && !p.td_dz;   // (the TD head consumes the last hidden layer in LDS: backward never reads it)
-    float* gout = (keep_last || (pstash && !full_tile)) ? pacts + p.a_off[l] + (long long)net * p.B * N : nullptr;
+    const bool td_last = last && p.td_dz;   // ... so a ragged tile, which stashes from the epilogue, leaves that block alone too
+    float* gout = (keep_last || (pstash && !full_tile && !td_last)) ? pacts + p.a_off[l] + (long long)net * p.B * N : nullptr;
     float* gprev = (defer && l > 0) ? pacts + p.a_off[l - 1] + (long long)net * p.B * p.dims[l] : nullptr;
     const int nprev4 = p.dims[l] >> 2;
     const float4* packed_n = last ? nullptr : packed_net + (p.p_off[l + 1] >> 2);

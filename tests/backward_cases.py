@@ -1,4 +1,5 @@
-"""Cases, inputs, references and checks for tests/test_backward_paths_gpu.py (plain numpy, no GPU, no library).
+"""Cases, inputs, references and checks for tests/test_backward_paths_gpu.py and, in the TD family at the end of this file, for
+tests/test_td_paths_gpu.py (plain numpy, no GPU, no library).
 
 pqlk_mlp_backward picks, per call, between three implementations of the output layer's backward (skinny.h), per hidden layer a dW
 and a dX k_gemm in two tile sizes, two main loops and three block orders (gemm.hip), and for the input gradient a GEMM or
@@ -557,12 +558,13 @@ def elu_prime(h):
     return np.where(h > 0, 1.0, h.astype(F64) + 1.0)
 
 
-def _chain(case, dy=None, measure=False):
+def _chain(case, dy=None, measure=False, parts=None):
     """Walks the backward in float64: ({(net, layer): dW}, {(net, layer): db}, dx summed over the nets) and, with measure, one
-    (name, sum_i |t_i| per output element, granularity g of the terms) per product of the chain."""
+    (name, sum_i |t_i| per output element, granularity g of the terms) per product of the chain.  parts: (W, H, x) of a case that
+    brings its own weights, hidden activations and input (the TD family below)."""
     dims, B, L = case.dims, case.B, len(case.dims) - 1
-    W, H = weights(case), hidden(case)
-    x = x_input(case)[:, : dims[0]].astype(F64)
+    W, H, x = parts if parts is not None else (weights(case), hidden(case), x_input(case))
+    x = x[:, : dims[0]].astype(F64)
     dy = dy_input(case) if dy is None else dy
     prods, dW, db, dx = [], {}, {}, np.zeros((B, dims[0]))
     dx_mass, dx_g = np.zeros((B, dims[0])), 0
@@ -758,3 +760,440 @@ def model_backward(case, fault=None):
         out[:rows, : dims[0]] = dx[:rows]
         out[:rows, dims[0]: ld(dims[0])] = 0
     return grads.astype(F32), out
+
+
+# ================================================================ the TD family
+# pqlk_mlp_backward_td (k_skinny_bwd<1, CH, true>), pqlk_mlp_forward_td + pqlk_mlp_backward_td_tail (fused_head's TD part in
+# fused.h), pqlk_mlp_backward_layers with the TD inputs, the squared-norm partials of k_reduce_slabs and the prenorm / loss fold
+# of pqlk_adamw_polyak_fused: the scalar twin critic's step.  tests/test_td_paths_gpu.py runs the cases below, and
+# tests/test_backward_cases_cpu.py holds this mirror against the library and the data against the conditions the `==` rest on.
+#
+# TD inputs: Q and Q' integers in [-2, 2], gamma^n = 0.5, r a multiple of 0.5, done in {0, 1} (one case per path: 0.5 on some
+# rows), so y = r + ((1 - d) gamma^n) min(Q1', Q2'), dq = Q - y and dq^2 are small dyadic rationals.  2.0f / (float)B is exact
+# for B a power of two, and a gradient element is then exactly summable under the same condition as above (`td_exactness_bits`).
+# For any other B the head's dL/dQ is rounded once, dy = float32(2) / float32(B) * dq, and the checks are bit equality with
+# pqlk_mlp_backward fed that dy, plus the bound `head_sum_bound` where the forward path sums the head in other groups.
+from types import SimpleNamespace
+
+GAMMA_N = 0.5
+FUSED_NW = 8                              # pqlk_common.h
+
+
+# ---------------------------------------------------------------- mirror: the fused forward (gemm.hip)
+def fused_lds_bytes(dims, bld, R):
+    """gemm.hip, fused_lds_bytes."""
+    return max((32 * R * bld + (len(dims) - 2) * (bld - 4)) * 4, 8 * R * 16 * 64 * 4)
+
+
+def buf_ld(dims):
+    """gemm.hip, fusable: the row stride of the LDS activation tile, max(ld(in), hidden widths) + 4; 0 when not fusable."""
+    if len(dims) < 3 or any(d % 32 != 0 or d > 1024 for d in dims[1:-1]):
+        return 0
+    bld = max([ld(dims[0])] + list(dims[1:-1])) + 4
+    return bld if fused_lds_bytes(dims, bld, 1) <= LDS_BYTES else 0
+
+
+def head_fusable(dims):
+    """gemm.hip, head_fusable."""
+    return len(dims) >= 3 and dims[-1] <= 32 and dims[-2] % 32 == 0
+
+
+def fused_rows(dims, nets, B):
+    """gemm.hip, fused_rows (PQLK_FUSED_ROWS unset): R, the 32-row tiles per block of k_mlp_fwd_fused."""
+    bld = buf_ld(dims)
+    wide = any(d > 512 for d in dims[1:-1])
+    if not wide and fused_lds_bytes(dims, bld, 2) <= LDS_BYTES:
+        b1, b2 = cdiv(B, 32) * nets, cdiv(B, 64) * nets
+        if 2.0 * cdiv(b2, 256) <= 1.15 * cdiv(b1, 256):
+            return 2
+    return 1
+
+
+def fwd_kernel(dims, nets, B):
+    """gemm.hip, launch_fused_hidden: (R, TM) of k_mlp_fwd_fused<R, TM>."""
+    return fused_rows(dims, nets, B), (4 if any(d > 512 for d in dims[1:-1]) else 2)
+
+
+def td_forward_tiles(dims, nets, B):
+    """gemm.hip, td_forward_tiles (PQLK_NO_FUSED_HEAD unset)."""
+    bld = buf_ld(dims)
+    if B <= 0 or not bld or not head_fusable(dims):
+        return 0
+    if nets != 2 or dims[-1] != 1 or not head_is_fused(dims):
+        return 0
+    if bld - dims[-2] < 256 or (len(dims) - 2) * (bld - 4) < 128:
+        return 0
+    return cdiv(B, 32 * fused_rows(dims, nets, B))
+
+
+def td_forward_loss_parts(dims, nets, B):
+    """gemm.hip, pqlk_td_forward_loss_parts."""
+    return td_forward_tiles(dims, nets, B) * nets
+
+
+def td_head_loss_parts(dims, nets, B):
+    """gemm.hip, pqlk_td_head_loss_parts."""
+    if B <= 0 or nets != 2 or dims[-1] != 1 or not head_is_fused(dims):
+        return 0
+    return skinny_bwd_blocks(B, nets) * nets
+
+
+# ---------------------------------------------------------------- the tables
+TdCase = namedtuple("TdCase", "name dims B splits path data")
+# path "bwd": the stash is an input (pqlk_mlp_backward_td, pqlk_mlp_backward_layers + TD, pqlk_mlp_backward_norm)
+# path "fwd": the forward is real (pqlk_mlp_forward_td + pqlk_mlp_backward_td_tail) on the exactly evaluable network below
+# data "std" | "half" (done = 0.5 on some rows) | "int" (B = 8, dq a multiple of 4: integer gradients) | "head_only" ("int"
+# with an all-dead last hidden layer: only the head's dW / db are non-zero)
+_TD_BWD = [
+    # CH = 1, tiny dims: a lone row, 15 | 16 | 17 on 16-row blocks, the 16 | 32 and 32 | 64 switches of skinny_bwd_rows with a ragged
+    # last block behind each, and the power of two on 32-row blocks
+    ([8, 32, 1], 1, "std"), ([8, 32, 1], 15, "std"), ([8, 32, 1], 16, "std"), ([8, 32, 1], 17, "std"),
+    ([8, 32, 1], 4097, "std"),
+    ([8, 32, 1], B_ROWS32 - 1, "std"), ([8, 32, 1], B_ROWS32, "std"), ([8, 32, 1], 8192, "std"),
+    ([8, 32, 1], B_ROWS64 - 1, "std"), ([8, 32, 1], B_ROWS64, "std"),
+    # CH = 2 (ld 288, 512) and CH = 4 (ld 1024)
+    ([8, 288, 1], 16, "std"), ([8, 288, 1], 33, "std"), ([8, 512, 1], 32, "std"),
+    ([8, 1024, 1], 16, "std"), ([8, 1024, 1], 65, "std"),
+    # hidden layers below the head
+    ([8, 64, 32, 1], 128, "half"), ([8, 64, 32, 1], 95, "std"), ([8, 64, 288, 1], 64, "std"),
+    # integer gradients: the squared-norm partials
+    ([8, 64, 32, 1], 8, "int"), ([8, 64, 32, 1], 8, "head_only"), ([8, 32, 288, 1], 8, "int"),
+]
+_TD_FWD = [
+    # R = 1, Kh = 32: a lone row, 31 | 32 | 33, two and three tiles; R = 2 at its first batch (the last 64-row tile holds one row)
+    # and at 8192
+    ([8, 288, 32, 1], 1, "std"), ([8, 288, 32, 1], 31, "std"), ([8, 288, 32, 1], 32, "std"), ([8, 288, 32, 1], 33, "std"),
+    ([8, 288, 32, 1], 65, "std"), ([8, 288, 32, 1], 95, "std"), ([8, 288, 32, 1], 4097, "std"), ([8, 288, 32, 1], 8192, "std"),
+    ([8, 288, 32, 1], 8, "int"),
+    # Kh = 256; Kh = 288 (two chunks of the quad loop) under TM = 4 and under TM = 2; an input wider than every hidden layer
+    ([8, 512, 256, 1], 32, "std"), ([8, 512, 256, 1], 33, "std"),
+    ([8, 544, 288, 1], 64, "std"), ([8, 544, 288, 1], 33, "std"),
+    ([540, 32, 288, 1], 16, "std"),
+    ([300, 64, 64, 1], 32, "half"), ([300, 64, 64, 1], 33, "std"),
+]
+TD_TAKEN, TD_REFUSED = [8, 288, 32, 1], [8, 256, 32, 1]     # buf_ld - Kh = 260 | 228: the eligibility edge of the forward path
+
+
+def _td_name(dims, B, path, data):
+    return "x".join(str(d) for d in dims) + f"-B{B}-{path}" + ("" if data == "std" else f"-{data}")
+
+
+TD_CASES = [TdCase(_td_name(dims, B, path, data), list(dims), B, default_splits(B), path, data)
+            for path, table in (("bwd", _TD_BWD), ("fwd", _TD_FWD)) for dims, B, data in table]
+TD_BY_NAME = {c.name: c for c in TD_CASES}
+assert len(TD_BY_NAME) == len(TD_CASES)
+TD_BWD_NAMES = [c.name for c in TD_CASES if c.path == "bwd"]
+TD_FWD_NAMES = [c.name for c in TD_CASES if c.path == "fwd"]
+# the kernel instances the tables must reach (the CPU test holds the union against these)
+TD_BWD_INSTANCES = [(1, 16), (1, 32), (1, 64), (2, 16), (4, 16)]        # (CH, rows per block) of k_skinny_bwd<1, CH, true>
+TD_FWD_INSTANCES = [(1, 2), (2, 2), (1, 4)]                              # (R, TM) of k_mlp_fwd_fused<R, TM>
+# rows on which the buckets of pqlk_mlp_backward_layers are held against the single pqlk_mlp_backward_td call
+TD_LAYERS_NAMES = ["8x32x1-B17-bwd", "8x64x32x1-B128-bwd-half", "8x64x32x1-B95-bwd", "8x64x288x1-B64-bwd"]
+# rows whose squared-norm partials are summed: integer gradients (bwd), dyadic ones with exact squares (fwd)
+TD_NORM_BWD_NAMES = ["8x64x32x1-B8-bwd-int", "8x64x32x1-B8-bwd-head_only", "8x32x288x1-B8-bwd-int"]
+TD_NORM_FWD_NAMES = ["8x288x32x1-B8-fwd-int"]
+NORM_PLAIN_DIMS = [8, 512, 16]            # a non-fused head (16 outputs on K = 512) for pqlk_mlp_backward_norm
+
+
+def is_pow2(B):
+    return B & (B - 1) == 0
+
+
+def td_instance(tc):
+    """The kernel instance a case reaches: (CH, rows per block) on path "bwd", (R, TM) on path "fwd"."""
+    if tc.path == "bwd":
+        return skinny_bwd_ch(ld(tc.dims[-2])), skinny_bwd_rows(tc.B, 2)
+    return fwd_kernel(tc.dims, 2, tc.B)
+
+
+def td_as_case(tc):
+    return Case(tc.name, list(tc.dims), 2, tc.B, tc.splits, "g", 0, 0, ld(tc.dims[0]), ())
+
+
+# ---------------------------------------------------------------- an exactly evaluable network (path "fwd")
+GATE = 48                                 # x[:, 0] on the rows whose gated units of layer 0 are dead
+
+
+def exact_network(case, twin=False):
+    """(W, bias, x): weights over {-1, 0, 1} with one or two non-zeros per hidden unit, integer biases, integer x, such that
+    every hidden pre-activation is an integer >= 0 or <= -32 whatever the row: ELU gives z itself or (__expf(z) - 1.f = ) -1
+    exactly, ELU' 1 or 0.  Units j % 4 == 3 are dead on every row (bias below -32 minus the largest sum), units j % 4 == 2 of
+    layer 0 are dead on the rows with x[:, 0] = GATE (rows b % 4 == 1) and alive elsewhere, the others are alive: the bias lifts
+    the smallest possible sum to 0.  The head has dims[-2] / 8 non-zero weights and a small integer bias.  twin: both nets hold
+    net 0's weights and the head biases differ by 4, so that Q2 = Q1 + 4 on every row (data "int": dq a multiple of 4 on both)."""
+    dims, B, L = case.dims, case.B, len(case.dims) - 1
+    x = x_input(case)
+    x[:, 0] = np.where(np.arange(B) % 4 == 1, GATE, 0)
+    Ws, bs = [], []
+    for net in range(case.nets):
+        n = 0 if twin else net
+        lo, hi = -2, 2                                             # range of the layer's inputs
+        Wn, bn = [], []
+        for l in range(L - 1):
+            N, K = dims[l + 1], dims[l]
+            first = 1 if l == 0 else 0                             # column 0 of x is the gate
+            k1 = dd.integers((N,), _seed(case, 11, n, l), K - first) + first
+            k2 = dd.integers((N,), _seed(case, 12, n, l), K - first) + first
+            sg = dd.integers((N, 2), _seed(case, 13, n, l), 2) * 2 - 1
+            two = (dd.integers((N,), _seed(case, 14, n, l), 2) == 1) & (k1 != k2)
+            W = np.zeros((N, K), dtype=F32)
+            W[np.arange(N), k1] = sg[:, 0]
+            W[np.arange(N)[two], k2[two]] = sg[two, 1]
+            pos, neg = (W > 0).sum(1), (W < 0).sum(1)
+            smin, smax = pos * lo - neg * hi, pos * hi - neg * lo
+            dead = np.arange(N) % 4 == 3
+            b = np.where(dead, -32 - smax, -smin).astype(F32)
+            if l == 0:
+                gated = np.arange(N) % 4 == 2
+                assert (smax - smin)[gated].max() <= GATE - 32
+                W[gated, 0] = -1
+            Wn.append(W); bn.append(b)
+            lo, hi = -1, int((smax - smin)[~dead].max())
+        Kh = dims[L - 1]
+        W = np.zeros((1, Kh), dtype=F32)
+        at = 8 * np.arange(Kh // 8) + dd.integers((Kh // 8,), _seed(case, 15, n), 8)
+        W[0, at] = dd.integers((Kh // 8,), _seed(case, 16, n), 2) * 2 - 1
+        Wn.append(W); bn.append(np.array([4 * net if twin else net - 1], dtype=F32))
+        Ws.append(Wn); bs.append(bn)
+    return Ws, bs, x
+
+
+def exact_forward(case, W, bias, x):
+    """float64: ([net][layer] hidden pre-activations z, [net][layer] hidden activations h as float32, Q (nets, B))."""
+    dims, L = case.dims, len(case.dims) - 1
+    Z, H, Q = [], [], np.zeros((case.nets, case.B))
+    for n in range(case.nets):
+        a, zn, hn = x[:, : dims[0]].astype(F64), [], []
+        for l in range(L - 1):
+            z = a @ W[n][l].astype(F64).T + bias[n][l].astype(F64)
+            a = np.where(z >= 0, z, -1.0)
+            zn.append(z); hn.append(a.astype(F32))
+        Z.append(zn); H.append(hn)
+        Q[n] = (a @ W[n][L - 1].astype(F64).T + bias[n][L - 1].astype(F64))[:, 0]
+    return Z, H, Q
+
+
+# ---------------------------------------------------------------- TD inputs and the problem of one case
+HINT = np.array([2, 1, 0, -1], dtype=F32)                          # integer activations: ELU' = 1, 1, 1, 0
+
+
+def _td_targets(case, data):
+    """(qt (2, B), rew, done): row b % 3 == 0 has net 1 as the minimum, 1 is a tie, 2 has net 0."""
+    B, pat = case.B, np.arange(case.B) % 3
+    qt = np.zeros((2, B))
+    qt[0] = rc.ints((B,), _seed(case, 21), -1, 1)
+    qt[1] = qt[0] + np.where(pat == 0, -1, np.where(pat == 1, 0, 1))
+    rew = rc.ints((B,), _seed(case, 22), -4, 4).astype(F64) * 0.5
+    done = (dd.integers((B,), _seed(case, 23), 4) == 0).astype(F64)
+    if data == "half":
+        done[np.arange(B) % 5 == 2] = 0.5
+    return qt, rew, done
+
+
+@functools.lru_cache(maxsize=6)
+def td_problem(name):
+    """Everything of one TD case, float64 unless said: case, W, bias (fwd; None on path bwd, whose arena holds 1.0), H (float32),
+    x (float32), q, qt (2, B), rew, done, y, dq (2, B), dy (2, B, 32) float32 = float32(2) / float32(B) * dq."""
+    tc = TD_BY_NAME[name]
+    case = td_as_case(tc)
+    B, L = tc.B, len(tc.dims) - 1
+    qt, rew, done = _td_targets(case, tc.data)
+    cmin = ((1.0 - done) * GAMMA_N) * np.minimum(qt[0], qt[1])
+    if tc.path == "fwd":
+        W, bias, x = exact_network(case, twin=tc.data == "int")
+        _, H, q = exact_forward(case, W, bias, x)
+        if tc.data == "int":                                       # Q2 = Q1 + 4: dq = 4 k on net 0, 4 k + 4 on net 1
+            assert B == 8 and np.array_equal(q[1], q[0] + 4)
+            rew = q[0] - 4.0 * rc.ints((B,), _seed(case, 25), -1, 1) - cmin
+    else:
+        W, bias, x = weights(case), None, x_input(case)
+        if tc.data in ("int", "head_only"):
+            H = [[HINT[dd.integers((B, tc.dims[l + 1]), _seed(case, 2, n, l), len(HINT))] for l in range(L - 1)] for n in range(2)]
+            if tc.data == "head_only":
+                for n in range(2):
+                    H[n][L - 2][:] = -1
+            assert B == 8                                          # dq a multiple of B / 2 = 4 on both nets: Q1 - Q2 in {0, +-4}
+            q = np.zeros((2, B))
+            q[0] = rc.ints((B,), _seed(case, 24), -2, 2)
+            q[1] = np.where(np.abs(q[0]) == 2, -q[0], q[0])
+            rew = q[0] - 4.0 * rc.ints((B,), _seed(case, 25), -1, 1) - cmin
+        else:
+            H = hidden(case)
+            q = rc.ints((2, B), _seed(case, 24), -2, 2).astype(F64)
+    y = rew + cmin
+    dq = q - y[None, :]
+    dy = np.zeros((2, B, 32), dtype=F32)
+    dy[:, :, 0] = (F32(2) / F32(B)) * dq.astype(F32)
+    assert np.array_equal(dq.astype(F32).astype(F64), dq)
+    p = SimpleNamespace(tc=tc, case=case, W=W, bias=bias, H=H, x=x, q=q, qt=qt, rew=rew, done=done, y=y, dq=dq, dy=dy)
+    for v in [x, q, qt, rew, done, y, dq, dy] + [h for net in H for h in net]:
+        v.setflags(write=False)
+    return p
+
+
+def td_arena(p):
+    """The parameter arena of a TD case: as `arena`, with the network's own biases on path "fwd"."""
+    out = arena(p.case) if p.bias is None else np.zeros(net_stride(p.case.dims) * 2, dtype=F32)
+    if p.bias is not None:
+        dims, ns = p.case.dims, net_stride(p.case.dims)
+        for n in range(2):
+            for l, w in enumerate(p.W[n]):
+                wo, bo = layer_offsets(dims, l)
+                out[n * ns + wo: n * ns + bo].reshape(dims[l + 1], ld(dims[l]))[:, : dims[l]] = w
+                out[n * ns + bo: n * ns + bo + dims[l + 1]] = p.bias[n][l]
+    return out
+
+
+def td_stash(p, last_hidden=True):
+    """The online stash: hidden blocks with zero pads, Q in column 0 of the output block and zeros beside it.  On path "fwd" this
+    is what the forward must leave; last_hidden = False leaves the last hidden layer's block NaN (pqlk_mlp_forward_td)."""
+    dims, B = p.case.dims, p.case.B
+    out = np.zeros(acts_floats(dims, 2, B), dtype=F32)
+    for n in range(2):
+        for l, h in enumerate(p.H[n]):
+            off, ldh = act_offset(dims, 2, B, n, l)
+            blk = out[off: off + B * ldh].reshape(B, ldh)
+            blk[:, : dims[l + 1]] = h
+            if l == len(dims) - 3 and not last_hidden:
+                blk[:] = np.nan
+    off, ldo = act_offset(dims, 2, B, 0, len(dims) - 2)
+    out[off:].reshape(2, B, ldo)[:, :, 0] = p.q
+    return out
+
+
+def td_target_stash(p):
+    """The target critic's stash: NaN but for Q' in column 0 of the output block -- nothing else of it may be read."""
+    dims, B = p.case.dims, p.case.B
+    out = np.full(acts_floats(dims, 2, B), np.nan, dtype=F32)
+    off, ldo = act_offset(dims, 2, B, 0, len(dims) - 2)
+    out[off:].reshape(2, B, ldo)[:, :, 0] = p.qt
+    return out
+
+
+def _arena_of(dims, dW, db):
+    ns = net_stride(dims)
+    grads = np.zeros(ns * 2, dtype=F64)
+    for (n, l), g in dW.items():
+        wo, bo = layer_offsets(dims, l)
+        grads[n * ns + wo: n * ns + bo].reshape(dims[l + 1], ld(dims[l]))[:, : dims[l]] = g
+        grads[n * ns + bo: n * ns + bo + dims[l + 1]] = db[n, l]
+    return grads
+
+
+@functools.lru_cache(maxsize=6)
+def td_reference(name):
+    """float64, read-only: "grads" (arena layout) of the chain fed p.dy, "head_mass" (arena layout) sum_b |dy_b h_bk| on the
+    head's elements (0 elsewhere), "sumsq" sum g^2."""
+    p = td_problem(name)
+    dims, L = p.case.dims, len(p.case.dims) - 1
+    _, dW, db, _ = _chain(p.case, p.dy, parts=(p.W, p.H, p.x))
+    grads = _arena_of(dims, dW, db)
+    ady = np.abs(p.dy[:, :, :1].astype(F64))
+    mass = _arena_of(dims, {(n, L - 1): ady[n].T @ np.abs(p.H[n][L - 2].astype(F64)) for n in range(2)},
+                     {(n, L - 1): ady[n].sum(0) for n in range(2)})
+    out = {"grads": grads, "head_mass": mass, "sumsq": float((grads * grads).sum())}
+    grads.setflags(write=False); mass.setflags(write=False)
+    return out
+
+
+def head_range(dims, net):
+    """[start, end) of a net's head block (W row, then the bias block) in the arena."""
+    ns = net_stride(dims)
+    wo, _ = layer_offsets(dims, len(dims) - 2)
+    return net * ns + wo, (net + 1) * ns
+
+
+def head_sum_bound(p, ref):
+    """(B + 8) 2^-24 sum_b |dy_b h_bk| per arena element: the standard bound on an fp32 sum of B products taken in any order
+    against its float64 value (each product and each of at most B - 1 additions rounds once; 8 spare roundings for the fold of
+    partials)."""
+    return (p.case.B + 8) * 2.0 ** -24 * ref["head_mass"]
+
+
+def td_loss_parts(name):
+    """float64 sum of dq^2 per (row block, net), in the order the kernels leave them: [block][net].  Row blocks of
+    skinny_bwd_rows(B, 2) rows on path "bwd", of 32 R rows on path "fwd"."""
+    p = td_problem(name)
+    rows = skinny_bwd_rows(p.case.B, 2) if p.tc.path == "bwd" else 32 * fused_rows(p.case.dims, 2, p.case.B)
+    sq = p.dq * p.dq
+    return np.array([sq[n, r0: r0 + rows].sum() for r0 in range(0, p.case.B, rows) for n in range(2)])
+
+
+def td_exactness_bits(name):
+    """`exactness_bits` of the chain fed p.dy, and of the loss partials: log2 of the largest partial times 2^(2 g), g the
+    granularity of dq."""
+    p = td_problem(name)
+    prods, _, _, _ = _chain(p.case, p.dy, measure=True, parts=(p.W, p.H, p.x))
+    worst = 0.0
+    for _, mass, g in prods:
+        if mass.size and mass.max() > 0:
+            worst = max(worst, float(np.log2(mass.max() * 2.0 ** g)))
+    parts = td_loss_parts(name)
+    return worst, float(np.log2(max(parts.max(), 2.0 ** -40) * 4.0 ** _gran(p.dq)))
+
+
+def sumsq_bits(grads):
+    """log2 of sum (g 2^k)^2, k the granularity of the gradient: at most 24 means every g^2 and every partial sum of them in any
+    order or grouping is exact in fp32.  Returns (bits, k)."""
+    k = _gran(grads)
+    return float(np.log2(max(float(((grads * 2.0 ** k) ** 2).sum()), 1.0))), k
+
+
+def norm_plain_case():
+    """pqlk_mlp_backward_norm on a non-fused head: 16 outputs on K = 512, integer stash, integer dy."""
+    return Case("8x512x16-n2-B16-norm", list(NORM_PLAIN_DIMS), 2, 16, 1, "g", 0, 0, 32, ())
+
+
+def norm_plain_parts(case):
+    """(W, H, x) with integer activations for `norm_plain_case`."""
+    H = [[HINT[dd.integers((case.B, case.dims[l + 1]), _seed(case, 2, n, l), len(HINT))] for l in range(len(case.dims) - 2)]
+         for n in range(case.nets)]
+    return weights(case), H, x_input(case)
+
+
+def norm_plain_stash(case):
+    _, H, _ = norm_plain_parts(case)
+    out = np.zeros(acts_floats(case.dims, case.nets, case.B), dtype=F32)
+    for n in range(case.nets):
+        for l, h in enumerate(H[n]):
+            off, ldh = act_offset(case.dims, case.nets, case.B, n, l)
+            out[off: off + case.B * ldh].reshape(case.B, ldh)[:, : case.dims[l + 1]] = h
+    off, _ = act_offset(case.dims, case.nets, case.B, 0, len(case.dims) - 2)
+    out[off:] = np.nan
+    return out
+
+
+def norm_plain_reference(case):
+    _, dW, db, _ = _chain(case, dy_input(case), parts=norm_plain_parts(case))
+    return _arena_of(case.dims, dW, db)
+
+
+# ---------------------------------------------------------------- operand order (B = 1, values that are no dyadic rationals)
+# found by search: with these, forming (1 - d) (gamma^n min Q') instead of ((1 - d) gamma^n) min Q', or contracting the product
+# and the addition of r into one fma, moves the last bit of the head's db for the Q of either path (the CPU test holds that)
+ORDER = dict(gamma_n=0.99, rew=-0.7488293647766113, done=0.16398358345031738, qt=(-1.7941311597824097, -2.2908599376678467),
+             q=(-1.8804951906204224, -0.17266710102558136))
+ORDER_BWD_NAME, ORDER_FWD_NAME = "8x32x1-B1-bwd", "8x288x32x1-B1-fwd"
+
+
+def td_db_in_order(q, order="documented"):
+    """The head's db at B = 1 (2.0f / B = 2) for Q = q in numpy float32: 2 (Q - (r + ((1 - d) gamma^n) min(Q1', Q2'))) in that
+    order, or in one of the two orders it must not be taken in."""
+    r, d, g = F32(ORDER["rew"]), F32(ORDER["done"]), F32(ORDER["gamma_n"])
+    t = np.minimum(F32(ORDER["qt"][0]), F32(ORDER["qt"][1]))
+    if order == "documented":
+        y = F32(r + F32(F32(F32(1) - d) * g) * t)
+    elif order == "gamma_first":
+        y = F32(r + F32(F32(1) - d) * F32(g * t))
+    else:                                                          # "fma": the product is not rounded before r is added
+        y = F32(F64(r) + F64(F32(F32(F32(1) - d) * g)) * F64(t))
+    return F32(F32(2) * F32(F32(q) - y))
+
+
+def order_problem(name):
+    """The one-row problem of `name` with the TD inputs of ORDER (and, on path "bwd", its Q)."""
+    p = td_problem(name)
+    q = p.q if p.tc.path == "fwd" else np.array([[F32(v)] for v in ORDER["q"]], dtype=F64)
+    qt = np.array([[F32(v)] for v in ORDER["qt"]], dtype=F64)
+    rew, done = np.array([F32(ORDER["rew"])], dtype=F64), np.array([F32(ORDER["done"])], dtype=F64)
+    return SimpleNamespace(tc=p.tc, case=p.case, W=p.W, bias=p.bias, H=p.H, x=p.x, q=q, qt=qt, rew=rew, done=done, dq=p.dq, dy=p.dy)

@@ -2,7 +2,9 @@
 agrees with the library wherever the library lets it be asked, every row reaches the launches it names and the union of the
 rows' plans is the declared list, the threshold batches are minimal, every row satisfies the exactness condition the equality
 asserts rest on, the stashes exercise every branch of ELU', and the checks fail on the wrong results they are there to catch.
-No GPU needed."""
+The same for the TD family (tests/test_td_paths_gpu.py): the mirror of the fused forward's and the TD entries' dispatch against
+the library's host-only counts, the kernel instances the tables reach, the data rules, exact summability, and the exactly
+evaluable network of the forward path.  No GPU needed."""
 import ctypes as C
 import os
 
@@ -329,3 +331,203 @@ def test_gpu_module_skips_nothing_and_has_no_tolerance():
     src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_backward_paths_gpu.py")).read()
     for word in ("skip", "xfail", "importorskip", "rtol", "atol", "allclose", "assert_close"):
         assert word not in src, word
+
+
+# =========================================================================== the TD family (tests/test_td_paths_gpu.py)
+_TD_EXTRA_DIMS = [bc.TD_TAKEN, bc.TD_REFUSED, [8, 32, 32, 1], [8, 1024, 32, 1], [8, 1056, 32, 1], [8, 100, 32, 1], [8, 288, 32, 2],
+                  [8, 288, 36, 1], [8, 128, 1], [8, 288, 1], [8, 640, 32, 1], [620, 32, 288, 1], [8, 288, 288, 32, 1],
+                  [104, 512, 512, 256, 1], [8, 288, 32, 17]]
+_TD_EXTRA_B = [1, 31, 32, 33, 63, 64, 65, 4095, 4096, 4097, 8160, 8161, 8191, 8192, 8193, 16320, 16321, 16384, 16385]
+
+
+def _td_dims():
+    seen = []
+    for dims in [c.dims for c in bc.TD_CASES] + _TD_EXTRA_DIMS + [bc.NORM_PLAIN_DIMS]:
+        if dims not in seen:
+            seen.append(dims)
+    return seen
+
+
+def test_td_mirror_agrees_with_the_library():
+    """pqlk_td_forward_loss_parts (fusable / buf_ld, fused_lds_bytes, fused_rows, td_forward_tiles), pqlk_td_head_loss_parts
+    (skinny_bwd_blocks) and pqlk_mlp_norm_parts over every TD case and a sweep across the edges: buf_ld - Kh = 256, one hidden
+    layer, a width over 1024 or no multiple of 32, two outputs, the R = 1 | 2 switch at 4096 | 4097, a tile too wide for R = 2, the
+    16 | 32 | 64-row switches of k_skinny_bwd."""
+    from pql_amd import _lib as L
+    fwd, head, rows2 = set(), set(), set()
+    for dims in _td_dims():
+        for nets in (1, 2):
+            d = L.mlp_desc(dims, nets)
+            assert int(L.lib.pqlk_mlp_norm_parts(C.byref(d))) == bc.norm_parts(dims, nets), (dims, nets)
+            for B in _TD_EXTRA_B + [c.B for c in bc.TD_CASES if c.dims == dims]:
+                got = int(L.lib.pqlk_td_forward_loss_parts(C.byref(d), B))
+                assert got == bc.td_forward_loss_parts(dims, nets, B), (dims, nets, B)
+                fwd.add(got > 0)
+                if got:
+                    rows2.add(bc.fused_rows(dims, nets, B))
+                got = int(L.lib.pqlk_td_head_loss_parts(C.byref(d), B))
+                assert got == bc.td_head_loss_parts(dims, nets, B) == (bc.skinny_bwd_blocks(B, 2) * 2 if got else 0), (dims, nets, B)
+                head.add(got > 0)
+    assert fwd == {True, False} and head == {True, False} and rows2 == {1, 2}
+    # the edges themselves
+    assert bc.buf_ld(bc.TD_TAKEN) - bc.TD_TAKEN[-2] == 260 and bc.buf_ld(bc.TD_REFUSED) - bc.TD_REFUSED[-2] == 228
+    assert bc.td_forward_tiles(bc.TD_TAKEN, 2, 33) == 2 and bc.td_forward_tiles(bc.TD_REFUSED, 2, 33) == 0
+    assert bc.buf_ld([300, 64, 64, 1]) == 324 and bc.buf_ld([8, 1056, 32, 1]) == 0 and bc.buf_ld([8, 100, 32, 1]) == 0
+    assert bc.fused_rows(bc.TD_TAKEN, 2, 4096) == 1 and bc.fused_rows(bc.TD_TAKEN, 2, 4097) == 2 and bc.fused_rows(bc.TD_TAKEN, 2, 8192) == 2
+    assert bc.fused_rows(bc.TD_TAKEN, 2, 8193) == 1
+    assert bc.fused_rows([620, 32, 288, 1], 2, 8192) == 1 and bc.td_forward_tiles([620, 32, 288, 1], 2, 8192) == 256
+    assert bc.td_forward_tiles(bc.TD_TAKEN, 1, 33) == 0 and bc.td_forward_tiles([8, 288, 32, 2], 2, 33) == 0
+    assert bc.td_head_loss_parts([8, 32, 1], 2, 8160) == 1020 and bc.td_head_loss_parts([8, 32, 1], 2, 8161) == 512
+    assert bc.td_head_loss_parts([8, 32, 1], 2, 16320) == 1020 and bc.td_head_loss_parts([8, 32, 1], 2, 16321) == 512
+    assert bc.td_head_loss_parts([8, 1056, 1], 2, 16) == 0 and bc.td_head_loss_parts([8, 32, 2], 2, 16) == 0
+
+
+def test_td_tables_reach_every_kernel_instance():
+    bwd = [c for c in bc.TD_CASES if c.path == "bwd"]
+    fwd = [c for c in bc.TD_CASES if c.path == "fwd"]
+    assert {bc.td_instance(c) for c in bwd} == set(bc.TD_BWD_INSTANCES)
+    assert {bc.td_instance(c) for c in fwd} == set(bc.TD_FWD_INSTANCES)
+    for c in bc.TD_CASES:
+        d = c.dims
+        assert c.splits == bc.default_splits(c.B) and bc.td_head_loss_parts(d, 2, c.B) > 0, c.name
+        assert c.path == "bwd" or bc.td_forward_loss_parts(d, 2, c.B) > 0, c.name
+    # k_skinny_bwd<1, CH, true>: CH by the last hidden ld; every row count with a whole and with a ragged last block
+    assert {bc.ld(c.dims[-2]) for c in bwd} >= {32, 288, 512, 1024}
+    assert {c.B for c in bwd} >= {1, 15, 16, 17, 8160, 8161, 8192, 16320, 16321} and max(c.B for c in bc.TD_CASES) == 16321
+    for rows in (16, 32, 64):
+        mine = [c for c in bwd if bc.td_instance(c)[1] == rows]
+        assert any(c.B % rows for c in mine), rows
+    assert any(bc.td_instance(c) == (1, 32) and bc.is_pow2(c.B) for c in bwd)
+    # k_mlp_fwd_fused: R = 1 at 1, 31, 32, 33; R = 2 at its first batch (one row in the last 64-row tile) and at 8192; TM = 4; the
+    # last hidden widths; two chunks of the head-backward quad loop under both TM; an input wider than every hidden layer
+    r1 = {c.B for c in fwd if bc.td_instance(c) == (1, 2) and c.dims == bc.TD_TAKEN}
+    assert r1 >= {1, 31, 32, 33} and {c.B for c in fwd if bc.td_instance(c)[0] == 2} == {4097, 8192} and 4097 % 64 == 1
+    assert {c.dims[-2] for c in fwd} == {32, 64, 256, 288}
+    assert {bc.td_instance(c)[1] for c in fwd if c.dims[-2] // 4 > 64} == {2, 4}
+    assert any(bc.ld(c.dims[0]) > max(c.dims[1:-1]) for c in fwd)
+    # section 4's batches on both paths; done = 0.5 on both paths
+    for path in (bwd, fwd):
+        assert {c.B for c in path} >= {33, 65, 95, 4097}
+        assert any(c.data == "half" for c in path)
+    for names in (bc.TD_LAYERS_NAMES, bc.TD_NORM_BWD_NAMES, bc.TD_NORM_FWD_NAMES):
+        assert all(n in bc.TD_BY_NAME for n in names)
+    assert any(len(bc.TD_BY_NAME[n].dims) == 3 for n in bc.TD_LAYERS_NAMES) and any(len(bc.TD_BY_NAME[n].dims) == 4 for n in bc.TD_LAYERS_NAMES)
+    assert any(not bc.is_pow2(bc.TD_BY_NAME[n].B) for n in bc.TD_LAYERS_NAMES)
+
+
+@pytest.mark.parametrize("name", [c.name for c in bc.TD_CASES])
+def test_td_case_holds_the_data_rules_and_is_exactly_summable(name):
+    """Q' integers in [-2, 2] with ties and rows where net 1 is the minimum, gamma^n = 0.5, r a multiple of 0.5, done in {0, 1} (or
+    0.5 where the case says so); on path "bwd" Q integers in [-2, 2]; every loss partial exactly summable; for B a power of two
+    every gradient element exactly summable (at most 24 bits), dy = 2 / B dq exact."""
+    p, tc = bc.td_problem(name), bc.TD_BY_NAME[name]
+    assert bc.GAMMA_N == 0.5
+    assert np.array_equal(p.qt, np.round(p.qt)) and np.abs(p.qt).max() <= 2
+    tie, net1 = p.qt[0] == p.qt[1], p.qt[1] < p.qt[0]
+    assert net1[0] and (tc.B < 3 or (tie.any() and net1.any() and (p.qt[0] < p.qt[1]).any()))
+    assert np.array_equal(p.rew * 2, np.round(p.rew * 2))
+    assert set(np.unique(p.done)) <= ({0.0, 0.5, 1.0} if tc.data == "half" else {0.0, 1.0})
+    assert tc.data != "half" or {0.0, 0.5, 1.0} == set(np.unique(p.done))
+    assert tc.B < 16 or {0.0, 1.0} <= set(np.unique(p.done))
+    assert np.array_equal(p.q, np.round(p.q))
+    if tc.path == "bwd":
+        assert np.abs(p.q).max() <= 2
+    assert np.array_equal(p.y, p.rew + ((1.0 - p.done) * 0.5) * np.minimum(p.qt[0], p.qt[1])) and np.array_equal(p.dq, p.q - p.y)
+    bits, loss_bits = bc.td_exactness_bits(name)
+    assert loss_bits <= 24
+    parts = bc.td_loss_parts(name)
+    n_parts = bc.td_head_loss_parts(tc.dims, 2, tc.B) if tc.path == "bwd" else bc.td_forward_loss_parts(tc.dims, 2, tc.B)
+    assert len(parts) == n_parts and parts.sum() == (p.dq ** 2).sum()
+    assert np.log2(max(parts.sum(), 1.0) * 4.0 ** bc._gran(p.dq)) <= 24          # ... and so is their fold
+    if bc.is_pow2(tc.B):
+        assert bits <= 24
+        assert np.array_equal(p.dy[:, :, 0].astype(np.float64), 2.0 / tc.B * p.dq)
+    assert np.all(p.dy[:, :, 1:] == 0)
+
+
+@pytest.mark.parametrize("name", bc.TD_FWD_NAMES)
+def test_forward_case_is_exactly_evaluable(name):
+    """Weights over {-1, 0, 1} and sparse, x and biases integers, every hidden pre-activation (float64) an integer >= 0 or <= -32
+    with both branches in every hidden layer of every net; the fp32 ELU of such a z is z or exactly -1; the sums of the forward
+    stay far below 2^24, so any order gives them."""
+    p = bc.td_problem(name)
+    case, dims = p.case, p.case.dims
+    Z, H, Q = bc.exact_forward(case, p.W, p.bias, p.x)
+    assert np.array_equal(p.x, np.round(p.x)) and np.all(p.x[:, dims[0]:] == 0)
+    for n in range(2):
+        for l, w in enumerate(p.W[n]):
+            assert set(np.unique(w)) <= {-1.0, 0.0, 1.0} and (w != 0).sum(1).max() <= max(3, dims[-2] // 8)
+            assert np.array_equal(p.bias[n][l], np.round(p.bias[n][l]))
+            mass = np.abs(p.x[:, : dims[0]] if l == 0 else H[n][l - 1]).astype(np.float64) @ np.abs(w).T.astype(np.float64)
+            assert (mass + np.abs(p.bias[n][l])).max() < 2 ** 20
+        for l, z in enumerate(Z[n]):
+            assert np.array_equal(z, np.round(z)) and np.all((z >= 0) | (z <= -32)), (n, l)
+            assert (z > 0).any() and (z <= -32).any(), (n, l)
+            elu = np.where(z > 0, z, np.exp(np.minimum(z, 0.0)).astype(F32) - F32(1)).astype(F32)
+            assert np.array_equal(elu, H[n][l]) and np.array_equal(H[n][l], p.H[n][l])
+        if case.B > 4:      # layer 0's gated units are dead on some rows and alive on others
+            z = Z[n][0][:, 2]
+            assert (z <= -32).any() and (z >= 0).any()
+    assert np.array_equal(Q, p.q)
+    assert p.tc.data == "int" or not np.array_equal(p.W[0][0], p.W[1][0])
+
+
+def test_exp_of_minus_32_vanishes_beside_one():
+    """exp(z) < 2^-25 for z <= -32: whatever a fast exponential returns there, within a factor of two, `__expf(z) - 1.f` is -1."""
+    assert 2 * np.exp(-32.0) < 2.0 ** -25 and F32(F32(2 * np.exp(-32.0)) - F32(1)) == F32(-1)
+
+
+def test_norm_cases_have_integer_gradients_within_24_bits():
+    for name in bc.TD_NORM_BWD_NAMES + bc.TD_NORM_FWD_NAMES:
+        ref, p = bc.td_reference(name), bc.td_problem(name)
+        assert p.case.B == 8 and np.array_equal(p.dq / 4, np.round(p.dq / 4)), name
+        assert np.array_equal(ref["grads"], np.round(ref["grads"])) and 0 < ref["sumsq"] <= 2 ** 24, name
+        assert bc.sumsq_bits(ref["grads"]) == (float(np.log2(ref["sumsq"])), 0)
+        assert bc.head_is_fused(p.case.dims)
+    # head only: every hidden-layer gradient is zero, the head's dW and db are not
+    name = [n for n in bc.TD_NORM_BWD_NAMES if n.endswith("head_only")][0]
+    g, dims = bc.td_reference(name)["grads"], bc.TD_BY_NAME[name].dims
+    for net in range(2):
+        a, b = bc.head_range(dims, net)
+        assert np.all(g[net * bc.net_stride(dims): a] == 0) and np.count_nonzero(g[a: a + dims[-2]]) == dims[-2] and g[a + dims[-2]] != 0
+    # the non-fused head of pqlk_mlp_backward_norm
+    case = bc.norm_plain_case()
+    assert not bc.head_is_fused(case.dims) and bc.skinny_bwd_ok(case.dims[-1], bc.ld(case.dims[-2]))
+    assert bc.norm_parts(case.dims, 2) == bc.cdiv(bc.net_stride(case.dims) * 2 // 4, 256)
+    g = bc.norm_plain_reference(case)
+    assert np.array_equal(g, np.round(g)) and 0 < (g * g).sum() <= 2 ** 24
+    assert not np.isnan(bc.norm_plain_stash(case)[: bc.act_offset(case.dims, 2, case.B, 0, 1)[0]]).any()
+
+
+def test_head_sum_bound_catches_a_dropped_and_a_doubled_row():
+    """The bound of the forward path's head sums, (B + 8) 2^-24 sum |t|, is about B^2 2^-24 average terms: at B = 95 one dropped or
+    doubled row moves a sum by hundreds of times the bound; at B = 4097 it is about one average term, and there the bit-equal
+    hidden gradients (which read every row's dL/dQ) and the exact loss partials carry the row count.  fp32 sums taken forward and
+    reversed stay inside the bound at either size."""
+    for name, factor in (("8x288x32x1-B95-fwd", 100.0), ("8x288x32x1-B4097-fwd", 1.0)):
+        p, ref = bc.td_problem(name), bc.td_reference(name)
+        a, _ = bc.head_range(p.case.dims, 0)
+        Kh = p.case.dims[-2]
+        bound = bc.head_sum_bound(p, ref)[a: a + Kh + 1]
+        row = int(np.argmax(np.abs(p.dy[0, :, 0])))
+        moved = np.abs(np.concatenate([p.dy[0, row, 0] * p.H[0][-1][row].astype(np.float64), [p.dy[0, row, 0]]]))
+        assert moved.max() > factor * bound.max(), name
+        terms = p.dy[0, :, :1] * p.H[0][-1]
+        for order in (terms, terms[::-1]):
+            got = np.cumsum(order, axis=0, dtype=F32)[-1]
+            assert np.all(np.abs(got - ref["grads"][a: a + Kh]) <= bound[:Kh]), name
+
+
+def test_td_gpu_module_skips_nothing():
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_td_paths_gpu.py")).read()
+    for word in ("skip", "xfail", "importorskip", "rtol", "atol", "allclose", "assert_close"):
+        assert word not in src, word
+
+
+def test_operand_order_values_tell_the_orders_apart():
+    for name in (bc.ORDER_BWD_NAME, bc.ORDER_FWD_NAME):
+        p = bc.order_problem(name)
+        assert p.case.B == 1 and p.qt[1, 0] < p.qt[0, 0]
+        for q in p.q[:, 0]:
+            want = bc.td_db_in_order(q)
+            assert want != bc.td_db_in_order(q, "gamma_first") and want != bc.td_db_in_order(q, "fma"), (name, q)
