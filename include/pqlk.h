@@ -778,6 +778,41 @@ int pqlk_ln_elu_backward(const float* dy, const float* y, const float* z, int64_
                          const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
                          pqlk_stream_t stream);
 
+/* Dropout fused into the LayerNorm + ELU rows: the `Linear -> Dropout(p) -> LayerNorm -> ELU` blocks of the DroQ critic
+ * (Hiraoka et al. 2022; pql_amd/models/droq.py).  The mask is generated inside the row launches, forward and backward, from a
+ * counter-based generator: no mask tensor is written or read, no extra pass over the (m, cols) activations, no extra workspace.
+ *
+ * The mask law: a pure function of (seed, tag, row r, column c), r the row index in the whole (m, cols) matrix.
+ *   x(r, c)    = component (c & 3) of the Philox4x32-10 block with key (seed & 0xffffffff, seed >> 32) and counter words
+ *                (c >> 2, r, tag & 0xffffffff, tag >> 32)
+ *   thr        = (uint32_t) floor((double)p * 4294967296.0)          (on the host)
+ *   keep(r, c) = x(r, c) >= thr
+ *   s          = 1.0f / (1.0f - p)                                   (on the host; one rounding each)
+ *   u_j        = keep ? z_j * s : 0.0f
+ * Forward: the LayerNorm + ELU law above applied to u instead of z; mean and rstd are those of u.  Backward: the law above with
+ * xhat re-formed from u -- from z and the regenerated mask, never a stored one -- gives du; then dz_j = keep ? du_j * s : 0.0f;
+ * dgamma and dbeta are unchanged in form.  dz may alias dy.
+ * p == 0: thr = 0 and s = 1.0f, so u = z bit for bit and both entries give the bits of pqlk_ln_elu_forward / _backward.
+ *
+ * Dispatch, alignment modes, grid caps and summation orders: those of pqlk_ln_elu_* (the same row bodies).  In the 16-byte layout
+ * a lane's chunk of four consecutive columns is one Philox block, generated once per chunk (the 8-byte layout at cols <= 128: half a
+ * block per chunk); the scalar layout and the strided path for cols > 1024 spend one block per element, the strided path once per
+ * pass over the row.
+ * Errors: as for pqlk_ln_elu_*, and PQLK_E_SHAPE for p < 0, p >= 1, a non-finite p, or m > 2^32 (r is one counter word). */
+
+/* keep(r, c) as bytes (1 keep, 0 drop) into keep[r * ld_keep + c], c < cols <= ld_keep: the law alone, for tests and inspection. */
+int pqlk_drop_mask(uint64_t seed, uint64_t tag, float p, int64_t m, int32_t cols, uint8_t* keep, int64_t ld_keep,
+                   pqlk_stream_t stream);
+
+int pqlk_drop_ln_elu_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps,
+                             float p, uint64_t seed, uint64_t tag, float* y, float* mean, float* rstd, pqlk_stream_t stream);
+
+/* y / mean / rstd of pqlk_drop_ln_elu_forward with the same (p, seed, tag); z the forward's input.  NULL outputs and scratch as for
+ * pqlk_ln_elu_backward. */
+int pqlk_drop_ln_elu_backward(const float* dy, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols, const float* mean,
+                              const float* rstd, const float* gamma, float p, uint64_t seed, uint64_t tag, float* dz, float* dgamma,
+                              float* dbeta, float* scratch, pqlk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Synthetic vectorised environment step (the Isaac-Gym stand-in of BASELINE.json; not a reference component).
  * Counter-based: outputs depend only on (seed, env_offset + env, t, column), so shards of the env axis reproduce

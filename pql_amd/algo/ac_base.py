@@ -68,12 +68,21 @@ class ActorCriticBase(PQLActor):
         st = super().training_state()
         if self.per is not None:
             st["per_calls"] = int(self.per_calls)
+        for name, net in self._drop_nets().items():   # the dropout critic's mask state: seed, call counter, stream id
+            st.setdefault("drop", {})[name] = net.drop_state()
         return st
 
     def load_training_state(self, st, nstep=True):
         super().load_training_state(st, nstep=nstep)
         if self.per is not None:
             self.per_calls = int(st.get("per_calls", 0))
+        for name, net in self._drop_nets().items():
+            net.load_drop_state(st["drop"][name])
+
+    def _drop_nets(self):
+        """The critics that carry dropout state (DoubleQDropoutLayerNorm: the critic and its target), by their training-state name."""
+        nets = {"critic": self.critic, **({"critic_target": self.critic_target} if self.TARGET_CRITIC else {})}
+        return {k: v for k, v in nets.items() if hasattr(v, "drop_state")}
 
     def explore_env(self, env, timesteps, random=False):
         _, cri_data, steps = super().explore_env(env, timesteps, random)

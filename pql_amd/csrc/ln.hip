@@ -7,7 +7,45 @@
 // cols <= 128 / 256 / 512 / 1024, ragged widths masked); wider rows take a strided path that re-reads the row.  16-byte (8-byte at
 // VPL = 2) accesses when every pointer is 16-B aligned and ld % 4 == 0, scalar ones otherwise.  Row sums: per-lane partials in
 // register order, then the xor butterfly of wave_sum (every lane ends with the same bits).  No float atomics anywhere.
+//
+// Dropout (DroQ, DoubleQDropoutLayerNorm): the pqlk_drop_ln_elu_* entries run the SAME row bodies on u = keep ? z * s : 0 with the
+// keep mask regenerated from Philox4x32-10 in registers (the mask law of include/pqlk.h): no mask tensor, no extra pass.  Every row
+// kernel below ends in a parameter pack `D... dr` that is either empty (the plain kernel: the signature, the instructions and the
+// bits of pqlk_ln_elu_* are what they were, every `if constexpr (DROP)` is compiled out) or one LnDrop (the dropout sibling).
 #include "pqlk_common.h"
+
+// Philox4x32-10 (Salmon et al. 2011), ten rounds written out: counter (c0, c1, c2, c3), key (k0, k1) -> one block of four words
+__device__ __forceinline__ uint4 ln_philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return make_uint4(c0, c1, c2, c3);
+}
+
+// the mask law's host-made constants: key = seed, counter words 2 / 3 = tag, thr = floor(p * 2^32), s = 1 / (1 - p)
+struct LnDrop {
+  uint32_t k0, k1, t0, t1, thr;
+  float s;
+};
+
+// the LnDrop of a kernel's trailing pack (an empty pack: the plain kernel, which never reads it)
+__device__ __forceinline__ LnDrop ln_drop_of() { return LnDrop{}; }
+__device__ __forceinline__ LnDrop ln_drop_of(const LnDrop& d) { return d; }
+
+// word (c & 3) of a block (selects on values: an indexed uint4 would be promoted to LDS)
+__device__ __forceinline__ uint32_t ln_word(uint4 b, int c) {
+  const uint32_t lo = (c & 1) ? b.y : b.x, hi = (c & 1) ? b.w : b.z;
+  return (c & 2) ? hi : lo;
+}
+
+// keep(r, c) of one element: one Philox block per call (the scalar layout, the strided wide path)
+__device__ __forceinline__ bool ln_keep1(const LnDrop& d, uint32_t r, int c) {
+  return ln_word(ln_philox(d.k0, d.k1, (uint32_t)c >> 2, r, d.t0, d.t1), c) >= d.thr;
+}
 
 __device__ __forceinline__ float ln_elu(float x) { return x > 0.f ? x : expm1f(x); }   // nn.ELU(alpha=1)
 
@@ -62,11 +100,38 @@ __device__ __forceinline__ void ln_store(float* __restrict__ p, int cols, int la
   }
 }
 
+// bit i = keep of register slot i of row r (slots past cols: 0; they hold 0.f anyway).  VEC: a lane's chunk lies in ONE Philox block
+// (V = 4: the whole block; V = 2: its lower or upper half), generated once per chunk; scalar: one block per element.
 template <int VPL, bool VEC>
+__device__ __forceinline__ unsigned ln_keep_bits(const LnDrop& d, uint32_t r, int cols, int lane) {
+  using M = LnMap<VPL, VEC>;
+  unsigned km = 0;
+  if (VEC) {
+#pragma unroll
+    for (int k = 0; k < M::NCH; ++k) {
+      const int c0 = (k * 64 + lane) * M::V;
+      if (c0 < cols) {
+        const uint4 b = ln_philox(d.k0, d.k1, (uint32_t)c0 >> 2, r, d.t0, d.t1);
+#pragma unroll
+        for (int e = 0; e < M::V; ++e) km |= (unsigned)(ln_word(b, c0 + e) >= d.thr) << (k * M::V + e);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c = i * 64 + lane;
+      if (c < cols) km |= (unsigned)ln_keep1(d, r, c) << i;
+    }
+  }
+  return km;
+}
+
+template <int VPL, bool VEC, typename... D>
 __global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z, int64_t ld, int64_t m, int cols,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                    float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
+                                                    float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, D... dr) {
   using M = LnMap<VPL, VEC>;
+  constexpr bool DROP = sizeof...(D) != 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float ga[VPL], be[VPL];
   ln_load<VPL, VEC>(gamma, cols, lane, ga);
@@ -75,6 +140,12 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z,
   for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
     float v[VPL];
     ln_load<VPL, VEC>(z + r * ld, cols, lane, v);
+    if constexpr (DROP) {   // u = keep ? z * s : 0
+      const LnDrop d = ln_drop_of(dr...);
+      const unsigned km = ln_keep_bits<VPL, VEC>(d, (uint32_t)r, cols, lane);
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) v[i] = (km >> i) & 1u ? v[i] * d.s : 0.f;
+    }
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) s += v[i];
@@ -95,35 +166,44 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z,
   }
 }
 
+// element (r, c) of u (one LnDrop) or of z (none) from the loaded z: the strided paths re-read the row and, with it, re-form the
+// mask, one block per element
+__device__ __forceinline__ float ln_u(float zv, uint32_t, int) { return zv; }
+__device__ __forceinline__ float ln_u(float zv, uint32_t r, int c, const LnDrop& d) { return ln_keep1(d, r, c) ? zv * d.s : 0.f; }
+
 // rows wider than LN_MAX_REG_COLS: the same law with the row re-read from memory (sum, squared deviations, output)
+template <typename... D>
 __global__ __launch_bounds__(256) void k_ln_elu_fwd_wide(const float* __restrict__ z, int64_t ld, int64_t m, int cols,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                         float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
+                                                         float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd,
+                                                         D... dr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float n = (float)cols;
   for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
     const float* zr = z + r * ld;
     float* yr = y + r * ld;
     float s = 0.f;
-    for (int c = lane; c < cols; c += 64) s += zr[c];
+    for (int c = lane; c < cols; c += 64) s += ln_u(zr[c], (uint32_t)r, c, dr...);
     const float mu = wave_sum(s) / n;
     float q = 0.f;
-    for (int c = lane; c < cols; c += 64) { const float d = zr[c] - mu; q += d * d; }
+    for (int c = lane; c < cols; c += 64) { const float d = ln_u(zr[c], (uint32_t)r, c, dr...) - mu; q += d * d; }
     const float var = wave_sum(q) / n;
     const float rs = 1.0f / sqrtf(var + eps);
-    for (int c = lane; c < cols; c += 64) yr[c] = ln_elu((zr[c] - mu) * rs * gamma[c] + beta[c]);
+    for (int c = lane; c < cols; c += 64) yr[c] = ln_elu((ln_u(zr[c], (uint32_t)r, c, dr...) - mu) * rs * gamma[c] + beta[c]);
     if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
   }
 }
 
 // Backward, one wave per row.  PARAMS: each wave also accumulates its rows' g and g * xhat per column in registers; the block
 // folds its waves through LDS in wave order and writes one partial row: part[(blockIdx.x * 2 + {0: dbeta, 1: dgamma}) * cols + c].
-template <int VPL, bool VEC, bool PARAMS>
+// DROP: xhat is re-formed from u = keep ? z * s : 0 (the mask regenerated, never stored), the law gives du, dz = keep ? du * s : 0.
+template <int VPL, bool VEC, bool PARAMS, typename... D>
 __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float* __restrict__ y, const float* __restrict__ z,
                                                     int64_t ld, int64_t m, int cols, const float* __restrict__ mean,
                                                     const float* __restrict__ rstd, const float* __restrict__ gamma, float* dz,
-                                                    float* __restrict__ part) {
+                                                    float* __restrict__ part, D... dr) {
   using M = LnMap<VPL, VEC>;
+  constexpr bool DROP = sizeof...(D) != 0;
   __shared__ float sh[PARAMS ? 2 * LN_WAVES * VPL * 64 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float ga[VPL], accb[VPL], accg[VPL];
@@ -137,6 +217,13 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float
     ln_load<VPL, VEC>(dy + r * ld, cols, lane, h);
     ln_load<VPL, VEC>(y + r * ld, cols, lane, yv);
     ln_load<VPL, VEC>(z + r * ld, cols, lane, xh);
+    [[maybe_unused]] unsigned km = 0;
+    if constexpr (DROP) {
+      const LnDrop d = ln_drop_of(dr...);
+      km = ln_keep_bits<VPL, VEC>(d, (uint32_t)r, cols, lane);
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) xh[i] = (km >> i) & 1u ? xh[i] * d.s : 0.f;
+    }
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
@@ -152,6 +239,11 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float
     const float c1 = wave_sum(s1) / n, c2 = wave_sum(s2) / n;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) h[i] = rs * (h[i] - c1 - xh[i] * c2);
+    if constexpr (DROP) {
+      const float sc = ln_drop_of(dr...).s;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) h[i] = (km >> i) & 1u ? h[i] * sc : 0.f;
+    }
     ln_store<VPL, VEC>(dz + r * ld, cols, lane, h);
   }
   if (PARAMS) {
@@ -175,38 +267,51 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float
   }
 }
 
+
 // wide rows: dz with the row re-read (dy fully read before dz, which may alias it, is written: the sums need all of it first,
 // and every element is then read and written by the same lane)
+template <typename... D>
 __global__ __launch_bounds__(256) void k_ln_elu_bwd_wide(const float* dy, const float* __restrict__ y, const float* __restrict__ z,
                                                          int64_t ld, int64_t m, int cols, const float* __restrict__ mean,
-                                                         const float* __restrict__ rstd, const float* __restrict__ gamma, float* dz) {
+                                                         const float* __restrict__ rstd, const float* __restrict__ gamma, float* dz,
+                                                         D... dr) {
+  constexpr bool DROP = sizeof...(D) != 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float n = (float)cols;
   for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
     const float mu = mean[r], rs = rstd[r];
-    const float *dr = dy + r * ld, *yr = y + r * ld, *zr = z + r * ld;
+    const float *dyr = dy + r * ld, *yr = y + r * ld, *zr = z + r * ld;
     float* o = dz + r * ld;
     float s1 = 0.f, s2 = 0.f;
     for (int c = lane; c < cols; c += 64) {
       const float yy = yr[c];
-      const float hh = dr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      const float hh = dyr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
       s1 += hh;
-      s2 += hh * ((zr[c] - mu) * rs);
+      s2 += hh * ((ln_u(zr[c], (uint32_t)r, c, dr...) - mu) * rs);
     }
     const float c1 = wave_sum(s1) / n, c2 = wave_sum(s2) / n;
     for (int c = lane; c < cols; c += 64) {
       const float yy = yr[c];
-      const float hh = dr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
-      o[c] = rs * (hh - c1 - ((zr[c] - mu) * rs) * c2);
+      const float hh = dyr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      if constexpr (!DROP) {
+        o[c] = rs * (hh - c1 - ((zr[c] - mu) * rs) * c2);
+      } else {
+        const LnDrop d = ln_drop_of(dr...);
+        const bool keep = ln_keep1(d, (uint32_t)r, c);
+        const float u = keep ? zr[c] * d.s : 0.f;
+        const float du = rs * (hh - c1 - ((u - mu) * rs) * c2);
+        o[c] = keep ? du * d.s : 0.f;
+      }
     }
   }
 }
 
 // wide rows: the column sums of g and g * xhat over a chunk of rows, down the columns like k_bn_bwd_sums -> the same partial layout
+template <typename... D>
 __global__ __launch_bounds__(256) void k_ln_bwd_sums_wide(const float* __restrict__ dy, const float* __restrict__ y,
                                                           const float* __restrict__ z, int64_t ld, int64_t m, int cols,
                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          float* __restrict__ part) {
+                                                          float* __restrict__ part, D... dr) {
   __shared__ float sh[2][4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
@@ -218,7 +323,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_sums_wide(const float* __restric
       const float yy = y[r * ld + c];
       const float g = dy[r * ld + c] * (yy > 0.f ? 1.f : yy + 1.f);
       s1 += g;
-      s2 += g * ((z[r * ld + c] - mean[r]) * rstd[r]);
+      s2 += g * ((ln_u(z[r * ld + c], (uint32_t)r, c, dr...) - mean[r]) * rstd[r]);
     }
   }
   sh[0][rl][cl] = s1; sh[1][rl][cl] = s2;
@@ -228,6 +333,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_sums_wide(const float* __restric
     part[((int64_t)blockIdx.y * 2 + 1) * cols + c] = (sh[1][0][cl] + sh[1][1][cl]) + (sh[1][2][cl] + sh[1][3][cl]);
   }
 }
+
 
 // fold the chunk partials in index order: 16 columns x 16 groups of consecutive chunks per block, the groups then in group order.
 // blockIdx.y: 0 -> dbeta, 1 -> dgamma
@@ -259,49 +365,53 @@ static inline unsigned ln_blocks(int64_t m, int64_t cap) {
   return (unsigned)(nb < cap ? nb : cap);
 }
 
-template <int VPL>
+// `D... dr` below: nothing (the plain kernels) or one LnDrop (their dropout siblings), handed on behind the kernels' arguments
+template <int VPL, typename... D>
 static void ln_launch_fwd(bool vec, unsigned grid, hipStream_t s, const float* z, int64_t ld, int64_t m, int cols, const float* gamma,
-                          const float* beta, float eps, float* y, float* mean, float* rstd) {
+                          const float* beta, float eps, float* y, float* mean, float* rstd, D... dr) {
   if (vec)
-    hipLaunchKernelGGL((k_ln_elu_fwd<VPL, true>), dim3(grid), dim3(256), 0, s, z, ld, m, cols, gamma, beta, eps, y, mean, rstd);
+    k_ln_elu_fwd<VPL, true><<<dim3(grid), dim3(256), 0, s>>>(z, ld, m, cols, gamma, beta, eps, y, mean, rstd, dr...);
   else
-    hipLaunchKernelGGL((k_ln_elu_fwd<VPL, false>), dim3(grid), dim3(256), 0, s, z, ld, m, cols, gamma, beta, eps, y, mean, rstd);
+    k_ln_elu_fwd<VPL, false><<<dim3(grid), dim3(256), 0, s>>>(z, ld, m, cols, gamma, beta, eps, y, mean, rstd, dr...);
 }
 
-template <int VPL>
+template <int VPL, typename... D>
 static void ln_launch_bwd(bool vec, bool params, unsigned grid, hipStream_t s, const float* dy, const float* y, const float* z, int64_t ld,
-                          int64_t m, int cols, const float* mean, const float* rstd, const float* gamma, float* dz, float* part) {
+                          int64_t m, int cols, const float* mean, const float* rstd, const float* gamma, float* dz, float* part, D... dr) {
   if (vec && params)
-    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, true, true>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+    k_ln_elu_bwd<VPL, true, true><<<dim3(grid), dim3(256), 0, s>>>(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part, dr...);
   else if (vec)
-    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, true, false>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+    k_ln_elu_bwd<VPL, true, false><<<dim3(grid), dim3(256), 0, s>>>(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part, dr...);
   else if (params)
-    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, false, true>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+    k_ln_elu_bwd<VPL, false, true><<<dim3(grid), dim3(256), 0, s>>>(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part, dr...);
   else
-    hipLaunchKernelGGL((k_ln_elu_bwd<VPL, false, false>), dim3(grid), dim3(256), 0, s, dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part);
+    k_ln_elu_bwd<VPL, false, false><<<dim3(grid), dim3(256), 0, s>>>(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, part, dr...);
 }
 
 extern "C" int64_t pqlk_ln_scratch_floats(int32_t cols) { return cols > 0 ? (int64_t)2 * PQLK_LN_CHUNKS * cols : 0; }
 
-extern "C" int pqlk_ln_elu_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps,
-                                   float* y, float* mean, float* rstd, pqlk_stream_t stream) {
+// the one forward / backward dispatch of the plain and the dropout entries
+template <typename... D>
+static int ln_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps, float* y,
+                      float* mean, float* rstd, pqlk_stream_t stream, D... dr) {
   PQLK_REQUIRE(z && gamma && beta && y && mean && rstd, PQLK_E_NULL);
   PQLK_REQUIRE(m > 0 && cols > 0 && ld >= cols, PQLK_E_SHAPE);
   const unsigned grid = ln_blocks(m, PQLK_LN_ROW_BLOCKS);
   const bool vec = pqlk_aligned16(z) && pqlk_aligned16(y) && pqlk_aligned16(gamma) && pqlk_aligned16(beta) && ld % 4 == 0;
   hipStream_t s = pqlk_s(stream);
-  if (cols <= 128) ln_launch_fwd<2>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
-  else if (cols <= 256) ln_launch_fwd<4>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
-  else if (cols <= 512) ln_launch_fwd<8>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
-  else if (cols <= LN_MAX_REG_COLS) ln_launch_fwd<16>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
-  else hipLaunchKernelGGL(k_ln_elu_fwd_wide, dim3(grid), dim3(256), 0, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd);
+  if (cols <= 128) ln_launch_fwd<2>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd, dr...);
+  else if (cols <= 256) ln_launch_fwd<4>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd, dr...);
+  else if (cols <= 512) ln_launch_fwd<8>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd, dr...);
+  else if (cols <= LN_MAX_REG_COLS) ln_launch_fwd<16>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd, dr...);
+  else k_ln_elu_fwd_wide<<<dim3(grid), dim3(256), 0, s>>>(z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd, dr...);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }
 
-extern "C" int pqlk_ln_elu_backward(const float* dy, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols, const float* mean,
-                                    const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
-                                    pqlk_stream_t stream) {
+template <typename... D>
+static int ln_backward(const float* dy, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols, const float* mean,
+                       const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
+                       pqlk_stream_t stream, D... dr) {
   const bool params = dgamma || dbeta;
   PQLK_REQUIRE(dy && y && z && mean && rstd && gamma && dz && (scratch || !params), PQLK_E_NULL);
   PQLK_REQUIRE(m > 0 && cols > 0 && ld >= cols, PQLK_E_SHAPE);
@@ -311,20 +421,20 @@ extern "C" int pqlk_ln_elu_backward(const float* dy, const float* y, const float
   if (cols <= LN_MAX_REG_COLS) {
     const unsigned grid = ln_blocks(m, params ? PQLK_LN_CHUNKS : PQLK_LN_ROW_BLOCKS);
     const bool vec = pqlk_aligned16(dy) && pqlk_aligned16(y) && pqlk_aligned16(z) && pqlk_aligned16(gamma) && pqlk_aligned16(dz) && ld % 4 == 0;
-    if (cols <= 128) ln_launch_bwd<2>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
-    else if (cols <= 256) ln_launch_bwd<4>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
-    else if (cols <= 512) ln_launch_bwd<8>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
-    else ln_launch_bwd<16>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch);
+    if (cols <= 128) ln_launch_bwd<2>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch, dr...);
+    else if (cols <= 256) ln_launch_bwd<4>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch, dr...);
+    else if (cols <= 512) ln_launch_bwd<8>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch, dr...);
+    else ln_launch_bwd<16>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch, dr...);
     PQLK_LAUNCH_CHECK();
     chunks = (int)grid;
   } else {
     chunks = (int)(m < PQLK_LN_CHUNKS ? m : PQLK_LN_CHUNKS);
     if (params) {   // before dz, which may alias dy, is written
-      hipLaunchKernelGGL(k_ln_bwd_sums_wide, dim3((unsigned)((cols + 63) / 64), (unsigned)chunks), dim3(256), 0, s, dy, y, z, ld, m, c, mean,
-                         rstd, scratch);
+      k_ln_bwd_sums_wide<<<dim3((unsigned)((cols + 63) / 64), (unsigned)chunks), dim3(256), 0, s>>>(dy, y, z, ld, m, c, mean, rstd, scratch,
+                                                                                                    dr...);
       PQLK_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_ln_elu_bwd_wide, dim3(ln_blocks(m, PQLK_LN_ROW_BLOCKS)), dim3(256), 0, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz);
+    k_ln_elu_bwd_wide<<<dim3(ln_blocks(m, PQLK_LN_ROW_BLOCKS)), dim3(256), 0, s>>>(dy, y, z, ld, m, c, mean, rstd, gamma, dz, dr...);
     PQLK_LAUNCH_CHECK();
   }
   if (params) {
@@ -333,3 +443,66 @@ extern "C" int pqlk_ln_elu_backward(const float* dy, const float* y, const float
   }
   return PQLK_OK;
 }
+
+extern "C" int pqlk_ln_elu_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps,
+                                   float* y, float* mean, float* rstd, pqlk_stream_t stream) {
+  return ln_forward(z, ld, m, cols, gamma, beta, eps, y, mean, rstd, stream);
+}
+
+extern "C" int pqlk_ln_elu_backward(const float* dy, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols, const float* mean,
+                                    const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
+                                    pqlk_stream_t stream) {
+  return ln_backward(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, dgamma, dbeta, scratch, stream);
+}
+
+// ---- dropout entries: the mask law's constants are made here, on the host (include/pqlk.h)
+static bool ln_drop_make(float p, uint64_t seed, uint64_t tag, int64_t m, LnDrop* d) {
+  if (!(p >= 0.f && p < 1.f) || m > (int64_t)1 << 32) return false;   // (a NaN p fails the first test)
+  d->k0 = (uint32_t)seed; d->k1 = (uint32_t)(seed >> 32);
+  d->t0 = (uint32_t)tag; d->t1 = (uint32_t)(tag >> 32);
+  d->thr = (uint32_t)floor((double)p * 4294967296.0);
+  const float q = 1.0f - p;
+  d->s = 1.0f / q;
+  return true;
+}
+
+// keep(r, c) as bytes: one thread per Philox block = four consecutive columns of a row
+__global__ __launch_bounds__(256) void k_drop_mask(LnDrop dr, int64_t m, int cols, uint8_t* __restrict__ keep, int64_t ld_keep) {
+  const int64_t per_row = (cols + 3) / 4, total = m * per_row;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t r = i / per_row;
+    const int c0 = (int)(i % per_row) * 4;
+    const uint4 b = ln_philox(dr.k0, dr.k1, (uint32_t)c0 >> 2, (uint32_t)r, dr.t0, dr.t1);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (c0 + e < cols) keep[r * ld_keep + c0 + e] = ln_word(b, e) >= dr.thr;
+  }
+}
+
+extern "C" int pqlk_drop_mask(uint64_t seed, uint64_t tag, float p, int64_t m, int32_t cols, uint8_t* keep, int64_t ld_keep,
+                              pqlk_stream_t stream) {
+  PQLK_REQUIRE(keep, PQLK_E_NULL);
+  LnDrop d;
+  PQLK_REQUIRE(m > 0 && cols > 0 && ld_keep >= cols && ln_drop_make(p, seed, tag, m, &d), PQLK_E_SHAPE);
+  const int64_t nb = (m * (((int64_t)cols + 3) / 4) + 255) / 256;
+  hipLaunchKernelGGL(k_drop_mask, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, pqlk_s(stream), d, m, (int)cols, keep, ld_keep);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
+extern "C" int pqlk_drop_ln_elu_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta,
+                                        float eps, float p, uint64_t seed, uint64_t tag, float* y, float* mean, float* rstd,
+                                        pqlk_stream_t stream) {
+  LnDrop d;
+  PQLK_REQUIRE(ln_drop_make(p, seed, tag, m, &d), PQLK_E_SHAPE);
+  return ln_forward(z, ld, m, cols, gamma, beta, eps, y, mean, rstd, stream, d);
+}
+
+extern "C" int pqlk_drop_ln_elu_backward(const float* dy, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols,
+                                         const float* mean, const float* rstd, const float* gamma, float p, uint64_t seed, uint64_t tag,
+                                         float* dz, float* dgamma, float* dbeta, float* scratch, pqlk_stream_t stream) {
+  LnDrop d;
+  PQLK_REQUIRE(ln_drop_make(p, seed, tag, m, &d), PQLK_E_SHAPE);
+  return ln_backward(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, dgamma, dbeta, scratch, stream, d);
+}
+
