@@ -778,6 +778,41 @@ int pqlk_ln_elu_backward(const float* dy, const float* y, const float* z, int64_
                          const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
                          pqlk_stream_t stream);
 
+/* The skip connection of the residual LayerNorm critic (BroNet; pql_amd/models/bronet.py) inside the LayerNorm rows: a block is
+ * h_k = h_{k-1} + LN(zb), so the forward adds the skip to the normalised row it already holds, and the backward takes its incoming
+ * gradient as a sum of two addends (the gradient through the block's successor and the running skip gradient) and hands the sum on.
+ * No stand-alone add launch, no extra pass over the (m, cols) activations.
+ *
+ * pqlk_ln_res_forward: LayerNorm WITHOUT activation, plus the skip.  Per row:
+ *   mean, var, rstd, xhat_j : as in the LayerNorm + ELU law above
+ *   t_j = xhat_j * gamma_j
+ *   t_j = t_j + beta_j
+ *   y_j = res_j + t_j
+ * res has the layout of z ((m, ld), columns [cols, ld) never read).  y aliases neither z nor res.  mean[r], rstd[r] are written.
+ *
+ * pqlk_ln_sum_backward: the LayerNorm backward above with the incoming gradient dy + dy2, with or without the ELU.  Per row:
+ *   g0_j   = dy2 ? dy_j + dy2_j : dy_j
+ *   dsum_j = g0_j                                          (only if dsum != NULL)
+ *   g_j    = y ? g0_j * (y_j > 0 ? 1 : y_j + 1) : g0_j     (y == NULL: no activation behind the norm, the block's second half)
+ *   h_j, c1, c2, dz_j, dgamma_j, dbeta_j : as in the law above, from g
+ * dy2, y, dsum, dgamma, dbeta are optional (NULL).  dy2 and dsum have the layout of dy.  With dy2 == dsum == NULL and y given the
+ * entry runs the operations of pqlk_ln_elu_backward in its order: the same bits.
+ * Aliasing.  dz may alias dy; dsum may alias dy2 (the running skip gradient is updated in place); both at once is allowed.  Nothing
+ * else may overlap: dz and dsum are distinct, and neither aliases y, z or the other input.  (A row held in registers is read whole
+ * before anything of it is written; in the strided path every element of dy and dy2 is read by the lane that then writes dsum and
+ * dz at that element, after the row sums, and the column-sum launch runs before the launch that writes.)
+ * scratch, and the launches: as for pqlk_ln_elu_backward (pqlk_ln_scratch_floats(cols) floats when dgamma or dbeta is wanted).
+ *
+ * Dispatch, alignment modes, grid caps and summation orders: those of pqlk_ln_elu_* (the same row bodies); 16-byte accesses need
+ * res (backward: dy2, dsum, where given) 16-B aligned too.  Columns [cols, ld) of y, dz and dsum are left untouched.
+ * Errors: as for pqlk_ln_elu_*; res is required, and so are dy, z, mean, rstd, gamma, dz. */
+int pqlk_ln_res_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps,
+                        const float* res, float* y, float* mean, float* rstd, pqlk_stream_t stream);
+
+int pqlk_ln_sum_backward(const float* dy, const float* dy2, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols,
+                         const float* mean, const float* rstd, const float* gamma, float* dsum, float* dz, float* dgamma, float* dbeta,
+                         float* scratch, pqlk_stream_t stream);
+
 /* Dropout fused into the LayerNorm + ELU rows: the `Linear -> Dropout(p) -> LayerNorm -> ELU` blocks of the DroQ critic
  * (Hiraoka et al. 2022; pql_amd/models/droq.py).  The mask is generated inside the row launches, forward and backward, from a
  * counter-based generator: no mask tensor is written or read, no extra pass over the (m, cols) activations, no extra workspace.

@@ -18,6 +18,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.models import model_name_to_path
+from pql_amd.models.bronet import check_width_blocks
 from pql_amd.models.droq import check_dropout
 from pql_amd.models.mlp import PackedWeights, check_num_atoms, check_num_quantiles
 from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
@@ -275,6 +276,17 @@ def check_critic_class(cfg, fused_learner=None):
             raise ValueError("algo.cri_class=DoubleQDropoutLayerNorm cannot run with algo=crossq_algo: CrossQ is the BatchNorm critic on "
                              "joint batches, without a target critic; the class is for algo=droq_algo / algo=sac_algo / algo=ddpg_algo")
         check_dropout(_cfg_get(algo, "critic_dropout", 0.01))
+    if is_bronet(algo):
+        if _cfg_get(algo, "distl", False):
+            raise ValueError("algo.distl=True is not supported with algo.cri_class=DoubleQBroNet: the residual LayerNorm critic has no "
+                             "C51 head")
+        if fused_learner is not None:
+            raise ValueError(f"algo.cri_class=DoubleQBroNet cannot run in {fused_learner}, whose launch sequences are built on the fused "
+                             f"MLP kernels: the class is for algo=ddpg_algo / algo=sac_algo (scripts/train_baselines.py)")
+        if str(_cfg_get(algo, "name", "")) == "CrossQ":
+            raise ValueError("algo.cri_class=DoubleQBroNet cannot run with algo=crossq_algo: CrossQ is the BatchNorm critic on joint "
+                             "batches, without a target critic; the class is for algo=ddpg_algo / algo=sac_algo")
+        bronet_shape(algo)
     if is_quantile(algo):
         if _cfg_get(algo, "distl", False):
             raise ValueError("algo.distl=True is not supported with algo.cri_class=QuantileDoubleQ: algo.distl selects the C51 head and "
@@ -305,6 +317,17 @@ def is_droq(algo):
     return str(_cfg_get(algo, "cri_class")).endswith("DoubleQDropoutLayerNorm")
 
 
+def is_bronet(algo):
+    """Whether `algo.cri_class` names the residual LayerNorm critic (BroNet)."""
+    return str(_cfg_get(algo, "cri_class")).endswith("DoubleQBroNet")
+
+
+def bronet_shape(algo):
+    """(algo.critic_width, algo.critic_blocks), checked; a config without the keys gets the defaults, a null is refused like any other
+    non-integer."""
+    return check_width_blocks(algo.get("critic_width", 512), algo.get("critic_blocks", 2))
+
+
 def is_quantile(algo):
     """Whether `algo.cri_class` names the quantile-regression critic."""
     return str(_cfg_get(algo, "cri_class")).endswith("QuantileDoubleQ")
@@ -330,6 +353,9 @@ def make_critic(cfg, obs_dim, action_dim, device):
             return cri_class(obs_dim, action_dim, num_quantiles=int(_cfg_get(algo, "num_quantiles", 32)), hidden_layers=hidden).to(device)
         if is_droq(algo):
             return cri_class(obs_dim, action_dim, hidden_layers=hidden, dropout=float(_cfg_get(algo, "critic_dropout", 0.01))).to(device)
+        if is_bronet(algo):   # (its own width and depth; algo.hidden_layers stays the actor's)
+            width, blocks = bronet_shape(algo)
+            return cri_class(obs_dim, action_dim, width=width, blocks=blocks).to(device)
         return cri_class(obs_dim, action_dim, hidden_layers=hidden).to(device)
 
 

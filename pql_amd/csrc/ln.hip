@@ -12,6 +12,12 @@
 // keep mask regenerated from Philox4x32-10 in registers (the mask law of include/pqlk.h): no mask tensor, no extra pass.  Every row
 // kernel below ends in a parameter pack `D... dr` that is either empty (the plain kernel: the signature, the instructions and the
 // bits of pqlk_ln_elu_* are what they were, every `if constexpr (DROP)` is compiled out) or one LnDrop (the dropout sibling).
+//
+// Skip connection (BroNet, DoubleQBroNet): pqlk_ln_res_forward / pqlk_ln_sum_backward run the same row bodies again, the pack now
+// one LnRes (forward: no ELU, y = res + LN(z)) or one LnSum (backward: the incoming gradient is dy + dy2, handed on as dsum; the ELU
+// factor only where y is given).  The skip and the second addend are loaded a chunk at a time where they are used, not held as a row.
+#include <type_traits>
+
 #include "pqlk_common.h"
 
 // Philox4x32-10 (Salmon et al. 2011), ten rounds written out: counter (c0, c1, c2, c3), key (k0, k1) -> one block of four words
@@ -35,6 +41,21 @@ struct LnDrop {
 // the LnDrop of a kernel's trailing pack (an empty pack: the plain kernel, which never reads it)
 __device__ __forceinline__ LnDrop ln_drop_of() { return LnDrop{}; }
 __device__ __forceinline__ LnDrop ln_drop_of(const LnDrop& d) { return d; }
+
+// the skip connection's extra operands (include/pqlk.h): the forward's res; the backward's second addend and where the sum goes
+struct LnRes {
+  const float* res;
+};
+struct LnSum {
+  const float* dy2;   // NULL: one addend
+  float* dsum;        // NULL: the sum is not handed on
+};
+__device__ __forceinline__ LnRes ln_res_of(const LnRes& r) { return r; }
+__device__ __forceinline__ LnSum ln_sum_of(const LnSum& a) { return a; }
+
+// whether a kernel's trailing pack is one T
+template <typename T, typename... D>
+inline constexpr bool ln_has = (std::is_same_v<T, D> || ...);
 
 // word (c & 3) of a block (selects on values: an indexed uint4 would be promoted to LDS)
 __device__ __forceinline__ uint32_t ln_word(uint4 b, int c) {
@@ -79,6 +100,14 @@ __device__ __forceinline__ void ln_load(const float* __restrict__ p, int cols, i
       for (int e = 0; e < M::V; ++e) v[k * M::V + e] = c0 + e < cols ? p[c0 + e] : 0.f;
     }
   }
+}
+
+// chunk k of a lane alone -> v: register slots [k * V, (k + 1) * V) of ln_load<VPL, VEC>.  A chunk is the whole of a one-chunk row
+// map that starts 64 * V columns per chunk further on
+template <int VPL, bool VEC>
+__device__ __forceinline__ void ln_load_chunk(const float* __restrict__ p, int cols, int lane, int k, float (&v)[LnMap<VPL, VEC>::V]) {
+  constexpr int V = LnMap<VPL, VEC>::V;
+  ln_load<V, VEC>(p + k * 64 * V, cols - k * 64 * V, lane, v);
 }
 
 // v -> p[0, cols); nothing past cols is written
@@ -131,7 +160,7 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                     float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, D... dr) {
   using M = LnMap<VPL, VEC>;
-  constexpr bool DROP = sizeof...(D) != 0;
+  constexpr bool DROP = ln_has<LnDrop, D...>, RES = ln_has<LnRes, D...>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float ga[VPL], be[VPL];
   ln_load<VPL, VEC>(gamma, cols, lane, ga);
@@ -159,8 +188,19 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z,
     }
     const float var = wave_sum(q) / n;
     const float rs = 1.0f / sqrtf(var + eps);
+    if constexpr (!RES) {
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) v[i] = ln_elu(v[i] * rs * ga[i] + be[i]);
+      for (int i = 0; i < VPL; ++i) v[i] = ln_elu(v[i] * rs * ga[i] + be[i]);
+    } else {   // no activation; y = res + t, the skip loaded chunk by chunk
+      const float* rr = ln_res_of(dr...).res + r * ld;
+#pragma unroll
+      for (int k = 0; k < M::NCH; ++k) {
+        float sk[M::V];
+        ln_load_chunk<VPL, VEC>(rr, cols, lane, k, sk);
+#pragma unroll
+        for (int e = 0; e < M::V; ++e) v[k * M::V + e] = sk[e] + (v[k * M::V + e] * rs * ga[k * M::V + e] + be[k * M::V + e]);
+      }
+    }
     ln_store<VPL, VEC>(y + r * ld, cols, lane, v);
     if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
   }
@@ -169,6 +209,8 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z,
 // element (r, c) of u (one LnDrop) or of z (none) from the loaded z: the strided paths re-read the row and, with it, re-form the
 // mask, one block per element
 __device__ __forceinline__ float ln_u(float zv, uint32_t, int) { return zv; }
+__device__ __forceinline__ float ln_u(float zv, uint32_t, int, const LnRes&) { return zv; }
+__device__ __forceinline__ float ln_u(float zv, uint32_t, int, const LnSum&) { return zv; }
 __device__ __forceinline__ float ln_u(float zv, uint32_t r, int c, const LnDrop& d) { return ln_keep1(d, r, c) ? zv * d.s : 0.f; }
 
 // rows wider than LN_MAX_REG_COLS: the same law with the row re-read from memory (sum, squared deviations, output)
@@ -177,6 +219,7 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd_wide(const float* __restrict
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                          float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd,
                                                          D... dr) {
+  constexpr bool RES = ln_has<LnRes, D...>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float n = (float)cols;
   for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
@@ -189,7 +232,12 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd_wide(const float* __restrict
     for (int c = lane; c < cols; c += 64) { const float d = ln_u(zr[c], (uint32_t)r, c, dr...) - mu; q += d * d; }
     const float var = wave_sum(q) / n;
     const float rs = 1.0f / sqrtf(var + eps);
-    for (int c = lane; c < cols; c += 64) yr[c] = ln_elu((ln_u(zr[c], (uint32_t)r, c, dr...) - mu) * rs * gamma[c] + beta[c]);
+    if constexpr (!RES) {
+      for (int c = lane; c < cols; c += 64) yr[c] = ln_elu((ln_u(zr[c], (uint32_t)r, c, dr...) - mu) * rs * gamma[c] + beta[c]);
+    } else {
+      const float* rr = ln_res_of(dr...).res + r * ld;
+      for (int c = lane; c < cols; c += 64) yr[c] = rr[c] + ((zr[c] - mu) * rs * gamma[c] + beta[c]);
+    }
     if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
   }
 }
@@ -203,7 +251,7 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float
                                                     const float* __restrict__ rstd, const float* __restrict__ gamma, float* dz,
                                                     float* __restrict__ part, D... dr) {
   using M = LnMap<VPL, VEC>;
-  constexpr bool DROP = sizeof...(D) != 0;
+  constexpr bool DROP = ln_has<LnDrop, D...>, SUM = ln_has<LnSum, D...>;
   __shared__ float sh[PARAMS ? 2 * LN_WAVES * VPL * 64 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float ga[VPL], accb[VPL], accg[VPL];
@@ -215,7 +263,24 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float
     const float mu = mean[r], rs = rstd[r];
     float h[VPL], xh[VPL], yv[VPL];
     ln_load<VPL, VEC>(dy + r * ld, cols, lane, h);
-    ln_load<VPL, VEC>(y + r * ld, cols, lane, yv);
+    [[maybe_unused]] bool act = true;   // whether an ELU stands behind the norm (SUM: only where y is given)
+    if constexpr (SUM) {   // h = g0 = dy + dy2, the second addend chunk by chunk; handed on as dsum before anything else is written
+      const LnSum a = ln_sum_of(dr...);
+      act = y != nullptr;
+      if (a.dy2) {
+#pragma unroll
+        for (int k = 0; k < M::NCH; ++k) {
+          float t[M::V];
+          ln_load_chunk<VPL, VEC>(a.dy2 + r * ld, cols, lane, k, t);
+#pragma unroll
+          for (int e = 0; e < M::V; ++e) h[k * M::V + e] = h[k * M::V + e] + t[e];
+        }
+      }
+      if (a.dsum) ln_store<VPL, VEC>(a.dsum + r * ld, cols, lane, h);
+      if (act) ln_load<VPL, VEC>(y + r * ld, cols, lane, yv);
+    } else {
+      ln_load<VPL, VEC>(y + r * ld, cols, lane, yv);
+    }
     ln_load<VPL, VEC>(z + r * ld, cols, lane, xh);
     [[maybe_unused]] unsigned km = 0;
     if constexpr (DROP) {
@@ -228,7 +293,9 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const bool in = M::col(i, lane) < cols;
-      const float g = in ? h[i] * (yv[i] > 0.f ? 1.f : yv[i] + 1.f) : 0.f;
+      float g;
+      if constexpr (SUM) g = in ? (act ? h[i] * (yv[i] > 0.f ? 1.f : yv[i] + 1.f) : h[i]) : 0.f;
+      else g = in ? h[i] * (yv[i] > 0.f ? 1.f : yv[i] + 1.f) : 0.f;
       const float x = in ? (xh[i] - mu) * rs : 0.f;
       const float hh = g * ga[i];
       if (PARAMS) { accb[i] += g; accg[i] += g * x; }
@@ -268,6 +335,14 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd(const float* dy, const float
 }
 
 
+// the summed-gradient backward's g0 = dy (+ dy2) and g = g0 (* ELU' from y, where y is given) of element i = r * ld + c
+__device__ __forceinline__ float ln_elu_slope(float y) { return y > 0.f ? 1.f : y + 1.f; }
+__device__ __forceinline__ float ln_g0(const float* dy, int64_t i, const LnSum& a) { return a.dy2 ? dy[i] + a.dy2[i] : dy[i]; }
+__device__ __forceinline__ float ln_g(const float* dy, const float* y, int64_t i, const LnSum& a) {
+  const float g0 = ln_g0(dy, i, a);
+  return y ? g0 * ln_elu_slope(y[i]) : g0;
+}
+
 // wide rows: dz with the row re-read (dy fully read before dz, which may alias it, is written: the sums need all of it first,
 // and every element is then read and written by the same lane)
 template <typename... D>
@@ -275,7 +350,7 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd_wide(const float* dy, const 
                                                          int64_t ld, int64_t m, int cols, const float* __restrict__ mean,
                                                          const float* __restrict__ rstd, const float* __restrict__ gamma, float* dz,
                                                          D... dr) {
-  constexpr bool DROP = sizeof...(D) != 0;
+  constexpr bool DROP = ln_has<LnDrop, D...>, SUM = ln_has<LnSum, D...>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float n = (float)cols;
   for (int64_t r = (int64_t)blockIdx.x * LN_WAVES + wave; r < m; r += (int64_t)gridDim.x * LN_WAVES) {
@@ -284,15 +359,28 @@ __global__ __launch_bounds__(256) void k_ln_elu_bwd_wide(const float* dy, const 
     float* o = dz + r * ld;
     float s1 = 0.f, s2 = 0.f;
     for (int c = lane; c < cols; c += 64) {
-      const float yy = yr[c];
-      const float hh = dyr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      float hh;
+      if constexpr (SUM) {
+        hh = ln_g(dy, y, r * ld + c, dr...) * gamma[c];
+      } else {
+        const float yy = yr[c];
+        hh = dyr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      }
       s1 += hh;
       s2 += hh * ((ln_u(zr[c], (uint32_t)r, c, dr...) - mu) * rs);
     }
     const float c1 = wave_sum(s1) / n, c2 = wave_sum(s2) / n;
     for (int c = lane; c < cols; c += 64) {
-      const float yy = yr[c];
-      const float hh = dyr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      float hh;
+      if constexpr (SUM) {   // dy and dy2 at c are read here, by the lane that then writes dsum and dz at c
+        const LnSum a = ln_sum_of(dr...);
+        const float g0 = ln_g0(dy, r * ld + c, a);
+        hh = (y ? g0 * ln_elu_slope(yr[c]) : g0) * gamma[c];
+        if (a.dsum) a.dsum[r * ld + c] = g0;
+      } else {
+        const float yy = yr[c];
+        hh = dyr[c] * (yy > 0.f ? 1.f : yy + 1.f) * gamma[c];
+      }
       if constexpr (!DROP) {
         o[c] = rs * (hh - c1 - ((zr[c] - mu) * rs) * c2);
       } else {
@@ -320,8 +408,13 @@ __global__ __launch_bounds__(256) void k_ln_bwd_sums_wide(const float* __restric
     const int64_t rows_per = (m + gridDim.y - 1) / gridDim.y;
     const int64_t r0 = (int64_t)blockIdx.y * rows_per, r1 = min(m, r0 + rows_per);
     for (int64_t r = r0 + rl; r < r1; r += 4) {
-      const float yy = y[r * ld + c];
-      const float g = dy[r * ld + c] * (yy > 0.f ? 1.f : yy + 1.f);
+      float g;
+      if constexpr (ln_has<LnSum, D...>) {
+        g = ln_g(dy, y, r * ld + c, dr...);
+      } else {
+        const float yy = y[r * ld + c];
+        g = dy[r * ld + c] * (yy > 0.f ? 1.f : yy + 1.f);
+      }
       s1 += g;
       s2 += g * ((ln_u(z[r * ld + c], (uint32_t)r, c, dr...) - mean[r]) * rstd[r]);
     }
@@ -365,7 +458,14 @@ static inline unsigned ln_blocks(int64_t m, int64_t cap) {
   return (unsigned)(nb < cap ? nb : cap);
 }
 
-// `D... dr` below: nothing (the plain kernels) or one LnDrop (their dropout siblings), handed on behind the kernels' arguments
+// whether the pack's own pointers allow 16-byte accesses
+static inline bool ln_pack_aligned16() { return true; }
+static inline bool ln_pack_aligned16(const LnDrop&) { return true; }
+static inline bool ln_pack_aligned16(const LnRes& r) { return pqlk_aligned16(r.res); }
+static inline bool ln_pack_aligned16(const LnSum& a) { return pqlk_aligned16(a.dy2) && pqlk_aligned16(a.dsum); }   // (NULL counts as aligned)
+
+// `D... dr` below: nothing (the plain kernels), one LnDrop (their dropout siblings), or one LnRes (forward) / LnSum (backward) of the
+// skip connection, handed on behind the kernels' arguments
 template <int VPL, typename... D>
 static void ln_launch_fwd(bool vec, unsigned grid, hipStream_t s, const float* z, int64_t ld, int64_t m, int cols, const float* gamma,
                           const float* beta, float eps, float* y, float* mean, float* rstd, D... dr) {
@@ -397,7 +497,8 @@ static int ln_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const
   PQLK_REQUIRE(z && gamma && beta && y && mean && rstd, PQLK_E_NULL);
   PQLK_REQUIRE(m > 0 && cols > 0 && ld >= cols, PQLK_E_SHAPE);
   const unsigned grid = ln_blocks(m, PQLK_LN_ROW_BLOCKS);
-  const bool vec = pqlk_aligned16(z) && pqlk_aligned16(y) && pqlk_aligned16(gamma) && pqlk_aligned16(beta) && ld % 4 == 0;
+  const bool vec = pqlk_aligned16(z) && pqlk_aligned16(y) && pqlk_aligned16(gamma) && pqlk_aligned16(beta) && ld % 4 == 0 &&
+                   ln_pack_aligned16(dr...);
   hipStream_t s = pqlk_s(stream);
   if (cols <= 128) ln_launch_fwd<2>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd, dr...);
   else if (cols <= 256) ln_launch_fwd<4>(vec, grid, s, z, ld, m, (int)cols, gamma, beta, eps, y, mean, rstd, dr...);
@@ -413,14 +514,15 @@ static int ln_backward(const float* dy, const float* y, const float* z, int64_t 
                        const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
                        pqlk_stream_t stream, D... dr) {
   const bool params = dgamma || dbeta;
-  PQLK_REQUIRE(dy && y && z && mean && rstd && gamma && dz && (scratch || !params), PQLK_E_NULL);
+  PQLK_REQUIRE(dy && (y || ln_has<LnSum, D...>) && z && mean && rstd && gamma && dz && (scratch || !params), PQLK_E_NULL);
   PQLK_REQUIRE(m > 0 && cols > 0 && ld >= cols, PQLK_E_SHAPE);
   hipStream_t s = pqlk_s(stream);
   const int c = (int)cols;
   int chunks;
   if (cols <= LN_MAX_REG_COLS) {
     const unsigned grid = ln_blocks(m, params ? PQLK_LN_CHUNKS : PQLK_LN_ROW_BLOCKS);
-    const bool vec = pqlk_aligned16(dy) && pqlk_aligned16(y) && pqlk_aligned16(z) && pqlk_aligned16(gamma) && pqlk_aligned16(dz) && ld % 4 == 0;
+    const bool vec = pqlk_aligned16(dy) && pqlk_aligned16(y) && pqlk_aligned16(z) && pqlk_aligned16(gamma) && pqlk_aligned16(dz) && ld % 4 == 0 &&
+                     ln_pack_aligned16(dr...);
     if (cols <= 128) ln_launch_bwd<2>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch, dr...);
     else if (cols <= 256) ln_launch_bwd<4>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch, dr...);
     else if (cols <= 512) ln_launch_bwd<8>(vec, params, grid, s, dy, y, z, ld, m, c, mean, rstd, gamma, dz, scratch, dr...);
@@ -453,6 +555,19 @@ extern "C" int pqlk_ln_elu_backward(const float* dy, const float* y, const float
                                     const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
                                     pqlk_stream_t stream) {
   return ln_backward(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, dgamma, dbeta, scratch, stream);
+}
+
+// ---- skip-connection entries (the residual LayerNorm critic)
+extern "C" int pqlk_ln_res_forward(const float* z, int64_t ld, int64_t m, int32_t cols, const float* gamma, const float* beta, float eps,
+                                   const float* res, float* y, float* mean, float* rstd, pqlk_stream_t stream) {
+  PQLK_REQUIRE(res, PQLK_E_NULL);
+  return ln_forward(z, ld, m, cols, gamma, beta, eps, y, mean, rstd, stream, LnRes{res});
+}
+
+extern "C" int pqlk_ln_sum_backward(const float* dy, const float* dy2, const float* y, const float* z, int64_t ld, int64_t m, int32_t cols,
+                                    const float* mean, const float* rstd, const float* gamma, float* dsum, float* dz, float* dgamma,
+                                    float* dbeta, float* scratch, pqlk_stream_t stream) {
+  return ln_backward(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, dgamma, dbeta, scratch, stream, LnSum{dy2, dsum});
 }
 
 // ---- dropout entries: the mask law's constants are made here, on the host (include/pqlk.h)

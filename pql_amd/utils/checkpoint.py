@@ -237,6 +237,9 @@ def structure(cfg, obs_dim, act_dim):
             "algo.num_atoms": int(algo.get("num_atoms") or 0) if distl else 0,
             # (the width of the quantile critic's heads; 0 for every other class)
             "algo.num_quantiles": int(algo.get("num_quantiles") or 0) if cri.endswith("QuantileDoubleQ") else 0, "algo.nstep": int(algo.get("nstep") or 1),
+            # (the residual LayerNorm critic's own width and depth; 0 for every other class)
+            "algo.critic_width": int(algo.get("critic_width") or 0) if cri.endswith("DoubleQBroNet") else 0,
+            "algo.critic_blocks": int(algo.get("critic_blocks") or 0) if cri.endswith("DoubleQBroNet") else 0,
             "algo.memory_size": int(algo.get("memory_size") or 0),
             "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32"),
             # (the V-learner's target forwards: bf16 targets change every later step, so a run resumes in the dtype it was saved in)
@@ -248,9 +251,10 @@ def structure(cfg, obs_dim, act_dim):
 
 
 def check_structure(saved, current, has_rings=True):
-    # (a checkpoint from before a key existed was written with float32 targets, uniform replay and no quantile critic; prioritized, with
-    #  per-step refresh)
-    saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, "algo.num_quantiles": 0, **saved}
+    # (a checkpoint from before a key existed was written with float32 targets, uniform replay, no quantile and no residual critic;
+    #  prioritized, with per-step refresh)
+    saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, "algo.num_quantiles": 0,
+             "algo.critic_width": 0, "algo.critic_blocks": 0, **saved}
     saved.setdefault("algo.per.refresh", "step" if saved["algo.per.enabled"] else None)
     for key, want in saved.items():
         if key in ("algo.memory_size", "algo.replay_obs_dtype") and not has_rings:
