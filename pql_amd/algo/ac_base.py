@@ -13,7 +13,8 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.heads import CriticHead
-from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_critic_class, check_per_refresh, make_actor, make_critic
+from pql_amd.algo.critics import check_critic_class, make_critic
+from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_per_refresh, make_actor
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.prioritized_replay import per_beta, per_cfg  # noqa: F401  (per_beta: imported from here by its users)
@@ -24,7 +25,7 @@ class ActorCriticBase(PQLActor):
     TARGET_CRITIC = True   # False (CrossQ): the agent has no `critic_target` attribute at all
 
     def __init__(self, env, cfg):
-        check_critic_class(cfg)   # before anything is allocated
+        check_critic_class(cfg, agent=True)   # before anything is allocated
         check_per_refresh(cfg, f"algo={cfg.algo.name}")
         cfg.algo.v_learner_gpu = cfg.algo.get("v_learner_gpu", 0) or 0
         cfg.algo.p_learner_gpu = cfg.algo.get("p_learner_gpu", 0) or 0

@@ -21,12 +21,6 @@ from pql_amd.models.mlp import mlp_forward_raw, output_view
 class AgentCrossQ(ActorCriticBase):
     TARGET_CRITIC = False
 
-    def __init__(self, env, cfg):
-        # (crossQ.py:21,71,132-133: the target-policy actions come from a Polyak-averaged copy unless no_tgt_actor=True, the default)
-        if str(cfg.algo.cri_class) != "DoubleQBatchNorm":   # before anything is allocated
-            raise ValueError(f"CrossQ needs the BatchNorm critic: algo.cri_class=DoubleQBatchNorm, not {cfg.algo.cri_class}")
-        super().__init__(env, cfg)
-
     def _own_state(self):
         extra, opts = super()._own_state()   # stats: BatchNorm running moments
         return dict(extra, critic_stats=self.critic.stats, critic_batches=self.critic.num_batches_tracked), opts

@@ -18,9 +18,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.models import model_name_to_path
-from pql_amd.models.bronet import check_width_blocks
-from pql_amd.models.droq import check_dropout
-from pql_amd.models.mlp import PackedWeights, check_num_atoms, check_num_quantiles
+from pql_amd.models.mlp import PackedWeights
 from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
 from pql_amd.utils import dp as DP
 from pql_amd.utils import handoff as H
@@ -232,131 +230,6 @@ def check_per_refresh(cfg, where):
     if per is not None and per_refresh(per) != "step":
         raise ValueError(f"algo.per.refresh=run cannot run in {where}: it samples from the live tree and writes priorities back every step "
                          f"(algo.per.refresh=step); run is the PQL V-learner's mode (scripts/train_pql.py)")
-
-
-def check_critic_class(cfg, fused_learner=None):
-    """Refusals that follow from `algo.cri_class` (and, for the fused learners, `algo.per.enabled` with `algo.per.refresh`) alone, raised
-    before anything is allocated.  fused_learner: the name of a component whose launch sequences are built on the fused MLP kernels
-    (scripts/train_pql.py, PQLVLearner, PQLPLearner)."""
-    algo = cfg.algo
-    per = per_cfg(algo)
-    if fused_learner is not None and per is not None and per_refresh(per) != "run":
-        raise ValueError(f"algo.per.enabled=True cannot run in {fused_learner}: the PQL learners gather batches ahead and replay steps as one "
-                         f"hipGraph, which assumes a sampling distribution that does not change between hand-offs; prioritized replay works "
-                         f"in scripts/train_baselines.py (algo=ddpg_algo / sac_algo / crossq_algo), and in the PQL V-learner with "
-                         f"algo.per.refresh=run (the distribution frozen for each run of prefetched steps)")
-    cri = str(_cfg_get(algo, "cri_class"))
-    drop = _cfg_get(algo, "qr_drop", None)
-    if str(_cfg_get(algo, "name", "")) == "TQC":   # algo=tqc_algo is the quantile critic on the truncated soft target, nothing else
-        if not is_quantile(algo):
-            raise ValueError(f"algo=tqc_algo needs algo.cri_class=QuantileDoubleQ (got algo.cri_class={cri}): its soft truncated target and "
-                             f"its mean-of-critics actor loss are laws of the quantile heads; algo=sac_algo runs the scalar critics")
-        if drop is None:
-            raise ValueError("algo.qr_drop=null cannot run with algo=tqc_algo: the non-truncated soft quantile law (one whole target net "
-                             "per row, shifted by the entropy term) is not built; set algo.qr_drop to an integer from 0 to "
-                             "algo.num_quantiles - 1 (0 keeps every pooled atom)")
-    if drop is not None and not is_quantile(algo):
-        raise ValueError(f"algo.qr_drop={drop!r} needs algo.cri_class=QuantileDoubleQ (got algo.cri_class={cri}): it truncates the pooled "
-                         f"target atoms of the quantile critic; leave algo.qr_drop null with any other critic")
-    if cri.endswith("DoubleQLayerNorm"):
-        if _cfg_get(algo, "distl", False):
-            raise ValueError("algo.distl=True is not supported with algo.cri_class=DoubleQLayerNorm: the LayerNorm critic has no C51 head")
-        if fused_learner is not None:
-            raise ValueError(f"algo.cri_class=DoubleQLayerNorm cannot run in {fused_learner}, whose launch sequences are built on the fused "
-                             f"MLP kernels: the class is for algo=ddpg_algo / algo=sac_algo (scripts/train_baselines.py)")
-    if is_droq(algo):
-        if _cfg_get(algo, "distl", False):
-            raise ValueError("algo.distl=True is not supported with algo.cri_class=DoubleQDropoutLayerNorm: the dropout LayerNorm critic "
-                             "has no C51 head")
-        if fused_learner is not None:
-            raise ValueError(f"algo.cri_class=DoubleQDropoutLayerNorm cannot run in {fused_learner}, whose launch sequences are built on "
-                             f"the fused MLP kernels: the class is for algo=droq_algo / algo=sac_algo / algo=ddpg_algo "
-                             f"(scripts/train_baselines.py)")
-        if str(_cfg_get(algo, "name", "")) == "CrossQ":
-            raise ValueError("algo.cri_class=DoubleQDropoutLayerNorm cannot run with algo=crossq_algo: CrossQ is the BatchNorm critic on "
-                             "joint batches, without a target critic; the class is for algo=droq_algo / algo=sac_algo / algo=ddpg_algo")
-        check_dropout(_cfg_get(algo, "critic_dropout", 0.01))
-    if is_bronet(algo):
-        if _cfg_get(algo, "distl", False):
-            raise ValueError("algo.distl=True is not supported with algo.cri_class=DoubleQBroNet: the residual LayerNorm critic has no "
-                             "C51 head")
-        if fused_learner is not None:
-            raise ValueError(f"algo.cri_class=DoubleQBroNet cannot run in {fused_learner}, whose launch sequences are built on the fused "
-                             f"MLP kernels: the class is for algo=ddpg_algo / algo=sac_algo (scripts/train_baselines.py)")
-        if str(_cfg_get(algo, "name", "")) == "CrossQ":
-            raise ValueError("algo.cri_class=DoubleQBroNet cannot run with algo=crossq_algo: CrossQ is the BatchNorm critic on joint "
-                             "batches, without a target critic; the class is for algo=ddpg_algo / algo=sac_algo")
-        bronet_shape(algo)
-    if is_quantile(algo):
-        if _cfg_get(algo, "distl", False):
-            raise ValueError("algo.distl=True is not supported with algo.cri_class=QuantileDoubleQ: algo.distl selects the C51 head and "
-                             "the class the quantile head -- drop algo.distl=True to train the quantile critic")
-        name = str(_cfg_get(algo, "name", ""))
-        if name in ("SAC", "CrossQ"):
-            why = "the entropy shift of the SAC target has" if name == "SAC" else "the BatchNorm critic has"
-            tail = " (the maximum-entropy agent on this class is algo=tqc_algo)" if name == "SAC" else ""
-            raise ValueError(f"algo.cri_class=QuantileDoubleQ cannot run with algo={name.lower()}_algo: {why} no N-wide head; the class "
-                             f"is for algo=pql_algo and algo=ddpg_algo{tail}")
-        if str(_cfg_get(algo, "target_dtype", "float32")) == "bfloat16":
-            raise ValueError("algo.target_dtype=bfloat16 is not supported with algo.cri_class=QuantileDoubleQ: the bf16 target forward "
-                             "has not been taken to the quantile head (use algo.target_dtype=float32)")
-        check_num_quantiles(_cfg_get(algo, "num_quantiles", 32))
-        kappa = _cfg_get(algo, "huber_kappa", 1.0)
-        if not float(kappa) > 0.0:
-            raise ValueError(f"algo.huber_kappa must be > 0, got {kappa!r}")
-        if drop is not None:
-            n = int(_cfg_get(algo, "num_quantiles", 32))
-            ok = isinstance(drop, (int, float)) and not isinstance(drop, bool) and int(drop) == drop
-            if not ok or not 0 <= int(drop) <= n - 1:
-                raise ValueError(f"algo.qr_drop must be null or an integer from 0 to algo.num_quantiles - 1 = {n - 1} (the atoms dropped "
-                                 f"per target net; at least one per net is kept), got {drop!r}")
-
-
-def is_droq(algo):
-    """Whether `algo.cri_class` names the dropout LayerNorm critic (DroQ)."""
-    return str(_cfg_get(algo, "cri_class")).endswith("DoubleQDropoutLayerNorm")
-
-
-def is_bronet(algo):
-    """Whether `algo.cri_class` names the residual LayerNorm critic (BroNet)."""
-    return str(_cfg_get(algo, "cri_class")).endswith("DoubleQBroNet")
-
-
-def bronet_shape(algo):
-    """(algo.critic_width, algo.critic_blocks), checked; a config without the keys gets the defaults, a null is refused like any other
-    non-integer."""
-    return check_width_blocks(algo.get("critic_width", 512), algo.get("critic_blocks", 2))
-
-
-def is_quantile(algo):
-    """Whether `algo.cri_class` names the quantile-regression critic."""
-    return str(_cfg_get(algo, "cri_class")).endswith("QuantileDoubleQ")
-
-
-def make_critic(cfg, obs_dim, action_dim, device):
-    """The critic `cfg.algo` names, freshly initialised on `device` (consumes the CPU generator like any module constructor)."""
-    algo = cfg.algo
-    check_critic_class(cfg)
-    distl = _cfg_get(algo, "distl", False)   # (the baselines' configs need not carry the key)
-    if distl and "Distributional" not in algo.cri_class:
-        algo.cri_class = "Distributional" + algo.cri_class  # same rewrite as the reference (:30-31)
-    cri_class = load_class_from_path(algo.cri_class, model_name_to_path[algo.cri_class])
-    hidden = _cfg_get(algo, "hidden_layers")
-    hidden = list(hidden) if hidden is not None else None
-    if distl:
-        check_num_atoms(algo.num_atoms)   # before anything is allocated: a wrong value fails here, not after the warm-up rollout
-    with torch.cuda.device(device):
-        if distl:
-            return cri_class(obs_dim, action_dim, v_min=algo.v_min, v_max=algo.v_max, num_atoms=algo.num_atoms, device=device,
-                             hidden_layers=hidden).to(device)
-        if is_quantile(algo):
-            return cri_class(obs_dim, action_dim, num_quantiles=int(_cfg_get(algo, "num_quantiles", 32)), hidden_layers=hidden).to(device)
-        if is_droq(algo):
-            return cri_class(obs_dim, action_dim, hidden_layers=hidden, dropout=float(_cfg_get(algo, "critic_dropout", 0.01))).to(device)
-        if is_bronet(algo):   # (its own width and depth; algo.hidden_layers stays the actor's)
-            width, blocks = bronet_shape(algo)
-            return cri_class(obs_dim, action_dim, width=width, blocks=blocks).to(device)
-        return cri_class(obs_dim, action_dim, hidden_layers=hidden).to(device)
 
 
 def make_actor(cfg, obs_dim, action_dim, device):

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.algo.learner import _AdamState, _cfg_get, apply_optimizer, make_actor, make_critic
+from pql_amd.algo.critics import make_critic
+from pql_amd.algo.learner import _AdamState, _cfg_get, apply_optimizer, make_actor
 from pql_amd.algo.pql_actor import DeviceTracker, PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.utils.info_track import InfoTrackers

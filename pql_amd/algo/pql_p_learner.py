@@ -17,8 +17,9 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.heads import CriticHead
-from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip,
-                                  check_critic_class, load_artifact, make_actor, make_critic, pump, resident_norm)
+from pql_amd.algo.critics import check_critic_class, make_critic
+from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, f32_recip, load_artifact,
+                                  make_actor, pump, resident_norm)
 from pql_amd.models.mlp import PackedWeights, default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.replay.simple_replay import RecordRing, _obs_width, cfg_obs_dtype, ring_plan
 from pql_amd.utils import handoff as H

@@ -21,8 +21,9 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.heads import CriticHead
-from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, check_critic_class,
-                                  graph_collective_enabled, load_artifact, make_actor, make_critic, pump, resident_norm)
+from pql_amd.algo.critics import check_critic_class, check_target_dtype, make_critic
+from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, graph_collective_enabled,
+                                  load_artifact, make_actor, pump, resident_norm)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
                                 output_view)
 from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer, per_beta, per_cfg
@@ -98,8 +99,7 @@ class PQLVLearner(Learner):
             raise ValueError(f"algo.target_dtype must be float32 or bfloat16, got {value!r}")
         self.flush_priorities()   # (the workspace, and with it the |TD| slabs, is rebuilt below)
         if value == "bfloat16":
-            if self.head.kind == "quantile":   # (the config's own refusal: check_critic_class)
-                raise ValueError("algo.target_dtype=bfloat16 is not supported with algo.cri_class=QuantileDoubleQ")
+            check_target_dtype(self.cfg.algo, value)   # (the class's own rule, as `check_critic_class` applied it to the config's value)
             if not self._fused:
                 raise ValueError("algo.target_dtype=bfloat16 needs the fused path (algo.fused=True)")
             hidden = _cfg_get(self.cfg.algo, "hidden_layers")

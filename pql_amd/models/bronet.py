@@ -44,22 +44,30 @@ from pql_amd.models.layernorm import LN_EPS, DoubleQLayerNorm
 MAX_BLOCKS = 16
 
 
-def check_width_blocks(width, blocks):
-    """`algo.critic_width` (an integer >= 1) and `algo.critic_blocks` (an integer from 0 to 16); -> (width, blocks) as ints."""
-    whole = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and int(v) == v  # noqa: E731
-    if not whole(width) or int(width) < 1:
+def _whole(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and int(v) == v
+
+
+def check_width(width):
+    """`algo.critic_width`: an integer >= 1; -> the int."""
+    if not _whole(width) or int(width) < 1:
         raise ValueError(f"algo.critic_width must be an integer >= 1 (the width of every hidden layer of DoubleQBroNet), got {width!r}")
-    if not whole(blocks) or not 0 <= int(blocks) <= MAX_BLOCKS:
+    return int(width)
+
+
+def check_blocks(blocks):
+    """`algo.critic_blocks`: an integer from 0 to 16; -> the int."""
+    if not _whole(blocks) or not 0 <= int(blocks) <= MAX_BLOCKS:
         raise ValueError(f"algo.critic_blocks must be an integer from 0 to {MAX_BLOCKS} (the residual blocks of DoubleQBroNet; 0 is "
                          f"DoubleQLayerNorm with one hidden layer), got {blocks!r}")
-    return int(width), int(blocks)
+    return int(blocks)
 
 
 class DoubleQBroNet(DoubleQLayerNorm):
     key_prefixes = ("net_q1.", "net_q2.")
 
     def __init__(self, state_dim, act_dim, width=512, blocks=2):
-        self.width, self.blocks = check_width_blocks(width, blocks)   # before anything is allocated
+        self.width, self.blocks = check_width(width), check_blocks(blocks)   # before anything is allocated
         super().__init__(state_dim, act_dim, hidden_layers=[self.width] * (2 * self.blocks + 1))
         self.init_kwargs = dict(state_dim=self.state_dim, act_dim=self.act_dim, width=self.width, blocks=self.blocks)
 

@@ -223,23 +223,19 @@ def refuse(cfg, world=1):
 def structure(cfg, obs_dim, act_dim):
     """The part of the config a checkpoint's tensors depend on.  Learning rates, batch_size, max_step / max_time and logging keys
     are free to differ between the run that saved and the run that resumes."""
+    from pql_amd.algo import critics   # (loads libpqlk.so through the model files: put off to this call, which every caller makes with it loaded)
     algo = cfg.algo
     hidden = algo.get("hidden_layers")
-    cri = str(algo.get("cri_class"))
-    if cri.startswith("Distributional"):   # the V-learner rewrites cri_class when algo.distl is set
-        cri = cri[len("Distributional"):]
     distl = bool(algo.get("distl") or False)
     per = algo.get("per") or {}
     per_on = bool(per.get("enabled") or False)
     return {"task.obs_dim": int(obs_dim), "task.act_dim": int(act_dim), "num_envs": int(cfg.num_envs),
             "algo.hidden_layers": None if hidden is None else [int(h) for h in hidden],
-            "algo.act_class": str(algo.get("act_class")), "algo.cri_class": cri, "algo.distl": distl,
+            "algo.act_class": str(algo.get("act_class")), "algo.distl": distl,
+            "algo.cri_class": critics.critic_rules(algo).name,   # (without the Distributional the V-learner puts in front when algo.distl is set)
             "algo.num_atoms": int(algo.get("num_atoms") or 0) if distl else 0,
-            # (the width of the quantile critic's heads; 0 for every other class)
-            "algo.num_quantiles": int(algo.get("num_quantiles") or 0) if cri.endswith("QuantileDoubleQ") else 0, "algo.nstep": int(algo.get("nstep") or 1),
-            # (the residual LayerNorm critic's own width and depth; 0 for every other class)
-            "algo.critic_width": int(algo.get("critic_width") or 0) if cri.endswith("DoubleQBroNet") else 0,
-            "algo.critic_blocks": int(algo.get("critic_blocks") or 0) if cri.endswith("DoubleQBroNet") else 0,
+            # (the class's own keys -- the quantile heads' width, the residual critic's width and depth; 0 for every other class)
+            **critics.structure_keys(algo), "algo.nstep": int(algo.get("nstep") or 1),
             "algo.memory_size": int(algo.get("memory_size") or 0),
             "algo.replay_obs_dtype": str(algo.get("replay_obs_dtype") or "float32"),
             # (the V-learner's target forwards: bf16 targets change every later step, so a run resumes in the dtype it was saved in)
@@ -251,10 +247,10 @@ def structure(cfg, obs_dim, act_dim):
 
 
 def check_structure(saved, current, has_rings=True):
-    # (a checkpoint from before a key existed was written with float32 targets, uniform replay, no quantile and no residual critic;
-    #  prioritized, with per-step refresh)
-    saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, "algo.num_quantiles": 0,
-             "algo.critic_width": 0, "algo.critic_blocks": 0, **saved}
+    # (a checkpoint from before a key existed was written with float32 targets, uniform replay, none of the critic classes that have
+    #  structure keys of their own; prioritized, with per-step refresh)
+    from pql_amd.algo.critics import STRUCTURE_DEFAULTS
+    saved = {"algo.target_dtype": "float32", "algo.per.enabled": False, "algo.per.alpha": None, **STRUCTURE_DEFAULTS, **saved}
     saved.setdefault("algo.per.refresh", "step" if saved["algo.per.enabled"] else None)
     for key, want in saved.items():
         if key in ("algo.memory_size", "algo.replay_obs_dtype") and not has_rings:

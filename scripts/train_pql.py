@@ -35,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import pql_amd  # noqa: E402,F401
-from pql_amd.algo.learner import check_critic_class  # noqa: E402
+from pql_amd.algo.critics import check_critic_class  # noqa: E402
 from pql_amd.algo.pql_actor import PQLActor  # noqa: E402
 from pql_amd.algo.pql_p_learner import PQLPLearner, asyn_p_learner  # noqa: E402
 from pql_amd.algo.pql_v_learner import PQLVLearner, asyn_v_learner  # noqa: E402

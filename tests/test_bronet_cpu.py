@@ -143,7 +143,7 @@ def _script(name):
 def test_config_keys_defaults_and_the_factory(monkeypatch):
     import contextlib
     monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())   # (make_critic selects the device; none here)
-    from pql_amd.algo.learner import check_critic_class, make_critic
+    from pql_amd.algo.critics import check_critic_class, make_critic
     for name in ("ddpg_algo", "sac_algo", "pql_algo"):
         algo = _cfg(name).algo
         assert (algo.critic_width, algo.critic_blocks, algo.cri_class) == (512, 2, "DoubleQ")
@@ -183,7 +183,7 @@ def test_fused_learners_refuse_the_class():
 
 def test_crossq_tqc_and_qr_drop_refuse_the_class():
     from pql_amd.algo.crossq import AgentCrossQ
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     with pytest.raises(ValueError, match=r"algo\.cri_class=DoubleQBroNet cannot run with algo=crossq_algo"):
         check_critic_class(_cfg("crossq_algo", BRO))
     with pytest.raises(ValueError, match=r"algo\.cri_class.*DoubleQBroNet"):
@@ -217,7 +217,7 @@ def test_critic_blocks_refused(bad):
 
 
 def test_other_classes_do_not_read_the_keys():
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     check_critic_class(_cfg("ddpg_algo", "algo.critic_width=0", "algo.critic_blocks=99"))
     check_critic_class(_cfg("sac_algo", "algo.cri_class=DoubleQLayerNorm", "algo.critic_width=-1"))
 

@@ -89,7 +89,7 @@ def test_num_atoms_is_checked_where_the_critic_is_built():
 
 
 def test_make_critic_refuses_more_than_256_atoms_before_it_allocates():
-    from pql_amd.algo.learner import make_critic
+    from pql_amd.algo.critics import make_critic
     from pql_amd.utils.cfg import load_cfg
     cfg = load_cfg(["algo.distl=True", "algo.num_atoms=257"])
     with pytest.raises(ValueError, match="256"):

@@ -212,7 +212,7 @@ def _script(name):
 
 
 def test_droq_algo_composes_to_sac_on_the_dropout_critic():
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     from pql_amd.models import model_name_to_path
     algo = _cfg("droq_algo").algo
     assert (algo.name, algo.cri_class, algo.critic_dropout, algo.update_times) == ("SAC", "DoubleQDropoutLayerNorm", 0.01, 20)
@@ -257,7 +257,7 @@ def test_fused_learners_refuse_the_class():
 
 
 def test_crossq_and_tqc_refuse_the_class():
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     with pytest.raises(ValueError, match=r"algo\.cri_class=DoubleQDropoutLayerNorm cannot run with algo=crossq_algo"):
         check_critic_class(_cfg("crossq_algo", DROQ))
     from pql_amd.algo.crossq import AgentCrossQ
@@ -272,5 +272,5 @@ def test_critic_dropout_outside_the_unit_interval_refused(bad):
     from pql_amd.algo.sac import AgentSAC
     with pytest.raises(ValueError, match=r"algo\.critic_dropout must be a number in \[0, 1\)"):
         AgentSAC(None, _cfg("droq_algo", f"algo.critic_dropout={bad}"))
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     check_critic_class(_cfg("sac_algo", f"algo.critic_dropout={bad}"))    # only this class reads the key

@@ -68,7 +68,7 @@ def test_pql_accepts_run():
     """`check_critic_class` lets the three PQL components pass; without a GPU the learners then stop at their device check, which
     comes after every refusal."""
     from pql_amd import _lib as L
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     cfg = _cfg("pql_algo", *RUN)
     for name in ("scripts/train_pql.py", "PQLVLearner", "PQLPLearner"):
         check_critic_class(cfg, name)

@@ -115,7 +115,7 @@ def test_q_min_is_the_min_of_the_means(monkeypatch):
 
 @pytest.mark.parametrize("bad", [1, 65, 2.5])
 def test_num_quantiles_out_of_range_names_the_key(bad):
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     from pql_amd.models.mlp import QuantileDoubleQ, check_num_quantiles
     for make in (lambda: check_num_quantiles(bad), lambda: QuantileDoubleQ((8,), 2, num_quantiles=bad),
                  lambda: check_critic_class(_cfg("pql_algo", QR, f"algo.num_quantiles={bad}"), "PQLVLearner")):
@@ -130,7 +130,7 @@ def test_num_quantiles_out_of_range_names_the_key(bad):
 def test_config_keys_and_make_critic(algo, monkeypatch):
     import contextlib
     monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())   # (make_critic selects the device; none here)
-    from pql_amd.algo.learner import make_critic
+    from pql_amd.algo.critics import make_critic
     from pql_amd.models.mlp import DoubleQ, QuantileDoubleQ
     cfg = _cfg(algo)
     assert cfg.algo.num_quantiles == 32 and cfg.algo.huber_kappa == 1.0 and cfg.algo.cri_class == "DoubleQ"
@@ -143,7 +143,7 @@ def test_config_keys_and_make_critic(algo, monkeypatch):
 
 
 def test_refusals_name_their_keys():
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     with pytest.raises(ValueError, match=r"algo\.distl=True is not supported with algo\.cri_class=QuantileDoubleQ.*drop algo\.distl=True"):
         check_critic_class(_cfg("pql_algo", QR, "algo.distl=True"), "PQLVLearner")
     with pytest.raises(ValueError, match=r"algo\.cri_class=QuantileDoubleQ cannot run with algo=sac_algo.*entropy shift"):

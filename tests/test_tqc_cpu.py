@@ -102,7 +102,8 @@ def test_dyadic_cases_are_exact_in_fp32():
 # ------------------------------------------------------------------------------------------------ config, refusals
 @pytest.mark.parametrize("algo", ["pql_algo", "ddpg_algo"])
 def test_key_defaults_to_null_and_accepts_the_range(algo):
-    from pql_amd.algo.learner import check_critic_class, qr_drop, qr_targets
+    from pql_amd.algo.critics import check_critic_class
+    from pql_amd.algo.learner import qr_drop, qr_targets
     cfg = _cfg(algo)
     assert cfg.algo.qr_drop is None and qr_drop(cfg.algo) is None and qr_targets(cfg.algo, 32) == 32
     check_critic_class(cfg)
@@ -117,7 +118,7 @@ def test_key_defaults_to_null_and_accepts_the_range(algo):
 
 @pytest.mark.parametrize("cri", ["DoubleQ", "DoubleQLayerNorm"])
 def test_key_with_another_critic_is_refused_naming_both_keys(cri):
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     with pytest.raises(ValueError, match=r"algo\.qr_drop=2 needs algo\.cri_class=QuantileDoubleQ"):
         check_critic_class(_cfg("ddpg_algo", f"algo.cri_class={cri}", "algo.qr_drop=2"))
     with pytest.raises(ValueError, match=r"algo\.qr_drop=0 needs algo\.cri_class=QuantileDoubleQ"):
@@ -126,7 +127,7 @@ def test_key_with_another_critic_is_refused_naming_both_keys(cri):
 
 @pytest.mark.parametrize("n,bad", [(32, -1), (32, 32), (8, 8), (8, 2.5), (2, 2), (8, "half")])
 def test_key_out_of_range_names_the_key_the_range_and_num_quantiles(n, bad):
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     with pytest.raises(ValueError, match=rf"algo\.qr_drop must be null or an integer from 0 to algo\.num_quantiles - 1 = {n - 1}\b"):
         check_critic_class(_cfg("pql_algo", QR, f"algo.num_quantiles={n}", f"algo.qr_drop={bad}"), "PQLVLearner")
 

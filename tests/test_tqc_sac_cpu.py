@@ -96,7 +96,8 @@ def test_dyadic_cases_are_exact_in_fp32():
 
 # ------------------------------------------------------------------------------------------------ config, refusals, plumbing
 def test_config_composes_with_the_papers_values_and_sacs_keys():
-    from pql_amd.algo.learner import check_critic_class, qr_drop, qr_targets
+    from pql_amd.algo.critics import check_critic_class
+    from pql_amd.algo.learner import qr_drop, qr_targets
     cfg, sac = _cfg("tqc_algo"), _cfg("sac_algo")
     a = cfg.algo
     assert (a.name, a.act_class, a.cri_class, a.num_quantiles, a.qr_drop) == ("TQC", "TanhDiagGaussianMLPPolicy", "QuantileDoubleQ", 25, 2)
@@ -132,7 +133,7 @@ def test_new_refusals_name_their_keys_and_come_before_anything_is_allocated():
 
 
 def test_sac_keeps_refusing_the_quantile_critic_and_points_at_the_new_algorithm():
-    from pql_amd.algo.learner import check_critic_class
+    from pql_amd.algo.critics import check_critic_class
     from pql_amd.algo.sac import AgentSAC
     pat = r"algo\.cri_class=QuantileDoubleQ cannot run with algo=sac_algo.*entropy shift.*algo=tqc_algo"
     with pytest.raises(ValueError, match=pat):
