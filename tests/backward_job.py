@@ -1,42 +1,17 @@
 """The guarded buffers and the one-case job shared by the exact backward tests, tests/test_backward_paths_gpu.py and
 tests/test_td_paths_gpu.py: every written buffer has SLACK floats of poison behind it, which must come back intact, and can start
-as NaN; every read buffer has 1.0 in front of and behind it, which would move a sum by a whole unit.  A HIP error ends the
-session: nothing more may be started on a device that has faulted.  (tests/guarded.py holds the other kernel tests' Guarded, which
-places its tensor off a 16-byte boundary instead.)"""
+as NaN; every read buffer has 1.0 in front of (tests/guarded.py's off=SLACK) and behind it, which would move a sum by a whole unit.
+A HIP error ends the session: nothing more may be started on a device that has faulted."""
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
 
 import backward_cases as bc
-import reduction_cases as rc
+from guarded import Guarded, T  # noqa: F401
 
-T = rc.T
 POISON, SLACK, IN_ONE = bc.POISON, bc.SLACK, bc.IN_ONE
 NAN = float("nan")
-
-
-class Guarded:
-    """A device tensor of `shape` with `fill` in SLACK elements behind it and, for `front`, in SLACK elements in front (the tensor
-    stays 256-byte aligned)."""
-
-    def __init__(self, dev, shape, fill, init=None, front=False, body=None, dtype=torch.float32):
-        n, off = int(np.prod(shape)), SLACK if front else 0
-        self.full = torch.full((off + n + SLACK,), fill, dtype=dtype, device=dev)
-        self.t = self.full[off: off + n].view(*shape)
-        self.n, self.off, self.fill = n, off, fill
-        if init is not None:
-            self.t.copy_(T(np.asarray(init)))
-        elif body is not None:
-            self.t.fill_(body)
-        assert self.t.data_ptr() % 16 == 0
-
-    def intact(self):
-        return bool((self.full[: self.off] == self.fill).all()) and bool((self.full[self.off + self.n:] == self.fill).all())
-
-    def host(self):
-        return self.t.cpu().numpy()
 
 
 def _sync_or_stop(what):
@@ -60,14 +35,14 @@ class _Job:
         self.dev, self.case = dev, case
         self.desc = L.mlp_desc(case.dims, case.nets)
         self.want_grads, self.want_dx = case.form in ("gdx", "g"), case.form != "g"
-        self.arena = Guarded(dev, (bc.net_stride(case.dims) * case.nets,), IN_ONE, bc.arena(case), front=True)
-        self.acts = Guarded(dev, (bc.acts_floats(case.dims, case.nets, case.B),), IN_ONE, bc.stash(case) if stash is None else stash, front=True)
-        self.x = Guarded(dev, (case.B, case.ldx), IN_ONE, bc.x_input(case), front=True)
-        self.dy = Guarded(dev, (case.nets, case.B, bc.ld(case.dims[-1])), IN_ONE, bc.dy_input(case) if dy is None else dy, front=True)
+        self.arena = Guarded(dev, (bc.net_stride(case.dims) * case.nets,), IN_ONE, bc.arena(case), off=SLACK)
+        self.acts = Guarded(dev, (bc.acts_floats(case.dims, case.nets, case.B),), IN_ONE, bc.stash(case) if stash is None else stash, off=SLACK)
+        self.x = Guarded(dev, (case.B, case.ldx), IN_ONE, bc.x_input(case), off=SLACK)
+        self.dy = Guarded(dev, (case.nets, case.B, bc.ld(case.dims[-1])), IN_ONE, bc.dy_input(case) if dy is None else dy, off=SLACK)
         self.ld_dx, self.ld_tanh = bc.dx_geometry(case)
         self.tanh = None
         if case.form == "slice":
-            self.tanh = Guarded(dev, (case.B, self.ld_tanh), IN_ONE, front=True)
+            self.tanh = Guarded(dev, (case.B, self.ld_tanh), IN_ONE, off=SLACK)
             self.tanh.t[:, : case.cols] = T(bc.tanh_input(case)).to(dev)
         self.inputs = [g for g in (self.arena, self.acts, self.x, self.dy, self.tanh) if g is not None]
         self.before = [g.full.clone() for g in self.inputs]

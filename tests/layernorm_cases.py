@@ -20,9 +20,9 @@ import torch
 import torch.nn.functional as F
 
 import detdata as dd
+from support import T  # noqa: F401  (re-exported)
 
 F32 = np.float32
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
 EPS = 1e-5
 POISON, SLACK = 5.0, 64          # as tests/reduction_cases.py
 

@@ -360,7 +360,7 @@ def gae_inputs(Tn, n):
 
 
 def gae_reference(rew, done, val, nv, nd, gamma, lam, gae, tmo):
-    """test_ppo_gpu._gae_torch (ppo.py:88-124) restated in fp32 numpy, op for op; tmo = None: no time-outs."""
+    """`_gae_torch` below (ppo.py:88-124) restated in fp32 numpy, op for op; tmo = None: no time-outs."""
     Tn = rew.shape[0]
     g, gl, one = F32(gamma), F32(gamma * lam), F32(1)     # gamma * lambda in double, then one fp32 rounding, as torch's scalar
     adv, ret = np.zeros_like(rew), np.zeros_like(rew)
@@ -393,3 +393,30 @@ def elementwise_inputs():
 
 def noise_reference(act, draw, sigma, lo, hi):
     return np.minimum(np.maximum((act + (draw * sigma).astype(F32)).astype(F32), F32(lo)), F32(hi)).astype(F32)
+
+
+def _gae_torch(rew, dones, values, next_value, next_done, gamma, lam, gae, timeout):
+    """ppo.py:88-124, op for op (one torch launch per op: no contraction)."""
+    Tn = rew.shape[0]
+    next_value = next_value.reshape(1, -1)
+    if gae:
+        adv = torch.zeros_like(rew)
+        last = 0
+        for t in reversed(range(Tn)):
+            if t == Tn - 1:
+                nnt, nv = 1.0 - next_done, next_value
+            else:
+                nnt, nv = 1.0 - dones[t + 1], values[t + 1]
+            nnt2 = torch.logical_xor(nnt, timeout[t]) if timeout is not None else nnt
+            delta = rew[t] + gamma * nv * nnt2 - values[t]
+            last = delta + gamma * lam * nnt * last
+            adv[t] = last
+        return adv, adv + values
+    ret = torch.zeros_like(rew)
+    for t in reversed(range(Tn)):
+        if t == Tn - 1:
+            nnt, nr = 1.0 - next_done, next_value
+        else:
+            nnt, nr = 1.0 - dones[t + 1], ret[t + 1]
+        ret[t] = rew[t] + gamma * nnt * nr
+    return ret - values, ret

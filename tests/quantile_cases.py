@@ -4,8 +4,14 @@ learner tests.  Nothing here runs on a GPU; tests/test_quantile_cpu.py checks th
 
 u = 2^-24 below is the unit roundoff of fp32 round-to-nearest: fl(x op y) = (x op y)(1 + e), |e| <= u.
 """
+import functools
+
 import numpy as np
 import torch
+
+import detdata as dd
+import learner_harness as lh
+from support import T
 
 U = 2.0 ** -24
 SLOP = 1.0 + 1e-3   # covers the second-order terms (products of two roundings, each <= u ~ 6e-8) dropped in the bounds below
@@ -293,3 +299,49 @@ def fold_ref(parts, scale):
         v = v + v[:, lanes ^ o]
     w = v[:, 0]
     return np.float32(np.float32(np.float32(w[0] + w[1]) + np.float32(w[2] + w[3])) * np.float32(scale))
+
+
+# ------------------------------------------------------------------------------------------------ shared by the kernel tests
+def _heads(dev, a, ld):
+    """(2, B, N) -> a device (2, B, ld) block whose pad columns hold NaN: a kernel that read them would show it."""
+    _, B, N = a.shape
+    t = torch.full((2, B, ld), float("nan"), dtype=torch.float32, device=dev)
+    t[:, :, :N] = T(a).to(dev)
+    return t
+
+
+def _check_buffers(got, per=False):
+    assert got["intact"], "a guard word behind dy, scratch or abs_td was overwritten"
+    assert (got["pad"] == 0).all(), "pad columns of dy must be written as zero"
+    assert np.isfinite(got["dy"]).all() and np.isfinite(got["parts"]).all()
+    assert np.isfinite(got["abs_td"]).all() if per else np.isnan(got["abs_td"]).all()   # the plain instance never touches abs_td
+
+
+# ------------------------------------------------------------------------------------------------ the learner tests' toy shape
+O, A, B, K, HID = 8, 2, 256, 4, (64, 64)
+QR = "algo.cri_class=QuantileDoubleQ"
+
+
+def _cfg(N, *extra, graph=False, memory=4096, algo="pql_algo"):
+    from pql_amd.utils.cfg import load_cfg
+    base = [f"algo={algo}", "task.name=Toy", f"algo.batch_size={B}", f"algo.memory_size={memory}", QR, f"algo.num_quantiles={N}"]
+    if algo == "pql_algo":
+        base += ["algo.v_learner_gpu=0", "algo.p_learner_gpu=0", "algo.num_gpus=1", f"algo.prefetch_steps={K}", f"algo.graph={graph}"]
+    else:
+        base += ["num_envs=64", "device=cuda:0", "sim_device=cuda:0"]
+    cfg = load_cfg(base + list(extra))
+    cfg.algo.hidden_layers = list(HID)
+    return cfg
+
+
+def _weights(N):
+    return dd.doubleq_state(O, A, N, 21 + N, HID), dd.mlp_state(O, A, 11, HID)
+
+
+_fill = functools.partial(lh._fill, O, A, rew=0.5)
+_rows = functools.partial(lh._rows, O, A)
+_run = functools.partial(lh._run, n=K)
+
+
+def _learner(N, *extra, graph, cap=4096, rows=1500, seed=11):
+    return lh._learner(lambda: _cfg(N, *extra, graph=graph, memory=cap), O, A, rows, seed)

@@ -8,9 +8,9 @@ import numpy as np
 import torch
 
 import detdata as dd
+from support import T  # noqa: F401  (re-exported)
 
 F32 = np.float32
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
 
 POISON = 5.0          # output slack / pad columns: must come back bit-identical ("untouched") or 0 ("written as zero")
 IN_ONE = 1.0          # input slack of the exact-integer designs: an over-read moves the sum by a whole unit

@@ -17,18 +17,13 @@ import torch
 import backward_cases as bc
 import reduction_cases as rc
 from backward_job import Guarded, _Job, _returned, _sync_or_stop
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 T = rc.T
 POISON, SLACK, IN_ONE = bc.POISON, bc.SLACK, bc.IN_ONE
 NAN = float("nan")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 @pytest.mark.parametrize("name", [c.name for c in bc.CASES])

@@ -8,16 +8,11 @@ import pytest
 import torch
 
 import bf16_model as M
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TANH_ATOL = 1e-5   # the absolute bar of the fp32 actor forward: tests/test_kernels_gpu.py:369 (test_actor_module)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def build(dims, n_nets, W, b, dev):

@@ -5,17 +5,12 @@ import torch
 
 import bf16_model as M
 import detdata as dd
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 O, A, B, HIDDEN = 8, 2, 256, [128, 128]
 T = lambda a: torch.from_numpy(a.copy())   # noqa: E731
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def make_cfg(target_dtype="bfloat16", graph=False, distl=False, rng="auto", memory=3000, hidden=HIDDEN):

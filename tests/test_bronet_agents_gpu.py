@@ -1,29 +1,25 @@
 """`DoubleQBroNet` (pql_amd/models/bronet.py) and AgentDDPG / AgentSAC running with it: the module against float64 autograd of the
 torch twin (tests/bronet_cases.py), the K = 0 tie to `DoubleQLayerNorm`, the target's own workspace, and the agents' ties,
 determinism and resume.  Small shapes: obs 8, act 2, batch 37, widths 64 (16-byte rows) and 130 (ragged), K = 2."""
-import importlib
+import functools
 from copy import deepcopy
 
 import numpy as np
 import pytest
 import torch
 
+import agent_harness as ah
 import bronet_cases as bc
 import detdata as dd
 import task_cases as tc
+from agent_harness import _same, _state
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
 O, A, B, K = 8, 2, 37, 2
 WIDTHS = [64, 130]
 LN, BRO = "algo.cri_class=DoubleQLayerNorm", "algo.cri_class=DoubleQBroNet"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # =========================================================================== the module
@@ -34,17 +30,7 @@ def _critic(dev, W, blocks=K, seed=43):
     return q
 
 
-def _x(dev, seed=73):
-    from pql_amd import _lib as L
-    from pql_amd.models.mlp import pad_cols
-    x = np.concatenate([dd.uniform((B, O), seed, -2, 2), dd.uniform((B, A), seed + 1, -1, 1)], axis=1)
-    return pad_cols(T(x).to(dev), L.ld(O + A))
-
-
-def _dq(dev):
-    dq = torch.zeros((2, B, 32), device=dev)
-    dq[:, :, 0] = T(dd.uniform((2, B), 76, -1, 1)).to(dev)
-    return dq
+_x, _dq = functools.partial(ah._x, O=O, A=A, B=B), functools.partial(ah._dq, B=B)
 
 
 def _float64(q, x, dq):
@@ -149,58 +135,10 @@ def test_target_forward_does_not_disturb_the_stash(dev):
 
 
 # =========================================================================== the agents
-AGENTS = {"ddpg_algo": ("pql_amd.algo.ddpg", "AgentDDPG"), "sac_algo": ("pql_amd.algo.sac", "AgentSAC")}
 SHAPE = ["task=pointmass", f"task.obs_dim={O}", f"task.act_dim={A}", "num_envs=16", f"algo.batch_size={B}", "algo.memory_size=1024"]
 
 
-def _agent(algo, *extra, seed=3):
-    """Agent and a ring filled by the warm-up rollout, all from `seed`."""
-    from pql_amd.envs.synthetic import create_task_env
-    from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer
-    from pql_amd.replay.simple_replay import ReplayBuffer
-    from pql_amd.utils.cfg import load_cfg
-    from pql_amd.utils.common import preprocess_cfg, set_random_seed
-    cfg = load_cfg([f"algo={algo}", *SHAPE, "device=cuda:0", "sim_device=cuda:0", "rl_device=cuda:0", f"seed={seed}", *extra])
-    set_random_seed(cfg.seed)
-    cfg.algo.v_learner_gpu = cfg.algo.p_learner_gpu = 0
-    preprocess_cfg(cfg)
-    env = create_task_env(cfg)
-    mod, cls = AGENTS[algo]
-    agent = getattr(importlib.import_module(mod), cls)(env=env, cfg=cfg)
-    agent.reset_agent()
-    if cfg.algo.per.enabled:
-        memory = PrioritizedReplayBuffer(1024, agent.obs_dim, agent.action_dim, device=agent.device, alpha=float(cfg.algo.per.alpha),
-                                         eps=float(cfg.algo.per.eps))
-    else:
-        memory = ReplayBuffer(1024, agent.obs_dim, agent.action_dim, device=agent.device)
-    trajectory, _ = agent.explore_env(env, cfg.algo.warm_up, random=True)
-    memory.add_to_buffer(trajectory)
-    assert memory.cur_capacity >= 256
-    return agent, memory
-
-
-def _updates(agent, memory, which):
-    """update_once with injected indices and draws: update s takes the s-th draws, whoever runs it."""
-    sac = type(agent).__name__ == "AgentSAC"
-    for s in which:
-        g = torch.Generator().manual_seed(1000 + s)
-        idx = torch.randint(256, (B,), generator=g)
-        d1, d2 = torch.randn((B, A), generator=g), torch.randn((B, A), generator=g)
-        if sac:
-            agent.update_once(memory, indices=idx, eps_next=d1, eps_cur=d2)
-        else:
-            agent.update_once(memory, indices=idx, noise=0.2 * d1)
-    torch.cuda.synchronize()
-
-
-def _state(agent):
-    torch.cuda.synchronize()
-    return {k: v.detach().cpu().clone() for k, v in agent._state_tensors().items()}
-
-
-def _same(a, b):
-    assert set(a) == set(b) and {"critic", "critic_target", "copt.m", "copt.v", "aopt.m", "closs", "aloss", "actor"} <= set(a)
-    return all(torch.equal(a[k], b[k]) for k in a)
+_agent, _updates = functools.partial(ah._agent, shape=SHAPE), functools.partial(ah._updates, B=B, A=A)
 
 
 @pytest.mark.parametrize("W", WIDTHS)

@@ -1,6 +1,5 @@
 """The residual LayerNorm critic without a GPU: the two exports and their host argument errors, `DoubleQBroNet`'s construction, keys,
 parameter count and state_dict against the torch twin, the configuration keys, every refusal, and the checkpoint structure."""
-import importlib.util
 import os
 import re
 
@@ -8,6 +7,8 @@ import pytest
 import torch
 
 import bronet_cases as bc
+from support import cfg_of as _cfg
+from task_cases import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NULL, E_SHAPE = 1, 2
@@ -129,15 +130,8 @@ def test_deepcopy_gets_its_own_empty_workspace():
 
 
 # --------------------------------------------------------------------------- configuration and refusals (env = None: nothing allocated)
-def _cfg(algo, *extra):
-    from pql_amd.utils.cfg import load_cfg
-    return load_cfg([f"algo={algo}", "task.name=Toy", "num_envs=4", *extra])
-
-
 def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-    return mod
+    return load_script(f"scripts/{name}.py", name)
 
 
 def test_config_keys_defaults_and_the_factory(monkeypatch):

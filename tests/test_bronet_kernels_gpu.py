@@ -1,5 +1,5 @@
 """pqlk_ln_res_forward / pqlk_ln_sum_backward (pql_amd/csrc/ln.hip) over the shape table of tests/layernorm_cases.py: every dispatch
-seam and grid cap, the 16-byte and the scalar path, in the guarded, poisoned buffers of tests/test_layernorm_kernels_gpu.py (pad
+seam and grid cap, the 16-byte and the scalar path, in the guarded, poisoned buffers of tests/row_harness.py (pad
 columns of the inputs hold POISON too).  Float64 at layernorm_cases' bars where the input is generic; equality wherever the law
 makes two calls the same chain of roundings (the ties to pqlk_ln_elu_backward, to the pre-added gradient, between aliased and
 separate buffers, between the frozen and the full call) and on the exact design."""
@@ -11,7 +11,9 @@ import torch
 
 import bronet_cases as bc
 import layernorm_cases as lc
-from test_layernorm_kernels_gpu import Guarded, _backward, _forward, _layout, _mat, _np, _pads_intact, _vec
+from guarded import Guarded, bits as _bits
+from row_harness import _backward, _forward, _layout, _mat, _np, _pads_intact, _vec, backward, forward
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,48 +22,16 @@ E_NULL, E_SHAPE = 1, 2
 BWD_SHAPES = [s for s in bc.SHAPES if s[1] >= 2]
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _res_forward(dev, z, gamma, beta, res, align):
-    from pql_amd import _lib as L
-    m, cols = z.shape
-    ld, off = _layout(align, cols)
-    b = dict(ld=ld, off=off, z=_mat(dev, z, ld, off), res=_mat(dev, res, ld, off), gamma=_vec(dev, gamma, off), beta=_vec(dev, beta, off),
-             y=Guarded(dev, (m, ld), POISON, off=off), mean=Guarded(dev, (m,), POISON, off=off), rstd=Guarded(dev, (m,), POISON, off=off))
-    L.check(L.lib.pqlk_ln_res_forward(b["z"].ptr, ld, m, cols, b["gamma"].ptr, b["beta"].ptr, lc.EPS, b["res"].ptr, b["y"].ptr,
-                                      b["mean"].ptr, b["rstd"].ptr, L.stream(dev)))
-    torch.cuda.synchronize()
-    return b
+    return forward(dev, "pqlk_ln_res_forward", z, gamma, beta, align, res=res)
 
 
 def _sum_backward(dev, b, dy, dy2=None, act=True, dsum=True, params=True, alias_dz=False, alias_dsum=False):
     """pqlk_ln_sum_backward on a forward's buffers (act: hand the forward's y on, i.e. an ELU stands behind the norm).
     Returns guarded (dz, dsum, dgamma, dbeta, scratch); what was not asked for is None."""
-    from pql_amd import _lib as L
     m, cols = dy.shape
-    ld, off = b["ld"], b["off"]
-    gdy = _mat(dev, dy, ld, off)
-    gdy2 = _mat(dev, dy2, ld, off) if dy2 is not None else None
-    gdz = gdy if alias_dz else Guarded(dev, (m, ld), POISON, off=off)
-    gds = None
-    if dsum:
-        gds = gdy2 if alias_dsum else Guarded(dev, (m, ld), POISON, off=off)
-    dg = db = sc = None
-    if params:
-        dg, db = Guarded(dev, (cols,), POISON, off=off), Guarded(dev, (cols,), POISON, off=off)
-        sc = Guarded(dev, (int(L.lib.pqlk_ln_scratch_floats(cols)),), POISON)
-    p = lambda g: g.ptr if g is not None else None  # noqa: E731
-    L.check(L.lib.pqlk_ln_sum_backward(gdy.ptr, p(gdy2), b["y"].ptr if act else None, b["z"].ptr, ld, m, cols, b["mean"].ptr, b["rstd"].ptr,
-                                       b["gamma"].ptr, p(gds), gdz.ptr, p(dg), p(db), p(sc), L.stream(dev)))
-    torch.cuda.synchronize()
+    gdy, gdy2, gdz, gds, dg, db, sc = backward(dev, "pqlk_ln_sum_backward", b, dy, params=params, alias=alias_dz, summed=True, dy2=dy2, act=act,
+                                               dsum=dsum, alias_dsum=alias_dsum)
     if not alias_dz:
         assert torch.equal(gdy.t[:, :cols].cpu(), lc.T(dy)) and _pads_intact(gdy, cols)           # inputs are left alone
     if gdy2 is not None and not alias_dsum:

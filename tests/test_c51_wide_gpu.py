@@ -14,6 +14,9 @@ import torch
 import c51_wide_cases as wc
 import detdata as dd
 import reduction_cases as rc
+from guarded import Guarded
+from learner_harness import _compare_nets, _sd
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,34 +25,9 @@ POISON, SLACK = rc.POISON, rc.SLACK
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def ref():
     from oracle import pql_ref_cpu
     return pql_ref_cpu
-
-
-class Guarded:
-    """A device tensor of `shape` with `fill` in SLACK elements behind it."""
-
-    def __init__(self, dev, shape, fill, init=None):
-        n = int(np.prod(shape))
-        self.full = torch.full((n + SLACK,), fill, dtype=torch.float32, device=dev)
-        self.t = self.full[:n].view(*shape)
-        self.n, self.fill = n, fill
-        if init is not None:
-            self.t.copy_(init if torch.is_tensor(init) else T(np.asarray(init)))
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.t.data_ptr())
-
-    def intact(self):
-        return bool((self.full[self.n:] == self.fill).all())
 
 
 def _g(dev, arr, fill):
@@ -270,10 +248,6 @@ def _cfg(graph=False, extra=()):
     return cfg
 
 
-def _sd(state):
-    return {k: T(v) for k, v in state.items()}
-
-
 def _learner_data():
     rows = CAP_ - 100
     data = (T(dd.uniform((rows, O_), 177, -3, 3)), T(dd.uniform((rows, A_), 178)), T(dd.uniform((rows, 1), 179, -2.0, 2.0)),
@@ -295,16 +269,6 @@ def _make_learners(dev, graph):
     critic, _, _ = v.update(p.actor, tuple(t.to(dev) for t in data), norm, 0)
     p.update(critic, data[0].to(dev), norm, 0)
     return v, p, cst, ast
-
-
-def _compare_nets(module, nets, rtol=1e-5, atol=1e-5):
-    lay = module.layout
-    for n, net in enumerate(nets):
-        for l in range(lay.n_layers):
-            np.testing.assert_allclose(lay.weight(module.arena.data, n, l).cpu().numpy(), net[2 * l].detach().numpy(),
-                                       rtol=rtol, atol=atol, err_msg=f"net {n} layer {l} weight")
-            np.testing.assert_allclose(lay.bias(module.arena.data, n, l).cpu().numpy(), net[2 * l + 1].detach().numpy(),
-                                       rtol=rtol, atol=atol, err_msg=f"net {n} layer {l} bias")
 
 
 def test_learners_at_101_atoms_vs_oracle(dev, ref):

@@ -17,8 +17,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import detdata as dd
-
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
+from support import T
 
 
 def _free_port():
@@ -51,8 +50,6 @@ def run2(fn):
 
 # --------------------------------------------------------------------------- gradient all-reduce == full batch
 def _dp_grad(rank, world):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from oracle import pql_ref_cpu as ref
     O, A, B = 8, 2, 64
     st = dd.doubleq_state(O, A, 1, 21)
@@ -91,8 +88,6 @@ def test_allreduced_shard_gradients_equal_full_batch_gradient():
 
 # --------------------------------------------------------------------------- running statistics
 def _rms(rank, world):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pql_amd.utils.torch_util import RunningMeanStd
     rms = RunningMeanStd(shape=(6,), device="cpu")
     rms.pg = dist.group.WORLD
@@ -160,8 +155,6 @@ def test_shard_sizes_strong_and_weak():
 
 
 def _groups(rank, world):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pql_amd.utils.dp import component_groups
     g = component_groups(dist.group.WORLD)
     assert len({id(x) for x in g.values()}) == 3 and all(dist.get_world_size(x) == world for x in g.values())
@@ -183,8 +176,6 @@ def test_component_groups_are_independent_communicators():
 def _strong_half_steps(rank, world):
     """Two ranks in STRONG mode: each owns half the envs' rows of a sharded ring and half the batch; the all-reduced mean
     gradient and the replicated optimiser step must reproduce the one-process step on the whole batch."""
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from oracle import pql_ref_cpu as ref
     from pql_amd.utils.dp import shard
     O, A, B, rows = 8, 2, 64, 96
@@ -270,8 +261,6 @@ def _cfg3_rank(rank, world):
     """One of the 8 ranks of configs[3] (PQL-D, 16384 ShadowHand-shape envs, replay 5 M, batch 8192, env-sharded + gradient
     all-reduce): the host-side and collective logic of the data-parallel path at the sizes the config names -- shard arithmetic,
     the rank's env shard, the merged running statistics, the global noise index, the gradient buckets of the C51 twin critic."""
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pql_amd.envs.synthetic import SyntheticVecEnv
     from pql_amd.models.mlp import ArenaLayout
     from pql_amd.utils.dp import BucketAllReduce, bucket_views, component_groups, layer_buckets, shard

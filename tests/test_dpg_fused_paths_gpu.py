@@ -16,21 +16,16 @@ import torch
 import backward_cases as bc
 import dpg_fused_cases as fc
 from backward_job import Guarded, _returned, _sync_or_stop
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
-POISON, IN_ONE = bc.POISON, bc.IN_ONE
+POISON, SLACK, IN_ONE = bc.POISON, bc.SLACK, bc.IN_ONE
 NAN = float("nan")
 PART_ROOM = 2048          # floats of room in sumsq_part (include/pqlk.h)
 STEP0 = 5
 LD_DZ = 32
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 def _same(a, b):
@@ -47,15 +42,15 @@ class FusedJob:
         c, B = p.c, p.c.B
         self.A = A = c.adims[-1]
         self.cdesc, self.adesc = L.mlp_desc(c.cdims, 2), L.mlp_desc(c.adims, 1)
-        self.c_arena = Guarded(dev, (bc.net_stride(c.cdims) * 2,), IN_ONE, fc.arena_of(c.cdims, p.Wc), front=True)
-        self.a_arena = Guarded(dev, (bc.net_stride(c.adims),), IN_ONE, fc.arena_of(c.adims, [p.Wa]), front=True)
-        self.c_acts = c_acts if c_acts is not None else Guarded(dev, (bc.acts_floats(c.cdims, 2, B),), IN_ONE, fc.stash_of(c.cdims, p.Hc, B), front=True)
-        self.a_acts = Guarded(dev, (bc.acts_floats(c.adims, 1, B),), IN_ONE, fc.stash_of(c.adims, [p.Ha], B), front=True)
-        self.x_obs = Guarded(dev, (B, 64), IN_ONE, fc.tiled(p.xa, B), front=True)
+        self.c_arena = Guarded(dev, (bc.net_stride(c.cdims) * 2,), IN_ONE, fc.arena_of(c.cdims, p.Wc), off=SLACK)
+        self.a_arena = Guarded(dev, (bc.net_stride(c.adims),), IN_ONE, fc.arena_of(c.adims, [p.Wa]), off=SLACK)
+        self.c_acts = c_acts if c_acts is not None else Guarded(dev, (bc.acts_floats(c.cdims, 2, B),), IN_ONE, fc.stash_of(c.cdims, p.Hc, B), off=SLACK)
+        self.a_acts = Guarded(dev, (bc.acts_floats(c.adims, 1, B),), IN_ONE, fc.stash_of(c.adims, [p.Ha], B), off=SLACK)
+        self.x_obs = Guarded(dev, (B, 64), IN_ONE, fc.tiled(p.xa, B), off=SLACK)
         self.ld_tanh = fc.ld_tanh(c)
-        self.a_out = Guarded(dev, (B, self.ld_tanh), IN_ONE, front=True)
+        self.a_out = Guarded(dev, (B, self.ld_tanh), IN_ONE, off=SLACK)
         self.a_out.t[:, :A] = bc.rc.T(fc.tiled(p.tanh, B)).to(dev)
-        self.qc = qc if qc is not None else Guarded(dev, (2, B), IN_ONE, p.q, front=True)
+        self.qc = qc if qc is not None else Guarded(dev, (2, B), IN_ONE, p.q, off=SLACK)
         self.inputs = [self.c_arena, self.a_arena, self.c_acts, self.a_acts, self.x_obs, self.a_out, self.qc]
         self.before = [g.full.clone() for g in self.inputs]
         self.ws = fc.compact_ws(bc.max_hidden_ld(c.cdims), B)
@@ -239,10 +234,10 @@ class QcJob:
         self.dev, self.B = dev, B
         self.case, self.W, self.bias, self.x, self.H, self.q = fc.qc_problem(B, twin)
         self.desc = L.mlp_desc(self.case.dims, 2)
-        self.arena = Guarded(dev, (bc.net_stride(self.case.dims) * 2,), IN_ONE, fc.qc_arena(self.case, self.W, self.bias), front=True)
+        self.arena = Guarded(dev, (bc.net_stride(self.case.dims) * 2,), IN_ONE, fc.qc_arena(self.case, self.W, self.bias), off=SLACK)
         n = int(L.lib.pqlk_mlp_packed_floats(C.byref(self.desc)))
         assert n > 0
-        self.packed = Guarded(dev, (n,), IN_ONE, body=NAN, front=True)
+        self.packed = Guarded(dev, (n,), IN_ONE, body=NAN, off=SLACK)
         assert _returned(L.lib.pqlk_mlp_pack(C.byref(self.desc), L.ptr(self.arena.t), L.ptr(self.packed.t), L.stream(dev)), "pqlk_mlp_pack") == 0
         _sync_or_stop("pqlk_mlp_pack")
         assert self.packed.intact() and not bool(torch.isnan(self.packed.t).any())
@@ -251,13 +246,13 @@ class QcJob:
         """(x, ldx, x2, ldx2, x2_col0) of one input form; the columns of x past x2_col0 and of x2 past its share hold NaN."""
         O, K = fc.QC_O, self.case.dims[0]
         if form == "cat":
-            return Guarded(self.dev, (self.B, 32), IN_ONE, self.x, front=True), 32, None, 0, 0
+            return Guarded(self.dev, (self.B, 32), IN_ONE, self.x, off=SLACK), 32, None, 0, 0
         col0, ldx = {"split4": (4, 32), "splitO": (O, 32), "split64": (O, 64)}[form]
         x = np.full((self.B, ldx), np.nan, dtype=F32)
         x[:, :col0] = self.x[:, :col0]
         x2 = np.full((self.B, 32), np.nan, dtype=F32)
         x2[:, : K - col0] = self.x[:, col0: K]
-        return Guarded(self.dev, x.shape, IN_ONE, x, front=True), ldx, Guarded(self.dev, x2.shape, IN_ONE, x2, front=True), 32, col0
+        return Guarded(self.dev, x.shape, IN_ONE, x, off=SLACK), ldx, Guarded(self.dev, x2.shape, IN_ONE, x2, off=SLACK), 32, col0
 
     def forward(self, form):
         from pql_amd import _lib as L

@@ -10,6 +10,7 @@ import torch
 
 import draw_cases as dc
 from guarded import Guarded
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +24,6 @@ pytestmark = pytest.mark.gpu
 # constant to raise.
 TORCH_DISTANCE = 2.643e-06
 NORMAL_BAR = 2 * TORCH_DISTANCE          # 5.286e-06
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

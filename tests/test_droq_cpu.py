@@ -1,7 +1,6 @@
 """The DroQ critic without a GPU: the numpy model of the mask law (tests/droq_cases.py) against Philox known answers, the law's
 constants, what the references of tests/test_droq_kernels_gpu.py guarantee, `DoubleQDropoutLayerNorm` on the CPU (construction,
 state_dict, deepcopy), the configuration and every refusal."""
-import importlib.util
 import math
 import os
 import re
@@ -13,6 +12,8 @@ import torch
 
 import droq_cases as dc
 import layernorm_cases as lc
+from support import cfg_of as _cfg
+from task_cases import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NULL, E_SHAPE = 1, 2
@@ -200,15 +201,8 @@ def test_deepcopy_bumps_the_stream_and_the_tag_layout():
 
 
 # --------------------------------------------------------------------------- configuration and refusals (env = None: nothing allocated)
-def _cfg(algo, *extra):
-    from pql_amd.utils.cfg import load_cfg
-    return load_cfg([f"algo={algo}", "task.name=Toy", "num_envs=4", *extra])
-
-
 def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-    return mod
+    return load_script(f"scripts/{name}.py", name)
 
 
 def test_droq_algo_composes_to_sac_on_the_dropout_critic():

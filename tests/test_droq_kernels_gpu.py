@@ -1,15 +1,15 @@
 """pqlk_drop_mask / pqlk_drop_ln_elu_forward / pqlk_drop_ln_elu_backward (pql_amd/csrc/ln.hip) over the shape table of
 tests/droq_cases.py: the mask against the numpy model of the law bit for bit, the p = 0 tie to pqlk_ln_elu_* bit for bit, p > 0 against
-float64 on u at the bars of tests/layernorm_cases.py, in the guarded, poisoned buffers of tests/test_layernorm_kernels_gpu.py."""
-import ctypes as C
-
+float64 on u at the bars of tests/layernorm_cases.py, in the guarded, poisoned buffers of tests/row_harness.py."""
 import numpy as np
 import pytest
 import torch
 
 import droq_cases as dc
 import layernorm_cases as lc
-from test_layernorm_kernels_gpu import Guarded, _backward, _forward, _layout, _mat, _np, _pads_intact, _vec
+from guarded import Guarded, bits as _bits
+from row_harness import _backward, _forward, _np, _pads_intact, backward, forward
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -18,44 +18,14 @@ E_NULL, E_SHAPE = 1, 2
 TAG = dc.TAGS[1]          # the tag of droq_cases.drop_case's references
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
-
-
 def _drop_forward(dev, z, gamma, beta, align, p, tag=TAG, seed=dc.SEED):
-    from pql_amd import _lib as L
-    m, cols = z.shape
-    ld, off = _layout(align, cols)
-    b = dict(ld=ld, off=off, p=p, tag=tag, seed=seed, z=_mat(dev, z, ld, off), gamma=_vec(dev, gamma, off), beta=_vec(dev, beta, off),
-             y=Guarded(dev, (m, ld), POISON, off=off), mean=Guarded(dev, (m,), POISON, off=off), rstd=Guarded(dev, (m,), POISON, off=off))
-    L.check(L.lib.pqlk_drop_ln_elu_forward(b["z"].ptr, ld, m, cols, b["gamma"].ptr, b["beta"].ptr, lc.EPS, p, seed, tag, b["y"].ptr,
-                                           b["mean"].ptr, b["rstd"].ptr, L.stream(dev)))
-    torch.cuda.synchronize()
-    return b
+    return forward(dev, "pqlk_drop_ln_elu_forward", z, gamma, beta, align, extras=(p, seed, tag), p=p, tag=tag, seed=seed)
 
 
 def _drop_backward(dev, b, dy, params=True, alias=False):
-    """As test_layernorm_kernels_gpu._backward, through the dropout entry with the forward's (p, seed, tag)."""
-    from pql_amd import _lib as L
-    m, cols = dy.shape
-    ld, off = b["ld"], b["off"]
-    gdy = _mat(dev, dy, ld, off)
-    gdz = gdy if alias else Guarded(dev, (m, ld), POISON, off=off)
-    dg = db = sc = None
-    if params:
-        dg, db = Guarded(dev, (cols,), POISON, off=off), Guarded(dev, (cols,), POISON, off=off)
-        sc = Guarded(dev, (int(L.lib.pqlk_ln_scratch_floats(cols)),), POISON)
-    L.check(L.lib.pqlk_drop_ln_elu_backward(gdy.ptr, b["y"].ptr, b["z"].ptr, ld, m, cols, b["mean"].ptr, b["rstd"].ptr, b["gamma"].ptr,
-                                            b["p"], b["seed"], b["tag"], gdz.ptr, dg.ptr if params else None, db.ptr if params else None,
-                                            sc.ptr if params else None, L.stream(dev)))
-    torch.cuda.synchronize()
+    """As row_harness._backward, through the dropout entry with the forward's (p, seed, tag)."""
+    _, _, gdz, _, dg, db, sc = backward(dev, "pqlk_drop_ln_elu_backward", b, dy, extras=(b["p"], b["seed"], b["tag"]), params=params, alias=alias)
     return gdz, dg, db, sc
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # =========================================================================== the mask

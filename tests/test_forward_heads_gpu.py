@@ -14,32 +14,13 @@ import torch
 
 import forward_head_cases as fc
 import reduction_cases as rc
+from guarded import Guarded
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 T = rc.T
 POISON, SLACK = fc.POISON, fc.SLACK
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
-
-
-class Guarded:
-    """A device tensor of `shape` with `fill` in SLACK elements behind it."""
-
-    def __init__(self, dev, shape, fill, init=None):
-        n = int(np.prod(shape))
-        self.full = torch.full((n + SLACK,), fill, dtype=torch.float32, device=dev)
-        self.t = self.full[:n].view(*shape)
-        self.n, self.fill = n, fill
-        if init is not None:
-            self.t.copy_(init if torch.is_tensor(init) else T(np.asarray(init)))
-
-    def intact(self):
-        return bool((self.full[self.n:] == self.fill).all())
 
 
 class _Net:

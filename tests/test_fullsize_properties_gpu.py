@@ -8,13 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from support import dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _rows(idx, width, salt):

@@ -20,17 +20,12 @@ import torch
 import gather_cases as gc
 from guarded import Guarded
 from reduction_cases import IN_BIG, SLACK, T
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 POISON = float(gc.POISON)
 CAP, START = gc.CAP, gc.START
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 def _launched(rcode, what):

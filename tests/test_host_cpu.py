@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import detdata as dd
+from task_cases import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -521,9 +522,7 @@ def test_bench_refuses_more_gpus_than_visible():
 def test_no_kernel_of_the_library_goes_through_scratch():
     """Every kernel's own metadata (tools/kernel_resources.py): no spilled VGPR, no private segment.  A spilling kernel stays
     correct and green everywhere else; round 3's k_mlp_fwd_fused<1,4> (hidden widths > 512) carried 59 spilled registers."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    kr = load_script("tools/kernel_resources.py", "kernel_resources")
     if not os.path.exists(f"{kr.LLVM}/llvm-readelf"):
         pytest.skip("no llvm-readelf")
     res = kr.resources()
@@ -541,9 +540,7 @@ def test_c51_kernels_with_one_atom_per_lane_hold_no_lds_image():
     """The C51 kernels are one template over NJ = atoms per lane.  NJ = 1 (K <= 64) projects with cross-lane shuffles and must not
     allocate the LDS image of the NJ > 1 instances, which would cost the shipped 51-atom path its occupancy: static LDS is
     block_sum_256's four floats, or nothing.  NJ > 1: sizeof(C51Image) * 4 waves (+ those four floats)."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    kr = load_script("tools/kernel_resources.py", "kernel_resources")
     if not os.path.exists(f"{kr.LLVM}/llvm-readelf"):
         pytest.skip("no llvm-readelf")
     res = kr.resources()
@@ -561,9 +558,7 @@ def test_gather_kernels_keep_their_counted_waits():
     compiler waiting with COUNTED `s_waitcnt vmcnt(n)`.  Round 4 twice produced a kernel with the same bits and 14 full drains
     (`vmcnt(0)`) instead of 2 -- 23 -> 28-30 us -- by adding a wave-uniform branch, then a template flag and selects, to the
     per-record loop; no parity test can see that.  This counts the drains in the built library (tools/kernel_resources.py)."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    kr = load_script("tools/kernel_resources.py", "kernel_resources")
     if not os.path.exists(f"{kr.LLVM}/llvm-objdump"):
         pytest.skip("no llvm-objdump")
     drains = kr.full_drains(want=("k_replay_gather_fast<true", "k_replay_gather_obs<true"))

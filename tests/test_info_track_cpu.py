@@ -1,93 +1,18 @@
 """info_track_keys without a GPU: the tasks' info channels as `_step_torch` defines them, `InfoTrackers`' torch form against a deque
 model of the reference's `Tracker` written here, the config errors, the C ABI of the new exports and the training state.
 
-`TrackerModel`, `ModelTrackers` and `scripted_steps` are shared with tests/test_info_track_gpu.py."""
+`TrackerModel`, `ModelTrackers` and `scripted_steps`, shared with tests/test_info_track_gpu.py, are in tests/task_cases.py."""
 import ctypes as C
 import os
 import re
-from collections import deque
 
 import numpy as np
 import pytest
 import torch
 
+from task_cases import ModelTrackers, assert_trackers_equal, pointmass_infos_from_log, scripted_steps
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-# --------------------------------------------------------------------------- the model: the reference's Tracker and its callers
-class TrackerModel:
-    """A deque of `max_len` zeros, `extend`, mean over all slots (what pql/utils/common.py's Tracker is), plus how many values it
-    has been given, so that its content can be laid out like the device ring: value i of the deque sits in slot (count + i) % max_len."""
-
-    def __init__(self, max_len):
-        self.max_len, self.window, self.count = max_len, deque([0.0] * max_len, maxlen=max_len), 0
-
-    def update(self, values):
-        self.window.extend(values)
-        self.count += len(values)
-
-    def ring(self):
-        return torch.from_numpy(np.roll(np.asarray(self.window, dtype=np.float32), self.count % self.max_len))
-
-    def ptr(self):
-        return self.count % self.max_len
-
-    def mean(self):
-        return float(self.ring().mean())   # fp32, summed in the ring's slot order like DeviceTracker.mean
-
-
-class ModelTrackers:
-    """update_tracker's info part (pql_actor.py:138-146, ac_base.py:88-101, evaluator.py:89-102) on the host, index lists and all."""
-
-    def __init__(self, keys, steps, num_envs, window_len):
-        self.keys, self.steps = list(keys), list(steps)
-        self.trackers = [TrackerModel(window_len) for _ in keys]
-        self.accs = [torch.zeros(num_envs, dtype=torch.float32) for _ in keys]
-
-    def update(self, done, info):
-        idx = torch.where(done.cpu())[0]
-        for key, step, tr, acc in zip(self.keys, self.steps, self.trackers, self.accs):
-            if key not in info:
-                continue
-            v = info[key].cpu().to(torch.float32)
-            if step == "last":
-                tr.update(v[idx].tolist())
-            elif step in ("all-episode", "all"):
-                acc += v
-                tr.update(acc[idx].tolist())
-                acc[idx] = 0
-            elif step == "all-step":
-                tr.update(v.tolist())
-            else:
-                raise AssertionError(step)
-
-
-def assert_trackers_equal(got, want, where=""):
-    """Windows (the discard slot left out), pointers, accumulators and means of an `InfoTrackers` against a `ModelTrackers`."""
-    for i, key in enumerate(want.keys):
-        t, m = got.trackers[i], want.trackers[i]
-        assert torch.equal(t.ring[: t.max_len].cpu(), m.ring()), (where, key, "ring")
-        assert int(t.ptr.item()) == m.ptr(), (where, key, "ptr")
-        if got.accs[i] is not None:
-            assert torch.equal(got.accs[i].cpu(), want.accs[i]), (where, key, "acc")
-        assert float(t.ring[: t.max_len].cpu().mean()) == m.mean(), (where, key, "mean")
-
-
-def scripted_steps(n, n_float, n_bool, seed=0, missing=()):
-    """Six (done, info) steps: nobody finishes, everybody, then about 30 % scattered four times.  info holds float keys f0.., bool
-    keys b0.. and one uint8 key u0; the keys in `missing` are absent on steps 1 and 3."""
-    g = torch.Generator().manual_seed(seed)
-    out = []
-    for t in range(6):
-        done = torch.zeros(n, dtype=torch.bool) if t == 0 else torch.ones(n, dtype=torch.bool) if t == 1 else torch.rand(n, generator=g) < 0.3
-        info = {f"f{i}": 4.0 * torch.rand(n, generator=g) - 1.0 for i in range(n_float)}
-        info.update({f"b{i}": torch.rand(n, generator=g) < 0.4 for i in range(n_bool)})
-        info["u0"] = (torch.rand(n, generator=g) < 0.5).to(torch.uint8)
-        if t in (1, 3):
-            for key in missing:
-                del info[key]
-        out.append((done, info))
-    return out
 
 
 # --------------------------------------------------------------------------- channel definitions
@@ -240,35 +165,6 @@ def test_entry_points_take_the_keys_instead_of_refusing(tmp_path):
         RolloutEngine(cfg, run)
     for path in ("pql_amd/algo/pql_actor.py", "pql_amd/algo/ppo.py", "pql_amd/utils/evaluator.py"):
         assert "NotImplementedError(\"info_track_keys" not in open(os.path.join(ROOT, path)).read(), path
-
-
-def pointmass_channels_np(obs, act, A):
-    """(dist2, oob) of the step that `act` (N, A) takes from the state in the observation rows `obs` = [x | v | g | 0 ...]: the
-    formulas of pql_amd/envs/pointmass.py's docstring in numpy float32, one rounding per operation, sums in index order."""
-    F = np.float32
-    o = obs.cpu().numpy().astype(F)
-    x, v, g = o[:, :A], o[:, A:2 * A], o[:, 2 * A:3 * A]
-    a = np.clip(act.cpu().numpy().astype(F), F(-1), F(1))
-    vn = F(0.8) * v + F(0.2) * a
-    xn = x + F(0.25) * vn
-    df = xn - g
-    sq = df * df
-    d2 = sq[:, 0]
-    for j in range(1, A):
-        d2 = d2 + sq[:, j]
-    d2 = d2 * (F(1.0) / F(A))
-    return torch.from_numpy(d2.astype(F)), torch.from_numpy((np.abs(xn) > F(1.5)).any(1))
-
-
-def pointmass_infos_from_log(first_obs, log, A):
-    """[(done, info)] of the transitions `task_cases.RecordingEnv` kept, the channels recomputed on the host."""
-    out, obs = [], first_obs.cpu()
-    for act, nobs, _rew, done, trunc in log:
-        d2, oob = pointmass_channels_np(obs, act, A)
-        assert torch.equal(oob, done & ~trunc)   # leaving the box is PointMass's only terminal
-        out.append((done, {"dist2": d2, "oob": oob.to(torch.float32), "TimeLimit.truncated": trunc}))
-        obs = nobs
-    return out
 
 
 def test_evaluation_on_cpu_reports_eval_keys_from_zero(tmp_path):

@@ -3,7 +3,6 @@
 produced by the same operations in the same order, so it is exact.  Run with `pytest -m gpu`."""
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -11,19 +10,12 @@ import torch
 
 import detdata as dd
 import task_cases as tc
-from test_info_track_cpu import ModelTrackers, assert_trackers_equal, pointmass_infos_from_log, scripted_steps
+from support import dev  # noqa: F401
+from task_cases import ModelTrackers, assert_trackers_equal, pointmass_infos_from_log, scripted_steps
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(autouse=True)

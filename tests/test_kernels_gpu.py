@@ -10,16 +10,10 @@ import pytest
 import torch
 
 import detdata as dd
+from learner_harness import _sd
+from support import T, child_env, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -343,10 +337,6 @@ def test_nstep_random_call_sequences_vs_oracle(dev, ref, seed):
 
 # --------------------------------------------------------------------------- MLP family vs golden
 SHAPES = [(8, 2), (88, 16), (211, 20), (108, 21)]
-
-
-def _sd(state):
-    return {k: T(v) for k, v in state.items()}
 
 
 def _check_grads(module, garena, g, prefix, rtol=2e-4, atol=2e-6):
@@ -1167,8 +1157,7 @@ def test_output_only_forward_over_k_batches_equals_the_per_batch_forwards(dev):
 
 
 _GEMM_LOOP_SCRIPT = r"""
-import ctypes as C, hashlib, sys
-sys.path.insert(0, {tests!r}); sys.path.insert(0, {root!r})
+import ctypes as C, hashlib
 import numpy as np, torch
 import detdata as dd
 from pql_amd import _lib as L
@@ -1204,15 +1193,11 @@ def test_gemm_lds_dma_loop_is_bitwise_the_register_staged_loop(dev):
     otherwise (gemm.hip, launch_gemm).  Same reduction order by construction; here: the gradients and the input gradient of
     three BASELINE-shaped MLPs hash identically with the DMA loop on and with PQLK_GEMM_DMA=0 / PQLK_GEMM_XCD=0 (the
     switches are read once per process, hence the subprocesses)."""
-    import os
     import subprocess
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = _GEMM_LOOP_SCRIPT.format(tests=os.path.join(root, "tests"), root=root)
     hashes = {}
     for name, extra in (("dma+xcd", {}), ("staged", {"PQLK_GEMM_DMA": "0"}), ("dma, dispatch order", {"PQLK_GEMM_XCD": "0"})):
-        env = dict(os.environ, **extra)
-        r = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, "-c", _GEMM_LOOP_SCRIPT], env=child_env(**extra), capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         hashes[name] = r.stdout.strip().split()
     assert len(hashes["dma+xcd"]) == 3
@@ -1294,13 +1279,10 @@ def test_first_calls_from_two_threads_at_once(dev):
     instant.  The per-device once-flag must not let the second caller launch (with > 64 KB of dynamic LDS) before the first has
     raised the kernel's limit -- round 3 marked the device done before calling hipFuncSetAttribute.  Run in a fresh process so
     that the calls really are the first ones."""
-    import os
     import subprocess
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = r'''
-import ctypes as C, threading, sys, torch
-sys.path.insert(0, %r)
+import ctypes as C, threading, torch
 from pql_amd import _lib as L
 from pql_amd.models.mlp import DoubleQ, PackedWeights, mlp_forward_raw, output_view
 dev = torch.device("cuda:0")
@@ -1343,6 +1325,6 @@ assert torch.equal(outs[0], outs[1])
 ref = mlp_forward_raw(lay, q.arena.data, x, packed=pk); torch.cuda.synchronize()
 assert torch.equal(output_view(lay, ref, B), output_view(lay, outs[0], B))
 print("ok")
-''' % root
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+'''
+    r = subprocess.run([sys.executable, "-c", code], env=child_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

@@ -1,32 +1,22 @@
 """`DoubleQLayerNorm` (pql_amd/models/layernorm.py) and AgentDDPG / AgentSAC running with it, against tests/golden/layernorm.npz: the
 torch twin (`nn.Sequential` with `nn.LayerNorm`) plugged into the reference's own AgentDDPG / AgentSAC by tools/gen_golden.py."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import detdata as dd
+import learner_harness as lh
 import task_cases as tc
+from learner_harness import _sd
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
 O, A, B = 8, 2, 64
 LN = "algo.cri_class=DoubleQLayerNorm"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _sd(state):
-    return {k: T(v) for k, v in state.items()}
-
-
-def _fill(rows, seed):
-    return (T(dd.uniform((rows, O), seed, -3, 3)), T(dd.uniform((rows, A), seed + 1)), T(dd.uniform((rows, 1), seed + 2, -0.05, 0.05)),
-            T(dd.uniform((rows, O), seed + 3, -3, 3)), T(dd.bernoulli((rows, 1), seed + 4, 0.1)))
+_fill = functools.partial(lh._fill, O, A)
 
 
 def _check_views(views, g, prefix, rtol=5e-5, atol=5e-7):

@@ -1,6 +1,5 @@
 """The LayerNorm twin critic without a GPU: host argument errors of the three entries, their prototypes, the module's state_dict
 against the torch twin, the refusals, and DoubleQBatchNorm's keys and arena size after the move to the shared base."""
-import importlib.util
 import os
 import re
 
@@ -8,6 +7,9 @@ import numpy as np
 import pytest
 import torch
 from torch import nn
+
+from support import cfg_of as _cfg
+from task_cases import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NULL, E_SHAPE = 1, 2
@@ -117,15 +119,8 @@ def test_batchnorm_critic_keys_and_arena_unchanged():
 
 
 # --------------------------------------------------------------------------- refusals: before anything is allocated (env = None)
-def _cfg(algo, *extra):
-    from pql_amd.utils.cfg import load_cfg
-    return load_cfg([f"algo={algo}", "task.name=Toy", "num_envs=4", *extra])
-
-
 def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-    return mod
+    return load_script(f"scripts/{name}.py", name)
 
 
 def test_pql_learners_refuse_the_layernorm_critic():

@@ -1,102 +1,19 @@
 """pqlk_ln_elu_forward / pqlk_ln_elu_backward (pql_amd/csrc/ln.hip) over the shape table of tests/layernorm_cases.py: every dispatch
-seam and grid cap, the 16-byte and the scalar path, in guarded, poisoned buffers (pad columns of the inputs hold POISON too: an
-over-read moves a row sum by whole units, an over-write is seen).  Bars: those of the BatchNorm pair's tests, named in
-layernorm_cases; equality where the design makes the result exact."""
-import ctypes as C
-
+seam and grid cap, the 16-byte and the scalar path, in the guarded, poisoned buffers of tests/row_harness.py (pad columns of the
+inputs hold POISON too: an over-read moves a row sum by whole units, an over-write is seen).  Bars: those of the BatchNorm pair's
+tests, named in layernorm_cases; equality where the design makes the result exact."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import layernorm_cases as lc
+from row_harness import _backward, _forward, _np, _pads_intact
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 T, F32 = lc.T, np.float32
-POISON, SLACK = lc.POISON, lc.SLACK
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
-
-
-class Guarded:
-    """A device tensor of `shape` with `fill` in SLACK elements behind it and in `off` elements in front (off = 1 also puts the
-    tensor one float past a 16-byte boundary).  (As in tests/test_reductions_gpu.py.)"""
-
-    def __init__(self, dev, shape, fill, init=None, off=0, dtype=torch.float32):
-        n = int(np.prod(shape))
-        self.full = torch.full((off + n + SLACK,), fill, dtype=dtype, device=dev)
-        self.t = self.full[off: off + n].view(*shape)
-        self.n, self.off, self.fill = n, off, fill
-        if init is not None:
-            self.t.copy_(init if torch.is_tensor(init) else T(np.asarray(init)))
-        assert self.t.data_ptr() % 16 == (4 * off) % 16
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.t.data_ptr())
-
-    def intact(self):
-        return bool((self.full[: self.off] == self.fill).all()) and bool((self.full[self.off + self.n:] == self.fill).all())
-
-
-def _layout(align, cols):
-    from pql_amd import _lib as L
-    return (cols + 3, 1) if align == "scalar" else (L.ld(cols), 0)
-
-
-def _mat(dev, a, ld, off):
-    """(m, cols) values in a guarded (m, ld) buffer whose pad columns hold POISON."""
-    m, cols = a.shape
-    g = Guarded(dev, (m, ld), POISON, off=off)
-    g.t[:, :cols] = T(a).to(dev)
-    return g
-
-
-def _vec(dev, a, off):
-    return Guarded(dev, a.shape, POISON, a, off)
-
-
-def _pads_intact(g, cols):
-    return g.intact() and bool((g.t[:, cols:] == POISON).all())
-
-
-def _forward(dev, z, gamma, beta, align, eps=lc.EPS):
-    from pql_amd import _lib as L
-    m, cols = z.shape
-    ld, off = _layout(align, cols)
-    b = dict(ld=ld, off=off, z=_mat(dev, z, ld, off), gamma=_vec(dev, gamma, off), beta=_vec(dev, beta, off),
-             y=Guarded(dev, (m, ld), POISON, off=off), mean=Guarded(dev, (m,), POISON, off=off), rstd=Guarded(dev, (m,), POISON, off=off))
-    L.check(L.lib.pqlk_ln_elu_forward(b["z"].ptr, ld, m, cols, b["gamma"].ptr, b["beta"].ptr, eps, b["y"].ptr, b["mean"].ptr,
-                                      b["rstd"].ptr, L.stream(dev)))
-    torch.cuda.synchronize()
-    return b
-
-
-def _backward(dev, b, dy, params=True, alias=False):
-    """Backward of `_forward`'s buffers.  Returns (dz buffer, dgamma, dbeta, scratch) -- guarded, the last three None without params."""
-    from pql_amd import _lib as L
-    m, cols = dy.shape
-    ld, off = b["ld"], b["off"]
-    gdy = _mat(dev, dy, ld, off)
-    gdz = gdy if alias else Guarded(dev, (m, ld), POISON, off=off)
-    dg = db = sc = None
-    if params:
-        dg, db = Guarded(dev, (cols,), POISON, off=off), Guarded(dev, (cols,), POISON, off=off)
-        sc = Guarded(dev, (int(L.lib.pqlk_ln_scratch_floats(cols)),), POISON)
-    L.check(L.lib.pqlk_ln_elu_backward(gdy.ptr, b["y"].ptr, b["z"].ptr, ld, m, cols, b["mean"].ptr, b["rstd"].ptr, b["gamma"].ptr, gdz.ptr,
-                                       dg.ptr if params else None, db.ptr if params else None, sc.ptr if params else None, L.stream(dev)))
-    torch.cuda.synchronize()
-    return gdz, dg, db, sc
-
-
-def _np(g, cols=None):
-    a = g.t.cpu().numpy()
-    return a if cols is None else a[:, :cols]
 
 
 # =========================================================================== forward

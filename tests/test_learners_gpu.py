@@ -6,38 +6,10 @@ import pytest
 import torch
 
 import detdata as dd
+from learner_harness import _compare_nets, _fill, _sd, make_cfg
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def make_cfg(distl=False, B=64, memory=400, hidden=None, graph=False, nstep=3, streams=False, task=None):
-    """streams=False: learner work on the caller's stream (results readable right after the call); streams=True: the
-    learners' own HIP streams with event-fenced hand-offs -- read results after `learner.synchronize()`."""
-    from pql_amd.utils.cfg import load_cfg
-    ov = [f"algo.batch_size={B}", f"algo.memory_size={memory}", f"algo.distl={distl}", "algo.v_learner_gpu=0",
-          "algo.p_learner_gpu=0", "algo.num_gpus=1", f"algo.graph={graph}", f"algo.nstep={nstep}", f"algo.streams={streams}"]
-    if task:
-        ov.append(f"task={task}")
-    cfg = load_cfg(ov)
-    cfg.algo.hidden_layers = hidden
-    return cfg
-
-
-def _sd(state):
-    return {k: T(v) for k, v in state.items()}
-
-
-def _fill(O, A, rows, seed):
-    return (T(dd.uniform((rows, O), seed, -3, 3)), T(dd.uniform((rows, A), seed + 1)), T(dd.uniform((rows, 1), seed + 2, -0.05, 0.05)),
-            T(dd.uniform((rows, O), seed + 3, -3, 3)), T(dd.bernoulli((rows, 1), seed + 4, 0.1)))
 
 
 def _check_module(module, g, prefix, rtol=5e-5, atol=5e-7):
@@ -168,16 +140,6 @@ def test_full_size_step_vs_oracle(dev, hidden, streams):
         np.testing.assert_allclose(al.weight(p.actor.arena.data, 0, l).cpu().numpy(), pr.actor[2 * l].detach().numpy(),
                                    rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(lay.weight(v.critic_target.arena.data, 0, 0).cpu().numpy(), vr.t1[0].numpy(), rtol=1e-5, atol=1e-5)
-
-
-def _compare_nets(module, nets, rtol=1e-5, atol=1e-5):
-    lay = module.layout
-    for n, net in enumerate(nets):
-        for l in range(lay.n_layers):
-            np.testing.assert_allclose(lay.weight(module.arena.data, n, l).cpu().numpy(), net[2 * l].detach().numpy(),
-                                       rtol=rtol, atol=atol, err_msg=f"net {n} layer {l} weight")
-            np.testing.assert_allclose(lay.bias(module.arena.data, n, l).cpu().numpy(), net[2 * l + 1].detach().numpy(),
-                                       rtol=rtol, atol=atol, err_msg=f"net {n} layer {l} bias")
 
 
 def test_cfg4_pqld_shadowhand_shape_learner_steps_vs_oracle(dev):

@@ -6,9 +6,9 @@ import pytest
 import torch
 
 import detdata as dd
+from learner_harness import _fill
 from oracle import pql_ref_cpu as ref
-
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
+from support import T
 
 
 # --------------------------------------------------------------------------- ring
@@ -223,11 +223,6 @@ def test_rng_draw_equivalence(golden):
 
 
 # --------------------------------------------------------------------------- learners
-def _fill(O, A, rows, seed):
-    return (T(dd.uniform((rows, O), seed, -3, 3)), T(dd.uniform((rows, A), seed + 1)), T(dd.uniform((rows, 1), seed + 2, -0.05, 0.05)),
-            T(dd.uniform((rows, O), seed + 3, -3, 3)), T(dd.bernoulli((rows, 1), seed + 4, 0.1)))
-
-
 def _check_params(named, g, prefix, rtol=5e-5, atol=5e-7):
     for k, p in named:
         np.testing.assert_allclose(dd.summarize(p.detach().numpy()), g[f"{prefix}{k}"], rtol=rtol, atol=atol, err_msg=prefix + k)

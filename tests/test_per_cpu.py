@@ -1,21 +1,18 @@
 """Prioritized replay without a GPU: the entry points' declarations and sizing helpers, their argument errors, the config block, the
 refusals of the PQL learners, the checkpoint structure and the beta schedule."""
 import ctypes as C
-import importlib.util
 import os
 import re
 
 import pytest
 
+from support import cfg_of as _cfg
+from task_cases import load_script
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("pqlk_per_insert", "pqlk_per_rebuild", "pqlk_per_sample", "pqlk_per_weights", "pqlk_per_update", "pqlk_td_mse_loss_per")
 SIZING = ("pqlk_per_levels", "pqlk_per_tree_floats")
 E_NULL, E_SHAPE, E_RANGE, E_ALIGN = 1, 2, 3, 4
-
-
-def _cfg(algo, *extra):
-    from pql_amd.utils.cfg import load_cfg
-    return load_cfg([f"algo={algo}", "task.name=Toy", "num_envs=4", *extra])
 
 
 def test_entries_are_declared_exported_and_bound():
@@ -105,9 +102,7 @@ def test_ppo_ignores_the_key():
 
 
 def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-    return mod
+    return load_script(f"scripts/{name}.py", name)
 
 
 def test_pql_learners_refuse_prioritized_replay():

@@ -1,11 +1,13 @@
 """Prioritized replay in the PQL V-learner (`algo.per.refresh=run`) without a GPU: the config key, who refuses what, the
 checkpoint structure, and the declaration and argument errors of `pqlk_per_sample_steps`."""
 import ctypes as C
-import importlib.util
 import os
 import re
 
 import pytest
+
+from support import cfg_of as _cfg
+from task_cases import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NULL, E_SHAPE, E_RANGE = 1, 2, 3
@@ -13,15 +15,8 @@ ON = ("algo.per.enabled=True",)
 RUN = ON + ("algo.per.refresh=run",)
 
 
-def _cfg(algo, *extra):
-    from pql_amd.utils.cfg import load_cfg
-    return load_cfg([f"algo={algo}", "task.name=Toy", "num_envs=4", *extra])
-
-
 def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-    return mod
+    return load_script(f"scripts/{name}.py", name)
 
 
 @pytest.mark.parametrize("algo", ["ddpg_algo", "sac_algo", "crossq_algo", "pql_algo"])

@@ -7,30 +7,24 @@ learner's are those same entries applied to a clone of the tree taken before the
 write-back (alpha = 0.5), its own other modes (eager, per-slot graphs, one run graph), a plain learner when every weight is 1, and the
 uninterrupted run for a resumed one.
 """
+import functools
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import learner_harness as lh
+from learner_harness import PER, _same_state, _state
+from per_cases import Tree, model_tree
+from resume_cases import PQL, PQL_KEYS, PQL_TOY, child, same
+from support import T, dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if os.path.join(ROOT, "tests") not in sys.path:
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_per_gpu import T, Tree, model_tree  # noqa: E402
-from test_resume_gpu import PQL, PQL_KEYS, PQL_TOY, child, same  # noqa: E402
-
 R24 = 1 << 24
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(autouse=True)
@@ -52,7 +46,7 @@ CAPS = (50, 4096, 4097)                # one level; two levels of full nodes; th
 
 
 def sample_steps(tree, r, n_valid, beta):
-    """pqlk_per_sample_steps on `tree` (a test_per_gpu.Tree) -> (idx (steps, b), w (steps, b), wmax (steps)) as NumPy, outputs poisoned first."""
+    """pqlk_per_sample_steps on `tree` (a per_cases.Tree) -> (idx (steps, b), w (steps, b), wmax (steps)) as NumPy, outputs poisoned first."""
     L = tree.L
     steps, b = r.shape
     rd = T(np.asarray(r, dtype=np.int64)).to(tree.dev)
@@ -149,45 +143,14 @@ def test_sample_steps_on_exactly_summable_priorities(dev, capacity):
 
 # ------------------------------------------------------------------------------------------------ the learner
 O, A, B, K = 8, 2, 256, 4
-PER = ("algo.per.enabled=True", "algo.per.refresh=run", "algo.per.alpha=0.5", "algo.per.eps=1.0e-3")
-
-
-def _rows(n, seed, device):
-    g = torch.Generator().manual_seed(seed)
-    u = lambda shape, lo, hi: (torch.rand(shape, generator=g) * (hi - lo) + lo).to(device)  # noqa: E731
-    return (u((n, O), -3, 3), u((n, A), -1, 1), u((n, 1), -0.5, 0.5), u((n, O), -3, 3), (torch.rand((n, 1), generator=g) < 0.1).float().to(device))
+_rows = functools.partial(lh._rows, O, A)
 
 
 def _learner(*extra, graph, cap, rows, seed=11):
     """A V-learner at the toy shape (obs 8, act 2, batch 256, K = 4 steps per run), a policy, statistics and `rows` rows in the ring."""
-    from pql_amd.algo.learner import make_actor
-    from pql_amd.algo.pql_v_learner import PQLVLearner
     from pql_amd.utils.cfg import load_cfg
-    torch.manual_seed(seed)
-    cfg = load_cfg(["task.name=Toy", f"algo.batch_size={B}", f"algo.memory_size={cap}", "algo.v_learner_gpu=0", "algo.p_learner_gpu=0",
-                    "algo.num_gpus=1", f"algo.prefetch_steps={K}", f"algo.graph={graph}", *extra])
-    v = PQLVLearner((O,), A, cfg)
-    actor = make_actor(cfg, (O,), A, v.device)
-    g = torch.Generator().manual_seed(seed + 1)
-    norm = ((torch.rand(O, generator=g) - 0.5).to(v.device), (torch.rand(O, generator=g) * 1.5 + 0.5).to(v.device), 1e-4)
-    v.update(actor, _rows(rows, seed + 2, v.device), norm, 0)
-    return v, actor, norm
-
-
-def _state(v):
-    v.flush_priorities()
-    torch.cuda.synchronize()
-    out = dict(critic=v.critic.arena.data, target=v.critic_target.arena.data, adam_m=v.opt.m, adam_v=v.opt.v, adam_step=v.opt.step,
-               loss_ring=v.loss_ring)
-    if getattr(v.memory, "prioritized", False):
-        out.update(tree=v.memory.tree, pmax=v.memory.pmax)
-    return {k: t.detach().cpu().clone() for k, t in out.items()}
-
-
-def _same_state(a, b):
-    assert set(a) == set(b)
-    for k in a:
-        assert torch.equal(a[k], b[k]) and a[k].dtype == b[k].dtype, k
+    return lh._learner(lambda: load_cfg(["task.name=Toy", f"algo.batch_size={B}", f"algo.memory_size={cap}", "algo.v_learner_gpu=0", "algo.p_learner_gpu=0",
+                                         "algo.num_gpus=1", f"algo.prefetch_steps={K}", f"algo.graph={graph}", *extra]), O, A, rows, seed)
 
 
 def test_a_run_samples_from_the_tree_as_it_stood(dev):

@@ -240,8 +240,8 @@ def test_head_references_agree_with_float64():
 @pytest.mark.parametrize("gae", [True, False])
 @pytest.mark.parametrize("with_timeout", [False, True])
 def test_gae_reference_is_the_torch_loop_bit_for_bit(gae, with_timeout):
-    """The numpy restatement against test_ppo_gpu._gae_torch evaluated in fp32 on the CPU."""
-    from test_ppo_gpu import _gae_torch
+    """The numpy restatement against ppo_cases._gae_torch evaluated in fp32 on the CPU."""
+    _gae_torch = pc._gae_torch
     for Tn in pc.GAE_T:
         for n in pc.GAE_N:
             c = pc.gae_inputs(Tn, n)

@@ -6,19 +6,10 @@ import pytest
 import torch
 
 import detdata as dd
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 TRACES = [(g, v) for g in (1, 0) for v in (0, 1)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 def _cfg(extra=()):

@@ -12,19 +12,11 @@ import torch.nn as nn
 from torch.distributions import Independent, Normal
 
 import detdata as dd
+from ppo_cases import _gae_torch
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 def _ppo_cfg(extra=()):
@@ -33,33 +25,6 @@ def _ppo_cfg(extra=()):
 
 
 # ---------------------------------------------------------------------------------------------------- GAE
-def _gae_torch(rew, dones, values, next_value, next_done, gamma, lam, gae, timeout):
-    """ppo.py:88-124, op for op (one torch launch per op: no contraction)."""
-    Tn = rew.shape[0]
-    next_value = next_value.reshape(1, -1)
-    if gae:
-        adv = torch.zeros_like(rew)
-        last = 0
-        for t in reversed(range(Tn)):
-            if t == Tn - 1:
-                nnt, nv = 1.0 - next_done, next_value
-            else:
-                nnt, nv = 1.0 - dones[t + 1], values[t + 1]
-            nnt2 = torch.logical_xor(nnt, timeout[t]) if timeout is not None else nnt
-            delta = rew[t] + gamma * nv * nnt2 - values[t]
-            last = delta + gamma * lam * nnt * last
-            adv[t] = last
-        return adv, adv + values
-    ret = torch.zeros_like(rew)
-    for t in reversed(range(Tn)):
-        if t == Tn - 1:
-            nnt, nr = 1.0 - next_done, next_value
-        else:
-            nnt, nr = 1.0 - dones[t + 1], ret[t + 1]
-        ret[t] = rew[t] + gamma * nnt * nr
-    return ret - values, ret
-
-
 def _gae_hip(rew, dones, values, nv, nd, gamma, lam, gae, timeout):
     from pql_amd import _lib as L
     Tn, n = rew.shape

@@ -16,17 +16,12 @@ import torch
 
 import ppo_cases as pc
 from guarded import Guarded
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 T, F32 = pc.T, np.float32
 POISON, IN_ONE, IN_BIG = pc.POISON, pc.IN_ONE, pc.IN_BIG
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 def _g(dev, arr, fill, dtype=torch.float32):

@@ -5,14 +5,9 @@ import pytest
 import torch
 
 import quantile_cases as Q
+from support import cfg_of as _cfg
 
-BASE = ["task.name=Toy", "num_envs=4"]
 QR = "algo.cri_class=QuantileDoubleQ"
-
-
-def _cfg(algo, *extra):
-    from pql_amd.utils.cfg import load_cfg
-    return load_cfg([f"algo={algo}", *BASE, *extra])
 
 
 # ------------------------------------------------------------------------------------------------ references vs autograd

@@ -9,7 +9,9 @@ import torch
 
 import quantile_cases as Q
 from guarded import Guarded
+from quantile_cases import _check_buffers, _heads
 from reduction_cases import T
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,23 +24,9 @@ GAMMA_N = 0.99 ** 3
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def L():
     from pql_amd import _lib
     return _lib
-
-
-def _heads(dev, a, ld):
-    """(2, B, N) -> a device (2, B, ld) block whose pad columns hold NaN: a kernel that read them would show it."""
-    _, B, N = a.shape
-    t = torch.full((2, B, ld), float("nan"), dtype=torch.float32, device=dev)
-    t[:, :, :N] = T(a).to(dev)
-    return t
 
 
 def _launch(L, dev, case, gamma_n, kappa, per=False, ld=None, ring=False, slot=0, dpg=False):
@@ -69,13 +57,6 @@ def _launch(L, dev, case, gamma_n, kappa, per=False, ld=None, ring=False, slot=0
     full = dy.t.cpu().numpy()
     return dict(dy=full[:, :, :N], pad=full[:, :, N:], parts=scratch.t.cpu().numpy(), n_parts=parts, ring=out.cpu().numpy(),
                 abs_td=abs_td.t.cpu().numpy(), intact=dy.intact() and scratch.intact() and abs_td.intact(), B=B, N=N)
-
-
-def _check_buffers(got, per=False):
-    assert got["intact"], "a guard word behind dy, scratch or abs_td was overwritten"
-    assert (got["pad"] == 0).all(), "pad columns of dy must be written as zero"
-    assert np.isfinite(got["dy"]).all() and np.isfinite(got["parts"]).all()
-    assert np.isfinite(got["abs_td"]).all() if per else np.isnan(got["abs_td"]).all()   # the plain instance never touches abs_td
 
 
 # ------------------------------------------------------------------------------------------------ exact data

@@ -16,54 +16,11 @@ import torch
 
 import detdata as dd
 import quantile_cases as Q
+from learner_harness import PER, _compare_nets, _same_state, _sd, _state
+from quantile_cases import A, B, K, O, _cfg, _fill, _learner, _rows, _run, _weights
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
-O, A, B, K, HID = 8, 2, 256, 4, (64, 64)
-QR = "algo.cri_class=QuantileDoubleQ"
-PER = ("algo.per.enabled=True", "algo.per.refresh=run", "algo.per.alpha=0.5", "algo.per.eps=1.0e-3")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _sd(state):
-    return {k: T(v) for k, v in state.items()}
-
-
-def _fill(rows, seed):
-    return (T(dd.uniform((rows, O), seed, -3, 3)), T(dd.uniform((rows, A), seed + 1)), T(dd.uniform((rows, 1), seed + 2, -0.5, 0.5)),
-            T(dd.uniform((rows, O), seed + 3, -3, 3)), T(dd.bernoulli((rows, 1), seed + 4, 0.1)))
-
-
-def _cfg(N, *extra, graph=False, memory=4096, algo="pql_algo"):
-    from pql_amd.utils.cfg import load_cfg
-    base = [f"algo={algo}", "task.name=Toy", f"algo.batch_size={B}", f"algo.memory_size={memory}", QR, f"algo.num_quantiles={N}"]
-    if algo == "pql_algo":
-        base += ["algo.v_learner_gpu=0", "algo.p_learner_gpu=0", "algo.num_gpus=1", f"algo.prefetch_steps={K}", f"algo.graph={graph}"]
-    else:
-        base += ["num_envs=64", "device=cuda:0", "sim_device=cuda:0"]
-    cfg = load_cfg(base + list(extra))
-    cfg.algo.hidden_layers = list(HID)
-    return cfg
-
-
-def _compare_nets(module, nets, what, rtol=1e-5, atol=1e-5):
-    lay = module.layout
-    for n, net in enumerate(nets):
-        for l in range(lay.n_layers):
-            np.testing.assert_allclose(lay.weight(module.arena.data, n, l).cpu().numpy(), net[2 * l].detach().numpy(), rtol=rtol, atol=atol,
-                                       err_msg=f"{what} net {n} layer {l} weight")
-            np.testing.assert_allclose(lay.bias(module.arena.data, n, l).cpu().numpy(), net[2 * l + 1].detach().numpy(), rtol=rtol, atol=atol,
-                                       err_msg=f"{what} net {n} layer {l} bias")
-
-
-def _weights(N):
-    return dd.doubleq_state(O, A, N, 21 + N, HID), dd.mlp_state(O, A, 11, HID)
 
 
 # ------------------------------------------------------------------------------------------------ against the autograd learners
@@ -156,49 +113,6 @@ def test_ddpg_vs_autograd(dev, per):
 
 
 # ------------------------------------------------------------------------------------------------ modes, resume, priorities
-def _rows(n, seed, device):
-    g = torch.Generator().manual_seed(seed)
-    u = lambda shape, lo, hi: (torch.rand(shape, generator=g) * (hi - lo) + lo).to(device)  # noqa: E731
-    return (u((n, O), -3, 3), u((n, A), -1, 1), u((n, 1), -0.5, 0.5), u((n, O), -3, 3), (torch.rand((n, 1), generator=g) < 0.1).float().to(device))
-
-
-def _learner(N, *extra, graph, cap=4096, rows=1500, seed=11):
-    from pql_amd.algo.learner import make_actor
-    from pql_amd.algo.pql_v_learner import PQLVLearner
-    torch.manual_seed(seed)
-    cfg = _cfg(N, *extra, graph=graph, memory=cap)
-    v = PQLVLearner((O,), A, cfg)
-    actor = make_actor(cfg, (O,), A, v.device)
-    g = torch.Generator().manual_seed(seed + 1)
-    norm = ((torch.rand(O, generator=g) - 0.5).to(v.device), (torch.rand(O, generator=g) * 1.5 + 0.5).to(v.device), 1e-4)
-    v.update(actor, _rows(rows, seed + 2, v.device), norm, 0)
-    return v, actor, norm
-
-
-def _state(v):
-    v.flush_priorities()
-    torch.cuda.synchronize()
-    out = dict(critic=v.critic.arena.data, target=v.critic_target.arena.data, adam_m=v.opt.m, adam_v=v.opt.v, adam_step=v.opt.step,
-               loss_ring=v.loss_ring)
-    if getattr(v.memory, "prioritized", False):
-        out.update(tree=v.memory.tree, pmax=v.memory.pmax)
-    return {k: t.detach().cpu().clone() for k, t in out.items()}
-
-
-def _same_state(a, b):
-    assert set(a) == set(b)
-    for k in a:
-        assert torch.equal(a[k], b[k]) and a[k].dtype == b[k].dtype, k
-
-
-def _run(v, mode, n=K):
-    if mode == "run":
-        v.learn_many(n)
-    else:
-        for _ in range(n):
-            v.learn()
-
-
 @pytest.mark.parametrize("N,extra", [(8, ()), (33, ()), (8, PER)])
 def test_modes_agree(dev, N, extra):
     """Eager learn() x K, per-slot graphs and one run graph: two runs with an `update()` between leave the same arenas, Adam state

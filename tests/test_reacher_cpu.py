@@ -17,36 +17,13 @@ from pql_amd.envs.reacher import ReacherVecEnv, episode_return, jacobian_policy,
 from pql_amd.envs.swingup import SwingUpVecEnv
 from pql_amd.envs.synthetic import TASK_ENVS, TASK_SHAPES, SyntheticVecEnv, create_task_env
 from pql_amd.utils.cfg import load_cfg
+from task_cases import F, rot_np, tip_np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
-C4, S3, S5 = F(0.041666668), F(0.16666667), F(0.008333334)
 STREAM_TH, STREAM_W = 15, 16
 
 
-# --------------------------------------------------------------------------- the definition, once more, in numpy scalars
-def rot_np(c, s, d):
-    d2 = d * d
-    cd = F(1.0) - d2 * (F(0.5) - d2 * C4)
-    sd = d * (F(1.0) - d2 * (S3 - d2 * S5))
-    cn = c * cd - s * sd
-    sn = s * cd + c * sd
-    m = F(1.5) - F(0.5) * (cn * cn + sn * sn)
-    return cn * m, sn * m
-
-
-def tip_np(c, s):
-    """(ex, ey) of one env's chain c, s (A,)."""
-    A = len(c)
-    C, S = c[0], s[0]
-    x, y = C, S
-    for j in range(1, A):
-        C, S = C * c[j] - S * s[j], S * c[j] + C * s[j]
-        x, y = x + C, y + S
-    inv_a = F(1.0) / F(A)
-    return x * inv_a - F(0.6), y * inv_a
-
-
+# --------------------------------------------------------------------------- the definition, once more, in numpy scalars (rot_np, tip_np: tests/task_cases.py)
 class ReacherNp:
     """The issue's definition on numpy float32 scalars, env by env and joint by joint (independent of the env's code)."""
 

@@ -5,27 +5,18 @@ interact.  Run with `pytest -m gpu`."""
 import functools
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import task_cases as tc
-from test_info_track_cpu import ModelTrackers, assert_trackers_equal
-from test_reacher_cpu import F, rot_np, tip_np
+from support import dev  # noqa: F401
+from task_cases import F, ModelTrackers, assert_trackers_equal, rot_np, tip_np
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(autouse=True)

@@ -16,18 +16,13 @@ import torch
 import detdata as dd
 import reduction_cases as rc
 from guarded import Guarded
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 T = rc.T
 F32 = np.float32
 POISON, SLACK = rc.POISON, rc.SLACK
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -2,9 +2,10 @@
 record widths, the config key, the public header and the drain counts of the built fp16 gather kernels."""
 import os
 import re
-import sys
 
 import pytest
+
+from task_cases import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F16 = 0, 1
@@ -91,8 +92,7 @@ def test_fp16_gather_kernels_keep_their_counted_waits():
     test_gather_kernels_keep_their_counted_waits holds the fp32 kernels to: at most 3 full drains of the vector-memory queue
     (`s_waitcnt vmcnt(0)`) in the fast kernel, 5 in the obs kernel.  7 instantiations each, as there (4 + 3 with normalisation), of
     the 16-B-chunk kernels (`_f16`) and of the 8-B-chunk kernels that serve records of at most 512 B (`_h8`)."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    kr = load_script("tools/kernel_resources.py", "kernel_resources")
     if not os.path.exists(f"{kr.LLVM}/llvm-objdump"):
         pytest.skip("no llvm-objdump")
     drains = kr.full_drains(want=("k_replay_gather_fast_f16<true", "k_replay_gather_obs_f16<true", "k_replay_gather_fast_h8<true",

@@ -12,6 +12,9 @@ import pytest
 import torch
 
 import detdata as dd
+from learner_harness import _fill, _sd, make_cfg
+from resume_cases import PQL, PQL_KEYS, child, same
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -24,12 +27,6 @@ SHAPES = [(8, 2), (88, 16), (211, 20), (108, 21), (3, 1), (13, 5), (600, 7), (30
           (600, -1)]
 SENTINEL = -777.25
 CLAMP5, PADS_ZERO, NT_LOADS = 1, 2, 4
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def q(x):
@@ -347,7 +344,6 @@ def _qdata(data, dtype):
 
 
 def _pql_run(dev, dtype, distl, graph):
-    from test_learners_gpu import _fill, _sd, make_cfg
     from pql_amd.algo.pql_p_learner import PQLPLearner
     from pql_amd.algo.pql_v_learner import PQLVLearner
     O, A, B = 8, 2, 256
@@ -398,7 +394,6 @@ def _baseline_run(dev, algo, dtype):
     from pql_amd.envs.synthetic import create_task_env
     from pql_amd.replay.simple_replay import ReplayBuffer
     from pql_amd.utils.cfg import load_cfg
-    from test_learners_gpu import _fill
     O, A = 8, 2
     cfg = load_cfg([f"algo={algo}_algo", "task.name=Toy", "num_envs=64", "algo.batch_size=64", "algo.memory_size=400", "device=cuda:0",
                     "sim_device=cuda:0", "algo.update_times=3", f"algo.replay_obs_dtype={dtype}"])
@@ -446,7 +441,6 @@ _CK16 = {}
 
 def _half_way_fp16(tmp_path):
     """B1: the float16 run stopped at 3000 steps with a checkpoint (made once, used by both tests below)."""
-    from test_resume_gpu import PQL, child
     if "b1" not in _CK16:
         ck = tmp_path / "ck16"
         _CK16["b1"] = child(PQL, PM_SMALL + [H16, "max_step=3000", f"checkpoint.dir={ck}"], tmp_path)
@@ -459,7 +453,6 @@ def test_train_pql_on_fp16_rings_runs_and_resumes_bit_exact(tmp_path):
     tests/test_resume_gpu.py): A runs to max_step with finite losses; B1 stops half way with a checkpoint, B2 resumes it and ends with
     A's bits (scalar critic, graph mode)."""
     import math
-    from test_resume_gpu import PQL, PQL_KEYS, child, same
     a = child(PQL, PM_SMALL + [H16, "max_step=6000"], tmp_path)
     assert a["resumed_from"] is None and a["rollout_iterations"] == 62 and a["global_steps"] > 6000
     assert math.isfinite(a["critic_loss"]) and math.isfinite(a["actor_loss"]) and a["critic_updates"] == 8 * 62
@@ -472,7 +465,6 @@ def test_train_pql_on_fp16_rings_runs_and_resumes_bit_exact(tmp_path):
 
 def test_a_checkpoint_of_the_other_format_is_refused_by_name(tmp_path):
     """A float16 checkpoint under algo.replay_obs_dtype=float32, and a float32 one under float16: ValueError naming obs_dtype."""
-    from test_resume_gpu import PQL, child
     ck, b1 = _half_way_fp16(tmp_path)
     r = child(PQL, PM_SMALL + [F32, "max_step=6000", f"resume={ck}"], tmp_path, check=False)
     assert r.returncode != 0 and "ValueError" in r.stderr and "obs_dtype" in r.stderr and "float16" in r.stderr, r.stderr[-2000:]

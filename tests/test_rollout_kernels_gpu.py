@@ -19,6 +19,7 @@ import torch
 import rollout_cases as rc
 from guarded import Guarded
 from reduction_cases import IN_BIG, SLACK, T
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +28,10 @@ PTR_FILL = 12345           # slack around the two window pointers
 COUNTS = {"rollout-step launches": 0, "n-step calls": 0, "n-step launches": 0, "merge traces": 0, "merge launches": 0}
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
+@pytest.fixture(scope="module", autouse=True)
+def _launch_counts(dev):  # noqa: F811
     t0 = time.perf_counter()
-    yield torch.device("cuda:0")
+    yield
     print(f"\n[rollout kernels] {', '.join(f'{v} {k}' for k, v in COUNTS.items())}; {time.perf_counter() - t0:.2f} s in all")
 
 

@@ -2,24 +2,16 @@
 truncations against the oracle's assembler, bit-exact resume of a DDPG run on the task, and a training run that improves a policy on a
 task where neither the zero action nor a linear law does.  Run with `pytest -m gpu`."""
 import os
-import sys
 
 import pytest
 import torch
 
 import task_cases as tc
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(autouse=True)

@@ -19,6 +19,7 @@ import torch
 import backward_cases as bc
 import reduction_cases as rc
 from backward_job import Guarded, _returned, _sync_or_stop
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +29,6 @@ POISON, SLACK, IN_ONE = bc.POISON, bc.SLACK, bc.IN_ONE
 NAN = float("nan")
 PART_ROOM = 2048          # floats of room in loss_part and sumsq_part (include/pqlk.h)
 STEP0 = 5                 # the device step counter before a call that must move it by exactly 1
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 def _same(a, b):
@@ -51,16 +46,16 @@ class TdJob:
         self.dev, self.case, self.name = dev, p.case, p.case.name
         c = self.case
         self.desc = L.mlp_desc(c.dims, 2)
-        self.arena = Guarded(dev, (bc.net_stride(c.dims) * 2,), IN_ONE, bc.td_arena(p), front=True)
-        self.x = Guarded(dev, (c.B, c.ldx), IN_ONE, np.array(p.x), front=True)
-        self.acts_t = Guarded(dev, (bc.acts_floats(c.dims, 2, c.B),), IN_ONE, bc.td_target_stash(p), front=True)
-        self.rew = Guarded(dev, (c.B,), IN_ONE, p.rew.astype(F32), front=True)
-        self.done = Guarded(dev, (c.B,), IN_ONE, p.done.astype(F32), front=True)
-        self.dy = Guarded(dev, (2, c.B, 32), IN_ONE, np.array(p.dy), front=True)
+        self.arena = Guarded(dev, (bc.net_stride(c.dims) * 2,), IN_ONE, bc.td_arena(p), off=SLACK)
+        self.x = Guarded(dev, (c.B, c.ldx), IN_ONE, np.array(p.x), off=SLACK)
+        self.acts_t = Guarded(dev, (bc.acts_floats(c.dims, 2, c.B),), IN_ONE, bc.td_target_stash(p), off=SLACK)
+        self.rew = Guarded(dev, (c.B,), IN_ONE, p.rew.astype(F32), off=SLACK)
+        self.done = Guarded(dev, (c.B,), IN_ONE, p.done.astype(F32), off=SLACK)
+        self.dy = Guarded(dev, (2, c.B, 32), IN_ONE, np.array(p.dy), off=SLACK)
         self.inputs = [self.arena, self.x, self.acts_t, self.rew, self.done, self.dy]
         self.acts = None
         if p.tc.path == "bwd":
-            self.acts = Guarded(dev, (self.acts_t.n,), IN_ONE, bc.td_stash(p), front=True)
+            self.acts = Guarded(dev, (self.acts_t.n,), IN_ONE, bc.td_stash(p), off=SLACK)
             self.inputs.append(self.acts)
         self.gamma_n = bc.GAMMA_N
         self.ws_floats = int(L.lib.pqlk_mlp_bwd_ws_floats(C.byref(self.desc), c.B, c.splits))
@@ -88,7 +83,7 @@ class TdJob:
         from pql_amd import _lib as L
         n = int(L.lib.pqlk_mlp_packed_floats(C.byref(self.desc)))
         assert n > 0
-        self.packed = Guarded(self.dev, (n,), IN_ONE, body=NAN, front=True)
+        self.packed = Guarded(self.dev, (n,), IN_ONE, body=NAN, off=SLACK)
         assert _returned(L.lib.pqlk_mlp_pack(C.byref(self.desc), L.ptr(self.arena.t), L.ptr(self.packed.t), L.stream(self.dev)), "pqlk_mlp_pack") == 0
         _sync_or_stop(f"pqlk_mlp_pack on {self.name}")
         assert self.packed.intact() and not bool(torch.isnan(self.packed.t).any())
@@ -399,10 +394,10 @@ def test_sumsq_partials_with_a_head_that_is_not_fused(dev):
     desc = L.mlp_desc(case.dims, 2)
     parts = int(L.lib.pqlk_mlp_norm_parts(C.byref(desc)))
     assert parts == bc.norm_parts(case.dims, 2) and not bc.head_is_fused(case.dims)
-    arena = Guarded(dev, (bc.net_stride(case.dims) * 2,), IN_ONE, bc.arena(case), front=True)
-    acts = Guarded(dev, (bc.acts_floats(case.dims, 2, case.B),), IN_ONE, bc.norm_plain_stash(case), front=True)
-    x = Guarded(dev, (case.B, case.ldx), IN_ONE, bc.x_input(case), front=True)
-    dy = Guarded(dev, (2, case.B, bc.ld(case.dims[-1])), IN_ONE, bc.dy_input(case), front=True)
+    arena = Guarded(dev, (bc.net_stride(case.dims) * 2,), IN_ONE, bc.arena(case), off=SLACK)
+    acts = Guarded(dev, (bc.acts_floats(case.dims, 2, case.B),), IN_ONE, bc.norm_plain_stash(case), off=SLACK)
+    x = Guarded(dev, (case.B, case.ldx), IN_ONE, bc.x_input(case), off=SLACK)
+    dy = Guarded(dev, (2, case.B, bc.ld(case.dims[-1])), IN_ONE, bc.dy_input(case), off=SLACK)
     ws_floats = int(L.lib.pqlk_mlp_bwd_ws_floats(C.byref(desc), case.B, case.splits))
     ws = Guarded(dev, (ws_floats,), POISON, body=NAN)
     grads = Guarded(dev, (arena.n,), POISON, body=NAN)

@@ -9,8 +9,9 @@ import torch
 import quantile_cases as Q
 import tqc_cases as TQ
 from guarded import Guarded
+from quantile_cases import _check_buffers, _heads
 from reduction_cases import T
-from test_quantile_kernels_gpu import _check_buffers, _heads
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -19,12 +20,6 @@ RING = 5
 BS, NS = (1, 3, 4, 5, 257, 4100), (2, 3, 31, 32, 33, 64)
 GAMMA_N = 0.99 ** 3
 WORST = dict(dy=0.0, loss=0.0, abs_td=0.0)   # the largest observed fraction of each bound, printed by the last normal-data case
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

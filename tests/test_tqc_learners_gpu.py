@@ -4,7 +4,7 @@ Yardsticks: the CPU torch-autograd learners of tests/tqc_cases.py (the oracle's 
 identical weights, replay rows, injected indices and draws, at the tolerances of tests/test_learners_gpu.py for the same comparison
 (losses at rtol 1e-5; parameters at rtol 1e-5 with atol 1e-5 = 2 % of one Adam step); the learner's own other modes (eager, per-slot
 graphs, one run graph); the uninterrupted run for a resumed one; and the loss entries called directly on the heads a step produced.
-Helpers and sizes are those of tests/test_quantile_learners_gpu.py.
+Helpers and sizes are those of tests/test_quantile_learners_gpu.py (tests/quantile_cases.py, tests/learner_harness.py).
 """
 import numpy as np
 import pytest
@@ -12,18 +12,14 @@ import torch
 
 import detdata as dd
 import tqc_cases as TQ
-from test_quantile_learners_gpu import A, B, K, O, PER, T, _cfg, _compare_nets, _fill, _learner, _rows, _run, _same_state, _sd, _state, _weights
+from learner_harness import PER, _compare_nets, _same_state, _sd, _state
+from quantile_cases import A, B, K, O, _cfg, _fill, _learner, _rows, _run, _weights
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SETUPS = [(8, 2), (33, 5)]   # (N, d); 33: a padded head (ld 64), an odd pool
 ENTRIES = ("pqlk_qr_huber_loss", "pqlk_qr_huber_loss_per", "pqlk_tqc_huber_loss", "pqlk_tqc_huber_loss_per")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _drop(d):

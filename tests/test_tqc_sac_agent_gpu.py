@@ -16,8 +16,10 @@ import torch
 
 import detdata as dd
 import tqc_sac_cases as TS
-from test_quantile_learners_gpu import A, B, HID, O, T, _cfg, _compare_nets, _fill, _sd
-from test_resume_gpu import BASELINE_KEYS, BASELINES, TOY, child, same
+from learner_harness import _compare_nets, _sd
+from quantile_cases import A, B, HID, O, _cfg, _fill
+from resume_cases import BASELINE_KEYS, BASELINES, TOY, child, same
+from support import T, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -27,12 +29,6 @@ CAP, ROWS = 4096, 3000
 WATCHED = ("pqlk_sac_entropy_shift", "pqlk_dpg_loss_quantile", "pqlk_dpg_loss", "pqlk_td_mse_loss", "pqlk_td_mse_loss_per", "pqlk_qr_huber_loss",
            "pqlk_qr_huber_loss_per", "pqlk_tqc_huber_loss", "pqlk_tqc_huber_loss_per", "pqlk_tqc_huber_loss_soft", "pqlk_tqc_huber_loss_soft_per",
            "pqlk_dpg_loss_quantile_mean", "pqlk_sac_alpha_terms", "pqlk_sg_head_forward", "pqlk_sg_head_backward")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _tqc_cfg(N, d, *extra):

@@ -12,17 +12,12 @@ import torch
 import quantile_cases as Q
 import tqc_cases as TQ
 import tqc_sac_cases as TS
-from test_tqc_cpu import _tied_case
+from support import cfg_of as _cfg
+from tqc_cases import _tied_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE = ["task.name=Toy", "num_envs=4"]
 QR = "algo.cri_class=QuantileDoubleQ"
 E_NULL, E_SHAPE, E_ALIGN, E_UNSUPPORTED = 1, 2, 4, 5   # include/pqlk.h
-
-
-def _cfg(algo, *extra):
-    from pql_amd.utils.cfg import load_cfg
-    return load_cfg([f"algo={algo}", *BASE, *extra])
 
 
 # ------------------------------------------------------------------------------------------------ the references vs autograd

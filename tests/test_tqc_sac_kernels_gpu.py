@@ -12,8 +12,9 @@ import quantile_cases as Q
 import tqc_cases as TQ
 import tqc_sac_cases as TS
 from guarded import Guarded
+from quantile_cases import _check_buffers, _heads
 from reduction_cases import T
-from test_quantile_kernels_gpu import _check_buffers, _heads
+from support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +24,6 @@ BS, NS = (1, 3, 4, 5, 257, 4100), (2, 3, 31, 32, 33, 64)
 GAMMA_N = 0.99 ** 3
 LOG_ALPHA = float(np.log(0.2))
 WORST = dict(dy=0.0, loss=0.0, abs_td=0.0)   # the largest observed fraction of each bound, printed by every normal-data case
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -227,3 +227,24 @@ def make_ddpg_ref(O, A, hp, cap, actor, q1, q2, drop, kappa=1.0):
             return float(closs.detach()), float(aloss.detach())
 
     return TqcDDPGRef(O, A, hp, cap, actor, q1, q2)
+
+
+def _tied_case(B, N, seed):
+    """Normal data with rows made for the ranking: row 0 two values only, row 1 all atoms equal, row 2 the two target nets identical,
+    row 3 net 1 = net 0 reversed, row 4 done with ties; done elsewhere as drawn."""
+    case = Q.normal_case(B, N, seed, per=True)
+    rng = np.random.default_rng(seed + 1)
+    tt = case["theta_t"]
+    def two_values():   # N of the 2 N atoms low (3 of 4 at N = 2), anywhere in the pool: no cut M = 2 or 2 N - 2 falls on the edge
+        pool = np.full(2 * N, 0.75, np.float32)
+        pool[rng.permutation(2 * N)[: N if N > 2 else 3]] = np.float32(-0.5)
+        return pool.reshape(2, N)
+
+    tt[:, 0] = two_values()
+    tt[:, 1] = np.float32(0.25)
+    tt[1, 2] = tt[0, 2]
+    tt[1, 3] = tt[0, 3, ::-1]
+    tt[:, 4] = two_values()
+    case["done"][:5] = np.array([0, 0, 0, 0, 1], np.float32)
+    case["done"][5] = 1.0
+    return case
