@@ -625,6 +625,48 @@ int pqlk_dpg_loss_quantile_mean(const float* theta, int64_t ld, int32_t n, int64
                                 const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * HL-Gauss loss for the categorical twin critic (Farebrother et al. 2024, "Stop regressing").  The reference has no such loss; the
+ * formulas below are the paper's, adapted to twin critics and clipped double-Q.  Network, support, layout and the actor's loss
+ * (pqlk_dpg_loss with k > 1) are those of pqlk_c51_bce_loss: logits, logits_t (2, B, ld), 2 <= K <= PQLK_C51_MAX_ATOMS atoms,
+ * support = z (K).  Every operation is fp32 without contraction unless stated.
+ *
+ * Target value.  For each target net i: P = softmax(logits_t[i, b, :K]) and E_i = sum_k P_k z_k (the softmax and the dot product
+ * of pqlk_dpg_loss: per lane over its atoms lane + 64 j in increasing j, then a wave butterfly).
+ * y = r + ((1 - d) * gamma_n) * fminf(E_0, E_1), in this order (pqlk_td_mse_loss's); then y = fminf(fmaxf(y, v_min), v_max).
+ * Bins.  dz = (v_max - v_min) / (K - 1), formed in double and rounded once, as in C51.  Edge e_k = v_min + ((float)k - 0.5f) * dz
+ * for k = 0 ... K.  inv = (float)(1.0 / ((double)sigma_ratio * (double)dz * sqrt(2.0))), formed in double on the host from the
+ * fp32 sigma_ratio and the rounded fp32 dz: 1 / (sigma sqrt 2) with sigma = sigma_ratio bin widths.  u_k = (e_k - y) * inv.
+ * c(u) = 1 if u >= 4, -1 if u <= -4, else erff(u): what a correctly rounded erf returns there, so that the saturated bits do not
+ * depend on the math library.
+ * Target pmf.  t_k = (c(u_{k+1}) - c(u_k)) / (c(u_K) - c(u_0)): the mass of N(y, sigma^2) in bin k over its mass on the support.
+ * Each lane evaluates its own two edges and the two outer ones; there is no cross-lane sum in the target.
+ * Loss.  Per net i: m = max_k x_k, s = sum_k expf(x_k - m), lse = m + logf(s) with x = logits[i, b, :K] (the reduction order of the
+ * softmax above); l_ib = sum_k t_k * (lse - x_k), where a term with t_k == 0 contributes 0 (per lane in increasing j, then a wave
+ * butterfly).  The row adds wh * (l_0b + l_1b) to its block's partial (wh = 1: l_0b + l_1b); the fold scale is 1 / B, formed as
+ * 1.0f / (float)B -- not C51's 1 / (B K).  The partial count stays pqlk_loss_parts(b, k).
+ * Gradient.  dy[i, b, k] = (wh * (1 / B)) * (p_k - t_k) with p_k = expf(x_k - m) / s; pad columns [K, ld) are written as zero.
+ * Prioritized variant (_per).  wh = w[b] / wmax[0]; abs_td_out[b] = max_i |sum_k p_ik z_k - y|.  The plain entry never reads w,
+ * wmax or abs_td_out; with every w and wmax 1.0 the weighted entry gives its bits.
+ * target_out: optional (B, K), receives t (tests); it changes no other output.
+ * Non-finite inputs.  A row whose reward, done flag or any of whose 4 K logits is not finite takes y = NaN: its dy, its target_out,
+ * its abs_td_out and the loss are NaN.  No value ever becomes an address: such a row cannot make a kernel read or write out of
+ * bounds.
+ *
+ * loss_out / slot_dev / ring_len / scratch: as for every loss above.  No float atomics, every reduction in a fixed order: two
+ * launches on the same inputs give the same bits.
+ * Errors, before any launch: PQLK_E_NULL a NULL pointer; PQLK_E_SHAPE b <= 0, k < 2, sigma_ratio not > 0, v_max <= v_min or a ring
+ * without a length; PQLK_E_UNSUPPORTED k > PQLK_C51_MAX_ATOMS; PQLK_E_ALIGN ld not a multiple of 32 or ld < k.
+ * ---------------------------------------------------------------------------------------------- */
+int pqlk_hlgauss_ce_loss(const float* logits, const float* logits_t, int64_t ld, int32_t k, const float* rew, const float* done,
+                         const float* support /*(K) z atoms*/, float gamma_n, float v_min, float v_max, float sigma_ratio, int64_t b,
+                         float* dy, float* loss_out, const int32_t* slot_dev, int32_t ring_len, float* target_out, float* scratch,
+                         pqlk_stream_t stream);
+int pqlk_hlgauss_ce_loss_per(const float* logits, const float* logits_t, int64_t ld, int32_t k, const float* rew, const float* done,
+                             const float* support, float gamma_n, float v_min, float v_max, float sigma_ratio, int64_t b, float* dy,
+                             float* loss_out, const int32_t* slot_dev, int32_t ring_len, float* target_out, float* scratch,
+                             const float* w, const float* wmax, float* abs_td_out, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser: clip_grad_norm_ + AdamW (+ Polyak) over flat arenas
  * (pql_v_learner.py:124-133, pql_p_learner.py:87-96, pql/utils/torch_util.py:9-12).
  *   g *= grad_scale   (1/world_size after a data-parallel sum all-reduce; 1.0 otherwise)

@@ -97,6 +97,20 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     if drop is not None and not quantile:
         raise ValueError(f"algo.qr_drop={drop!r} needs algo.cri_class=QuantileDoubleQ (got algo.cri_class={cri}): it truncates the pooled "
                          f"target atoms of the quantile critic; leave algo.qr_drop null with any other critic")
+    # (algo.distl_loss, algo.hl_sigma: which law trains the C51 head's logits -- the loss launch alone, so neither a row's key nor a
+    # constructor argument nor a checkpoint's structure)
+    loss, sigma = algo.get("distl_loss", "c51"), algo.get("hl_sigma", 0.75)
+    if loss not in ("c51", "hl_gauss"):
+        raise ValueError(f"algo.distl_loss must be c51 or hl_gauss, got {loss!r}")
+    if loss == "hl_gauss":
+        if not algo.get("distl"):
+            raise ValueError(f"algo.distl_loss=hl_gauss needs algo.distl=True (got algo.distl={algo.get('distl')!r}): HL-Gauss is a loss of "
+                             f"the categorical head; leave algo.distl_loss=c51 with a scalar or quantile critic")
+        if name not in ("PQL", "DDPG"):
+            raise ValueError(f"algo.distl_loss=hl_gauss cannot run with algo.name={name}: the HL-Gauss loss is built for algo=pql_algo and "
+                             f"algo=ddpg_algo (its target carries no entropy term and no joint-batch statistics)")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not float(sigma) > 0.0:
+        raise ValueError(f"algo.hl_sigma must be > 0 (sigma of the HL-Gauss target in bin widths), got {sigma!r}")
     # ---- the class's row
     where = f"algo.cri_class={r.name}"
     if algo.get("distl") and r.no_distl:

@@ -100,6 +100,16 @@ def qr_targets(algo, n):
     return int(n) if d is None else 2 * (int(n) - d)
 
 
+def distl_loss(algo):
+    """`algo.distl_loss`, the law the categorical head is trained with: "c51" (also for a config without the key) or "hl_gauss"."""
+    return str(_cfg_get(algo, "distl_loss", "c51"))
+
+
+def hl_sigma(algo):
+    """`algo.hl_sigma` as the HL-Gauss entries take it: sigma in bin widths (0.75 for a config without the key)."""
+    return float(_cfg_get(algo, "hl_sigma", 0.75))
+
+
 def f32_recip(*factors, sign=1.0):
     """sign / (f0 * f1 ...) evaluated in fp32, like the kernels' `1.0f / ((float)b * (float)k)`."""
     import numpy as np

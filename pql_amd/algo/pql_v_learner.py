@@ -22,8 +22,8 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.algo.heads import CriticHead
 from pql_amd.algo.critics import check_critic_class, check_target_dtype, make_critic
-from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, graph_collective_enabled,
-                                  load_artifact, make_actor, pump, resident_norm)
+from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, distl_loss,
+                                  graph_collective_enabled, load_artifact, make_actor, pump, resident_norm)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
                                 output_view)
 from pql_amd.replay.prioritized_replay import PrioritizedReplayBuffer, per_beta, per_cfg
@@ -43,7 +43,7 @@ class PQLVLearner(Learner):
         self._per = per_cfg(cfg.algo)
         self._per_pending = 0   # steps taken since the last write-back: rows [0, n) of the |TD| slabs wait for `flush_priorities`
         if self._per is not None:
-            if _cfg_get(cfg.algo, "distl", False):
+            if _cfg_get(cfg.algo, "distl", False) and distl_loss(cfg.algo) == "c51":   # (hl_gauss has a |TD| and a weighted entry)
                 raise ValueError("algo.distl=True is not supported with algo.per.enabled=True (algo.per.refresh=run): there is no weighted C51 loss")
             if process_group is not None:
                 raise ValueError("algo.per.enabled=True (algo.per.refresh=run) is single-GPU only: PQLVLearner was given a process group "

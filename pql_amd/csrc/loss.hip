@@ -1,4 +1,4 @@
-// Loss kernels: TD target + twin MSE, C51 softmax/projection/BCE, DPG actor loss.
+// Loss kernels: TD target + twin MSE, C51 softmax/projection/BCE, HL-Gauss cross-entropy, DPG actor loss, quantile Huber losses.
 // Reference: pql/algo/pql_v_learner.py:80-108, pql/utils/distl_util.py:4-20, pql/algo/pql_p_learner.py:55-57,
 // pql/models/mlp.py:256-263.  Each kernel writes the gradient w.r.t. the critic's last-layer output
 // (padded (2,B,ld) layout expected by pqlk_mlp_backward) and deterministic per-block loss partials.
@@ -392,7 +392,155 @@ extern "C" int pqlk_c51_bce_loss(const float* logits, const float* logits_t, int
 }
 
 // ------------------------------------------------------------------------------------------------
-// DPG: L = -mean(min(Q1, Q2)); gradient w.r.t. the critic outputs (ties split evenly like torch.min).
+// HL-Gauss (Farebrother et al. 2024) on the categorical head: the law is written out in include/pqlk.h.  Geometry of k_c51_bce
+// without its image: the scalar TD target y of k_td_mse, formed from the target nets' expectations, is spread over the K bins as
+// a Gaussian histogram that each lane evaluates for its own atoms (no cross-lane sum in the target), and the logits are trained
+// with a soft-target cross-entropy.  The bin edges depend on the support alone and stay in registers over the row loop.
+__device__ __forceinline__ float hl_cdf(float u) { return u >= 4.f ? 1.f : (u <= -4.f ? -1.f : erff(u)); }
+
+template <int NJ, bool PER>
+__global__ __launch_bounds__(256) void k_hlgauss_ce(const float* __restrict__ logits, const float* __restrict__ logits_t,
+                                                    int64_t ld, int K, const float* __restrict__ rew,
+                                                    const float* __restrict__ done, const float* __restrict__ support,
+                                                    float gamma_n, float v_min, float v_max, float dz, float inv, int64_t b,
+                                                    float* __restrict__ dy, float* __restrict__ target_out,
+                                                    float* __restrict__ part, const float* __restrict__ w,
+                                                    const float* __restrict__ wmax, float* __restrict__ abs_td) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const float inv_b = 1.0f / (float)b;
+  float wm = 1.f;
+  if constexpr (PER) wm = wmax[0];
+  float zk[NJ], e_lo[NJ], e_hi[NJ];
+  load_row<NJ>(support, K, lane, zk);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {   // the edges of bin k = lane + 64 j: e_k and e_{k + 1}
+    e_lo[j] = v_min + ((float)(lane + 64 * j) - 0.5f) * dz;
+    e_hi[j] = v_min + ((float)(lane + 64 * j + 1) - 0.5f) * dz;
+  }
+  const float e_first = v_min + (0.f - 0.5f) * dz, e_last = v_min + ((float)K - 0.5f) * dz;
+  float acc = 0.f;
+  for (int64_t i = wave; i < b; i += nw) {
+    const float r = rew[i], d = done[i];
+    float x0[NJ], x1[NJ], pt[NJ];
+    load_row<NJ>(logits + i * ld, K, lane, x0);
+    load_row<NJ>(logits + (b + i) * ld, K, lane, x1);
+    // y = clamp(r + (1 - d) gamma^n min_i E_i[z]) -- k_td_mse's target on the target nets' expectations (k_dpg_dist's E[z])
+    bool odd = !(fabsf(r) < INFINITY) || !(fabsf(d) < INFINITY);
+    load_row<NJ>(logits_t + i * ld, K, lane, pt);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) odd |= !(fabsf(pt[j]) < INFINITY) || !(fabsf(x0[j]) < INFINITY) || !(fabsf(x1[j]) < INFINITY);
+    wave_softmax<NJ>(pt, K, lane);
+    const float q0 = wave_dot<NJ>(pt, zk);
+    load_row<NJ>(logits_t + (b + i) * ld, K, lane, pt);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) odd |= !(fabsf(pt[j]) < INFINITY);
+    wave_softmax<NJ>(pt, K, lane);
+    const float q1 = wave_dot<NJ>(pt, zk);
+    float y = r + ((1.f - d) * gamma_n) * fminf(q0, q1);
+    y = fminf(fmaxf(y, v_min), v_max);
+    if (__ballot(odd) != 0) y = NAN;   // a row with a non-finite input: every output of the row, and the loss, is NaN
+    // target pmf: the mass of N(y, sigma^2) between the edges of each bin, over its mass on the whole support
+    const float c_first = hl_cdf((e_first - y) * inv), c_last = hl_cdf((e_last - y) * inv);
+    const float norm = c_last - c_first;
+    float t[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      t[j] = (hl_cdf((e_hi[j] - y) * inv) - hl_cdf((e_lo[j] - y) * inv)) / norm;
+      if (lane + 64 * j >= K) t[j] = 0.f;
+      else if (target_out) target_out[i * K + lane + 64 * j] = t[j];
+    }
+    float wh = 1.f, g = inv_b, td = 0.f;
+    if constexpr (PER) {
+      wh = w[i] / wm;
+      g = wh * inv_b;
+    }
+    float lrow = 0.f;
+#pragma unroll
+    for (int net = 0; net < 2; ++net) {
+      float(&x)[NJ] = net == 0 ? x0 : x1;
+      float p[NJ];
+      // log-sum-exp and softmax in wave_softmax's reduction order
+      float m = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        if (lane + 64 * j < K) m = fmaxf(m, x[j]);
+      m = wave_max(m);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) p[j] = lane + 64 * j < K ? expf(x[j] - m) : 0.f;
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) s += p[j];
+      s = wave_sum(s);
+      const float lse = m + logf(s);
+      float le = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        p[j] = p[j] / s;
+        le += t[j] == 0.f ? 0.f : t[j] * (lse - x[j]);   // (t is 0 past K)
+      }
+      lrow += wave_sum(le);
+      if constexpr (PER) td = fmaxf(td, fabsf(wave_dot<NJ>(p, zk) - y));
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) p[j] = g * (p[j] - t[j]);
+      store_dy_row<NJ>(dy + ((int64_t)net * b + i) * ld, ld, K, lane, p);
+    }
+    if constexpr (PER) {
+      lrow = wh * lrow;
+      if (lane == 0) abs_td[i] = y != y ? y : td;   // (fmaxf drops a NaN: the row's |TD| is NaN with its y)
+    }
+    if (lane == 0) acc += lrow;
+  }
+  const float s = block_sum_256(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+template <int NJ>
+static constexpr auto k_hlgauss_plain = &k_hlgauss_ce<NJ, false>;   // (C51_LAUNCH names its kernel with one argument)
+template <int NJ>
+static constexpr auto k_hlgauss_weighted = &k_hlgauss_ce<NJ, true>;
+
+template <bool PER>
+static int hlgauss_impl(const float* logits, const float* logits_t, int64_t ld, int32_t k, const float* rew, const float* done,
+                        const float* support, float gamma_n, float v_min, float v_max, float sigma_ratio, int64_t b, float* dy,
+                        float* loss_out, const int32_t* slot_dev, int32_t ring_len, float* target_out, float* scratch, const float* w,
+                        const float* wmax, float* abs_td_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(logits && logits_t && rew && done && support && dy && scratch, PQLK_E_NULL);
+  PQLK_REQUIRE(!PER || (w && wmax && abs_td_out), PQLK_E_NULL);
+  PQLK_REQUIRE(!slot_dev || ring_len > 0, PQLK_E_SHAPE);
+  PQLK_REQUIRE(b > 0 && k >= 2 && sigma_ratio > 0.f && v_max > v_min, PQLK_E_SHAPE);
+  PQLK_REQUIRE(k <= PQLK_C51_MAX_ATOMS, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(ld % 32 == 0 && ld >= k, PQLK_E_ALIGN);
+  const float dz = (float)(((double)v_max - (double)v_min) / (double)(k - 1));
+  const float inv = (float)(1.0 / ((double)sigma_ratio * (double)dz * sqrt(2.0)));
+  const int blocks = loss_blocks(b, k);
+  if constexpr (PER)
+    C51_LAUNCH(k_hlgauss_weighted, k, blocks, stream, logits, logits_t, ld, (int)k, rew, done, support, gamma_n, v_min, v_max, dz, inv,
+               b, dy, target_out, scratch, w, wmax, abs_td_out);
+  else
+    C51_LAUNCH(k_hlgauss_plain, k, blocks, stream, logits, logits_t, ld, (int)k, rew, done, support, gamma_n, v_min, v_max, dz, inv, b,
+               dy, target_out, scratch, w, wmax, abs_td_out);
+  PQLK_LAUNCH_CHECK();
+  return fold_partials(scratch, blocks, 1.0f / (float)b, loss_out, slot_dev, ring_len, stream);
+}
+
+extern "C" int pqlk_hlgauss_ce_loss(const float* logits, const float* logits_t, int64_t ld, int32_t k, const float* rew,
+                                    const float* done, const float* support, float gamma_n, float v_min, float v_max,
+                                    float sigma_ratio, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                                    int32_t ring_len, float* target_out, float* scratch, pqlk_stream_t stream) {
+  return hlgauss_impl<false>(logits, logits_t, ld, k, rew, done, support, gamma_n, v_min, v_max, sigma_ratio, b, dy, loss_out, slot_dev,
+                             ring_len, target_out, scratch, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int pqlk_hlgauss_ce_loss_per(const float* logits, const float* logits_t, int64_t ld, int32_t k, const float* rew,
+                                        const float* done, const float* support, float gamma_n, float v_min, float v_max,
+                                        float sigma_ratio, int64_t b, float* dy, float* loss_out, const int32_t* slot_dev,
+                                        int32_t ring_len, float* target_out, float* scratch, const float* w, const float* wmax,
+                                        float* abs_td_out, pqlk_stream_t stream) {
+  return hlgauss_impl<true>(logits, logits_t, ld, k, rew, done, support, gamma_n, v_min, v_max, sigma_ratio, b, dy, loss_out, slot_dev,
+                            ring_len, target_out, scratch, w, wmax, abs_td_out, stream);
+}
+
 __global__ __launch_bounds__(256) void k_dpg_scalar(const float* __restrict__ q, int64_t ld, int64_t b,
                                                     float* __restrict__ dy, float* __restrict__ part,
                                                     uint8_t* __restrict__ owner) {
