@@ -667,6 +667,62 @@ int pqlk_hlgauss_ce_loss_per(const float* logits, const float* logits_t, int64_t
                              const float* w, const float* wmax, float* abs_td_out, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Critic diagnostics (opt-in, algo.diag.enabled; the reference logs none).  Read-only on every input; no gradient, no loss.
+ *
+ * pqlk_critic_stats.  q: the twin heads' output, qt: the target heads' output, both (2, B, ld) as the loss entries take them.
+ * head / k: PQLK_HEAD_SCALAR with k = 1; PQLK_HEAD_CATEGORICAL with 2 <= k <= PQLK_C51_MAX_ATOMS, z_atoms (k), v_min < v_max;
+ * PQLK_HEAD_QUANTILE with 2 <= k <= PQLK_QR_MAX_QUANTILES (z_atoms, v_min, v_max are not looked at off the categorical head).
+ * Every operation is fp32 without contraction.
+ * Row value V_i of net i (V'_i: of target net i, the same law on qt):
+ *   scalar       column 0;
+ *   categorical  E_i[z] = sum_k P_k z_k, P = softmax(q[i, b, :k]): the softmax and the dot product of pqlk_dpg_loss and
+ *                pqlk_hlgauss_ce_loss (per lane over its atoms lane + 64 j in increasing j, then a wave butterfly): their bits;
+ *   quantile     (sum_j q[i, b, j]) * (1.0f / (float)k), the sum a wave butterfly over the 64 lanes (lanes >= k hold 0): the Q of
+ *                pqlk_dpg_loss_quantile.
+ * Target: y = r + ((1 - d) * gamma_n) * fminf(V'_0, V'_1), in this order (pqlk_td_mse_loss's).  On the categorical head y is then
+ * clamped, fminf(fmaxf(y, v_min), v_max) as pqlk_hlgauss_ce_loss does, except that a NaN stays a NaN.
+ * out[0 .. PQLK_CRITIC_STATS), over the B rows:
+ *   0 mean V_0    1 mean V_1    2 min of fminf(V_0, V_1)    3 max of fmaxf(V_0, V_1)    4 mean y
+ *   5 mean of (V_0 + V_1) * 0.5f - y (bias)       6 mean of td = fmaxf(fabsf(V_0 - y), fabsf(V_1 - y))       7 max of td
+ *   8 mean of fabsf(V_0 - V_1) (twin gap)         9 the number of rows where V_0, V_1 or the unclamped y is not finite, as a float
+ *                                                   (exact below 2^24 rows)
+ * A mean is the sum times 1.0f / (float)B -- one multiplication by the rounded reciprocal, the fold scale of the loss entries -- and
+ * the sums start from 0.f.  Non-finite values are not filtered out of the sums: they propagate into the means; out[9] says how many
+ * rows carried them.  The min and the max are fminf / fmaxf folds from +inf / -inf: they keep an infinity and drop a NaN operand.
+ * Geometry: pqlk_loss_parts(b, k) blocks, as the loss entries (scalar: one row per thread, 256 per block; wider heads: one wave per
+ * row, four per block; a row loop above 1024 blocks); PQLK_CRITIC_STATS partials per block in scratch, folded by a second launch of
+ * one block: per thread a chain over blocks t, t + 256, ..., a wave butterfly, the four waves as (w0 + w1) + (w2 + w3).  No float
+ * atomics: two calls on the same inputs give the same bits.
+ * scratch: >= pqlk_critic_stats_scratch_floats(b, k) floats (PQLK_CRITIC_STATS * pqlk_loss_parts(b, k)).
+ * Errors, before any launch: PQLK_E_NULL a NULL q, qt, rew, done, out, scratch, or z_atoms on the categorical head; PQLK_E_UNSUPPORTED
+ * an unknown head or k above the head's maximum; PQLK_E_SHAPE b <= 0, k != 1 on the scalar head, k < 2 on the others, v_max <= v_min
+ * on the categorical head; PQLK_E_ALIGN ld < 32, ld not a multiple of 32 or ld < k.
+ *
+ * pqlk_unit_stats.  h (rows, ld): one layer's post-ELU activations with `cols` valid columns (a stash block addressed through
+ * pqlk_mlp_act_offset, or a per-layer critic's own matrix); columns >= cols are never read.  0 <= tau < 1.
+ *   a_c = (sum_r fabsf(h[r, c])) / (float)rows;   A = (sum_c a_c) / (float)cols;   unit c is dormant iff a_c <= tau * A
+ *   (Sokar et al. 2023, "The dormant neuron phenomenon"; tau * A one fp32 product);   s(x) = x > 0 ? 1 : x + 1 (ELU' from ELU's output)
+ *   out[0] = (number of dormant units) / (float)cols      out[1] = A      out[2] = (sum_c sum_r s(h[r, c])) / ((float)rows * (float)cols)
+ * Order of the sums: rows are cut into min(rows, PQLK_UNIT_CHUNKS) chunks of ceil(rows / chunks) consecutive rows; within a chunk wave
+ * w of the block adds rows w, w + 4, ... of its column, the four waves join as (w0 + w1) + (w2 + w3); a second launch of one block
+ * adds a column's chunks in index order; thread t of it then adds its columns t, t + 256, ... in increasing c (a_c and the slope sums
+ * alike), and the 256 threads join by a wave butterfly and (w0 + w1) + (w2 + w3).  No float atomics.
+ * scratch: >= pqlk_unit_stats_scratch_floats(cols) floats ((2 * PQLK_UNIT_CHUNKS + 1) * cols).
+ * Errors, before any launch: PQLK_E_NULL a NULL h, out or scratch; PQLK_E_SHAPE rows <= 0, cols <= 0, ld < cols, or tau outside
+ * [0, 1) (a NaN included).
+ * ---------------------------------------------------------------------------------------------- */
+#define PQLK_CRITIC_STATS 10
+#define PQLK_UNIT_CHUNKS 64
+enum { PQLK_HEAD_SCALAR = 0, PQLK_HEAD_CATEGORICAL = 1, PQLK_HEAD_QUANTILE = 2 };
+int64_t pqlk_critic_stats_scratch_floats(int64_t b, int32_t k);   /* 0 for b <= 0 or k < 1.  Host only. */
+int pqlk_critic_stats(const float* q, const float* qt, int64_t ld, int32_t head, int32_t k, const float* z_atoms, float v_min,
+                      float v_max, const float* rew, const float* done, float gamma_n, int64_t b, float* out, float* scratch,
+                      pqlk_stream_t stream);
+int64_t pqlk_unit_stats_scratch_floats(int32_t cols);             /* 0 for cols <= 0.  Host only. */
+int pqlk_unit_stats(const float* h, int64_t ld, int64_t rows, int32_t cols, float tau, float* out, float* scratch,
+                    pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimiser: clip_grad_norm_ + AdamW (+ Polyak) over flat arenas
  * (pql_v_learner.py:124-133, pql_p_learner.py:87-96, pql/utils/torch_util.py:9-12).
  *   g *= grad_scale   (1/world_size after a data-parallel sum all-reduce; 1.0 otherwise)

@@ -14,6 +14,7 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.algo.heads import CriticHead
 from pql_amd.algo.critics import check_critic_class, make_critic
+from pql_amd.algo.diag import CriticProbe, diag_cfg
 from pql_amd.algo.learner import LOSS_RING, _AdamState, apply_optimizer, check_per_refresh, make_actor
 from pql_amd.algo.pql_actor import PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
@@ -27,6 +28,7 @@ class ActorCriticBase(PQLActor):
     def __init__(self, env, cfg):
         check_critic_class(cfg, agent=True)   # before anything is allocated
         check_per_refresh(cfg, f"algo={cfg.algo.name}")
+        diag = diag_cfg(cfg)   # algo.diag.enabled=True is refused here for every agent but DDPG
         cfg.algo.v_learner_gpu = cfg.algo.get("v_learner_gpu", 0) or 0
         cfg.algo.p_learner_gpu = cfg.algo.get("p_learner_gpu", 0) or 0
         super().__init__(env, cfg)
@@ -46,6 +48,8 @@ class ActorCriticBase(PQLActor):
         self._ws = None
         self.per = per_cfg(algo)   # algo.per when prioritized replay is on (None: every launch below is the plain one)
         self.per_calls = 0         # calls of update_net so far: the position on the beta schedule (host side, saved)
+        # algo.diag.enabled: the probe at the end of `update_net` (pql_amd/algo/diag.py); None = off
+        self._diag = None if diag is None else CriticProbe(self.head, *diag, len(self._elu_layers()), self.device)
 
     # ---- training state ----------------------------------------------------------------------------
     def _own_state(self):
@@ -156,14 +160,46 @@ class ActorCriticBase(PQLActor):
     def _one_layout(self):
         return hasattr(self.critic, "layout")
 
-    def _critic_forward(self, ws, net, x, slot):
+    def _critic_forward(self, ws, net, x, slot, probe=False):
         """Q of `net` (the critic or its target) on x (B, ld_sa) -> ((2, B, ld) output, ld).  slot: "c" (the stash `_critic_grads` /
-        `_critic_dx` read) or "t" (the target's)."""
+        `_critic_dx` read) or "t" (the target's).  probe (the diagnostics): a stash of the probe's own, and a dropout critic runs
+        without dropout and leaves its call counter alone."""
         if self._one_layout:
             cl = net.layout
-            mlp_forward_raw(cl, net.arena.data, x, L.ACT_NONE, acts=ws["acts_" + slot])
-            return output_view(cl, ws["acts_" + slot], ws["B"]), cl.ld_out
+            key = ("diag_" if probe else "acts_") + slot
+            if key not in ws:
+                ws[key] = torch.empty(cl.acts_floats(ws["B"]), dtype=torch.float32, device=self.device)
+            mlp_forward_raw(cl, net.arena.data, x, L.ACT_NONE, acts=ws[key])
+            return output_view(cl, ws[key], ws["B"]), cl.ld_out
+        if probe and hasattr(net, "drop_state"):
+            return net.forward_raw(x, drop=False), 32
         return net.forward_raw(x), 32
+
+    def _elu_layers(self):
+        """The critic's hidden layers that end in an ELU (0-based), whose outputs the diagnostics' unit statistics read."""
+        if self._one_layout:
+            return list(range(self.critic.layout.n_layers - 1))
+        return self.critic.elu_layers()
+
+    def _probe(self):
+        """The diagnostics of the critic as `update_net` leaves it, on the last batch it was trained on (ws["xn_sa"] holds a' in its
+        action columns): pql_amd/algo/diag.py.  Runs after the last `update_once`, when no backward is waiting for a stash."""
+        d, ws, algo = self._diag, self._ws, self.cfg.algo
+        B = ws["B"]
+        with torch.cuda.device(self.device):
+            qt, _ = self._critic_forward(ws, self.critic_target, ws["xn_sa"], "t", probe=True)
+            q, ld = self._critic_forward(ws, self.critic, ws["x_sa"], "c", probe=True)
+            d.critic_stats(q, qt, ld, ws["rew"], ws["done"], float(algo.gamma) ** int(algo.nstep), B)
+            for net in range(2):
+                for k, layer in enumerate(self._elu_layers()):
+                    if self._one_layout:
+                        cl = self.critic.layout
+                        off, ldh = cl.act_offset(B, net, layer)
+                        d.unit_stats(net, k, ws["diag_c"][off:], ldh, B, cl.dims[layer + 1])
+                    else:
+                        y = self.critic.elu_output(B, self.device, net, layer)
+                        d.unit_stats(net, k, y, y.stride(0), B, self.critic.dims[layer + 1])
+            d.ship()
 
     def _critic_grads(self, ws, x):
         """Backward of the critic's last forward on x from ws["dy"]: the parameter gradient -> ws["gc"]."""
@@ -227,13 +263,19 @@ class ActorCriticBase(PQLActor):
                                       L.stream(self.device)))
 
     def _extra_log(self):
-        return {}
+        return self.diagnostics()
+
+    def diagnostics(self):
+        """The `diag/*` values of the last probe whose copy has reached the host ({}: algo.diag.enabled off, or none has landed yet)."""
+        return {} if self._diag is None else self._diag.diagnostics()
 
     def update_net(self, memory):
         n = int(self.cfg.algo.update_times)
         for _ in range(n):
             self.update_once(memory)
         self.per_calls += 1
+        if self._diag is not None and self._diag.due() and n > 0:
+            self._probe()
         c, a = self.closs.tolist(), self.aloss.tolist()
         k = min(n, LOSS_RING)
         return {"train/critic_loss": float(np.mean(c[:k])), "train/actor_loss": float(np.mean(a[:k])),

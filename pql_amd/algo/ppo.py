@@ -15,6 +15,7 @@ import torch
 
 from pql_amd import _lib as L
 from pql_amd.algo.critics import make_critic
+from pql_amd.algo.diag import diag_cfg
 from pql_amd.algo.learner import _AdamState, _cfg_get, apply_optimizer, make_actor
 from pql_amd.algo.pql_actor import DeviceTracker, PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
@@ -26,6 +27,7 @@ TIMEOUT_KEYS = ("TimeLimit.truncated", "time_outs")
 
 class AgentPPO:
     def __init__(self, env, cfg):
+        diag_cfg(cfg)   # algo.diag.enabled=True is refused before anything is allocated: the critic diagnostics are the Q learners'
         self.env, self.cfg = env, cfg
         self.obs_dim = env.observation_space.shape
         self.action_dim = env.action_space.shape[0]

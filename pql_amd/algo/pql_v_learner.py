@@ -22,6 +22,7 @@ import torch
 from pql_amd import _lib as L
 from pql_amd.algo.heads import CriticHead
 from pql_amd.algo.critics import check_critic_class, check_target_dtype, make_critic
+from pql_amd.algo.diag import CriticProbe, diag_cfg
 from pql_amd.algo.learner import (GATHER_FLAGS, Learner, _cfg_get, _cpu, apply_optimizer, apply_optimizer_fused, distl_loss,
                                   graph_collective_enabled, load_artifact, make_actor, pump, resident_norm)
 from pql_amd.models.mlp import (HIDDEN_DEFAULT, PackedWeights, PackedWeightsBf16, default_splits, mlp_backward_raw, mlp_forward_bf16_raw, mlp_forward_raw,
@@ -38,6 +39,7 @@ class PQLVLearner(Learner):
 
     def __init__(self, obs_dim, action_dim, cfg, process_group=None):
         check_critic_class(cfg, "PQLVLearner")
+        diag = diag_cfg(cfg)   # algo.diag: refused or accepted before anything is allocated
         # algo.per.enabled=True with algo.per.refresh=run (anything else was refused above): prioritized replay whose distribution is
         # frozen for each run of prefetched steps.  What it cannot be combined with is refused before anything is allocated.
         self._per = per_cfg(cfg.algo)
@@ -88,6 +90,9 @@ class PQLVLearner(Learner):
         self.pk_target_bf16 = self.pk_actor_bf16 = None
         self._bf16 = False
         self.set_target_dtype(_cfg_get(algo, "target_dtype", "float32"))
+        # algo.diag.enabled: the probe `update()` runs on the last trained batch (pql_amd/algo/diag.py); None = off, nothing below exists
+        self._diag = None if diag is None else CriticProbe(self.head, *diag, self.critic.layout.n_layers - 1, self.device)
+        self._diag_slot = None   # the slot of the last step taken since the last hand-off (None: no step since)
 
     def set_target_dtype(self, value):
         """algo.target_dtype: float32 (default) = the two no-gradient forwards of a step -- target policy, target twin critic --
@@ -301,6 +306,8 @@ class PQLVLearner(Learner):
         super()._drop_ahead()
 
     def _after_step(self, ws, slot):
+        if self._diag is not None:   # the tiles the weights were last trained on (a per-step or injected step: slot 0's)
+            self._diag_slot = 0 if slot is None else slot
         if self._per is None:
             return
         if slot is not None:   # a slot of the run: its |TD| waits with the run's others
@@ -405,6 +412,35 @@ class PQLVLearner(Learner):
         self._allreduce_grads(ws)
         self._step_post(ws)
 
+    def _probe(self):
+        """The diagnostics of the weights about to be handed out, on the tiles of the last step they took: one fp32 per-layer forward
+        of the critic with its full stash (the last hidden layer is never stashed by the training step's own fused forward), one of
+        the target critic on that step's xn_sa tile (its action columns hold a' in every mode), the two reductions.  Eager, on this
+        learner's stream, under its lock; writes only the probe's own buffers."""
+        d, ws, cl = self._diag, self._ws, self.critic.layout
+        B, tiles = ws["B"], ws["slots"][self._diag_slot]
+        if "diag_acts" not in ws:
+            ws["diag_acts"] = [torch.empty(cl.acts_floats(B), dtype=torch.float32, device=self.device) for _ in range(2)]
+        acts_c, acts_t = ws["diag_acts"]
+        mlp_forward_raw(cl, self.critic.arena.data, tiles["x_sa"], L.ACT_NONE, acts=acts_c, stash_all=True)
+        mlp_forward_raw(cl, self.critic_target.arena.data, tiles["xn_sa"], L.ACT_NONE, acts=acts_t, stash_all=True)
+        gamma_n = float(self.cfg.algo.gamma) ** int(self.cfg.algo.nstep)
+        d.critic_stats(output_view(cl, acts_c, B), output_view(cl, acts_t, B), cl.ld_out, tiles["rew"], tiles["done"], gamma_n, B)
+        for net in range(2):
+            for layer in range(cl.n_layers - 1):
+                off, ld = cl.act_offset(B, net, layer)
+                d.unit_stats(net, layer, acts_c[off:], ld, B, cl.dims[layer + 1])
+        d.ship()
+
+    def diagnostics(self):
+        """The `diag/*` values of the last probe whose copy has reached the host: {} when algo.diag.enabled is off or before the
+        first one lands.  Never synchronises.  They describe the weights handed out at that hand-off on the last batch they were
+        trained on (the TD residual is that batch's after its step); under data parallel this rank's own shard."""
+        if self._diag is None:
+            return {}
+        with self._lock:
+            return self._diag.diagnostics()
+
     def _step_post(self, ws):
         self._optimizer(ws)
         if self._bf16:   # the Polyak step moved the target: its bf16 copy follows in one launch, inside the captured step
@@ -503,6 +539,9 @@ class PQLVLearner(Learner):
         home = torch.cuda.current_stream(self.device)   # the caller's stream, before we switch to ours
         with self._lock, torch.cuda.device(self.device), self._on_stream():
             st = torch.cuda.current_stream(self.device)
+            if self._diag is not None and self._diag.due() and self._diag_slot is not None and self._ws is not None:
+                self._probe()   # before the actor, the ring and the statistics move: the batch is the one the weights last saw
+            self._diag_slot = None
             self.set_actor(actor, home)
             self.flush_priorities()   # before the insert: a sampled row it overwrites must end with pmax^alpha
             with H.LOCK:

@@ -946,3 +946,158 @@ extern "C" int pqlk_dpg_loss_quantile_mean(const float* theta, int64_t ld, int32
                                            const int32_t* slot_dev, int32_t ring_len, float* scratch, pqlk_stream_t stream) {
   return dpg_quantile_impl(true, theta, ld, n, b, dy, loss_out, slot_dev, ring_len, scratch, stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Critic diagnostics (pqlk_critic_stats): the law is written out in include/pqlk.h.  No gradient, no loss: PQLK_CRITIC_STATS
+// reductions over the rows of the twin heads' row values V_1, V_2 and the scalar TD target y.  Geometry of the loss kernels above --
+// k_td_mse's on the scalar head (one row per thread), k_dpg_dist's on the wider ones (one wave per row, load_row / wave_softmax /
+// wave_dot: the categorical row value is the E[z] of k_dpg_dist and k_hlgauss_ce, bit for bit) -- with PQLK_CRITIC_STATS partials per
+// block in place of one: part[j * gridDim.x + block].  Statistic j joins its operands with stat_join: + (the sums and the count),
+// fminf (j = 2) or fmaxf (j = 3, 7).  A second launch of one block folds the partials in a fixed order.  No float atomics.
+struct CriticAcc {
+  float v[PQLK_CRITIC_STATS];
+};
+__device__ __forceinline__ constexpr int stat_op(int j) { return j == 2 ? 1 : ((j == 3 || j == 7) ? 2 : 0); }
+__device__ __forceinline__ constexpr float stat_identity(int j) { return stat_op(j) == 0 ? 0.f : (stat_op(j) == 1 ? INFINITY : -INFINITY); }
+__device__ __forceinline__ float stat_join(int j, float a, float b) {
+  return stat_op(j) == 0 ? a + b : (stat_op(j) == 1 ? fminf(a, b) : fmaxf(a, b));
+}
+__device__ __forceinline__ void stat_reset(CriticAcc& a) {
+#pragma unroll
+  for (int j = 0; j < PQLK_CRITIC_STATS; ++j) a.v[j] = stat_identity(j);
+}
+__device__ __forceinline__ bool stat_finite(float x) { return fabsf(x) < INFINITY; }
+
+// one row joins the accumulator.  y_raw: the target before the categorical head's clamp (the other heads: y itself)
+__device__ __forceinline__ void stat_row(CriticAcc& a, float v1, float v2, float y, float y_raw) {
+  const float td = fmaxf(fabsf(v1 - y), fabsf(v2 - y));   // (k_td_mse's and k_hlgauss_ce's |TD|)
+  const float row[PQLK_CRITIC_STATS] = {v1, v2, fminf(v1, v2), fmaxf(v1, v2), y, (v1 + v2) * 0.5f - y, td, td, fabsf(v1 - v2),
+                                        (stat_finite(v1) && stat_finite(v2) && stat_finite(y_raw)) ? 0.f : 1.f};
+#pragma unroll
+  for (int j = 0; j < PQLK_CRITIC_STATS; ++j) a.v[j] = stat_join(j, a.v[j], row[j]);
+}
+
+__device__ __forceinline__ float stat_wave(int j, float v) {   // the xor butterfly of wave_sum under statistic j's join
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = stat_join(j, v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// the block's partials from what each wave holds (UNIFORM: every lane of a wave already holds the wave's value)
+template <bool UNIFORM>
+__device__ __forceinline__ void stat_block_store(CriticAcc& a, float* __restrict__ part) {
+  __shared__ float shw[4][PQLK_CRITIC_STATS];
+#pragma unroll
+  for (int j = 0; j < PQLK_CRITIC_STATS; ++j) {
+    if constexpr (!UNIFORM) a.v[j] = stat_wave(j, a.v[j]);
+    if ((threadIdx.x & 63) == 0) shw[threadIdx.x >> 6][j] = a.v[j];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < PQLK_CRITIC_STATS; ++j)
+      part[(int64_t)j * gridDim.x + blockIdx.x] = stat_join(j, stat_join(j, shw[0][j], shw[1][j]), stat_join(j, shw[2][j], shw[3][j]));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_critic_stats_scalar(const float* __restrict__ q, const float* __restrict__ qt, int64_t ld,
+                                                             const float* __restrict__ rew, const float* __restrict__ done,
+                                                             float gamma_n, int64_t b, float* __restrict__ part) {
+  CriticAcc a;
+  stat_reset(a);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < b; i += (int64_t)gridDim.x * 256) {
+    const float tq = fminf(qt[i * ld], qt[(b + i) * ld]);
+    const float y = rew[i] + ((1.f - done[i]) * gamma_n) * tq;   // k_td_mse's target, op for op
+    stat_row(a, q[i * ld], q[(b + i) * ld], y, y);
+  }
+  stat_block_store<false>(a, part);
+}
+
+// CAT: the categorical head (NJ = ceil(K / 64); V = E[z] of the softmax, y clamped); otherwise the quantile head (NJ = 1; V = the
+// mean of the K quantile locations, wave_sum * (1.0f / (float)K) as in dpg_quantile_rows)
+template <int NJ, bool CAT>
+__global__ __launch_bounds__(256) void k_critic_stats_rows(const float* __restrict__ q, const float* __restrict__ qt, int64_t ld, int K,
+                                                           const float* __restrict__ support, float v_min, float v_max,
+                                                           const float* __restrict__ rew, const float* __restrict__ done,
+                                                           float gamma_n, int64_t b, float* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const float inv_k = 1.0f / (float)K;
+  float zk[NJ];
+  if constexpr (CAT) load_row<NJ>(support, K, lane, zk);
+  CriticAcc a;
+  stat_reset(a);
+  for (int64_t i = wave; i < b; i += nw) {
+    float v[4];   // V_1, V_2, V'_1, V'_2
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      float x[NJ];
+      load_row<NJ>((n < 2 ? q : qt) + ((int64_t)(n & 1) * b + i) * ld, K, lane, x);
+      if constexpr (CAT) {
+        wave_softmax<NJ>(x, K, lane);
+        v[n] = wave_dot<NJ>(x, zk);
+      } else {
+        v[n] = wave_sum(x[0]) * inv_k;
+      }
+    }
+    const float y_raw = rew[i] + ((1.f - done[i]) * gamma_n) * fminf(v[2], v[3]);
+    float y = y_raw;
+    if constexpr (CAT) y = y_raw != y_raw ? y_raw : fminf(fmaxf(y_raw, v_min), v_max);   // (the clamp would turn a NaN into v_min)
+    stat_row(a, v[0], v[1], y, y_raw);
+  }
+  stat_block_store<true>(a, part);
+}
+template <int NJ>
+static constexpr auto k_critic_stats_cat = &k_critic_stats_rows<NJ, true>;   // (C51_LAUNCH names its kernel with one argument)
+
+// part[j * n + block] -> out[j]: per thread a chain over its blocks (block t, t + 256, ...), the butterfly, the four waves in order;
+// the sums (not the count) times inv_b
+__global__ __launch_bounds__(256) void k_critic_stats_fold(const float* __restrict__ part, int n, float inv_b, float* __restrict__ out) {
+  __shared__ float shw[4][PQLK_CRITIC_STATS];
+#pragma unroll
+  for (int j = 0; j < PQLK_CRITIC_STATS; ++j) {
+    float v = stat_identity(j);
+    for (int i = threadIdx.x; i < n; i += 256) v = stat_join(j, v, part[(int64_t)j * n + i]);
+    v = stat_wave(j, v);
+    if ((threadIdx.x & 63) == 0) shw[threadIdx.x >> 6][j] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < PQLK_CRITIC_STATS; ++j) {
+      const float r = stat_join(j, stat_join(j, shw[0][j], shw[1][j]), stat_join(j, shw[2][j], shw[3][j]));
+      out[j] = (stat_op(j) == 0 && j != PQLK_CRITIC_STATS - 1) ? r * inv_b : r;
+    }
+  }
+}
+
+extern "C" int64_t pqlk_critic_stats_scratch_floats(int64_t b, int32_t k) {
+  return b > 0 && k >= 1 ? (int64_t)PQLK_CRITIC_STATS * loss_blocks(b, k) : 0;
+}
+
+extern "C" int pqlk_critic_stats(const float* q, const float* qt, int64_t ld, int32_t head, int32_t k, const float* z_atoms, float v_min,
+                                 float v_max, const float* rew, const float* done, float gamma_n, int64_t b, float* out, float* scratch,
+                                 pqlk_stream_t stream) {
+  PQLK_REQUIRE(q && qt && rew && done && out && scratch, PQLK_E_NULL);
+  PQLK_REQUIRE(head == PQLK_HEAD_SCALAR || head == PQLK_HEAD_CATEGORICAL || head == PQLK_HEAD_QUANTILE, PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(head != PQLK_HEAD_CATEGORICAL || z_atoms, PQLK_E_NULL);
+  PQLK_REQUIRE(b > 0, PQLK_E_SHAPE);
+  if (head == PQLK_HEAD_SCALAR) PQLK_REQUIRE(k == 1, PQLK_E_SHAPE);
+  else PQLK_REQUIRE(k >= 2, PQLK_E_SHAPE);
+  PQLK_REQUIRE(k <= (head == PQLK_HEAD_QUANTILE ? PQLK_QR_MAX_QUANTILES : PQLK_C51_MAX_ATOMS), PQLK_E_UNSUPPORTED);
+  PQLK_REQUIRE(head != PQLK_HEAD_CATEGORICAL || v_max > v_min, PQLK_E_SHAPE);
+  PQLK_REQUIRE(ld >= 32 && ld % 32 == 0 && ld >= k, PQLK_E_ALIGN);
+  const int blocks = loss_blocks(b, k);
+  if (head == PQLK_HEAD_SCALAR)
+    hipLaunchKernelGGL(k_critic_stats_scalar, dim3(blocks), dim3(256), 0, pqlk_s(stream), q, qt, ld, rew, done, gamma_n, b, scratch);
+  else if (head == PQLK_HEAD_QUANTILE)
+    hipLaunchKernelGGL((k_critic_stats_rows<1, false>), dim3(blocks), dim3(256), 0, pqlk_s(stream), q, qt, ld, (int)k, z_atoms, v_min, v_max,
+                       rew, done, gamma_n, b, scratch);
+  else
+    C51_LAUNCH(k_critic_stats_cat, k, blocks, stream, q, qt, ld, (int)k, z_atoms, v_min, v_max, rew, done, gamma_n, b, scratch);
+  PQLK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_critic_stats_fold, dim3(1), dim3(256), 0, pqlk_s(stream), scratch, blocks, 1.0f / (float)b, out);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}

@@ -90,6 +90,10 @@ class DoubleQBroNet(DoubleQLayerNorm):
                     yield f"{pre}{norm}.weight", self.norm_param(n, l, "gamma", arena)
                     yield f"{pre}{norm}.bias", self.norm_param(n, l, "beta", arena)
 
+    def elu_layers(self):
+        """The stem and the first half of every block: a block's second half adds the skip to a bare LayerNorm, no ELU."""
+        return [l for l in range(self.n_layers - 1) if not self._closes_block(l)]
+
     # ---- the norm step, by layer -------------------------------------------------------------------------------
     def _closes_block(self, l):
         """Whether hidden layer `l` is the second half of a block: its norm has no ELU and carries the skip."""

@@ -190,6 +190,14 @@ class NormTwinQ(nn.Module):
                     x, ldx = y, z.stride(0)
         return ws
 
+    def elu_layers(self):
+        """The hidden layers whose norm step ends in an ELU (0-based): what the diagnostics' unit statistics are taken of."""
+        return list(range(self.n_layers - 1))
+
+    def elu_output(self, M, dev, n, l):
+        """The post-ELU matrix (M, ld) of hidden layer `l` of net `n` as the last forward on M rows left it."""
+        return self._workspace(M, dev)["y"][(n, l)]
+
     def _q_of(self, ws):
         return torch.stack((ws["z"][(0, self.n_layers - 1)], ws["z"][(1, self.n_layers - 1)]))
 

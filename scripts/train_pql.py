@@ -36,6 +36,7 @@ import torch  # noqa: E402
 
 import pql_amd  # noqa: E402,F401
 from pql_amd.algo.critics import check_critic_class  # noqa: E402
+from pql_amd.algo.diag import diag_cfg  # noqa: E402
 from pql_amd.algo.pql_actor import PQLActor  # noqa: E402
 from pql_amd.algo.pql_p_learner import PQLPLearner, asyn_p_learner  # noqa: E402
 from pql_amd.algo.pql_v_learner import PQLVLearner, asyn_v_learner  # noqa: E402
@@ -112,6 +113,7 @@ def main(cfg, on_finish=None):
     """`on_finish(pql_actor, v_learner, p_learner)`: called once the loop has stopped and the device is idle (tools/learn_pointmass.py
     evaluates the trained policy)."""
     check_critic_class(cfg, "scripts/train_pql.py")
+    diag_cfg(cfg)   # (a bad algo.diag is refused here, before the environment is built)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -248,7 +250,7 @@ def main(cfg, on_finish=None):
                 "train/critic_loss": critic_loss, "train/actor_loss": actor_loss,
                 "train/return": pql_actor.return_tracker.mean(), "train/episode_length": pql_actor.step_tracker.mean(),
                 "train/critic_update_times": critic_update_times, "train/actor_update_times": actor_update_times,
-                "train/global_steps": global_steps}
+                "train/global_steps": global_steps, **v_learner.diagnostics()}   # (algo.diag.enabled: the diag/* values; else nothing)
             pql_actor.add_info_tracker_log(log_info)   # info_track_keys: the windows' means under the bare key names
             logger.log(log_info, global_steps)
             if iter_t % cfg.algo.eval_freq == 0:
