@@ -121,7 +121,8 @@ def launch_tile(mode, epi, M, ncols, gz):
 
 def gemm_plan(mode, epi, tile, M, N, K, lda, ldb, ncols_store, gz, splits=1, rows_per_split=0, col0=0, ncol=0):
     """gemm.hip:751-782 with PQLK_GEMM_DMA and PQLK_GEMM_XCD unset and every operand 16-byte aligned (the arena, the stash, the
-    workspace and the tests' buffers all are; group strides are multiples of 32 floats): (grid, loop, xcd, n_base)."""
+    workspace and the tests' buffers all are; group strides are multiples of 32 floats): (grid, loop, xcd, n_base).  mode: "dW" |
+    "dX" | "FWD" -- the forward (tests/forward_hidden_cases.py) has dX's grid and tile groups and never the LDS-DMA loop (:768)."""
     ncols, n_base = (N if mode == "dW" else ncols_store), 0        # :753-754
     if epi == "DTANH_SLICE":
         n_base = col0 & ~3                                         # :756
@@ -130,7 +131,7 @@ def gemm_plan(mode, epi, tile, M, N, K, lda, ldb, ncols_store, gz, splits=1, row
     tiles, group = grid[0] * grid[1] * grid[2], (grid[0] * grid[1] if mode == "dW" else grid[0])   # :761
     xcd = "groups" if tiles % (8 * group) == 0 else "runs" if tiles >= 64 else 0                   # :764-765
     dma = False
-    if epi in ("NONE", "DELU"):                                    # :768
+    if mode != "FWD" and epi in ("NONE", "DELU"):                  # :768
         dma = M % tile == 0 and lda % 4 == 0 and ldb % 4 == 0      # :769-770
         if mode == "dX":                                           # :771
             dma = dma and ncols % tile == 0 and N % tile == 0 and K % (4 * KT) == 0 and K <= lda and ncols <= ldb

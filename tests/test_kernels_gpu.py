@@ -865,9 +865,10 @@ _SWEEP = [
 
 @pytest.mark.parametrize("dims,nets,B,fused", _SWEEP)
 def test_mlp_shape_sweep_vs_oracle(dev, ref, dims, nets, B, fused):
-    """Forward (every stashed activation) and backward (parameter + input gradients) of arbitrary MLP shapes against the
-    oracle's torch-CPU autograd: covers the fused / per-layer split, skinny / narrow / MFMA heads, interior and edge GEMM
-    tiles, ragged batches."""
+    """Forward (the output block alone, rtol = atol = 1e-5; the hidden blocks of the stash are held to their own references in
+    tests/test_forward_hidden_gpu.py) and backward (parameter + input gradients) of arbitrary MLP shapes against the oracle's
+    torch-CPU autograd: covers the fused / per-layer split, skinny / narrow / MFMA heads, interior and edge GEMM tiles, ragged
+    batches."""
     from pql_amd import _lib as L
     from pql_amd.models.mlp import ArenaLayout, PackedWeights, default_splits, mlp_forward_raw, output_view
     lay = ArenaLayout(dims, nets)
