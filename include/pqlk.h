@@ -1082,6 +1082,29 @@ int pqlk_rms_normalize(const float* x, int64_t rows, int32_t cols, const float* 
 int pqlk_action_noise(const float* act, const float* draw, const float* std_rows, float std_scalar, int64_t rows, int32_t cols,
                       float lo, float hi, float* out, pqlk_stream_t stream);
 
+/* Temporally correlated exploration noise (algo.noise.color = ar1 | pink, pql_amd/utils/noise.py `ColoredNoise`): per element
+ * (e, a) of a (rows, cols) action matrix, R = octaves unit-variance AR(1) states s_k are advanced by one step and their scaled sum
+ * takes the place of pqlk_action_noise's white draw.  Everything is fp32, every written operation one rounding (no contraction).
+ * With E = env_offset + e the row's GLOBAL env index and g = E mod groups its correlation group:
+ *   eps_k = draw[e, k * cols + a]                                                     draw is (rows, R * cols), standard normal
+ *   s_k   = fresh[e] ? eps_k : (rho[g, k] * s_k) + (coef[g, k] * eps_k)               for k = 0 ... R-1, in index order
+ *   n     = (((s_0 + s_1) + s_2) + ...) * w
+ *   out   = clamp(act + n * sigma_e, lo, hi)                                          sigma_e = std_rows[e], or std_scalar when NULL
+ * with pqlk_action_noise's expression order in the last line: with R = 1, w = 1 and rho = 0, coef = 1 `out` has its bits.
+ * rho, coef: (groups, R) tables; the caller builds coef = fp32(sqrt(1 - rho^2)) (evaluated in float64) and w = fp32(1 / sqrt(R)), so
+ * every s_k and n have stationary variance 1.  ar1: R = 1, groups = corr_groups, rho = linspace(corr_min, corr_max, groups);
+ * pink: groups = 1, rho[0] = 0, rho[k] = 1 - 2^-k.  fresh (rows) bytes: non-zero = the row's process starts over from this draw (an
+ * env's first step, and the step after one that ended an episode).  state (rows, R, cols) is updated in place.
+ * Contract: act, draw, rho, coef, fresh, state, out non-NULL (PQLK_E_NULL); rows > 0, cols > 0, 1 <= octaves <=
+ * PQLK_NOISE_MAX_OCTAVES, groups >= 1, env_offset >= 0, lo <= hi (PQLK_E_SHAPE); float-aligned pointers suffice; out may not
+ * overlap state (PQLK_E_RANGE).  Nothing outside [0, rows) x [0, cols) of out and [0, rows) x [0, R * cols) of state is written.
+ * One launch of one thread per element (grid-stride past 4096 blocks of 256), no LDS, no atomics: deterministic. */
+#define PQLK_NOISE_MAX_OCTAVES 8
+int pqlk_action_noise_colored(const float* act, const float* draw, const float* std_rows, float std_scalar, const float* rho,
+                              const float* coef, int32_t groups, int32_t octaves, int64_t env_offset, const uint8_t* fresh,
+                              float* state, int64_t rows, int32_t cols, float w, float lo, float hi, float* out,
+                              pqlk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * On-policy PPO baseline (reference pql/algo/ppo.py:79-183, pql/models/mlp.py:43-75).  All reductions in a fixed order.
  *

@@ -20,6 +20,7 @@ from pql_amd.algo.learner import _AdamState, _cfg_get, apply_optimizer, make_act
 from pql_amd.algo.pql_actor import DeviceTracker, PQLActor
 from pql_amd.models.mlp import default_splits, mlp_backward_raw, mlp_forward_raw, output_view
 from pql_amd.utils.info_track import InfoTrackers
+from pql_amd.utils.noise import noise_color
 from pql_amd.utils.torch_util import RunningMeanStd
 
 TIMEOUT_KEYS = ("TimeLimit.truncated", "time_outs")
@@ -28,6 +29,7 @@ TIMEOUT_KEYS = ("TimeLimit.truncated", "time_outs")
 class AgentPPO:
     def __init__(self, env, cfg):
         diag_cfg(cfg)   # algo.diag.enabled=True is refused before anything is allocated: the critic diagnostics are the Q learners'
+        noise_color(cfg)   # algo.noise.color != white likewise: PPO samples its own Gaussian policy
         self.env, self.cfg = env, cfg
         self.obs_dim = env.observation_space.shape
         self.action_dim = env.action_space.shape[0]

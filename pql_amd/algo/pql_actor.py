@@ -17,7 +17,7 @@ from pql_amd.replay.nstep_replay import NStepReplay
 from pql_amd.utils import handoff as H
 from pql_amd.utils.common import handle_timeout
 from pql_amd.utils.info_track import InfoTrackers
-from pql_amd.utils.noise import add_mixed_normal_noise, add_normal_noise
+from pql_amd.utils.noise import ColoredNoise, add_mixed_normal_noise, add_normal_noise, mixed_std_rows, noise_color
 from pql_amd.utils.schedule_util import ExponentialSchedule, LinearSchedule
 from pql_amd.utils.torch_util import RunningMeanStd
 
@@ -54,6 +54,9 @@ class DeviceTracker:
 
 class PQLActor:
     def __init__(self, env, cfg, env_offset=0, total_envs=None):
+        # algo.noise.color and its keys, checked before anything is allocated (None = white); the agents that sample their own
+        # policy (SAC, TQC) reach this line through ActorCriticBase and are refused a colour here
+        color = noise_color(cfg)
         self.env, self.cfg = env, cfg
         self.obs_dim = env.observation_space.shape
         self.action_dim = env.action_space.shape[0]
@@ -74,6 +77,9 @@ class PQLActor:
         self.obs_rms = RunningMeanStd(shape=self.obs_dim, device=dev) if algo.obs_norm else None
         self.n_step_buffer = NStepReplay(self.obs_dim, self.action_dim, n, algo.nstep, device=dev)
         self.noise_scheduler = self._make_scheduler(algo.noise)
+        # algo.noise.color = ar1 | pink: the AR(1) states of the exploration noise and their reset flags; under
+        # white (None) nothing of it exists: no state, no launch, no checkpoint entry
+        self._colored = None if color is None else ColoredNoise(color, n, self.action_dim, dev, env_offset=self.env_offset)
         # own device generator for the exploration draws, as the reference's actor process has its own: the default generator
         # is switched into capture mode whenever ANY hipGraph is being captured (a learner thread re-capturing its step),
         # and an eager draw from it at that moment raises
@@ -110,6 +116,8 @@ class PQLActor:
         out = {"current_returns": self.current_returns, "current_lengths": self.current_lengths}
         if self._actor is not None:
             out["actor"] = self._actor.arena.data
+        if self._colored is not None:   # a checkpoint of one colour is refused under another by the one-side-only check
+            out.update(noise_state=self._colored.state, noise_fresh=self._colored.fresh)
         return out
 
     def training_state(self):
@@ -157,6 +165,8 @@ class PQLActor:
     # ---- small API kept from the reference ---------------------------------------------------
     def reset_agent(self):
         self.obs = self.env.reset()
+        if self._colored is not None:
+            self._colored.reset()
 
     def get_noise_std(self):
         return self.cfg.algo.noise.std_max if self.noise_scheduler is None else self.noise_scheduler.val()
@@ -172,6 +182,13 @@ class PQLActor:
         if not sample:
             return act
         noise = self.cfg.algo.noise
+        if self._colored is not None:   # ar1 | pink: the same sigma (per-env rows, or the scheduled scalar) on a correlated draw
+            if noise.type == "mixed":
+                rows = mixed_std_rows(act.shape[0], act.device, noise.std_max, noise.std_min, self.env_offset, self.total_envs)
+                return self._colored.step(act, std_rows=rows, draw=draw, generator=self.gen)
+            if noise.type == "fixed":
+                return self._colored.step(act, std_scalar=self.get_noise_std(), draw=draw, generator=self.gen)
+            raise NotImplementedError(noise.type)
         if noise.type == "mixed":
             return add_mixed_normal_noise(act, std_min=noise.std_min, std_max=noise.std_max, out_bounds=[-1., 1.],
                                           env_offset=self.env_offset, total_envs=self.total_envs, generator=self.gen, draw=draw)
@@ -284,11 +301,14 @@ class PQLActor:
         env steps taken)` -- the contract of pql_actor.py:87-127.  Everything stays on the GPU and nothing synchronises
         with the host: running statistics, trackers, the n-step window and the hand-off copies are all stream work.
         `draws`: optional per-step (N, A) samples to use instead of this actor's generator (parity tests): U(0,1) when
-        `random`, N(0,1) otherwise -- the two draws the reference makes (pql_actor.py:101, noise.py:34-35)."""
+        `random`, N(0,1) otherwise -- the two draws the reference makes (pql_actor.py:101, noise.py:34-35); under algo.noise.color
+        = pink the N(0,1) samples are (N, octaves * A)."""
         algo, n = self.cfg.algo, self.cfg.num_envs
         sl = self._trajectory_slabs(timesteps)
         self._pk_stale = True   # the replica may have been stepped or loaded in place since the last call: re-pack once per call
         obs = self.obs
+        if random and self._colored is not None:   # the random actions carry no noise state: the processes start over after them
+            self._colored.reset()
         for t in range(timesteps):
             if self.obs_rms is not None:
                 self.obs_rms.update(obs)
@@ -300,6 +320,8 @@ class PQLActor:
                 action = (self.get_actions(obs, sample=True) if draws is None
                           else self.get_actions(obs, sample=True, draw=draws[t].to(self.sim_device)))
             next_obs, reward, done, info = env.step(action)
+            if self._colored is not None and not random:   # the raw done, time limits included: those rows start over next step
+                self._colored.mark(done)
             if not self._bookkeep_hip(sl, t, timesteps, obs, action, next_obs, reward, done, info):
                 self.update_tracker(reward, done, info)
                 if algo.handle_timeout:
