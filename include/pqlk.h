@@ -947,6 +947,53 @@ int pqlk_drop_ln_elu_backward(const float* dy, const float* y, const float* z, i
                               float* dbeta, float* scratch, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Whole-stack forward of the LayerNorm twin critic (pql_amd/csrc/fwd_ln.hip; algo.critic_fused_forward): ONE launch computes, for
+ * every net, x -> [Linear -> LayerNorm(eps, affine) -> ELU] x H -> Linear -> Q, what the per-layer form does in (2 H + 1) launches
+ * per net.  The descriptor is a PqlMlpDesc (dims = in, h1, ..., hH, 1); the arena is the normalised twin critics' own, read as it lies
+ * (no packed copy):
+ *   for net in 0..n_nets-1: for layer in 0..n_layers-1:
+ *       W  (out_l, pqlk_ld(in_l))  row-major, b (pqlk_ld(out_l))             -- the one-layer MLP arena of the per-layer form
+ *       gamma (pqlk_ld(out_l)), beta (pqlk_ld(out_l))                         -- behind a hidden layer only
+ * pqlk_lnmlp_offsets gives, in floats from a net's start, where [W | b], gamma and beta of `layer` lie (-1 for gamma / beta of the
+ * output layer); net n starts at n * (pqlk_lnmlp_param_floats / n_nets).
+ *
+ * The law, per net and batch row, everything fp32 and every written operation ONE rounding:
+ *   a_0 = x[:, :dims[0]] (columns [dims[0], ldx) of x are ignored)
+ *   hidden layer l = 0 .. H-1, output feature j:
+ *     acc_j = 0;  for every 8-wide group of k, s = 0, 1, ..., in the order k = 8s + 0, 4, 1, 5, 2, 6, 3, 7, two k at a time:
+ *             acc_j = acc_j + (a_l[k] W_l[j][k] + a_l[k'] W_l[j][k'])   as v_mfma_f32_32x32x2_f32 forms it (k = 8s + e, k' = 8s + 4 + e,
+ *             e = 0 .. 3); a last group of layer 0 is filled with a = 0 up to a multiple of 8 (W's pad columns are zero in the arena)
+ *     z_j   = acc_j + b_l[j]
+ *     mean, var, rstd, xhat_j, y_j = elu(xhat_j * gamma_j + beta_j): the LayerNorm + ELU law above, operation for operation, with the
+ *             row sums of its 16-byte layout (per-lane partials in register order, then the 64-lane xor butterfly): y, mean and rstd
+ *             are bit for bit what pqlk_ln_elu_forward gives on this z
+ *     a_{l+1} = y
+ *   output layer (width 1): Q = (sum_j y_j * w_j) + b, the products summed like a row sum of the last norm (same lanes, same order)
+ * A row's bits depend on neither m, its position in the batch, nor whether a stash is written.  NaN / Inf propagate.
+ *
+ * Eligible (pqlk_lnmlp_ok): 1 <= H <= PQLK_MAX_LAYERS - 1 hidden layers (n_layers = H + 1), every hidden width a multiple of 32 and
+ * <= 1024, dims[n_layers] == 1, pqlk_ld(dims[0]) <= 1248 (a 32-row fp32 image of the widest layer fits 160 KB of LDS), n_nets 1 or 2.
+ *
+ * Stash (what the per-layer backward reads; NULL: a forward-only call, nothing but Q is written): one slab of
+ * pqlk_lnmlp_stash_floats(d, m) floats; pqlk_lnmlp_stash_offset gives where `which` of hidden layer `layer` of net `net` starts and its
+ * row stride: Z / Y are (m, dims[layer+1]) matrices (ld = dims[layer+1]), MEAN / RSTD m floats (ld = 1).  Every offset is a
+ * multiple of 4.
+ *
+ * pqlk_lnmlp_forward: x (m, ldx), ldx % 32 == 0, ldx >= pqlk_ld(dims[0]); q_out (n_nets, m, 32): Q in column 0, columns 1 .. 31
+ * zero; nothing of a row >= m is touched.  Errors: PQLK_E_NULL (d, arena, x, q_out, an out-pointer of a query); PQLK_E_SHAPE for a
+ * descriptor that is not eligible, m <= 0 or m >= 2^30; PQLK_E_ALIGN for ldx or a pointer that is not 16-B aligned; PQLK_E_RANGE
+ * for a query's net, layer or `which` out of range.  The size queries return 0 for a descriptor that is not eligible. */
+enum { PQLK_LNMLP_Z = 0, PQLK_LNMLP_Y = 1, PQLK_LNMLP_MEAN = 2, PQLK_LNMLP_RSTD = 3 };
+
+int pqlk_lnmlp_ok(const PqlMlpDesc* d);                          /* 1 / 0 */
+int64_t pqlk_lnmlp_param_floats(const PqlMlpDesc* d);            /* arena size, all nets */
+int pqlk_lnmlp_offsets(const PqlMlpDesc* d, int32_t layer, int64_t* lin_off, int64_t* gamma_off, int64_t* beta_off);
+int64_t pqlk_lnmlp_stash_floats(const PqlMlpDesc* d, int64_t m); /* all nets */
+int pqlk_lnmlp_stash_offset(const PqlMlpDesc* d, int64_t m, int32_t net, int32_t layer, int32_t which, int64_t* off, int64_t* ld);
+int pqlk_lnmlp_forward(const PqlMlpDesc* d, const float* arena, const float* x, int64_t ldx, int64_t m, float eps,
+                       float* stash, float* q_out, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic vectorised environment step (the Isaac-Gym stand-in of BASELINE.json; not a reference component).
  * Counter-based: outputs depend only on (seed, env_offset + env, t, column), so shards of the env axis reproduce
  * slices of the global env.  next_obs ~ N(0,1) (N, obs_dim); reward = N(0,1) - 0.1 mean(action^2) (N);

@@ -173,6 +173,8 @@ class ActorCriticBase(PQLActor):
             return output_view(cl, ws[key], ws["B"]), cl.ld_out
         if probe and hasattr(net, "drop_state"):
             return net.forward_raw(x, drop=False), 32
+        if slot == "t" and getattr(net, "fused", None) is not None:   # algo.critic_fused_forward: nothing goes back through a target
+            return net.forward_raw(x, stash=False), 32
         return net.forward_raw(x), 32
 
     def _elu_layers(self):

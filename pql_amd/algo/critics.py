@@ -8,7 +8,8 @@ import torch
 from pql_amd.models import model_name_to_path
 from pql_amd.models.bronet import check_blocks, check_width
 from pql_amd.models.droq import check_dropout
-from pql_amd.models.mlp import check_num_atoms, check_num_quantiles
+from pql_amd.models.layernorm import FUSED_KEY, check_fused_forward
+from pql_amd.models.mlp import HIDDEN_DEFAULT, check_num_atoms, check_num_quantiles
 from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
 from pql_amd.utils.common import load_class_from_path
 
@@ -35,6 +36,11 @@ def check_huber_kappa(v):
         raise ValueError(f"algo.huber_kappa must be > 0, got {v!r}")
 
 
+def check_bool_fused(v):
+    if not isinstance(v, bool):
+        raise ValueError(f"{FUSED_KEY} must be True or False, got {v!r}")
+
+
 NO_CROSSQ = "CrossQ is the BatchNorm critic on joint batches, without a target critic; the class is for {algos}"
 TABLE = {r.name: r for r in (
     Rules("DoubleQ"),   # (and DistributionalDoubleQ, its C51 form)
@@ -46,7 +52,8 @@ TABLE = {r.name: r for r in (
           keys=(("num_quantiles", 32, check_num_quantiles, "num_quantiles"), ("huber_kappa", 1.0, check_huber_kappa, None), HIDDEN),
           structure=("num_quantiles",)),   # (algo.qr_drop, whose range depends on num_quantiles, is checked behind the keys)
     Rules("DoubleQBatchNorm", "the BatchNorm critic has no C51 head", needed_by={"CrossQ": "CrossQ needs the BatchNorm critic"}),
-    Rules("DoubleQLayerNorm", "the LayerNorm critic has no C51 head", fused=False, algos="algo=ddpg_algo / algo=sac_algo"),
+    Rules("DoubleQLayerNorm", "the LayerNorm critic has no C51 head", fused=False, algos="algo=ddpg_algo / algo=sac_algo",
+          keys=(HIDDEN, ("critic_fused_forward", False, check_bool_fused, "fused_forward"))),   # (a launch choice: no structure key)
     Rules("DoubleQDropoutLayerNorm", "the dropout LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
           algos="algo=droq_algo / algo=sac_algo / algo=ddpg_algo", keys=(("critic_dropout", 0.01, check_dropout, "dropout"), HIDDEN)),
     Rules("DoubleQBroNet", "the residual LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
@@ -113,6 +120,9 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
         raise ValueError(f"algo.hl_sigma must be > 0 (sigma of the HL-Gauss target in bin widths), got {sigma!r}")
     # ---- the class's row
     where = f"algo.cri_class={r.name}"
+    if algo.get("critic_fused_forward") and r.name != "DoubleQLayerNorm":
+        raise ValueError(f"{FUSED_KEY}=True is not supported with {where}: the one-launch forward is DoubleQLayerNorm's plain "
+                         f"Linear -> LayerNorm -> ELU stack (DroQ's mask and BroNet's skip are not in that kernel)")
     if algo.get("distl") and r.no_distl:
         raise ValueError(f"algo.distl=True is not supported with {where}: {r.no_distl}")
     if fused_learner is not None and not r.fused:
@@ -124,6 +134,9 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     for key, default, check, _ in r.keys:
         if check is not None:
             check(algo.get(key, default))
+    if algo.get("critic_fused_forward"):   # the hidden widths alone, on a 32-wide input; the constructor asks about the whole stack
+        hidden = algo.get("hidden_layers")
+        check_fused_forward([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1])
     n = int(algo.get("num_quantiles") or 0)
     if drop is not None and not (isinstance(drop, (int, float)) and not isinstance(drop, bool) and int(drop) == drop and 0 <= int(drop) <= n - 1):
         raise ValueError(f"algo.qr_drop must be null or an integer from 0 to algo.num_quantiles - 1 = {n - 1} (the atoms dropped "

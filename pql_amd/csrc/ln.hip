@@ -18,7 +18,7 @@
 // factor only where y is given).  The skip and the second addend are loaded a chunk at a time where they are used, not held as a row.
 #include <type_traits>
 
-#include "pqlk_common.h"
+#include "lnrow.h"   // LnMap, ln_load / ln_store, LN_ROW_CENTER, ln_elu: the row routine, shared with fwd_ln.hip
 
 // Philox4x32-10 (Salmon et al. 2011), ten rounds written out: counter (c0, c1, c2, c3), key (k0, k1) -> one block of four words
 __device__ __forceinline__ uint4 ln_philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
@@ -68,39 +68,8 @@ __device__ __forceinline__ bool ln_keep1(const LnDrop& d, uint32_t r, int c) {
   return ln_word(ln_philox(d.k0, d.k1, (uint32_t)c >> 2, r, d.t0, d.t1), c) >= d.thr;
 }
 
-__device__ __forceinline__ float ln_elu(float x) { return x > 0.f ? x : expm1f(x); }   // nn.ELU(alpha=1)
-
 #define LN_WAVES 4             // rows in flight per block
 #define LN_MAX_REG_COLS 1024   // widest row held in registers
-
-// register slot i of lane `lane` <-> column: VEC: chunks of V consecutive columns, chunk k of a lane at (k * 64 + lane) * V;
-// scalar: column i * 64 + lane
-template <int VPL, bool VEC>
-struct LnMap {
-  static constexpr int V = VEC ? (VPL == 2 ? 2 : 4) : 1;
-  static constexpr int NCH = VPL / V;
-  __device__ static __forceinline__ int col(int i, int lane) { return ((i / V) * 64 + lane) * V + (i % V); }
-};
-
-// p[0, cols) -> v, slots past cols = 0 (nothing past cols is read)
-template <int VPL, bool VEC>
-__device__ __forceinline__ void ln_load(const float* __restrict__ p, int cols, int lane, float (&v)[VPL]) {
-  using M = LnMap<VPL, VEC>;
-#pragma unroll
-  for (int k = 0; k < M::NCH; ++k) {
-    const int c0 = (k * 64 + lane) * M::V;
-    if (M::V == 4 && c0 + 4 <= cols) {
-      const float4 t = *reinterpret_cast<const float4*>(p + c0);
-      v[k * M::V + 0] = t.x; v[k * M::V + 1 % M::V] = t.y; v[k * M::V + 2 % M::V] = t.z; v[k * M::V + 3 % M::V] = t.w;
-    } else if (M::V == 2 && c0 + 2 <= cols) {
-      const float2 t = *reinterpret_cast<const float2*>(p + c0);
-      v[k * M::V + 0] = t.x; v[k * M::V + 1 % M::V] = t.y;
-    } else {
-#pragma unroll
-      for (int e = 0; e < M::V; ++e) v[k * M::V + e] = c0 + e < cols ? p[c0 + e] : 0.f;
-    }
-  }
-}
 
 // chunk k of a lane alone -> v: register slots [k * V, (k + 1) * V) of ln_load<VPL, VEC>.  A chunk is the whole of a one-chunk row
 // map that starts 64 * V columns per chunk further on
@@ -108,25 +77,6 @@ template <int VPL, bool VEC>
 __device__ __forceinline__ void ln_load_chunk(const float* __restrict__ p, int cols, int lane, int k, float (&v)[LnMap<VPL, VEC>::V]) {
   constexpr int V = LnMap<VPL, VEC>::V;
   ln_load<V, VEC>(p + k * 64 * V, cols - k * 64 * V, lane, v);
-}
-
-// v -> p[0, cols); nothing past cols is written
-template <int VPL, bool VEC>
-__device__ __forceinline__ void ln_store(float* __restrict__ p, int cols, int lane, const float (&v)[VPL]) {
-  using M = LnMap<VPL, VEC>;
-#pragma unroll
-  for (int k = 0; k < M::NCH; ++k) {
-    const int c0 = (k * 64 + lane) * M::V;
-    if (M::V == 4 && c0 + 4 <= cols) {
-      *reinterpret_cast<float4*>(p + c0) = make_float4(v[k * M::V + 0], v[k * M::V + 1 % M::V], v[k * M::V + 2 % M::V], v[k * M::V + 3 % M::V]);
-    } else if (M::V == 2 && c0 + 2 <= cols) {
-      *reinterpret_cast<float2*>(p + c0) = make_float2(v[k * M::V + 0], v[k * M::V + 1 % M::V]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < M::V; ++e)
-        if (c0 + e < cols) p[c0 + e] = v[k * M::V + e];
-    }
-  }
 }
 
 // bit i = keep of register slot i of row r (slots past cols: 0; they hold 0.f anyway).  VEC: a lane's chunk lies in ONE Philox block
@@ -175,19 +125,7 @@ __global__ __launch_bounds__(256) void k_ln_elu_fwd(const float* __restrict__ z,
 #pragma unroll
       for (int i = 0; i < VPL; ++i) v[i] = (km >> i) & 1u ? v[i] * d.s : 0.f;
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) s += v[i];
-    const float mu = wave_sum(s) / n;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const float d = M::col(i, lane) < cols ? v[i] - mu : 0.f;
-      v[i] = d;
-      q += d * d;
-    }
-    const float var = wave_sum(q) / n;
-    const float rs = 1.0f / sqrtf(var + eps);
+    LN_ROW_CENTER(v)
     if constexpr (!RES) {
 #pragma unroll
       for (int i = 0; i < VPL; ++i) v[i] = ln_elu(v[i] * rs * ga[i] + be[i]);

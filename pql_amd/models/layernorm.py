@@ -6,24 +6,84 @@ behaves the same in training and evaluation.  The arena, the views, the state_di
 loops are `NormTwinQ`'s (pql_amd/models/normq.py); the norm step is `pqlk_ln_elu_forward / _backward` (pql_amd/csrc/ln.hip, the law
 in include/pqlk.h).  state_dict keys are those of the equivalent `nn.Sequential`: `net_q{1,2}.net.{0,3,6,9}.{weight,bias}` for the
 Linears, `net_q{1,2}.net.{1,4,7}.{weight,bias}` for the norms; there are no buffers.
+
+`fused_forward=True` (`algo.critic_fused_forward`): the forward is ONE launch for both nets and every layer, `pqlk_lnmlp_forward`
+(pql_amd/csrc/fwd_ln.hip, the law in include/pqlk.h), reading the arena as it lies.  With `stash` it leaves z / y / mean / rstd of
+every hidden layer in one slab of which `ws["z"]`, `ws["y"]`, `ws["mean"]`, `ws["rstd"]` are views, so `backward_raw` and
+`elu_output` are what they were; without (a target forward) nothing but Q is written.  The switch is no part of a checkpoint.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import torch
 
 from pql_amd import _lib as L
+from pql_amd.models.mlp import HIDDEN_DEFAULT, _first
 from pql_amd.models.normq import NormTwinQ
 
 LN_EPS = 1e-5   # nn.LayerNorm default
 
 
+FUSED_KEY = "algo.critic_fused_forward"
+
+
+def lnmlp_desc(dims, n_nets=2) -> L.PqlMlpDesc:
+    """The descriptor of the whole stack for `pqlk_lnmlp_*` (any `dims`: an ineligible one is what `pqlk_lnmlp_ok` refuses)."""
+    d = L.PqlMlpDesc()
+    d.n_layers, d.n_nets = len(dims) - 1, n_nets
+    for i, x in enumerate(dims[:L.MAX_LAYERS + 1]):
+        d.dims[i] = int(x)
+    return d
+
+
+def check_fused_forward(dims):
+    """`algo.critic_fused_forward=True` on a stack the one-launch forward does not take: refused, never a silent per-layer run."""
+    if not L.lib.pqlk_lnmlp_ok(C.byref(lnmlp_desc(dims))):
+        raise ValueError(f"{FUSED_KEY}=True cannot run a critic of layers {list(dims)}: the one-launch forward takes 1 to "
+                         f"{L.MAX_LAYERS - 1} hidden layers whose widths are multiples of 32 and at most 1024, on an input of at most 1248 "
+                         f"padded columns; set {FUSED_KEY}=False for the per-layer forward")
+
+
 class DoubleQLayerNorm(NormTwinQ):
+    def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False):
+        if fused_forward:   # before anything is allocated
+            check_fused_forward([_first(state_dim) + int(act_dim), *(HIDDEN_DEFAULT if hidden_layers is None else hidden_layers), 1])
+        super().__init__(state_dim, act_dim, hidden_layers)
+        self.fused = lnmlp_desc(self.dims) if fused_forward else None   # None: the per-layer forward, no fused state anywhere
+        if self.fused is not None:   # the library's statement of the arena law is this module's
+            assert int(L.lib.pqlk_lnmlp_param_floats(C.byref(self.fused))) == self.total
+            for l in range(self.n_layers):
+                offs = [C.c_int64() for _ in range(3)]
+                L.check(L.lib.pqlk_lnmlp_offsets(C.byref(self.fused), l, *(C.byref(o) for o in offs)))
+                assert [o.value for o in offs] == [self.off.get((0, l, k), -1) for k in ("lin", "gamma", "beta")]
+
     def _norm_workspace(self, ws, key, M, w, f):
         ws.setdefault("mean", {})[key] = torch.zeros(M, **f)
         ws.setdefault("rstd", {})[key] = torch.zeros(M, **f)
 
     def _norm_scratch(self, ws, wmax, f):
         ws["ln_scratch"] = torch.zeros(int(L.lib.pqlk_ln_scratch_floats(wmax)), **f)
+
+    def _stash(self, ws, M, f):
+        """Fused: one slab, laid out by `pqlk_lnmlp_stash_offset`, and the (2, M, 32) Q block; z / y / mean / rstd are views of them."""
+        if self.fused is None:
+            return super()._stash(ws, M, f)
+        d, H = self.fused, self.n_layers - 1
+        slab = torch.zeros(int(L.lib.pqlk_lnmlp_stash_floats(C.byref(d), M)), **f)
+        ws.update(stash=slab, q=torch.zeros((2, M, 32), **f), mean={}, rstd={})
+
+        def view(n, l, which, *shape):
+            off, ld = C.c_int64(), C.c_int64()
+            L.check(L.lib.pqlk_lnmlp_stash_offset(C.byref(d), M, n, l, which, C.byref(off), C.byref(ld)))
+            return slab[off.value: off.value + M * ld.value].view(*shape)
+
+        for n in range(2):
+            for l in range(H):
+                w = self.dims[l + 1]
+                ws["z"][(n, l)], ws["y"][(n, l)] = view(n, l, L.LNMLP_Z, M, w), view(n, l, L.LNMLP_Y, M, w)
+                ws["mean"][(n, l)], ws["rstd"][(n, l)] = view(n, l, L.LNMLP_MEAN, M), view(n, l, L.LNMLP_RSTD, M)
+            ws["z"][(n, H)] = ws["q"][n]
 
     def _norm_forward(self, ws, n, l, z, y, M, st):
         L.check(L.lib.pqlk_ln_elu_forward(L.ptr(z), z.stride(0), M, self.dims[l + 1], L.ptr(self.norm_param(n, l, "gamma")),
@@ -36,10 +96,31 @@ class DoubleQLayerNorm(NormTwinQ):
                                            L.ptr(ws["mean"][(n, l)]), L.ptr(ws["rstd"][(n, l)]), L.ptr(self.norm_param(n, l, "gamma")),
                                            L.ptr(d), L.ptr(gg), L.ptr(gb), L.ptr(ws["ln_scratch"]) if gg is not None else None, st))
 
+    def _fused_forward(self, x_pad, stash):
+        """The one launch.  stash: into the workspace `backward_raw` reads; else Q alone, into a block that is no part of it."""
+        L.require_gpu(self.arena, "parameter arena")
+        M, dev = x_pad.shape[0], x_pad.device
+        if stash:
+            ws = self._workspace(M, dev)
+            slab, q = ws["stash"], ws["q"]
+        else:
+            q = self._ws.get(("q", M))
+            if q is None or q.device != dev:
+                q = self._ws[("q", M)] = torch.zeros((2, M, 32), dtype=torch.float32, device=dev)
+            slab = None
+        with torch.cuda.device(dev):
+            L.check(L.lib.pqlk_lnmlp_forward(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(x_pad), x_pad.stride(0), M, LN_EPS,
+                                             L.ptr(slab), L.ptr(q), L.stream(dev)))
+        return q
+
     @torch.no_grad()
-    def forward_raw(self, x_pad):
+    def forward_raw(self, x_pad, stash=True):
         """x_pad (M, ld(in)) with zero pad columns -> Q (2, M, 32) (column 0).  Keeps z / y / mean / rstd of every layer for
-        `backward_raw`."""
+        `backward_raw`.  stash=False (fused_forward only; a forward nothing goes back through, the target's): Q alone."""
+        if self.fused is not None:
+            return self._fused_forward(x_pad, stash)
+        if not stash:
+            raise ValueError(f"forward_raw(stash=False) is the one-launch forward's: it needs {FUSED_KEY}=True")
         return self._q_of(self._forward_layers(x_pad))
 
     # ---- reference surface: no train / eval difference ----------------------------------------------------------

@@ -147,13 +147,8 @@ class NormTwinQ(nn.Module):
         """d: grad of y, (M, ld) -> grad of z, in place; gg / gb: where dgamma / dbeta go (None: frozen)."""
         raise NotImplementedError
 
-    def _workspace(self, M, dev):
-        ws = self._ws.get(M)
-        if ws is not None and ws["dev"] == dev:
-            return ws
-        f = dict(dtype=torch.float32, device=dev)
-        ws = dict(dev=dev, z={}, y={}, splits=default_splits(M))
-        wmax = max(L.ld(d) for d in self.dims[1:])
+    def _stash(self, ws, M, f):
+        """What a forward keeps for `backward_raw`, put into `ws`: z of every layer, y and the norm's stash of every hidden layer."""
         for n in range(2):
             for l in range(self.n_layers):
                 w = L.ld(self.dims[l + 1])
@@ -161,6 +156,15 @@ class NormTwinQ(nn.Module):
                 if l < self.n_layers - 1:
                     ws["y"][(n, l)] = torch.zeros((M, w), **f)      # pad columns stay zero
                     self._norm_workspace(ws, (n, l), M, w, f)
+
+    def _workspace(self, M, dev):
+        ws = self._ws.get(M)
+        if ws is not None and ws["dev"] == dev:
+            return ws
+        f = dict(dtype=torch.float32, device=dev)
+        ws = dict(dev=dev, z={}, y={}, splits=default_splits(M))
+        wmax = max(L.ld(d) for d in self.dims[1:])
+        self._stash(ws, M, f)
         self._norm_scratch(ws, wmax, f)
         ws["dcur"] = [torch.zeros((M, wmax), **f) for _ in range(2)]
         ws["dx0"] = [torch.zeros((M, L.ld(self.dims[0])), **f) for _ in range(2)]
