@@ -993,6 +993,40 @@ int pqlk_lnmlp_stash_offset(const PqlMlpDesc* d, int64_t m, int32_t net, int32_t
 int pqlk_lnmlp_forward(const PqlMlpDesc* d, const float* arena, const float* x, int64_t ldx, int64_t m, float eps,
                        float* stash, float* q_out, pqlk_stream_t stream);
 
+/* Forward-only bf16-MFMA form of the same stack (pql_amd/csrc/fwd_ln_bf16.hip; algo.critic_target_dtype=bfloat16): the target
+ * critic's forward, through which nothing goes back.  Same descriptor, same arena; no stash.  The bf16 LayerNorm law, per net and
+ * batch row (RNE = round to nearest even, ties included; NaN stays NaN, overflow goes to +-inf):
+ *   1. a~_0 = bf16(x[:, :dims[0]]), RNE; columns [dims[0], ldx) of x are ignored (the k loop's last step is filled with zeros up to a
+ *      multiple of 16)
+ *   2. W~_l = bf16(W_l) for every layer, the output layer included, RNE; biases, gamma and beta stay fp32
+ *   3. hidden layer l, feature j: acc_j = sum_k a~_{l,k} W~_l[j][k] in fp32 as v_mfma_f32_32x32x16_bf16 accumulates it, 16 k per
+ *      instruction, the instructions in ascending k; z_j = acc_j + b_l[j].  z is never rounded to bf16
+ *   4. the row sums.  Feature j = 32 t + 8 g + 4 h + e (tile t, e and g the accumulator register 4 g + e, h the half) is held by wave
+ *      w = t mod 8 in its lane of half h.  A lane's partial: 0, then its features added one by one in ascending (t, g, e).  A wave's
+ *      partial: (half 0) + (half 1).  The row's sum: the partials of waves 0 .. min(dims[l+1] / 32, 8) - 1 added in wave order.
+ *      mean = sum(z) / n;  d_j = z_j - mean;  var = sum(d d) / n (the same order, each d_j * d_j one rounding);
+ *      rstd = 1 / sqrtf(var + eps)                                                  -- two-pass, everything fp32
+ *   5. y_j = elu(d_j * rstd * gamma_j + beta_j), one rounding per operation, elu(x) = x > 0 ? x : expm1f(x) (the LayerNorm + ELU law
+ *      above); a~_{l+1,j} = bf16(y_j), RNE
+ *   6. output layer (width 1): Q = sum_j a~_{H,j} W~_out[j] (every product exact in fp32), summed in the order of the row sums of 4.,
+ *      then + b_out; written as pqlk_lnmlp_forward writes it: q_out (n_nets, m, 32), Q in column 0, columns 1 .. 31 zero
+ *   7. NaN / Inf propagate within their row only; a row's bits depend on neither m, its position in the batch, nor the launch
+ * The packed copy (pqlk_lnmlp_pack_bf16: ONE launch, every net and layer; call it whenever the arena changes), uint16 bf16 patterns,
+ * pqlk_lnmlp_packed_bf16_elems() of them, net after net, in a net layer after layer:
+ *   hidden layer l (K = dims[l] padded to 16 with zeros):
+ *       packed[net][l][tile n/32][k/16][lane = 32 h + r][j] = bf16(W_l[32 tile + r][16 (k/16) + 8 h + j])
+ *   output layer: packed[net][H][k] = bf16(W_out[0][k]), k < dims[H]
+ * so the 64 16-byte fragments a wave loads for one k step of one tile are one contiguous 1 KB run.
+ * Eligible (pqlk_lnmlp_bf16_ok): what pqlk_lnmlp_ok takes, and a 32-row bf16 image of the widest layer (the input padded to 16) with
+ * its two row-sum tables inside 160 KB of LDS -- which holds for every input pqlk_lnmlp_ok admits (pqlk_ld(dims[0]) <= 1248).
+ * pqlk_lnmlp_forward_bf16: biases, gamma and beta are read from `arena`, the weights from `packed`; x, ldx, m, eps, q_out as
+ * pqlk_lnmlp_forward.  Errors as there: PQLK_E_NULL, PQLK_E_SHAPE (not eligible, m <= 0 or m >= 2^30), PQLK_E_ALIGN. */
+int pqlk_lnmlp_bf16_ok(const PqlMlpDesc* d);                     /* 1 / 0 */
+int64_t pqlk_lnmlp_packed_bf16_elems(const PqlMlpDesc* d);       /* uint16 elements, all nets; 0 when not ok */
+int pqlk_lnmlp_pack_bf16(const PqlMlpDesc* d, const float* arena, uint16_t* packed, pqlk_stream_t stream);
+int pqlk_lnmlp_forward_bf16(const PqlMlpDesc* d, const float* arena, const uint16_t* packed, const float* x, int64_t ldx, int64_t m,
+                            float eps, float* q_out, pqlk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Synthetic vectorised environment step (the Isaac-Gym stand-in of BASELINE.json; not a reference component).
  * Counter-based: outputs depend only on (seed, env_offset + env, t, column), so shards of the env axis reproduce

@@ -40,6 +40,7 @@ class ActorCriticBase(PQLActor):
         self.head = CriticHead(self.critic, algo)   # which loss entries the critic's output columns take
         if self.TARGET_CRITIC:
             self.critic_target = deepcopy(self.critic)
+            self._target_changed()
         # a Polyak-averaged copy of the actor, or (no_tgt_actor=True, every shipped config) the actor itself
         self.actor_target = self.actor if algo.no_tgt_actor else deepcopy(self.actor)
         self.aopt, self.copt = _AdamState(self.actor.arena.data), _AdamState(self.critic.arena.data)
@@ -83,6 +84,14 @@ class ActorCriticBase(PQLActor):
             self.per_calls = int(st.get("per_calls", 0))
         for name, net in self._drop_nets().items():
             net.load_drop_state(st["drop"][name])
+        self._target_changed()
+
+    def _target_changed(self):
+        """Behind every launch that changes the target critic's arena (Polyak, a hard copy, a loaded state): with
+        algo.critic_target_dtype=bfloat16 its packed bf16 copy follows, one launch on the same stream.  Nothing otherwise."""
+        tgt = getattr(self, "critic_target", None)
+        if getattr(tgt, "packed", None) is not None:
+            tgt.refresh()
 
     def _drop_nets(self):
         """The critics that carry dropout state (DoubleQDropoutLayerNorm: the critic and its target), by their training-state name."""
@@ -173,6 +182,8 @@ class ActorCriticBase(PQLActor):
             return output_view(cl, ws[key], ws["B"]), cl.ld_out
         if probe and hasattr(net, "drop_state"):
             return net.forward_raw(x, drop=False), 32
+        if probe and getattr(net, "packed", None) is not None:   # the diagnostics keep their fp32 stash forwards
+            return net.forward_raw(x), 32
         if slot == "t" and getattr(net, "fused", None) is not None:   # algo.critic_fused_forward: nothing goes back through a target
             return net.forward_raw(x, stash=False), 32
         return net.forward_raw(x), 32
@@ -263,6 +274,7 @@ class ActorCriticBase(PQLActor):
         for tgt, net in pairs:
             L.check(L.lib.pqlk_polyak(L.ptr(tgt.arena.data), L.ptr(net.arena.data), net.arena.numel(), float(self.cfg.algo.tau),
                                       L.stream(self.device)))
+        self._target_changed()
 
     def _extra_log(self):
         return self.diagnostics()

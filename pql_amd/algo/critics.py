@@ -8,7 +8,7 @@ import torch
 from pql_amd.models import model_name_to_path
 from pql_amd.models.bronet import check_blocks, check_width
 from pql_amd.models.droq import check_dropout
-from pql_amd.models.layernorm import FUSED_KEY, check_fused_forward
+from pql_amd.models.layernorm import FUSED_KEY, TARGET_DTYPE_KEY, check_fused_forward, check_target_bf16, check_target_dtype_value
 from pql_amd.models.mlp import HIDDEN_DEFAULT, check_num_atoms, check_num_quantiles
 from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
 from pql_amd.utils.common import load_class_from_path
@@ -53,7 +53,8 @@ TABLE = {r.name: r for r in (
           structure=("num_quantiles",)),   # (algo.qr_drop, whose range depends on num_quantiles, is checked behind the keys)
     Rules("DoubleQBatchNorm", "the BatchNorm critic has no C51 head", needed_by={"CrossQ": "CrossQ needs the BatchNorm critic"}),
     Rules("DoubleQLayerNorm", "the LayerNorm critic has no C51 head", fused=False, algos="algo=ddpg_algo / algo=sac_algo",
-          keys=(HIDDEN, ("critic_fused_forward", False, check_bool_fused, "fused_forward"))),   # (a launch choice: no structure key)
+          keys=(HIDDEN, ("critic_fused_forward", False, check_bool_fused, "fused_forward"),   # (launch choices: no structure keys)
+                ("critic_target_dtype", "float32", check_target_dtype_value, "target_dtype"))),
     Rules("DoubleQDropoutLayerNorm", "the dropout LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
           algos="algo=droq_algo / algo=sac_algo / algo=ddpg_algo", keys=(("critic_dropout", 0.01, check_dropout, "dropout"), HIDDEN)),
     Rules("DoubleQBroNet", "the residual LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
@@ -123,6 +124,11 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     if algo.get("critic_fused_forward") and r.name != "DoubleQLayerNorm":
         raise ValueError(f"{FUSED_KEY}=True is not supported with {where}: the one-launch forward is DoubleQLayerNorm's plain "
                          f"Linear -> LayerNorm -> ELU stack (DroQ's mask and BroNet's skip are not in that kernel)")
+    tdt = algo.get("critic_target_dtype", "float32")
+    if tdt != "float32" and r.name != "DoubleQLayerNorm":
+        check_target_dtype_value(tdt)
+        raise ValueError(f"{TARGET_DTYPE_KEY}={tdt} is not supported with {where}: the bf16 target forward is DoubleQLayerNorm's one-launch "
+                         f"forward on bf16 MFMA (algo.target_dtype is the PQL V-learner's)")
     if algo.get("distl") and r.no_distl:
         raise ValueError(f"algo.distl=True is not supported with {where}: {r.no_distl}")
     if fused_learner is not None and not r.fused:
@@ -137,6 +143,9 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     if algo.get("critic_fused_forward"):   # the hidden widths alone, on a 32-wide input; the constructor asks about the whole stack
         hidden = algo.get("hidden_layers")
         check_fused_forward([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1])
+    if tdt == "bfloat16":   # (the class is DoubleQLayerNorm, the value one of the two)
+        hidden = algo.get("hidden_layers")
+        check_target_bf16([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1], bool(algo.get("critic_fused_forward")))
     n = int(algo.get("num_quantiles") or 0)
     if drop is not None and not (isinstance(drop, (int, float)) and not isinstance(drop, bool) and int(drop) == drop and 0 <= int(drop) <= n - 1):
         raise ValueError(f"algo.qr_drop must be null or an integer from 0 to algo.num_quantiles - 1 = {n - 1} (the atoms dropped "

@@ -11,6 +11,11 @@ Linears, `net_q{1,2}.net.{1,4,7}.{weight,bias}` for the norms; there are no buff
 (pql_amd/csrc/fwd_ln.hip, the law in include/pqlk.h), reading the arena as it lies.  With `stash` it leaves z / y / mean / rstd of
 every hidden layer in one slab of which `ws["z"]`, `ws["y"]`, `ws["mean"]`, `ws["rstd"]` are views, so `backward_raw` and
 `elu_output` are what they were; without (a target forward) nothing but Q is written.  The switch is no part of a checkpoint.
+
+`target_dtype="bfloat16"` (`algo.critic_target_dtype`, with `fused_forward` only): the module also owns `packed`, the fragment-ordered
+bf16 copy of its weights as int16 (`pqlk_lnmlp_pack_bf16`; never saved), and `forward_raw(x, stash=False)` is the bf16-MFMA launch
+`pqlk_lnmlp_forward_bf16` (pql_amd/csrc/fwd_ln_bf16.hip) reading it.  `refresh()` must run behind every change of the arena; a forward
+with a stash stays the fp32 launch.
 """
 from __future__ import annotations
 
@@ -26,6 +31,8 @@ LN_EPS = 1e-5   # nn.LayerNorm default
 
 
 FUSED_KEY = "algo.critic_fused_forward"
+TARGET_DTYPE_KEY = "algo.critic_target_dtype"
+TARGET_DTYPES = ("float32", "bfloat16")
 
 
 def lnmlp_desc(dims, n_nets=2) -> L.PqlMlpDesc:
@@ -45,10 +52,29 @@ def check_fused_forward(dims):
                          f"padded columns; set {FUSED_KEY}=False for the per-layer forward")
 
 
+def check_target_dtype_value(v):
+    if v not in TARGET_DTYPES:
+        raise ValueError(f"{TARGET_DTYPE_KEY} must be float32 or bfloat16, got {v!r}")
+
+
+def check_target_bf16(dims, fused_forward):
+    """`algo.critic_target_dtype=bfloat16` where the bf16 target forward cannot run: refused, never a silent fp32 run."""
+    if not fused_forward:
+        raise ValueError(f"{TARGET_DTYPE_KEY}=bfloat16 needs {FUSED_KEY}=True: the bf16 target forward is a form of the one-launch forward "
+                         f"(the per-layer forward has no bf16 kernels)")
+    if not L.lib.pqlk_lnmlp_bf16_ok(C.byref(lnmlp_desc(dims))):
+        raise ValueError(f"{TARGET_DTYPE_KEY}=bfloat16 cannot run a critic of layers {list(dims)}: the bf16 image of 32 batch rows of its "
+                         f"widest layer does not fit the LDS; set {TARGET_DTYPE_KEY}=float32")
+
+
 class DoubleQLayerNorm(NormTwinQ):
-    def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False):
+    def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False, target_dtype="float32"):
+        dims = [_first(state_dim) + int(act_dim), *(HIDDEN_DEFAULT if hidden_layers is None else hidden_layers), 1]
+        check_target_dtype_value(target_dtype)
         if fused_forward:   # before anything is allocated
-            check_fused_forward([_first(state_dim) + int(act_dim), *(HIDDEN_DEFAULT if hidden_layers is None else hidden_layers), 1])
+            check_fused_forward(dims)
+        if target_dtype == "bfloat16":
+            check_target_bf16(dims, fused_forward)
         super().__init__(state_dim, act_dim, hidden_layers)
         self.fused = lnmlp_desc(self.dims) if fused_forward else None   # None: the per-layer forward, no fused state anywhere
         if self.fused is not None:   # the library's statement of the arena law is this module's
@@ -57,6 +83,30 @@ class DoubleQLayerNorm(NormTwinQ):
                 offs = [C.c_int64() for _ in range(3)]
                 L.check(L.lib.pqlk_lnmlp_offsets(C.byref(self.fused), l, *(C.byref(o) for o in offs)))
                 assert [o.value for o in offs] == [self.off.get((0, l, k), -1) for k in ("lin", "gamma", "beta")]
+        self._packed_fresh = False
+        if target_dtype == "bfloat16":   # a buffer, so that it moves with the module; state_dict is the views' alone: never saved
+            self.register_buffer("packed", torch.zeros(int(L.lib.pqlk_lnmlp_packed_bf16_elems(C.byref(self.fused))), dtype=torch.int16),
+                                 persistent=False)
+        else:
+            self.packed = None   # every forward is fp32, no packed state anywhere
+
+    def refresh(self):
+        """The packed bf16 copy <- the arena as it is now: one launch on the current stream, behind whatever changed the arena."""
+        if self.packed is None:
+            raise ValueError(f"refresh() is the packed bf16 copy's: it needs {TARGET_DTYPE_KEY}=bfloat16")
+        L.require_gpu(self.arena, "parameter arena")
+        dev = self.arena.device
+        with torch.cuda.device(dev):
+            L.check(L.lib.pqlk_lnmlp_pack_bf16(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(self.packed), L.stream(dev)))
+        self._packed_fresh = True
+        return self
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        out = super().load_state_dict(state_dict, strict, assign)
+        if self.packed is not None and self.arena.is_cuda:
+            self.refresh()
+        return out
 
     def _norm_workspace(self, ws, key, M, w, f):
         ws.setdefault("mean", {})[key] = torch.zeros(M, **f)
@@ -108,6 +158,14 @@ class DoubleQLayerNorm(NormTwinQ):
             if q is None or q.device != dev:
                 q = self._ws[("q", M)] = torch.zeros((2, M, 32), dtype=torch.float32, device=dev)
             slab = None
+            if self.packed is not None:   # algo.critic_target_dtype=bfloat16: the forward nothing goes back through, on bf16 MFMA
+                if not self._packed_fresh:
+                    raise RuntimeError("forward_raw(stash=False) reads the packed bf16 copy, which was never written: call refresh() "
+                                       "behind every change of the arena")
+                with torch.cuda.device(dev):
+                    L.check(L.lib.pqlk_lnmlp_forward_bf16(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(self.packed), L.ptr(x_pad),
+                                                          x_pad.stride(0), M, LN_EPS, L.ptr(q), L.stream(dev)))
+                return q
         with torch.cuda.device(dev):
             L.check(L.lib.pqlk_lnmlp_forward(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(x_pad), x_pad.stride(0), M, LN_EPS,
                                              L.ptr(slab), L.ptr(q), L.stream(dev)))
@@ -116,7 +174,8 @@ class DoubleQLayerNorm(NormTwinQ):
     @torch.no_grad()
     def forward_raw(self, x_pad, stash=True):
         """x_pad (M, ld(in)) with zero pad columns -> Q (2, M, 32) (column 0).  Keeps z / y / mean / rstd of every layer for
-        `backward_raw`.  stash=False (fused_forward only; a forward nothing goes back through, the target's): Q alone."""
+        `backward_raw`.  stash=False (fused_forward only; a forward nothing goes back through, the target's): Q alone -- with
+        target_dtype="bfloat16" by the bf16 law of include/pqlk.h, from the packed copy `refresh()` last wrote."""
         if self.fused is not None:
             return self._fused_forward(x_pad, stash)
         if not stash:

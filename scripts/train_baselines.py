@@ -71,6 +71,7 @@ def main(cfg, on_finish=None):
         load_artifact(artifact, actor=agent.actor, critic=agent.critic, obs_rms=getattr(agent, "obs_rms", None))
         if getattr(agent, "critic_target", None) is not None:
             agent.critic_target.arena.data.copy_(agent.critic.arena.data)
+            agent._target_changed()   # (algo.critic_target_dtype=bfloat16: the target's packed copy follows)
     logger = MetricLogger(cfg.logging.get("jsonl") if cfg.get("logging") else None)   # (appends: a resumed run continues the file)
     start, global_steps, start_iter, resumed_from = time.time(), 0, 0, None
     agent.reset_agent()

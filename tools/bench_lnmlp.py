@@ -9,8 +9,11 @@ ONE call, variants alternating inside every round (deltas between variants come 
             around `--launches` back-to-back forwards, median and min over the rounds.
   update    `AgentDDPG.update_once` at the same sizes with `DoubleQLayerNorm`, key off and key on: host clock around `--updates`
             updates that end in a device synchronise.
+  bf16      (`algo.critic_target_dtype=bfloat16`, pql_amd/csrc/fwd_ln_bf16.hip) in the same rounds: the bf16 no-stash forward and the
+            pack launch that follows every Polyak step as two more forward columns -- to be read against `fused_no_stash`, the fp32
+            forward they replace -- and the update with the key on as a third update column.
 
-    python tools/bench_lnmlp.py --out profiles/lnmlp_bench.json
+    python tools/bench_lnmlp.py --out profiles/lnmlp_bf16_bench.json
 """
 import argparse
 import json
@@ -42,6 +45,11 @@ def forward_variants(dev, batch):
         out[(name, "fused_stash")] = lambda fus=fus, x=x: fus.forward_raw(x)
         out[(name, "fused_no_stash")] = lambda fus=fus, x=x: fus.forward_raw(x, stash=False)
         out[(name, "per_layer")] = lambda per=per, x=x: per.forward_raw(x)
+        b16 = DoubleQLayerNorm((O,), A, hidden, fused_forward=True, target_dtype="bfloat16").to(dev)
+        b16.arena.data.copy_(per.arena.data)
+        b16.refresh()
+        out[(name, "fused_bf16_no_stash")] = lambda b16=b16, x=x: b16.forward_raw(x, stash=False)
+        out[(name, "pack_bf16")] = b16.refresh
     return out
 
 
@@ -55,7 +63,7 @@ def time_launches(fn, n):
     return e0.elapsed_time(e1) / n * 1e3   # us per call
 
 
-def make_agent(hidden, fused, batch):
+def make_agent(hidden, fused, batch, target_dtype="float32"):
     from pql_amd.algo.ddpg import AgentDDPG
     from pql_amd.envs.synthetic import create_task_env
     from pql_amd.replay.simple_replay import ReplayBuffer
@@ -63,7 +71,7 @@ def make_agent(hidden, fused, batch):
     rows = 4 * batch
     cfg = load_cfg(["algo=ddpg_algo", "task.name=AllegroHand", "num_envs=64", f"algo.batch_size={batch}", f"algo.memory_size={rows}",
                     "device=cuda:0", "sim_device=cuda:0", "algo.cri_class=DoubleQLayerNorm", f"algo.hidden_layers={hidden}",
-                    f"algo.critic_fused_forward={fused}"])
+                    f"algo.critic_fused_forward={fused}", f"algo.critic_target_dtype={target_dtype}"])
     agent = AgentDDPG(create_task_env(cfg), cfg)
     dev = agent.device
     memory = ReplayBuffer(rows, (O,), A, device=dev)
@@ -93,7 +101,8 @@ def main():
     torch.manual_seed(0)
     dev = torch.device("cuda:0")
     fv = forward_variants(dev, a.batch)
-    agents = {(name, fused): make_agent(hidden, fused, a.batch) for name, hidden in HIDDEN.items() for fused in (False, True)}
+    agents = {(name, fused, dt): make_agent(hidden, fused, a.batch, dt) for name, hidden in HIDDEN.items()
+              for fused, dt in ((False, "float32"), (True, "float32"), (True, "bfloat16"))}
     ftimes, utimes = {k: [] for k in fv}, {k: [] for k in agents}
     for r in range(a.rounds + 1):     # round 0 warms up
         for k, fn in fv.items():
@@ -110,8 +119,8 @@ def main():
         rec = dict(hidden=HIDDEN[name], what=what, us_median=round(statistics.median(ts), 2), us_min=round(min(ts), 2))
         res["forward"].append(rec)
         print(json.dumps(rec), flush=True)
-    for (name, fused), ts in utimes.items():
-        rec = dict(hidden=HIDDEN[name], critic_fused_forward=fused, us_median=round(statistics.median(ts), 1), us_min=round(min(ts), 1))
+    for (name, fused, dt), ts in utimes.items():
+        rec = dict(hidden=HIDDEN[name], critic_fused_forward=fused, critic_target_dtype=dt, us_median=round(statistics.median(ts), 1), us_min=round(min(ts), 1))
         res["update_once"].append(rec)
         print(json.dumps(rec), flush=True)
     if a.out:
