@@ -1028,6 +1028,54 @@ int pqlk_lnmlp_forward_bf16(const PqlMlpDesc* d, const float* arena, const uint1
                             float eps, float* q_out, pqlk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Whole-stack forward of the residual LayerNorm twin critic (BroNet; pql_amd/csrc/fwd_bro.hip; algo.bronet_fused_forward): ONE launch
+ * computes, for every net, the stem, K residual blocks and the output layer, what the per-layer form does in 2 (2 K + 1) + 1 launches
+ * per net.  There is no descriptor: (in_dim, width W, blocks K, n_nets) say everything.  The stack has 2 K + 2 Linears, layer 0 the
+ * stem (in_dim -> W), layers 2 k - 1 / 2 k the opening / closing Linear of block k (W -> W), layer 2 K + 1 the output (W -> 1); the
+ * arena is the normalised twin critics' own, read as it lies:
+ *   for net in 0..n_nets-1: for layer in 0..2K+1:
+ *       W  (out_l, pqlk_ld(in_l))  row-major, b (pqlk_ld(out_l))
+ *       gamma (W), beta (W)                                                    -- behind a hidden layer (0 .. 2K) only
+ * so, in floats from a net's start, layer 0 lies at 0 and is W pqlk_ld(in_dim) + 3 W long, a block layer is W W + 3 W long, the output
+ * layer W + 32.  pqlk_bro_offsets gives where [W | b], gamma and beta of `layer` lie (-1 for gamma / beta of the output layer); net n
+ * starts at n * (pqlk_bro_param_floats / n_nets).
+ *
+ * The law, per net and batch row, everything fp32 and every written operation ONE rounding:
+ *   Linear (every hidden layer): z_j = acc_j + b_j with acc_j summed as pqlk_lnmlp_forward sums it (8-wide k groups in the order
+ *           0, 4, 1, 5, 2, 6, 3, 7, two k per v_mfma_f32_32x32x2_f32; the stem's last group filled with zeros)
+ *   stem:            z0 = Linear_0(x[:, :in_dim]);   h_0 = y_0 = elu(xhat(z0) * gamma + beta)            (the LayerNorm + ELU law)
+ *   block k = 1..K:  za = Linear_{2k-1}(h_{k-1});    t   = y_{2k-1} = elu(xhat(za) * gamma + beta)       (the LayerNorm + ELU law)
+ *                    zb = Linear_{2k}(t);            u_j = xhat(zb)_j * gamma_j;  u_j = u_j + beta_j;  h_k = y_{2k} = h_{k-1} + u
+ *                                                                                   (pqlk_ln_res_forward's law with res = h_{k-1})
+ *   output:          Q = (sum_j h_K[j] * w_j) + b, the products summed like a row sum of the last norm (same lanes, same order)
+ *   mean, var, rstd, xhat: those of the LayerNorm law above with the row sums of its 16-byte layout, so y, mean and rstd of a hidden
+ *   layer are bit for bit what pqlk_ln_elu_forward / pqlk_ln_res_forward give on the same z (and res).
+ * With K = 0 the launch gives the bits of pqlk_lnmlp_forward for dims = (in_dim, W, 1).  A row's bits depend on neither m, its
+ * position in the batch, nor whether a stash is written.  NaN / Inf propagate within their row.
+ *
+ * Eligible (pqlk_bro_ok): W a multiple of 32 and <= 1024, 0 <= K <= 16 (not bound by PQLK_MAX_LAYERS), in_dim >= 1 with
+ * pqlk_ld(in_dim) <= 1248 (a 32-row fp32 image fits 160 KB of LDS), n_nets 1 or 2.
+ *
+ * Stash (what the per-layer backward reads; NULL: a forward-only call, nothing but Q is written): one slab of pqlk_bro_stash_floats
+ * floats, a net after the other; in a net Z then Y of hidden layer 0, 1, .., 2 K, (m, W) matrices with ld = W, then MEAN and RSTD of
+ * hidden layer 0, 1, .., 2 K, m floats each rounded up to 4 (ld = 1).  Y of a closing layer is h_k.  Every offset is a multiple of 4;
+ * pqlk_bro_stash_offset gives them, `which` one of PQLK_LNMLP_Z .. PQLK_LNMLP_RSTD.
+ *
+ * pqlk_bro_forward: x (m, ldx), ldx % 32 == 0, ldx >= pqlk_ld(in_dim); q_out (n_nets, m, 32): Q in column 0, columns 1 .. 31 zero;
+ * nothing of a row >= m is touched.  Errors: PQLK_E_NULL (arena, x, q_out, an out-pointer of a query); PQLK_E_SHAPE for a stack that
+ * is not eligible, m <= 0 or m >= 2^30; PQLK_E_ALIGN for ldx or a pointer that is not 16-B aligned; PQLK_E_RANGE for a query's net,
+ * layer or `which` out of range.  A refused call writes nothing.  The size queries return 0 for a stack that is not eligible. */
+int pqlk_bro_ok(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets);                  /* 1 / 0 */
+int64_t pqlk_bro_param_floats(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets);    /* arena size, all nets */
+int pqlk_bro_offsets(int32_t in_dim, int32_t width, int32_t blocks, int32_t layer, int64_t* lin_off, int64_t* gamma_off,
+                     int64_t* beta_off);
+int64_t pqlk_bro_stash_floats(int32_t width, int32_t blocks, int32_t n_nets, int64_t m);         /* all nets */
+int pqlk_bro_stash_offset(int32_t width, int32_t blocks, int32_t n_nets, int64_t m, int32_t net, int32_t layer, int32_t which,
+                          int64_t* off, int64_t* ld);
+int pqlk_bro_forward(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets, const float* arena, const float* x, int64_t ldx,
+                     int64_t m, float eps, float* stash, float* q_out, pqlk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic vectorised environment step (the Isaac-Gym stand-in of BASELINE.json; not a reference component).
  * Counter-based: outputs depend only on (seed, env_offset + env, t, column), so shards of the env axis reproduce
  * slices of the global env.  next_obs ~ N(0,1) (N, obs_dim); reward = N(0,1) - 0.1 mean(action^2) (N);

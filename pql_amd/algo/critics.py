@@ -6,7 +6,7 @@ from typing import NamedTuple
 import torch
 
 from pql_amd.models import model_name_to_path
-from pql_amd.models.bronet import check_blocks, check_width
+from pql_amd.models.bronet import BRO_FUSED_KEY, check_blocks, check_bool_bro_fused, check_bro_fused, check_width
 from pql_amd.models.droq import check_dropout
 from pql_amd.models.layernorm import FUSED_KEY, TARGET_DTYPE_KEY, check_fused_forward, check_target_bf16, check_target_dtype_value
 from pql_amd.models.mlp import HIDDEN_DEFAULT, check_num_atoms, check_num_quantiles
@@ -59,7 +59,8 @@ TABLE = {r.name: r for r in (
           algos="algo=droq_algo / algo=sac_algo / algo=ddpg_algo", keys=(("critic_dropout", 0.01, check_dropout, "dropout"), HIDDEN)),
     Rules("DoubleQBroNet", "the residual LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
           algos="algo=ddpg_algo / algo=sac_algo", structure=("critic_width", "critic_blocks"),   # (algo.hidden_layers stays the actor's)
-          keys=(("critic_width", 512, check_width, "width"), ("critic_blocks", 2, check_blocks, "blocks"))),
+          keys=(("critic_width", 512, check_width, "width"), ("critic_blocks", 2, check_blocks, "blocks"),
+                ("bronet_fused_forward", False, check_bool_bro_fused, "fused_forward"))),   # (a launch choice: no structure key)
 )}
 STRUCTURE_DEFAULTS = {f"algo.{key}": 0 for row in TABLE.values() for key in row.structure}
 
@@ -124,6 +125,9 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     if algo.get("critic_fused_forward") and r.name != "DoubleQLayerNorm":
         raise ValueError(f"{FUSED_KEY}=True is not supported with {where}: the one-launch forward is DoubleQLayerNorm's plain "
                          f"Linear -> LayerNorm -> ELU stack (DroQ's mask and BroNet's skip are not in that kernel)")
+    if algo.get("bronet_fused_forward") and r.name != "DoubleQBroNet":
+        raise ValueError(f"{BRO_FUSED_KEY}=True is not supported with {where}: the one-launch residual forward is DoubleQBroNet's stack "
+                         f"(stem, blocks with a skip, output); {FUSED_KEY} is DoubleQLayerNorm's")
     tdt = algo.get("critic_target_dtype", "float32")
     if tdt != "float32" and r.name != "DoubleQLayerNorm":
         check_target_dtype_value(tdt)
@@ -143,6 +147,8 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     if algo.get("critic_fused_forward"):   # the hidden widths alone, on a 32-wide input; the constructor asks about the whole stack
         hidden = algo.get("hidden_layers")
         check_fused_forward([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1])
+    if r.name == "DoubleQBroNet" and algo.get("bronet_fused_forward"):   # the widths alone, on a 32-wide input; the constructor asks again
+        check_bro_fused(32, algo.get("critic_width", 512), algo.get("critic_blocks", 2))
     if tdt == "bfloat16":   # (the class is DoubleQLayerNorm, the value one of the two)
         hidden = algo.get("hidden_layers")
         check_target_bf16([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1], bool(algo.get("critic_fused_forward")))

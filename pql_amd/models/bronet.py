@@ -33,15 +33,25 @@ state_dict keys are those of the torch twin (tests/bronet_cases.py `Twin`): per 
     blocks.{k}.3 / blocks.{k}.4          Linear(W, W), LayerNorm(W)
     out.{weight,bias}                    Linear(W, 1)
 There are no buffers.
+
+`fused_forward=True` (`algo.bronet_fused_forward`): the forward is ONE launch for both nets and all 2 K + 2 layers, `pqlk_bro_forward`
+(pql_amd/csrc/fwd_bro.hip, the law in include/pqlk.h), reading the arena as it lies and carrying the residual stream in registers.
+With `stash` it leaves z / y / mean / rstd of every hidden layer in one slab of which `ws["z"]`, `ws["y"]`, `ws["mean"]`, `ws["rstd"]`
+are views, so `backward_raw`, `elu_layers` and `elu_output` are what they were; without (a target forward) nothing but Q is written.
+The switch is no part of a checkpoint and not in `init_kwargs`.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import torch
 
 from pql_amd import _lib as L
 from pql_amd.models.layernorm import LN_EPS, DoubleQLayerNorm
+from pql_amd.models.mlp import _first
 
 MAX_BLOCKS = 16
+BRO_FUSED_KEY = "algo.bronet_fused_forward"
 
 
 def _whole(v):
@@ -63,13 +73,37 @@ def check_blocks(blocks):
     return int(blocks)
 
 
+def check_bool_bro_fused(v):
+    if not isinstance(v, bool):
+        raise ValueError(f"{BRO_FUSED_KEY} must be True or False, got {v!r}")
+
+
+def check_bro_fused(in_dim, width, blocks):
+    """`algo.bronet_fused_forward=True` on a stack the one-launch forward does not take: refused, never a silent per-layer run."""
+    if not L.lib.pqlk_bro_ok(int(in_dim), int(width), int(blocks), 2):
+        raise ValueError(f"{BRO_FUSED_KEY}=True cannot run a residual critic of width {width} and {blocks} blocks on {in_dim} inputs: the "
+                         f"one-launch forward takes algo.critic_width a multiple of 32 and at most 1024, 0 to {MAX_BLOCKS} blocks and an "
+                         f"input of at most 1248 padded columns; set {BRO_FUSED_KEY}=False for the per-layer forward")
+
+
 class DoubleQBroNet(DoubleQLayerNorm):
     key_prefixes = ("net_q1.", "net_q2.")
 
-    def __init__(self, state_dim, act_dim, width=512, blocks=2):
+    def __init__(self, state_dim, act_dim, width=512, blocks=2, fused_forward=False):
         self.width, self.blocks = check_width(width), check_blocks(blocks)   # before anything is allocated
+        check_bool_bro_fused(fused_forward)
+        if fused_forward:
+            check_bro_fused(_first(state_dim) + int(act_dim), self.width, self.blocks)
         super().__init__(state_dim, act_dim, hidden_layers=[self.width] * (2 * self.blocks + 1))
         self.init_kwargs = dict(state_dim=self.state_dim, act_dim=self.act_dim, width=self.width, blocks=self.blocks)
+        # None: the per-layer forward, no fused state anywhere; else what every pqlk_bro_* entry is told about the stack
+        self.fused = (self.dims[0], self.width, self.blocks, 2) if fused_forward else None
+        if self.fused is not None:   # the library's statement of the arena law is this module's
+            assert int(L.lib.pqlk_bro_param_floats(*self.fused)) == self.total
+            for l in range(self.n_layers):
+                offs = [C.c_int64() for _ in range(3)]
+                L.check(L.lib.pqlk_bro_offsets(*self.fused[:3], l, *(C.byref(o) for o in offs)))
+                assert [o.value for o in offs] == [self.off.get((0, l, k), -1) for k in ("lin", "gamma", "beta")]
 
     def layer_key(self, l):
         """(key of Linear `l`, key of the norm behind it) under a net's prefix."""
@@ -103,6 +137,51 @@ class DoubleQBroNet(DoubleQLayerNorm):
         super()._norm_workspace(ws, key, M, w, f)
         if self.blocks and "skip" not in ws:
             ws["skip"] = torch.zeros((M, w), **f)    # the running skip gradient S_k; pad columns stay zero
+
+    def _stash(self, ws, M, f):
+        """Fused: one slab, laid out by `pqlk_bro_stash_offset`, and the (2, M, 32) Q block; z / y / mean / rstd are views of them."""
+        if self.fused is None:
+            return super()._stash(ws, M, f)
+        sizes, W = self.fused[1:], self.width
+        slab = torch.zeros(int(L.lib.pqlk_bro_stash_floats(*sizes, M)), **f)
+        ws.update(stash=slab, q=torch.zeros((2, M, 32), **f), mean={}, rstd={})
+        if self.blocks:
+            ws["skip"] = torch.zeros((M, W), **f)    # (the per-layer path makes it in _norm_workspace, which is not reached here)
+
+        def view(n, l, which, *shape):
+            off, ld = C.c_int64(), C.c_int64()
+            L.check(L.lib.pqlk_bro_stash_offset(*sizes, M, n, l, which, C.byref(off), C.byref(ld)))
+            return slab[off.value: off.value + M * ld.value].view(*shape)
+
+        H = self.n_layers - 1
+        for n in range(2):
+            for l in range(H):
+                ws["z"][(n, l)], ws["y"][(n, l)] = view(n, l, L.LNMLP_Z, M, W), view(n, l, L.LNMLP_Y, M, W)
+                ws["mean"][(n, l)], ws["rstd"][(n, l)] = view(n, l, L.LNMLP_MEAN, M), view(n, l, L.LNMLP_RSTD, M)
+            ws["z"][(n, H)] = ws["q"][n]
+
+    def _fused_forward(self, x_pad, stash):
+        """The one launch.  stash: into the workspace `backward_raw` reads; else Q alone, into a block that is no part of it."""
+        L.require_gpu(self.arena, "parameter arena")
+        M, dev = x_pad.shape[0], x_pad.device
+        if stash:
+            ws = self._workspace(M, dev)
+            slab, q = ws["stash"], ws["q"]
+        else:
+            slab, q = None, self._ws.get(("q", M))
+            if q is None or q.device != dev:
+                q = self._ws[("q", M)] = torch.zeros((2, M, 32), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib.pqlk_bro_forward(*self.fused, L.ptr(self.arena.data), L.ptr(x_pad), x_pad.stride(0), M, LN_EPS, L.ptr(slab),
+                                           L.ptr(q), L.stream(dev)))
+        return q
+
+    @torch.no_grad()
+    def forward_raw(self, x_pad, stash=True):
+        """As `DoubleQLayerNorm.forward_raw`; stash=False is the one-launch forward's (fused_forward only)."""
+        if self.fused is None and not stash:
+            raise ValueError(f"forward_raw(stash=False) is the one-launch forward's: it needs {BRO_FUSED_KEY}=True")
+        return super().forward_raw(x_pad, stash)
 
     def _norm_forward(self, ws, n, l, z, y, M, st):
         if not self._closes_block(l):
