@@ -1075,6 +1075,41 @@ int pqlk_bro_stash_offset(int32_t width, int32_t blocks, int32_t n_nets, int64_t
 int pqlk_bro_forward(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets, const float* arena, const float* x, int64_t ldx,
                      int64_t m, float eps, float* stash, float* q_out, pqlk_stream_t stream);
 
+/* Forward-only bf16-MFMA form of the same residual stack (pql_amd/csrc/fwd_bro_bf16.hip; algo.critic_target_dtype=bfloat16 with
+ * algo.bronet_fused_forward): the target critic's forward, through which nothing goes back.  Same (in_dim, W, K, n_nets), same arena;
+ * no stash.  The bf16 residual law combines the bf16 LayerNorm law and the residual law above; per net and batch row (RNE as there):
+ *   1. a~_0 = bf16(x[:, :in_dim]), RNE; columns [in_dim, ldx) of x are ignored (the stem's last k step is filled with zeros up to a
+ *      multiple of 16)
+ *   2. W~_l = bf16(W_l) for all 2 K + 2 Linears, RNE; biases, gamma and beta stay fp32
+ *   3. every hidden Linear, feature j: acc_j = sum_k a~_k W~_l[j][k] in fp32 as v_mfma_f32_32x32x16_bf16 accumulates it, 16 k per
+ *      instruction, the instructions in ascending k; z_j = acc_j + b_l[j].  z is never rounded
+ *   4. row sums, mean, two-pass variance, rstd, d_j = z_j - mean: items 4 - 5 of the bf16 LayerNorm law (the same lane, wave and
+ *      register order, n = W in every hidden layer); xhat_j = d_j * rstd
+ *   5. stem:               h_0 = elu(xhat(z0) * gamma + beta);  a~ = bf16(h_0)
+ *   6. opening layer of k: t   = elu(xhat(za) * gamma + beta);  a~ = bf16(t)
+ *   7. closing layer of k: u_j = xhat(zb)_j * gamma_j;  u_j = u_j + beta_j;  h_k = h_{k-1} + u   (pqlk_ln_res_forward's operation order)
+ *      The residual stream h_k is fp32 and is NEVER rounded; only the copy that feeds the next Linear is: a~ = bf16(h_k)
+ *   8. output layer: Q = sum_j bf16(h_K)_j W~_out[j] (every product exact in fp32), summed in the order of a row sum of 4., then
+ *      + b_out; written as pqlk_bro_forward writes it: q_out (n_nets, m, 32), Q in column 0, columns 1 .. 31 zero, rows >= m untouched
+ *   9. NaN / Inf propagate within their row only; a row's bits depend on neither m, its position in the batch, nor the launch
+ * With K = 0 the law IS pqlk_lnmlp_forward_bf16's for dims = (in_dim, W, 1), bit for bit, the packed copy included.
+ * The packed copy (pqlk_bro_pack_bf16: ONE launch, every net and layer; call it whenever the arena changes), uint16 bf16 patterns,
+ * pqlk_bro_packed_bf16_elems() = n_nets (W roundup16(in_dim) + 2 K W W + W) of them, net after net, in a net layer after layer:
+ *   hidden layer l (its input width padded to 16 with zeros):
+ *       packed[net][l][tile n/32][k/16][lane = 32 h + r][j] = bf16(W_l[32 tile + r][16 (k/16) + 8 h + j])
+ *   output layer: packed[net][2 K + 1][k] = bf16(W_out[0][k]), k < W
+ * Eligible (pqlk_bro_bf16_ok): what pqlk_bro_ok takes, as long as a 32-row bf16 image [32][max(roundup16(in_dim), W) + 8] with its two
+ * row-sum tables fits 160 KB of LDS -- which narrows nothing: at pqlk_ld(in_dim) <= 1248 that is at most 82 432 B.
+ * pqlk_bro_forward_bf16: biases, gamma and beta are read from `arena`, the weights from `packed`; x, ldx, m, eps, q_out as
+ * pqlk_bro_forward.  Errors as there: PQLK_E_NULL, PQLK_E_SHAPE (not eligible, m <= 0 or m >= 2^30), PQLK_E_ALIGN.  A refused call
+ * writes nothing. */
+int pqlk_bro_bf16_ok(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets);                     /* 1 / 0 */
+int64_t pqlk_bro_packed_bf16_elems(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets);       /* uint16, all nets; 0 when not ok */
+int pqlk_bro_pack_bf16(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets, const float* arena, uint16_t* packed,
+                       pqlk_stream_t stream);
+int pqlk_bro_forward_bf16(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets, const float* arena, const uint16_t* packed,
+                          const float* x, int64_t ldx, int64_t m, float eps, float* q_out, pqlk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Synthetic vectorised environment step (the Isaac-Gym stand-in of BASELINE.json; not a reference component).
  * Counter-based: outputs depend only on (seed, env_offset + env, t, column), so shards of the env axis reproduce

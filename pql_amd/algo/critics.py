@@ -6,7 +6,7 @@ from typing import NamedTuple
 import torch
 
 from pql_amd.models import model_name_to_path
-from pql_amd.models.bronet import BRO_FUSED_KEY, check_blocks, check_bool_bro_fused, check_bro_fused, check_width
+from pql_amd.models.bronet import BRO_FUSED_KEY, check_blocks, check_bool_bro_fused, check_bro_fused, check_bro_target_bf16, check_width
 from pql_amd.models.droq import check_dropout
 from pql_amd.models.layernorm import FUSED_KEY, TARGET_DTYPE_KEY, check_fused_forward, check_target_bf16, check_target_dtype_value
 from pql_amd.models.mlp import HIDDEN_DEFAULT, check_num_atoms, check_num_quantiles
@@ -60,7 +60,8 @@ TABLE = {r.name: r for r in (
     Rules("DoubleQBroNet", "the residual LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
           algos="algo=ddpg_algo / algo=sac_algo", structure=("critic_width", "critic_blocks"),   # (algo.hidden_layers stays the actor's)
           keys=(("critic_width", 512, check_width, "width"), ("critic_blocks", 2, check_blocks, "blocks"),
-                ("bronet_fused_forward", False, check_bool_bro_fused, "fused_forward"))),   # (a launch choice: no structure key)
+                ("bronet_fused_forward", False, check_bool_bro_fused, "fused_forward"),    # (launch choices: no structure keys)
+                ("critic_target_dtype", "float32", check_target_dtype_value, "target_dtype"))),
 )}
 STRUCTURE_DEFAULTS = {f"algo.{key}": 0 for row in TABLE.values() for key in row.structure}
 
@@ -129,10 +130,10 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
         raise ValueError(f"{BRO_FUSED_KEY}=True is not supported with {where}: the one-launch residual forward is DoubleQBroNet's stack "
                          f"(stem, blocks with a skip, output); {FUSED_KEY} is DoubleQLayerNorm's")
     tdt = algo.get("critic_target_dtype", "float32")
-    if tdt != "float32" and r.name != "DoubleQLayerNorm":
+    if tdt != "float32" and r.name not in ("DoubleQLayerNorm", "DoubleQBroNet"):
         check_target_dtype_value(tdt)
-        raise ValueError(f"{TARGET_DTYPE_KEY}={tdt} is not supported with {where}: the bf16 target forward is DoubleQLayerNorm's one-launch "
-                         f"forward on bf16 MFMA (algo.target_dtype is the PQL V-learner's)")
+        raise ValueError(f"{TARGET_DTYPE_KEY}={tdt} is not supported with {where}: the bf16 target forward is the one-launch forward of "
+                         f"DoubleQLayerNorm / DoubleQBroNet on bf16 MFMA (algo.target_dtype is the PQL V-learner's)")
     if algo.get("distl") and r.no_distl:
         raise ValueError(f"algo.distl=True is not supported with {where}: {r.no_distl}")
     if fused_learner is not None and not r.fused:
@@ -149,7 +150,9 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
         check_fused_forward([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1])
     if r.name == "DoubleQBroNet" and algo.get("bronet_fused_forward"):   # the widths alone, on a 32-wide input; the constructor asks again
         check_bro_fused(32, algo.get("critic_width", 512), algo.get("critic_blocks", 2))
-    if tdt == "bfloat16":   # (the class is DoubleQLayerNorm, the value one of the two)
+    if tdt == "bfloat16" and r.name == "DoubleQBroNet":   # (the value is one of the two)
+        check_bro_target_bf16(32, algo.get("critic_width", 512), algo.get("critic_blocks", 2), bool(algo.get("bronet_fused_forward")))
+    elif tdt == "bfloat16":   # (the class is DoubleQLayerNorm)
         hidden = algo.get("hidden_layers")
         check_target_bf16([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1], bool(algo.get("critic_fused_forward")))
     n = int(algo.get("num_quantiles") or 0)

@@ -39,6 +39,11 @@ There are no buffers.
 With `stash` it leaves z / y / mean / rstd of every hidden layer in one slab of which `ws["z"]`, `ws["y"]`, `ws["mean"]`, `ws["rstd"]`
 are views, so `backward_raw`, `elu_layers` and `elu_output` are what they were; without (a target forward) nothing but Q is written.
 The switch is no part of a checkpoint and not in `init_kwargs`.
+
+`target_dtype="bfloat16"` (`algo.critic_target_dtype`, with `fused_forward` only): the module also owns `packed`, the fragment-ordered
+bf16 copy of its weights as int16 (`pqlk_bro_pack_bf16`; never saved, not in `init_kwargs`), and `forward_raw(x, stash=False)` is the
+bf16-MFMA launch `pqlk_bro_forward_bf16` (pql_amd/csrc/fwd_bro_bf16.hip): the Linears' operands are rounded, the residual stream stays
+fp32 in registers.  `refresh()` must run behind every change of the arena; a forward with a stash stays the fp32 launch.
 """
 from __future__ import annotations
 
@@ -47,7 +52,7 @@ import ctypes as C
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.models.layernorm import LN_EPS, DoubleQLayerNorm
+from pql_amd.models.layernorm import LN_EPS, TARGET_DTYPE_KEY, DoubleQLayerNorm, check_target_dtype_value
 from pql_amd.models.mlp import _first
 
 MAX_BLOCKS = 16
@@ -86,14 +91,28 @@ def check_bro_fused(in_dim, width, blocks):
                          f"input of at most 1248 padded columns; set {BRO_FUSED_KEY}=False for the per-layer forward")
 
 
+def check_bro_target_bf16(in_dim, width, blocks, fused_forward):
+    """`algo.critic_target_dtype=bfloat16` where the residual critic's bf16 target forward cannot run: refused, never a silent fp32 run."""
+    if not fused_forward:
+        raise ValueError(f"{TARGET_DTYPE_KEY}=bfloat16 needs {BRO_FUSED_KEY}=True with DoubleQBroNet: the bf16 target forward is a form of "
+                         f"the one-launch forward (the per-layer forward has no bf16 kernels)")
+    if not L.lib.pqlk_bro_bf16_ok(int(in_dim), int(width), int(blocks), 2):
+        raise ValueError(f"{TARGET_DTYPE_KEY}=bfloat16 cannot run a residual critic of width {width} and {blocks} blocks on {in_dim} inputs: "
+                         f"the bf16 target forward takes what {BRO_FUSED_KEY}=True takes (algo.critic_width a multiple of 32 and at most "
+                         f"1024); set {TARGET_DTYPE_KEY}=float32")
+
+
 class DoubleQBroNet(DoubleQLayerNorm):
     key_prefixes = ("net_q1.", "net_q2.")
 
-    def __init__(self, state_dim, act_dim, width=512, blocks=2, fused_forward=False):
+    def __init__(self, state_dim, act_dim, width=512, blocks=2, fused_forward=False, target_dtype="float32"):
         self.width, self.blocks = check_width(width), check_blocks(blocks)   # before anything is allocated
         check_bool_bro_fused(fused_forward)
+        check_target_dtype_value(target_dtype)
         if fused_forward:
             check_bro_fused(_first(state_dim) + int(act_dim), self.width, self.blocks)
+        if target_dtype == "bfloat16":
+            check_bro_target_bf16(_first(state_dim) + int(act_dim), self.width, self.blocks, fused_forward)
         super().__init__(state_dim, act_dim, hidden_layers=[self.width] * (2 * self.blocks + 1))
         self.init_kwargs = dict(state_dim=self.state_dim, act_dim=self.act_dim, width=self.width, blocks=self.blocks)
         # None: the per-layer forward, no fused state anywhere; else what every pqlk_bro_* entry is told about the stack
@@ -104,6 +123,21 @@ class DoubleQBroNet(DoubleQLayerNorm):
                 offs = [C.c_int64() for _ in range(3)]
                 L.check(L.lib.pqlk_bro_offsets(*self.fused[:3], l, *(C.byref(o) for o in offs)))
                 assert [o.value for o in offs] == [self.off.get((0, l, k), -1) for k in ("lin", "gamma", "beta")]
+        if target_dtype == "bfloat16":   # a buffer, so that it moves with the module; state_dict is the views' alone: never saved
+            del self.packed              # (the base class left None: every forward fp32)
+            self.register_buffer("packed", torch.zeros(int(L.lib.pqlk_bro_packed_bf16_elems(*self.fused)), dtype=torch.int16),
+                                 persistent=False)
+
+    def refresh(self):
+        """The packed bf16 copy <- the arena as it is now: one launch on the current stream, behind whatever changed the arena."""
+        if self.packed is None:
+            raise ValueError(f"refresh() is the packed bf16 copy's: it needs {TARGET_DTYPE_KEY}=bfloat16")
+        L.require_gpu(self.arena, "parameter arena")
+        dev = self.arena.device
+        with torch.cuda.device(dev):
+            L.check(L.lib.pqlk_bro_pack_bf16(*self.fused, L.ptr(self.arena.data), L.ptr(self.packed), L.stream(dev)))
+        self._packed_fresh = True
+        return self
 
     def layer_key(self, l):
         """(key of Linear `l`, key of the norm behind it) under a net's prefix."""
@@ -171,6 +205,14 @@ class DoubleQBroNet(DoubleQLayerNorm):
             slab, q = None, self._ws.get(("q", M))
             if q is None or q.device != dev:
                 q = self._ws[("q", M)] = torch.zeros((2, M, 32), dtype=torch.float32, device=dev)
+            if self.packed is not None:   # algo.critic_target_dtype=bfloat16: the forward nothing goes back through, on bf16 MFMA
+                if not self._packed_fresh:
+                    raise RuntimeError("forward_raw(stash=False) reads the packed bf16 copy, which was never written: call refresh() "
+                                       "behind every change of the arena")
+                with torch.cuda.device(dev):
+                    L.check(L.lib.pqlk_bro_forward_bf16(*self.fused, L.ptr(self.arena.data), L.ptr(self.packed), L.ptr(x_pad),
+                                                        x_pad.stride(0), M, LN_EPS, L.ptr(q), L.stream(dev)))
+                return q
         with torch.cuda.device(dev):
             L.check(L.lib.pqlk_bro_forward(*self.fused, L.ptr(self.arena.data), L.ptr(x_pad), x_pad.stride(0), M, LN_EPS, L.ptr(slab),
                                            L.ptr(q), L.stream(dev)))

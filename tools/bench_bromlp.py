@@ -8,10 +8,13 @@ same minutes):
   forward   at (obs 88, act 16), B = 8192, (critic_width, critic_blocks) = (512, 2) and (128, 1), on the same input and the same
             arena: the fused launch with stash, the fused launch without, and the per-layer forward (22 / 14 launches and a
             torch.stack); HIP events around `--launches` back-to-back forwards, median and min over the rounds.
-  update    `AgentDDPG.update_once` at the same sizes with `DoubleQBroNet`, key off and key on: host clock around `--updates` updates
-            that end in a device synchronise.
+  bf16      (`algo.critic_target_dtype=bfloat16`, pql_amd/csrc/fwd_bro_bf16.hip) in the same rounds, on the same input and arena: the
+            bf16 no-stash forward, the pack launch alone, and the forward with the pack launch in front of it (what a target forward
+            costs per update); compare them with fused_no_stash of the same call.
+  update    `AgentDDPG.update_once` at the same sizes with `DoubleQBroNet`: the per-layer forward, `algo.bronet_fused_forward`, and the
+            latter with `algo.critic_target_dtype=bfloat16`: host clock around `--updates` updates that end in a device synchronise.
 
-    python tools/bench_bromlp.py --out profiles/bro_fused_bench.json
+    python tools/bench_bromlp.py --out profiles/bro_bf16_bench.json
 """
 import argparse
 import json
@@ -44,10 +47,16 @@ def forward_variants(dev, batch):
         out[(name, "fused_stash")] = lambda fus=fus, x=x: fus.forward_raw(x)
         out[(name, "fused_no_stash")] = lambda fus=fus, x=x: fus.forward_raw(x, stash=False)
         out[(name, "per_layer")] = lambda per=per, x=x: per.forward_raw(x)
+        b16 = DoubleQBroNet((O,), A, w, k, fused_forward=True, target_dtype="bfloat16").to(dev)
+        b16.arena.data.copy_(per.arena.data)
+        b16.refresh()
+        out[(name, "bf16_no_stash")] = lambda b16=b16, x=x: b16.forward_raw(x, stash=False)
+        out[(name, "pack_bf16")] = lambda b16=b16: b16.refresh()
+        out[(name, "bf16_no_stash_plus_pack")] = lambda b16=b16, x=x: b16.refresh().forward_raw(x, stash=False)
     return out
 
 
-def make_agent(width, blocks, fused, batch):
+def make_agent(width, blocks, fused, batch, target_dtype="float32"):
     from pql_amd.algo.ddpg import AgentDDPG
     from pql_amd.envs.synthetic import create_task_env
     from pql_amd.replay.simple_replay import ReplayBuffer
@@ -55,7 +64,7 @@ def make_agent(width, blocks, fused, batch):
     rows = 4 * batch
     cfg = load_cfg(["algo=ddpg_algo", "task.name=AllegroHand", "num_envs=64", f"algo.batch_size={batch}", f"algo.memory_size={rows}",
                     "device=cuda:0", "sim_device=cuda:0", "algo.cri_class=DoubleQBroNet", f"algo.critic_width={width}",
-                    f"algo.critic_blocks={blocks}", f"algo.bronet_fused_forward={fused}"])
+                    f"algo.critic_blocks={blocks}", f"algo.bronet_fused_forward={fused}", f"algo.critic_target_dtype={target_dtype}"])
     agent = AgentDDPG(create_task_env(cfg), cfg)
     dev = agent.device
     memory = ReplayBuffer(rows, (O,), A, device=dev)
@@ -76,7 +85,8 @@ def main():
     torch.manual_seed(0)
     dev = torch.device("cuda:0")
     fv = forward_variants(dev, a.batch)
-    agents = {(name, fused): make_agent(w, k, fused, a.batch) for name, (w, k) in SHAPES.items() for fused in (False, True)}
+    agents = {(name, fused, dt): make_agent(w, k, fused, a.batch, dt) for name, (w, k) in SHAPES.items()
+              for fused, dt in ((False, "float32"), (True, "float32"), (True, "bfloat16"))}
     ftimes, utimes = {k: [] for k in fv}, {k: [] for k in agents}
     for r in range(a.rounds + 1):     # round 0 warms up
         for k, fn in fv.items():
@@ -94,9 +104,9 @@ def main():
         rec = dict(critic_width=w, critic_blocks=k, what=what, us_median=round(statistics.median(ts), 2), us_min=round(min(ts), 2))
         res["forward"].append(rec)
         print(json.dumps(rec), flush=True)
-    for (name, fused), ts in utimes.items():
+    for (name, fused, dt), ts in utimes.items():
         w, k = SHAPES[name]
-        rec = dict(critic_width=w, critic_blocks=k, bronet_fused_forward=fused, us_median=round(statistics.median(ts), 1), us_min=round(min(ts), 1))
+        rec = dict(critic_width=w, critic_blocks=k, bronet_fused_forward=fused, critic_target_dtype=dt, us_median=round(statistics.median(ts), 1), us_min=round(min(ts), 1))
         res["update_once"].append(rec)
         print(json.dumps(rec), flush=True)
     if a.out:
