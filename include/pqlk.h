@@ -1027,6 +1027,41 @@ int pqlk_lnmlp_pack_bf16(const PqlMlpDesc* d, const float* arena, uint16_t* pack
 int pqlk_lnmlp_forward_bf16(const PqlMlpDesc* d, const float* arena, const uint16_t* packed, const float* x, int64_t ldx, int64_t m,
                             float eps, float* q_out, pqlk_stream_t stream);
 
+/* Dropout forms of the two whole-stack forwards: the DroQ critic (`Linear -> Dropout(p) -> LayerNorm -> ELU` blocks;
+ * pql_amd/models/droq.py with algo.droq_fused_forward) in ONE launch, the masks regenerated where the values already sit.  Descriptor,
+ * arena, eligibility (pqlk_lnmlp_ok / pqlk_lnmlp_bf16_ok), stash layout and packed copy are those of pqlk_lnmlp_forward /
+ * pqlk_lnmlp_forward_bf16: there is no new layout and no new pack.
+ *
+ * The mask of hidden layer l of net n is the mask law's (above, "The mask law") with
+ *   tag  = tag_base | (n << 4) | l          (the low 5 bits of tag_base must be clear; at most 2 nets and 16 hidden layers)
+ *   r    = the row's index in the whole batch, 0 <= r < m (never its index inside a block of the launch)
+ *   c    = the feature's index in the layer, 0 <= c < dims[l + 1]
+ * and thr, s and keep(r, c) exactly those of pqlk_drop_ln_elu_forward for the same (p, seed, tag).
+ *
+ * pqlk_lnmlp_drop_forward, per net and batch row: the law of pqlk_lnmlp_forward with one operation more per hidden layer,
+ *     z_j   = acc_j + b_l[j]                                   (as there; with a stash, THIS z is what Z holds: the pre-dropout z)
+ *     u_j   = keep(r, j) ? z_j * s : 0.0f                      (one fp32 rounding)
+ *     mean, var, rstd, xhat_j, y_j = elu(xhat_j * gamma_j + beta_j): the LayerNorm + ELU law applied to u, with the row sums of its
+ *             16-byte layout: y, mean and rstd (those of u) are bit for bit what pqlk_drop_ln_elu_forward gives on the stashed z with
+ *             the tag of (n, l), so pqlk_drop_ln_elu_backward with that tag is the backward of every hidden layer
+ *     a_{l+1} = y;  the output layer as there.
+ *   In the 16-byte layout a lane's chunk of four consecutive columns is one Philox block (half a block at dims[l + 1] <= 128).
+ *
+ * pqlk_lnmlp_drop_forward_bf16, per net and batch row: the bf16 LayerNorm law with one operation more behind item 3,
+ *     3'. u_j = keep(r, j) ? z_j * s : 0.0f                    (one fp32 rounding; never rounded to bf16)
+ *   and items 4 - 6 applied to u instead of z.  z and u never leave the accumulator registers: registers 4 g .. 4 g + 3 of a lane are
+ *   features 32 t + 8 g + 4 h + (0 .. 3) of one row, which is one Philox block per four registers.
+ *
+ * Both: p = 0 gives the bits of the plain entry (thr = 0 and s = 1.0f: u = z bit for bit).  A row's bits depend on (seed, tag_base,
+ * its global row index r) and not on m or STASH (whether a stash is written); rows past m change nothing of a row below m.  NaN / Inf
+ * propagate within their row only (a dropped NaN is 0.0f).
+ * Errors: those of the plain entries, and PQLK_E_SHAPE, checked before any launch, for p < 0, p >= 1 or a non-finite p; any of the
+ * low 5 bits of tag_base set; n_nets > 2; more than 16 hidden layers. */
+int pqlk_lnmlp_drop_forward(const PqlMlpDesc* d, const float* arena, const float* x, int64_t ldx, int64_t m, float eps, float p,
+                            uint64_t seed, uint64_t tag_base, float* stash, float* q_out, pqlk_stream_t stream);
+int pqlk_lnmlp_drop_forward_bf16(const PqlMlpDesc* d, const float* arena, const uint16_t* packed, const float* x, int64_t ldx, int64_t m,
+                                 float eps, float p, uint64_t seed, uint64_t tag_base, float* q_out, pqlk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Whole-stack forward of the residual LayerNorm twin critic (BroNet; pql_amd/csrc/fwd_bro.hip; algo.bronet_fused_forward): ONE launch
  * computes, for every net, the stem, K residual blocks and the output layer, what the per-layer form does in 2 (2 K + 1) + 1 launches

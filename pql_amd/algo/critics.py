@@ -7,7 +7,7 @@ import torch
 
 from pql_amd.models import model_name_to_path
 from pql_amd.models.bronet import BRO_FUSED_KEY, check_blocks, check_bool_bro_fused, check_bro_fused, check_bro_target_bf16, check_width
-from pql_amd.models.droq import check_dropout
+from pql_amd.models.droq import DROQ_FUSED_KEY, check_dropout
 from pql_amd.models.layernorm import FUSED_KEY, TARGET_DTYPE_KEY, check_fused_forward, check_target_bf16, check_target_dtype_value
 from pql_amd.models.mlp import HIDDEN_DEFAULT, check_num_atoms, check_num_quantiles
 from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
@@ -41,6 +41,11 @@ def check_bool_fused(v):
         raise ValueError(f"{FUSED_KEY} must be True or False, got {v!r}")
 
 
+def check_bool_droq_fused(v):
+    if not isinstance(v, bool):
+        raise ValueError(f"{DROQ_FUSED_KEY} must be True or False, got {v!r}")
+
+
 NO_CROSSQ = "CrossQ is the BatchNorm critic on joint batches, without a target critic; the class is for {algos}"
 TABLE = {r.name: r for r in (
     Rules("DoubleQ"),   # (and DistributionalDoubleQ, its C51 form)
@@ -56,7 +61,10 @@ TABLE = {r.name: r for r in (
           keys=(HIDDEN, ("critic_fused_forward", False, check_bool_fused, "fused_forward"),   # (launch choices: no structure keys)
                 ("critic_target_dtype", "float32", check_target_dtype_value, "target_dtype"))),
     Rules("DoubleQDropoutLayerNorm", "the dropout LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
-          algos="algo=droq_algo / algo=sac_algo / algo=ddpg_algo", keys=(("critic_dropout", 0.01, check_dropout, "dropout"), HIDDEN)),
+          algos="algo=droq_algo / algo=sac_algo / algo=ddpg_algo",
+          keys=(("critic_dropout", 0.01, check_dropout, "dropout"), HIDDEN,
+                ("droq_fused_forward", False, check_bool_droq_fused, "fused_forward"),     # (launch choices: no structure keys)
+                ("critic_target_dtype", "float32", check_target_dtype_value, "target_dtype"))),
     Rules("DoubleQBroNet", "the residual LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
           algos="algo=ddpg_algo / algo=sac_algo", structure=("critic_width", "critic_blocks"),   # (algo.hidden_layers stays the actor's)
           keys=(("critic_width", 512, check_width, "width"), ("critic_blocks", 2, check_blocks, "blocks"),
@@ -129,11 +137,16 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     if algo.get("bronet_fused_forward") and r.name != "DoubleQBroNet":
         raise ValueError(f"{BRO_FUSED_KEY}=True is not supported with {where}: the one-launch residual forward is DoubleQBroNet's stack "
                          f"(stem, blocks with a skip, output); {FUSED_KEY} is DoubleQLayerNorm's")
+    droq_fused = algo.get("droq_fused_forward", False)
+    check_bool_droq_fused(droq_fused)
+    if droq_fused and r.name != "DoubleQDropoutLayerNorm":
+        raise ValueError(f"{DROQ_FUSED_KEY}=True is not supported with {where}: the one-launch dropout forward is DoubleQDropoutLayerNorm's "
+                         f"stack, the mask regenerated inside the launch; {FUSED_KEY} is DoubleQLayerNorm's and {BRO_FUSED_KEY} DoubleQBroNet's")
     tdt = algo.get("critic_target_dtype", "float32")
-    if tdt != "float32" and r.name not in ("DoubleQLayerNorm", "DoubleQBroNet"):
+    if tdt != "float32" and r.name not in ("DoubleQLayerNorm", "DoubleQBroNet", "DoubleQDropoutLayerNorm"):
         check_target_dtype_value(tdt)
         raise ValueError(f"{TARGET_DTYPE_KEY}={tdt} is not supported with {where}: the bf16 target forward is the one-launch forward of "
-                         f"DoubleQLayerNorm / DoubleQBroNet on bf16 MFMA (algo.target_dtype is the PQL V-learner's)")
+                         f"DoubleQLayerNorm / DoubleQBroNet / DoubleQDropoutLayerNorm on bf16 MFMA (algo.target_dtype is the PQL V-learner's)")
     if algo.get("distl") and r.no_distl:
         raise ValueError(f"algo.distl=True is not supported with {where}: {r.no_distl}")
     if fused_learner is not None and not r.fused:
@@ -148,13 +161,17 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
     if algo.get("critic_fused_forward"):   # the hidden widths alone, on a 32-wide input; the constructor asks about the whole stack
         hidden = algo.get("hidden_layers")
         check_fused_forward([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1])
+    if droq_fused:   # (the class is DoubleQDropoutLayerNorm) the same eligibility, asked under this class's key
+        hidden = algo.get("hidden_layers")
+        check_fused_forward([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1], DROQ_FUSED_KEY)
     if r.name == "DoubleQBroNet" and algo.get("bronet_fused_forward"):   # the widths alone, on a 32-wide input; the constructor asks again
         check_bro_fused(32, algo.get("critic_width", 512), algo.get("critic_blocks", 2))
     if tdt == "bfloat16" and r.name == "DoubleQBroNet":   # (the value is one of the two)
         check_bro_target_bf16(32, algo.get("critic_width", 512), algo.get("critic_blocks", 2), bool(algo.get("bronet_fused_forward")))
-    elif tdt == "bfloat16":   # (the class is DoubleQLayerNorm)
+    elif tdt == "bfloat16":   # (the class is DoubleQLayerNorm, or DoubleQDropoutLayerNorm with its own switch)
         hidden = algo.get("hidden_layers")
-        check_target_bf16([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1], bool(algo.get("critic_fused_forward")))
+        fused, key = (droq_fused, DROQ_FUSED_KEY) if r.name == "DoubleQDropoutLayerNorm" else (algo.get("critic_fused_forward"), FUSED_KEY)
+        check_target_bf16([32, *(HIDDEN_DEFAULT if hidden is None else hidden), 1], bool(fused), key)
     n = int(algo.get("num_quantiles") or 0)
     if drop is not None and not (isinstance(drop, (int, float)) and not isinstance(drop, bool) and int(drop) == drop and 0 <= int(drop) <= n - 1):
         raise ValueError(f"algo.qr_drop must be null or an integer from 0 to algo.num_quantiles - 1 = {n - 1} (the atoms dropped "

@@ -21,7 +21,15 @@
 // (width 1) rides on the last epilogue: the wave that normalised a row still holds its y in registers, multiplies it with the output
 // weights in register order and sums with the same butterfly, so nothing but Q leaves the block when STASH is off.
 // No atomics, no scratch; a row's bits depend on neither m, its position in the batch, nor STASH.
+//
+// Dropout (DoubleQDropoutLayerNorm with algo.droq_fused_forward; pqlk_lnmlp_drop_forward): lm_norm and the kernel end in a parameter
+// pack `D... dr` that is either empty (the plain kernel: the instructions and the bits of pqlk_lnmlp_forward are what they were) or
+// one LnDrop.  With it the wave that holds a row under LnMap<VPL, true> regenerates the row's keep bits -- one Philox4x32-10 block per
+// chunk of four columns, ln.hip's own ln_keep_bits -- and normalises u = keep ? z * s : 0; the row index of the mask is the row's
+// index in the whole batch, the tag tag_base | (net << 4) | layer.  The stashed z stays the pre-dropout z, so the per-layer dropout
+// backward, which regenerates the masks itself, reads the stash as it reads the per-layer forward's.
 #include "lnrow.h"
+#include "lndrop.h"
 
 constexpr int LM_NW = 8;                 // waves per block
 constexpr int LM_LDS_MAX = 160 * 1024;
@@ -105,10 +113,10 @@ struct LmStash {
 
 // LayerNorm + ELU over the block's rows of the image, a wave per row: z -> y in place.  wout (the last hidden layer only): the output
 // layer's weights; y is then not written back but multiplied out to Q, column 0 of the row's 32 floats of qout (pad columns zero).
-template <int VPL, bool STASH>
+template <int VPL, bool STASH, typename... D>
 __device__ __forceinline__ void lm_norm(float* img, int ld, int cols, int rows, long long row0, int m, const float* __restrict__ gamma,
                                         const float* __restrict__ beta, float eps, const LmStash& st, const float* __restrict__ wout,
-                                        float bout, float* __restrict__ qout, int wave, int lane) {
+                                        float bout, float* __restrict__ qout, int wave, int lane, D... dr) {
   using M = LnMap<VPL, true>;
   float ga[VPL], be[VPL], wo[VPL];
   ln_load<VPL, true>(gamma, cols, lane, ga);
@@ -121,6 +129,12 @@ __device__ __forceinline__ void lm_norm(float* img, int ld, int cols, int rows, 
     float v[VPL];
     ln_load<VPL, true>(img + rr * ld, cols, lane, v);
     if constexpr (STASH) ln_store<VPL, true>(st.z + row * cols, cols, lane, v);
+    if constexpr (ln_has<LnDrop, D...>) {   // u = keep ? z * s : 0, the mask of the row's place in the whole batch
+      const LnDrop d = ln_drop_of(dr...);
+      const unsigned km = ln_keep_bits<VPL, true>(d, (uint32_t)row, cols, lane);
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) v[i] = (km >> i) & 1u ? v[i] * d.s : 0.f;
+    }
     LN_ROW_CENTER(v)
 #pragma unroll
     for (int i = 0; i < VPL; ++i) v[i] = ln_elu(v[i] * rs * ga[i] + be[i]);
@@ -140,8 +154,8 @@ __device__ __forceinline__ void lm_norm(float* img, int ld, int cols, int rows, 
   }
 }
 
-template <int R, bool STASH>
-__global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_fwd(LnMlpP p) {
+template <int R, bool STASH, typename... D>
+__global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_fwd(LnMlpP p, D... dr) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int net = blockIdx.y, H = p.n_layers - 1, ld = p.ld;
   const long long row0 = (long long)blockIdx.x * (32 * R);
@@ -182,10 +196,13 @@ __global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_fwd(LnMlpP p) {
     const float *ga = prm + p.g_off[l], *be = prm + p.be_off[l];
     LmStash st = {};
     if constexpr (STASH) st = LmStash{sb + p.z_off[l], sb + p.y_off[l], sb + p.mean_off[l], sb + p.rstd_off[l]};
-    if (N <= 128) lm_norm<2, STASH>(img, ld, N, 32 * R, row0, p.m, ga, be, p.eps, st, wout, bout, q, wave, lane);
-    else if (N <= 256) lm_norm<4, STASH>(img, ld, N, 32 * R, row0, p.m, ga, be, p.eps, st, wout, bout, q, wave, lane);
-    else if (R == 2 || N <= 512) lm_norm<8, STASH>(img, ld, N, 32 * R, row0, p.m, ga, be, p.eps, st, wout, bout, q, wave, lane);
-    else if constexpr (R == 1) lm_norm<16, STASH>(img, ld, N, 32 * R, row0, p.m, ga, be, p.eps, st, wout, bout, q, wave, lane);
+    // (dr: empty, or the launch's LnDrop, which gets the tag of this (net, layer))
+#define LM_NORM(VPL) lm_norm<VPL, STASH>(img, ld, N, 32 * R, row0, p.m, ga, be, p.eps, st, wout, bout, q, wave, lane, ln_drop_at(dr, net, l)...)
+    if (N <= 128) LM_NORM(2);
+    else if (N <= 256) LM_NORM(4);
+    else if (R == 2 || N <= 512) LM_NORM(8);
+    else if constexpr (R == 1) LM_NORM(16);
+#undef LM_NORM
     if (!last) __syncthreads();   // y is complete: the next layer reads it
   }
 }
@@ -289,13 +306,13 @@ extern "C" int pqlk_lnmlp_stash_offset(const PqlMlpDesc* desc, int64_t m, int32_
   return PQLK_OK;
 }
 
-extern "C" int pqlk_lnmlp_forward(const PqlMlpDesc* desc, const float* arena, const float* x, int64_t ldx, int64_t m, float eps,
-                                  float* stash, float* q_out, pqlk_stream_t stream) {
-  PQLK_REQUIRE(desc && arena && x && q_out, PQLK_E_NULL);
+// the one dispatch of the plain entry (an empty pack) and the dropout entry (one LnDrop, its tag the launch's tag_base)
+template <typename... D>
+static int lm_forward(const PqlMlpDesc* desc, const float* arena, const float* x, int64_t ldx, int64_t m, float eps, float* stash,
+                      float* q_out, pqlk_stream_t stream, D... dr) {
   LmLayout lay;
   PQLK_REQUIRE(lm_layout(desc, &lay), PQLK_E_SHAPE);
   const LmLayout* d = &lay;
-  PQLK_REQUIRE(m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
   PQLK_REQUIRE(ldx % 32 == 0 && ldx >= pqlk_ld(d->dims[0]), PQLK_E_ALIGN);
   PQLK_REQUIRE(pqlk_aligned16(arena) && pqlk_aligned16(x) && pqlk_aligned16(stash) && pqlk_aligned16(q_out), PQLK_E_ALIGN);
   const int L = d->n_layers;
@@ -317,10 +334,10 @@ extern "C" int pqlk_lnmlp_forward(const PqlMlpDesc* desc, const float* arena, co
     lm_stash_at(d, m, l, PQLK_LNMLP_RSTD, &p.rstd_off[l], &unused);
     widest = widest > d->dims[l + 1] ? widest : d->dims[l + 1];
   }
-  static PqlkPerDeviceOnce attr_once;
+  static PqlkPerDeviceOnce attr_once;   // (one per instantiation: each entry raises the limit of its own four kernels)
   if (int arc = attr_once.run([&] {
-        const void* ks[4] = {reinterpret_cast<const void*>(&k_lnmlp_fwd<1, false>), reinterpret_cast<const void*>(&k_lnmlp_fwd<1, true>),
-                             reinterpret_cast<const void*>(&k_lnmlp_fwd<2, false>), reinterpret_cast<const void*>(&k_lnmlp_fwd<2, true>)};
+        const void* ks[4] = {reinterpret_cast<const void*>(&k_lnmlp_fwd<1, false, D...>), reinterpret_cast<const void*>(&k_lnmlp_fwd<1, true, D...>),
+                             reinterpret_cast<const void*>(&k_lnmlp_fwd<2, false, D...>), reinterpret_cast<const void*>(&k_lnmlp_fwd<2, true, D...>)};
         for (const void* k : ks) {
           hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_MAX);
           if (err != hipSuccess) return -(int)err;
@@ -331,10 +348,26 @@ extern "C" int pqlk_lnmlp_forward(const PqlMlpDesc* desc, const float* arena, co
   const int r = lm_lds_bytes(d, 2) <= (size_t)LM_LDS_MAX && widest <= LM_MAX_R2_WIDTH ? 2 : 1;
   dim3 grid((unsigned)((m + 32 * r - 1) / (32 * r)), (unsigned)d->n_nets), block(64 * LM_NW);
   hipStream_t s = pqlk_s(stream);
-  if (r == 2 && stash) hipLaunchKernelGGL((k_lnmlp_fwd<2, true>), grid, block, lm_lds_bytes(d, 2), s, p);
-  else if (r == 2) hipLaunchKernelGGL((k_lnmlp_fwd<2, false>), grid, block, lm_lds_bytes(d, 2), s, p);
-  else if (stash) hipLaunchKernelGGL((k_lnmlp_fwd<1, true>), grid, block, lm_lds_bytes(d, 1), s, p);
-  else hipLaunchKernelGGL((k_lnmlp_fwd<1, false>), grid, block, lm_lds_bytes(d, 1), s, p);
+  if (r == 2 && stash) hipLaunchKernelGGL((k_lnmlp_fwd<2, true, D...>), grid, block, lm_lds_bytes(d, 2), s, p, dr...);
+  else if (r == 2) hipLaunchKernelGGL((k_lnmlp_fwd<2, false, D...>), grid, block, lm_lds_bytes(d, 2), s, p, dr...);
+  else if (stash) hipLaunchKernelGGL((k_lnmlp_fwd<1, true, D...>), grid, block, lm_lds_bytes(d, 1), s, p, dr...);
+  else hipLaunchKernelGGL((k_lnmlp_fwd<1, false, D...>), grid, block, lm_lds_bytes(d, 1), s, p, dr...);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
+}
+
+extern "C" int pqlk_lnmlp_forward(const PqlMlpDesc* desc, const float* arena, const float* x, int64_t ldx, int64_t m, float eps,
+                                  float* stash, float* q_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(desc && arena && x && q_out, PQLK_E_NULL);
+  PQLK_REQUIRE(pqlk_lnmlp_ok(desc) && m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
+  return lm_forward(desc, arena, x, ldx, m, eps, stash, q_out, stream);
+}
+
+extern "C" int pqlk_lnmlp_drop_forward(const PqlMlpDesc* desc, const float* arena, const float* x, int64_t ldx, int64_t m, float eps,
+                                       float p, uint64_t seed, uint64_t tag_base, float* stash, float* q_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(desc && arena && x && q_out, PQLK_E_NULL);
+  PQLK_REQUIRE(pqlk_lnmlp_ok(desc) && m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
+  LnDrop dr;
+  PQLK_REQUIRE(ln_drop_make_stack(p, seed, tag_base, m, desc->n_nets, desc->n_layers - 1, &dr), PQLK_E_SHAPE);
+  return lm_forward(desc, arena, x, ldx, m, eps, stash, q_out, stream, dr);
 }

@@ -21,7 +21,15 @@
 // features go as one ds_write_b64 into the image.  The output layer (width 1) rides on the last epilogue: the rounded activations are
 // multiplied with the bf16 output weights in the registers and summed through the first table, so nothing but Q leaves the block.
 // Three barriers per hidden layer, no atomics, no scratch; a row's bits depend on neither m, its position in the batch, nor the launch.
+//
+// Dropout (DoubleQDropoutLayerNorm's target with algo.critic_target_dtype=bfloat16; pqlk_lnmlp_drop_forward_bf16): lb_layer and the
+// kernel end in a parameter pack that is either empty (the plain kernel: the instructions and the bits of pqlk_lnmlp_forward_bf16 are
+// what they were) or one LnDrop.  Accumulator registers 4g .. 4g+3 of a lane are four consecutive, 4-aligned features of one row:
+// exactly one Philox4x32-10 block of the mask law.  So behind z = acc + b the lane generates that block in registers and leaves
+// u = keep ? z * s : 0 in the accumulators, in front of the first row-sum table; everything behind it runs on u as it ran on z.  The
+// mask's row index is the row's index in the whole batch (row0 + its row of the block), the tag tag_base | (net << 4) | layer.
 #include "lnrow.h"
+#include "lndrop.h"
 
 constexpr int LB_NW = 8;                 // waves per block
 constexpr int LB_LDS_MAX = 160 * 1024;
@@ -61,6 +69,17 @@ struct LnPackBf16P {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char lb_sm[];
 
+// what lb_layer's dropout form gets: the mask constants with the tag of its (net, layer), and the block's first batch row
+struct LbDrop {
+  LnDrop d;
+  uint32_t row0;
+};
+__device__ __forceinline__ LbDrop lb_drop_of() { return LbDrop{}; }
+__device__ __forceinline__ LbDrop lb_drop_of(const LbDrop& d) { return d; }
+__device__ __forceinline__ LbDrop lb_drop_at(const LnDrop& d, int net, int layer, long long row0) {
+  return LbDrop{ln_drop_at(d, net, layer), (uint32_t)row0};
+}
+
 // the sum of a row's partials, one per wave that holds features, in wave order
 __device__ __forceinline__ float lb_row_total(const float* tab, int rows, int row, int nw) {
   float t = tab[row];
@@ -71,11 +90,11 @@ __device__ __forceinline__ float lb_row_total(const float* tab, int rows, int ro
 // One hidden layer for the block's 32 R rows: img holds a~ (K columns, zeros past the input's width up to a multiple of 16) and is
 // overwritten with a~ of the next layer (N columns) -- or, with wout (the last hidden layer), the rows' Q partials are left in tab1.
 // Every wave of the block runs through the same barriers; ends behind the one after which the image (or tab1) is complete.
-template <int R, int NTW>
+template <int R, int NTW, typename... D>
 __device__ __forceinline__ void lb_layer(const uint4* __restrict__ w, int KS, int N, const float* __restrict__ bias,
                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                          const uint16_t* __restrict__ wout, uint16_t* img, int ld, float* tab1, float* tab2, int wave,
-                                         int lane) {
+                                         int lane, D... dr) {
   constexpr int ROWS = 32 * R;
   const int r = lane & 31, h = lane >> 5, NT = N >> 5;
   const int cnt = wave < NT ? (NT - 1 - wave) / LB_NW + 1 : 0;   // this wave's tiles: wave, wave + 8, ... (<= NTW)
@@ -130,6 +149,12 @@ __device__ __forceinline__ void lb_layer(const uint4* __restrict__ w, int KS, in
 #pragma unroll
         for (int i = 0; i < R; ++i) {
           acc[j][i][4 * g] += b4.x; acc[j][i][4 * g + 1] += b4.y; acc[j][i][4 * g + 2] += b4.z; acc[j][i][4 * g + 3] += b4.w;
+          if constexpr (ln_has<LbDrop, D...>) {   // u = keep ? z * s : 0: the four registers are one Philox block of row row0 + 32 i + r
+            const LbDrop d = lb_drop_of(dr...);
+            const float4 u = ln_drop4(d.d, d.row0 + (uint32_t)(32 * i + r), n0,
+                                      make_float4(acc[j][i][4 * g], acc[j][i][4 * g + 1], acc[j][i][4 * g + 2], acc[j][i][4 * g + 3]));
+            acc[j][i][4 * g] = u.x; acc[j][i][4 * g + 1] = u.y; acc[j][i][4 * g + 2] = u.z; acc[j][i][4 * g + 3] = u.w;
+          }
 #pragma unroll
           for (int e = 0; e < 4; ++e) s[i] += acc[j][i][4 * g + e];
         }
@@ -212,8 +237,8 @@ __device__ __forceinline__ void lb_layer(const uint4* __restrict__ w, int KS, in
   __syncthreads();   // the image (the Q partials) is complete
 }
 
-template <int R>
-__global__ __launch_bounds__(64 * LB_NW) void k_lnmlp_fwd_bf16(LnBf16P p) {
+template <int R, typename... D>
+__global__ __launch_bounds__(64 * LB_NW) void k_lnmlp_fwd_bf16(LnBf16P p, D... dr) {
   constexpr int ROWS = 32 * R;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int net = blockIdx.y, H = p.n_layers - 1, ld = p.ld;
@@ -245,12 +270,15 @@ __global__ __launch_bounds__(64 * LB_NW) void k_lnmlp_fwd_bf16(LnBf16P p) {
     const float *bias = prm + p.b_off[l], *ga = prm + p.g_off[l], *be = prm + p.be_off[l];
     const uint16_t* wout = l == H - 1 ? pk + p.p_off[H] : nullptr;
     const int ntw = ((N >> 5) + LB_NW - 1) / LB_NW;   // (block-uniform: the barriers inside are reached by every wave)
-    if (ntw == 1) lb_layer<R, 1>(w, KS, N, bias, ga, be, p.eps, wout, img, ld, tab1, tab2, wave, lane);
-    else if (ntw == 2) lb_layer<R, 2>(w, KS, N, bias, ga, be, p.eps, wout, img, ld, tab1, tab2, wave, lane);
+    // (dr: empty, or the launch's LnDrop, which gets the tag of this (net, layer) and the block's first row)
+#define LB_LAYER(R_, NTW) lb_layer<R_, NTW>(w, KS, N, bias, ga, be, p.eps, wout, img, ld, tab1, tab2, wave, lane, lb_drop_at(dr, net, l, row0)...)
+    if (ntw == 1) LB_LAYER(R, 1);
+    else if (ntw == 2) LB_LAYER(R, 2);
     else if constexpr (R == 1) {
-      if (ntw == 3) lb_layer<1, 3>(w, KS, N, bias, ga, be, p.eps, wout, img, ld, tab1, tab2, wave, lane);
-      else lb_layer<1, 4>(w, KS, N, bias, ga, be, p.eps, wout, img, ld, tab1, tab2, wave, lane);
+      if (ntw == 3) LB_LAYER(1, 3);
+      else LB_LAYER(1, 4);
     }
+#undef LB_LAYER
   }
   // Q = (the row's partials in wave order) + b: column 0 of the row's 32 floats, the rest zero; 8 threads write a row
   {
@@ -367,12 +395,10 @@ extern "C" int pqlk_lnmlp_pack_bf16(const PqlMlpDesc* desc, const float* arena, 
   return PQLK_OK;
 }
 
-extern "C" int pqlk_lnmlp_forward_bf16(const PqlMlpDesc* desc, const float* arena, const uint16_t* packed, const float* x, int64_t ldx,
-                                       int64_t m, float eps, float* q_out, pqlk_stream_t stream) {
-  PQLK_REQUIRE(desc && arena && packed && x && q_out, PQLK_E_NULL);
-  LnBf16Layout d;
-  PQLK_REQUIRE(lb_layout(desc, &d), PQLK_E_SHAPE);
-  PQLK_REQUIRE(m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
+// the one dispatch of the plain entry (an empty pack) and the dropout entry (one LnDrop, its tag the launch's tag_base)
+template <typename... D>
+static int lb_forward(const LnBf16Layout& d, const float* arena, const uint16_t* packed, const float* x, int64_t ldx, int64_t m, float eps,
+                      float* q_out, pqlk_stream_t stream, D... dr) {
   PQLK_REQUIRE(ldx % 32 == 0 && ldx >= pqlk_ld(d.dims[0]), PQLK_E_ALIGN);
   PQLK_REQUIRE(pqlk_aligned16(arena) && pqlk_aligned16(packed) && pqlk_aligned16(x) && pqlk_aligned16(q_out), PQLK_E_ALIGN);
   const int L = d.n_layers;
@@ -386,9 +412,9 @@ extern "C" int pqlk_lnmlp_forward_bf16(const PqlMlpDesc* desc, const float* aren
     p.p_off[l] = d.p_off[l];
     if (l < L - 1) { p.g_off[l] = d.gamma_off[l]; p.be_off[l] = d.beta_off[l]; }
   }
-  static PqlkPerDeviceOnce attr_once;
+  static PqlkPerDeviceOnce attr_once;   // (one per instantiation: each entry raises the limit of its own two kernels)
   if (int arc = attr_once.run([&] {
-        const void* ks[2] = {reinterpret_cast<const void*>(&k_lnmlp_fwd_bf16<1>), reinterpret_cast<const void*>(&k_lnmlp_fwd_bf16<2>)};
+        const void* ks[2] = {reinterpret_cast<const void*>(&k_lnmlp_fwd_bf16<1, D...>), reinterpret_cast<const void*>(&k_lnmlp_fwd_bf16<2, D...>)};
         for (const void* k : ks) {
           hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LB_LDS_MAX);
           if (err != hipSuccess) return -(int)err;
@@ -397,8 +423,27 @@ extern "C" int pqlk_lnmlp_forward_bf16(const PqlMlpDesc* desc, const float* aren
       }))
     return arc;
   dim3 grid((unsigned)((m + 32 * d.r - 1) / (32 * d.r)), (unsigned)d.n_nets), block(64 * LB_NW);
-  if (d.r == 2) hipLaunchKernelGGL(k_lnmlp_fwd_bf16<2>, grid, block, lb_lds_bytes(d.ld, 2), pqlk_s(stream), p);
-  else hipLaunchKernelGGL(k_lnmlp_fwd_bf16<1>, grid, block, lb_lds_bytes(d.ld, 1), pqlk_s(stream), p);
+  if (d.r == 2) hipLaunchKernelGGL((k_lnmlp_fwd_bf16<2, D...>), grid, block, lb_lds_bytes(d.ld, 2), pqlk_s(stream), p, dr...);
+  else hipLaunchKernelGGL((k_lnmlp_fwd_bf16<1, D...>), grid, block, lb_lds_bytes(d.ld, 1), pqlk_s(stream), p, dr...);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
+}
+
+extern "C" int pqlk_lnmlp_forward_bf16(const PqlMlpDesc* desc, const float* arena, const uint16_t* packed, const float* x, int64_t ldx,
+                                       int64_t m, float eps, float* q_out, pqlk_stream_t stream) {
+  PQLK_REQUIRE(desc && arena && packed && x && q_out, PQLK_E_NULL);
+  LnBf16Layout d;
+  PQLK_REQUIRE(lb_layout(desc, &d) && m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
+  return lb_forward(d, arena, packed, x, ldx, m, eps, q_out, stream);
+}
+
+extern "C" int pqlk_lnmlp_drop_forward_bf16(const PqlMlpDesc* desc, const float* arena, const uint16_t* packed, const float* x, int64_t ldx,
+                                            int64_t m, float eps, float p, uint64_t seed, uint64_t tag_base, float* q_out,
+                                            pqlk_stream_t stream) {
+  PQLK_REQUIRE(desc && arena && packed && x && q_out, PQLK_E_NULL);
+  LnBf16Layout d;
+  PQLK_REQUIRE(lb_layout(desc, &d) && m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
+  LnDrop dr;
+  PQLK_REQUIRE(ln_drop_make_stack(p, seed, tag_base, m, d.n_nets, d.n_layers - 1, &dr), PQLK_E_SHAPE);
+  return lb_forward(d, arena, packed, x, ldx, m, eps, q_out, stream, dr);
 }

@@ -16,31 +16,8 @@
 // Skip connection (BroNet, DoubleQBroNet): pqlk_ln_res_forward / pqlk_ln_sum_backward run the same row bodies again, the pack now
 // one LnRes (forward: no ELU, y = res + LN(z)) or one LnSum (backward: the incoming gradient is dy + dy2, handed on as dsum; the ELU
 // factor only where y is given).  The skip and the second addend are loaded a chunk at a time where they are used, not held as a row.
-#include <type_traits>
-
-#include "lnrow.h"   // LnMap, ln_load / ln_store, LN_ROW_CENTER, ln_elu: the row routine, shared with fwd_ln.hip
-
-// Philox4x32-10 (Salmon et al. 2011), ten rounds written out: counter (c0, c1, c2, c3), key (k0, k1) -> one block of four words
-__device__ __forceinline__ uint4 ln_philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return make_uint4(c0, c1, c2, c3);
-}
-
-// the mask law's host-made constants: key = seed, counter words 2 / 3 = tag, thr = floor(p * 2^32), s = 1 / (1 - p)
-struct LnDrop {
-  uint32_t k0, k1, t0, t1, thr;
-  float s;
-};
-
-// the LnDrop of a kernel's trailing pack (an empty pack: the plain kernel, which never reads it)
-__device__ __forceinline__ LnDrop ln_drop_of() { return LnDrop{}; }
-__device__ __forceinline__ LnDrop ln_drop_of(const LnDrop& d) { return d; }
+#include "lnrow.h"    // LnMap, ln_load / ln_store, LN_ROW_CENTER, ln_elu: the row routine, shared with fwd_ln.hip
+#include "lndrop.h"   // ln_philox, LnDrop, ln_keep1 / ln_keep_bits, ln_drop_make: the mask law, shared with fwd_ln.hip and fwd_ln_bf16.hip
 
 // the skip connection's extra operands (include/pqlk.h): the forward's res; the backward's second addend and where the sum goes
 struct LnRes {
@@ -53,21 +30,6 @@ struct LnSum {
 __device__ __forceinline__ LnRes ln_res_of(const LnRes& r) { return r; }
 __device__ __forceinline__ LnSum ln_sum_of(const LnSum& a) { return a; }
 
-// whether a kernel's trailing pack is one T
-template <typename T, typename... D>
-inline constexpr bool ln_has = (std::is_same_v<T, D> || ...);
-
-// word (c & 3) of a block (selects on values: an indexed uint4 would be promoted to LDS)
-__device__ __forceinline__ uint32_t ln_word(uint4 b, int c) {
-  const uint32_t lo = (c & 1) ? b.y : b.x, hi = (c & 1) ? b.w : b.z;
-  return (c & 2) ? hi : lo;
-}
-
-// keep(r, c) of one element: one Philox block per call (the scalar layout, the strided wide path)
-__device__ __forceinline__ bool ln_keep1(const LnDrop& d, uint32_t r, int c) {
-  return ln_word(ln_philox(d.k0, d.k1, (uint32_t)c >> 2, r, d.t0, d.t1), c) >= d.thr;
-}
-
 #define LN_WAVES 4             // rows in flight per block
 #define LN_MAX_REG_COLS 1024   // widest row held in registers
 
@@ -77,32 +39,6 @@ template <int VPL, bool VEC>
 __device__ __forceinline__ void ln_load_chunk(const float* __restrict__ p, int cols, int lane, int k, float (&v)[LnMap<VPL, VEC>::V]) {
   constexpr int V = LnMap<VPL, VEC>::V;
   ln_load<V, VEC>(p + k * 64 * V, cols - k * 64 * V, lane, v);
-}
-
-// bit i = keep of register slot i of row r (slots past cols: 0; they hold 0.f anyway).  VEC: a lane's chunk lies in ONE Philox block
-// (V = 4: the whole block; V = 2: its lower or upper half), generated once per chunk; scalar: one block per element.
-template <int VPL, bool VEC>
-__device__ __forceinline__ unsigned ln_keep_bits(const LnDrop& d, uint32_t r, int cols, int lane) {
-  using M = LnMap<VPL, VEC>;
-  unsigned km = 0;
-  if (VEC) {
-#pragma unroll
-    for (int k = 0; k < M::NCH; ++k) {
-      const int c0 = (k * 64 + lane) * M::V;
-      if (c0 < cols) {
-        const uint4 b = ln_philox(d.k0, d.k1, (uint32_t)c0 >> 2, r, d.t0, d.t1);
-#pragma unroll
-        for (int e = 0; e < M::V; ++e) km |= (unsigned)(ln_word(b, c0 + e) >= d.thr) << (k * M::V + e);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = i * 64 + lane;
-      if (c < cols) km |= (unsigned)ln_keep1(d, r, c) << i;
-    }
-  }
-  return km;
 }
 
 template <int VPL, bool VEC, typename... D>
@@ -508,17 +444,7 @@ extern "C" int pqlk_ln_sum_backward(const float* dy, const float* dy2, const flo
   return ln_backward(dy, y, z, ld, m, cols, mean, rstd, gamma, dz, dgamma, dbeta, scratch, stream, LnSum{dy2, dsum});
 }
 
-// ---- dropout entries: the mask law's constants are made here, on the host (include/pqlk.h)
-static bool ln_drop_make(float p, uint64_t seed, uint64_t tag, int64_t m, LnDrop* d) {
-  if (!(p >= 0.f && p < 1.f) || m > (int64_t)1 << 32) return false;   // (a NaN p fails the first test)
-  d->k0 = (uint32_t)seed; d->k1 = (uint32_t)(seed >> 32);
-  d->t0 = (uint32_t)tag; d->t1 = (uint32_t)(tag >> 32);
-  d->thr = (uint32_t)floor((double)p * 4294967296.0);
-  const float q = 1.0f - p;
-  d->s = 1.0f / q;
-  return true;
-}
-
+// ---- dropout entries: the mask law's constants are made on the host (ln_drop_make of lndrop.h; include/pqlk.h)
 // keep(r, c) as bytes: one thread per Philox block = four consecutive columns of a row
 __global__ __launch_bounds__(256) void k_drop_mask(LnDrop dr, int64_t m, int cols, uint8_t* __restrict__ keep, int64_t ld_keep) {
   const int64_t per_row = (cols + 3) / 4, total = m * per_row;

@@ -14,6 +14,13 @@ generated inside the LayerNorm + ELU row launches from Philox4x32-10, forward an
 a `deepcopy` (the target critic) gets `drop_stream + 1`, so a critic and its target never share a mask.  `backward_raw` regenerates
 the masks of the forward it belongs to from the counter value that forward stashed.  (seed, drop_calls, drop_stream) is the whole
 state of the dropout: `drop_state()` / `load_drop_state()`, saved with an agent's training state.
+
+`fused_forward=True` (`algo.droq_fused_forward`): a dropout forward is ONE launch for both nets and every layer,
+`pqlk_lnmlp_drop_forward` (pql_amd/csrc/fwd_ln.hip) with tag_base = (drop_calls << 8) | (drop_stream << 5): the masks are the per-layer
+path's, regenerated inside the launch, and the stash holds the pre-dropout z, so `backward_raw` is what it was.  With
+`target_dtype="bfloat16"` (`algo.critic_target_dtype`) `forward_raw(x, stash=False)` is the bf16-MFMA launch
+`pqlk_lnmlp_drop_forward_bf16` (pql_amd/csrc/fwd_ln_bf16.hip) on the packed copy.  drop=False runs `DoubleQLayerNorm`'s plain launches.
+Both switches are launch choices: no part of `init_kwargs`, of the state_dict or of a checkpoint.
 """
 from __future__ import annotations
 
@@ -25,6 +32,7 @@ from pql_amd import _lib as L
 from pql_amd.models.layernorm import LN_EPS, DoubleQLayerNorm
 
 MAX_DROP_LAYERS, MAX_DROP_STREAM = 16, 7   # the tag's 4 layer bits and 3 stream bits
+DROQ_FUSED_KEY = "algo.droq_fused_forward"
 
 
 def check_dropout(p):
@@ -37,9 +45,11 @@ def check_dropout(p):
 
 
 class DoubleQDropoutLayerNorm(DoubleQLayerNorm):
-    def __init__(self, state_dim, act_dim, hidden_layers=None, dropout=0.01, seed=None):
+    fused_key = DROQ_FUSED_KEY
+
+    def __init__(self, state_dim, act_dim, hidden_layers=None, dropout=0.01, seed=None, fused_forward=False, target_dtype="float32"):
         p = check_dropout(dropout)   # before anything is allocated
-        super().__init__(state_dim, act_dim, hidden_layers)
+        super().__init__(state_dim, act_dim, hidden_layers, fused_forward, target_dtype)
         self.dropout = p
         if self.n_layers - 1 > MAX_DROP_LAYERS:
             raise ValueError(f"DoubleQDropoutLayerNorm: {self.n_layers - 1} hidden layers, the mask tag has room for {MAX_DROP_LAYERS}")
@@ -84,16 +94,25 @@ class DoubleQDropoutLayerNorm(DoubleQLayerNorm):
                                                 L.ptr(ws["ln_scratch"]) if gg is not None else None, st))
 
     @torch.no_grad()
-    def forward_raw(self, x_pad, drop=True):
+    def forward_raw(self, x_pad, drop=True, stash=True):
         """x_pad (M, ld(in)) with zero pad columns -> Q (2, M, 32) (column 0).  drop=True (every learning forward): the hidden blocks
         run with this call's masks and `drop_calls` advances; `backward_raw` on the same x_pad regenerates them.  drop=False: the plain
-        LayerNorm entries, forward and backward -- `DoubleQLayerNorm`'s bits."""
+        LayerNorm entries, forward and backward -- `DoubleQLayerNorm`'s bits.  stash=False (fused_forward only; a forward nothing
+        goes back through, the target's): Q alone, with target_dtype="bfloat16" from the packed copy on bf16 MFMA."""
         call = self.drop_calls if drop else None
-        ws = self._forward_layers(x_pad, call=call)
-        ws["drop_call"] = call
+        if self.fused is None:
+            if not stash:
+                raise ValueError(f"forward_raw(stash=False) is the one-launch forward's: it needs {self.fused_key}=True")
+            ws = self._forward_layers(x_pad, call=call)
+            ws["drop_call"] = call
+            q = self._q_of(ws)
+        else:
+            q = self._fused_forward(x_pad, stash, None if call is None else (self.dropout, self.seed, self.tag(call, 0, 0)))
+            if stash:   # (a forward without a stash leaves the workspace, and the backward it belongs to, alone)
+                self._workspace(x_pad.shape[0], x_pad.device)["drop_call"] = call
         if drop:
             self.drop_calls += 1
-        return self._q_of(ws)
+        return q
 
     # ---- reference surface (evaluation, logging): no dropout ---------------------------------------------------
     def _heads(self, state, action):

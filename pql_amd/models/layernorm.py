@@ -44,12 +44,13 @@ def lnmlp_desc(dims, n_nets=2) -> L.PqlMlpDesc:
     return d
 
 
-def check_fused_forward(dims):
-    """`algo.critic_fused_forward=True` on a stack the one-launch forward does not take: refused, never a silent per-layer run."""
+def check_fused_forward(dims, key=FUSED_KEY):
+    """`algo.critic_fused_forward=True` on a stack the one-launch forward does not take: refused, never a silent per-layer run.
+    key: the switch of the class that asks (the dropout critic has its own, `algo.droq_fused_forward`)."""
     if not L.lib.pqlk_lnmlp_ok(C.byref(lnmlp_desc(dims))):
-        raise ValueError(f"{FUSED_KEY}=True cannot run a critic of layers {list(dims)}: the one-launch forward takes 1 to "
+        raise ValueError(f"{key}=True cannot run a critic of layers {list(dims)}: the one-launch forward takes 1 to "
                          f"{L.MAX_LAYERS - 1} hidden layers whose widths are multiples of 32 and at most 1024, on an input of at most 1248 "
-                         f"padded columns; set {FUSED_KEY}=False for the per-layer forward")
+                         f"padded columns; set {key}=False for the per-layer forward")
 
 
 def check_target_dtype_value(v):
@@ -57,10 +58,10 @@ def check_target_dtype_value(v):
         raise ValueError(f"{TARGET_DTYPE_KEY} must be float32 or bfloat16, got {v!r}")
 
 
-def check_target_bf16(dims, fused_forward):
+def check_target_bf16(dims, fused_forward, key=FUSED_KEY):
     """`algo.critic_target_dtype=bfloat16` where the bf16 target forward cannot run: refused, never a silent fp32 run."""
     if not fused_forward:
-        raise ValueError(f"{TARGET_DTYPE_KEY}=bfloat16 needs {FUSED_KEY}=True: the bf16 target forward is a form of the one-launch forward "
+        raise ValueError(f"{TARGET_DTYPE_KEY}=bfloat16 needs {key}=True: the bf16 target forward is a form of the one-launch forward "
                          f"(the per-layer forward has no bf16 kernels)")
     if not L.lib.pqlk_lnmlp_bf16_ok(C.byref(lnmlp_desc(dims))):
         raise ValueError(f"{TARGET_DTYPE_KEY}=bfloat16 cannot run a critic of layers {list(dims)}: the bf16 image of 32 batch rows of its "
@@ -68,13 +69,15 @@ def check_target_bf16(dims, fused_forward):
 
 
 class DoubleQLayerNorm(NormTwinQ):
+    fused_key = FUSED_KEY   # the config key of this class's `fused_forward`, for its messages
+
     def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False, target_dtype="float32"):
         dims = [_first(state_dim) + int(act_dim), *(HIDDEN_DEFAULT if hidden_layers is None else hidden_layers), 1]
         check_target_dtype_value(target_dtype)
         if fused_forward:   # before anything is allocated
-            check_fused_forward(dims)
+            check_fused_forward(dims, self.fused_key)
         if target_dtype == "bfloat16":
-            check_target_bf16(dims, fused_forward)
+            check_target_bf16(dims, fused_forward, self.fused_key)
         super().__init__(state_dim, act_dim, hidden_layers)
         self.fused = lnmlp_desc(self.dims) if fused_forward else None   # None: the per-layer forward, no fused state anywhere
         if self.fused is not None:   # the library's statement of the arena law is this module's
@@ -146,8 +149,12 @@ class DoubleQLayerNorm(NormTwinQ):
                                            L.ptr(ws["mean"][(n, l)]), L.ptr(ws["rstd"][(n, l)]), L.ptr(self.norm_param(n, l, "gamma")),
                                            L.ptr(d), L.ptr(gg), L.ptr(gb), L.ptr(ws["ln_scratch"]) if gg is not None else None, st))
 
-    def _fused_forward(self, x_pad, stash):
-        """The one launch.  stash: into the workspace `backward_raw` reads; else Q alone, into a block that is no part of it."""
+    def _fused_forward(self, x_pad, stash, drop=None):
+        """The one launch.  stash: into the workspace `backward_raw` reads; else Q alone, into a block that is no part of it.
+        drop (the dropout subclass, pql_amd/models/droq.py): (p, seed, tag_base) -- the `pqlk_lnmlp_drop_*` form of the same launch."""
+        fp32, bf16 = (L.lib.pqlk_lnmlp_forward, L.lib.pqlk_lnmlp_forward_bf16) if drop is None else \
+            (L.lib.pqlk_lnmlp_drop_forward, L.lib.pqlk_lnmlp_drop_forward_bf16)
+        drop = () if drop is None else drop
         L.require_gpu(self.arena, "parameter arena")
         M, dev = x_pad.shape[0], x_pad.device
         if stash:
@@ -163,12 +170,12 @@ class DoubleQLayerNorm(NormTwinQ):
                     raise RuntimeError("forward_raw(stash=False) reads the packed bf16 copy, which was never written: call refresh() "
                                        "behind every change of the arena")
                 with torch.cuda.device(dev):
-                    L.check(L.lib.pqlk_lnmlp_forward_bf16(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(self.packed), L.ptr(x_pad),
-                                                          x_pad.stride(0), M, LN_EPS, L.ptr(q), L.stream(dev)))
+                    L.check(bf16(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(self.packed), L.ptr(x_pad), x_pad.stride(0), M, LN_EPS,
+                                 *drop, L.ptr(q), L.stream(dev)))
                 return q
         with torch.cuda.device(dev):
-            L.check(L.lib.pqlk_lnmlp_forward(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(x_pad), x_pad.stride(0), M, LN_EPS,
-                                             L.ptr(slab), L.ptr(q), L.stream(dev)))
+            L.check(fp32(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(x_pad), x_pad.stride(0), M, LN_EPS, *drop, L.ptr(slab), L.ptr(q),
+                         L.stream(dev)))
         return q
 
     @torch.no_grad()
@@ -179,7 +186,7 @@ class DoubleQLayerNorm(NormTwinQ):
         if self.fused is not None:
             return self._fused_forward(x_pad, stash)
         if not stash:
-            raise ValueError(f"forward_raw(stash=False) is the one-launch forward's: it needs {FUSED_KEY}=True")
+            raise ValueError(f"forward_raw(stash=False) is the one-launch forward's: it needs {self.fused_key}=True")
         return self._q_of(self._forward_layers(x_pad))
 
     # ---- reference surface: no train / eval difference ----------------------------------------------------------

@@ -14,6 +14,13 @@ ONE call, variants alternating inside every round (deltas between variants come 
             forward they replace -- and the update with the key on as a third update column.
 
     python tools/bench_lnmlp.py --out profiles/lnmlp_bf16_bench.json
+
+`--droq`: the same protocol for the DroQ critic's one-launch dropout forwards (`algo.droq_fused_forward`, pqlk_lnmlp_drop_forward /
+_bf16) at hidden [512, 512, 256], p = 0.01: the dropout launches against the per-layer dropout forward and against the plain fused
+launches of the same module on the same buffers (`drop=False`), and one `update_net` of algo=droq_algo (20 updates, each with three
+dropout forwards) with the key off, on, and on with a bf16 target.
+
+    python tools/bench_lnmlp.py --droq --out profiles/droq_fused_bench.json
 """
 import argparse
 import json
@@ -51,6 +58,77 @@ def forward_variants(dev, batch):
         out[(name, "fused_bf16_no_stash")] = lambda b16=b16, x=x: b16.forward_raw(x, stash=False)
         out[(name, "pack_bf16")] = b16.refresh
     return out
+
+
+def droq_forward_variants(dev, batch, p=0.01):
+    from pql_amd.models.droq import DoubleQDropoutLayerNorm
+    from pql_amd.models.mlp import pad_cols
+    hidden = HIDDEN["default"]
+    per, fus, b16 = (DoubleQDropoutLayerNorm((O,), A, hidden, dropout=p, seed=1, **kw).to(dev)
+                     for kw in ({}, dict(fused_forward=True), dict(fused_forward=True, target_dtype="bfloat16")))
+    fus.arena.data.copy_(per.arena.data)
+    b16.arena.data.copy_(per.arena.data)
+    b16.refresh()
+    x = pad_cols(torch.randn((batch, O + A), device=dev), L.ld(O + A))
+    return {"per_layer_drop": lambda: per.forward_raw(x),
+            "drop_fused_stash": lambda: fus.forward_raw(x), "plain_fused_stash": lambda: fus.forward_raw(x, drop=False),
+            "drop_fused_no_stash": lambda: fus.forward_raw(x, stash=False), "plain_fused_no_stash": lambda: fus.forward_raw(x, drop=False, stash=False),
+            "drop_bf16_no_stash": lambda: b16.forward_raw(x, stash=False), "plain_bf16_no_stash": lambda: b16.forward_raw(x, drop=False, stash=False)}
+
+
+def make_droq_agent(fused, batch, target_dtype):
+    from pql_amd.algo.sac import AgentSAC
+    from pql_amd.envs.synthetic import create_task_env
+    from pql_amd.replay.simple_replay import ReplayBuffer
+    from pql_amd.utils.cfg import load_cfg
+    rows = 4 * batch
+    cfg = load_cfg(["algo=droq_algo", "task.name=AllegroHand", "num_envs=64", f"algo.batch_size={batch}", f"algo.memory_size={rows}",
+                    "device=cuda:0", "sim_device=cuda:0", f"algo.hidden_layers={HIDDEN['default']}", "algo.critic_dropout=0.01",
+                    f"algo.droq_fused_forward={fused}", f"algo.critic_target_dtype={target_dtype}"])
+    agent = AgentSAC(create_task_env(cfg), cfg)
+    dev = agent.device
+    memory = ReplayBuffer(rows, (O,), A, device=dev)
+    memory.add_to_buffer((torch.randn((rows, O), device=dev), torch.rand((rows, A), device=dev) * 2 - 1, torch.randn((rows, 1), device=dev) * 0.05,
+                          torch.randn((rows, O), device=dev), (torch.rand((rows, 1), device=dev) < 0.1).float()))
+    return agent, memory
+
+
+def time_update_net(agent, memory):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    agent.update_net(memory)   # (ends in a host read of the loss rings: a device synchronise)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e6
+
+
+def droq_main(a, dev):
+    fv = droq_forward_variants(dev, a.batch)
+    agents = {(fused, dt): make_droq_agent(fused, a.batch, dt) for fused, dt in ((False, "float32"), (True, "float32"), (True, "bfloat16"))}
+    ftimes, utimes = {k: [] for k in fv}, {k: [] for k in agents}
+    for r in range(a.rounds + 1):     # round 0 warms up
+        for k, fn in fv.items():
+            t = time_launches(fn, a.launches)
+            if r:
+                ftimes[k].append(t)
+        for k, (agent, memory) in agents.items():
+            t = time_update_net(agent, memory)
+            if r:
+                utimes[k].append(t)
+    med = {k: statistics.median(ts) for k, ts in ftimes.items()}
+    res = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, rounds=a.rounds, launches=a.launches, obs_dim=O, act_dim=A,
+               batch=a.batch, hidden=HIDDEN["default"], dropout=0.01, forward=[], update_net=[],
+               drop_over_plain={k: round(med[f"drop_{k}"] / med[f"plain_{k}"], 3) for k in ("fused_stash", "fused_no_stash", "bf16_no_stash")},
+               per_layer_over_drop={k: round(med["per_layer_drop"] / med[f"drop_{k}"], 2) for k in ("fused_stash", "fused_no_stash", "bf16_no_stash")})
+    for what, ts in ftimes.items():
+        res["forward"].append(dict(what=what, us_median=round(statistics.median(ts), 2), us_min=round(min(ts), 2)))
+    for (fused, dt), ts in utimes.items():
+        res["update_net"].append(dict(droq_fused_forward=fused, critic_target_dtype=dt, update_times=int(agents[(fused, dt)][0].cfg.algo.update_times),
+                                      us_median=round(statistics.median(ts), 1), us_min=round(min(ts), 1)))
+    for rec in (*res["forward"], *res["update_net"], dict(drop_over_plain=res["drop_over_plain"], per_layer_over_drop=res["per_layer_over_drop"])):
+        print(json.dumps(rec), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
 
 
 def time_launches(fn, n):
@@ -96,10 +174,13 @@ def main():
     ap.add_argument("--updates", type=int, default=50)
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--droq", action="store_true", help="the DroQ critic's one-launch dropout forwards (see the module docstring)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_lnmlp needs a GPU"
     torch.manual_seed(0)
     dev = torch.device("cuda:0")
+    if a.droq:
+        return droq_main(a, dev)
     fv = forward_variants(dev, a.batch)
     agents = {(name, fused, dt): make_agent(hidden, fused, a.batch, dt) for name, hidden in HIDDEN.items()
               for fused, dt in ((False, "float32"), (True, "float32"), (True, "bfloat16"))}
