@@ -993,6 +993,44 @@ int pqlk_lnmlp_stash_offset(const PqlMlpDesc* d, int64_t m, int32_t net, int32_t
 int pqlk_lnmlp_forward(const PqlMlpDesc* d, const float* arena, const float* x, int64_t ldx, int64_t m, float eps,
                        float* stash, float* q_out, pqlk_stream_t stream);
 
+/* Input gradient of the same stack with its parameters frozen (pql_amd/csrc/bwd_ln.hip; algo.critic_fused_dx): the critic's part of
+ * the actor step of DDPG and SAC.  ONE launch for every net and layer, where the per-layer form runs H row launches and H + 1 one-layer
+ * backward GEMMs per net, a torch add of the nets and, for DDPG, a torch slice and tanh factor.  Same descriptor, same arena, and the
+ * stash slab that pqlk_lnmlp_forward(..., stash, ...) wrote for these m rows; nothing of the arena or the stash is written.  No
+ * parameter gradient is formed (a backward with parameter gradients is the per-layer form's).
+ *
+ * The law, per net n and batch row, everything fp32 and every written operation ONE rounding; dq (n_nets, m, 32) holds d loss / d Q_n
+ * in column 0 (columns 1 .. 31 are never read):
+ *   output layer (width 1, rank 1):  d_{H-1}[j] = dq_n * w_out[j]
+ *   hidden layer l = H-1 .. 0, with y, z, mean, rstd of (n, l) from the stash:
+ *     g_j  = d_l[j] * (y_j > 0 ? 1 : y_j + 1)
+ *     xhat_j = (z_j - mean) * rstd
+ *     h_j  = g_j * gamma_j
+ *     c1   = (sum_j h_j) / n_l,   c2 = (sum_j h_j * xhat_j) / n_l
+ *     dz_j = rstd * (h_j - c1 - xhat_j * c2)                (left to right)
+ *            the LayerNorm + ELU backward law above with the row sums of its 16-byte layout (per-lane partials in register order, then
+ *            the 64-lane xor butterfly): dz is bit for bit what pqlk_ln_elu_backward with dgamma == dbeta == NULL gives on this d_l
+ *     d_{l-1}[k] = acc_k;  acc_k = 0;  for every 8-wide group of output features j, s = 0, 1, ..., in the order j = 8s + 0, 4, 1, 5, 2,
+ *            6, 3, 7, two j at a time:  acc_k = acc_k + (dz_j W_l[j][k] + dz_j' W_l[j'][k])   as v_mfma_f32_32x32x2_f32 forms it
+ *            (j = 8s + e, j' = 8s + 4 + e, e = 0 .. 3)
+ *   g[k] = d_{-1}[k] of net 0, + that of net 1 (net order), k < dims[0]
+ * Plain form (tanh_of == NULL; col0, cols, ld_a are ignored): dx[row][k] = g[k] for k < dims[0], zeros in [dims[0], pqlk_ld(dims[0]));
+ * dx (m, ld_dx), ld_dx >= pqlk_ld(dims[0]); columns past pqlk_ld(dims[0]) stay untouched.
+ * Tanh form (tanh_of (m, ld_a): the actor's tanh output): dx[row][j] = g[col0 + j] * (1 - a * a), a = tanh_of[row][j], for j < cols;
+ * dx (m, ld_dx), ld_dx >= cols, ld_a >= cols; columns [cols, ld_dx) of dx stay untouched.  Layer 0's product runs only over the
+ * 32-column tiles that intersect [col0, col0 + cols).
+ * A row's bits depend on neither m nor its position in the batch; nothing of a row >= m is read or written; NaN / Inf stay in their
+ * row.  dx is written by net 0 and re-read by net 1 inside the launch, so it aliases nothing the launch reads.
+ *
+ * r: the rows a block takes through the chain, 32 r.  0: the library's choice; 1 or 2: forced (a tuning knob for measurements; 2 only
+ * where the forward may take 64 rows: a 64-row image inside 160 KB of LDS and no hidden layer wider than 512).  The bits do not
+ * depend on r.
+ * Errors, before any launch: PQLK_E_NULL (d, arena, stash, dq, dx); PQLK_E_SHAPE for a descriptor pqlk_lnmlp_ok refuses, m <= 0,
+ * m >= 2^30, an r that is not allowed, ld_dx (or ld_a) below what the form writes (reads); PQLK_E_RANGE for col0 < 0, cols < 1 or
+ * col0 + cols > dims[0] in the tanh form; PQLK_E_ALIGN for ld_dx % 4 != 0 or a pointer that is not 16-B aligned. */
+int pqlk_lnmlp_dx(const PqlMlpDesc* d, const float* arena, const float* stash, const float* dq, int64_t m, float* dx, int64_t ld_dx,
+                  int32_t col0, int32_t cols, const float* tanh_of, int64_t ld_a, int32_t r, pqlk_stream_t stream);
+
 /* Forward-only bf16-MFMA form of the same stack (pql_amd/csrc/fwd_ln_bf16.hip; algo.critic_target_dtype=bfloat16): the target
  * critic's forward, through which nothing goes back.  Same descriptor, same arena; no stash.  The bf16 LayerNorm law, per net and
  * batch row (RNE = round to nearest even, ties included; NaN stays NaN, overflow goes to +-inf):

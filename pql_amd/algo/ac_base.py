@@ -234,6 +234,12 @@ class ActorCriticBase(PQLActor):
                 mlp_backward_raw(cl, self.critic.arena.data, x, ws["acts_c"], ws["dy"], ws["bwd_c"], dx=dx, dx_col0=O, dx_cols=A,
                                  dx_tanh_of=tanh_of)
             return
+        if getattr(self.critic, "fused_dx_on", False):   # algo.critic_fused_dx: one launch, straight into dx
+            if tanh_of is None:
+                self.critic.fused_dx(ws["dy"], dx)
+            else:
+                self.critic.fused_dx(ws["dy"], dx[0], O, A, tanh_of[0])
+            return
         g = self.critic.backward_raw(x, ws["dy"], grads=None, need_dx=True)
         if tanh_of is None:
             dx.copy_(g)

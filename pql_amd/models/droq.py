@@ -114,6 +114,10 @@ class DoubleQDropoutLayerNorm(DoubleQLayerNorm):
             self.drop_calls += 1
         return q
 
+    def fused_dx(self, *args, **kw):
+        raise ValueError("DoubleQDropoutLayerNorm has no one-launch input gradient: the mask is not in pqlk_lnmlp_dx's row step "
+                         "(algo.critic_fused_dx is DoubleQLayerNorm's)")
+
     # ---- reference surface (evaluation, logging): no dropout ---------------------------------------------------
     def _heads(self, state, action):
         return self.forward_raw(self._x_of(state, action), drop=False)

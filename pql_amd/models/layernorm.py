@@ -16,6 +16,11 @@ every hidden layer in one slab of which `ws["z"]`, `ws["y"]`, `ws["mean"]`, `ws[
 bf16 copy of its weights as int16 (`pqlk_lnmlp_pack_bf16`; never saved), and `forward_raw(x, stash=False)` is the bf16-MFMA launch
 `pqlk_lnmlp_forward_bf16` (pql_amd/csrc/fwd_ln_bf16.hip) reading it.  `refresh()` must run behind every change of the arena; a forward
 with a stash stays the fp32 launch.
+
+`fused_dx=True` (`algo.critic_fused_dx`, with `fused_forward` only): the way back to the input with the parameters frozen -- the actor
+step's `backward_raw(grads=None, need_dx=True)` -- is ONE launch for both nets and every layer, `pqlk_lnmlp_dx`
+(pql_amd/csrc/bwd_ln.hip, the law in include/pqlk.h), reading the slab the last stash forward wrote; `fused_dx(...)` is that call, in
+its plain form or through the actor's tanh.  A backward that forms parameter gradients stays the per-layer one.  No part of a checkpoint.
 """
 from __future__ import annotations
 
@@ -32,6 +37,7 @@ LN_EPS = 1e-5   # nn.LayerNorm default
 
 FUSED_KEY = "algo.critic_fused_forward"
 TARGET_DTYPE_KEY = "algo.critic_target_dtype"
+FUSED_DX_KEY = "algo.critic_fused_dx"
 TARGET_DTYPES = ("float32", "bfloat16")
 
 
@@ -68,16 +74,25 @@ def check_target_bf16(dims, fused_forward, key=FUSED_KEY):
                          f"widest layer does not fit the LDS; set {TARGET_DTYPE_KEY}=float32")
 
 
+def check_fused_dx(fused_forward, key=FUSED_KEY):
+    """`algo.critic_fused_dx=True` without the one-launch forward: refused, never a silent per-layer run."""
+    if not fused_forward:
+        raise ValueError(f"{FUSED_DX_KEY}=True needs {key}=True: the one-launch input gradient reads the stash slab as the one-launch "
+                         f"forward lays it out (the per-layer forward keeps a tensor per layer)")
+
+
 class DoubleQLayerNorm(NormTwinQ):
     fused_key = FUSED_KEY   # the config key of this class's `fused_forward`, for its messages
 
-    def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False, target_dtype="float32"):
+    def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False, target_dtype="float32", fused_dx=False):
         dims = [_first(state_dim) + int(act_dim), *(HIDDEN_DEFAULT if hidden_layers is None else hidden_layers), 1]
         check_target_dtype_value(target_dtype)
         if fused_forward:   # before anything is allocated
             check_fused_forward(dims, self.fused_key)
         if target_dtype == "bfloat16":
             check_target_bf16(dims, fused_forward, self.fused_key)
+        if fused_dx:
+            check_fused_dx(fused_forward, self.fused_key)
         super().__init__(state_dim, act_dim, hidden_layers)
         self.fused = lnmlp_desc(self.dims) if fused_forward else None   # None: the per-layer forward, no fused state anywhere
         if self.fused is not None:   # the library's statement of the arena law is this module's
@@ -86,6 +101,7 @@ class DoubleQLayerNorm(NormTwinQ):
                 offs = [C.c_int64() for _ in range(3)]
                 L.check(L.lib.pqlk_lnmlp_offsets(C.byref(self.fused), l, *(C.byref(o) for o in offs)))
                 assert [o.value for o in offs] == [self.off.get((0, l, k), -1) for k in ("lin", "gamma", "beta")]
+        self.fused_dx_on = bool(fused_dx)   # backward_raw(grads=None, need_dx=True) is the one launch
         self._packed_fresh = False
         if target_dtype == "bfloat16":   # a buffer, so that it moves with the module; state_dict is the views' alone: never saved
             self.register_buffer("packed", torch.zeros(int(L.lib.pqlk_lnmlp_packed_bf16_elems(C.byref(self.fused))), dtype=torch.int16),
@@ -188,6 +204,33 @@ class DoubleQLayerNorm(NormTwinQ):
         if not stash:
             raise ValueError(f"forward_raw(stash=False) is the one-launch forward's: it needs {self.fused_key}=True")
         return self._q_of(self._forward_layers(x_pad))
+
+    @torch.no_grad()
+    def fused_dx(self, dq, out, col0=None, cols=None, tanh_of=None, r=0):
+        """The one launch back to the input, parameters frozen, on the slab of the LAST `forward_raw(x, stash=True)` on dq.shape[1] rows.
+        dq (2, M, 32): d loss / d Q (column 0).  Plain: out (M, >= ld(in)) <- d loss / d x summed over the nets, pad columns zero.
+        tanh_of (M, ld_a), with col0 and cols: out[:, :cols] <- the columns [col0, col0 + cols) times 1 - tanh_of^2; the rest of `out`
+        stays.  r: rows per block / 32 (0: the library's choice)."""
+        if self.fused is None:
+            check_fused_dx(False, self.fused_key)
+        M, dev = dq.shape[1], dq.device
+        ws = self._workspace(M, dev)
+        if tanh_of is None:
+            col0 = cols = ld_a = 0
+        else:
+            ld_a = tanh_of.stride(0)
+        with torch.cuda.device(dev):
+            L.check(L.lib.pqlk_lnmlp_dx(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(ws["stash"]), L.ptr(dq), M, L.ptr(out),
+                                        out.stride(0), int(col0), int(cols), L.ptr(tanh_of), ld_a, int(r), L.stream(dev)))
+        return out
+
+    @torch.no_grad()
+    def backward_raw(self, x_pad, dq, grads=None, need_dx=False):
+        """`NormTwinQ.backward_raw`; with `fused_dx` the frozen-parameter way back to the input is the one launch (the result is a
+        workspace tensor, valid until the next such call on as many rows)."""
+        if self.fused_dx_on and grads is None and need_dx:
+            return self.fused_dx(dq, self._workspace(x_pad.shape[0], x_pad.device)["dx0"][0])
+        return super().backward_raw(x_pad, dq, grads, need_dx)
 
     # ---- reference surface: no train / eval difference ----------------------------------------------------------
     def _heads(self, state, action):

@@ -1,0 +1,34 @@
+"""`algo.critic_fused_dx` without a GPU: what is refused names the key, and the default builds a critic with the switch off."""
+import pytest
+
+from support import cfg_of
+
+KEY = "algo.critic_fused_dx"
+LN = "algo.cri_class=DoubleQLayerNorm"
+FWD = "algo.critic_fused_forward=True"
+
+
+@pytest.mark.parametrize("extra", [(LN, f"{KEY}=True"), ("algo.cri_class=DoubleQDropoutLayerNorm", "algo.droq_fused_forward=True", f"{KEY}=True"),
+                                   ("algo.cri_class=DoubleQBroNet", f"{KEY}=True"), (f"{KEY}=True",), (LN, FWD, f"{KEY}=2")],
+                         ids=["no_fused_forward", "DroQ", "BroNet", "DoubleQ", "not_bool"])
+def test_refusals_name_the_key(extra):
+    from pql_amd.algo.critics import check_critic_class
+    with pytest.raises(ValueError, match=KEY.replace(".", r"\.")):
+        check_critic_class(cfg_of("ddpg_algo", *extra), agent=True)
+
+
+def test_the_switch_needs_the_fused_forward_and_names_both_keys():
+    from pql_amd.models.layernorm import DoubleQLayerNorm
+    with pytest.raises(ValueError, match=r"algo\.critic_fused_dx=True needs algo\.critic_fused_forward=True"):
+        DoubleQLayerNorm((8,), 2, [64, 32], fused_dx=True)
+
+
+def test_default_builds_the_switch_off():
+    from pql_amd.algo.critics import check_critic_class, critic_rules, structure_keys
+    from pql_amd.models.layernorm import DoubleQLayerNorm
+    cfg = cfg_of("ddpg_algo", LN)
+    check_critic_class(cfg, agent=True)
+    assert cfg.algo.critic_fused_dx is False and KEY not in structure_keys(cfg.algo)
+    kwargs = {arg: cfg.algo.get(key, default) for key, default, _, arg in critic_rules(cfg.algo).keys if arg}   # what make_critic passes
+    assert kwargs["fused_dx"] is False and DoubleQLayerNorm((8,), 2, **kwargs).fused_dx_on is False
+    assert DoubleQLayerNorm((8,), 2, [64, 32], fused_forward=True, fused_dx=True).fused_dx_on is True

@@ -21,6 +21,14 @@ launches of the same module on the same buffers (`drop=False`), and one `update_
 dropout forwards) with the key off, on, and on with a bf16 target.
 
     python tools/bench_lnmlp.py --droq --out profiles/droq_fused_bench.json
+
+`--dx`: the same protocol for the one-launch input gradient of the frozen critic (`algo.critic_fused_dx`, pqlk_lnmlp_dx,
+pql_amd/csrc/bwd_ln.hip) at hidden [512, 512, 256] and [1024]: on ONE stash, the per-layer `backward_raw(grads=None, need_dx=True)` with
+the torch add, and the copy (plain form, SAC) or the slice and tanh factor over 16 columns (tanh form, DDPG) that `_critic_dx` does
+without the key, against the one launch in both forms at 32 and, where it may, 64 rows per block; and one DDPG `update_once` with
+`algo.critic_fused_forward=True` and the key off and on.
+
+    python tools/bench_lnmlp.py --dx --out profiles/lnmlp_dx_bench.json
 """
 import argparse
 import json
@@ -39,6 +47,7 @@ from pql_amd import _lib as L  # noqa: E402
 
 O, A = 88, 16
 HIDDEN = {"default": [512, 512, 256], "small": [128, 128]}
+DX_HIDDEN = {"default": [512, 512, 256], "wide": [1024]}
 
 
 def forward_variants(dev, batch):
@@ -74,6 +83,59 @@ def droq_forward_variants(dev, batch, p=0.01):
             "drop_fused_stash": lambda: fus.forward_raw(x), "plain_fused_stash": lambda: fus.forward_raw(x, drop=False),
             "drop_fused_no_stash": lambda: fus.forward_raw(x, stash=False), "plain_fused_no_stash": lambda: fus.forward_raw(x, drop=False, stash=False),
             "drop_bf16_no_stash": lambda: b16.forward_raw(x, stash=False), "plain_bf16_no_stash": lambda: b16.forward_raw(x, drop=False, stash=False)}
+
+
+def dx_variants(dev, batch):
+    from pql_amd.models.layernorm import DoubleQLayerNorm
+    from pql_amd.models.mlp import pad_cols
+    out = {}
+    for name, hidden in DX_HIDDEN.items():
+        q = DoubleQLayerNorm((O,), A, hidden, fused_forward=True).to(dev)
+        x = pad_cols(torch.randn((batch, O + A), device=dev), L.ld(O + A))
+        dq = torch.zeros((2, batch, 32), device=dev)
+        dq[:, :, 0] = torch.randn((2, batch), device=dev)
+        a, dx, dz = torch.tanh(torch.randn((batch, L.ld(A)), device=dev)), torch.zeros_like(x), torch.zeros((batch, L.ld(A)), device=dev)
+        q.forward_raw(x)   # the one stash every variant reads
+
+        def per_plain(q=q, x=x, dq=dq, dx=dx):
+            dx.copy_(q.backward_raw(x, dq, grads=None, need_dx=True))
+
+        def per_tanh(q=q, x=x, dq=dq, a=a, dz=dz):
+            g = q.backward_raw(x, dq, grads=None, need_dx=True)
+            dz[:, :A] = g[:, O:O + A] * (1.0 - a[:, :A] * a[:, :A])
+
+        out[(name, "per_layer_plain")], out[(name, "per_layer_tanh")] = per_plain, per_tanh
+        for r in (1, 2) if max(hidden) <= 512 else (1,):
+            out[(name, f"fused_plain_r{r}")] = lambda q=q, dq=dq, dx=dx, r=r: q.fused_dx(dq, dx, r=r)
+            out[(name, f"fused_tanh_r{r}")] = lambda q=q, dq=dq, dz=dz, a=a, r=r: q.fused_dx(dq, dz, O, A, a, r=r)
+    return out
+
+
+def dx_main(a, dev):
+    fv = dx_variants(dev, a.batch)
+    agents = {(name, on): make_agent(hidden, True, a.batch, fused_dx=on) for name, hidden in DX_HIDDEN.items() for on in (False, True)}
+    ftimes, utimes = {k: [] for k in fv}, {k: [] for k in agents}
+    for r in range(a.rounds + 1):     # round 0 warms up
+        for k, fn in fv.items():
+            t = time_launches(fn, a.launches)
+            if r:
+                ftimes[k].append(t)
+        for k, (agent, memory) in agents.items():
+            t = time_updates(agent, memory, a.updates)
+            if r:
+                utimes[k].append(t)
+    res = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, rounds=a.rounds, launches=a.launches, updates=a.updates,
+               obs_dim=O, act_dim=A, batch=a.batch, dx=[], update_once=[])
+    for (name, what), ts in ftimes.items():
+        res["dx"].append(dict(hidden=DX_HIDDEN[name], what=what, us_median=round(statistics.median(ts), 2), us_min=round(min(ts), 2)))
+    for (name, on), ts in utimes.items():
+        res["update_once"].append(dict(hidden=DX_HIDDEN[name], critic_fused_forward=True, critic_fused_dx=on,
+                                       us_median=round(statistics.median(ts), 1), us_min=round(min(ts), 1)))
+    for rec in (*res["dx"], *res["update_once"]):
+        print(json.dumps(rec), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
 
 
 def make_droq_agent(fused, batch, target_dtype):
@@ -141,7 +203,7 @@ def time_launches(fn, n):
     return e0.elapsed_time(e1) / n * 1e3   # us per call
 
 
-def make_agent(hidden, fused, batch, target_dtype="float32"):
+def make_agent(hidden, fused, batch, target_dtype="float32", fused_dx=False):
     from pql_amd.algo.ddpg import AgentDDPG
     from pql_amd.envs.synthetic import create_task_env
     from pql_amd.replay.simple_replay import ReplayBuffer
@@ -149,7 +211,7 @@ def make_agent(hidden, fused, batch, target_dtype="float32"):
     rows = 4 * batch
     cfg = load_cfg(["algo=ddpg_algo", "task.name=AllegroHand", "num_envs=64", f"algo.batch_size={batch}", f"algo.memory_size={rows}",
                     "device=cuda:0", "sim_device=cuda:0", "algo.cri_class=DoubleQLayerNorm", f"algo.hidden_layers={hidden}",
-                    f"algo.critic_fused_forward={fused}", f"algo.critic_target_dtype={target_dtype}"])
+                    f"algo.critic_fused_forward={fused}", f"algo.critic_target_dtype={target_dtype}", f"algo.critic_fused_dx={fused_dx}"])
     agent = AgentDDPG(create_task_env(cfg), cfg)
     dev = agent.device
     memory = ReplayBuffer(rows, (O,), A, device=dev)
@@ -175,12 +237,15 @@ def main():
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--out", default=None)
     ap.add_argument("--droq", action="store_true", help="the DroQ critic's one-launch dropout forwards (see the module docstring)")
+    ap.add_argument("--dx", action="store_true", help="the one-launch input gradient of the frozen critic (see the module docstring)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_lnmlp needs a GPU"
     torch.manual_seed(0)
     dev = torch.device("cuda:0")
     if a.droq:
         return droq_main(a, dev)
+    if a.dx:
+        return dx_main(a, dev)
     fv = forward_variants(dev, a.batch)
     agents = {(name, fused, dt): make_agent(hidden, fused, a.batch, dt) for name, hidden in HIDDEN.items()
               for fused, dt in ((False, "float32"), (True, "float32"), (True, "bfloat16"))}
