@@ -1031,6 +1031,36 @@ int pqlk_lnmlp_forward(const PqlMlpDesc* d, const float* arena, const float* x, 
 int pqlk_lnmlp_dx(const PqlMlpDesc* d, const float* arena, const float* stash, const float* dq, int64_t m, float* dx, int64_t ld_dx,
                   int32_t col0, int32_t cols, const float* tanh_of, int64_t ld_a, int32_t r, pqlk_stream_t stream);
 
+/* Gradient form of the same chain (pql_amd/csrc/bwd_ln.hip; algo.critic_fused_backward): the critic's own update, which needs every
+ * parameter gradient and no dx.  The weight-gradient products dW, db stay on the one-layer backward GEMMs (pqlk_mlp_backward with
+ * dx == NULL); everything else of the per-layer backward -- per net H norm backwards of two launches each and H dX products -- is ONE
+ * chain launch and ONE small fold launch.  Same descriptor, same arena, same stash slab as pqlk_lnmlp_dx; nothing of either is written.
+ *
+ * The law, per net n and batch row: pqlk_lnmlp_dx's, operation for operation, from the output layer down to dz of hidden layer 0
+ * (layer 0's product is not formed), so dz_l has pqlk_lnmlp_dx's bits.  dz of (n, l) is written to a matrix (m, dims[l+1]) in the
+ * workspace -- the dy of that layer's weight-gradient GEMM -- and, down the columns, with g and xhat of the law:
+ *   dbeta_j = sum_r g_rj,   dgamma_j = sum_r g_rj * xhat_rj          (g * xhat one rounding, then the addition)
+ * Summation order (fixed: no float atomics, no ticket, no wait between blocks).  The unit is a tile of 32 consecutive rows, tile t =
+ * rows 32 t .. 32 t + 31: wave w (of 8) adds rows w, w + 8, w + 16, w + 24 of the tile in row order starting from 0, the 8 waves are
+ * added in wave order ((w0 + w1) + w2) + ..., and the tile's two rows go to the workspace, part[net][layer][tile][{0: dbeta, 1:
+ * dgamma}][dims[l+1]].  The fold launch adds the ceil(m / 32) tile rows in pqlk_ln_elu_backward's grouping: 16 groups of
+ * ceil(tiles / 16) consecutive tiles, each in tile order starting from 0, then the groups in group order; it writes dgamma / dbeta into
+ * the gamma / beta slots of `grads`, a tensor laid out like the arena.  Nothing else of `grads` is written (the Linear slots are the
+ * GEMMs').  Rows >= m are neither read nor written and contribute nothing.  The bits of dz, dgamma and dbeta depend on m alone, not on r.
+ *
+ * Workspace: pqlk_lnmlp_grad_ws_floats(d, m) floats (0: not eligible, or m out of range): the dz matrices of every net and hidden
+ * layer, then the partial rows.  pqlk_lnmlp_grad_offset: where dz of (net, layer) starts and its row stride dims[layer+1]; every offset
+ * is a multiple of 4.  The workspace aliases nothing the launch reads.
+ * r: as for pqlk_lnmlp_dx (2 where a 64-row image of the widest HIDDEN layer and the table of 2 x that width fit 160 KB of LDS and no
+ * hidden layer is wider than 512; the input width does not count: it bounds eligibility alone).
+ * Errors, before any launch: PQLK_E_NULL (d, arena, stash, dq, ws, grads; an out-pointer of the query); PQLK_E_SHAPE for a descriptor
+ * pqlk_lnmlp_ok refuses, m <= 0, m >= 2^30, an r that is not allowed, ws_floats below pqlk_lnmlp_grad_ws_floats(d, m); PQLK_E_RANGE for
+ * the query's net or layer out of range; PQLK_E_ALIGN for a pointer that is not 16-B aligned. */
+int64_t pqlk_lnmlp_grad_ws_floats(const PqlMlpDesc* d, int64_t m);
+int pqlk_lnmlp_grad_offset(const PqlMlpDesc* d, int64_t m, int32_t net, int32_t layer, int64_t* off, int64_t* ld);
+int pqlk_lnmlp_grad_chain(const PqlMlpDesc* d, const float* arena, const float* stash, const float* dq, int64_t m, float* ws,
+                          int64_t ws_floats, float* grads, int32_t r, pqlk_stream_t stream);
+
 /* Forward-only bf16-MFMA form of the same stack (pql_amd/csrc/fwd_ln_bf16.hip; algo.critic_target_dtype=bfloat16): the target
  * critic's forward, through which nothing goes back.  Same descriptor, same arena; no stash.  The bf16 LayerNorm law, per net and
  * batch row (RNE = round to nearest even, ties included; NaN stays NaN, overflow goes to +-inf):

@@ -8,7 +8,8 @@ import torch
 from pql_amd.models import model_name_to_path
 from pql_amd.models.bronet import BRO_FUSED_KEY, check_blocks, check_bool_bro_fused, check_bro_fused, check_bro_target_bf16, check_width
 from pql_amd.models.droq import DROQ_FUSED_KEY, check_dropout
-from pql_amd.models.layernorm import FUSED_DX_KEY, FUSED_KEY, TARGET_DTYPE_KEY, check_fused_dx, check_fused_forward, check_target_bf16, check_target_dtype_value
+from pql_amd.models.layernorm import (FUSED_BACKWARD_KEY, FUSED_DX_KEY, FUSED_KEY, TARGET_DTYPE_KEY, check_fused_backward, check_fused_dx,
+                                      check_fused_forward, check_target_bf16, check_target_dtype_value)
 from pql_amd.models.mlp import HIDDEN_DEFAULT, check_num_atoms, check_num_quantiles
 from pql_amd.replay.prioritized_replay import per_cfg, per_refresh
 from pql_amd.utils.common import load_class_from_path
@@ -46,6 +47,11 @@ def check_bool_fused_dx(v):
         raise ValueError(f"{FUSED_DX_KEY} must be True or False, got {v!r}")
 
 
+def check_bool_fused_backward(v):
+    if not isinstance(v, bool):
+        raise ValueError(f"{FUSED_BACKWARD_KEY} must be True or False, got {v!r}")
+
+
 def check_bool_droq_fused(v):
     if not isinstance(v, bool):
         raise ValueError(f"{DROQ_FUSED_KEY} must be True or False, got {v!r}")
@@ -65,7 +71,8 @@ TABLE = {r.name: r for r in (
     Rules("DoubleQLayerNorm", "the LayerNorm critic has no C51 head", fused=False, algos="algo=ddpg_algo / algo=sac_algo",
           keys=(HIDDEN, ("critic_fused_forward", False, check_bool_fused, "fused_forward"),   # (launch choices: no structure keys)
                 ("critic_target_dtype", "float32", check_target_dtype_value, "target_dtype"),
-                ("critic_fused_dx", False, check_bool_fused_dx, "fused_dx"))),
+                ("critic_fused_dx", False, check_bool_fused_dx, "fused_dx"),
+                ("critic_fused_backward", False, check_bool_fused_backward, "fused_backward"))),
     Rules("DoubleQDropoutLayerNorm", "the dropout LayerNorm critic has no C51 head", fused=False, refuses={"CrossQ": NO_CROSSQ},
           algos="algo=droq_algo / algo=sac_algo / algo=ddpg_algo",
           keys=(("critic_dropout", 0.01, check_dropout, "dropout"), HIDDEN,
@@ -147,6 +154,13 @@ def check_critic_class(cfg, fused_learner=None, agent=False):
                          f"Linear -> LayerNorm -> ELU stack (DroQ's mask and BroNet's skip are not in that kernel)")
     if fused_dx:
         check_fused_dx(bool(algo.get("critic_fused_forward")))
+    fused_bwd = algo.get("critic_fused_backward", False)
+    check_bool_fused_backward(fused_bwd)
+    if fused_bwd and r.name != "DoubleQLayerNorm":
+        raise ValueError(f"{FUSED_BACKWARD_KEY}=True is not supported with {where}: the one-launch gradient chain is DoubleQLayerNorm's plain "
+                         f"Linear -> LayerNorm -> ELU stack (DroQ's mask and BroNet's skip are not in that kernel)")
+    if fused_bwd:
+        check_fused_backward(bool(algo.get("critic_fused_forward")))
     if algo.get("bronet_fused_forward") and r.name != "DoubleQBroNet":
         raise ValueError(f"{BRO_FUSED_KEY}=True is not supported with {where}: the one-launch residual forward is DoubleQBroNet's stack "
                          f"(stem, blocks with a skip, output); {FUSED_KEY} is DoubleQLayerNorm's")

@@ -2,7 +2,8 @@
 // of DDPG and SAC): ONE launch walks back through both nets and every layer, dq -> d sum_n(dq_n Q_n) / dx, from the stash slab that
 // pqlk_lnmlp_forward wrote and the arena as it lies.  No weight gradient, no column sum: nothing crosses batch rows.  The per-layer
 // form (a row launch of ln.hip and a one-layer backward GEMM per net and layer, a torch add of the nets, a torch slice and tanh
-// factor) stays what it was; no existing kernel is touched.  The law is written op by op in include/pqlk.h.
+// factor) stays what it was; no existing kernel is touched.  The law is written op by op in include/pqlk.h.  (The gradient form of the
+// chain, for the critic's own update -- dz to HBM, column sums, no layer-0 product -- is the second half of this file.)
 //
 // Work split: a block of 8 waves owns 32 * R batch rows through the whole chain and through BOTH nets, one after the other; the
 // current gradient sits in ONE fp32 LDS image [row][feature], the forward's (lnmlp.h: row length = widest layer + 4 floats).
@@ -307,6 +308,265 @@ extern "C" int pqlk_lnmlp_dx(const PqlMlpDesc* desc, const float* arena, const f
   else if (rr == 2) hipLaunchKernelGGL((k_lnmlp_dx<2, false>), grid, block, lm_lds_bytes(d, 2), s, p);
   else if (tanh_of) hipLaunchKernelGGL((k_lnmlp_dx<1, true>), grid, block, lm_lds_bytes(d, 1), s, p);
   else hipLaunchKernelGGL((k_lnmlp_dx<1, false>), grid, block, lm_lds_bytes(d, 1), s, p);
+  PQLK_LAUNCH_CHECK();
+  return PQLK_OK;
+}
+
+// ---- the gradient form: the chain of the critic's own update (pqlk_lnmlp_grad_chain; DoubleQLayerNorm with algo.critic_fused_backward)
+// The same block, the same image, the same norm step and hidden-layer products -- dz of every (net, hidden layer) has k_lnmlp_dx's
+// bits -- with three differences.  No layer-0 product: the update needs no dx, the chain ends behind layer 0's norm step, so the image
+// row is the widest HIDDEN layer + LM_PAD.  dz goes to HBM too, a matrix (m, dims[l + 1]) per net and layer in the workspace: the dy
+// operand of the weight-gradient GEMMs, which stay what they are.  And the norm step forms the column sums dbeta_j = sum_r g_rj,
+// dgamma_j = sum_r g_rj xhat_rj from the g and xhat it holds anyway.  Their unit is a 32-row tile, whatever R: wave w adds rows w, w + 8,
+// w + 16, w + 24 of the tile in row order in 2 VPL registers per lane; the 8 waves are then added in wave order through ONE table of
+// 2 N floats behind the image (wave 0 stores, wave 1 .. 6 add to it, wave 7 adds and stores the tile's partial row to the workspace,
+// part[net][layer][tile][{0: dbeta, 1: dgamma}][N], in the map's vector stores).  k_lnmlp_grad_fold, a second launch for every net and
+// layer at once, adds the ceil(m / 32) tile rows as k_ln_fold of ln.hip does.  No float atomics, no ticket, no cross-block wait.
+struct LnGradP {
+  LnDxP c;   // the chain's arguments (dx, tanh_of, ld_dx, ld_a, col0, cols unused; ld = widest hidden layer + LM_PAD)
+  float* ws;
+  float* grads;
+  int64_t dz_off[2][PQLK_MAX_LAYERS], part_off[2][PQLK_MAX_LAYERS];   // in ws, per net and hidden layer
+  int64_t b_off[PQLK_MAX_LAYERS];                                     // beta inside a net (gamma: c.g_off)
+  int tab, tiles;                                                     // floats from the image's start to the table; ceil(m / 32)
+};
+
+// ld_norm over the block's `tiles` 32-row tiles, with dz also stored to its matrix and the tile's column sums to its partial row.
+// Every wave reaches every barrier: the tile loop's bounds are block-uniform.
+template <int VPL>
+__device__ __forceinline__ void ld_norm_sums(float* img, int ld, int cols, int tiles, long long row0, int m, const float* __restrict__ gamma,
+                                             const float* __restrict__ y, const float* __restrict__ z, const float* __restrict__ mean,
+                                             const float* __restrict__ rstd, float* __restrict__ dz, float* tab, float* __restrict__ part,
+                                             int wave, int lane) {
+  using M = LnMap<VPL, true>;
+  float ga[VPL];
+  ln_load<VPL, true>(gamma, cols, lane, ga);
+  const float n = (float)cols;
+  for (int t = 0; t < tiles; ++t) {
+    const long long trow = row0 + 32 * t;
+    if (trow >= m) break;   // (block-uniform) a tile past m: no rows, no partial row
+    float accb[VPL], accg[VPL];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) accb[i] = accg[i] = 0.f;
+    for (int rr = wave; rr < 32; rr += LM_NW) {
+      const long long row = trow + rr;
+      if (row >= m) break;
+      float* ir = img + (32 * t + rr) * ld;
+      const float mu = mean[row], rs = rstd[row];
+      float h[VPL], xh[VPL], yv[VPL];
+      ln_load<VPL, true>(ir, cols, lane, h);
+      ln_load<VPL, true>(y + row * cols, cols, lane, yv);
+      ln_load<VPL, true>(z + row * cols, cols, lane, xh);
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        const bool in = M::col(i, lane) < cols;
+        const float g = in ? h[i] * (yv[i] > 0.f ? 1.f : yv[i] + 1.f) : 0.f;
+        const float x = in ? (xh[i] - mu) * rs : 0.f;
+        const float hh = g * ga[i];
+        accb[i] += g; accg[i] += g * x;
+        s1 += hh;
+        s2 += hh * x;
+        h[i] = hh; xh[i] = x;
+      }
+      const float c1 = wave_sum(s1) / n, c2 = wave_sum(s2) / n;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) h[i] = rs * (h[i] - c1 - xh[i] * c2);
+      ln_store<VPL, true>(ir, cols, lane, h);
+      ln_store<VPL, true>(dz + row * cols, cols, lane, h);
+    }
+    float* pr = part + (trow >> 5) * (2 * cols);
+#pragma unroll
+    for (int w = 0; w < LM_NW; ++w) {
+      if (wave == w) {
+        if (w > 0) {
+          float tb[VPL], tg[VPL];
+          ln_load<VPL, true>(tab, cols, lane, tb);
+          ln_load<VPL, true>(tab + cols, cols, lane, tg);
+#pragma unroll
+          for (int i = 0; i < VPL; ++i) { accb[i] = tb[i] + accb[i]; accg[i] = tg[i] + accg[i]; }
+        }
+        float* o = w < LM_NW - 1 ? tab : pr;
+        ln_store<VPL, true>(o, cols, lane, accb);
+        ln_store<VPL, true>(o + cols, cols, lane, accg);
+      }
+      __syncthreads();   // the table is wave w + 1's; behind the last one it is free again and the tile's dz is complete
+    }
+  }
+}
+
+template <int R>
+__global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_grad(LnGradP q) {
+  constexpr int NTW_MAX = R == 2 ? 2 : 4;
+  const LnDxP& p = q.c;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int H = p.n_layers - 1, ld = p.ld;
+  const long long row0 = (long long)blockIdx.x * (32 * R);
+  float* img = reinterpret_cast<float*>(ld_sm);
+  float* tab = img + q.tab;
+  for (int net = 0; net < p.n_nets; ++net) {
+    const float* prm = p.arena + (long long)net * p.net_stride;
+    const float* sb = p.stash + (long long)net * p.stash_net_stride;
+    const float* dq = p.dq + (long long)net * p.m * 32;
+    // the output layer: d[j] = dq * w_out[j]; rows past m become zero (the previous net's last norm step ended behind a barrier)
+    {
+      const int N = p.dims[H], qpr = N >> 2;
+      const float* wout = prm + p.w_off[H];
+      for (int i = tid; i < 32 * R * qpr; i += 64 * LM_NW) {
+        const int row = i / qpr, c = (i - row * qpr) << 2;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row0 + row < p.m) {
+          const float d = dq[(row0 + row) * 32];
+          const float4 w4 = *reinterpret_cast<const float4*>(wout + c);
+          v = make_float4(d * w4.x, d * w4.y, d * w4.z, d * w4.w);
+        }
+        *reinterpret_cast<float4*>(img + row * ld + c) = v;
+      }
+    }
+    __syncthreads();
+    for (int l = H - 1; l >= 0; --l) {
+      const int K = p.dims[l], N = p.dims[l + 1];
+      const float* ga = prm + p.g_off[l];
+#define LD_NORM_SUMS(VPL)                                                                                                            \
+  ld_norm_sums<VPL>(img, ld, N, R, row0, p.m, ga, sb + p.y_off[l], sb + p.z_off[l], sb + p.mean_off[l], sb + p.rstd_off[l],           \
+                    q.ws + q.dz_off[net][l], tab, q.ws + q.part_off[net][l], wave, lane)
+      if (N <= 128) LD_NORM_SUMS(2);
+      else if (N <= 256) LD_NORM_SUMS(4);
+      else if (R == 2 || N <= 512) LD_NORM_SUMS(8);
+      else if constexpr (R == 1) LD_NORM_SUMS(16);
+#undef LD_NORM_SUMS
+      if (l == 0) break;   // no layer-0 product: the update needs no dx
+      const int T = K >> 5;   // (a hidden layer's width is a multiple of 32)
+      const int ntw = min((T + LM_NW - 1) / LM_NW, NTW_MAX);   // (block-uniform)
+      const float* W = prm + p.w_off[l];
+#define LD_PRODUCT(NTW) ld_product<R, NTW, false, false>(W, K, N >> 3, img, ld, 0, T, wave, lane, p, row0, false, false)
+      if (ntw == 1) LD_PRODUCT(1);
+      else if (ntw == 2) LD_PRODUCT(2);
+      else if constexpr (R == 1) {
+        if (ntw == 3) LD_PRODUCT(3);
+        else LD_PRODUCT(4);
+      }
+#undef LD_PRODUCT
+    }
+  }
+}
+
+// dgamma, dbeta of every net and hidden layer <- the tile rows, in k_ln_fold's order: 16 columns x 16 groups of consecutive tiles per
+// block, each group in tile order, then the groups in group order.  blockIdx.y: 0 -> dbeta, 1 -> dgamma; blockIdx.z: net * H + layer.
+constexpr int LN_GRAD_FOLD_GROUPS = 16;
+__global__ __launch_bounds__(256) void k_lnmlp_grad_fold(LnGradP q) {
+  __shared__ float sh[LN_GRAD_FOLD_GROUPS][16];
+  const int H = q.c.n_layers - 1, net = blockIdx.z / H, l = blockIdx.z - net * H;
+  const int cols = q.c.dims[l + 1];
+  if ((int)blockIdx.x * 16 >= cols) return;   // (uniform over the block) a narrower layer than the widest
+  const int cl = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl, which = blockIdx.y;   // (c < cols: a multiple of 32)
+  const float* part = q.ws + q.part_off[net][l];
+  const int per = (q.tiles + LN_GRAD_FOLD_GROUPS - 1) / LN_GRAD_FOLD_GROUPS;
+  const int k0 = g * per, k1 = min(q.tiles, k0 + per);
+  float s = 0.f;
+  for (int k = k0; k < k1; ++k) s += part[((int64_t)k * 2 + which) * cols + c];
+  sh[g][cl] = s;
+  __syncthreads();
+  if (g == 0) {
+    float t = sh[0][cl];
+#pragma unroll
+    for (int j = 1; j < LN_GRAD_FOLD_GROUPS; ++j) t += sh[j][cl];
+    q.grads[(int64_t)net * q.c.net_stride + (which ? q.c.g_off[l] : q.b_off[l]) + c] = t;
+  }
+}
+
+// ---- host side of the gradient form
+static int lg_widest(const LmLayout* d) {
+  int w = 0;
+  for (int l = 1; l < d->n_layers; ++l) w = w > d->dims[l] ? w : d->dims[l];
+  return w;
+}
+static size_t lg_lds_bytes(const LmLayout* d, int r) { return ((size_t)32 * r * (lg_widest(d) + LM_PAD) + 2 * lg_widest(d)) * sizeof(float); }
+static bool lg_r2_ok(const LmLayout* d) { return lg_lds_bytes(d, 2) <= (size_t)LM_LDS_MAX && lg_widest(d) <= LM_MAX_R2_WIDTH; }
+static int64_t lg_tiles(int64_t m) { return (m + 31) / 32; }
+
+// the workspace: dz (m, dims[l + 1]) of every net and hidden layer, net after net, then the partial rows (tiles, 2, dims[l + 1]) in
+// the same order.  Every width is a multiple of 32, so every offset is a multiple of 4.
+static int64_t lg_ws_floats(const LmLayout* d, int64_t m) {
+  int64_t o = 0;
+  for (int l = 1; l < d->n_layers; ++l) o += (m + 2 * lg_tiles(m)) * d->dims[l];
+  return o * d->n_nets;
+}
+static void lg_at(const LmLayout* d, int64_t m, int net, int layer, int64_t* dz_off, int64_t* part_off) {
+  int64_t per_net = 0, before = 0;
+  for (int l = 1; l < d->n_layers; ++l) {
+    if (l - 1 < layer) before += d->dims[l];
+    per_net += d->dims[l];
+  }
+  *dz_off = m * (net * per_net + before);
+  *part_off = m * d->n_nets * per_net + 2 * lg_tiles(m) * (net * per_net + before);
+}
+
+extern "C" int64_t pqlk_lnmlp_grad_ws_floats(const PqlMlpDesc* desc, int64_t m) {
+  LmLayout d;
+  return desc && lm_layout(desc, &d) && m > 0 && m < (1LL << 30) ? lg_ws_floats(&d, m) : 0;
+}
+
+extern "C" int pqlk_lnmlp_grad_offset(const PqlMlpDesc* desc, int64_t m, int32_t net, int32_t layer, int64_t* off, int64_t* ld) {
+  PQLK_REQUIRE(desc && off && ld, PQLK_E_NULL);
+  LmLayout d;
+  PQLK_REQUIRE(lm_layout(desc, &d) && m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
+  PQLK_REQUIRE(net >= 0 && net < d.n_nets && layer >= 0 && layer < d.n_layers - 1, PQLK_E_RANGE);
+  int64_t unused;
+  lg_at(&d, m, net, layer, off, &unused);
+  *ld = d.dims[layer + 1];
+  return PQLK_OK;
+}
+
+extern "C" int pqlk_lnmlp_grad_chain(const PqlMlpDesc* desc, const float* arena, const float* stash, const float* dq, int64_t m, float* ws,
+                                     int64_t ws_floats, float* grads, int32_t r, pqlk_stream_t stream) {
+  PQLK_REQUIRE(desc && arena && stash && dq && ws && grads, PQLK_E_NULL);
+  LmLayout lay;
+  PQLK_REQUIRE(lm_layout(desc, &lay) && lay.n_nets <= 2 && m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
+  const LmLayout* d = &lay;
+  const int L = d->n_layers;
+  const bool r2_ok = lg_r2_ok(d);
+  PQLK_REQUIRE(r == 0 || r == 1 || (r == 2 && r2_ok), PQLK_E_SHAPE);
+  PQLK_REQUIRE(ws_floats >= lg_ws_floats(d, m), PQLK_E_SHAPE);
+  PQLK_REQUIRE(pqlk_aligned16(arena) && pqlk_aligned16(stash) && pqlk_aligned16(dq) && pqlk_aligned16(ws) && pqlk_aligned16(grads),
+               PQLK_E_ALIGN);
+  LnGradP q = {};
+  LnDxP& p = q.c;
+  p.arena = arena; p.stash = stash; p.dq = dq;
+  p.net_stride = d->net_stride; p.stash_net_stride = lm_stash_net_floats(d, m);
+  p.n_layers = L; p.n_nets = d->n_nets; p.m = (int)m; p.ld = lg_widest(d) + LM_PAD;
+  q.ws = ws; q.grads = grads; q.tiles = (int)lg_tiles(m);
+  for (int l = 0; l <= L; ++l) p.dims[l] = d->dims[l];
+  for (int l = 0; l < L; ++l) {
+    p.w_off[l] = d->lin_off[l];
+    if (l == L - 1) break;
+    p.g_off[l] = d->gamma_off[l]; q.b_off[l] = d->beta_off[l];
+    int64_t unused;
+    lm_stash_at(d, m, l, PQLK_LNMLP_Z, &p.z_off[l], &unused);
+    lm_stash_at(d, m, l, PQLK_LNMLP_Y, &p.y_off[l], &unused);
+    lm_stash_at(d, m, l, PQLK_LNMLP_MEAN, &p.mean_off[l], &unused);
+    lm_stash_at(d, m, l, PQLK_LNMLP_RSTD, &p.rstd_off[l], &unused);
+    for (int n = 0; n < d->n_nets; ++n) lg_at(d, m, n, l, &q.dz_off[n][l], &q.part_off[n][l]);
+  }
+  static PqlkPerDeviceOnce attr_once;
+  if (int arc = attr_once.run([&] {
+        const void* ks[2] = {reinterpret_cast<const void*>(&k_lnmlp_grad<1>), reinterpret_cast<const void*>(&k_lnmlp_grad<2>)};
+        for (const void* k : ks) {
+          hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_MAX);
+          if (err != hipSuccess) return -(int)err;
+        }
+        return 0;
+      }))
+    return arc;
+  const int rr = r ? r : ld_choose_r(r2_ok, m);
+  q.tab = 32 * rr * p.ld;
+  dim3 grid((unsigned)((m + 32 * rr - 1) / (32 * rr))), block(64 * LM_NW);
+  hipStream_t s = pqlk_s(stream);
+  if (rr == 2) hipLaunchKernelGGL((k_lnmlp_grad<2>), grid, block, lg_lds_bytes(d, 2), s, q);
+  else hipLaunchKernelGGL((k_lnmlp_grad<1>), grid, block, lg_lds_bytes(d, 1), s, q);
+  PQLK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_lnmlp_grad_fold, dim3((unsigned)((lg_widest(d) + 15) / 16), 2, (unsigned)(d->n_nets * (L - 1))), dim3(256), 0, s, q);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }

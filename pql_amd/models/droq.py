@@ -47,8 +47,12 @@ def check_dropout(p):
 class DoubleQDropoutLayerNorm(DoubleQLayerNorm):
     fused_key = DROQ_FUSED_KEY
 
-    def __init__(self, state_dim, act_dim, hidden_layers=None, dropout=0.01, seed=None, fused_forward=False, target_dtype="float32"):
+    def __init__(self, state_dim, act_dim, hidden_layers=None, dropout=0.01, seed=None, fused_forward=False, target_dtype="float32",
+                 fused_backward=False):
         p = check_dropout(dropout)   # before anything is allocated
+        if fused_backward:
+            raise ValueError("DoubleQDropoutLayerNorm has no one-launch gradient chain: the mask is not in pqlk_lnmlp_grad_chain's row step "
+                             "(algo.critic_fused_backward is DoubleQLayerNorm's)")
         super().__init__(state_dim, act_dim, hidden_layers, fused_forward, target_dtype)
         self.dropout = p
         if self.n_layers - 1 > MAX_DROP_LAYERS:

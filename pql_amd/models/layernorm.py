@@ -21,6 +21,12 @@ with a stash stays the fp32 launch.
 step's `backward_raw(grads=None, need_dx=True)` -- is ONE launch for both nets and every layer, `pqlk_lnmlp_dx`
 (pql_amd/csrc/bwd_ln.hip, the law in include/pqlk.h), reading the slab the last stash forward wrote; `fused_dx(...)` is that call, in
 its plain form or through the actor's tanh.  A backward that forms parameter gradients stays the per-layer one.  No part of a checkpoint.
+
+`fused_backward=True` (`algo.critic_fused_backward`, with `fused_forward` only): the critic's own update,
+`backward_raw(grads=<tensor>, need_dx=False)`, is ONE `pqlk_lnmlp_grad_chain` call -- a chain launch that leaves dz of every net and
+hidden layer in the workspace slab `ws["grad_ws"]` and the column sums of dgamma / dbeta per 32-row tile, and a fold launch that
+writes dgamma / dbeta into `grads` (pql_amd/csrc/bwd_ln.hip, the law in include/pqlk.h) -- and then the 2 (H + 1) weight-gradient
+GEMMs `mlp_backward_raw(..., dx=None)` on those dz: no per-layer norm backward, no dX product.  No part of a checkpoint.
 """
 from __future__ import annotations
 
@@ -29,7 +35,7 @@ import ctypes as C
 import torch
 
 from pql_amd import _lib as L
-from pql_amd.models.mlp import HIDDEN_DEFAULT, _first
+from pql_amd.models.mlp import HIDDEN_DEFAULT, _first, mlp_backward_raw
 from pql_amd.models.normq import NormTwinQ
 
 LN_EPS = 1e-5   # nn.LayerNorm default
@@ -38,6 +44,7 @@ LN_EPS = 1e-5   # nn.LayerNorm default
 FUSED_KEY = "algo.critic_fused_forward"
 TARGET_DTYPE_KEY = "algo.critic_target_dtype"
 FUSED_DX_KEY = "algo.critic_fused_dx"
+FUSED_BACKWARD_KEY = "algo.critic_fused_backward"
 TARGET_DTYPES = ("float32", "bfloat16")
 
 
@@ -81,10 +88,19 @@ def check_fused_dx(fused_forward, key=FUSED_KEY):
                          f"forward lays it out (the per-layer forward keeps a tensor per layer)")
 
 
+def check_fused_backward(fused_forward, key=FUSED_KEY):
+    """`algo.critic_fused_backward=True` without the one-launch forward: refused, never a silent per-layer run."""
+    if not fused_forward:
+        raise ValueError(f"{FUSED_BACKWARD_KEY}=True needs {key}=True: the one-launch gradient chain reads the stash slab as the one-launch "
+                         f"forward lays it out (the per-layer forward keeps a tensor per layer)")
+
+
 class DoubleQLayerNorm(NormTwinQ):
     fused_key = FUSED_KEY   # the config key of this class's `fused_forward`, for its messages
+    grad_r = 0              # rows per block / 32 of the gradient chain's launch (0: the library's choice; a knob for measurements)
 
-    def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False, target_dtype="float32", fused_dx=False):
+    def __init__(self, state_dim, act_dim, hidden_layers=None, fused_forward=False, target_dtype="float32", fused_dx=False,
+                 fused_backward=False):
         dims = [_first(state_dim) + int(act_dim), *(HIDDEN_DEFAULT if hidden_layers is None else hidden_layers), 1]
         check_target_dtype_value(target_dtype)
         if fused_forward:   # before anything is allocated
@@ -93,6 +109,8 @@ class DoubleQLayerNorm(NormTwinQ):
             check_target_bf16(dims, fused_forward, self.fused_key)
         if fused_dx:
             check_fused_dx(fused_forward, self.fused_key)
+        if fused_backward:
+            check_fused_backward(fused_forward, self.fused_key)
         super().__init__(state_dim, act_dim, hidden_layers)
         self.fused = lnmlp_desc(self.dims) if fused_forward else None   # None: the per-layer forward, no fused state anywhere
         if self.fused is not None:   # the library's statement of the arena law is this module's
@@ -102,6 +120,7 @@ class DoubleQLayerNorm(NormTwinQ):
                 L.check(L.lib.pqlk_lnmlp_offsets(C.byref(self.fused), l, *(C.byref(o) for o in offs)))
                 assert [o.value for o in offs] == [self.off.get((0, l, k), -1) for k in ("lin", "gamma", "beta")]
         self.fused_dx_on = bool(fused_dx)   # backward_raw(grads=None, need_dx=True) is the one launch
+        self.fused_backward_on = bool(fused_backward)   # backward_raw(grads=<tensor>, need_dx=False) is the chain call + the dW GEMMs
         self._packed_fresh = False
         if target_dtype == "bfloat16":   # a buffer, so that it moves with the module; state_dict is the views' alone: never saved
             self.register_buffer("packed", torch.zeros(int(L.lib.pqlk_lnmlp_packed_bf16_elems(C.byref(self.fused))), dtype=torch.int16),
@@ -153,6 +172,14 @@ class DoubleQLayerNorm(NormTwinQ):
                 ws["z"][(n, l)], ws["y"][(n, l)] = view(n, l, L.LNMLP_Z, M, w), view(n, l, L.LNMLP_Y, M, w)
                 ws["mean"][(n, l)], ws["rstd"][(n, l)] = view(n, l, L.LNMLP_MEAN, M), view(n, l, L.LNMLP_RSTD, M)
             ws["z"][(n, H)] = ws["q"][n]
+        if self.fused_backward_on:   # dz of every (net, hidden layer) and the tiles' partial rows, laid out by `pqlk_lnmlp_grad_offset`
+            gw = ws["grad_ws"] = torch.zeros(int(L.lib.pqlk_lnmlp_grad_ws_floats(C.byref(d), M)), **f)
+            ws["dz"] = {}
+            for n in range(2):
+                for l in range(H):
+                    off, ld = C.c_int64(), C.c_int64()
+                    L.check(L.lib.pqlk_lnmlp_grad_offset(C.byref(d), M, n, l, C.byref(off), C.byref(ld)))
+                    ws["dz"][(n, l)] = gw[off.value: off.value + M * ld.value].view(M, ld.value)
 
     def _norm_forward(self, ws, n, l, z, y, M, st):
         L.check(L.lib.pqlk_ln_elu_forward(L.ptr(z), z.stride(0), M, self.dims[l + 1], L.ptr(self.norm_param(n, l, "gamma")),
@@ -225,9 +252,38 @@ class DoubleQLayerNorm(NormTwinQ):
         return out
 
     @torch.no_grad()
+    def fused_grad_chain(self, dq, grads, r=0):
+        """`pqlk_lnmlp_grad_chain` on the slab of the LAST `forward_raw(x, stash=True)` on dq.shape[1] rows: dz of every net and hidden
+        layer into `ws["dz"]`, dgamma / dbeta into their slots of `grads` (laid out like the arena; nothing else of it is written).
+        r: rows per block / 32 (0: the library's choice)."""
+        if not self.fused_backward_on:
+            raise ValueError(f"fused_grad_chain is the one-launch gradient chain's: it needs {FUSED_BACKWARD_KEY}=True")
+        M, dev = dq.shape[1], dq.device
+        ws = self._workspace(M, dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib.pqlk_lnmlp_grad_chain(C.byref(self.fused), L.ptr(self.arena.data), L.ptr(ws["stash"]), L.ptr(dq), M,
+                                                L.ptr(ws["grad_ws"]), ws["grad_ws"].numel(), L.ptr(grads), int(r), L.stream(dev)))
+        return ws["dz"]
+
+    def _fused_backward(self, x_pad, dq, grads):
+        """The critic's own update: the chain call, then the weight-gradient GEMMs of every layer on its dz (no dX product anywhere)."""
+        M, H = x_pad.shape[0], self.n_layers - 1
+        ws = self._workspace(M, x_pad.device)
+        dz = self.fused_grad_chain(dq, grads, self.grad_r)
+        arena = self.arena.data
+        for n in range(2):
+            for l in range(H, -1, -1):
+                o = self.off[(n, l, "lin")]
+                mlp_backward_raw(self.lin[l], arena[o:], x_pad if l == 0 else ws["y"][(n, l - 1)], ws["z"][(n, l)],
+                                 dq[n] if l == H else dz[(n, l)], ws["bwd"], grads[o:], ws["splits"], None, rows=M)
+
+    @torch.no_grad()
     def backward_raw(self, x_pad, dq, grads=None, need_dx=False):
         """`NormTwinQ.backward_raw`; with `fused_dx` the frozen-parameter way back to the input is the one launch (the result is a
-        workspace tensor, valid until the next such call on as many rows)."""
+        workspace tensor, valid until the next such call on as many rows); with `fused_backward` the update's parameter gradient
+        (grads given, no dx wanted) is the chain call and the weight-gradient GEMMs."""
+        if self.fused_backward_on and grads is not None and not need_dx:
+            return self._fused_backward(x_pad, dq, grads)
         if self.fused_dx_on and grads is None and need_dx:
             return self.fused_dx(dq, self._workspace(x_pad.shape[0], x_pad.device)["dx0"][0])
         return super().backward_raw(x_pad, dq, grads, need_dx)

@@ -29,6 +29,14 @@ without the key, against the one launch in both forms at 32 and, where it may, 6
 `algo.critic_fused_forward=True` and the key off and on.
 
     python tools/bench_lnmlp.py --dx --out profiles/lnmlp_dx_bench.json
+
+`--bwd`: the same protocol for the one-launch gradient chain of the critic's own update (`algo.critic_fused_backward`,
+pqlk_lnmlp_grad_chain, pql_amd/csrc/bwd_ln.hip) at hidden [512, 512, 256], [128, 128] and [1024], B = 8192 and 32768 in the one call:
+on ONE arena and stash, the per-layer `backward_raw(grads)` against the chain call with the weight-gradient GEMMs at 32 and, where it
+may, 64 rows per block and at the library's choice, and the chain call alone; and one DDPG `update_once` at B = `--batch` with
+`algo.critic_fused_forward=True` and the key off and on.
+
+    python tools/bench_lnmlp.py --bwd --out profiles/lnmlp_bwd_bench.json
 """
 import argparse
 import json
@@ -48,6 +56,7 @@ from pql_amd import _lib as L  # noqa: E402
 O, A = 88, 16
 HIDDEN = {"default": [512, 512, 256], "small": [128, 128]}
 DX_HIDDEN = {"default": [512, 512, 256], "wide": [1024]}
+BWD_HIDDEN = {"default": [512, 512, 256], "small": [128, 128], "wide": [1024]}
 
 
 def forward_variants(dev, batch):
@@ -138,6 +147,58 @@ def dx_main(a, dev):
             json.dump(res, f, indent=1)
 
 
+def bwd_variants(dev, batch):
+    from pql_amd.models.layernorm import DoubleQLayerNorm
+    from pql_amd.models.mlp import pad_cols
+    out = {}
+    for name, hidden in BWD_HIDDEN.items():
+        q = DoubleQLayerNorm((O,), A, hidden, fused_forward=True, fused_backward=True).to(dev)
+        x = pad_cols(torch.randn((batch, O + A), device=dev), L.ld(O + A))
+        dq = torch.zeros((2, batch, 32), device=dev)
+        dq[:, :, 0] = torch.randn((2, batch), device=dev)
+        g = torch.zeros(q.total, device=dev)
+        q.forward_raw(x)   # the one stash every variant reads
+
+        def run(r, q=q, x=x, dq=dq, g=g):   # r None: the per-layer path of the same module
+            q.fused_backward_on, q.grad_r = r is not None, r or 0
+            q.backward_raw(x, dq, grads=g)
+            q.fused_backward_on = True
+
+        out[(name, batch, "per_layer")] = lambda run=run: run(None)
+        for r in (0, 1, 2) if max(hidden) <= 512 else (0, 1):
+            out[(name, batch, f"fused_r{r}")] = lambda run=run, r=r: run(r)
+            out[(name, batch, f"chain_alone_r{r}")] = lambda q=q, dq=dq, g=g, r=r: q.fused_grad_chain(dq, g, r)
+    return out
+
+
+def bwd_main(a, dev):
+    fv = {k: fn for batch in (8192, 32768) for k, fn in bwd_variants(dev, batch).items()}
+    agents = {(name, on): make_agent(hidden, True, a.batch, fused_backward=on) for name, hidden in BWD_HIDDEN.items() for on in (False, True)}
+    ftimes, utimes = {k: [] for k in fv}, {k: [] for k in agents}
+    for r in range(a.rounds + 1):     # round 0 warms up
+        for k, fn in fv.items():
+            t = time_launches(fn, a.launches)
+            if r:
+                ftimes[k].append(t)
+        for k, (agent, memory) in agents.items():
+            t = time_updates(agent, memory, a.updates)
+            if r:
+                utimes[k].append(t)
+    res = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, rounds=a.rounds, launches=a.launches, updates=a.updates,
+               obs_dim=O, act_dim=A, backward=[], update_once=[])
+    for (name, batch, what), ts in ftimes.items():
+        res["backward"].append(dict(hidden=BWD_HIDDEN[name], batch=batch, what=what, us_median=round(statistics.median(ts), 2),
+                                    us_min=round(min(ts), 2)))
+    for (name, on), ts in utimes.items():
+        res["update_once"].append(dict(hidden=BWD_HIDDEN[name], batch=a.batch, critic_fused_forward=True, critic_fused_backward=on,
+                                       us_median=round(statistics.median(ts), 1), us_min=round(min(ts), 1)))
+    for rec in (*res["backward"], *res["update_once"]):
+        print(json.dumps(rec), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def make_droq_agent(fused, batch, target_dtype):
     from pql_amd.algo.sac import AgentSAC
     from pql_amd.envs.synthetic import create_task_env
@@ -203,7 +264,7 @@ def time_launches(fn, n):
     return e0.elapsed_time(e1) / n * 1e3   # us per call
 
 
-def make_agent(hidden, fused, batch, target_dtype="float32", fused_dx=False):
+def make_agent(hidden, fused, batch, target_dtype="float32", fused_dx=False, fused_backward=False):
     from pql_amd.algo.ddpg import AgentDDPG
     from pql_amd.envs.synthetic import create_task_env
     from pql_amd.replay.simple_replay import ReplayBuffer
@@ -211,7 +272,8 @@ def make_agent(hidden, fused, batch, target_dtype="float32", fused_dx=False):
     rows = 4 * batch
     cfg = load_cfg(["algo=ddpg_algo", "task.name=AllegroHand", "num_envs=64", f"algo.batch_size={batch}", f"algo.memory_size={rows}",
                     "device=cuda:0", "sim_device=cuda:0", "algo.cri_class=DoubleQLayerNorm", f"algo.hidden_layers={hidden}",
-                    f"algo.critic_fused_forward={fused}", f"algo.critic_target_dtype={target_dtype}", f"algo.critic_fused_dx={fused_dx}"])
+                    f"algo.critic_fused_forward={fused}", f"algo.critic_target_dtype={target_dtype}", f"algo.critic_fused_dx={fused_dx}",
+                    f"algo.critic_fused_backward={fused_backward}"])
     agent = AgentDDPG(create_task_env(cfg), cfg)
     dev = agent.device
     memory = ReplayBuffer(rows, (O,), A, device=dev)
@@ -238,6 +300,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--droq", action="store_true", help="the DroQ critic's one-launch dropout forwards (see the module docstring)")
     ap.add_argument("--dx", action="store_true", help="the one-launch input gradient of the frozen critic (see the module docstring)")
+    ap.add_argument("--bwd", action="store_true", help="the one-launch gradient chain of the critic's update (see the module docstring)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_lnmlp needs a GPU"
     torch.manual_seed(0)
@@ -246,6 +309,8 @@ def main():
         return droq_main(a, dev)
     if a.dx:
         return dx_main(a, dev)
+    if a.bwd:
+        return bwd_main(a, dev)
     fv = forward_variants(dev, a.batch)
     agents = {(name, fused, dt): make_agent(hidden, fused, a.batch, dt) for name, hidden in HIDDEN.items()
               for fused, dt in ((False, "float32"), (True, "float32"), (True, "bfloat16"))}
