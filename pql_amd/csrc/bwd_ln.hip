@@ -27,10 +27,7 @@
 // Summing the nets: net 0's layer-0 epilogue stores its partial to dx, net 1's re-reads the same elements -- the same lanes, the same
 // addresses, so program order suffices --, adds (net 0 + net 1) and, in the tanh form, applies 1 - a^2 before it stores.  No atomics,
 // no second launch.  A row's bits depend on neither m nor its position in the batch; rows at or past m are neither read nor written.
-#include "lnrow.h"
 #include "lnmlp.h"
-
-typedef float f32x16d __attribute__((ext_vector_type(16)));
 
 struct LnDxP {
   const float* arena; const float* stash; const float* dq; const float* tanh_of; float* dx;
@@ -40,8 +37,6 @@ struct LnDxP {
   int dims[PQLK_MAX_LAYERS + 1];
   int n_layers, n_nets, m, ld, ld_dx, ld_a, col0, cols;
 };
-
-extern __shared__ __attribute__((aligned(16))) unsigned char ld_sm[];
 
 // LayerNorm + ELU backward over the block's rows of the image, a wave per row: d (grad of y) -> dz in place.  The body of ln.hip's
 // k_ln_elu_bwd<VPL, true, false>, operation for operation.
@@ -53,7 +48,7 @@ __device__ __forceinline__ void ld_norm(float* img, int ld, int cols, int rows, 
   float ga[VPL];
   ln_load<VPL, true>(gamma, cols, lane, ga);
   const float n = (float)cols;
-  for (int rr = wave; rr < rows; rr += LM_NW) {
+  for (int rr = wave; rr < rows; rr += LS_NW) {
     const long long row = row0 + rr;
     if (row >= m) break;
     const float mu = mean[row], rs = rstd[row];
@@ -87,10 +82,10 @@ template <int R, int NTW, bool L0, bool TANH>
 __device__ __forceinline__ void ld_product(const float* __restrict__ W, int ldw, int NS, float* img, int ld, int t_lo, int T, int wave,
                                            int lane, const LnDxP& p, long long row0, bool first, bool last) {
   const int r = lane & 31, h = lane >> 5;
-  for (int u0 = 0; u0 < T; u0 += LM_NW * NTW) {   // (block-uniform; a hidden layer runs it once)
+  for (int u0 = 0; u0 < T; u0 += LS_NW * NTW) {   // (block-uniform; a hidden layer runs it once)
     const int left = T - u0;
-    const int cnt = wave < left ? min((left - 1 - wave) / LM_NW + 1, NTW) : 0;   // this wave's tiles: u0 + wave, u0 + wave + 8, ...
-    f32x16d acc[NTW][R];
+    const int cnt = wave < left ? min((left - 1 - wave) / LS_NW + 1, NTW) : 0;   // this wave's tiles: u0 + wave, u0 + wave + 8, ...
+    ls_f32x16 acc[NTW][R];
 #pragma unroll
     for (int j = 0; j < NTW; ++j)
 #pragma unroll
@@ -105,7 +100,7 @@ __device__ __forceinline__ void ld_product(const float* __restrict__ W, int ldw,
       for (int j = 0; j < NTW; ++j)
         if (j < cnt)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) wf[j][e] = wp[(size_t)e * ldw + 32 * LM_NW * j];
+          for (int e = 0; e < 4; ++e) wf[j][e] = wp[(size_t)e * ldw + 32 * LS_NW * j];
       for (int s = 0; s < NS; ++s) {
         float wn[NTW][4];
         if (s + 1 < NS) {   // the next group's weights, under this group's MFMAs
@@ -114,7 +109,7 @@ __device__ __forceinline__ void ld_product(const float* __restrict__ W, int ldw,
           for (int j = 0; j < NTW; ++j)
             if (j < cnt)
 #pragma unroll
-              for (int e = 0; e < 4; ++e) wn[j][e] = wq[(size_t)e * ldw + 32 * LM_NW * j];
+              for (int e = 0; e < 4; ++e) wn[j][e] = wq[(size_t)e * ldw + 32 * LS_NW * j];
         }
         float4 af[R];
 #pragma unroll
@@ -142,7 +137,7 @@ __device__ __forceinline__ void ld_product(const float* __restrict__ W, int ldw,
 #pragma unroll
     for (int j = 0; j < NTW; ++j)
       if (j < cnt) {
-        const int t = t_lo + u0 + wave + LM_NW * j;
+        const int t = t_lo + u0 + wave + LS_NW * j;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int c0 = 32 * t + 8 * g + 4 * h;   // accumulator registers 4g .. 4g+3 = input features c0 .. c0+3 of row r
@@ -187,12 +182,12 @@ __device__ __forceinline__ void ld_product(const float* __restrict__ W, int ldw,
 }
 
 template <int R, bool TANH>
-__global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_dx(LnDxP p) {
+__global__ __launch_bounds__(64 * LS_NW) void k_lnmlp_dx(LnDxP p) {
   constexpr int NTW_MAX = R == 2 ? 2 : 4;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int H = p.n_layers - 1, ld = p.ld;
   const long long row0 = (long long)blockIdx.x * (32 * R);
-  float* img = reinterpret_cast<float*>(ld_sm);
+  float* img = reinterpret_cast<float*>(ls_sm);
   for (int net = 0; net < p.n_nets; ++net) {
     const float* prm = p.arena + (long long)net * p.net_stride;
     const float* sb = p.stash + (long long)net * p.stash_net_stride;
@@ -202,7 +197,7 @@ __global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_dx(LnDxP p) {
     {
       const int N = p.dims[H], qpr = N >> 2;
       const float* wout = prm + p.w_off[H];
-      for (int i = tid; i < 32 * R * qpr; i += 64 * LM_NW) {
+      for (int i = tid; i < 32 * R * qpr; i += 64 * LS_NW) {
         const int row = i / qpr, c = (i - row * qpr) << 2;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (row0 + row < p.m) {
@@ -228,7 +223,7 @@ __global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_dx(LnDxP p) {
       const bool first = net == 0, last = net == p.n_nets - 1;
       int t_lo = 0, T = ldw >> 5;
       if (TANH && l == 0) { t_lo = p.col0 >> 5; T = ((p.col0 + p.cols - 1) >> 5) - t_lo + 1; }
-      const int ntw = min((T + LM_NW - 1) / LM_NW, NTW_MAX);   // (block-uniform: the barriers inside are reached by every wave)
+      const int ntw = min((T + LS_NW - 1) / LS_NW, NTW_MAX);   // (block-uniform: the barriers inside are reached by every wave)
 #define LD_PRODUCT(NTW)                                                                                          \
   do {                                                                                                           \
     if (l > 0) ld_product<R, NTW, false, TANH>(W, ldw, N >> 3, img, ld, t_lo, T, wave, lane, p, row0, first, last); \
@@ -262,7 +257,7 @@ extern "C" int pqlk_lnmlp_dx(const PqlMlpDesc* desc, const float* arena, const f
   const int L = d->n_layers;
   int widest = 0;
   for (int l = 1; l < L; ++l) widest = widest > d->dims[l] ? widest : d->dims[l];
-  const bool r2_ok = lm_lds_bytes(d, 2) <= (size_t)LM_LDS_MAX && widest <= LM_MAX_R2_WIDTH;
+  const bool r2_ok = ls_r2_ok(lm_lds_bytes(d, 2), widest);
   PQLK_REQUIRE(r == 0 || r == 1 || (r == 2 && r2_ok), PQLK_E_SHAPE);
   if (tanh_of) {
     PQLK_REQUIRE(col0 >= 0 && cols >= 1 && (int64_t)col0 + cols <= d->dims[0], PQLK_E_RANGE);
@@ -277,7 +272,7 @@ extern "C" int pqlk_lnmlp_dx(const PqlMlpDesc* desc, const float* arena, const f
   LnDxP p = {};
   p.arena = arena; p.stash = stash; p.dq = dq; p.tanh_of = tanh_of; p.dx = dx;
   p.net_stride = d->net_stride; p.stash_net_stride = lm_stash_net_floats(d, m);
-  p.n_layers = L; p.n_nets = d->n_nets; p.m = (int)m; p.ld = lm_image_cols(d) + LM_PAD;
+  p.n_layers = L; p.n_nets = d->n_nets; p.m = (int)m; p.ld = lm_image_cols(d) + LS_PAD;
   p.ld_dx = (int)ld_dx; p.ld_a = (int)ld_a; p.col0 = tanh_of ? col0 : 0; p.cols = tanh_of ? cols : d->dims[0];
   for (int l = 0; l <= L; ++l) p.dims[l] = d->dims[l];
   for (int l = 0; l < L; ++l) {
@@ -290,32 +285,15 @@ extern "C" int pqlk_lnmlp_dx(const PqlMlpDesc* desc, const float* arena, const f
     lm_stash_at(d, m, l, PQLK_LNMLP_MEAN, &p.mean_off[l], &unused);
     lm_stash_at(d, m, l, PQLK_LNMLP_RSTD, &p.rstd_off[l], &unused);
   }
-  static PqlkPerDeviceOnce attr_once;
-  if (int arc = attr_once.run([&] {
-        const void* ks[4] = {reinterpret_cast<const void*>(&k_lnmlp_dx<1, false>), reinterpret_cast<const void*>(&k_lnmlp_dx<1, true>),
-                             reinterpret_cast<const void*>(&k_lnmlp_dx<2, false>), reinterpret_cast<const void*>(&k_lnmlp_dx<2, true>)};
-        for (const void* k : ks) {
-          hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_MAX);
-          if (err != hipSuccess) return -(int)err;
-        }
-        return 0;
-      }))
-    return arc;
   const int rr = r ? r : ld_choose_r(r2_ok, m);
-  dim3 grid((unsigned)((m + 32 * rr - 1) / (32 * rr))), block(64 * LM_NW);
-  hipStream_t s = pqlk_s(stream);
-  if (rr == 2 && tanh_of) hipLaunchKernelGGL((k_lnmlp_dx<2, true>), grid, block, lm_lds_bytes(d, 2), s, p);
-  else if (rr == 2) hipLaunchKernelGGL((k_lnmlp_dx<2, false>), grid, block, lm_lds_bytes(d, 2), s, p);
-  else if (tanh_of) hipLaunchKernelGGL((k_lnmlp_dx<1, true>), grid, block, lm_lds_bytes(d, 1), s, p);
-  else hipLaunchKernelGGL((k_lnmlp_dx<1, false>), grid, block, lm_lds_bytes(d, 1), s, p);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
+  if (tanh_of) return ls_launch<&k_lnmlp_dx<1, true>, &k_lnmlp_dx<2, true>>(rr, m, 1, lm_lds_bytes(d, rr), stream, p);
+  return ls_launch<&k_lnmlp_dx<1, false>, &k_lnmlp_dx<2, false>>(rr, m, 1, lm_lds_bytes(d, rr), stream, p);
 }
 
 // ---- the gradient form: the chain of the critic's own update (pqlk_lnmlp_grad_chain; DoubleQLayerNorm with algo.critic_fused_backward)
 // The same block, the same image, the same norm step and hidden-layer products -- dz of every (net, hidden layer) has k_lnmlp_dx's
 // bits -- with three differences.  No layer-0 product: the update needs no dx, the chain ends behind layer 0's norm step, so the image
-// row is the widest HIDDEN layer + LM_PAD.  dz goes to HBM too, a matrix (m, dims[l + 1]) per net and layer in the workspace: the dy
+// row is the widest HIDDEN layer + LS_PAD.  dz goes to HBM too, a matrix (m, dims[l + 1]) per net and layer in the workspace: the dy
 // operand of the weight-gradient GEMMs, which stay what they are.  And the norm step forms the column sums dbeta_j = sum_r g_rj,
 // dgamma_j = sum_r g_rj xhat_rj from the g and xhat it holds anyway.  Their unit is a 32-row tile, whatever R: wave w adds rows w, w + 8,
 // w + 16, w + 24 of the tile in row order in 2 VPL registers per lane; the 8 waves are then added in wave order through ONE table of
@@ -323,7 +301,7 @@ extern "C" int pqlk_lnmlp_dx(const PqlMlpDesc* desc, const float* arena, const f
 // part[net][layer][tile][{0: dbeta, 1: dgamma}][N], in the map's vector stores).  k_lnmlp_grad_fold, a second launch for every net and
 // layer at once, adds the ceil(m / 32) tile rows as k_ln_fold of ln.hip does.  No float atomics, no ticket, no cross-block wait.
 struct LnGradP {
-  LnDxP c;   // the chain's arguments (dx, tanh_of, ld_dx, ld_a, col0, cols unused; ld = widest hidden layer + LM_PAD)
+  LnDxP c;   // the chain's arguments (dx, tanh_of, ld_dx, ld_a, col0, cols unused; ld = widest hidden layer + LS_PAD)
   float* ws;
   float* grads;
   int64_t dz_off[2][PQLK_MAX_LAYERS], part_off[2][PQLK_MAX_LAYERS];   // in ws, per net and hidden layer
@@ -348,7 +326,7 @@ __device__ __forceinline__ void ld_norm_sums(float* img, int ld, int cols, int t
     float accb[VPL], accg[VPL];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) accb[i] = accg[i] = 0.f;
-    for (int rr = wave; rr < 32; rr += LM_NW) {
+    for (int rr = wave; rr < 32; rr += LS_NW) {
       const long long row = trow + rr;
       if (row >= m) break;
       float* ir = img + (32 * t + rr) * ld;
@@ -377,7 +355,7 @@ __device__ __forceinline__ void ld_norm_sums(float* img, int ld, int cols, int t
     }
     float* pr = part + (trow >> 5) * (2 * cols);
 #pragma unroll
-    for (int w = 0; w < LM_NW; ++w) {
+    for (int w = 0; w < LS_NW; ++w) {
       if (wave == w) {
         if (w > 0) {
           float tb[VPL], tg[VPL];
@@ -386,7 +364,7 @@ __device__ __forceinline__ void ld_norm_sums(float* img, int ld, int cols, int t
 #pragma unroll
           for (int i = 0; i < VPL; ++i) { accb[i] = tb[i] + accb[i]; accg[i] = tg[i] + accg[i]; }
         }
-        float* o = w < LM_NW - 1 ? tab : pr;
+        float* o = w < LS_NW - 1 ? tab : pr;
         ln_store<VPL, true>(o, cols, lane, accb);
         ln_store<VPL, true>(o + cols, cols, lane, accg);
       }
@@ -396,13 +374,13 @@ __device__ __forceinline__ void ld_norm_sums(float* img, int ld, int cols, int t
 }
 
 template <int R>
-__global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_grad(LnGradP q) {
+__global__ __launch_bounds__(64 * LS_NW) void k_lnmlp_grad(LnGradP q) {
   constexpr int NTW_MAX = R == 2 ? 2 : 4;
   const LnDxP& p = q.c;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int H = p.n_layers - 1, ld = p.ld;
   const long long row0 = (long long)blockIdx.x * (32 * R);
-  float* img = reinterpret_cast<float*>(ld_sm);
+  float* img = reinterpret_cast<float*>(ls_sm);
   float* tab = img + q.tab;
   for (int net = 0; net < p.n_nets; ++net) {
     const float* prm = p.arena + (long long)net * p.net_stride;
@@ -412,7 +390,7 @@ __global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_grad(LnGradP q) {
     {
       const int N = p.dims[H], qpr = N >> 2;
       const float* wout = prm + p.w_off[H];
-      for (int i = tid; i < 32 * R * qpr; i += 64 * LM_NW) {
+      for (int i = tid; i < 32 * R * qpr; i += 64 * LS_NW) {
         const int row = i / qpr, c = (i - row * qpr) << 2;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (row0 + row < p.m) {
@@ -437,7 +415,7 @@ __global__ __launch_bounds__(64 * LM_NW) void k_lnmlp_grad(LnGradP q) {
 #undef LD_NORM_SUMS
       if (l == 0) break;   // no layer-0 product: the update needs no dx
       const int T = K >> 5;   // (a hidden layer's width is a multiple of 32)
-      const int ntw = min((T + LM_NW - 1) / LM_NW, NTW_MAX);   // (block-uniform)
+      const int ntw = min((T + LS_NW - 1) / LS_NW, NTW_MAX);   // (block-uniform)
       const float* W = prm + p.w_off[l];
 #define LD_PRODUCT(NTW) ld_product<R, NTW, false, false>(W, K, N >> 3, img, ld, 0, T, wave, lane, p, row0, false, false)
       if (ntw == 1) LD_PRODUCT(1);
@@ -482,8 +460,8 @@ static int lg_widest(const LmLayout* d) {
   for (int l = 1; l < d->n_layers; ++l) w = w > d->dims[l] ? w : d->dims[l];
   return w;
 }
-static size_t lg_lds_bytes(const LmLayout* d, int r) { return ((size_t)32 * r * (lg_widest(d) + LM_PAD) + 2 * lg_widest(d)) * sizeof(float); }
-static bool lg_r2_ok(const LmLayout* d) { return lg_lds_bytes(d, 2) <= (size_t)LM_LDS_MAX && lg_widest(d) <= LM_MAX_R2_WIDTH; }
+static size_t lg_lds_bytes(const LmLayout* d, int r) { return ((size_t)32 * r * (lg_widest(d) + LS_PAD) + 2 * lg_widest(d)) * sizeof(float); }
+static bool lg_r2_ok(const LmLayout* d) { return ls_r2_ok(lg_lds_bytes(d, 2), lg_widest(d)); }
 static int64_t lg_tiles(int64_t m) { return (m + 31) / 32; }
 
 // the workspace: dz (m, dims[l + 1]) of every net and hidden layer, net after net, then the partial rows (tiles, 2, dims[l + 1]) in
@@ -535,7 +513,7 @@ extern "C" int pqlk_lnmlp_grad_chain(const PqlMlpDesc* desc, const float* arena,
   LnDxP& p = q.c;
   p.arena = arena; p.stash = stash; p.dq = dq;
   p.net_stride = d->net_stride; p.stash_net_stride = lm_stash_net_floats(d, m);
-  p.n_layers = L; p.n_nets = d->n_nets; p.m = (int)m; p.ld = lg_widest(d) + LM_PAD;
+  p.n_layers = L; p.n_nets = d->n_nets; p.m = (int)m; p.ld = lg_widest(d) + LS_PAD;
   q.ws = ws; q.grads = grads; q.tiles = (int)lg_tiles(m);
   for (int l = 0; l <= L; ++l) p.dims[l] = d->dims[l];
   for (int l = 0; l < L; ++l) {
@@ -549,24 +527,10 @@ extern "C" int pqlk_lnmlp_grad_chain(const PqlMlpDesc* desc, const float* arena,
     lm_stash_at(d, m, l, PQLK_LNMLP_RSTD, &p.rstd_off[l], &unused);
     for (int n = 0; n < d->n_nets; ++n) lg_at(d, m, n, l, &q.dz_off[n][l], &q.part_off[n][l]);
   }
-  static PqlkPerDeviceOnce attr_once;
-  if (int arc = attr_once.run([&] {
-        const void* ks[2] = {reinterpret_cast<const void*>(&k_lnmlp_grad<1>), reinterpret_cast<const void*>(&k_lnmlp_grad<2>)};
-        for (const void* k : ks) {
-          hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_MAX);
-          if (err != hipSuccess) return -(int)err;
-        }
-        return 0;
-      }))
-    return arc;
   const int rr = r ? r : ld_choose_r(r2_ok, m);
   q.tab = 32 * rr * p.ld;
-  dim3 grid((unsigned)((m + 32 * rr - 1) / (32 * rr))), block(64 * LM_NW);
-  hipStream_t s = pqlk_s(stream);
-  if (rr == 2) hipLaunchKernelGGL((k_lnmlp_grad<2>), grid, block, lg_lds_bytes(d, 2), s, q);
-  else hipLaunchKernelGGL((k_lnmlp_grad<1>), grid, block, lg_lds_bytes(d, 1), s, q);
-  PQLK_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_lnmlp_grad_fold, dim3((unsigned)((lg_widest(d) + 15) / 16), 2, (unsigned)(d->n_nets * (L - 1))), dim3(256), 0, s, q);
+  if (int rc = ls_launch<&k_lnmlp_grad<1>, &k_lnmlp_grad<2>>(rr, m, 1, lg_lds_bytes(d, rr), stream, q)) return rc;
+  hipLaunchKernelGGL(k_lnmlp_grad_fold, dim3((unsigned)((lg_widest(d) + 15) / 16), 2, (unsigned)(d->n_nets * (L - 1))), dim3(256), 0, pqlk_s(stream), q);
   PQLK_LAUNCH_CHECK();
   return PQLK_OK;
 }

@@ -13,7 +13,7 @@
 // batch row sits on the lane and four consecutive output features in four consecutive accumulator registers: the epilogue
 // packs them to 8 bytes of bf16 and writes them with one ds_write_b64 into the [row][feature] image the next layer reads
 // back with ds_read_b128 -- both operands use the same "row r, k = 8 h + j" lane map (lane = 32 h + r).
-#include "pqlk_common.h"
+#include "bf16.h"
 
 constexpr int BF_NW = 8;           // waves per block
 constexpr int BF_LDS_MAX = 160 * 1024;
@@ -22,14 +22,6 @@ constexpr int BF_PAD = 8;          // bf16 elements of row padding in LDS (16 B:
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16b __attribute__((ext_vector_type(16)));
 
-// fp32 -> bf16, round to nearest even, ties included; NaN stays a (quiet) NaN, overflow goes to +-inf
-__device__ __forceinline__ unsigned bf16_rne(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-__device__ __forceinline__ unsigned bf16_pack2(float lo, float hi) { return bf16_rne(lo) | (bf16_rne(hi) << 16); }
 __device__ __forceinline__ float bf16_elu(float x) { return x > 0.f ? x : __expf(x) - 1.f; }
 
 struct Bf16P {

@@ -9,11 +9,9 @@
 // width W, so the vector width of the row routine (VPL) and the tiles a wave holds (NTW) are template arguments of the whole stack:
 // the kernel branches once, on W, and what follows is straight code for one geometry.
 //
-// Linear: v_mfma_f32_32x32x2_f32, the WEIGHT tile as A and the activation tile from LDS as B (lane = 32 h + r: batch row r, four
-// consecutive features in four consecutive accumulator registers).  Wave w takes the feature tiles w, w + 8, ..; at most 64
-// accumulators.  Fragments and the k order inside an 8-wide group (0, 4, 1, 5, 2, 6, 3, 7) are pqlk_lnmlp_forward's, so z's bits are
-// defined by the header.  The k loop is software-pipelined: the 16-byte weight (HBM / L2) and activation (LDS) fragments of step s + 1
-// are fetched ahead of the MFMAs of step s; no sum changes its order by that.
+// Linear: the fp32 steps of lnstack.h -- the geometry, the fragments and the k order inside an 8-wide group are pqlk_lnmlp_forward's,
+// one text for both, so z's bits are defined by the header.  The k loop here is software-pipelined: the 16-byte weight (HBM / L2) and
+// activation (LDS) fragments of step s + 1 are fetched ahead of the MFMAs of step s; no sum changes its order by that.
 //
 // Skip in registers: in the epilogue row rr of the block belongs to wave rr mod 8 in EVERY layer, so the wave that normalises a row
 // also normalised it two layers earlier.  The epilogue runs its 4 R rows as a fully unrolled loop (a row >= m is predicated off) and
@@ -21,20 +19,13 @@
 // them alone, a closing one reads them as the skip.  The residual stream never touches LDS or HBM; the image only ever holds the
 // current layer's input or output.
 //
-// Output layer: rides on the last epilogue (the stem's for K = 0, else a closing one): y in registers x Wo in register order, the row
-// sum's butterfly, + bo.  Without STASH nothing but Q leaves the block; with it z, y (16-byte runs), mean, rstd of every hidden layer
+// Output layer: rides on the last epilogue (the stem's for K = 0, else a closing one) through lnstack.h's ls_q_row.  Without STASH nothing but Q leaves the block; with it z, y (16-byte runs), mean, rstd of every hidden layer
 // go where backward_raw reads them.  Plain vector stores, no atomics, no scratch; a row's bits depend on neither m, its position in
 // the batch, nor STASH.
-#include "lnrow.h"
+#include "lnstack.h"
 
-constexpr int BR_NW = 8;                 // waves per block
-constexpr int BR_LDS_MAX = 160 * 1024;
-constexpr int BR_PAD = 4;                // floats of row padding in LDS (16 B: consecutive rows start 4 banks apart)
-constexpr int BR_MAX_R2_WIDTH = 512;     // widest stack at R = 2: 2 tiles x 2 row tiles x 16 = 64 accumulator registers
 constexpr int BR_MAX_WIDTH = 1024;
 constexpr int BR_MAX_BLOCKS = 16;
-
-typedef float f32x16b __attribute__((ext_vector_type(16)));
 
 struct BroP {
   const float* X; const float* arena; float* stash; float* q;
@@ -43,81 +34,32 @@ struct BroP {
   float eps;
 };
 
-extern __shared__ __attribute__((aligned(16))) unsigned char br_sm[];
-
-// the fragments of k step s: the weights of this wave's tiles (HBM / L2) and the activations of the block's row tiles (LDS)
-template <int R, int NTW>
-__device__ __forceinline__ void br_fetch(const float* __restrict__ wp, int ldw, const float* ap, int ld, int s, int cnt,
-                                         float4 (&wf)[NTW], float4 (&af)[R]) {
-#pragma unroll
-  for (int j = 0; j < NTW; ++j)
-    if (j < cnt) wf[j] = *reinterpret_cast<const float4*>(wp + (long long)j * (32 * BR_NW) * ldw + 8 * s);
-#pragma unroll
-  for (int i = 0; i < R; ++i) af[i] = *reinterpret_cast<const float4*>(ap + 32 * i * ld + 8 * s);
-}
-
-// the four MFMAs of one k step per (tile, row tile): MFMA e takes columns 8 s + e (h = 0) and 8 s + 4 + e (h = 1)
-template <int R, int NTW>
-__device__ __forceinline__ void br_mfma(f32x16b (&acc)[NTW][R], int cnt, const float4 (&wf)[NTW], const float4 (&af)[R]) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-#pragma unroll
-    for (int j = 0; j < NTW; ++j)
-      if (j < cnt) {
-        const float wv = e == 0 ? wf[j].x : e == 1 ? wf[j].y : e == 2 ? wf[j].z : wf[j].w;
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-          const float av = e == 0 ? af[i].x : e == 1 ? af[i].y : e == 2 ? af[i].z : af[i].w;
-          acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, av, acc[j][i], 0, 0, 0);
-        }
-      }
-}
-
 // z = W a + b of one hidden layer for the block's 32 R rows: img holds a (8 KS columns, zeros past the layer's input width) and is
 // overwritten with z.  cnt: this wave's tiles (wave, wave + 8, ..; <= NTW).  Ends behind the barrier after which z is complete.
+// The k loop is software-pipelined: step s is in flight while step s - 1 multiplies.
 template <int R, int NTW>
 __device__ __forceinline__ void br_linear(const float* __restrict__ W, int ldw, int KS, const float* __restrict__ bias, float* img, int ld,
                                           int cnt, int wave, int lane) {
   const int r = lane & 31, h = lane >> 5;
-  f32x16b acc[NTW][R];
-#pragma unroll
-  for (int j = 0; j < NTW; ++j)
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[j][i][e] = 0.f;
+  ls_f32x16 acc[NTW][R];
+  ls_zero<R, NTW>(acc);
   if (cnt > 0) {
     const float* wp = W + (long long)(32 * wave + r) * ldw + 4 * h;
     const float* ap = img + r * ld + 4 * h;
     float4 wf[NTW], af[R], wn[NTW], an[R];
-    br_fetch<R, NTW>(wp, ldw, ap, ld, 0, cnt, wf, af);
-    for (int s = 1; s < KS; ++s) {   // step s is in flight while step s - 1 multiplies
-      br_fetch<R, NTW>(wp, ldw, ap, ld, s, cnt, wn, an);
-      br_mfma<R, NTW>(acc, cnt, wf, af);
+    ls_fetch<R, NTW>(wp, ldw, ap, ld, 0, cnt, wf, af);
+    for (int s = 1; s < KS; ++s) {
+      ls_fetch<R, NTW>(wp, ldw, ap, ld, s, cnt, wn, an);
+      ls_mfma<R, NTW>(acc, cnt, wf, af);
 #pragma unroll
       for (int j = 0; j < NTW; ++j)
         if (j < cnt) wf[j] = wn[j];
 #pragma unroll
       for (int i = 0; i < R; ++i) af[i] = an[i];
     }
-    br_mfma<R, NTW>(acc, cnt, wf, af);
+    ls_mfma<R, NTW>(acc, cnt, wf, af);
   }
-  __syncthreads();   // nobody reads the layer's input any more
-#pragma unroll
-  for (int j = 0; j < NTW; ++j)
-    if (j < cnt) {
-      const int t = wave + BR_NW * j;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n0 = 32 * t + 8 * g + 4 * h;   // accumulator registers 4g .. 4g+3 = features n0 .. n0+3 of row r
-        const float4 b4 = *reinterpret_cast<const float4*>(bias + n0);
-#pragma unroll
-        for (int i = 0; i < R; ++i)
-          *reinterpret_cast<float4*>(img + (32 * i + r) * ld + n0) =
-              make_float4(acc[j][i][4 * g] + b4.x, acc[j][i][4 * g + 1] + b4.y, acc[j][i][4 * g + 2] + b4.z, acc[j][i][4 * g + 3] + b4.w);
-      }
-    }
-  __syncthreads();   // z is complete
+  ls_write_z<R, NTW>(acc, cnt, bias, img, ld, wave, lane);
 }
 
 enum { BR_STEM = 0, BR_OPEN = 1, BR_CLOSE = 2 };
@@ -146,7 +88,7 @@ __device__ __forceinline__ void br_norm(float* img, int ld, int cols, long long 
   }
 #pragma unroll
   for (int i = 0; i < 4 * R; ++i) {
-    const int rr = wave + BR_NW * i;
+    const int rr = wave + LS_NW * i;
     const long long row = row0 + rr;
     if (row < m) {
       float v[VPL];
@@ -170,12 +112,8 @@ __device__ __forceinline__ void br_norm(float* img, int ld, int cols, long long 
       }
       if (!wout) {
         ln_store<VPL, true>(img + rr * ld, cols, lane, v);
-      } else {   // Q = sum_j y_j w_j + b: per-lane partials in register order (slots past cols hold 0), the butterfly, then the bias
-        float dot = 0.f;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j) dot += v[j] * wo[j];
-        const float qv = wave_sum(dot) + bout;
-        if (lane < 8) *reinterpret_cast<float4*>(qout + row * 32 + 4 * lane) = make_float4(lane == 0 ? qv : 0.f, 0.f, 0.f, 0.f);
+      } else {
+        ls_q_row<VPL>(v, wo, bout, qout + row * 32, lane);
       }
     }
   }
@@ -186,7 +124,7 @@ template <int R, bool STASH, int VPL, int NTW>
 __device__ __forceinline__ void br_stack(const BroP& p, float* img, const float* __restrict__ prm, float* __restrict__ sb,
                                          float* __restrict__ q, long long row0, int wave, int lane) {
   const int W = p.W, K = p.K, ld = p.ld, NT = W >> 5, nh = 2 * K + 1;
-  const int cnt = wave < NT ? (NT - 1 - wave) / BR_NW + 1 : 0;
+  const int cnt = ls_tiles(NT, wave);
   const long long blk = (long long)W * W + 3 * W;                // a block layer: [W | b | gamma | beta]
   const float* lay = prm;                                         // the current layer's start
   float skip[4 * R][VPL];
@@ -218,26 +156,12 @@ __device__ __forceinline__ void br_stack(const BroP& p, float* img, const float*
 }
 
 template <int R, bool STASH>
-__global__ __launch_bounds__(64 * BR_NW) void k_bro_fwd(BroP p) {
+__global__ __launch_bounds__(64 * LS_NW) void k_bro_fwd(BroP p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int net = blockIdx.y, ld = p.ld;
   const long long row0 = (long long)blockIdx.x * (32 * R);
-  float* img = reinterpret_cast<float*>(br_sm);
-  // stage the input tile; rows past m and columns past in_dim (up to the next multiple of 8) become zero
-  {
-    const int K0 = p.in_dim, qpr = ((K0 + 7) & ~7) >> 2;
-    for (int i = tid; i < 32 * R * qpr; i += 64 * BR_NW) {
-      const int row = i / qpr, c = (i - row * qpr) << 2;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row0 + row < p.m && c < K0) {   // c + 3 < ldx: ldx >= roundup(K0, 32)
-        v = *reinterpret_cast<const float4*>(p.X + (row0 + row) * p.ldx + c);
-        if (c + 1 >= K0) v.y = 0.f;
-        if (c + 2 >= K0) v.z = 0.f;
-        if (c + 3 >= K0) v.w = 0.f;
-      }
-      *reinterpret_cast<float4*>(img + row * ld + c) = v;
-    }
-  }
+  float* img = reinterpret_cast<float*>(ls_sm);
+  ls_stage<32 * R>(p, p.in_dim, img, ld, row0, tid);
   __syncthreads();
   const float* prm = p.arena + (long long)net * p.net_stride;
   float* sb = STASH ? p.stash + (long long)net * p.stash_net_stride : nullptr;
@@ -257,7 +181,7 @@ struct BroLayout {
 };
 
 static int br_image_cols(const BroLayout* d) { return d->ldin > d->W ? d->ldin : d->W; }
-static size_t br_lds_bytes(const BroLayout* d, int r) { return (size_t)32 * r * (br_image_cols(d) + BR_PAD) * sizeof(float); }
+static size_t br_lds_bytes(const BroLayout* d, int r) { return ls_lds_bytes(br_image_cols(d), r); }
 
 static bool br_shape_ok(int32_t width, int32_t blocks, int32_t n_nets) {
   return width > 0 && width % 32 == 0 && width <= BR_MAX_WIDTH && blocks >= 0 && blocks <= BR_MAX_BLOCKS && (n_nets == 1 || n_nets == 2);
@@ -271,16 +195,14 @@ static bool br_layout(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_n
   d.stem = (int64_t)width * d.ldin + 3 * width;
   d.blk = (int64_t)width * width + 3 * width;
   d.net_stride = d.stem + 2 * blocks * d.blk + width + pqlk_ld(1);
-  if (br_lds_bytes(&d, 1) > (size_t)BR_LDS_MAX) return false;
+  if (br_lds_bytes(&d, 1) > (size_t)LS_LDS_MAX) return false;
   *out = d;
   return true;
 }
 
-static int64_t br_round4(int64_t x) { return (x + 3) & ~(int64_t)3; }
-
 // a net's stash: z, y of every hidden layer, (m, W) each, then mean, rstd of every hidden layer, m floats rounded up to 4
 static int64_t br_stash_net_floats(int32_t width, int32_t blocks, int64_t m) {
-  return (int64_t)(2 * blocks + 1) * (2 * m * width + 2 * br_round4(m));
+  return (int64_t)(2 * blocks + 1) * (2 * m * width + 2 * ls_round4(m));
 }
 
 extern "C" int pqlk_bro_ok(int32_t in_dim, int32_t width, int32_t blocks, int32_t n_nets) {
@@ -322,7 +244,7 @@ extern "C" int pqlk_bro_stash_offset(int32_t width, int32_t blocks, int32_t n_ne
     *off = base + (2 * (int64_t)layer + (which == PQLK_LNMLP_Y ? 1 : 0)) * m * width;
     *ld = width;
   } else {
-    *off = base + 2 * (int64_t)nh * m * width + (2 * (int64_t)layer + (which == PQLK_LNMLP_RSTD ? 1 : 0)) * br_round4(m);
+    *off = base + 2 * (int64_t)nh * m * width + (2 * (int64_t)layer + (which == PQLK_LNMLP_RSTD ? 1 : 0)) * ls_round4(m);
     *ld = 1;
   }
   return PQLK_OK;
@@ -335,31 +257,13 @@ extern "C" int pqlk_bro_forward(int32_t in_dim, int32_t width, int32_t blocks, i
   PQLK_REQUIRE(br_layout(in_dim, width, blocks, n_nets, &lay), PQLK_E_SHAPE);
   const BroLayout* d = &lay;
   PQLK_REQUIRE(m > 0 && m < (1LL << 30), PQLK_E_SHAPE);
-  PQLK_REQUIRE(ldx % 32 == 0 && ldx >= d->ldin, PQLK_E_ALIGN);
-  PQLK_REQUIRE(pqlk_aligned16(arena) && pqlk_aligned16(x) && pqlk_aligned16(stash) && pqlk_aligned16(q_out), PQLK_E_ALIGN);
+  if (int rc = ls_forward_args(ldx, in_dim, arena, x, stash, q_out)) return rc;
   BroP p = {};
   p.X = x; p.arena = arena; p.stash = stash; p.q = q_out;
-  p.net_stride = d->net_stride; p.stash_net_stride = br_stash_net_floats(width, blocks, m); p.m4 = br_round4(m);
-  p.in_dim = in_dim; p.ldin = d->ldin; p.W = width; p.K = blocks; p.m = (int)m; p.ldx = (int)ldx; p.ld = br_image_cols(d) + BR_PAD;
+  p.net_stride = d->net_stride; p.stash_net_stride = br_stash_net_floats(width, blocks, m); p.m4 = ls_round4(m);
+  p.in_dim = in_dim; p.ldin = d->ldin; p.W = width; p.K = blocks; p.m = (int)m; p.ldx = (int)ldx; p.ld = br_image_cols(d) + LS_PAD;
   p.eps = eps;
-  static PqlkPerDeviceOnce attr_once;
-  if (int arc = attr_once.run([&] {
-        const void* ks[4] = {reinterpret_cast<const void*>(&k_bro_fwd<1, false>), reinterpret_cast<const void*>(&k_bro_fwd<1, true>),
-                             reinterpret_cast<const void*>(&k_bro_fwd<2, false>), reinterpret_cast<const void*>(&k_bro_fwd<2, true>)};
-        for (const void* k : ks) {
-          hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, BR_LDS_MAX);
-          if (err != hipSuccess) return -(int)err;
-        }
-        return 0;
-      }))
-    return arc;
-  const int r = br_lds_bytes(d, 2) <= (size_t)BR_LDS_MAX && width <= BR_MAX_R2_WIDTH ? 2 : 1;
-  dim3 grid((unsigned)((m + 32 * r - 1) / (32 * r)), (unsigned)n_nets), block(64 * BR_NW);
-  hipStream_t s = pqlk_s(stream);
-  if (r == 2 && stash) hipLaunchKernelGGL((k_bro_fwd<2, true>), grid, block, br_lds_bytes(d, 2), s, p);
-  else if (r == 2) hipLaunchKernelGGL((k_bro_fwd<2, false>), grid, block, br_lds_bytes(d, 2), s, p);
-  else if (stash) hipLaunchKernelGGL((k_bro_fwd<1, true>), grid, block, br_lds_bytes(d, 1), s, p);
-  else hipLaunchKernelGGL((k_bro_fwd<1, false>), grid, block, br_lds_bytes(d, 1), s, p);
-  PQLK_LAUNCH_CHECK();
-  return PQLK_OK;
+  const int r = ls_r2_ok(br_lds_bytes(d, 2), width) ? 2 : 1;
+  if (stash) return ls_launch<&k_bro_fwd<1, true>, &k_bro_fwd<2, true>>(r, m, n_nets, br_lds_bytes(d, r), stream, p);
+  return ls_launch<&k_bro_fwd<1, false>, &k_bro_fwd<2, false>>(r, m, n_nets, br_lds_bytes(d, r), stream, p);
 }

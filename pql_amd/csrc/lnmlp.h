@@ -1,12 +1,8 @@
 // What the whole-stack launches of the LayerNorm twin critic share on the host: the forward of fwd_ln.hip and the input-gradient pass
 // of bwd_ln.hip read the same arena, the same stash slab and the same LDS image, so the layout of all three is stated once, here.
+// (The block geometry and what the residual critic's launches share too: lnstack.h.)
 #pragma once
-#include "pqlk_common.h"
-
-constexpr int LM_NW = 8;                 // waves per block
-constexpr int LM_LDS_MAX = 160 * 1024;
-constexpr int LM_PAD = 4;                // floats of row padding in LDS (16 B: consecutive rows start 4 banks apart)
-constexpr int LM_MAX_R2_WIDTH = 512;     // widest hidden layer at R = 2: 2 tiles x 2 row tiles x 16 = 64 accumulator registers
+#include "lnstack.h"
 
 // the arena law of the normalised twin critics (include/pqlk.h): per net and layer [W | b], then [gamma | beta] behind a hidden one
 struct LmLayout {
@@ -20,7 +16,7 @@ static int lm_image_cols(const LmLayout* d) {
   for (int l = 1; l < d->n_layers; ++l) w = w > d->dims[l] ? w : d->dims[l];
   return w;
 }
-static size_t lm_lds_bytes(const LmLayout* d, int r) { return (size_t)32 * r * (lm_image_cols(d) + LM_PAD) * sizeof(float); }
+static size_t lm_lds_bytes(const LmLayout* d, int r) { return ls_lds_bytes(lm_image_cols(d), r); }
 
 // the layout of an eligible descriptor -> *out; false: not eligible
 static bool lm_layout(const PqlMlpDesc* m, LmLayout* out) {
@@ -40,17 +36,15 @@ static bool lm_layout(const PqlMlpDesc* m, LmLayout* out) {
     }
   }
   d.net_stride = o;
-  if (lm_lds_bytes(&d, 1) > (size_t)LM_LDS_MAX) return false;   // (bounds the input width: ld(dims[0]) <= 1248)
+  if (lm_lds_bytes(&d, 1) > (size_t)LS_LDS_MAX) return false;   // (bounds the input width: ld(dims[0]) <= 1248)
   *out = d;
   return true;
 }
 
-static int64_t lm_round4(int64_t x) { return (x + 3) & ~(int64_t)3; }
-
 // a net's stash: z, y of every hidden layer, (m, dims[l + 1]) each, then mean, rstd of every hidden layer, m floats rounded up to 4
 static int64_t lm_stash_net_floats(const LmLayout* d, int64_t m) {
   int64_t o = 0;
-  for (int l = 1; l < d->n_layers; ++l) o += 2 * m * d->dims[l] + 2 * lm_round4(m);
+  for (int l = 1; l < d->n_layers; ++l) o += 2 * m * d->dims[l] + 2 * ls_round4(m);
   return o;
 }
 
@@ -63,7 +57,7 @@ static void lm_stash_at(const LmLayout* d, int64_t m, int layer, int which, int6
     *ld = d->dims[layer + 1];
   } else {
     for (int l = 1; l < d->n_layers; ++l) o += 2 * m * d->dims[l];
-    *off = o + (2 * layer + (which == PQLK_LNMLP_RSTD ? 1 : 0)) * lm_round4(m);
+    *off = o + (2 * layer + (which == PQLK_LNMLP_RSTD ? 1 : 0)) * ls_round4(m);
     *ld = 1;
   }
 }
